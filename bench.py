@@ -9,6 +9,11 @@ the per-GPU top-k + merge on every rank (N > 1; --all-to-all: each rank merges a
 
 Workload at N = 1 = BASELINE.json config C3 (10M docs, 5-term BM25 disjunction, top-1000); for
 N > 1 the same index is sharded by contiguous docid range over the ranks (strong scaling).
+
+A plain run sets up, warms up, times the steps and prints the line; --full adds the measurements and checks that take runs of
+their own (CPU baselines, the exhaustive route, the C2 / C5 / C4 legs, closed loops, the C4 line's fp64 verification and
+two-caller run).  --dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy (docs, scores,
+n_hits, total_hits, relation_gte; float64 / float32), from inputs that are the same in every run with the same arguments.
 """
 from __future__ import annotations
 
@@ -128,6 +133,11 @@ def parse_args():
                          "out to the ranks and each rank is filled up from the big segments' docid space -- every rank holds 2-3 leaves "
                          "instead of the last rank holding all the small ones")
     ap.add_argument("--debug-k", type=int, default=0, help="debug: numHits override (what a shard costs at a smaller k)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baselines, the exhaustive route, the C2 / C5 / C4 legs, the closed loops, the C4 "
+                         "line's fp64 verification and two-caller run (a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps: what the timed path returned in its last step, as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--torch-collective", action="store_true",
                     help="N>1: exchange with torch.distributed's all-gather instead of the library's own RCCL stage "
                          "(nrtgpu_dist_allgather_merge, the default; falls back to torch by itself if RCCL cannot be bound)")
@@ -192,6 +202,53 @@ def stdout_to_stderr(fn):
         libc.fflush(None)
         os.dup2(saved, 1)
         os.close(saved)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def topdocs_arrays(docs, scores, n_hits, total_hits, relation_gte):
+    """What a caller of the batch receives, per query: docids and scores of its hits (rows padded past n_hits with docid -1 and
+    score 0), the hit count, totalHits and its relation -- as float64 / float32 arrays (docids and counts are exact in float64)."""
+    import numpy as np
+
+    n_hits = np.asarray(n_hits, dtype=np.int64)
+    width = docs.shape[1]
+    live = np.arange(width)[None, :] < n_hits[:, None]
+    return {"docs": np.where(live, docs, -1).astype(np.float64),
+            "scores": np.where(live, scores, 0.0).astype(np.float32),
+            "n_hits": n_hits.astype(np.float64),
+            "total_hits": np.asarray(total_hits, dtype=np.float64),
+            "relation_gte": np.asarray(relation_gte, dtype=np.float32)}
+
+
+def topdocs_list_arrays(tds, k):
+    """topdocs_arrays of a list of api.TopDocs (None: a query this rank does not deliver -- no hits, totalHits -1)."""
+    import numpy as np
+
+    n = len(tds)
+    docs, scores = np.full((n, k), -1, dtype=np.int64), np.zeros((n, k), dtype=np.float32)
+    n_hits, total, gte = np.zeros(n, dtype=np.int64), np.full(n, -1, dtype=np.int64), np.zeros(n, dtype=bool)
+    for qi, td in enumerate(tds):
+        if td is None:
+            continue
+        m = len(td.docs)
+        docs[qi, :m], scores[qi, :m], n_hits[qi], total[qi], gte[qi] = td.docs, td.scores, m, td.total_hits, td.relation_gte
+    return topdocs_arrays(docs, scores, n_hits, total, gte)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy (float32 / float64 only, DUMP_LIMIT_BYTES in all)."""
+    import numpy as np
+
+    total = 0
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        total += a.nbytes
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def cpu_baseline(corpus, query_ranks, k, n_queries):
@@ -435,7 +492,7 @@ def run_c4(args, emit=True):
     # is compared with below ("verify").  One GPU only (a rank of a job sees its rows only).
     qrng = np.random.Generator(np.random.PCG64(778))
     panels = [qrng.standard_normal((Q, dim), dtype=np.float32) for _ in range(4)]
-    verify_q = sorted(set([0, Q // 2, Q - 1])) if (world == 1 and shard_world == 1 and not args.no_verify) else []
+    verify_q = sorted(set([0, Q // 2, Q - 1])) if (world == 1 and shard_world == 1 and not args.no_verify and args.full) else []
     last_panel = panels[(args.warmup + args.steps - 1) % len(panels)]
     vq64 = torch.from_numpy(last_panel[verify_q].astype(np.float64)).cuda() if verify_q else None
     v_best = None    # (scores fp64 [nq, <=2k], docs int64)
@@ -460,7 +517,7 @@ def run_c4(args, emit=True):
         g.add_vectors(0, host)
         g.seal()
         leaves.append(g)
-        if first_seg is None:
+        if first_seg is None and args.full:   # (the CPU port's sample)
             first_seg = host[: min(rows, 1_000_000)].copy()
         del host
         base += rows
@@ -520,6 +577,8 @@ def run_c4(args, emit=True):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     st = ctx.stats()
+    if args.dump_outputs and rank == 0 and emit:
+        dump_outputs(args.dump_outputs, topdocs_list_arrays(last, k))
     # Two callers taking the steps in turn ("staging overlapped with the previous panel"): a caller's
     # staging, small selection / rescoring kernels, result copy and unpacking can overlap the other caller's stream of the rows.
     # Measured (round 6, 10 M x 768, 64 queries per pass; profiles/r06_c2_threads_c4_two_callers.log): 3.26 - 3.31 ms per pass call
@@ -531,7 +590,7 @@ def run_c4(args, emit=True):
     #  thread, api._topdocs_outputs: one caller 3.16 - 3.22 ms per pass call at 64 queries, profiles/r06_c4_wrapper.log.)
     # (Kernel times come from the one-caller loop above: with overlapping launches a launch's HIP-event time is no longer its own.)
     two = None
-    if world == 1 and n_thr == 1 and args.steps >= 4 and not args.c4_callers:
+    if world == 1 and n_thr == 1 and args.steps >= 4 and not args.c4_callers and args.full:
         import threading
         gc.disable()
         t2 = time.perf_counter()
@@ -574,7 +633,7 @@ def run_c4(args, emit=True):
                                         *(knn_traffic_record(build.build_id(_lib.LIB_PATH), q_per_panel) if (sketched and world == 1 and shard_world == 1) else (None, None))),
     }
     out["roofline"]["build_id"] = build.build_id(_lib.LIB_PATH)
-    if rank == 0 and world == 1 and shard_world == 1 and args.closed_loop and emit:
+    if rank == 0 and world == 1 and shard_world == 1 and args.closed_loop and emit and args.full:
         # queries/s AND latency under concurrent clients: C native caller threads, ONE query per call through
         # nrtgpu_knn_exact_coalesced -- the library merges them into panels of up to 64 that share a pass over the rows
         import ctypes as C
@@ -611,7 +670,7 @@ def run_c4(args, emit=True):
                     ok = ok and int(gd[r]) in score_of and abs(score_of[int(gd[r])] - ref_s[r]) <= 2e-5 * ref_s[r] + 2e-6
         out["verify"] = {"agrees_with_fp64": bool(ok), "queries": len(verify_q), "rows": n, "docids_off_rank_among_near_ties": off_rank,
                          "what": "device top-100 vs fp64 cosine score map over every row (torch, on the device), last timed panel"}
-    if not args.no_cpu_baseline and rank == 0 and world == 1:
+    if not args.no_cpu_baseline and rank == 0 and world == 1 and args.full:
         # the C restatement of ExactVectorQuery + collector on the host cores, bounded sample: first rows of segment 0
         from oracle import oracle
 
@@ -1233,6 +1292,7 @@ def main():
                         shard_spec_stat["queries"] += mq_e
                         shard_spec_stat["failed"] += len(bad)
                         batches[batch_index(first + i)].note_shard_speculation(mq_e, len(bad))
+                        last["rerun"] = None
                         if len(bad):
                             # the failed queries alone: run again, their W_e lists stood in for as at the setup, merged on their own
                             tk, tc, th_ = run_again(bi_, bad)
@@ -1241,7 +1301,9 @@ def main():
                             rc = tc.unsqueeze(0).expand(W_e, nb_).contiguous()
                             rh = th_.unsqueeze(0).expand(W_e, nb_).contiguous()
                             torch.cuda.current_stream().synchronize()
-                            api.PreparedMerge(ctx, W_e, nb_, k_stride, [w.k] * nb_, [api.TOTAL_HITS_THRESHOLD] * nb_).run(rk.data_ptr(), rc.data_ptr(), rh.data_ptr())
+                            pm_ = api.PreparedMerge(ctx, W_e, nb_, k_stride, [w.k] * nb_, [api.TOTAL_HITS_THRESHOLD] * nb_)
+                            pm_.run(rk.data_ptr(), rc.data_ptr(), rh.data_ptr())
+                            last["rerun"] = (bad, pm_)
                     if record:
                         lat.append(time.perf_counter() - t_start[i])
                         stage["exchange_s"] += te1 - te0
@@ -1257,11 +1319,12 @@ def main():
                     shard_spec_stat["queries"] += B
                     shard_spec_stat["failed"] += len(bad)
                     pb_.note_shard_speculation(B, len(bad))
+                    last["rerun"] = None   # (bad queries, their answers): what the caller receives in place of the merged lists' rows
                     if len(bad):
                         shard_spec_stat["reran_batches"] += 1
                         q0 = batch_index(first + i) * B
-                        last["rerun"] = searcher.dist_search_batch([queries[q0 + int(j)] for j in bad], [mgr] * len(bad),
-                                                                   mode=api.EXCHANGE_ALLGATHER | api.EXCHANGE_NO_SPECULATION)
+                        last["rerun"] = (bad, searcher.dist_search_batch([queries[q0 + int(j)] for j in bad], [mgr] * len(bad),
+                                                                         mode=api.EXCHANGE_ALLGATHER | api.EXCHANGE_NO_SPECULATION))
                     if record:
                         lat.append(time.perf_counter() - t_start[i])
                         stage["exchange_s"] += time.perf_counter() - te0
@@ -1349,6 +1412,20 @@ def main():
         elapsed = float(t.item())
 
     st = ctx.stats()
+    if args.dump_outputs and rank == 0:
+        # the last timed step's answers: one GPU -- the batch that step ran; N > 1 -- this rank's merged lists of its last step
+        # (the queries whose shard-level guess failed: the answers of their second run)
+        if use_dist:
+            tds = [merger.topdocs(qi) if merger.owned(qi) else None for qi in range(merger.n)]
+            if last.get("rerun") is not None:
+                bad, res = last["rerun"]
+                for j, qi in enumerate(bad):
+                    if tds[int(qi)] is not None:
+                        tds[int(qi)] = res.topdocs(j) if isinstance(res, api.PreparedMerge) else res[j]
+        else:
+            pb = batches[batch_index(args.warmup + args.steps - 1)]
+            tds = [pb.topdocs(qi) for qi in range(pb.n)]
+        dump_outputs(args.dump_outputs, topdocs_list_arrays(tds, w.k))
     n_q = args.steps * B * R   # (every doc-shard group ran `steps` batches of its own)
     qps = n_q / elapsed
     # Dominant kernel: whichever of the two scorers took more device time -- bm25_maxscore_kernel (dynamic pruning;
@@ -1445,7 +1522,7 @@ def main():
         "merge_ms_per_step": round(st["merge_ms"] / max(1, st["batches"]), 4),
         "host_plan_ms_per_step": round(st["host_plan_ms"] / max(1, st["batches"]), 4),
     })
-    if rank == 0 and world == 1 and not use_dist and not args.no_prune and args.exhaustive_steps > 0 and args.workload in ("C3", "C2"):
+    if rank == 0 and world == 1 and not use_dist and not args.no_prune and args.exhaustive_steps > 0 and args.workload in ("C3", "C2") and args.full:
         # The north star's ">= 40 % of the HBM-read roofline on the postings scan": the EXHAUSTIVE route over the same batches
         # (NRTGPU_FLAG_NO_PRUNE: every posting of every query term is streamed, nothing skipped), timed here in the same run --
         # algorithmic bytes (9 B per posting) / the scan kernel's average launch (HIP events on the library's stream).
@@ -1491,11 +1568,12 @@ def main():
         for l in leaves_x:
             l.release()
         ctx_x.close()
-    if rank == 0 and world == 1 and not use_dist and args.c2_steps > 0 and args.workload == "C3" and not args.docs and not args.no_prune:
+    if rank == 0 and world == 1 and not use_dist and args.c2_steps > 0 and args.workload == "C3" and not args.docs and not args.no_prune and args.full:
         out["roofline"]["c2"] = c2_leg(args, local_rank, flags, planner_threads)
-    if rank == 0 and world == 1 and not use_dist and args.c5_steps > 0 and args.workload == "C3" and not args.docs and not args.no_prune and not args.packed:
+    if (rank == 0 and world == 1 and not use_dist and args.c5_steps > 0 and args.workload == "C3" and not args.docs and not args.no_prune and not args.packed
+            and args.full):
         out["roofline"]["c5"] = c5_leg(args, local_rank, planner_threads)
-    if rank == 0 and world == 1 and not use_dist and args.c4_steps > 0 and args.workload == "C3" and not args.docs:
+    if rank == 0 and world == 1 and not use_dist and args.c4_steps > 0 and args.workload == "C3" and not args.docs and args.full:
         # The other half of the path in the same line: BASELINE config 4 -- 10 M x 768 fp32 rows, exact
         # cosine top-100, 64 queries per pass -- for --c4-steps passes: the sketch kernel's physical HBM fraction, the matrix cores'
         # rate against the fp16 peak, the fp64 check over every row, and the C port on the host cores.  (bench.py --workload C4 is
@@ -1516,12 +1594,12 @@ def main():
             "two_callers": c4.get("two_callers"),   # the same passes with two callers taking turns: staging overlapped with the other's stream
             "corpus_build_s": c4["config"]["corpus_build_s"],
         }
-    if rank == 0 and world == 1 and not use_dist and args.closed_loop and args.workload in ("C3", "C2"):
+    if rank == 0 and world == 1 and not use_dist and args.closed_loop and args.workload in ("C3", "C2") and args.full:
         # queries/s AND latency (BASELINE.json's metric): the closed loop of SURVEY 8d, same index, same query set
         callers = [int(x) for x in args.closed_loop.split(",") if x.strip()]
         out["closed_loop"] = closed_loop(ctx, searcher, queries, mgr, callers, args.closed_loop_ms)
         out["closed_loop"]["entry"] = "nrtgpu_search_bm25_coalesced, one query per call, native caller threads (bench/loadgen)"
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_queries > 0:
+    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_queries > 0 and args.full:
         out["cpu_baseline"] = cpu_baseline(corpus, qranks, w.k, args.cpu_queries)
         luc = lucene_baseline(w, searcher, queries, mgr, min(256, n_distinct))
         out["cpu_baseline"]["lucene"] = luc

@@ -4,7 +4,7 @@
 #     gpurun --timeout 1500 -- 'bash scripts/gpu_measure.sh <tag> <step> [<step> ...]'
 # writes under gpurun_out/<tag>/ (copy what is to be judged into profiles/).  Steps:
 #   suite        the driver's GPU suite (pytest -m gpu) + smoke
-#   bench        the default bench line twice in the driver's form (--steps 20 --warmup 5) and once at 200 steps
+#   bench        the plain bench line twice in the driver's form (--steps 20 --warmup 5) and the --full line at 200 steps
 #   variants     bench lines: C2, packed postings, exhaustive route, clustered / sorted corpora
 #   trace        rocprofv3 --kernel-trace --stats of the driver's command -> <tag>_kernel_stats.csv
 #   pmc          rocprofv3 --pmc passes (each a run of its own): FETCH_SIZE of the default / exhaustive / packed lines, the SQ
@@ -54,14 +54,14 @@ suite)
 bench)
   el "bench lines"
   for rep in 1 2; do timeout 400 python bench.py --steps 20 --warmup 5 2>/dev/null | tee $O/${TAG}_bench_steps20_$rep.json | show "c3 --steps 20 --warmup 5 (driver's form)"; done
-  timeout 400 python bench.py --c4-steps 0 2>/dev/null | tee $O/${TAG}_bench_line.json | show "c3 default (200 steps)" ;;
+  timeout 400 python bench.py --full --c4-steps 0 2>/dev/null | tee $O/${TAG}_bench_line.json | show "c3 default (200 steps)" ;;
 variants)
   el "bench variants"
-  timeout 200 python bench.py --workload C2 --no-cpu-baseline 2>/dev/null | tee $O/${TAG}_bench_c2.json | show "c2"
-  timeout 200 python bench.py --packed --no-cpu-baseline --closed-loop '' --c4-steps 0 2>/dev/null | tee $O/${TAG}_bench_c3_packed.json | show "c3 packed"
+  timeout 200 python bench.py --full --workload C2 --no-cpu-baseline 2>/dev/null | tee $O/${TAG}_bench_c2.json | show "c2"
+  timeout 200 python bench.py --full --packed --no-cpu-baseline --closed-loop '' --c4-steps 0 2>/dev/null | tee $O/${TAG}_bench_c3_packed.json | show "c3 packed"
   timeout 200 python bench.py --no-prune --no-cpu-baseline --closed-loop '' --c4-steps 0 2>/dev/null | tee $O/${TAG}_bench_line_no_prune.json | show "c3 no-prune"
   for v in clustered sorted; do
-    timeout 300 python bench.py --corpus-variant $v --steps 100 --warmup 10 --c4-steps 0 --exhaustive-steps 0 --no-cpu-baseline --closed-loop "64" 2>/dev/null | tee $O/${TAG}_bench_c3_$v.json | show "c3 $v"
+    timeout 300 python bench.py --full --corpus-variant $v --steps 100 --warmup 10 --c4-steps 0 --exhaustive-steps 0 --no-cpu-baseline --closed-loop "64" 2>/dev/null | tee $O/${TAG}_bench_c3_$v.json | show "c3 $v"
   done ;;
 trace)
   el "kernel trace"
@@ -101,7 +101,7 @@ import csv,sys
 for r in csv.DictReader(open(sys.argv[1])): print(r['Name'][:60].ljust(60), r['Calls'], round(float(r['AverageNs'])/1e3,1), 'us', r['Percentage'])" $O/${TAG}_emulate8_kernel_stats.csv | head -14 ;;
 c4)
   el "C4 lines"
-  for q in 1 32 64; do timeout 400 python bench.py --workload C4 --knn-queries $q --steps 20 --warmup 4 2>/dev/null | tee $O/${TAG}_bench_c4_q$q.json | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print('c4 q$q', d['value'], d['ms_per_step'], r['kernel'], r['avg_launch_ms'], 'frac', r['frac'], 'mfma', r['mfma_frac'], 'traffic', r['traffic'], 'verify', (d.get('verify') or {}).get('agrees_with_fp64'))"; done ;;
+  for q in 1 32 64; do timeout 400 python bench.py --full --workload C4 --knn-queries $q --steps 20 --warmup 4 2>/dev/null | tee $O/${TAG}_bench_c4_q$q.json | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print('c4 q$q', d['value'], d['ms_per_step'], r['kernel'], r['avg_launch_ms'], 'frac', r['frac'], 'mfma', r['mfma_frac'], 'traffic', r['traffic'], 'verify', (d.get('verify') or {}).get('agrees_with_fp64'))"; done ;;
 cache)
   el "cache-path PMC passes"
   rm -f $O/${TAG}_pmc_cache.txt

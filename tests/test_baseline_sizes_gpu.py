@@ -199,7 +199,9 @@ def test_knn_c4_full_size_against_fp64(oracle):
         blk = _normal_chunk(777, c, rows, dim)
         seg_buf[a0: a0 + rows] = blk
         b64 = blk.astype(np.float64)
-        cos = (b64 @ q64.T) / (np.linalg.norm(b64, axis=1)[:, None] * qn[None, :])
+        # einsum, not `b64 @ q64.T`: matrix products that several of these threads run at once through the bundled OpenBLAS
+        # (0.3.29) come back with wrong rows now and then -- a reference that ranks a doc it should not, or drops one
+        cos = np.einsum("ij,kj->ik", b64, q64) / (np.linalg.norm(b64, axis=1)[:, None] * qn[None, :])
         sc = np.maximum((1.0 + cos) / 2.0, 0.0)
         out = []
         for j in range(len(check_q)):
