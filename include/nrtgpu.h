@@ -360,12 +360,21 @@ int  nrtgpu_search_bm25_batch_device_epoch(nrtgpu_ctx* ctx, const nrtgpu_seg* co
  * TopDocs.merge on every rank; every rank receives every answer.  total_hits sums the shards' counts; the relation is
  * GREATER_THAN_OR_EQUAL_TO iff some shard's is.
  * Failure of ONE rank's part of a one-call search (nrtgpu_dist_search_bm25_batch[_mode], nrtgpu_dist_knn_exact,
- * nrtgpu_dist_search_hybrid_batch): a rank whose shard search fails -- its thread's deadline, a planner refusal, a device
- * error -- still enters the exchange, with empty lists and its status word in the same grouped collective, so that no peer is
- * left waiting in a collective this rank would never issue; EVERY rank then returns an error (the failed rank its own, the
- * others NRTGPU_ERR_STATE naming the first failed rank), and the communicator stays usable.  The re-run of queries whose
- * speculative threshold failed ignores the thread's deadline (it is the tail of a search that was launched in time).  A caller
- * that pipelines with the two halves below vouches for its own ranks: nothing of this travels there. */
+ * nrtgpu_dist_search_hybrid_batch) -- its thread's deadline, a planner refusal, a device error: every rank issues the same
+ * collectives whatever fails; a failed rank skips its remaining local steps and enters each exchange with empty lists and its
+ * status word in the same collective.
+ *   - a failure BEFORE the call's last exchange (the local search, BM25's merge and verdicts when the all-to-all form's verdict
+ *     all-gather follows, BM25's re-run, the hybrid's first-pass merge and tail): EVERY rank returns an error (the failed rank its
+ *     own, the others NRTGPU_ERR_STATE naming the first failed rank), and the communicator stays usable;
+ *   - a failure AFTER it (the final merge): that rank's alone -- it returns its error, its peers return their answers;
+ *   - in either case no rank waits in a collective a peer will not issue.  Two cases are left out by design: a failure to
+ *     reserve the call's buffers (before any collective: that rank leaves before the first exchange -- after the first call of
+ *     a shape this cannot happen), and, when the lists are gathered whole (the all-gather form, or a batch the all-to-all form
+ *     cannot slice: nrtgpu_dist_owned_range), a failure of BM25's merge on one rank after an exchange in which every rank
+ *     succeeded, while queries are to be run again: that rank cannot know whether its peers will re-run, and closing this
+ *     would take one more collective on every speculating call.
+ * The re-run of queries whose speculative threshold failed ignores the thread's deadline (it is the tail of a search that was
+ * launched in time).  A caller that pipelines with the two halves below vouches for its own ranks: nothing of this travels there. */
 int  nrtgpu_dist_unique_id(void* out128);
 int  nrtgpu_dist_init(nrtgpu_ctx* ctx, int32_t world, int32_t rank, const void* id128);
 int  nrtgpu_dist_search_bm25_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,

@@ -25,6 +25,14 @@ int  nrtgpu_bench_closed_loop(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, co
  * production callers: a held coalescer parks every request. */
 int  nrtgpu_debug_hold_coalescers(nrtgpu_ctx* ctx, int32_t hold);
 int  nrtgpu_debug_coalescer_pending(nrtgpu_ctx* ctx, int32_t which);
+/* TEST HOOK for the one-call multi-GPU searches (nrtgpu_dist_search_bm25_batch[_mode], nrtgpu_dist_knn_exact,
+ * nrtgpu_dist_search_hybrid_batch): the NEXT such call on this context (nrtgpu_dist_init first) fails `step` (>= 0) with
+ * NRTGPU_ERR_STATE ("injected"), as a host-side error before anything of that step is enqueued: 0 the shard search (BM25, kNN,
+ * the hybrid's first pass), 1 the merge after an exchange (BM25: the first one, with the verdicts), 2 the BM25 re-run, 3 the
+ * hybrid's merge of the first pass, 4 the hybrid tail, 5 the merge after the BM25 re-run's exchange.  failed_query (>= 0): that
+ * query's speculative guess counts as failed in this rank's verdicts (BM25 with speculation), so that the call runs it again --
+ * a test plants the same query on every rank.  -1: none. */
+int  nrtgpu_debug_dist_inject(nrtgpu_ctx* ctx, int32_t step, int32_t failed_query);
 /* TEST HOOK: segment handles of the context (uploads and forks) that have not been freed yet.  nrtgpu_segment_release under
  * running searches defers the free to the last of them: this count is how a test observes that it happened. */
 int64_t nrtgpu_debug_live_segments(nrtgpu_ctx* ctx);

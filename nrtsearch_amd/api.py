@@ -330,6 +330,11 @@ class GpuContext:
         """Requests parked in a coalescer: 0 = nrtgpu_search_bm25_coalesced, 1 = nrtgpu_knn_exact_coalesced."""
         return int(_lib.load().nrtgpu_debug_coalescer_pending(self._h, int(which)))
 
+    def debug_dist_inject(self, step: int = -1, failed_query: int = -1) -> None:
+        """Test hook (nrtgpu_debug_dist_inject): the next one-call dist search on this context fails `step`, and / or counts
+        `failed_query`'s speculative guess as failed."""
+        _lib.check(_lib.load().nrtgpu_debug_dist_inject(self._h, int(step), int(failed_query)))
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             _lib.load().nrtgpu_destroy(self._h)

@@ -113,6 +113,12 @@ extern thread_local nrtgpu_diagnostics g_diag;       // nrtgpu_last_diagnostics
 extern thread_local std::vector<int32_t> g_thread_slices;   // nrtgpu_set_thread_slices: the caller's slice of every leaf of its next calls
 int64_t monotonic_ns();
 inline bool deadline_passed(int64_t deadline_ns) { return deadline_ns != 0 && monotonic_ns() >= deadline_ns; }
+// clear != false: the calling thread runs without its deadline until the scope ends, then has it back
+struct DeadlineScope {
+  int64_t saved;
+  explicit DeadlineScope(bool clear) : saved(g_deadline_ns) { if (clear) g_deadline_ns = 0; }
+  ~DeadlineScope() { g_deadline_ns = saved; }
+};
 #define NRT_CHECK_DEADLINE(what)                                                                             \
   do {                                                                                                       \
     if (deadline_passed(g_deadline_ns)) return fail(NRTGPU_ERR_TIMEOUT, "deadline passed %s", what);        \

@@ -567,11 +567,9 @@ static int search_batch_spec(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, con
       seeds[i] = kth > 0 ? kth - 1 : 0ull;
     }
   }
-  const int64_t deadline = g_deadline_ns;
-  g_deadline_ns = 0;
+  DeadlineScope no_deadline(true);
   // (a few queries: a follow-up launch beside the next batch -- enqueue_search; more than that and it is a batch of its own)
   const int rc2 = search_batch_impl(ctx, segs, doc_bases, n_segs, rq.data(), (int32_t)rq.size(), ro.data(), nullptr, true, seeds.data(), rq.size() <= 32);
-  g_deadline_ns = deadline;
   if (rc2 != 0) return rc2;
   for (size_t i = 0; i < rerun.size(); ++i) out[rerun[i]] = ro[i];
   nrtgpu_diagnostics d = g_diag;   // both passes
@@ -761,11 +759,9 @@ extern "C" int nrtgpu_search_hybrid_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* con
     ro[i] = out[rerun[i]];
     memcpy(rv.data() + i * (size_t)dim, query_vectors + (size_t)rerun[i] * (size_t)dim, (size_t)dim * sizeof(float));
   }
-  const int64_t deadline = g_deadline_ns;
-  g_deadline_ns = 0;
+  DeadlineScope no_deadline(true);
   const int rc2 = search_hybrid_impl(ctx, segs, doc_bases, n_segs, rq.data(), (int32_t)rq.size(), field_id, sim, rv.data(), dim, boost, query_weight,
                                      rescore_weight, window, ro.data(), nullptr, true);
-  g_deadline_ns = deadline;
   if (rc2 != 0) return rc2;
   for (size_t i = 0; i < rerun.size(); ++i) out[rerun[i]] = ro[i];
   return NRTGPU_OK;
@@ -1052,11 +1048,7 @@ extern "C" int nrtgpu_search_bm25_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* c
   }
   // (a batch of several requests is not failed for the leader's deadline: its mates have not expired -- they were checked when the
   //  batch was formed -- and a batch is a few milliseconds.  A lone request keeps its deadline.)
-  struct DeadlineScope {
-    int64_t saved;
-    explicit DeadlineScope(bool clear) : saved(g_deadline_ns) { if (clear) g_deadline_ns = 0; }
-    ~DeadlineScope() { g_deadline_ns = saved; }
-  } deadline_scope(batch.size() > 1);
+  DeadlineScope deadline_scope(batch.size() > 1);
   // A member whose query is run again (a speculative threshold failed the merge's check) must not hold up its batch mates: they
   // are woken between the two passes with the answer they already have.
   std::vector<char> released(batch.size(), 0);

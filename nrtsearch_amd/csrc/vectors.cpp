@@ -724,11 +724,7 @@ extern "C" int nrtgpu_knn_exact_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* con
   int rc;
   {
     // (a panel of several requests does not run under its leader's deadline: its mates have not expired)
-    struct DeadlineScope {
-      int64_t saved;
-      explicit DeadlineScope(bool clear) : saved(g_deadline_ns) { if (clear) g_deadline_ns = 0; }
-      ~DeadlineScope() { g_deadline_ns = saved; }
-    } deadline_scope(batch.size() > 1);
+    DeadlineScope deadline_scope(batch.size() > 1);
     rc = knn_impl(ctx, segs, doc_bases, n_segs, field_id, sim, qs.data(), (int32_t)batch.size(), dim, kmax, boost, false, 0, 0.0f, outs.data());
   }
   const std::string err = rc ? g_last_error : std::string();

@@ -15,7 +15,7 @@ def main():
     rank, world, sync_dir, out_path = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], sys.argv[4]
     n_docs, n_queries, k = int(sys.argv[5]), int(sys.argv[6]), int(sys.argv[7])
     variant = sys.argv[8] if len(sys.argv) > 8 else "iid"
-    host_only = os.environ.get("NRTGPU_TEST_HOST_ONLY") == "1"   # tests/test_dist_two_ranks_host.py: against tests/mockhip, BM25 only
+    host_only = os.environ.get("NRTGPU_TEST_HOST_ONLY") == "1"   # tests/test_dist_two_ranks_host.py: against tests/mockhip
     import numpy as np
 
     from nrtsearch_amd import api, synth, workload
@@ -32,8 +32,7 @@ def main():
         g = api.GpuSegment(ctx, seg.max_doc, seg.doc_base)
         g.add_field_norms(0, seg.norms)
         g.add_terms(0, seg.term_ids, seg.offsets, seg.docids, seg.freqs)
-        if not host_only:
-            g.add_vectors(1, all_vecs[seg.doc_base: seg.doc_base + seg.max_doc])
+        g.add_vectors(1, all_vecs[seg.doc_base: seg.doc_base + seg.max_doc])
         g.seal()
         leaves.append(g)
     sr = api.GpuIndexSearcher(ctx, leaves, api.IndexStatistics.from_corpus(corpus))
@@ -62,7 +61,7 @@ def main():
         out["spec_" + name] = {k_: c1[k_] - c0[k_] for k_ in ("queries", "reruns")}   # the shard-level guesses of this call
         got = sr.dist_search_batch(queries, [mgr] * n_queries, mode=mode | api.EXCHANGE_NO_SPECULATION)
         out["bm25_nospec_" + name] = [None if g is None else (g.docs, g.scores, g.total_hits, g.relation_gte) for g in got]
-        if variant != "iid" or host_only:
+        if variant != "iid" or host_only:   # (see the failure cases below)
             continue
         qv = all_vecs[:8] + np.float32(0.25)
         kn = sr.dist_knn_exact(1, "cosine", qv, 10, mode=mode)
@@ -123,6 +122,38 @@ def main():
             api.GpuContext.set_thread_deadline(None)
     got = sr.dist_search_batch(queries, [mgr] * n_queries, mode=api.EXCHANGE_ALLGATHER)
     out["after_failure_allgather"] = [None if g is None else (g.docs, g.scores, g.total_hits, g.relation_gte) for g in got]
+    # every one-call entry x every step x both exchange forms: rank 1's part fails at that step (the development library's hook,
+    # include/nrtgpu_dev.h: nrtgpu_debug_dist_inject; tests/test_dist_two_ranks_*.py load it through NRTGPU_LIB_PATH).  A step before
+    # the call's last exchange: BOTH ranks raise -- rank 1 its own error, rank 0 one that names rank 1 -- and nobody hangs.  The final
+    # merge: rank 1 raises, rank 0 answers.  Either way the next call on the communicator answers.  The re-run is reached through a
+    # query planted on both ranks; BM25's merge before the re-run is tested where the verdicts' all-gather follows it (all-to-all),
+    # and as a final merge without speculation (the lists gathered whole with a re-run pending is the case include/nrtgpu.h leaves
+    # open).  Against tests/mockhip the kNN and hybrid entries run here only: no kernel writes a merge's outputs under the stand-in,
+    # so what a vector search leaves in the reused workspaces would come back as the answers of the BM25 calls above
+    SEARCH, MERGE, RERUN, HYBRID_MERGE, HYBRID_TAIL, RERUN_MERGE = range(6)
+    NOSPEC = api.EXCHANGE_NO_SPECULATION
+    qv = all_vecs[:8] + np.float32(0.25)
+    entries = {
+        "bm25": lambda m: [None if g is None else (g.docs, g.scores, g.total_hits, g.relation_gte) for g in sr.dist_search_batch(queries, [mgr] * n_queries, mode=m)],
+        "knn": lambda m: [None if g is None else (g.docs, g.scores, g.total_hits) for g in sr.dist_knn_exact(1, "cosine", qv, 10, mode=m)],
+        "hybrid": lambda m: [None if g is None else (g.docs, g.scores, g.total_hits, g.relation_gte)
+                             for g in sr.dist_search_hybrid_batch(queries[:8], [mgr] * 8, 1, "cosine", qv, 20, 1.0, 2.0, mode=m)],
+    }
+    cases = [("bm25", SEARCH, 0, -1, False), ("bm25", MERGE, 0, -1, False), ("bm25", MERGE, NOSPEC, -1, True), ("bm25", RERUN, 0, 3, False), ("bm25", RERUN_MERGE, 0, 3, True)]
+    if variant == "iid":
+        cases += [("knn", SEARCH, 0, -1, False), ("knn", MERGE, 0, -1, True), ("hybrid", SEARCH, 0, -1, False), ("hybrid", HYBRID_MERGE, 0, -1, False),
+                  ("hybrid", HYBRID_TAIL, 0, -1, False), ("hybrid", MERGE, 0, -1, True)]
+    out["injected"] = []
+    for entry, step, flags, plant, final in cases:
+        for name, mode in (("allgather", api.EXCHANGE_ALLGATHER), ("alltoall", api.EXCHANGE_ALLTOALL)):
+            if (entry, step, flags) == ("bm25", MERGE, 0) and mode == api.EXCHANGE_ALLGATHER:
+                continue
+            ctx.debug_dist_inject(step if rank == 1 else -1, plant)
+            try:
+                got = entries[entry](mode | flags)
+            except Exception as e:   # noqa: BLE001
+                got = str(e)
+            out["injected"].append(dict(entry=entry, step=step, flags=flags, form=name, final=final, got=got, next=entries[entry](mode | flags)))
     out["stats"] = ctx.stats()
     with open(out_path, "wb") as f:
         pickle.dump(out, f)

@@ -27,6 +27,9 @@ HIPCC = "/opt/rocm/bin/hipcc"
 def mockrccl(tmp_path_factory):
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc is not here")
+    from nrtsearch_amd import build
+
+    build.build_dev()   # (the workers run the development library: its failure hook)
     d = tmp_path_factory.mktemp("mockrccl")
     out = str(d / "librccl.so.1")
     subprocess.run([HIPCC, "-O1", "-fPIC", "-shared", "-x", "hip", "--offload-arch=gfx950", "-Wl,-soname,librccl.so.1",
@@ -45,8 +48,8 @@ def test_two_ranks_through_the_librarys_collective_equal_the_whole_index(mockrcc
     world, n_docs, n_q, k = 2, 600_000, 32, 100
     sync_dir = tempfile.mkdtemp(prefix="nrtgpu_dist2_")
     outs = [os.path.join(sync_dir, f"rank{r}.pkl") for r in range(world)]
-    env = dict(os.environ, LD_LIBRARY_PATH=mockrccl + ":" + os.environ.get("LD_LIBRARY_PATH", ""))
-    env.pop("NRTGPU_LIB_PATH", None)
+    env = dict(os.environ, LD_LIBRARY_PATH=mockrccl + ":" + os.environ.get("LD_LIBRARY_PATH", ""),
+               NRTGPU_LIB_PATH=os.path.join(ROOT, "nrtsearch_amd", "libnrtgpu_dev.so"))
     procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_dist_worker.py"), str(r), str(world), sync_dir, outs[r],
                                str(n_docs), str(n_q), str(k), variant], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for r in range(world)]
     logs = []
@@ -133,6 +136,27 @@ def test_two_ranks_through_the_librarys_collective_equal_the_whole_index(mockrcc
                 assert ("deadline" in msg) if r == 1 else ("rank 1 of 2 failed" in msg), (r, form, msg)
             for qi in range(n_q):
                 same(ranks[r]["after_failure_allgather"][qi], whole[qi])
+        # rank 1's part failed at every step of every entry in turn (tests/_dist_worker.py): before the call's last exchange both ranks
+        # raised (rank 0 naming rank 1); at the final merge rank 1 raised and rank 0 returned the whole-index answers; the next call on
+        # the communicator returned them on both ranks
+        expected = {"bm25": (whole, True), "knn": (whole_knn, False), "hybrid": (whole_hy, True)}
+        cases = [(c["entry"], c["step"], c["flags"], c["form"]) for c in ranks[0]["injected"]]
+        assert cases == [(c["entry"], c["step"], c["flags"], c["form"]) for c in ranks[1]["injected"]]
+        assert len(cases) == (21 if variant == "iid" else 9), cases
+        for c0, c1 in zip(ranks[0]["injected"], ranks[1]["injected"]):
+            exp_list, rel = expected[c0["entry"]]
+            assert isinstance(c1["got"], str) and "injected" in c1["got"], c1["got"]
+            answered = [c0["next"], c1["next"]]
+            if c0["final"]:
+                assert isinstance(c0["got"], list), c0["got"]
+                answered.append(c0["got"])
+            else:
+                assert isinstance(c0["got"], str) and "rank 1 of 2 failed" in c0["got"], c0["got"]
+            for got in answered:
+                assert len(got) == len(exp_list) and any(g is not None for g in got)
+                for qi, g in enumerate(got):
+                    if g is not None:
+                        same(g, exp_list[qi], rel)
         cases = [("bm25", whole, True), ("bm25_nospec", whole, True), ("bm25_pipelined", whole, True)]
         if variant == "iid":
             cases += [("knn", whole_knn, False), ("hybrid", whole_hy, True)]
