@@ -115,6 +115,15 @@ int  nrtgpu_segment_add_terms(nrtgpu_seg* seg, int32_t field_id, int64_t n_terms
  * (the reference's vector tests run at dim = 3: VectorFieldDefTest.java:1885-1965).  Queries pass the field's dim. */
 int  nrtgpu_segment_add_vectors(nrtgpu_seg* seg, int32_t field_id, int32_t dim, int32_t n,
                                 const int32_t* ord_to_doc, const float* row_major);
+/* byte vectors of one field (leaf.getByteVectorValues; VECTOR_ELEMENT_BYTE fields, VectorFieldDef.java:677-882): n rows of `dim`
+ * int8, row-major; ord_to_doc as nrtgpu_segment_add_vectors.  dim <= 2048 (more: NRTGPU_ERR_UNSUPPORTED).  Rows are kept
+ * zero-padded to whole 64-element steps of the i8 matrix instruction, in its operand order -- up to 8 steps (512 elements) as
+ * many as the dimension needs, beyond that the next step count with a divisor in 4..8 (9 -> 10, 11 -> 12, 13 -> 14, 17 -> 18,
+ * 19 -> 20, 22 and 23 -> 24, 26 and 27 -> 28, 29 -> 30, 31 -> 32: up to 11 % more bytes, for dimensions 513-576) -- with |v|^2
+ * per row (int32) computed on the device at upload; queries pass the field's dim.  A field holds float rows or byte rows, never both (the second kind:
+ * NRTGPU_ERR_INVALID_ARG). */
+int  nrtgpu_segment_add_byte_vectors(nrtgpu_seg* seg, int32_t field_id, int32_t dim, int32_t n,
+                                     const int32_t* ord_to_doc, const int8_t* row_major);
 /* builds the per-term doc-range tables; the segment becomes searchable */
 int  nrtgpu_segment_seal(nrtgpu_seg* seg);
 /* leaf.getLiveDocs() as 64-bit words, bit d set = doc d live; NULL => all live.  May be called
@@ -485,6 +494,49 @@ int  nrtgpu_knn_exact_relation(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, c
 int  nrtgpu_knn_search(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
                        int32_t field_id, int32_t sim, const float* queries, int32_t n_queries, int32_t dim, int32_t k,
                        float boost, int32_t filter_mask, float min_score, nrtgpu_topdocs* out /* n_queries */);
+
+/* ---------------------------------------------------------------------------------------------
+ * Exact search over BYTE (int8) vector fields (nrtgpu_segment_add_byte_vectors).
+ * nrtgpu_knn_exact_bytes replaces ExactVectorQuery.ExactByteVectorQuery (query/vector/ExactVectorQuery.java:230-247) as
+ * nrtgpu_knn_exact replaces the float query; nrtgpu_knn_search_bytes answers the `knn` request path over a byte field
+ * (NrtKnnByteVectorQuery, VectorFieldDef.java:789-829) exactly, as nrtgpu_knn_search does: pre-filter mask, min_score on the
+ * UNBOOSTED score, boost afterwards, total_hits = hits returned.  queries: n_queries * dim int8, row-major.
+ *   sim: 0 cosine, 1 dot_product, 2 l2_norm, 3 max_inner_product ("normalized_cosine" does not exist for byte fields:
+ *        VectorFieldDef.java:698-701)
+ * The unboosted score of a (query, row) pair, from the INTEGERS dot = sum q_i v_i, nq = sum q_i^2, nv = sum v_i^2 (int32; below
+ * 2^28 at dim <= 2048) -- all float32, each operation rounded once, int -> float conversions round to nearest even.  The four
+ * shapes are ByteVectorFieldDef.similarityToScore (VectorFieldDef.java:870-881); how Lucene's
+ * VectorSimilarityFunction.compare(byte[], byte[]) reaches them is [Lucene-recall] like the rest of the vector arithmetic
+ * (SURVEY A.7):
+ *   cosine            c = (float)((double)dot / sqrt((double)nq * (double)nv));  (1.0f + c) / 2.0f
+ *   dot_product       0.5f + (float)dot / (float)(dim * 32768)      (dim: the field's own dimension)
+ *   l2_norm           d2 = nq + nv - 2 * dot (int32, == sum (q_i - v_i)^2);  1.0f / (1.0f + (float)d2)
+ *   max_inner_product x = (float)dot;  x < 0 ? 1.0f / (1.0f + -1.0f * x) : x + 1.0f
+ * Returned score = unboosted score * boost (float), as VectorValuesScorer.score() (ExactVectorQuery.java:165-167).  The matrix
+ * cores return the integers exactly, so these are final score bits from ONE pass over the rows: no tolerance, no second pass.
+ * Cosine: a zero QUERY is refused (NRTGPU_ERR_INVALID_ARG; validateVectorForSearch, VectorFieldDef.java:853-861).  A zero ROW
+ * cannot exist in a cosine field of the reference (the same check at indexing, :750), but the library does not know a field's
+ * similarity at upload: such a row scores 0 under sim = 0 (never NaN, never a fault).
+ * boost: finite and >= 0 (else NRTGPU_ERR_INVALID_ARG: hits are ranked through keys that order like non-negative scores).
+ * Otherwise the float entries' contract: ranking (score desc, doc asc), global docids, liveDocs always apply, k <= NRTGPU_MAX_K
+ * (else NRTGPU_ERR_UNSUPPORTED), dim <= 2048 (else UNSUPPORTED), a query dim other than the field's: NRTGPU_ERR_INVALID_ARG,
+ * thread deadlines checked on entry and between passes (64 queries per pass), nrtgpu_knn_exact_bytes reports total_hits = live
+ * docs that have a vector, nrtgpu_knn_exact_relation answers for byte fields too, forks share the rows, nrtgpu_get_stats counts
+ * the passes in knn_panels / knn_rows / knn_score_launches / knn_score_ms.  A float entry point called on a byte field, and a
+ * byte entry point on a float field, return NRTGPU_ERR_INVALID_ARG naming the field's element type.
+ * Out of scope for byte fields (all INVALID_ARG by that rule): nrtgpu_knn_exact_coalesced, the nrtgpu_dist_* entries,
+ * nrtgpu_rescore_vectors and the hybrid tail; the Java shim does not bind these functions yet.
+ * --------------------------------------------------------------------------------------------- */
+int  nrtgpu_knn_exact_bytes(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                            int32_t field_id, int32_t sim, const int8_t* queries, int32_t n_queries, int32_t dim, int32_t k,
+                            float boost, nrtgpu_topdocs* out /* n_queries */);
+int  nrtgpu_knn_search_bytes(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                             int32_t field_id, int32_t sim, const int8_t* queries, int32_t n_queries, int32_t dim, int32_t k,
+                             float boost, int32_t filter_mask, float min_score, nrtgpu_topdocs* out /* n_queries */);
+/* The score of one (query, row) pair of a byte field from its three integers (the table above), exposed for the tests like
+ * nrtgpu_fixed_point_scale: needs no device; it is the very function the kernel compiles.  Writes the UNBOOSTED score; returns 0,
+ * or NRTGPU_ERR_INVALID_ARG (sim outside 0..3, dim outside 1..2048, integers `dim` int8 pairs cannot produce). */
+int  nrtgpu_byte_vector_score(int32_t sim, int32_t dim, int32_t dot, int32_t q_norm2, int32_t v_norm2, float* out);
 
 /* Vector rescorer: RescoreOperation.rescore(hits, ctx) of a QueryRescore whose rescoreQuery is an exact
  * vector query (src/main/java/com/yelp/nrtsearch/server/rescore/QueryRescore.java:40-57): every

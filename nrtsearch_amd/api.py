@@ -112,6 +112,14 @@ class TopDocs:
 _OUT_ARRAYS = threading.local()
 
 
+def _int8_rows(a, what: str) -> np.ndarray:
+    """int8[n, dim], contiguous.  Anything but int8 is a TypeError: a cast would wrap -129 to 127 without a word."""
+    a = np.asarray(a)
+    if a.dtype != np.int8:
+        raise TypeError(f"{what} of a byte vector field must be int8, got {a.dtype}")
+    return np.ascontiguousarray(np.atleast_2d(a))
+
+
 def _topdocs_outputs(nq: int, k: int):
     """(outs, docs, scores) for a call that returns nq lists of up to k hits: an array of nrtgpu_topdocs whose docs / scores pointers
     address the rows of two numpy arrays.  Built once per thread and shape and used again -- 2 x nq pointer objects through
@@ -395,6 +403,16 @@ class GpuSegment:
             op = ord_to_doc.ctypes.data
         _lib.check(_lib.load().nrtgpu_segment_add_vectors(self._h, int(field), vectors.shape[1], vectors.shape[0],
                                                           op, vectors.ctypes.data))
+
+    def add_byte_vectors(self, field: int, vectors: np.ndarray, ord_to_doc: Optional[np.ndarray] = None) -> None:
+        """The rows of a byte (int8) vector field: int8[n, dim] (nrtgpu_segment_add_byte_vectors).  No silent cast."""
+        vectors = _int8_rows(vectors, "vectors")
+        op = None
+        if ord_to_doc is not None:
+            ord_to_doc = np.ascontiguousarray(ord_to_doc, dtype=np.int32)
+            op = ord_to_doc.ctypes.data
+        _lib.check(_lib.load().nrtgpu_segment_add_byte_vectors(self._h, int(field), vectors.shape[1], vectors.shape[0],
+                                                               op, vectors.ctypes.data))
 
     def seal(self) -> None:
         _lib.check(_lib.load().nrtgpu_segment_seal(self._h))
@@ -706,6 +724,36 @@ class GpuIndexSearcher:
                                                  self.SIMILARITY[similarity], queries.ctypes.data, nq, dim, int(k),
                                                  C.c_float(boost), int(filter.mask_id) if filter else 0,
                                                  C.c_float(min_score), outs))
+        return _topdocs_lists(outs, docs, scores, nq)
+
+    # ---- byte (int8) vector fields: ExactByteVectorQuery / NrtKnnByteVectorQuery ---------------------
+    BYTE_SIMILARITY = {"cosine": 0, "dot_product": 1, "l2_norm": 2, "max_inner_product": 3}
+
+    def _byte_similarity(self, similarity: str) -> int:
+        if similarity not in self.BYTE_SIMILARITY:   # ("normalized_cosine" does not exist for byte fields: VectorFieldDef.java:698-701)
+            raise ValueError(f"similarity {similarity!r} is not defined for byte vector fields")
+        return self.BYTE_SIMILARITY[similarity]
+
+    def knn_exact_bytes(self, field: int, similarity: str, queries: np.ndarray, k: int, boost: float = 1.0) -> List[TopDocs]:
+        """Brute-force exact search over a byte vector field (ExactVectorQuery.ExactByteVectorQuery); queries: int8."""
+        sim = self._byte_similarity(similarity)
+        queries = _int8_rows(queries, "queries")
+        nq, dim = queries.shape
+        outs, docs, scores = _topdocs_outputs(nq, int(k))
+        _lib.check(_lib.load().nrtgpu_knn_exact_bytes(self.ctx._h, self._segs, self._bases, len(self.leaves), int(field), sim,
+                                                      queries.ctypes.data, nq, dim, int(k), C.c_float(boost), outs))
+        return _topdocs_lists(outs, docs, scores, nq)
+
+    def knn_search_bytes(self, field: int, similarity: str, queries: np.ndarray, k: int, boost: float = 1.0,
+                         filter: Optional[MaskFilter] = None, min_score: float = 0.0) -> List[TopDocs]:
+        """The `knn` request path over a byte vector field (NrtKnnByteVectorQuery with filter and similarity threshold), exact."""
+        sim = self._byte_similarity(similarity)
+        queries = _int8_rows(queries, "queries")
+        nq, dim = queries.shape
+        outs, docs, scores = _topdocs_outputs(nq, int(k))
+        _lib.check(_lib.load().nrtgpu_knn_search_bytes(self.ctx._h, self._segs, self._bases, len(self.leaves), int(field), sim,
+                                                       queries.ctypes.data, nq, dim, int(k), C.c_float(boost),
+                                                       int(filter.mask_id) if filter else 0, C.c_float(min_score), outs))
         return _topdocs_lists(outs, docs, scores, nq)
 
     def rescore_vectors(self, hits: TopDocs, field: int, similarity: str, query: np.ndarray, window: int,

@@ -1,0 +1,423 @@
+// knn_bytes.hip -- exact (brute-force) search over byte (int8) vector fields on the i8 matrix cores of gfx950.
+//
+// Replaces ExactVectorQuery.ExactByteVectorQuery (query/vector/ExactVectorQuery.java:230-247) and the exact reading of
+// NrtKnnByteVectorQuery (field/VectorFieldDef.java:789-829): score = similarityToScore(compare(query, doc vector)) * boost
+// (VectorFieldDef.java:870-881) for every doc that has a vector, and the top-k collector behind it.
+//
+// Every quantity the byte scorers compute is an INTEGER -- dot product, squared norms, squared distance; below 2^28 at 2048
+// dimensions -- and v_mfma_i32_16x16x64_i8 returns integers exactly, in whatever order it sums.  So ONE pass over the rows gives
+// final score bits (plan.h: knn_byte_score, the function nrtgpu_byte_vector_score exposes): nothing is nominated, rescored or
+// certified here, unlike the fp32 search (knn.hip).  What is kept of that search is its skeleton -- one workgroup per CU, the query
+// panel in LDS in operand order, a wave streaming a contiguous run of 16-row tiles over ALL leaves of the call with a ring of
+// 16-byte requests in flight, a workgroup-local queue of the rows that beat theta -- and its selection contract (candidate lists
+// of `cap` keys, theta, overflow; knn_select_kernel<false>), with keys that are results.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "plan.h"
+
+namespace nrtgpu {
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));   // 16 int8 of an operand, or 4 int32 of a result
+
+constexpr int kKnnBytesThreads = 1024;   // 16 waves, one workgroup per CU (the panel takes up to 128 KiB of LDS)
+constexpr size_t kKnnBytesStaticLds = 1280;   // knn_bytes_kernel's per-query tables
+
+// Resident format, written at upload from a staged chunk of the caller's rows (row-major, `dim` bytes each, rows
+// [row0, row0 + n_chunk) of the field; row0 is a multiple of 16): one thread per 16-byte piece of the chunk's tiles.  Elements
+// beyond `dim` and rows beyond n_chunk are zero: they add nothing to a dot product or a squared norm.  The piece's share of its
+// row's |v|^2 is added to norm2[row] (integer atomics: exact in any order; zeroed by the caller).
+__global__ __launch_bounds__(256) void knn_bytes_pack_kernel(const int8_t* __restrict__ rows, int32_t dim, int64_t row0, int64_t n_chunk,
+                                                            int32_t steps, i32x4* __restrict__ tiles, int32_t* __restrict__ norm2) {
+  const int64_t piece = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t chunk_tiles = (n_chunk + 15) >> 4;
+  if (piece >= chunk_tiles * steps * 64) return;
+  const int32_t l = (int32_t)(piece & 63);
+  const int64_t ts = piece >> 6;
+  const int32_t s = (int32_t)(ts % steps);
+  const int64_t row = (ts / steps) * 16 + (l & 15);   // in the chunk
+  const int32_t k0 = 64 * s + 16 * (l >> 4);
+  uint32_t w[4] = {0u, 0u, 0u, 0u};
+  int32_t n2 = 0;
+  if (row < n_chunk) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int32_t k = k0 + e;
+      const int32_t x = k < dim ? (int32_t)rows[row * dim + k] : 0;
+      n2 += x * x;
+      w[e >> 2] |= ((uint32_t)x & 0xFFu) << (8 * (e & 3));
+    }
+  }
+  tiles[(row0 >> 4) * steps * 64 + piece] = i32x4{(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
+  if (n2) atomicAdd(&norm2[row0 + row], n2);
+}
+
+// The ring of row pieces is driven by hand, as knn_sketch_kernel's (knn.hip): the requests are inline asm loads, and before slot
+// i is consumed the wave waits until at most D - 1 requests are outstanding -- exactly the ones issued after slot i's.
+template <int OFF>
+__device__ __forceinline__ void kb_request(i32x4& dst, const i32x4* p) {
+  asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(dst) : "v"(p), "n"(OFF) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void kb_wait(i32x4& slot) {
+  asm volatile("s_waitcnt vmcnt(%1)" : "+v"(slot) : "n"(N) : "memory");
+}
+template <int D, int I>
+__device__ __forceinline__ void kb_fill(i32x4 (&abuf)[D], const i32x4* cur) {
+  if constexpr (I < D) {
+    kb_request<(I & 3) * 1024>(abuf[I], I < 4 ? cur : cur + 256);
+    kb_fill<D, I + 1>(abuf, cur);
+  }
+}
+// steps I .. D - 1 of a group of D: the step's P query operands are asked of the LDS together and before the wait for the row
+// piece; the piece D ahead is requested into the registers the matrix instructions have just read
+template <int P, int D, int I>
+__device__ __forceinline__ void kb_steps(i32x4 (&abuf)[D], i32x4 (&acc)[P], const i32x4* qs_group, const i32x4* nxt) {
+  if constexpr (I < D) {
+    i32x4 b[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) b[p] = qs_group[(I * P + p) * 64];
+    __builtin_amdgcn_sched_barrier(0);
+    kb_wait<D - 1>(abuf[I]);
+#pragma unroll
+    for (int p = 0; p < P; ++p) acc[p] = __builtin_amdgcn_mfma_i32_16x16x64_i8(abuf[I], b[p], acc[p], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    kb_request<(I & 3) * 1024>(abuf[I], I < 4 ? nxt : nxt + 256);
+    __builtin_amdgcn_sched_barrier(0);
+    kb_steps<P, D, I + 1>(abuf, acc, qs_group, nxt);
+  }
+}
+
+__device__ __forceinline__ uint64_t kb_uniform_u64(uint64_t v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+  return ((uint64_t)hi << 32) | (uint64_t)lo;
+}
+__device__ __forceinline__ int32_t kb_leaf_of_tile(const DKnnBytesLeaf* __restrict__ leaves, int32_t n_leaves, int64_t tile) {
+  int32_t lo = 0, hi = n_leaves;   // the last leaf whose tile_begin <= tile
+  while (hi - lo > 1) {
+    const int32_t mid = (lo + hi) >> 1;
+    if (leaves[mid].tile_begin <= tile) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// Which rows can beat theta, decided on the INTEGERS (one compare per element; the score proper is computed for the few that pass).
+// The score is a monotone function of the dot product (dot_product, max_inner_product: non-decreasing) or of the squared distance
+// (l2_norm: non-increasing) -- every step of knn_byte_score is one correctly rounded, hence monotone, operation, and so is the
+// multiplication by a boost > 0 -- so "score * boost >= theta's score" is "dot >= D" / "d2 <= D" for an integer D found by
+// bisection over the very function the epilogue calls: the test is exact, not a bound.  Cosine divides by the row's own norm:
+// there the test is a necessary condition on (float)dot * rsq(|v|^2), lowered by 2^-16 of the scale the estimate's few fp32
+// roundings (2^-21) live on.  One 32-bit word per query:
+//   sim 1, 3: a row may pass iff dot >= thr          (everything: INT32_MIN, nothing: INT32_MAX)
+//   sim 2   : iff |v|^2 - 2 dot <= thr               (thr = D - |q|^2; everything: INT32_MAX, nothing: INT32_MIN)
+//   sim 0   : iff !((float)dot * rsq|v|^2 <= thr as float)   (everything: -inf, nothing: +inf; a NaN product -- a zero row -- passes)
+constexpr int32_t kKnnBytesMaxDot = 1 << 26;   // > 2048 * 128 * 128
+__device__ inline int32_t knn_bytes_threshold(int sim, int32_t dim, int32_t nq, unsigned long long th, float boost, bool has_query) {
+  const bool upward = sim != 2;
+  const int32_t all = sim == 0 ? (int32_t)__float_as_uint(-INFINITY) : (upward ? INT32_MIN : INT32_MAX);
+  const int32_t none = sim == 0 ? (int32_t)__float_as_uint(INFINITY) : (upward ? INT32_MAX : INT32_MIN);
+  if (!has_query || th == ~0ull) return none;
+  const float ts = key_score(th);
+  if (th == 0ull || !(boost > 0.0f) || !(boost < INFINITY) || !(ts > 0.0f)) return all;
+  if (sim == 0) {
+    const float x = 2.0f * (ts / boost) - 1.0f;   // the cosine must reach about this
+    if (!(x > -INFINITY && x < INFINITY)) return all;
+    const float t = (x - (fabsf(x) + 1.0f) * 0x1p-16f) * sqrtf((float)nq);
+    return t == t ? (int32_t)__float_as_uint(t) : all;
+  }
+  if (upward) {   // the smallest dot whose score reaches ts
+    int32_t lo = -kKnnBytesMaxDot, hi = kKnnBytesMaxDot;
+    if (!(knn_byte_score(sim, dim, hi, 0, 0) * boost >= ts)) return none;
+    while (lo < hi) {
+      const int32_t mid = lo + ((hi - lo) >> 1);
+      if (knn_byte_score(sim, dim, mid, 0, 0) * boost >= ts) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+  }
+  int32_t lo = 0, hi = 1 << 28;   // the largest squared distance whose score reaches ts (knn_byte_score(2, ., 0, d2, 0): d2 = nq + 0 - 0)
+  if (!(knn_byte_score(2, dim, 0, lo, 0) * boost >= ts)) return none;
+  while (lo < hi) {
+    const int32_t mid = lo + ((hi - lo + 1) >> 1);
+    if (knn_byte_score(2, dim, 0, mid, 0) * boost >= ts) lo = mid; else hi = mid - 1;
+  }
+  return lo - nq;
+}
+
+// Scores the global tiles [tile_begin, tile_end) of the call's leaves against <= 16 P queries; rows whose key beats theta[q] are
+// appended to query q's candidate list (knn.hip: knn_score_kernel's contract: `cap` keys per list, cand_cnt may exceed cap =>
+// overflow, the host redoes; a query without a theta gives every padded row of the launch its own slot of the list unless
+// append_only).  `steps` = resident dimension / 64, a multiple of D (the ring's depth; launch_knn_bytes picks it).
+//   panel  : [steps][P][64] 16-byte operands: step s, panel p, lane l -> q[(l & 15) + 16p][64s + 16(l >> 4) .. +15] (the host stages it)
+//   qnorm2 : |q|^2 per query; dim_user: the field's own dimension (dot_product's divisor)
+//   min_score > 0: rows whose UNBOOSTED score is below it are no hits (the knn request path, which passes boost = 1)
+// C/D layout of the instruction: query col = lane & 15 (+ 16p), row in tile = 4 (lane >> 4) + reg.
+template <int P, int D>
+__global__ __launch_bounds__(kKnnBytesThreads, 1)
+void knn_bytes_kernel(const DKnnBytesLeaf* __restrict__ leaves, int32_t n_leaves, int32_t steps, int32_t dim_user, int64_t tile_begin,
+                      int64_t tile_end, const i32x4* __restrict__ panel, const int32_t* __restrict__ qnorm2, int32_t n_q, int32_t sim,
+                      float boost, float min_score, const unsigned long long* __restrict__ theta, uint64_t* __restrict__ cand,
+                      uint32_t* __restrict__ cand_cnt, uint32_t cap, int32_t append_only, uint32_t qcap) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  i32x4* qs = (i32x4*)smem;
+  // behind the panel: the workgroup's queue of rows that passed (score bits << 32 | padded row << 6 | query), written out once when
+  // the workgroup has streamed its rows -- a global atomic in the tile epilogue would have the wave wait for its whole ring
+  uint32_t* const q_n = (uint32_t*)(smem + (size_t)steps * P * 1024);
+  uint64_t* const q_e = (uint64_t*)(smem + (size_t)steps * P * 1024 + 16);
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  __shared__ int32_t kb_nq[64], kb_thr[64];
+  __shared__ float kb_thhi[64];
+  __shared__ unsigned long long kb_th[64];
+  static_assert(4 * 64 * 3 + 8 * 64 == kKnnBytesStaticLds, "launch_knn_bytes sizes the queue by this");
+  if (tid == 0) *q_n = 0u;
+  if (tid < 64u) {
+    const int32_t q = (int32_t)tid;
+    const unsigned long long th_q = q < n_q ? theta[q] : ~0ull;
+    const int32_t nq_q = q < n_q ? qnorm2[q] : 0;
+    kb_nq[q] = nq_q;
+    kb_th[q] = th_q;
+    kb_thr[q] = knn_bytes_threshold(sim, dim_user, nq_q, th_q, boost, q < n_q);
+    // a key above theta carries a score >= theta's (equal scores: the docid decides): rows strictly below are rejected on the
+    // score alone (theta = ~0 is a NaN score: every compare with it is false)
+    const uint32_t tsb = __float_as_uint(key_score(th_q));
+    kb_thhi[q] = tsb ? __uint_as_float(tsb - 1u) : -1.0f;
+  }
+  for (int32_t i = (int32_t)tid; i < steps * P * 64; i += kKnnBytesThreads) qs[i] = panel[i];
+  __syncthreads();
+  const uint32_t j = lane & 15u, kk = lane >> 4;
+  int32_t thr[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) thr[p] = kb_thr[j + 16u * (uint32_t)p];
+  auto may_pass = [&](int p, int32_t dot, int32_t nv, float rn) -> bool {   // (sim is uniform)
+    if (sim == 0) return !((float)dot * rn <= __uint_as_float((uint32_t)thr[p]));
+    if (sim == 2) return nv - 2 * dot <= thr[p];
+    return dot >= thr[p];
+  };
+  const int64_t padded_rows = (tile_end - tile_begin) << 4;   // of this launch
+  // a contiguous run of tiles per wave: one sequential stream of 1 KiB pieces per leaf it crosses
+  const int64_t n_tiles = tile_end - tile_begin;
+  const int64_t n_waves = (int64_t)gridDim.x * (kKnnBytesThreads / 64), w = (int64_t)blockIdx.x * (kKnnBytesThreads / 64) + wave;
+  int64_t t_run = tile_begin + n_tiles * w / n_waves;
+  const int64_t t_run_end = tile_begin + n_tiles * (w + 1) / n_waves;
+  int32_t li = t_run < t_run_end ? kb_leaf_of_tile(leaves, n_leaves, t_run) : 0;
+  while (t_run < t_run_end) {   // (a wave without tiles still meets the others at the queue's barrier)
+    const DKnnBytesLeaf& lf = leaves[li];
+    const uint64_t u_tiles = kb_uniform_u64((uint64_t)lf.tiles), u_norms = kb_uniform_u64((uint64_t)lf.vnorm2);
+    const uint64_t u_o2d = kb_uniform_u64((uint64_t)lf.ord_to_doc), u_accept = kb_uniform_u64((uint64_t)lf.accept);
+    const int64_t leaf_t0 = (int64_t)kb_uniform_u64((uint64_t)lf.tile_begin);
+    const int32_t leaf_rows = __builtin_amdgcn_readfirstlane(lf.n_rows), doc_base = __builtin_amdgcn_readfirstlane(lf.doc_base);
+    const int32_t* const ord_to_doc = (const int32_t*)u_o2d;
+    const uint64_t* const live_bits = (const uint64_t*)u_accept;
+    // the norms through the SCALAR cache (constant address space: s_load, counted by lgkmcnt, not by the ring's vmcnt)
+    typedef const int32_t __attribute__((address_space(4))) cint_k;
+    cint_k* const vnorm2 = (cint_k*)u_norms;
+    const int64_t t0 = t_run - leaf_t0, t1 = min(t_run_end, leaf_t0 + (((int64_t)leaf_rows + 15) >> 4)) - leaf_t0;   // local tiles
+    // the run as groups of D pieces (a tile is steps / D whole groups): ring slot i holds piece i of the current group, and the
+    // same slot of the NEXT group is requested the moment slot i has been consumed
+    const i32x4* cur = (const i32x4*)u_tiles + (t0 * steps) * 64 + lane;
+    const i32x4* const last_group = cur + ((t1 - t0) * steps - D) * 64;
+    i32x4 abuf[D];
+    kb_fill<D, 0>(abuf, cur);
+    for (int64_t tile = t0; tile < t1; ++tile) {
+      const uint32_t t_lo = __builtin_amdgcn_readfirstlane((uint32_t)(tile & 0xFFFFFFFFll));
+      const uint32_t t_hi = __builtin_amdgcn_readfirstlane((uint32_t)(tile >> 32));
+      const int64_t u_r0 = (int64_t)(((uint64_t)t_hi << 32) | t_lo) << 4;
+      int32_t nvt[16];
+#pragma unroll
+      for (int c = 0; c < 16; ++c) nvt[c] = vnorm2[u_r0 + c];
+      i32x4 acc[P];
+#pragma unroll
+      for (int p = 0; p < P; ++p) acc[p] = i32x4{0, 0, 0, 0};
+      for (int32_t s0 = 0; s0 < steps; s0 += D) {
+        const i32x4* nxt = cur < last_group ? cur + D * 64 : cur;   // (past the run's end: its last group again, never used)
+        kb_steps<P, D, 0>(abuf, acc, qs + (size_t)s0 * P * 64 + lane, nxt);
+        cur = nxt;
+      }
+      int32_t nv4[4];
+      float rn4[4];
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        nv4[reg] = kk == 0 ? nvt[reg] : kk == 1 ? nvt[4 + reg] : kk == 2 ? nvt[8 + reg] : nvt[12 + reg];
+        rn4[reg] = sim == 0 ? __builtin_amdgcn_rsqf((float)nv4[reg]) : 0.0f;
+      }
+      const int64_t r0 = tile << 4;                                   // the tile's first row in its leaf
+      const int64_t g0 = (leaf_t0 + tile - tile_begin) << 4;          // ... and its padded position in this launch
+      bool maybe = false;
+#pragma unroll
+      for (int p = 0; p < P; ++p)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) maybe |= may_pass(p, acc[p][reg], nv4[reg], rn4[reg]);
+      if (maybe)
+#pragma unroll
+      for (int p = 0; p < P; ++p) {
+        const int32_t q = (int32_t)j + 16 * p;
+        if (q < n_q) {
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg) {
+            if (!may_pass(p, acc[p][reg], nv4[reg], rn4[reg])) continue;
+            const int32_t nq_p = kb_nq[q];
+            const unsigned long long th_p = kb_th[q];
+            const float th_hi_p = kb_thhi[q];
+            const bool slot_round = th_p == 0ull && !append_only;   // no theta yet: every padded row owns a slot
+            uint32_t qv = (uint32_t)q;
+            asm volatile("" : "+v"(qv));   // (the list's address is computed where a row is written, not hoisted out of the stream)
+            const int64_t drow = r0 + 4 * (int32_t)kk + reg;
+            const int64_t gpos = g0 + 4 * (int32_t)kk + reg;
+            bool valid = drow < (int64_t)leaf_rows;
+            float sc = 0.f;
+            if (valid) {
+              const float s = knn_byte_score(sim, dim_user, acc[p][reg], nq_p, nv4[reg]);
+              if (min_score > 0.0f && !(s >= min_score)) valid = false;
+              sc = s * boost;
+            }
+            if (slot_round || (valid && sc > th_hi_p)) {
+              uint32_t qi = 0xFFFFFFFFu;
+              if (!slot_round) qi = atomicAdd(q_n, 1u);
+              if (qi < qcap) {
+                q_e[qi] = ((uint64_t)__float_as_uint(sc) << 32) | ((uint64_t)gpos << 6) | (uint64_t)q;
+              } else {   // the first round's slots (a padding row's holds "nothing"), or a full queue: straight to the list
+                uint64_t key = 0;  // 0 = "nothing": never above a theta
+                if (valid) {
+                  const int32_t ldoc = ord_to_doc ? ord_to_doc[drow] : (int32_t)drow;
+                  bool live = true;
+                  if (live_bits) live = (live_bits[ldoc >> 6] >> (ldoc & 63)) & 1ull;
+                  if (live) key = pack_key(sc, (uint32_t)(doc_base + ldoc));
+                }
+                if (slot_round) {
+                  if ((uint64_t)gpos < (uint64_t)cap) cand[(size_t)qv * cap + (size_t)gpos] = key;
+                  if (gpos == padded_rows - 1) cand_cnt[qv] = (uint32_t)min<int64_t>(padded_rows, (int64_t)0xFFFFFFFFll);
+                } else if (key > th_p) {
+                  const uint32_t pos = atomicAdd(&cand_cnt[qv], 1u);
+                  if (pos < cap) cand[(size_t)qv * cap + pos] = key;
+                }
+                // (its loads and stores are complete here as far as the compiler's bookkeeping goes: with vector memory events
+                // pending at the next tile's loop it would wait vmcnt(0) in front of it -- the ring with them)
+                __builtin_amdgcn_s_waitcnt(0x0F70);
+              }
+            }
+          }
+        }
+      }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the ring's last requests (never used) land before the registers are reused
+    t_run = leaf_t0 + t1;
+    ++li;
+  }
+  __syncthreads();
+  // The queue goes out: a row's place in its query's list comes from the list's counter in global memory -- ONE atomic per
+  // (workgroup, query).  A thread keeps its (<= kFlushPerThread) entries in registers between the count and the write.
+  constexpr int kFlushPerThread = 4;   // qcap <= 4096 = 4 x kKnnBytesThreads (launch_knn_bytes)
+  static_assert(kFlushPerThread * kKnnBytesThreads >= 4096, "the queue's capacity is bounded by what the flush holds in registers");
+  const uint32_t n_queued = min(*q_n, qcap);
+  uint32_t* const f_cnt = (uint32_t*)kb_nq;    // (the per-query tables are done with: their LDS holds the counts and the bases)
+  uint32_t* const f_base = (uint32_t*)kb_thr;
+  __syncthreads();
+  if (tid < 64u) f_cnt[tid] = 0u;
+  __syncthreads();
+  uint64_t my_key[kFlushPerThread];
+  uint32_t my_q[kFlushPerThread], my_rank[kFlushPerThread];
+#pragma unroll
+  for (int r = 0; r < kFlushPerThread; ++r) {
+    const uint32_t i = tid + (uint32_t)r * kKnnBytesThreads;
+    my_q[r] = 0xFFFFFFFFu;
+    my_key[r] = 0ull;
+    my_rank[r] = 0u;
+    if (i < n_queued) {
+      const uint64_t e = q_e[i];
+      const uint32_t q = (uint32_t)(e & 63ull);
+      const int64_t gpos = (int64_t)((e >> 6) & 0x3FFFFFFull);
+      const int64_t tile = tile_begin + (gpos >> 4);
+      const DKnnBytesLeaf lf = leaves[kb_leaf_of_tile(leaves, n_leaves, tile)];
+      const int64_t drow = ((tile - lf.tile_begin) << 4) + (gpos & 15);
+      const int32_t ldoc = lf.ord_to_doc ? lf.ord_to_doc[drow] : (int32_t)drow;
+      bool live = true;
+      if (lf.accept) live = (lf.accept[ldoc >> 6] >> (ldoc & 63)) & 1ull;
+      const uint64_t key = pack_key(__uint_as_float((uint32_t)(e >> 32)), (uint32_t)(lf.doc_base + ldoc));
+      if (live && key > theta[q]) {
+        my_q[r] = q;
+        my_key[r] = key;
+        my_rank[r] = atomicAdd(&f_cnt[q], 1u);
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < 64u) {
+    const uint32_t c = f_cnt[tid];
+    f_base[tid] = c ? atomicAdd(&cand_cnt[tid], c) : 0u;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < kFlushPerThread; ++r)
+    if (my_q[r] != 0xFFFFFFFFu) {
+      const uint32_t pos = f_base[my_q[r]] + my_rank[r];
+      if (pos < cap) cand[(size_t)my_q[r] * cap + pos] = my_key[r];
+    }
+}
+
+// ---- launchers ------------------------------------------------------------------------------------
+// Steps (64 dimensions each) a row is resident with, and the ring's depth: the depth must divide the steps (the ring is indexed
+// statically and the epilogue stands once per tile).  Up to 8 steps the ring holds a whole tile; beyond, the steps are padded
+// (with zeros) to the next count that has a divisor in 4 .. 8: 9 -> 10 (dimensions 513-576: 11 % more bytes stored and streamed, the worst case),
+// 11 -> 12, 13 -> 14, 17 -> 18, 19 -> 20, 22 / 23 -> 24, 26 / 27 -> 28, 29 -> 30, 31 -> 32.
+static int32_t knn_bytes_depth_of(int32_t steps) {
+  if (steps <= 8) return steps;
+  for (int32_t d = 8; d >= 4; --d)
+    if (steps % d == 0) return d;
+  return 0;
+}
+int32_t knn_bytes_steps(int32_t dim) {
+  int32_t steps = std::max((dim + 63) >> 6, 1);
+  while (knn_bytes_depth_of(steps) == 0) ++steps;
+  return steps;
+}
+size_t knn_bytes_tile_bytes(int32_t dim, int64_t n) { return (size_t)((n + 15) >> 4) * (size_t)knn_bytes_steps(dim) * 1024; }
+size_t knn_bytes_panel_bytes(int32_t dim, int32_t n_q) { return (size_t)knn_bytes_steps(dim) * (size_t)(n_q > 16 ? 4 : 1) * 1024; }
+
+void launch_knn_bytes_pack(hipStream_t st, const int8_t* rows, int32_t dim, int64_t row0, int64_t n_chunk, void* tiles, int32_t* norm2) {
+  if (n_chunk <= 0) return;
+  const int32_t steps = knn_bytes_steps(dim);
+  const int64_t pieces = ((n_chunk + 15) >> 4) * steps * 64;
+  hipLaunchKernelGGL(knn_bytes_pack_kernel, dim3((uint32_t)((pieces + 255) / 256)), dim3(256), 0, st, rows, dim, row0, n_chunk, steps,
+                     (i32x4*)tiles, norm2);
+}
+
+int launch_knn_bytes(hipStream_t st, uint32_t blocks, const DKnnBytesLeaf* leaves, int32_t n_leaves, int32_t dim, int64_t tile_begin,
+                     int64_t tile_end, const void* panel, const int32_t* qnorm2, int32_t n_q, int32_t sim, float boost, float min_score,
+                     const unsigned long long* theta, uint64_t* cand, uint32_t* cand_cnt, uint32_t cap, int32_t append_only) {
+  if (tile_end <= tile_begin || n_leaves <= 0) return 0;
+  if (n_q < 1 || n_q > 64 || dim < 1 || dim > 2048) return (int)hipErrorInvalidValue;
+  const int32_t steps = knn_bytes_steps(dim), depth = knn_bytes_depth_of(steps);
+  const size_t panel_bytes = knn_bytes_panel_bytes(dim, n_q);
+  // the queue behind the panel: what 160 KiB leave next to the panel and the static tables, 4096 entries at most
+  const uint32_t qcap = (uint32_t)std::min<size_t>(4096, (160 * 1024 - kKnnBytesStaticLds - panel_bytes - 16) / 8);
+  const size_t lds = panel_bytes + 16 + (size_t)qcap * 8;
+#define NRT_BYTES_LAUNCH(PANELS, DEPTH)                                                                                            \
+  {                                                                                                                                \
+    hipError_t e = hipFuncSetAttribute((const void*)knn_bytes_kernel<PANELS, DEPTH>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
+                                       (int)lds);                                                                                  \
+    if (e != hipSuccess) return (int)e;                                                                                            \
+    hipLaunchKernelGGL((knn_bytes_kernel<PANELS, DEPTH>), dim3(blocks), dim3(kKnnBytesThreads), lds, st, leaves, n_leaves, steps,  \
+                       dim, tile_begin, tile_end, (const i32x4*)panel, qnorm2, n_q, sim, boost, min_score, theta, cand, cand_cnt,  \
+                       cap, append_only, qcap);                                                                                    \
+  }
+#define NRT_BYTES_DEPTH(PANELS)                          \
+  switch (depth) {                                       \
+    case 1: NRT_BYTES_LAUNCH(PANELS, 1) break;           \
+    case 2: NRT_BYTES_LAUNCH(PANELS, 2) break;           \
+    case 3: NRT_BYTES_LAUNCH(PANELS, 3) break;           \
+    case 4: NRT_BYTES_LAUNCH(PANELS, 4) break;           \
+    case 5: NRT_BYTES_LAUNCH(PANELS, 5) break;           \
+    case 6: NRT_BYTES_LAUNCH(PANELS, 6) break;           \
+    case 7: NRT_BYTES_LAUNCH(PANELS, 7) break;           \
+    default: NRT_BYTES_LAUNCH(PANELS, 8) break;          \
+  }
+  if (n_q <= 16) { NRT_BYTES_DEPTH(1) }
+  else { NRT_BYTES_DEPTH(4) }
+#undef NRT_BYTES_DEPTH
+#undef NRT_BYTES_LAUNCH
+  return 0;
+}
+
+}  // namespace nrtgpu

@@ -3,6 +3,7 @@
 // (item, term) posting columns.  Names follow the reference's domain: leaves/segments, postings,
 // slices (here: items), collectors.
 #pragma once
+#include <math.h>
 #include <stdint.h>
 
 namespace nrtgpu {
@@ -367,6 +368,40 @@ __host__ __device__ inline double knn_estimate_lower(int sim, double s, double e
     return boost / (1.0 + (d2 > 0.0 ? d2 : 0.0) + e_abs + e_rel * (1.0 + d2)) * (1.0 - 1e-6);
   }
   return (s - (e_abs + e_rel * (s < 0.0 ? -s : s))) * (1.0 - 1e-6);
+}
+
+// Byte (int8) vector fields (knn_bytes.hip).  A leaf as knn_bytes_kernel sees it: the rows as tiles of 16 in the operand order of
+// v_mfma_i32_16x16x64_i8 -- tile t, step s (64 dimensions), lane l: 16 bytes = row 16t + (l & 15), dimensions 64s + 16(l >> 4) .. +15;
+// 1 KiB per (tile, step), a leaf's tiles contiguous -- and |v|^2 per row as int32.
+struct alignas(16) DKnnBytesLeaf {
+  const void* tiles;
+  const int32_t* vnorm2;       // allocation padded to whole tiles: a tile's 16 norms are read whole
+  const int32_t* ord_to_doc;   // nullptr: row == docid
+  const uint64_t* accept;      // liveDocs (& filter) bits of the leaf; nullptr: every doc
+  int64_t tile_begin;
+  int32_t n_rows, doc_base;
+  int32_t pad[4];
+};
+static_assert(sizeof(DKnnBytesLeaf) == 64, "DKnnBytesLeaf layout");
+
+// The UNBOOSTED score of one (query, row) pair of a byte vector field from its three integers dot = sum q_i v_i, nq = sum q_i^2,
+// nv = sum v_i^2 -- ByteVectorFieldDef.similarityToScore's four shapes (VectorFieldDef.java:870-881) over what Lucene's
+// VectorSimilarityFunction.compare(byte[], byte[]) hands it [Lucene-recall].  Every operation is one fp32 (cosine: fp64, then one
+// cast) operation rounded once; int -> float conversions round to nearest even.  The ONE statement of it: knn_bytes_kernel and
+// nrtgpu_byte_vector_score both call this function.  dim: the field's own dimension.  A zero vector under cosine scores 0.
+__host__ __device__ inline float knn_byte_score(int sim, int32_t dim, int32_t dot, int32_t nq, int32_t nv) {
+  if (sim == 0) {
+    if (nq == 0 || nv == 0) return 0.0f;
+    const float c = (float)((double)dot / sqrt((double)nq * (double)nv));
+    return (1.0f + c) / 2.0f;
+  }
+  if (sim == 1) return 0.5f + (float)dot / (float)(dim * 32768);
+  if (sim == 2) {
+    const int32_t d2 = nq + nv - 2 * dot;   // == sum (q_i - v_i)^2: < 2^28 at dim <= 2048
+    return 1.0f / (1.0f + (float)d2);
+  }
+  const float x = (float)dot;
+  return x < 0.0f ? 1.0f / (1.0f + -1.0f * x) : x + 1.0f;
 }
 
 __host__ __device__ inline uint64_t pack_key(float score, uint32_t global_doc) {

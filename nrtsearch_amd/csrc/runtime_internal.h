@@ -101,6 +101,14 @@ void launch_hybrid_rescore(hipStream_t st, uint32_t n_queries, const uint64_t* f
                            uint64_t* out_keys, uint32_t* out_counts, uint32_t w_stride, int32_t drop_foreign = 0);
 void launch_hybrid_hits(hipStream_t st, const uint64_t* first_hits, const uint32_t* first_counts, const uint32_t* q_k, int32_t carries,
                         uint64_t* out_hits, uint32_t n);
+// byte (int8) vector fields (knn_bytes.hip)
+int32_t knn_bytes_steps(int32_t dim);                     // 64-dimension steps a row is resident with
+size_t knn_bytes_tile_bytes(int32_t dim, int64_t n);      // the rows of a field in tile order
+size_t knn_bytes_panel_bytes(int32_t dim, int32_t n_q);   // a query panel in operand order: [steps][1 or 4 panels][64 lanes] x 16 bytes
+void launch_knn_bytes_pack(hipStream_t st, const int8_t* rows, int32_t dim, int64_t row0, int64_t n_chunk, void* tiles, int32_t* norm2);
+int launch_knn_bytes(hipStream_t st, uint32_t blocks, const DKnnBytesLeaf* leaves, int32_t n_leaves, int32_t dim, int64_t tile_begin,
+                     int64_t tile_end, const void* panel, const int32_t* qnorm2, int32_t n_q, int32_t sim, float boost, float min_score,
+                     const unsigned long long* theta, uint64_t* cand, uint32_t* cand_cnt, uint32_t cap, int32_t append_only = 0);
 }  // namespace nrtgpu
 
 namespace nrtgpu {
@@ -279,6 +287,12 @@ struct FieldData {
   int sketch_state = -1;                 // 0: to be built by the first exact search over the field (segment.cpp: ensure_vector_sketch), 1: built, -1: never
   float sketch_scale = 1.f;              // the power of two the rows were multiplied by before rounding
   float absmax = 0.f, vnorm2_min = 0.f;  // largest |element|, smallest non-zero |v|^2 (the sketch's error bound)
+  // A byte (int8) vector field (nrtgpu_segment_add_byte_vectors; a field holds float rows or byte rows, never both): the rows as
+  // tiles of 16 in the i8 matrix instruction's operand order, zero-padded to whole 64-dimension steps (knn_bytes.hip), and |v|^2
+  // per row as int32.  n_vec, dim_user, d_ord_to_doc, h_ord_to_doc and live_vec serve both kinds; dim = 64 x the resident steps.
+  bool byte_rows = false;
+  void* d_btiles = nullptr;
+  int32_t* d_bnorm2 = nullptr;
   // rows whose doc is live under the segment's current liveDocs (what an exact vector query matches), counted on first
   // use per liveDocs version
   mutable std::atomic<int64_t> live_vec{-1};
@@ -288,7 +302,7 @@ struct FieldData {
       : d_norms(o.d_norms), max_norm(o.max_norm), dict(o.dict), flat(o.flat), groups(o.groups), d_vectors(o.d_vectors),
         d_vnorm2(o.d_vnorm2), d_ord_to_doc(o.d_ord_to_doc), h_ord_to_doc(o.h_ord_to_doc), dim(o.dim), n_vec(o.n_vec),
         vnorm2_max(o.vnorm2_max), d_sketch(o.d_sketch), sketch_state(o.sketch_state), sketch_scale(o.sketch_scale), absmax(o.absmax),
-        vnorm2_min(o.vnorm2_min) {}
+        vnorm2_min(o.vnorm2_min), byte_rows(o.byte_rows), d_btiles(o.d_btiles), d_bnorm2(o.d_bnorm2) {}
 };
 
 }  // namespace rt

@@ -645,6 +645,11 @@ static int search_hybrid_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, co
     if (!segs[si]) return fail(NRTGPU_ERR_INVALID_ARG, "segment %d is NULL", si);
   std::optional<SegReadLocks> content;   // until this call's kernels have finished (content_held: the caller holds them over both passes)
   if (!content_held) content.emplace(segs, n_segs);
+  for (int si = 0; si < n_segs; ++si) {   // (this entry does not pad its queries through pad_query_vectors, where the other float entries refuse byte fields)
+    auto fit = segs[si]->fields.find(field_id);
+    if (fit != segs[si]->fields.end() && fit->second.byte_rows)
+      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d holds byte (int8) vectors: the hybrid tail rescores float vector fields only", si, field_id);
+  }
   if (int rc = build_plan(ctx, segs, doc_bases, n_segs, queries, n_queries, hp, 1)) return rc;
   const double plan_ms = now_ms() - t0;
   for (int si = 0; si < n_segs; ++si) {

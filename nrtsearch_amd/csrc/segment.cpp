@@ -245,6 +245,7 @@ extern "C" int nrtgpu_segment_add_vectors(nrtgpu_seg* seg, int32_t field_id, int
   if (n > seg->max_doc) return fail(NRTGPU_ERR_INVALID_ARG, "more vectors (%d) than docs (%d)", n, seg->max_doc);
   HIP_TRY(hipSetDevice(seg->ctx->device));
   FieldData& f = seg->fields[field_id];
+  if (f.byte_rows) return fail(NRTGPU_ERR_INVALID_ARG, "field %d holds byte (int8) vectors: float rows cannot be added to it", field_id);
   if (f.d_vectors) return fail(NRTGPU_ERR_STATE, "vectors of field %d already added", field_id);
   // Resident rows are a multiple of 16 elements long (the matrix-core kernels' pieces): a field of another dimension is padded
   // with zeros, which change none of the sums (x + 0 * 0 = x, (q - v)^2 = 0 for a zero pair) -- results are the field's own.
@@ -297,6 +298,74 @@ extern "C" int nrtgpu_segment_add_vectors(nrtgpu_seg* seg, int32_t field_id, int
     f.d_ord_to_doc = (int32_t*)p;
     HIP_TRY(hipMemcpy(f.d_ord_to_doc, ord_to_doc, (size_t)n * 4, hipMemcpyHostToDevice));
     f.h_ord_to_doc.assign(ord_to_doc, ord_to_doc + n);
+  }
+  return NRTGPU_OK;
+}
+
+// Byte (int8) rows of a field (leaf.getByteVectorValues).  The caller's rows are staged on the device a chunk at a time and written
+// from there into the resident format (knn_bytes.hip: knn_bytes_pack_kernel -- tiles of 16 rows in the i8 matrix instruction's
+// operand order, |v|^2 per row): no second copy of the rows stays.
+extern "C" int nrtgpu_segment_add_byte_vectors(nrtgpu_seg* seg, int32_t field_id, int32_t dim, int32_t n, const int32_t* ord_to_doc,
+                                               const int8_t* row_major) {
+  if (!seg) return fail(NRTGPU_ERR_INVALID_ARG, "seg is NULL");
+  if (seg->sealed) return fail(NRTGPU_ERR_STATE, "segment already sealed");
+  if (dim <= 0 || n < 0 || (n > 0 && !row_major)) return fail(NRTGPU_ERR_INVALID_ARG, "bad vector arguments");
+  if (dim > 2048) return fail(NRTGPU_ERR_UNSUPPORTED, "vector dimension %d (device path takes <= 2048)", dim);
+  if (n > seg->max_doc) return fail(NRTGPU_ERR_INVALID_ARG, "more vectors (%d) than docs (%d)", n, seg->max_doc);
+  if (ord_to_doc)
+    for (int32_t i = 0; i < n; ++i)
+      if (ord_to_doc[i] < 0 || ord_to_doc[i] >= seg->max_doc || (i > 0 && ord_to_doc[i] <= ord_to_doc[i - 1]))
+        return fail(NRTGPU_ERR_INVALID_ARG, "ord_to_doc must be strictly ascending docids in [0,max_doc)");
+  HIP_TRY(hipSetDevice(seg->ctx->device));
+  FieldData& f = seg->fields[field_id];
+  if (f.d_vectors || (f.dim > 0 && !f.byte_rows))
+    return fail(NRTGPU_ERR_INVALID_ARG, "field %d holds float (fp32) vectors: byte rows cannot be added to it", field_id);
+  if (f.byte_rows) return fail(NRTGPU_ERR_STATE, "vectors of field %d already added", field_id);
+  // (the field's members are set when everything is resident: a failed upload leaves no half-written byte field behind)
+  const size_t tile_bytes = knn_bytes_tile_bytes(dim, n) + 256;
+  const size_t norm_bytes = (size_t)(((int64_t)n + 15) & ~(int64_t)15) * 4 + 64;   // whole tiles: a tile's 16 norms are read whole
+  const int64_t chunk_rows = std::max<int64_t>(16, (((int64_t)256 << 20) / dim) & ~(int64_t)15);   // 256 MiB of staging at most
+  void *tiles = nullptr, *norms = nullptr, *o2d = nullptr, *stage = nullptr;
+  int rc = NRTGPU_OK;
+  auto upload = [&]() -> int {
+    if (n == 0) return NRTGPU_OK;
+    HIP_TRY(hipMalloc(&tiles, tile_bytes));
+    HIP_TRY(hipMalloc(&norms, norm_bytes));
+    HIP_TRY(hipMemset(norms, 0, norm_bytes));
+    HIP_TRY(hipMalloc(&stage, (size_t)std::min<int64_t>(chunk_rows, n) * (size_t)dim));
+    for (int64_t r0 = 0; r0 < n; r0 += chunk_rows) {
+      const int64_t nc = std::min<int64_t>(chunk_rows, (int64_t)n - r0);
+      HIP_TRY(hipMemcpy(stage, row_major + (size_t)r0 * dim, (size_t)nc * dim, hipMemcpyHostToDevice));
+      launch_knn_bytes_pack(nullptr, (const int8_t*)stage, dim, r0, nc, tiles, (int32_t*)norms);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipDeviceSynchronize());   // (the staging buffer is written again by the next chunk)
+    }
+    if (ord_to_doc) {
+      HIP_TRY(hipMalloc(&o2d, (size_t)n * 4));
+      HIP_TRY(hipMemcpy(o2d, ord_to_doc, (size_t)n * 4, hipMemcpyHostToDevice));
+    }
+    return NRTGPU_OK;
+  };
+  rc = upload();
+  if (stage) (void)hipFree(stage);
+  if (rc) {
+    if (tiles) (void)hipFree(tiles);
+    if (norms) (void)hipFree(norms);
+    if (o2d) (void)hipFree(o2d);
+    return rc;
+  }
+  f.byte_rows = true;
+  f.dim = 64 * knn_bytes_steps(dim);
+  f.dim_user = dim;
+  f.n_vec = n;
+  f.sketch_state = -1;
+  f.d_btiles = tiles;
+  f.d_bnorm2 = (int32_t*)norms;
+  if (n > 0) seg->device_bytes += (int64_t)(tile_bytes + norm_bytes);
+  if (o2d) {
+    f.d_ord_to_doc = (int32_t*)o2d;
+    f.h_ord_to_doc.assign(ord_to_doc, ord_to_doc + n);
+    seg->device_bytes += (int64_t)n * 4;
   }
   return NRTGPU_OK;
 }
@@ -800,6 +869,8 @@ SegCore::~SegCore() {
     if (f.d_vectors) (void)hipFree(f.d_vectors);
     if (f.d_vnorm2) (void)hipFree(f.d_vnorm2);
     if (f.d_sketch) (void)hipFree(f.d_sketch);
+    if (f.d_btiles) (void)hipFree(f.d_btiles);
+    if (f.d_bnorm2) (void)hipFree(f.d_bnorm2);
     if (f.d_ord_to_doc) (void)hipFree(f.d_ord_to_doc);
     for (auto& g : f.groups) {
       if (g.d_docids) (void)hipFree(g.d_docids);

@@ -17,6 +17,9 @@ int nrtgpu::rt::pad_query_vectors(const nrtgpu_seg* const* segs, int32_t n_segs,
   for (int si = 0; si < n_segs; ++si) {
     if (!segs[si]) continue;
     auto fit = segs[si]->fields.find(field_id);
+    if (fit != segs[si]->fields.end() && fit->second.byte_rows)   // (knn_impl, the rescorer and the multi-GPU hybrid tail pad their queries here; nrtgpu_search_hybrid_batch checks for itself: search.cpp)
+      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d holds byte (int8) vectors: search it with nrtgpu_knn_exact_bytes / nrtgpu_knn_search_bytes",
+                  si, field_id);
     if (fit == segs[si]->fields.end() || !fit->second.d_vectors) continue;
     if (fit->second.dim_user != dim_user)
       return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d has dimension %d, query has %d", si, field_id, fit->second.dim_user, dim_user);
@@ -590,7 +593,7 @@ extern "C" int nrtgpu_knn_exact_relation(nrtgpu_ctx* ctx, const nrtgpu_seg* cons
   for (int32_t i = 0; i < n_segs; ++i) {
     if (!segs[i] || !segs[i]->sealed) return fail(NRTGPU_ERR_STATE, "segment %d missing or not sealed", i);
     auto fit = segs[i]->fields.find(field_id);
-    if (fit != segs[i]->fields.end() && fit->second.d_vectors) live[(size_t)i] = live_vector_count(segs[i], fit->second);
+    if (fit != segs[i]->fields.end() && (fit->second.d_vectors || fit->second.d_btiles)) live[(size_t)i] = live_vector_count(segs[i], fit->second);
     all[(size_t)i] = {i, segs[i]->max_doc, segs[i]->max_doc - segs[i]->n_deleted, doc_bases ? doc_bases[i] : base};
     base += segs[i]->max_doc;
   }
