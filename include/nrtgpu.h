@@ -524,8 +524,9 @@ int  nrtgpu_knn_search(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int
  * docs that have a vector, nrtgpu_knn_exact_relation answers for byte fields too, forks share the rows, nrtgpu_get_stats counts
  * the passes in knn_panels / knn_rows / knn_score_launches / knn_score_ms.  A float entry point called on a byte field, and a
  * byte entry point on a float field, return NRTGPU_ERR_INVALID_ARG naming the field's element type.
- * Out of scope for byte fields (all INVALID_ARG by that rule): nrtgpu_knn_exact_coalesced, the nrtgpu_dist_* entries,
- * nrtgpu_rescore_vectors and the hybrid tail; the Java shim does not bind these functions yet.
+ * A byte field as a RESCORER: nrtgpu_rescore_byte_vectors and nrtgpu_search_hybrid_bytes_batch below.
+ * Out of scope for byte fields (all INVALID_ARG by that rule): nrtgpu_knn_exact_coalesced and the nrtgpu_dist_* entries; the Java
+ * shim does not bind the byte functions yet.
  * --------------------------------------------------------------------------------------------- */
 int  nrtgpu_knn_exact_bytes(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
                             int32_t field_id, int32_t sim, const int8_t* queries, int32_t n_queries, int32_t dim, int32_t k,
@@ -537,6 +538,32 @@ int  nrtgpu_knn_search_bytes(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, con
  * nrtgpu_fixed_point_scale: needs no device; it is the very function the kernel compiles.  Writes the UNBOOSTED score; returns 0,
  * or NRTGPU_ERR_INVALID_ARG (sim outside 0..3, dim outside 1..2048, integers `dim` int8 pairs cannot produce). */
 int  nrtgpu_byte_vector_score(int32_t sim, int32_t dim, int32_t dot, int32_t q_norm2, int32_t v_norm2, float* out);
+
+/* QueryRescore (rescore/QueryRescore.java:40-57) with a byte field's exact query (ExactByteVectorQuery, VectorFieldDef.java:842) in
+ * the rescore slot: nrtgpu_rescore_vectors and nrtgpu_search_hybrid_batch (below) over a byte (int8) vector field.  query /
+ * query_vectors: int8, `dim` per query.  The float entries keep refusing byte fields, and these refuse float fields.
+ *   second pass  = (unboosted score of the table above) * boost, a float multiply: the bits nrtgpu_knn_exact_bytes returns for that
+ *                  (query, row, boost); a zero row under cosine scores 0
+ *   combined     = (float)(query_weight * (double)first + rescore_weight * (double)second)
+ *   no vector    : a hit whose leaf lacks the field, or whose doc has no row, keeps (float)(query_weight * first)
+ * Hits are re-sorted by (combined desc, doc asc) and trimmed to `window` (above NRTGPU_MAX_K: clamped, as the float entries do).
+ * The two entries return the same bits: both kernels take the dot product -- an integer, exact in any order -- from one routine.
+ * The rows are read where they lie, in the tiles of the search; a byte field has no second, row-major copy.
+ * NRTGPU_ERR_INVALID_ARG: sim outside 0..3, a zero query under cosine, a query dim other than the field's, a float field (the message
+ * names the element type), a boost that is not finite or < 0, and for nrtgpu_rescore_byte_vectors a hit outside every segment or
+ * a weight that is not finite.  NRTGPU_ERR_UNSUPPORTED: dim > 2048, and for the hybrid entry a negative weight (the combined
+ * scores are ranked on the device as keys that order like non-negative floats; nrtgpu_rescore_byte_vectors sorts on the host and
+ * takes any finite weights).  Everything else of nrtgpu_search_hybrid_bytes_batch -- deadlines, content locks, the speculative
+ * first pass with its re-run of tagged queries, statistics, total_hits and relation of the FIRST pass -- is
+ * nrtgpu_search_hybrid_batch's: one code path. */
+int  nrtgpu_rescore_byte_vectors(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                 int32_t field_id, int32_t sim, const int8_t* query, int32_t dim, float boost,
+                                 const int32_t* docs, const float* first_scores, int32_t n, double query_weight,
+                                 double rescore_weight, int32_t window, nrtgpu_topdocs* out);
+int  nrtgpu_search_hybrid_bytes_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                      const nrtgpu_bm25_query* queries, int32_t n_queries, int32_t field_id, int32_t sim,
+                                      const int8_t* query_vectors /* n_queries * dim */, int32_t dim, float boost,
+                                      double query_weight, double rescore_weight, int32_t window, nrtgpu_topdocs* out /* n_queries */);
 
 /* Vector rescorer: RescoreOperation.rescore(hits, ctx) of a QueryRescore whose rescoreQuery is an exact
  * vector query (src/main/java/com/yelp/nrtsearch/server/rescore/QueryRescore.java:40-57): every

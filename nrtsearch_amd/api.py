@@ -760,7 +760,20 @@ class GpuIndexSearcher:
                         query_weight: float = 1.0, rescore_weight: float = 1.0, boost: float = 1.0) -> TopDocs:
         """RescoreOperation.rescore with a QueryRescore whose rescoreQuery is an exact vector query
         (S/rescore/QueryRescore.java:40-57)."""
-        query = np.ascontiguousarray(query, dtype=np.float32)
+        return self._rescore("nrtgpu_rescore_vectors", hits, field, self.SIMILARITY[similarity],
+                             np.ascontiguousarray(query, dtype=np.float32), window, query_weight, rescore_weight, boost)
+
+    def rescore_byte_vectors(self, hits: TopDocs, field: int, similarity: str, query: np.ndarray, window: int,
+                             query_weight: float = 1.0, rescore_weight: float = 1.0, boost: float = 1.0) -> TopDocs:
+        """The same over a byte vector field (the rescoreQuery is an ExactByteVectorQuery); query: int8."""
+        sim = self._byte_similarity(similarity)
+        query = _int8_rows(query, "query")
+        if query.shape[0] != 1:
+            raise ValueError("one query vector")
+        return self._rescore("nrtgpu_rescore_byte_vectors", hits, field, sim, query[0], window, query_weight, rescore_weight, boost)
+
+    def _rescore(self, entry: str, hits: TopDocs, field: int, sim: int, query: np.ndarray, window: int, query_weight: float,
+                 rescore_weight: float, boost: float) -> TopDocs:
         d = np.ascontiguousarray(hits.docs, dtype=np.int32)
         s = np.ascontiguousarray(hits.scores, dtype=np.float32)
         out = _lib.TopDocs()
@@ -769,19 +782,28 @@ class GpuIndexSearcher:
         out.capacity = window
         out.docs = od.ctypes.data_as(C.POINTER(C.c_int32))
         out.scores = os_.ctypes.data_as(C.POINTER(C.c_float))
-        _lib.check(_lib.load().nrtgpu_rescore_vectors(self.ctx._h, self._segs, self._bases, len(self.leaves), int(field),
-                                                      self.SIMILARITY[similarity], query.ctypes.data, len(query),
-                                                      C.c_float(boost), d.ctypes.data, s.ctypes.data, len(d),
-                                                      float(query_weight), float(rescore_weight), int(window),
-                                                      C.byref(out)))
+        _lib.check(getattr(_lib.load(), entry)(self.ctx._h, self._segs, self._bases, len(self.leaves), int(field), sim,
+                                               query.ctypes.data, len(query), C.c_float(boost), d.ctypes.data, s.ctypes.data, len(d),
+                                               float(query_weight), float(rescore_weight), int(window), C.byref(out)))
         return TopDocs(od[: out.n_hits].copy(), os_[: out.n_hits].copy(), hits.total_hits, hits.relation_gte)
 
     def search_hybrid_batch(self, queries: Sequence[Query], managers: Sequence[TopScoreDocCollectorManager], field: int,
                             similarity: str, query_vectors: np.ndarray, window: int, query_weight: float = 1.0,
                             rescore_weight: float = 1.0, boost: float = 1.0) -> List[TopDocs]:
         """search() followed by the vector rescorer for every query, fused on the device (config C5)."""
+        return self._hybrid("nrtgpu_search_hybrid_batch", queries, managers, field, self.SIMILARITY[similarity],
+                            np.ascontiguousarray(np.atleast_2d(query_vectors), dtype=np.float32), window, query_weight, rescore_weight, boost)
+
+    def search_hybrid_bytes_batch(self, queries: Sequence[Query], managers: Sequence[TopScoreDocCollectorManager], field: int,
+                                  similarity: str, query_vectors: np.ndarray, window: int, query_weight: float = 1.0,
+                                  rescore_weight: float = 1.0, boost: float = 1.0) -> List[TopDocs]:
+        """The same with a byte vector field as the rescorer (search() + rescore_byte_vectors per query); query_vectors: int8."""
+        return self._hybrid("nrtgpu_search_hybrid_bytes_batch", queries, managers, field, self._byte_similarity(similarity),
+                            _int8_rows(query_vectors, "query vectors"), window, query_weight, rescore_weight, boost)
+
+    def _hybrid(self, entry: str, queries: Sequence[Query], managers: Sequence[TopScoreDocCollectorManager], field: int, sim: int,
+                qv: np.ndarray, window: int, query_weight: float, rescore_weight: float, boost: float) -> List[TopDocs]:
         n = len(queries)
-        qv = np.ascontiguousarray(np.atleast_2d(query_vectors), dtype=np.float32)
         if qv.shape[0] != n:
             raise ValueError("one query vector per query")
         m = self._marshal(queries, managers)
@@ -795,11 +817,10 @@ class GpuIndexSearcher:
                 outs[qi].capacity = window
                 outs[qi].docs = docs[qi].ctypes.data_as(C.POINTER(C.c_int32))
                 outs[qi].scores = scores[qi].ctypes.data_as(C.POINTER(C.c_float))
-        _lib.check(_lib.load().nrtgpu_search_hybrid_batch(
-            self.ctx._h, self._segs, self._bases, len(self.leaves), m.queries, n, int(field), self.SIMILARITY[similarity],
+        _lib.check(getattr(_lib.load(), entry)(
+            self.ctx._h, self._segs, self._bases, len(self.leaves), m.queries, n, int(field), sim,
             qv.ctypes.data, qv.shape[1], C.c_float(boost), float(query_weight), float(rescore_weight), int(window), outs))
         return _topdocs_lists(outs, docs, scores, n)
-
 
     def dist_search_hybrid_batch(self, queries: Sequence[Query], managers: Sequence[TopScoreDocCollectorManager], field: int,
                                  similarity: str, query_vectors: np.ndarray, window: int, query_weight: float = 1.0,

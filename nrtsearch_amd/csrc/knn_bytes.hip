@@ -17,6 +17,7 @@
 #include <algorithm>
 
 #include "plan.h"
+#include "topk.hiph"
 
 namespace nrtgpu {
 
@@ -356,6 +357,181 @@ void knn_bytes_kernel(const DKnnBytesLeaf* __restrict__ leaves, int32_t n_leaves
     }
 }
 
+// ---- the RESCORER over a byte field (QueryRescore with an ExactByteVectorQuery in the rescore slot) -------------------------
+// A first-pass hit names ONE row, and the rows have one copy: the tiles above.  Row r is not contiguous there -- it is the 16-byte
+// PIECES (s, kk), s < steps, kk < 4 (dimensions 64s + 16kk .. +15), at
+//   tiles[((r >> 4) * steps + s) * 64 + kk * 16 + (r & 15)]
+// that is piece p = 4s + kk (dimensions 16p .. 16p + 15) at 16 p operands = 256 p bytes behind the row's BASE
+// tiles + (r >> 4) * steps * 64 + (r & 15): a walk at a fixed stride.  The query is kept in the same piece order, which is the
+// query itself, zero-padded to whole pieces.
+constexpr int kByteRescoreRows = 8;   // hits a wave scores side by side: one or two 16-byte loads per row and lane, all in flight together
+// The dot products of R rows (bases as above, wave-uniform; nullptr: no row) with the query in LDS.  Lane l takes pieces l and
+// l + 64 of every row (dimension 768: 48 lanes, one load per row; 2048: two); only pieces that hold dimensions of the field are
+// read (n_pieces = ceil(dim / 16) <= 128).  Products through the packed int8 dot instruction, then an integer butterfly: the
+// integers are exact in any order, so every caller gets the same numbers -- the ONE routine of both rescore kernels.
+template <int R>
+__device__ __forceinline__ void kb_rows_dot(const i32x4* const (&rows)[R], const i32x4* q_lds, int32_t n_pieces, uint32_t lane,
+                                            int32_t (&dot)[R]) {
+  // (the bases come out of LDS or are computed from a kernel argument: say that they are global memory)
+  typedef const __attribute__((address_space(1))) i32x4* gpiece_ptr;
+  const bool p0 = (int32_t)lane < n_pieces, p1 = (int32_t)lane + 64 < n_pieces;
+  const i32x4 zero = i32x4{0, 0, 0, 0};
+  i32x4 x0[R], x1[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) x0[r] = (rows[r] && p0) ? ((gpiece_ptr)rows[r])[16u * lane] : zero;   // (rows[r]: wave-uniform)
+#pragma unroll
+  for (int r = 0; r < R; ++r) x1[r] = zero;
+  if (n_pieces > 64) {
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+      if (rows[r] && p1) x1[r] = ((gpiece_ptr)rows[r])[16u * (lane + 64u)];
+  }
+  const i32x4 q0 = p0 ? q_lds[lane] : zero, q1 = p1 ? q_lds[lane + 64u] : zero;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    int32_t a = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) a = __builtin_amdgcn_sdot4(x0[r][w], q0[w], a, false);
+#pragma unroll
+    for (int w = 0; w < 4; ++w) a = __builtin_amdgcn_sdot4(x1[r][w], q1[w], a, false);
+    dot[r] = a;
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) dot[r] += __shfl_xor(dot[r], d, 64);
+}
+__device__ __forceinline__ const i32x4* kb_uniform_row(const i32x4* p) {   // a pointer every lane holds, as scalars
+  return (const i32x4*)(uintptr_t)kb_uniform_u64((uint64_t)(uintptr_t)p);
+}
+// QueryRescore.combine over the byte scorer: second = knn_byte_score(...) * boost -- what knn_bytes_kernel returns for the
+// (query, row, boost) -- and (float)(qw * first + rw * second) in double; a hit without a row keeps (float)(qw * first).
+__device__ __forceinline__ float kb_combined(bool has_row, int sim, int32_t dim, int32_t dot, int32_t nq, int32_t nv, float boost,
+                                             float first, double qw, double rw) {
+  if (!has_row) return (float)(qw * (double)first);
+  const float second = knn_byte_score(sim, dim, dot, nq, nv) * boost;
+  return (float)(qw * (double)first + rw * (double)second);
+}
+
+// One wave per kByteRescoreRows hits of one leaf; vec_row[i] = the hit's row in the leaf's field (< 0: no vector), given by the
+// host as for rescore_vectors_kernel (knn.hip).  query: the query in piece order, 64 `steps` bytes.
+__global__ __launch_bounds__(256)
+void rescore_byte_vectors_kernel(const i32x4* __restrict__ tiles, const int32_t* __restrict__ vnorm2, int32_t steps, int32_t dim,
+                                 const i32x4* __restrict__ query, int32_t qnorm2, int32_t sim, float boost,
+                                 const int64_t* __restrict__ vec_row, const float* __restrict__ first_scores, int32_t n, double qw,
+                                 double rw, float* __restrict__ out_scores) {
+  __shared__ i32x4 qs[128];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const int32_t n_pieces = (dim + 15) >> 4;
+  if ((int32_t)tid < n_pieces) qs[tid] = query[tid];
+  __syncthreads();
+  const int32_t i0 = (int32_t)(blockIdx.x * 4u + wave) * kByteRescoreRows;
+  if (i0 >= n) return;
+  const i32x4* rows[kByteRescoreRows];
+#pragma unroll
+  for (int r = 0; r < kByteRescoreRows; ++r) {
+    const int64_t row = i0 + r < n ? vec_row[i0 + r] : -1;
+    rows[r] = kb_uniform_row(row >= 0 ? tiles + (row >> 4) * steps * 64 + (row & 15) : nullptr);
+  }
+  int32_t dot[kByteRescoreRows];
+  kb_rows_dot<kByteRescoreRows>(rows, qs, n_pieces, lane, dot);
+  // lane r finishes hit r (every lane holds every sum)
+  int32_t my_dot = 0;
+#pragma unroll
+  for (int r = 0; r < kByteRescoreRows; ++r)
+    if (lane == (uint32_t)r) my_dot = dot[r];
+  const int32_t i = i0 + (int32_t)lane;
+  if (lane < (uint32_t)kByteRescoreRows && i < n) {
+    const int64_t row = vec_row[i];
+    out_scores[i] = kb_combined(row >= 0, sim, dim, my_dot, qnorm2, row >= 0 ? vnorm2[row] : 0, boost, first_scores[i], qw, rw);
+  }
+}
+
+// The hybrid tail over a byte field: hybrid_rescore_kernel's two phases (knn.hip) -- one workgroup per query over its sorted
+// first-pass hits in HBM --
+//   1. a THREAD per hit: key -> (leaf, row) -> the row's base in the tiles and its norm into LDS -- every hit's chain at once;
+//   2. a wave per kByteRescoreRows hits: kb_rows_dot, then a lane per hit for the score and QueryRescore.combine,
+// then QueryRescorer's sort (combined score desc, doc asc) in LDS and the window.  qvecs: the queries in piece order, 64 `steps`
+// bytes each.
+constexpr int kHybridBytesThreads = 1024;
+__global__ __launch_bounds__(kHybridBytesThreads)
+void hybrid_rescore_bytes_kernel(const uint64_t* __restrict__ first_keys, const uint32_t* __restrict__ first_counts, uint32_t k_stride,
+                                 const DByteVecSeg* __restrict__ segs, int32_t n_segs, int32_t steps, int32_t dim,
+                                 const i32x4* __restrict__ qvecs, const int32_t* __restrict__ qnorm2, int32_t sim, float boost, double qw,
+                                 double rw, uint32_t window, uint64_t* __restrict__ out_keys, uint32_t* __restrict__ out_counts,
+                                 uint32_t w_stride) {
+  __shared__ uint64_t cand[1024];        // phase 1: the first-pass keys; phase 2: the combined keys
+  __shared__ const i32x4* h_row[1024];   // the hit's row base (nullptr: the doc has no vector)
+  __shared__ int32_t h_nv[1024];
+  __shared__ i32x4 qs[128];
+  const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint32_t n = min(first_counts[q], 1024u);
+  const int32_t n_pieces = (dim + 15) >> 4;
+  const int32_t nq = qnorm2[q];
+  if ((int32_t)tid < n_pieces) qs[tid] = qvecs[(size_t)q * (size_t)steps * 4 + tid];
+  for (uint32_t i = tid; i < n; i += (uint32_t)kHybridBytesThreads) {
+    const uint64_t key = first_keys[(size_t)q * k_stride + i];
+    const uint32_t gdoc = 0xFFFFFFFFu - (uint32_t)key;
+    const i32x4* base = nullptr;
+    int32_t nv = 0;
+    for (int32_t si = 0; si < n_segs; ++si) {
+      const DByteVecSeg sg = segs[si];
+      const int64_t local = (int64_t)gdoc - (int64_t)sg.doc_base;
+      if (local < 0 || local >= (int64_t)sg.max_doc) continue;
+      if (sg.tiles) {
+        int64_t row = -1;
+        if (!sg.ord_to_doc) {
+          if (local < (int64_t)sg.n_vec) row = local;
+        } else {  // lower_bound over the leaf's ascending ord -> doc map
+          int32_t lo = 0, hi = sg.n_vec;
+          while (lo < hi) {
+            const int32_t mid = lo + ((hi - lo) >> 1);
+            if (sg.ord_to_doc[mid] < (int32_t)local) lo = mid + 1; else hi = mid;
+          }
+          if (lo < sg.n_vec && sg.ord_to_doc[lo] == (int32_t)local) row = lo;
+        }
+        if (row >= 0) {
+          base = (const i32x4*)sg.tiles + (row >> 4) * steps * 64 + (row & 15);
+          nv = sg.vnorm2[row];
+        }
+      }
+      break;
+    }
+    cand[i] = key;
+    h_row[i] = base;
+    h_nv[i] = nv;
+  }
+  __syncthreads();
+  constexpr uint32_t kWaves = (uint32_t)(kHybridBytesThreads / 64);
+  for (uint32_t i0 = wave; i0 < n; i0 += kWaves * (uint32_t)kByteRescoreRows) {
+    const i32x4* rows[kByteRescoreRows];
+#pragma unroll
+    for (int r = 0; r < kByteRescoreRows; ++r) {
+      const uint32_t idx = i0 + (uint32_t)r * kWaves;
+      rows[r] = kb_uniform_row(idx < n ? h_row[idx] : nullptr);   // (uniform LDS reads)
+    }
+    int32_t dot[kByteRescoreRows];
+    kb_rows_dot<kByteRescoreRows>(rows, qs, n_pieces, lane, dot);
+    int32_t my_dot = 0;
+#pragma unroll
+    for (int r = 0; r < kByteRescoreRows; ++r)
+      if (lane == (uint32_t)r) my_dot = dot[r];
+    const uint32_t idx = i0 + lane * kWaves;   // lane r finishes hit r
+    if (lane < (uint32_t)kByteRescoreRows && idx < n) {
+      const uint64_t key = cand[idx];
+      const float comb = kb_combined(h_row[idx] != nullptr, sim, dim, my_dot, nq, h_nv[idx], boost, key_score(key), qw, rw);
+      cand[idx] = pack_key(comb, 0xFFFFFFFFu - (uint32_t)key);
+    }
+  }
+  uint32_t n2 = 1;
+  while (n2 < n) n2 <<= 1;
+  for (uint32_t i = n + tid; i < n2; i += (uint32_t)kHybridBytesThreads) cand[i] = 0;
+  bitonic_sort_desc<kHybridBytesThreads>(cand, n2);  // starts with a barrier
+  const uint32_t m = min(n, window);
+  for (uint32_t i = tid; i < w_stride; i += (uint32_t)kHybridBytesThreads) out_keys[(size_t)q * w_stride + i] = i < m ? cand[i] : 0;
+  if (tid == 0) out_counts[q] = m;
+}
+
 // ---- launchers ------------------------------------------------------------------------------------
 // Steps (64 dimensions each) a row is resident with, and the ring's depth: the depth must divide the steps (the ring is indexed
 // statically and the epilogue stands once per tile).  Up to 8 steps the ring holds a whole tile; beyond, the steps are padded
@@ -418,6 +594,23 @@ int launch_knn_bytes(hipStream_t st, uint32_t blocks, const DKnnBytesLeaf* leave
 #undef NRT_BYTES_DEPTH
 #undef NRT_BYTES_LAUNCH
   return 0;
+}
+
+void launch_rescore_byte_vectors(hipStream_t st, const void* tiles, const int32_t* vnorm2, int32_t dim, const void* query, int32_t qnorm2,
+                                 int32_t sim, float boost, const int64_t* vec_row, const float* first_scores, int32_t n, double qw, double rw,
+                                 float* out_scores) {
+  if (n <= 0) return;
+  const uint32_t per_block = 4u * (uint32_t)kByteRescoreRows;
+  hipLaunchKernelGGL(rescore_byte_vectors_kernel, dim3(((uint32_t)n + per_block - 1) / per_block), dim3(256), 0, st, (const i32x4*)tiles, vnorm2,
+                     knn_bytes_steps(dim), dim, (const i32x4*)query, qnorm2, sim, boost, vec_row, first_scores, n, qw, rw, out_scores);
+}
+void launch_hybrid_rescore_bytes(hipStream_t st, uint32_t n_queries, const uint64_t* first_keys, const uint32_t* first_counts,
+                                 uint32_t k_stride, const DByteVecSeg* segs, int32_t n_segs, int32_t dim, const void* qvecs,
+                                 const int32_t* qnorm2, int32_t sim, float boost, double qw, double rw, uint32_t window, uint64_t* out_keys,
+                                 uint32_t* out_counts, uint32_t w_stride) {
+  if (n_queries == 0) return;
+  hipLaunchKernelGGL(hybrid_rescore_bytes_kernel, dim3(n_queries), dim3(kHybridBytesThreads), 0, st, first_keys, first_counts, k_stride, segs,
+                     n_segs, knn_bytes_steps(dim), dim, (const i32x4*)qvecs, qnorm2, sim, boost, qw, rw, window, out_keys, out_counts, w_stride);
 }
 
 }  // namespace nrtgpu

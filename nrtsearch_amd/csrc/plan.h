@@ -383,6 +383,15 @@ struct alignas(16) DKnnBytesLeaf {
   int32_t pad[4];
 };
 static_assert(sizeof(DKnnBytesLeaf) == 64, "DKnnBytesLeaf layout");
+// One leaf's byte vector field as the rescorers see it (knn_bytes.hip: hybrid_rescore_bytes_kernel maps a hit's doc to its row on
+// the device, as hybrid_rescore_kernel does through DVecSeg): the same tiles, the only copy of the rows.
+struct DByteVecSeg {
+  const void* tiles;          // nullptr: the leaf has no vectors for the field
+  const int32_t* vnorm2;      // |v|^2 per row
+  const int32_t* ord_to_doc;  // ascending; nullptr: row == docid
+  int32_t doc_base, max_doc, n_vec, pad;
+};
+static_assert(sizeof(DByteVecSeg) == 40, "DByteVecSeg layout");
 
 // The UNBOOSTED score of one (query, row) pair of a byte vector field from its three integers dot = sum q_i v_i, nq = sum q_i^2,
 // nv = sum v_i^2 -- ByteVectorFieldDef.similarityToScore's four shapes (VectorFieldDef.java:870-881) over what Lucene's

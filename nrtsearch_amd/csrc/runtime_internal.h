@@ -109,6 +109,14 @@ void launch_knn_bytes_pack(hipStream_t st, const int8_t* rows, int32_t dim, int6
 int launch_knn_bytes(hipStream_t st, uint32_t blocks, const DKnnBytesLeaf* leaves, int32_t n_leaves, int32_t dim, int64_t tile_begin,
                      int64_t tile_end, const void* panel, const int32_t* qnorm2, int32_t n_q, int32_t sim, float boost, float min_score,
                      const unsigned long long* theta, uint64_t* cand, uint32_t* cand_cnt, uint32_t cap, int32_t append_only = 0);
+// the rescorers over a byte field; query / qvecs: int8 in piece order = the query, zero-padded to 64 * knn_bytes_steps(dim) bytes
+void launch_rescore_byte_vectors(hipStream_t st, const void* tiles, const int32_t* vnorm2, int32_t dim, const void* query, int32_t qnorm2,
+                                 int32_t sim, float boost, const int64_t* vec_row, const float* first_scores, int32_t n, double qw, double rw,
+                                 float* out_scores);
+void launch_hybrid_rescore_bytes(hipStream_t st, uint32_t n_queries, const uint64_t* first_keys, const uint32_t* first_counts,
+                                 uint32_t k_stride, const DByteVecSeg* segs, int32_t n_segs, int32_t dim, const void* qvecs,
+                                 const int32_t* qnorm2, int32_t sim, float boost, double qw, double rw, uint32_t window, uint64_t* out_keys,
+                                 uint32_t* out_counts, uint32_t w_stride);
 }  // namespace nrtgpu
 
 namespace nrtgpu {
@@ -661,6 +669,14 @@ void note_shard_speculation(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int3
 // hit totals), enqueued on `slot`'s stream; the caller synchronises.
 int merge_lists_on_device(nrtgpu_ctx* ctx, Slot* slot, int32_t n_lists, int32_t n_queries, int32_t k_stride, const void* g_keys,
                           const void* g_counts, const void* g_hits, const int32_t* ks, void* d_keys, void* d_counts, void* d_hits);
+// The rescorers over a byte field (vectors_bytes.cpp): what nrtgpu_rescore_byte_vectors and the byte tail of search_hybrid_impl
+// (search.cpp) share -- the refusals of the scalars, the queries in the kernels' piece order with |q|^2 (padded / qnorm2 may be
+// NULL: check only), the field's leaf table (out may be NULL: check only).
+int byte_rescore_check_args(int32_t sim, int32_t dim, float boost, int32_t window);
+size_t byte_query_stride(int32_t dim);
+int byte_queries_stage(const int8_t* queries, int32_t n, int32_t dim, int32_t sim, int8_t* padded, int32_t* qnorm2);
+int byte_rescore_leaves(const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, int32_t field_id, int32_t dim,
+                        DByteVecSeg* out);
 // The vector rescorer over device-resident first-pass lists (hybrid_rescore_kernel), enqueued on `slot`'s stream: uploads the leaf
 // table and the query vectors into the slot's aux buffers; windows -> d_win_keys (n_queries x w_stride), d_win_counts.
 // Query vectors of `dim_user` elements as the resident rows want them: padded with zeros to the field's resident dimension

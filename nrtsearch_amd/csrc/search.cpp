@@ -624,9 +624,13 @@ extern "C" int nrtgpu_debug_spec_counters(nrtgpu_ctx* ctx, int64_t* out3) {
 // the stages (RescoreTask.java:47-50 -> QueryRescore.java:39-57 applied to the hits of
 // SearchHandler.java:1412-1413).  Same results as nrtgpu_search_bm25_batch followed per query by
 // nrtgpu_rescore_vectors.
+// The TAIL stage is the only part that knows the field's element type: `bytes` -- query_vectors are int8, the field holds byte rows,
+// hybrid_rescore_bytes_kernel (knn_bytes.hip) scores them (same results as nrtgpu_rescore_byte_vectors; the entry has refused
+// what the byte scorer does not take) -- else fp32 and hybrid_rescore_kernel.  Planning, first pass, slots, locks, deadlines,
+// speculation tags, the copy back and the accounting are one code path.
 static int search_hybrid_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases,
                               int32_t n_segs, const nrtgpu_bm25_query* queries, int32_t n_queries,
-                              int32_t field_id, int32_t sim, const float* query_vectors, int32_t dim, float boost,
+                              int32_t field_id, int32_t sim, const void* query_vectors, bool bytes, int32_t dim, float boost,
                               double query_weight, double rescore_weight, int32_t window, nrtgpu_topdocs* out, std::vector<int32_t>* rerun,
                               bool content_held = false) {
   forget_foreign_hip_error();
@@ -645,10 +649,14 @@ static int search_hybrid_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, co
     if (!segs[si]) return fail(NRTGPU_ERR_INVALID_ARG, "segment %d is NULL", si);
   std::optional<SegReadLocks> content;   // until this call's kernels have finished (content_held: the caller holds them over both passes)
   if (!content_held) content.emplace(segs, n_segs);
-  for (int si = 0; si < n_segs; ++si) {   // (this entry does not pad its queries through pad_query_vectors, where the other float entries refuse byte fields)
-    auto fit = segs[si]->fields.find(field_id);
-    if (fit != segs[si]->fields.end() && fit->second.byte_rows)
-      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d holds byte (int8) vectors: the hybrid tail rescores float vector fields only", si, field_id);
+  if (bytes) {   // a float field, another dimension: refused before anything is planned
+    if (int rc = byte_rescore_leaves(segs, doc_bases, n_segs, field_id, dim, nullptr)) return rc;
+  } else {
+    for (int si = 0; si < n_segs; ++si) {   // (this entry does not pad its queries through pad_query_vectors, where the other float entries refuse byte fields)
+      auto fit = segs[si]->fields.find(field_id);
+      if (fit != segs[si]->fields.end() && fit->second.byte_rows)
+        return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d holds byte (int8) vectors: the hybrid tail rescores float vector fields only", si, field_id);
+    }
   }
   if (int rc = build_plan(ctx, segs, doc_bases, n_segs, queries, n_queries, hp, 1)) return rc;
   const double plan_ms = now_ms() - t0;
@@ -664,7 +672,9 @@ static int search_hybrid_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, co
   const uint32_t w_stride = round_up((uint32_t)std::min<int32_t>(window, NRTGPU_MAX_K), 16);
   const size_t nq = (size_t)n_queries;
   Carver ac;
-  const size_t o_segs = ac.take((size_t)std::max(n_segs, 1) * sizeof(DVecSeg)), o_qv = ac.take(nq * (size_t)dim * 4),
+  static_assert(sizeof(DByteVecSeg) == sizeof(DVecSeg), "one leaf table slot serves both tails");
+  const size_t qv_bytes = bytes ? nq * byte_query_stride(dim) : nq * (size_t)dim * 4;
+  const size_t o_segs = ac.take((size_t)std::max(n_segs, 1) * sizeof(DVecSeg)), o_qv = ac.take(qv_bytes),
                o_qn = ac.take(nq * 4);
   const size_t in_bytes = ac.off;
   const size_t o_wk = ac.take(nq * w_stride * 8), o_wc = ac.take(nq * 4);
@@ -675,30 +685,37 @@ static int search_hybrid_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, co
   if (int rc = slot->h_aux.reserve(hc.off)) return rc;
   char* ha = (char*)slot->h_aux.p;
   char* da = (char*)slot->d_aux.p;
-  DVecSeg* hs = (DVecSeg*)(ha + oh_in + o_segs);
-  for (int si = 0; si < n_segs; ++si) {
-    DVecSeg v{};
-    auto fit = segs[si]->fields.find(field_id);
-    if (fit != segs[si]->fields.end() && fit->second.d_vectors) {
-      v.vecs = fit->second.d_vectors;
-      v.vnorm2 = fit->second.d_vnorm2;
-      v.ord_to_doc = fit->second.d_ord_to_doc;
-      v.n_vec = fit->second.n_vec;
+  if (bytes) {   // the leaf table, the queries in piece order, |q|^2 as int32 (vectors_bytes.cpp)
+    if (int rc = byte_rescore_leaves(segs, doc_bases, n_segs, field_id, dim, (DByteVecSeg*)(ha + oh_in + o_segs))) return rc;
+    if (int rc = byte_queries_stage((const int8_t*)query_vectors, n_queries, dim, sim, (int8_t*)(ha + oh_in + o_qv), (int32_t*)(ha + oh_in + o_qn)))
+      return rc;
+  } else {
+    DVecSeg* hs = (DVecSeg*)(ha + oh_in + o_segs);
+    for (int si = 0; si < n_segs; ++si) {
+      DVecSeg v{};
+      auto fit = segs[si]->fields.find(field_id);
+      if (fit != segs[si]->fields.end() && fit->second.d_vectors) {
+        v.vecs = fit->second.d_vectors;
+        v.vnorm2 = fit->second.d_vnorm2;
+        v.ord_to_doc = fit->second.d_ord_to_doc;
+        v.n_vec = fit->second.n_vec;
+      }
+      v.doc_base = doc_bases[si];
+      v.max_doc = segs[si]->max_doc;
+      hs[si] = v;
     }
-    v.doc_base = doc_bases[si];
-    v.max_doc = segs[si]->max_doc;
-    hs[si] = v;
-  }
-  memcpy(ha + oh_in + o_qv, query_vectors, nq * (size_t)dim * 4);
-  float* hqn = (float*)(ha + oh_in + o_qn);
-  for (size_t q = 0; q < nq; ++q) {  // |q|^2 in the order nrtgpu_rescore_vectors uses
-    const float* qv = query_vectors + q * (size_t)dim;
-    float qn = 0.f;
-    for (int d = 0; d < dim; ++d) {
-      volatile float p2 = qv[d] * qv[d];
-      qn = qn + p2;
+    const float* fq = (const float*)query_vectors;
+    memcpy(ha + oh_in + o_qv, fq, nq * (size_t)dim * 4);
+    float* hqn = (float*)(ha + oh_in + o_qn);
+    for (size_t q = 0; q < nq; ++q) {  // |q|^2 in the order nrtgpu_rescore_vectors uses
+      const float* qv = fq + q * (size_t)dim;
+      float qn = 0.f;
+      for (int d = 0; d < dim; ++d) {
+        volatile float p2 = qv[d] * qv[d];
+        qn = qn + p2;
+      }
+      hqn[q] = qn;
     }
-    hqn[q] = qn;
   }
   HIP_TRY(hipMemcpyAsync(da, ha + oh_in, in_bytes, hipMemcpyHostToDevice, st));
   DeviceRun run;
@@ -708,9 +725,14 @@ static int search_hybrid_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, co
       (void)hipStreamSynchronize(st);   // the upload of the query vectors reads the slot's pinned buffer: not in flight when the slot is released
       return rc;
     }
-    launch_hybrid_rescore(st, (uint32_t)n_queries, run.out_keys, run.out_counts, hp.k_stride, (const DVecSeg*)(da + o_segs), n_segs,
-                          dim, (const float*)(da + o_qv), (const float*)(da + o_qn), sim, boost, query_weight, rescore_weight,
-                          (uint32_t)window, (uint64_t*)(da + o_wk), (uint32_t*)(da + o_wc), w_stride);
+    if (bytes)
+      launch_hybrid_rescore_bytes(st, (uint32_t)n_queries, run.out_keys, run.out_counts, hp.k_stride, (const DByteVecSeg*)(da + o_segs), n_segs,
+                                  dim, da + o_qv, (const int32_t*)(da + o_qn), sim, boost, query_weight, rescore_weight, (uint32_t)window,
+                                  (uint64_t*)(da + o_wk), (uint32_t*)(da + o_wc), w_stride);
+    else
+      launch_hybrid_rescore(st, (uint32_t)n_queries, run.out_keys, run.out_counts, hp.k_stride, (const DVecSeg*)(da + o_segs), n_segs,
+                            dim, (const float*)(da + o_qv), (const float*)(da + o_qn), sim, boost, query_weight, rescore_weight,
+                            (uint32_t)window, (uint64_t*)(da + o_wk), (uint32_t*)(da + o_wc), w_stride);
     HIP_TRY(hipGetLastError());
   }
   // (the answers behind the kernels on the same stream, ONE wait: see search_batch_impl)
@@ -734,10 +756,10 @@ static int search_hybrid_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, co
   return NRTGPU_OK;
 }
 
-extern "C" int nrtgpu_search_hybrid_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases,
-                                          int32_t n_segs, const nrtgpu_bm25_query* queries, int32_t n_queries,
-                                          int32_t field_id, int32_t sim, const float* query_vectors, int32_t dim, float boost,
-                                          double query_weight, double rescore_weight, int32_t window, nrtgpu_topdocs* out) {
+static int search_hybrid_entry(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                               const nrtgpu_bm25_query* queries, int32_t n_queries, int32_t field_id, int32_t sim, const void* query_vectors,
+                               bool bytes, int32_t dim, float boost, double query_weight, double rescore_weight, int32_t window,
+                               nrtgpu_topdocs* out) {
   // The first pass may run under speculative thresholds (plan.h: kHitsSpecInvalid), as in nrtgpu_search_bm25_batch: recall, tail
   // and the copy back stay one stream with no host round trip; the merge's tags arrive with the results, and a tagged query --
   // its recall set may lack docs -- is run again, first pass and tail, without speculation.
@@ -745,31 +767,54 @@ extern "C" int nrtgpu_search_hybrid_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* con
   std::vector<int32_t> rerun;
   const bool spec = speculating(ctx, segs, n_segs);
   if (!spec)
-    return search_hybrid_impl(ctx, segs, doc_bases, n_segs, queries, n_queries, field_id, sim, query_vectors, dim, boost, query_weight,
+    return search_hybrid_impl(ctx, segs, doc_bases, n_segs, queries, n_queries, field_id, sim, query_vectors, bytes, dim, boost, query_weight,
                               rescore_weight, window, out, nullptr);
   if (ctx && segs)
     for (int si = 0; si < n_segs; ++si)
       if (!segs[si]) return fail(NRTGPU_ERR_INVALID_ARG, "segment %d is NULL", si);
   SegReadLocks content(segs, n_segs);
-  const int rc = search_hybrid_impl(ctx, segs, doc_bases, n_segs, queries, n_queries, field_id, sim, query_vectors, dim, boost, query_weight,
+  const int rc = search_hybrid_impl(ctx, segs, doc_bases, n_segs, queries, n_queries, field_id, sim, query_vectors, bytes, dim, boost, query_weight,
                                     rescore_weight, window, out, &rerun, true);
   if (rc != 0) return rc;
   note_speculation(ctx, segs, n_segs, n_queries, (int64_t)rerun.size());
   if (rerun.empty()) return rc;
   std::vector<nrtgpu_bm25_query> rq(rerun.size());
   std::vector<nrtgpu_topdocs> ro(rerun.size());
-  std::vector<float> rv(rerun.size() * (size_t)dim);
+  const size_t row_bytes = (size_t)dim * (bytes ? sizeof(int8_t) : sizeof(float));
+  std::vector<float> rv((rerun.size() * row_bytes + sizeof(float) - 1) / sizeof(float));   // (the tagged queries' vectors, either element type)
   for (size_t i = 0; i < rerun.size(); ++i) {
     rq[i] = queries[rerun[i]];
     ro[i] = out[rerun[i]];
-    memcpy(rv.data() + i * (size_t)dim, query_vectors + (size_t)rerun[i] * (size_t)dim, (size_t)dim * sizeof(float));
+    memcpy((char*)rv.data() + i * row_bytes, (const char*)query_vectors + (size_t)rerun[i] * row_bytes, row_bytes);
   }
   DeadlineScope no_deadline(true);
-  const int rc2 = search_hybrid_impl(ctx, segs, doc_bases, n_segs, rq.data(), (int32_t)rq.size(), field_id, sim, rv.data(), dim, boost, query_weight,
+  const int rc2 = search_hybrid_impl(ctx, segs, doc_bases, n_segs, rq.data(), (int32_t)rq.size(), field_id, sim, rv.data(), bytes, dim, boost, query_weight,
                                      rescore_weight, window, ro.data(), nullptr, true);
   if (rc2 != 0) return rc2;
   for (size_t i = 0; i < rerun.size(); ++i) out[rerun[i]] = ro[i];
   return NRTGPU_OK;
+}
+
+extern "C" int nrtgpu_search_hybrid_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases,
+                                          int32_t n_segs, const nrtgpu_bm25_query* queries, int32_t n_queries,
+                                          int32_t field_id, int32_t sim, const float* query_vectors, int32_t dim, float boost,
+                                          double query_weight, double rescore_weight, int32_t window, nrtgpu_topdocs* out) {
+  return search_hybrid_entry(ctx, segs, doc_bases, n_segs, queries, n_queries, field_id, sim, query_vectors, false, dim, boost, query_weight,
+                             rescore_weight, window, out);
+}
+
+// The same over a byte (int8) vector field.  What the byte scorer refuses is refused here, before anything is planned, with the
+// byte entries' codes (vectors_bytes.cpp); the rest -- negative weights included -- is search_hybrid_impl's.
+extern "C" int nrtgpu_search_hybrid_bytes_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases,
+                                                int32_t n_segs, const nrtgpu_bm25_query* queries, int32_t n_queries,
+                                                int32_t field_id, int32_t sim, const int8_t* query_vectors, int32_t dim, float boost,
+                                                double query_weight, double rescore_weight, int32_t window, nrtgpu_topdocs* out) {
+  if (!ctx || !queries || !out || !query_vectors || (n_segs > 0 && (!segs || !doc_bases))) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
+  if (n_queries <= 0 || n_segs < 0) return fail(NRTGPU_ERR_INVALID_ARG, "n_queries must be > 0");
+  if (int rc = byte_rescore_check_args(sim, dim, boost, window)) return rc;
+  if (int rc = byte_queries_stage(query_vectors, n_queries, dim, sim, nullptr, nullptr)) return rc;   // (a zero query under cosine)
+  return search_hybrid_entry(ctx, segs, doc_bases, n_segs, queries, n_queries, field_id, sim, query_vectors, true, dim, boost, query_weight,
+                             rescore_weight, window, out);
 }
 
 int nrtgpu::rt::hybrid_tail_on_device(nrtgpu_ctx* ctx, Slot* slot, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,

@@ -241,6 +241,167 @@ extern "C" int nrtgpu_knn_search_bytes(nrtgpu_ctx* ctx, const nrtgpu_seg* const*
   return knn_bytes_impl(ctx, segs, doc_bases, n_segs, field_id, sim, queries, n_queries, dim, k, boost, true, filter_mask, min_score, out);
 }
 
+// ---- the rescorers over a byte field: QueryRescore (rescore/QueryRescore.java:40-57) with the field's ExactByteVectorQuery
+// (VectorFieldDef.java:842) in the rescore slot -- nrtgpu_rescore_byte_vectors here, the tail of nrtgpu_search_hybrid_bytes_batch in
+// search.cpp: search_hybrid_impl, which stages its inputs through the three functions below ------------------------------------
+// What the byte entries ask of their scalars, in knn_bytes_impl's order.
+int nrtgpu::rt::byte_rescore_check_args(int32_t sim, int32_t dim, float boost, int32_t window) {
+  if (dim <= 0 || sim < 0 || sim > 3 || window <= 0) return fail(NRTGPU_ERR_INVALID_ARG, "bad rescore arguments");
+  // (the fused tail keeps hits as keys that order like NON-NEGATIVE float bits; the two-call path refuses the same boosts)
+  if (!(boost >= 0.0f) || !(boost < INFINITY)) return fail(NRTGPU_ERR_INVALID_ARG, "byte vector rescore: a finite boost >= 0 expected");
+  if (dim > 2048) return fail(NRTGPU_ERR_UNSUPPORTED, "vector dimension %d (device path takes <= 2048)", dim);
+  return NRTGPU_OK;
+}
+// n queries of `dim` int8 -> piece order (knn_bytes.hip: the query itself, zero-padded to 64 x steps bytes per query) and |q|^2 as
+// int32; cosine refuses a zero query as the reference does (validateVectorForSearch, VectorFieldDef.java:853-861).
+size_t nrtgpu::rt::byte_query_stride(int32_t dim) { return (size_t)knn_bytes_steps(dim) * 64; }
+int nrtgpu::rt::byte_queries_stage(const int8_t* queries, int32_t n, int32_t dim, int32_t sim, int8_t* padded, int32_t* qnorm2) {
+  const size_t stride = byte_query_stride(dim);
+  for (int32_t q = 0; q < n; ++q) {
+    const int8_t* src = queries + (size_t)q * dim;
+    int32_t s = 0;
+    for (int32_t d = 0; d < dim; ++d) s += (int32_t)src[d] * (int32_t)src[d];
+    if (sim == 0 && s == 0) return fail(NRTGPU_ERR_INVALID_ARG, "query %d is a zero vector: cosine similarity is not defined for it", q);
+    if (qnorm2) qnorm2[q] = s;
+    if (padded) {
+      memcpy(padded + (size_t)q * stride, src, (size_t)dim);
+      memset(padded + (size_t)q * stride + dim, 0, stride - (size_t)dim);
+    }
+  }
+  return NRTGPU_OK;
+}
+// The field in every leaf: byte rows of the query's dimension, or absent.  `out` (may be NULL): the leaf table the kernel reads.
+int nrtgpu::rt::byte_rescore_leaves(const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, int32_t field_id, int32_t dim,
+                                    DByteVecSeg* out) {
+  for (int si = 0; si < n_segs; ++si) {
+    DByteVecSeg v{};
+    auto fit = segs[si]->fields.find(field_id);
+    if (fit != segs[si]->fields.end()) {
+      const FieldData& f = fit->second;
+      if (!f.byte_rows && (f.d_vectors || f.dim > 0))
+        return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d holds float (fp32) vectors: rescore it with nrtgpu_rescore_vectors / nrtgpu_search_hybrid_batch",
+                    si, field_id);
+      if (f.byte_rows && f.dim_user != dim)
+        return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d has dimension %d, query has %d", si, field_id, f.dim_user, dim);
+      if (f.byte_rows && f.d_btiles && f.n_vec > 0) {
+        v.tiles = f.d_btiles;
+        v.vnorm2 = f.d_bnorm2;
+        v.ord_to_doc = f.d_ord_to_doc;
+        v.n_vec = f.n_vec;
+      }
+    }
+    v.doc_base = doc_bases[si];
+    v.max_doc = segs[si]->max_doc;
+    if (out) out[si] = v;
+  }
+  return NRTGPU_OK;
+}
+
+extern "C" int nrtgpu_rescore_byte_vectors(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                           int32_t field_id, int32_t sim, const int8_t* query, int32_t dim, float boost,
+                                           const int32_t* docs, const float* first_scores, int32_t n, double query_weight,
+                                           double rescore_weight, int32_t window, nrtgpu_topdocs* out) {
+  forget_foreign_hip_error();
+  if (!ctx || !query || !out || (n > 0 && (!docs || !first_scores)) || (n_segs > 0 && (!segs || !doc_bases)))
+    return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
+  if (n < 0 || n_segs < 0) return fail(NRTGPU_ERR_INVALID_ARG, "bad rescore arguments");
+  if (int rc = byte_rescore_check_args(sim, dim, boost, window)) return rc;
+  // (the hits are sorted on the host: any finite weights)
+  if (!(std::fabs(query_weight) < INFINITY) || !(std::fabs(rescore_weight) < INFINITY))
+    return fail(NRTGPU_ERR_INVALID_ARG, "byte vector rescore: finite weights expected");
+  std::vector<int8_t> qpad(byte_query_stride(dim));
+  int32_t qn = 0;
+  if (int rc = byte_queries_stage(query, 1, dim, sim, qpad.data(), &qn)) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  for (int si = 0; si < n_segs; ++si)
+    if (!segs[si]) return fail(NRTGPU_ERR_INVALID_ARG, "segment %d is NULL", si);
+  if (int rc = byte_rescore_leaves(segs, doc_bases, n_segs, field_id, dim, nullptr)) return rc;
+  // hits -> (segment, vector row), on the host as nrtgpu_rescore_vectors does; per segment one kernel
+  std::vector<int> seg_of((size_t)n, -1);
+  std::vector<int64_t> row_of((size_t)n, -1);
+  for (int i = 0; i < n; ++i) {
+    for (int si = 0; si < n_segs; ++si) {
+      const int64_t local = (int64_t)docs[i] - (int64_t)doc_bases[si];
+      if (local < 0 || local >= (int64_t)segs[si]->max_doc) continue;
+      seg_of[(size_t)i] = si;
+      auto fit = segs[si]->fields.find(field_id);
+      if (fit == segs[si]->fields.end() || !fit->second.d_btiles) break;
+      const FieldData& f = fit->second;
+      if (f.h_ord_to_doc.empty()) {
+        if (local < (int64_t)f.n_vec) row_of[(size_t)i] = local;
+      } else {
+        auto it = std::lower_bound(f.h_ord_to_doc.begin(), f.h_ord_to_doc.end(), (int32_t)local);
+        if (it != f.h_ord_to_doc.end() && *it == (int32_t)local) row_of[(size_t)i] = it - f.h_ord_to_doc.begin();
+      }
+      break;
+    }
+    if (seg_of[(size_t)i] < 0) return fail(NRTGPU_ERR_INVALID_ARG, "hit %d (doc %d) is outside every segment", i, docs[i]);
+  }
+  Slot* slot = nullptr;
+  acquire_slot(ctx, &slot);
+  struct Guard { nrtgpu_ctx* c; Slot* s; ~Guard() { release_slot(c, s); } } guard{ctx, slot};
+  std::lock_guard<std::mutex> gpu(ctx->gpu_mu);
+  hipStream_t st = slot->stream;
+  std::vector<float> combined((size_t)n);
+  auto on_device = [&]() -> int {
+    if (ctx->last_turn) HIP_TRY(hipStreamWaitEvent(st, ctx->last_turn, 0));
+    Carver wc;
+    const size_t o_q = wc.take(qpad.size()), o_rows = wc.take((size_t)n * 8 + 8), o_first = wc.take((size_t)n * 4 + 4),
+                 o_out = wc.take((size_t)n * 4 + 4);
+    if (int rc = slot->d_work.reserve(wc.off)) return rc;
+    char* wb = (char*)slot->d_work.p;
+    HIP_TRY(hipMemcpyAsync(wb + o_q, qpad.data(), qpad.size(), hipMemcpyHostToDevice, st));
+    for (int si = 0; si < n_segs; ++si) {
+      std::vector<int> idx;
+      for (int i = 0; i < n; ++i)
+        if (seg_of[(size_t)i] == si) idx.push_back(i);
+      if (idx.empty()) continue;
+      auto fit = segs[si]->fields.find(field_id);
+      const FieldData* f = (fit != segs[si]->fields.end() && fit->second.d_btiles) ? &fit->second : nullptr;
+      if (!f) {  // no vectors in this leaf: the second pass matches nothing
+        for (int i : idx) combined[(size_t)i] = (float)(query_weight * (double)first_scores[i]);
+        continue;
+      }
+      std::vector<int64_t> rows(idx.size());
+      std::vector<float> first(idx.size()), res(idx.size());
+      for (size_t j = 0; j < idx.size(); ++j) {
+        rows[j] = row_of[(size_t)idx[j]];
+        first[j] = first_scores[idx[j]];
+      }
+      HIP_TRY(hipMemcpyAsync(wb + o_rows, rows.data(), rows.size() * 8, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(wb + o_first, first.data(), first.size() * 4, hipMemcpyHostToDevice, st));
+      launch_rescore_byte_vectors(st, f->d_btiles, f->d_bnorm2, dim, wb + o_q, qn, sim, boost, (const int64_t*)(wb + o_rows),
+                                  (const float*)(wb + o_first), (int32_t)idx.size(), query_weight, rescore_weight, (float*)(wb + o_out));
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(res.data(), wb + o_out, res.size() * 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));   // (the staging vectors of this leaf go out of scope)
+      for (size_t j = 0; j < idx.size(); ++j) combined[(size_t)idx[j]] = res[j];
+    }
+    return NRTGPU_OK;
+  };
+  if (int rc = on_device()) {
+    (void)hipStreamSynchronize(st);   // nothing of a failed call is in flight when the slot is released (its copies read this frame's vectors)
+    return rc;
+  }
+  // QueryRescorer: sort by (combined score desc, doc asc), keep the window
+  std::vector<int> order((size_t)n);
+  for (int i = 0; i < n; ++i) order[(size_t)i] = i;
+  std::sort(order.begin(), order.end(), [&](int a, int b) {
+    if (combined[(size_t)a] != combined[(size_t)b]) return combined[(size_t)a] > combined[(size_t)b];
+    return docs[a] < docs[b];
+  });
+  const int32_t cap = out->capacity > 0 ? out->capacity : window;
+  const int32_t m = std::min<int32_t>(std::min<int32_t>(n, window), cap);
+  for (int32_t i = 0; i < m; ++i) {
+    if (out->docs) out->docs[i] = docs[order[(size_t)i]];
+    if (out->scores) out->scores[i] = combined[(size_t)order[(size_t)i]];
+  }
+  out->n_hits = m;
+  out->total_hits = n;
+  out->total_hits_is_lower_bound = 0;
+  return NRTGPU_OK;
+}
+
 // Needs no device: the one statement of the byte scores (plan.h), as the kernel compiles it.
 extern "C" int nrtgpu_byte_vector_score(int32_t sim, int32_t dim, int32_t dot, int32_t q_norm2, int32_t v_norm2, float* out) {
   if (!out) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
