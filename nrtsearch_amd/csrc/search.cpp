@@ -652,7 +652,7 @@ static int search_hybrid_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, co
   if (bytes) {   // a float field, another dimension: refused before anything is planned
     if (int rc = byte_rescore_leaves(segs, doc_bases, n_segs, field_id, dim, nullptr)) return rc;
   } else {
-    for (int si = 0; si < n_segs; ++si) {   // (this entry does not pad its queries through pad_query_vectors, where the other float entries refuse byte fields)
+    for (int si = 0; si < n_segs; ++si) {   // (refused here, before anything is planned; the queries are padded below, once the dimension is known to fit)
       auto fit = segs[si]->fields.find(field_id);
       if (fit != segs[si]->fields.end() && fit->second.byte_rows)
         return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d holds byte (int8) vectors: the hybrid tail rescores float vector fields only", si, field_id);
@@ -664,6 +664,14 @@ static int search_hybrid_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, co
     auto fit = segs[si]->fields.find(field_id);
     if (fit != segs[si]->fields.end() && fit->second.d_vectors && fit->second.dim_user != dim)
       return fail(NRTGPU_ERR_INVALID_ARG, "vector dimension mismatch");
+  }
+  // Float rows are resident padded to a multiple of 16 elements (FieldData::dim is their stride): the queries likewise, and from
+  // here on the float tail's `dim` is the RESIDENT dimension, as in nrtgpu_rescore_vectors (trailing zeros change no sum).
+  PaddedQueries padded;
+  if (!bytes) {
+    if (int rc = pad_query_vectors(segs, n_segs, field_id, (const float*)query_vectors, n_queries, dim, &padded)) return rc;
+    query_vectors = padded.p;
+    dim = padded.dim;
   }
   Slot* slot = nullptr;
   acquire_slot(ctx, &slot);

@@ -17,7 +17,7 @@ int nrtgpu::rt::pad_query_vectors(const nrtgpu_seg* const* segs, int32_t n_segs,
   for (int si = 0; si < n_segs; ++si) {
     if (!segs[si]) continue;
     auto fit = segs[si]->fields.find(field_id);
-    if (fit != segs[si]->fields.end() && fit->second.byte_rows)   // (knn_impl, the rescorer and the multi-GPU hybrid tail pad their queries here; nrtgpu_search_hybrid_batch checks for itself: search.cpp)
+    if (fit != segs[si]->fields.end() && fit->second.byte_rows)   // (knn_impl, the rescorer and the multi-GPU hybrid tail pad their queries here; nrtgpu_search_hybrid_batch refuses byte fields itself, before it plans, and pads here afterwards: search.cpp)
       return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d holds byte (int8) vectors: search it with nrtgpu_knn_exact_bytes / nrtgpu_knn_search_bytes",
                   si, field_id);
     if (fit == segs[si]->fields.end() || !fit->second.d_vectors) continue;

@@ -256,6 +256,12 @@ def test_fused_hybrid_under_speculative_thresholds_equals_the_unspeculated_answe
     g.add_field_norms(0, seg.norms)
     g.add_terms(0, seg.term_ids, seg.offsets, seg.docids, seg.freqs)
     g.add_vectors(VEC_FIELD, rng.standard_normal((seg.max_doc, dim)).astype(np.float32))
+    # a field whose dimension is no multiple of 16 (resident rows are padded to 112 elements; the re-run hands the tagged queries'
+    # own 100 elements on), over a sparse ord -> doc map of the live range: the hits without a vector keep queryWeight * first
+    live_docs = int(seg.max_doc * 0.3) // 64 * 64
+    rng100 = np.random.default_rng(6)
+    have = np.flatnonzero(rng100.random(live_docs) < 0.2).astype(np.int32)
+    g.add_vectors(VEC_FIELD + 1, rng100.standard_normal((len(have), 100)).astype(np.float32), have)
     g.seal()
     live = np.zeros((seg.max_doc + 63) // 64, dtype=np.uint64)
     live[: int(seg.max_doc * 0.3) // 64] = np.uint64(0xFFFFFFFFFFFFFFFF)
@@ -264,17 +270,25 @@ def test_fused_hybrid_under_speculative_thresholds_equals_the_unspeculated_answe
     try:
         qs = [_bq(t) for t in ([1, 5, 20, 150, 400], [2, 9, 60], [1, 2, 5, 9, 20, 60, 150, 400], [5, 400], [9, 20, 150])]
         mg = [api.TopScoreDocCollectorManager(1000)] * len(qs)
-        qv = rng.standard_normal((len(qs), dim)).astype(np.float32)
-        ctx.set_speculation(5.0)
-        fused = sr.search_hybrid_batch(qs, mg, VEC_FIELD, "cosine", qv, 100, 1.0, 2.0)
-        c = ctx.spec_counters()
-        assert c["queries"] == len(qs) and c["reruns"] >= 2, c
-        ctx.set_speculation(0.0)
-        plain = sr.search_hybrid_batch(qs, mg, VEC_FIELD, "cosine", qv, 100, 1.0, 2.0)
-        assert ctx.spec_counters()["queries"] == 0
-        for a, b in zip(fused, plain):
-            assert a.docs.tolist() == b.docs.tolist() and a.scores.view(np.uint32).tolist() == b.scores.view(np.uint32).tolist()
-            assert len(a.docs) == 100 and a.relation_gte == b.relation_gte   # (the counts are lower bounds: what each run happened to evaluate)
+        for field, fdim in ((VEC_FIELD, dim), (VEC_FIELD + 1, 100)):
+            qv = (rng if field == VEC_FIELD else rng100).standard_normal((len(qs), fdim)).astype(np.float32)
+            ctx.set_speculation(5.0)
+            fused = sr.search_hybrid_batch(qs, mg, field, "cosine", qv, 100, 1.0, 2.0)
+            c = ctx.spec_counters()
+            assert c["queries"] == len(qs) and c["reruns"] >= 2, c
+            ctx.set_speculation(0.0)
+            plain = sr.search_hybrid_batch(qs, mg, field, "cosine", qv, 100, 1.0, 2.0)
+            assert ctx.spec_counters()["queries"] == 0
+            for a, b in zip(fused, plain):
+                assert a.docs.tolist() == b.docs.tolist() and a.scores.view(np.uint32).tolist() == b.scores.view(np.uint32).tolist()
+                assert len(a.docs) == 100 and a.relation_gte == b.relation_gte   # (the counts are lower bounds: what each run happened to evaluate)
+            if fdim % 16:   # and the two-call answer: the rescorer pads its query to the resident dimension, the fused tail must too
+                with_vector = 0
+                for i, a in enumerate(fused):
+                    two = sr.rescore_vectors(sr.search(qs[i], mg[i]), field, "cosine", qv[i], 100, 1.0, 2.0)
+                    assert a.docs.tolist() == two.docs.tolist() and a.scores.view(np.uint32).tolist() == two.scores.view(np.uint32).tolist(), i
+                    with_vector += int(np.isin(a.docs, have).sum())
+                assert with_vector >= 50, with_vector            # (a fifth of the live docs has one)
     finally:
         g.release()
         ctx.close()
