@@ -655,6 +655,120 @@ int knn_exact_device(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32
                      int32_t sim, const float* queries, int32_t n_queries, int32_t dim, int32_t k, float boost, int32_t k_stride,
                      void* d_keys, void* d_counts, void* d_hits);
 
+// A workspace slot for the length of a scope.
+struct SlotGuard {
+  nrtgpu_ctx* c;
+  Slot* s;
+  ~SlotGuard() { release_slot(c, s); }
+};
+
+// What the two exact searches (knn_impl in vectors.cpp, knn_bytes_impl in vectors_bytes.cpp) share around their kernels: the turns
+// on the device, the timed scoring launches, the rounds over the leaves' tiles, a panel's statistics and the unpacking.
+struct KnnRun {
+  nrtgpu_ctx* ctx;
+  Slot* slot;
+  size_t n_ev = 0;   // timing events recorded for the panel under way (two per scoring launch)
+  // Ordering on the device (search.cpp: enqueue_search has the BM25 side): a stage of a vector search -- nomination launches,
+  // selections, rescoring -- starts behind the BM25 scorers enqueued last (they want every CU's LDS) and they start behind it;
+  // but two vector searches do NOT queue behind each other: the nomination kernel streams, its workgroups are handed out as
+  // CUs come free, so a second call's launches fill the tail of this call's and run under its small selection / rescoring
+  // kernels (34 KB of LDS beside a nomination workgroup's 112).  Measured with two callers at 10 M x 768: 32 queries per call
+  // 3.21 -> 2.90 ms per step, 64: 3.61 -> 3.20.  The host lock is held for the two event operations only.
+  int take_turn();
+  int end_turn();
+  // One scoring launch: between two events when the context collects timing; a launch status != 0 fails as "<kernel> launch: ...".
+  template <class Launch>
+  int timed_launch(const char* kernel, Launch&& launch) {
+    const bool timing = ctx->cfg.collect_timing != 0;
+    if (timing) {
+      while (slot->round_ev.size() < n_ev + 2) {
+        hipEvent_t ev = nullptr;
+        HIP_TRY(hipEventCreate(&ev));
+        slot->round_ev.push_back(ev);
+      }
+      HIP_TRY(hipEventRecord(slot->round_ev[n_ev], slot->stream));
+    }
+    const int e = launch();
+    if (e) return fail(NRTGPU_ERR_HIP, "%s launch: %s", kernel, hipGetErrorString((hipError_t)e));
+    if (timing) {
+      HIP_TRY(hipEventRecord(slot->round_ev[n_ev + 1], slot->stream));
+      n_ev += 2;
+    }
+    return NRTGPU_OK;
+  }
+  // One pass over `total_tiles` tiles of 16 rows in rounds: launch(tile_begin, tile_end, blocks, append_only) scores a round,
+  // select() follows it.  Nominating, the first round is `first_round` tiles and at most the candidate list (cap rows: every row
+  // takes a slot); a later round is 15 x the tiles seen so far (later rounds only append rows that beat theta), and after two
+  // selections the remaining launches run back to back (append_only) with ONE selection behind them.  safe: rounds no longer than
+  // the list, growing x 4, a selection after each (a panel whose list overflowed is redone so).  Neither: theta is fixed and
+  // tight -- everything at once.  A launch takes at most 2^22 tiles.
+  template <class Launch, class Select>
+  int tile_rounds(int64_t total_tiles, int64_t first_round, uint32_t cap, bool nominate, int safe, Launch&& launch, Select&& select) {
+    int64_t seen = 0, round = first_round;
+    int selections = 0;
+    bool pending = false;
+    for (int64_t t = 0; t < total_tiles;) {
+      int64_t len = (safe || (nominate && seen == 0)) ? std::min<int64_t>(round, cap >> 4) : round;
+      if (!nominate && !safe) len = total_tiles;
+      len = std::min<int64_t>(len, (int64_t)1 << 22);   // (a queue entry carries the padded row inside the launch in 26 bits)
+      const int64_t te = std::min<int64_t>(total_tiles, t + len);
+      const uint32_t blocks = (uint32_t)std::min<int64_t>(((te - t) * 16 + 255) / 256, (int64_t)std::max(ctx->n_cus, 1));
+      const bool defer = nominate && !safe && selections >= 2;
+      if (int rc = launch(t, te, blocks, defer ? 1 : 0)) return rc;
+      if (defer) {
+        pending = true;
+      } else {
+        select();
+        ++selections;
+      }
+      seen += te - t;
+      t = te;
+      round = safe ? std::min<int64_t>(round * 4, cap >> 4) : std::min<int64_t>(seen * 15, (int64_t)1 << 36);
+    }
+    if (pending) select();
+    return NRTGPU_OK;
+  }
+  // the panel is answered: its launches, their time and its rows into the context's statistics; n_ev starts over
+  void add_stats(int64_t rows, int64_t sketch_launches, bool second_pass);
+};
+// A panel's sorted keys -> the callers' nrtgpu_topdocs.  clamp_to_k: counts[q] may exceed k (the byte search's running list).
+// knn_request: totalHits = the docs returned, the boost applied afterwards; else `total`.
+void knn_unpack_topdocs(const uint64_t* keys, const uint32_t* counts, uint32_t k_stride, int nq, int32_t k, bool clamp_to_k, int64_t total,
+                        bool knn_request, float boost, nrtgpu_topdocs* out);
+
+// ---- the vector rescorers (vectors.cpp; what is specific to byte fields: vectors_bytes.cpp) ----------------------------------
+// |q|^2 of a float query as the rescoring kernels' results depend on it: fp32, in element order, every product rounded before it is
+// added.  The one chain the rescoring kernels' inputs use (knn_impl stages its panels' |q|^2 with a walk of its own, eight queries side
+// by side in the same element order).
+float float_qnorm2(const float* q, int dim);
+// The inputs of the rescoring kernels (hybrid_rescore_kernel, hybrid_rescore_bytes_kernel, knn_refine_select_kernel) into host
+// memory of the caller, each part optional (NULL):
+//   leaves  n_segs slots of 40 bytes: DVecSeg, or DByteVecSeg for a byte field -- one layout (doc_bases may be NULL: zeros)
+//   staged  the n queries as the kernel reads them: floats of `dim` elements (the RESIDENT dimension: pad_query_vectors), or int8
+//           in piece order, byte_query_stride(dim) bytes each
+//   qnorm2  |q|^2 per query: float_qnorm2, or int32 for a byte field (cosine refuses a zero query there)
+int stage_rescore_inputs(const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, int32_t field_id, bool bytes, int32_t sim,
+                         const void* queries, int32_t n, int32_t dim, void* leaves, void* staged, void* qnorm2);
+// The two-call rescorer (QueryRescorer over a first pass's hits) for either element type: hits -> (segment, row), one gather
+// launch per leaf, sort by (combined score desc, doc asc), the window.  What differs comes in as a RescoreKind.
+struct RescoreKind {
+  const void* (*rows)(const FieldData&);   // the field's resident rows of this element type; NULL: the leaf has none
+  const void* query;                       // one staged query (stage_rescore_inputs)
+  size_t query_bytes;
+  // the leaf's launch: n hits of the leaf, their rows and first-pass scores on the device -> combined scores
+  std::function<void(hipStream_t, const FieldData&, const void* d_query, const int64_t* d_rows, const float* d_first, int32_t n, float* d_out)> launch;
+};
+int rescore_hits_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, int32_t field_id,
+                      const RescoreKind& kind, const int32_t* docs, const float* first_scores, int32_t n, double query_weight, int32_t window,
+                      nrtgpu_topdocs* out);
+// What the byte entries (vectors_bytes.cpp; the byte tail of search_hybrid_impl, search.cpp) ask before anything is staged: of their
+// scalars, and of the field in every leaf (byte rows of the query's dimension, or absent).
+int byte_rescore_check_args(int32_t sim, int32_t dim, float boost, int32_t window);
+int byte_rescore_check_leaves(const nrtgpu_seg* const* segs, int32_t n_segs, int32_t field_id, int32_t dim);
+size_t byte_query_stride(int32_t dim);
+// n queries of `dim` int8 -> piece order and |q|^2 as int32 (padded / qnorm2 may be NULL: check only)
+int byte_queries_stage(const int8_t* queries, int32_t n, int32_t dim, int32_t sim, int8_t* padded, int32_t* qnorm2);
+
 // ---- search (search.cpp): pieces the multi-GPU entry (dist.cpp) reuses ------------------------------
 // one shard's BM25 search with device-resident results and speculative thresholds guessed against the WHOLE search (search.cpp)
 int search_bm25_shard_device(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
@@ -669,16 +783,6 @@ void note_shard_speculation(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int3
 // hit totals), enqueued on `slot`'s stream; the caller synchronises.
 int merge_lists_on_device(nrtgpu_ctx* ctx, Slot* slot, int32_t n_lists, int32_t n_queries, int32_t k_stride, const void* g_keys,
                           const void* g_counts, const void* g_hits, const int32_t* ks, void* d_keys, void* d_counts, void* d_hits);
-// The rescorers over a byte field (vectors_bytes.cpp): what nrtgpu_rescore_byte_vectors and the byte tail of search_hybrid_impl
-// (search.cpp) share -- the refusals of the scalars, the queries in the kernels' piece order with |q|^2 (padded / qnorm2 may be
-// NULL: check only), the field's leaf table (out may be NULL: check only).
-int byte_rescore_check_args(int32_t sim, int32_t dim, float boost, int32_t window);
-size_t byte_query_stride(int32_t dim);
-int byte_queries_stage(const int8_t* queries, int32_t n, int32_t dim, int32_t sim, int8_t* padded, int32_t* qnorm2);
-int byte_rescore_leaves(const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, int32_t field_id, int32_t dim,
-                        DByteVecSeg* out);
-// The vector rescorer over device-resident first-pass lists (hybrid_rescore_kernel), enqueued on `slot`'s stream: uploads the leaf
-// table and the query vectors into the slot's aux buffers; windows -> d_win_keys (n_queries x w_stride), d_win_counts.
 // Query vectors of `dim_user` elements as the resident rows want them: padded with zeros to the field's resident dimension
 // (FieldData.dim).  p == the caller's array when nothing had to be padded.
 struct PaddedQueries {
@@ -688,6 +792,8 @@ struct PaddedQueries {
 };
 int pad_query_vectors(const nrtgpu_seg* const* segs, int32_t n_segs, int32_t field_id, const float* queries, int32_t n, int32_t dim_user,
                       PaddedQueries* out);
+// The vector rescorer over device-resident first-pass lists (hybrid_rescore_kernel), enqueued on `slot`'s stream: uploads the leaf
+// table and the query vectors into the slot's aux buffers; windows -> d_win_keys (n_queries x w_stride), d_win_counts.
 int hybrid_tail_on_device(nrtgpu_ctx* ctx, Slot* slot, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
                           int32_t field_id, int32_t sim, const float* query_vectors, int32_t dim, float boost, double qw, double rw,
                           int32_t window, int32_t n_queries, const void* d_first_keys, const void* d_first_counts, int32_t k_stride,

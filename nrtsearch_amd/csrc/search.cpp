@@ -459,7 +459,7 @@ static int search_batch_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, con
 
   Slot* slot = nullptr;
   acquire_slot(ctx, &slot);
-  struct Guard { nrtgpu_ctx* c; Slot* s; ~Guard() { release_slot(c, s); } } guard{ctx, slot};
+  SlotGuard guard{ctx, slot};
   const double queue_ms = now_ms() - t0 - plan_ms;
   NRT_CHECK_DEADLINE("while the search waited for a workspace");   // (nothing has been launched)
   DeviceRun run;
@@ -624,10 +624,20 @@ extern "C" int nrtgpu_debug_spec_counters(nrtgpu_ctx* ctx, int64_t* out3) {
 // the stages (RescoreTask.java:47-50 -> QueryRescore.java:39-57 applied to the hits of
 // SearchHandler.java:1412-1413).  Same results as nrtgpu_search_bm25_batch followed per query by
 // nrtgpu_rescore_vectors.
-// The TAIL stage is the only part that knows the field's element type: `bytes` -- query_vectors are int8, the field holds byte rows,
-// hybrid_rescore_bytes_kernel (knn_bytes.hip) scores them (same results as nrtgpu_rescore_byte_vectors; the entry has refused
-// what the byte scorer does not take) -- else fp32 and hybrid_rescore_kernel.  Planning, first pass, slots, locks, deadlines,
+// Only the refusals before the plan and the tail's LAUNCH know the field's element type: `bytes` -- query_vectors are int8, the
+// field holds byte rows, hybrid_rescore_bytes_kernel (knn_bytes.hip) scores them (same results as nrtgpu_rescore_byte_vectors; the
+// entry has refused what the byte scorer does not take) -- else fp32 and hybrid_rescore_kernel.  The tail's inputs (leaf table,
+// queries, |q|^2) are staged by stage_rescore_inputs (vectors.cpp) for both; planning, first pass, slots, locks, deadlines,
 // speculation tags, the copy back and the accounting are one code path.
+static int refuse_byte_field(const nrtgpu_seg* const* segs, int32_t n_segs, int32_t field_id) {
+  for (int si = 0; si < n_segs; ++si) {
+    auto fit = segs[si]->fields.find(field_id);
+    if (fit != segs[si]->fields.end() && fit->second.byte_rows)
+      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d holds byte (int8) vectors: the hybrid tail rescores float vector fields only", si, field_id);
+  }
+  return NRTGPU_OK;
+}
+
 static int search_hybrid_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases,
                               int32_t n_segs, const nrtgpu_bm25_query* queries, int32_t n_queries,
                               int32_t field_id, int32_t sim, const void* query_vectors, bool bytes, int32_t dim, float boost,
@@ -649,15 +659,9 @@ static int search_hybrid_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, co
     if (!segs[si]) return fail(NRTGPU_ERR_INVALID_ARG, "segment %d is NULL", si);
   std::optional<SegReadLocks> content;   // until this call's kernels have finished (content_held: the caller holds them over both passes)
   if (!content_held) content.emplace(segs, n_segs);
-  if (bytes) {   // a float field, another dimension: refused before anything is planned
-    if (int rc = byte_rescore_leaves(segs, doc_bases, n_segs, field_id, dim, nullptr)) return rc;
-  } else {
-    for (int si = 0; si < n_segs; ++si) {   // (refused here, before anything is planned; the queries are padded below, once the dimension is known to fit)
-      auto fit = segs[si]->fields.find(field_id);
-      if (fit != segs[si]->fields.end() && fit->second.byte_rows)
-        return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d holds byte (int8) vectors: the hybrid tail rescores float vector fields only", si, field_id);
-    }
-  }
+  // the other element type (a byte tail: another dimension too) is refused before anything is planned; the float queries are padded
+  // below, once the dimension is known to fit
+  if (int rc = bytes ? byte_rescore_check_leaves(segs, n_segs, field_id, dim) : refuse_byte_field(segs, n_segs, field_id)) return rc;
   if (int rc = build_plan(ctx, segs, doc_bases, n_segs, queries, n_queries, hp, 1)) return rc;
   const double plan_ms = now_ms() - t0;
   for (int si = 0; si < n_segs; ++si) {
@@ -675,12 +679,11 @@ static int search_hybrid_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, co
   }
   Slot* slot = nullptr;
   acquire_slot(ctx, &slot);
-  struct Guard { nrtgpu_ctx* c; Slot* s; ~Guard() { release_slot(c, s); } } guard{ctx, slot};
+  SlotGuard guard{ctx, slot};
   hipStream_t st = slot->stream;
   const uint32_t w_stride = round_up((uint32_t)std::min<int32_t>(window, NRTGPU_MAX_K), 16);
   const size_t nq = (size_t)n_queries;
   Carver ac;
-  static_assert(sizeof(DByteVecSeg) == sizeof(DVecSeg), "one leaf table slot serves both tails");
   const size_t qv_bytes = bytes ? nq * byte_query_stride(dim) : nq * (size_t)dim * 4;
   const size_t o_segs = ac.take((size_t)std::max(n_segs, 1) * sizeof(DVecSeg)), o_qv = ac.take(qv_bytes),
                o_qn = ac.take(nq * 4);
@@ -693,38 +696,9 @@ static int search_hybrid_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, co
   if (int rc = slot->h_aux.reserve(hc.off)) return rc;
   char* ha = (char*)slot->h_aux.p;
   char* da = (char*)slot->d_aux.p;
-  if (bytes) {   // the leaf table, the queries in piece order, |q|^2 as int32 (vectors_bytes.cpp)
-    if (int rc = byte_rescore_leaves(segs, doc_bases, n_segs, field_id, dim, (DByteVecSeg*)(ha + oh_in + o_segs))) return rc;
-    if (int rc = byte_queries_stage((const int8_t*)query_vectors, n_queries, dim, sim, (int8_t*)(ha + oh_in + o_qv), (int32_t*)(ha + oh_in + o_qn)))
-      return rc;
-  } else {
-    DVecSeg* hs = (DVecSeg*)(ha + oh_in + o_segs);
-    for (int si = 0; si < n_segs; ++si) {
-      DVecSeg v{};
-      auto fit = segs[si]->fields.find(field_id);
-      if (fit != segs[si]->fields.end() && fit->second.d_vectors) {
-        v.vecs = fit->second.d_vectors;
-        v.vnorm2 = fit->second.d_vnorm2;
-        v.ord_to_doc = fit->second.d_ord_to_doc;
-        v.n_vec = fit->second.n_vec;
-      }
-      v.doc_base = doc_bases[si];
-      v.max_doc = segs[si]->max_doc;
-      hs[si] = v;
-    }
-    const float* fq = (const float*)query_vectors;
-    memcpy(ha + oh_in + o_qv, fq, nq * (size_t)dim * 4);
-    float* hqn = (float*)(ha + oh_in + o_qn);
-    for (size_t q = 0; q < nq; ++q) {  // |q|^2 in the order nrtgpu_rescore_vectors uses
-      const float* qv = fq + q * (size_t)dim;
-      float qn = 0.f;
-      for (int d = 0; d < dim; ++d) {
-        volatile float p2 = qv[d] * qv[d];
-        qn = qn + p2;
-      }
-      hqn[q] = qn;
-    }
-  }
+  if (int rc = stage_rescore_inputs(segs, doc_bases, n_segs, field_id, bytes, sim, query_vectors, n_queries, dim, ha + oh_in + o_segs,
+                                    ha + oh_in + o_qv, ha + oh_in + o_qn))
+    return rc;
   HIP_TRY(hipMemcpyAsync(da, ha + oh_in, in_bytes, hipMemcpyHostToDevice, st));
   DeviceRun run;
   {
@@ -841,32 +815,8 @@ int nrtgpu::rt::hybrid_tail_on_device(nrtgpu_ctx* ctx, Slot* slot, const nrtgpu_
   if (int rc = slot->h_aux.reserve(ac.off)) return rc;
   char* ha = (char*)slot->h_aux.p;
   char* da = (char*)slot->d_aux.p;
-  DVecSeg* hs = (DVecSeg*)(ha + o_segs);
-  for (int si = 0; si < n_segs; ++si) {
-    DVecSeg v{};
-    auto fit = segs[si]->fields.find(field_id);
-    if (fit != segs[si]->fields.end() && fit->second.d_vectors) {
-      if (fit->second.dim != dim) return fail(NRTGPU_ERR_INVALID_ARG, "vector dimension mismatch");
-      v.vecs = fit->second.d_vectors;
-      v.vnorm2 = fit->second.d_vnorm2;
-      v.ord_to_doc = fit->second.d_ord_to_doc;
-      v.n_vec = fit->second.n_vec;
-    }
-    v.doc_base = doc_bases[si];
-    v.max_doc = segs[si]->max_doc;
-    hs[si] = v;
-  }
-  memcpy(ha + o_qv, query_vectors, nq * (size_t)dim * 4);
-  float* hqn = (float*)(ha + o_qn);
-  for (size_t q = 0; q < nq; ++q) {  // |q|^2 in the order nrtgpu_rescore_vectors uses
-    const float* qv = query_vectors + q * (size_t)dim;
-    float qn = 0.f;
-    for (int d = 0; d < dim; ++d) {
-      volatile float p2 = qv[d] * qv[d];
-      qn = qn + p2;
-    }
-    hqn[q] = qn;
-  }
+  // (every leaf's rows have this dimension once pad_query_vectors has accepted the field)
+  (void)stage_rescore_inputs(segs, doc_bases, n_segs, field_id, false, sim, query_vectors, n_queries, dim, ha + o_segs, ha + o_qv, ha + o_qn);
   HIP_TRY(hipMemcpyAsync(da, ha, ac.off, hipMemcpyHostToDevice, slot->stream));
   launch_hybrid_rescore(slot->stream, (uint32_t)n_queries, (const uint64_t*)d_first_keys, (const uint32_t*)d_first_counts, (uint32_t)k_stride,
                         (const DVecSeg*)(da + o_segs), n_segs, dim, (const float*)(da + o_qv), (const float*)(da + o_qn), sim, boost, qw, rw,
@@ -1412,7 +1362,7 @@ int nrtgpu::rt::merge_topk_device_kth(nrtgpu_ctx* ctx, int32_t n_lists, int32_t 
     if (ks[qi] <= 0 || ks[qi] > NRTGPU_MAX_K || ks[qi] > k_stride) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: bad k %d", qi, ks[qi]);
   Slot* slot = nullptr;
   acquire_slot(ctx, &slot);
-  struct Guard { nrtgpu_ctx* c; Slot* s; ~Guard() { release_slot(c, s); } } guard{ctx, slot};
+  SlotGuard guard{ctx, slot};
   // plan blob: list_idx (n_queries * n_lists), q_base, q_nlists, q_k
   const size_t nq = (size_t)n_queries, nl = (size_t)n_lists;
   Carver pc;

@@ -36,6 +36,106 @@ int nrtgpu::rt::pad_query_vectors(const nrtgpu_seg* const* segs, int32_t n_segs,
   return NRTGPU_OK;
 }
 
+// ---- what the float and the byte paths share (runtime_internal.h) --------------------------------------------------------------
+int nrtgpu::rt::KnnRun::take_turn() {
+  std::lock_guard<std::mutex> gpu(ctx->gpu_mu);
+  if (ctx->last_turn) HIP_TRY(hipStreamWaitEvent(slot->stream, ctx->last_turn, 0));
+  return NRTGPU_OK;
+}
+int nrtgpu::rt::KnnRun::end_turn() {
+  std::lock_guard<std::mutex> gpu(ctx->gpu_mu);
+  HIP_TRY(hipEventRecord(slot->ev_turn, slot->stream));
+  ctx->last_knn_turn = slot->ev_turn;
+  return NRTGPU_OK;
+}
+void nrtgpu::rt::KnnRun::add_stats(int64_t rows, int64_t sketch_launches, bool second_pass) {
+  double ms = 0.0;
+  for (size_t i = 0; i + 1 < n_ev; i += 2) {
+    float one = 0.f;
+    (void)hipEventElapsedTime(&one, slot->round_ev[i], slot->round_ev[i + 1]);
+    ms += (double)one;
+  }
+  std::lock_guard<std::mutex> lk(ctx->stats_mu);
+  ctx->stats.knn_panels += 1;
+  ctx->stats.knn_score_launches += (int64_t)(n_ev / 2);
+  ctx->stats.knn_score_ms += ms;
+  ctx->stats.knn_rows += rows;
+  ctx->stats.knn_second_passes += second_pass ? 1 : 0;
+  ctx->stats.knn_sketch_launches += sketch_launches;
+  n_ev = 0;
+}
+void nrtgpu::rt::knn_unpack_topdocs(const uint64_t* keys, const uint32_t* counts, uint32_t k_stride, int nq, int32_t k, bool clamp_to_k,
+                                    int64_t total, bool knn_request, float boost, nrtgpu_topdocs* out) {
+  for (int q = 0; q < nq; ++q) {
+    nrtgpu_topdocs* o = &out[q];
+    const int32_t cap = o->capacity > 0 ? o->capacity : k;
+    const int32_t m = std::min<int32_t>((int32_t)(clamp_to_k ? std::min<uint32_t>(counts[q], (uint32_t)k) : counts[q]), cap);
+    for (int32_t i = 0; i < m; ++i) {
+      if (o->docs) o->docs[i] = (int32_t)key_doc(keys[(size_t)q * k_stride + i]);
+      if (o->scores) o->scores[i] = key_score(keys[(size_t)q * k_stride + i]);
+    }
+    o->n_hits = m;
+    o->total_hits = total;   // every live doc with a vector matches an exact vector query
+    o->total_hits_is_lower_bound = 0;
+    if (knn_request) {
+      o->total_hits = m;  // the rewritten knn query matches exactly the docs it returns
+      if (boost != 1.0f && o->scores) {
+        for (int32_t i = 0; i < m; ++i) o->scores[i] = o->scores[i] * boost;
+        // distinct scores can round to one product: restore (score desc, doc asc) among equals
+        if (o->docs)
+          for (int32_t i = 1; i < m; ++i)
+            for (int32_t j = i; j > 0 && o->scores[j - 1] == o->scores[j] && o->docs[j - 1] > o->docs[j]; --j) std::swap(o->docs[j - 1], o->docs[j]);
+      }
+    }
+  }
+}
+
+float nrtgpu::rt::float_qnorm2(const float* q, int dim) {
+  float qn = 0.f;
+  for (int d = 0; d < dim; ++d) {
+    volatile float p2 = q[d] * q[d];   // (rounded, then added: no build flag can fuse the two)
+    qn = qn + p2;
+  }
+  return qn;
+}
+
+// A slot of the rescoring kernels' leaf table: DVecSeg and DByteVecSeg (plan.h) are this layout with their own pointer types.
+struct VecLeafSlot {
+  const void *rows, *vnorm2;
+  const int32_t* ord_to_doc;
+  int32_t doc_base, max_doc, n_vec, pad;
+};
+#define SAME_SLOT(m) (offsetof(VecLeafSlot, m) == offsetof(DVecSeg, m) && offsetof(VecLeafSlot, m) == offsetof(DByteVecSeg, m))
+static_assert(sizeof(VecLeafSlot) == sizeof(DVecSeg) && sizeof(VecLeafSlot) == sizeof(DByteVecSeg), "one leaf table slot serves both element types");
+static_assert(offsetof(VecLeafSlot, rows) == offsetof(DVecSeg, vecs) && offsetof(VecLeafSlot, rows) == offsetof(DByteVecSeg, tiles) &&
+              SAME_SLOT(vnorm2) && SAME_SLOT(ord_to_doc) && SAME_SLOT(doc_base) && SAME_SLOT(max_doc) &&
+              SAME_SLOT(n_vec), "leaf table layout");
+#undef SAME_SLOT
+
+int nrtgpu::rt::stage_rescore_inputs(const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, int32_t field_id, bool bytes,
+                                     int32_t sim, const void* queries, int32_t n, int32_t dim, void* leaves, void* staged, void* qnorm2) {
+  for (int si = 0; leaves && si < n_segs; ++si) {
+    VecLeafSlot v{};
+    auto fit = segs[si]->fields.find(field_id);
+    if (fit != segs[si]->fields.end()) {
+      const FieldData& f = fit->second;
+      if (bytes ? (f.byte_rows && f.d_btiles && f.n_vec > 0) : f.d_vectors != nullptr) {
+        v.rows = bytes ? f.d_btiles : (const void*)f.d_vectors;
+        v.vnorm2 = bytes ? (const void*)f.d_bnorm2 : (const void*)f.d_vnorm2;
+        v.ord_to_doc = f.d_ord_to_doc;
+        v.n_vec = f.n_vec;
+      }
+    }
+    v.doc_base = doc_bases ? doc_bases[si] : 0;
+    v.max_doc = segs[si]->max_doc;
+    memcpy((char*)leaves + (size_t)si * sizeof v, &v, sizeof v);
+  }
+  if (bytes) return byte_queries_stage((const int8_t*)queries, n, dim, sim, (int8_t*)staged, (int32_t*)qnorm2);
+  if (staged) memcpy(staged, queries, (size_t)n * (size_t)dim * 4);
+  for (int32_t q = 0; qnorm2 && q < n; ++q) ((float*)qnorm2)[q] = float_qnorm2((const float*)queries + (size_t)q * dim, dim);
+  return NRTGPU_OK;
+}
+
 static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
                     int32_t field_id, int32_t sim, const float* queries, int32_t n_queries, int32_t dim,
                     int32_t k, float boost, bool knn_request, int32_t filter_mask, float min_score, nrtgpu_topdocs* out,
@@ -69,26 +169,9 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
   const uint32_t ki_stride = round_up(k_int, 16);
   Slot* slot = nullptr;
   acquire_slot(ctx, &slot);
-  struct Guard { nrtgpu_ctx* c; Slot* s; ~Guard() { release_slot(c, s); } } guard{ctx, slot};
-  // Ordering on the device (search.cpp: enqueue_search has the BM25 side): a stage of this call -- nomination launches,
-  // selections, rescoring -- starts behind the BM25 scorers enqueued last (they want every CU's LDS) and they start behind it;
-  // but two vector searches do NOT queue behind each other: the nomination kernel streams, its workgroups are handed out as
-  // CUs come free, so a second call's launches fill the tail of this call's and run under its small selection / rescoring
-  // kernels (34 KB of LDS beside a nomination workgroup's 112).  Measured with two callers at 10 M x 768: 32 queries per call
-  // 3.21 -> 2.90 ms per step, 64: 3.61 -> 3.20.  The host lock is held for the two event operations only.
+  SlotGuard guard{ctx, slot};
+  KnnRun run{ctx, slot};   // (the turns on the device and what they order: runtime_internal.h)
   hipStream_t st = slot->stream;
-  auto take_turn = [&]() -> int {
-    std::lock_guard<std::mutex> gpu(ctx->gpu_mu);
-    if (ctx->last_turn) HIP_TRY(hipStreamWaitEvent(st, ctx->last_turn, 0));
-    return NRTGPU_OK;
-  };
-  auto end_turn = [&]() -> int {
-    std::lock_guard<std::mutex> gpu(ctx->gpu_mu);
-    HIP_TRY(hipEventRecord(slot->ev_turn, st));
-    ctx->last_knn_turn = slot->ev_turn;
-    return NRTGPU_OK;
-  };
-  const bool timing = ctx->cfg.collect_timing != 0;
   Carver wc;
   const size_t o_q = wc.take((size_t)kKnnMaxQ * dim * 4), o_qn = wc.take(kKnnMaxQ * 4), o_eb = wc.take(kKnnMaxQ * 4);
   const size_t o_eb16 = wc.take(kKnnMaxQ * 4), o_qs = wc.take(kKnnMaxQ * 4);
@@ -110,28 +193,19 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
   char* hs = (char*)slot->h_aux.p;
   float *qn = (float*)(hs + o_qn), *eb = (float*)(hs + o_eb), *eb16 = (float*)(hs + o_eb16), *qsc = (float*)(hs + o_qs);
   // the leaves' vector matrices, for docid -> row on the device (the rescoring reads rows by docid)
-  DVecSeg* hsegs = (DVecSeg*)(hs + o_segs);
+  (void)stage_rescore_inputs(segs, doc_bases, n_segs, field_id, false, sim, nullptr, 0, dim, hs + o_segs, nullptr, nullptr);
   double nv_max = 0.0, nv_min = INFINITY, rows_unit = 0.0;   // rows_unit: the largest 1 / scale of the leaves' sketches
   bool all_sketched = true, any_vectors = false;
   for (int si = 0; si < n_segs; ++si) {
-    DVecSeg v{};
-    v.doc_base = doc_bases ? doc_bases[si] : 0;
-    v.max_doc = segs[si]->max_doc;
     auto fit = segs[si]->fields.find(field_id);
-    if (fit != segs[si]->fields.end() && fit->second.d_vectors) {
-      v.vecs = fit->second.d_vectors;
-      v.vnorm2 = fit->second.d_vnorm2;
-      v.ord_to_doc = fit->second.d_ord_to_doc;
-      v.n_vec = fit->second.n_vec;
-      nv_max = std::max(nv_max, (double)fit->second.vnorm2_max);
-      if (fit->second.n_vec > 0) {
-        if (!fit->second.d_sketch) all_sketched = false;
-        any_vectors = true;
-        if (fit->second.vnorm2_min > 0.f) nv_min = std::min(nv_min, (double)fit->second.vnorm2_min);
-        rows_unit = std::max(rows_unit, 1.0 / (double)fit->second.sketch_scale);
-      }
+    if (fit == segs[si]->fields.end() || !fit->second.d_vectors) continue;
+    nv_max = std::max(nv_max, (double)fit->second.vnorm2_max);
+    if (fit->second.n_vec > 0) {
+      if (!fit->second.d_sketch) all_sketched = false;
+      any_vectors = true;
+      if (fit->second.vnorm2_min > 0.f) nv_min = std::min(nv_min, (double)fit->second.vnorm2_min);
+      rows_unit = std::max(rows_unit, 1.0 / (double)fit->second.sketch_scale);
     }
-    hsegs[(size_t)si] = v;
   }
   // the sketch kernel's view of the same leaves: ONE launch walks them all (tiles of 16 rows numbered through the leaves)
   DKnnLeaf* hleaves = (DKnnLeaf*)(hs + o_leaves);
@@ -258,14 +332,24 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
     memcpy(hs + o_q, queries + (size_t)q0 * dim, (size_t)nq * dim * 4);
     HIP_TRY(hipMemcpyAsync(wb + o_q, hs + o_q, (size_t)nq * dim * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(wb + o_qn, hs + o_qn, o_th - o_qn, hipMemcpyHostToDevice, st));   // |q|^2, bounds, scales, leaf table
-    if (int rc = take_turn()) return rc;   // (the staging above and its copies are not part of the turn)
+    if (int rc = run.take_turn()) return rc;   // (the staging above and its copies are not part of the turn)
     int64_t total_vec = 0, rows_scored = 0;
-    size_t n_ev = 0;
     // One pass over the rows of every leaf.  nominate: the estimates' running top-k_int, theta tightening (knn_select_kernel
     // <false>); else theta stays what the certification left and every nomination is rescored into the answer (<true>).
     // (rows of the first round: every row takes a slot of the list and the first selection scans them all)
     static const int64_t kFirstRound = []() { const long v = dev_env_int("NRTGPU_KNN_FIRST_ROUND", 0); return (int64_t)(v >= 1024 && v <= (1 << 18) ? (v & ~15L) : (1 << 16)); }();
     int64_t sketch_launches = 0;
+    auto select = [&]() {   // the candidates into the running top-k_int, theta tightened
+      launch_knn_select(st, (uint32_t)nq, (uint64_t*)(wb + o_tk), (uint32_t*)(wb + o_tc), ki_stride, k_int, (const uint64_t*)(wb + o_cd),
+                        (uint32_t*)(wb + o_cc), kKnnCap, (unsigned long long*)(wb + o_th), (uint32_t*)(wb + o_ov));
+    };
+    auto refine = [&](size_t o_list, size_t o_cnt, uint32_t cap, size_t o_bound, int32_t certify) {   // a list rescored into the answer
+      launch_knn_refine_select(st, (uint32_t)nq, (uint64_t*)(wb + o_xk), (uint32_t*)(wb + o_xc), k_stride, (uint32_t)k,
+                               (const uint64_t*)(wb + o_list), (uint32_t*)(wb + o_cnt), cap, (unsigned long long*)(wb + o_th),
+                               (uint32_t*)(wb + o_ov), (const DVecSeg*)(wb + o_segs), n_segs, dim, sim, (const float*)(wb + o_q),
+                               (const float*)(wb + o_qn), score_boost, (const float*)(wb + o_bound), erel, knn_request ? min_score : 0.0f,
+                               k_int, certify, (uint32_t*)(wb + o_cert));
+    };
     auto rows_pass = [&](bool nominate, int safe) -> int {   // (the fp32 rows: a launch per leaf and round)
       int64_t seen = 0, round = kFirstRound;
       // Nominating, theta tightens fast: after two selections (>= 1M rows seen) a later launch appends about k ln(rows / rows
@@ -294,102 +378,48 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
           const int64_t re = std::min<int64_t>(f.n_vec, (r + len + 15) & ~(int64_t)15);   // rounds begin on tile boundaries (16 rows)
           uint32_t blocks = (uint32_t)std::min<int64_t>((re - r + 255) / 256, (int64_t)std::max(ctx->n_cus, 1));  // 256 rows per workgroup step
           if (nq > 32) blocks = std::max(16u, std::min((uint32_t)std::max(ctx->n_cus, 16), 2u * blocks) / 16u * 16u);   // paired workgroups
-          if (timing) {
-            while (slot->round_ev.size() < n_ev + 2) {
-              hipEvent_t ev = nullptr;
-              HIP_TRY(hipEventCreate(&ev));
-              slot->round_ev.push_back(ev);
-            }
-            HIP_TRY(hipEventRecord(slot->round_ev[n_ev], st));
-          }
           const bool defer = nominate && !safe && selections >= 2;
-          const int e = launch_knn_score(st, blocks, f.d_vectors, f.d_vnorm2, f.d_ord_to_doc, accept, dim, r, re,
-                                         doc_bases ? doc_bases[si] : 0, (const float*)(wb + o_q), (const float*)(wb + o_qn), nq,
-                                         sim, score_boost, (const unsigned long long*)(wb + o_th), (uint64_t*)(wb + o_cd),
-                                         (uint32_t*)(wb + o_cc), kKnnCap, defer ? 1 : 0);
-          if (e) return fail(NRTGPU_ERR_HIP, "knn_score launch: %s", hipGetErrorString((hipError_t)e));
-          if (timing) {
-            HIP_TRY(hipEventRecord(slot->round_ev[n_ev + 1], st));
-            n_ev += 2;
-          }
+          if (int rc = run.timed_launch("knn_score", [&]() {
+                return launch_knn_score(st, blocks, f.d_vectors, f.d_vnorm2, f.d_ord_to_doc, accept, dim, r, re, doc_bases ? doc_bases[si] : 0,
+                                        (const float*)(wb + o_q), (const float*)(wb + o_qn), nq, sim, score_boost,
+                                        (const unsigned long long*)(wb + o_th), (uint64_t*)(wb + o_cd), (uint32_t*)(wb + o_cc), kKnnCap,
+                                        defer ? 1 : 0);
+              }))
+            return rc;
           if (defer) {
             pending = true;
           } else if (nominate) {
-            launch_knn_select(st, (uint32_t)nq, (uint64_t*)(wb + o_tk), (uint32_t*)(wb + o_tc), ki_stride, k_int,
-                              (const uint64_t*)(wb + o_cd), (uint32_t*)(wb + o_cc), kKnnCap,
-                              (unsigned long long*)(wb + o_th), (uint32_t*)(wb + o_ov));
+            select();
             ++selections;
           } else
-            launch_knn_refine_select(st, (uint32_t)nq, (uint64_t*)(wb + o_xk), (uint32_t*)(wb + o_xc), k_stride, (uint32_t)k,
-                                     (const uint64_t*)(wb + o_cd), (uint32_t*)(wb + o_cc), kKnnCap,
-                                     (unsigned long long*)(wb + o_th), (uint32_t*)(wb + o_ov), (const DVecSeg*)(wb + o_segs), n_segs, dim,
-                                     sim, (const float*)(wb + o_q), (const float*)(wb + o_qn), score_boost, (const float*)(wb + o_eb), erel,
-                                     knn_request ? min_score : 0.0f, k_int, 0, (uint32_t*)(wb + o_cert));
+            refine(o_cd, o_cc, kKnnCap, o_eb, 0);
           r = re;
           seen += re - rb;
           round = safe ? std::min<int64_t>(round * 4, kKnnCap) : std::min<int64_t>(seen * 15, (int64_t)1 << 40);
         }
       }
-      if (pending)
-        launch_knn_select(st, (uint32_t)nq, (uint64_t*)(wb + o_tk), (uint32_t*)(wb + o_tc), ki_stride, k_int,
-                          (const uint64_t*)(wb + o_cd), (uint32_t*)(wb + o_cc), kKnnCap,
-                          (unsigned long long*)(wb + o_th), (uint32_t*)(wb + o_ov));
+      if (pending) select();
       rows_scored += seen;
       return NRTGPU_OK;
     };
     // The same from the fp16 sketch: a round is a range of the leaves' tiles, ONE launch whatever the number of leaves it crosses.
     auto sketch_pass = [&](int safe, bool nominate) -> int {   // nominate = false: theta is fixed, every nomination is rescored into the answer
-      int64_t seen = 0, round = kFirstRound >> 4;   // in tiles of 16 rows
-      int selections = 0;
-      bool pending = false;
       total_vec = live_vectors;
-      for (int64_t t = 0; t < total_tiles;) {
-        int64_t len = (safe || (nominate && seen == 0)) ? std::min<int64_t>(round, kKnnCap >> 4) : round;
-        if (!nominate && !safe) len = total_tiles;   // theta is fixed and tight: everything at once
-        len = std::min<int64_t>(len, (int64_t)1 << 22);   // (a queue entry carries the padded row inside the launch in 26 bits)
-        const int64_t te = std::min<int64_t>(total_tiles, t + len);
-        const uint32_t blocks = (uint32_t)std::min<int64_t>(((te - t) * 16 + 255) / 256, (int64_t)std::max(ctx->n_cus, 1));
-        if (timing) {
-          while (slot->round_ev.size() < n_ev + 2) {
-            hipEvent_t ev = nullptr;
-            HIP_TRY(hipEventCreate(&ev));
-            slot->round_ev.push_back(ev);
-          }
-          HIP_TRY(hipEventRecord(slot->round_ev[n_ev], st));
-        }
-        const bool defer = nominate && !safe && selections >= 2;
-        const int e = launch_knn_sketch(st, blocks, (const DKnnLeaf*)(wb + o_leaves), n_kleaves, dim, t, te, (const void*)(wb + o_p16),
-                                        (const float*)(wb + o_qn), (const float*)(wb + o_qs), nq, sim, score_boost,
-                                        (const unsigned long long*)(wb + o_th), (uint64_t*)(wb + o_cd), (uint32_t*)(wb + o_cc), kKnnCap,
-                                        defer ? 1 : 0);
-        if (e) return fail(NRTGPU_ERR_HIP, "knn_sketch launch: %s", hipGetErrorString((hipError_t)e));
+      auto launch = [&](int64_t t, int64_t te, uint32_t blocks, int32_t append_only) -> int {
+        if (int rc = run.timed_launch("knn_sketch", [&]() {
+              return launch_knn_sketch(st, blocks, (const DKnnLeaf*)(wb + o_leaves), n_kleaves, dim, t, te, (const void*)(wb + o_p16),
+                                       (const float*)(wb + o_qn), (const float*)(wb + o_qs), nq, sim, score_boost,
+                                       (const unsigned long long*)(wb + o_th), (uint64_t*)(wb + o_cd), (uint32_t*)(wb + o_cc), kKnnCap, append_only);
+            }))
+          return rc;
         ++sketch_launches;
-        if (timing) {
-          HIP_TRY(hipEventRecord(slot->round_ev[n_ev + 1], st));
-          n_ev += 2;
-        }
-        if (defer) {
-          pending = true;
-        } else if (nominate) {
-          launch_knn_select(st, (uint32_t)nq, (uint64_t*)(wb + o_tk), (uint32_t*)(wb + o_tc), ki_stride, k_int,
-                            (const uint64_t*)(wb + o_cd), (uint32_t*)(wb + o_cc), kKnnCap, (unsigned long long*)(wb + o_th),
-                            (uint32_t*)(wb + o_ov));
-          ++selections;
-        } else {
-          launch_knn_refine_select(st, (uint32_t)nq, (uint64_t*)(wb + o_xk), (uint32_t*)(wb + o_xc), k_stride, (uint32_t)k,
-                                   (const uint64_t*)(wb + o_cd), (uint32_t*)(wb + o_cc), kKnnCap, (unsigned long long*)(wb + o_th),
-                                   (uint32_t*)(wb + o_ov), (const DVecSeg*)(wb + o_segs), n_segs, dim, sim, (const float*)(wb + o_q),
-                                   (const float*)(wb + o_qn), score_boost, (const float*)(wb + o_eb16), erel,
-                                   knn_request ? min_score : 0.0f, k_int, 0, (uint32_t*)(wb + o_cert));
-        }
-        seen += te - t;
-        t = te;
-        round = safe ? std::min<int64_t>(round * 4, kKnnCap >> 4) : std::min<int64_t>(seen * 15, (int64_t)1 << 36);
-      }
-      if (pending)
-        launch_knn_select(st, (uint32_t)nq, (uint64_t*)(wb + o_tk), (uint32_t*)(wb + o_tc), ki_stride, k_int,
-                          (const uint64_t*)(wb + o_cd), (uint32_t*)(wb + o_cc), kKnnCap, (unsigned long long*)(wb + o_th),
-                          (uint32_t*)(wb + o_ov));
+        return NRTGPU_OK;
+      };
+      if (int rc = run.tile_rounds(total_tiles, kFirstRound >> 4, kKnnCap, nominate, safe, launch, [&]() {
+            if (nominate) select();
+            else refine(o_cd, o_cc, kKnnCap, o_eb16, 0);
+          }))
+        return rc;
       rows_scored += total_rows;
       return NRTGPU_OK;
     };
@@ -402,7 +432,7 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
     };
     // 1. nominate, rescore the nominations, certify
     for (int safe = 0;; ++safe) {
-      if (int rc = take_turn()) return rc;
+      if (int rc = run.take_turn()) return rc;
       HIP_TRY(hipMemsetAsync(wb + o_th, 0, o_cd - o_th, st));  // theta, lists, counters
       if (knn_request && min_score > 0.0f) {  // start theta below the lowest key whose RESULT can still reach min_score
         std::vector<uint64_t> th0((size_t)nq);
@@ -415,12 +445,8 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
       }
       if (panel_sketch) launch_knn_panel_fp16(st, (const float*)(wb + o_q), (const float*)(wb + o_qs), dim, nq, wb + o_p16);
       if (int rc = panel_sketch ? sketch_pass(safe, true) : rows_pass(true, safe)) return rc;
-      launch_knn_refine_select(st, (uint32_t)nq, (uint64_t*)(wb + o_xk), (uint32_t*)(wb + o_xc), k_stride, (uint32_t)k,
-                               (const uint64_t*)(wb + o_tk), (uint32_t*)(wb + o_tc), ki_stride, (unsigned long long*)(wb + o_th),
-                               (uint32_t*)(wb + o_ov), (const DVecSeg*)(wb + o_segs), n_segs, dim, sim, (const float*)(wb + o_q),
-                               (const float*)(wb + o_qn), score_boost, (const float*)(wb + (panel_sketch ? o_eb16 : o_eb)), erel,
-                               knn_request ? min_score : 0.0f, k_int, 1, (uint32_t*)(wb + o_cert));
-      if (int rc = end_turn()) return rc;
+      refine(o_tk, o_tc, ki_stride, panel_sketch ? o_eb16 : o_eb, 1);
+      if (int rc = run.end_turn()) return rc;
       if (int rc = fetch()) return rc;
       if (*(const uint32_t*)(ho + oh_ov) == 0u) break;
       if (safe) return fail(NRTGPU_ERR_HIP, "knn: candidate list overflow in a bounded round");
@@ -449,14 +475,14 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
       }
     };
     auto second_pass = [&](bool from_sketch, int safe, const std::vector<uint64_t>& th2) -> int {
-      if (int rc = take_turn()) return rc;
+      if (int rc = run.take_turn()) return rc;
       HIP_TRY(hipMemcpyAsync(wb + o_th, th2.data(), (size_t)nq * 8, hipMemcpyHostToDevice, st));
       for (int q = 0; q < nq; ++q)   // their answers start over (a nomination found again must not be counted twice)
         if (((const uint32_t*)(ho + oh_cert))[q] == 0u) HIP_TRY(hipMemsetAsync(wb + o_xc + (size_t)q * 4, 0, 4, st));
       HIP_TRY(hipMemsetAsync(wb + o_cc, 0, kKnnMaxQ * 4, st));
       HIP_TRY(hipMemsetAsync(wb + o_ov, 0, 4, st));
       if (int rc = from_sketch ? sketch_pass(safe, false) : rows_pass(false, safe)) return rc;
-      if (int rc = end_turn()) return rc;
+      if (int rc = run.end_turn()) return rc;
       return fetch();   // (the second pass leaves the flags as they are)
     };
     if (uncertified) {
@@ -485,21 +511,7 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
         }
       }
     }
-    {
-      double ms = 0.0;
-      for (size_t i = 0; i + 1 < n_ev; i += 2) {
-        float one = 0.f;
-        (void)hipEventElapsedTime(&one, slot->round_ev[i], slot->round_ev[i + 1]);
-        ms += (double)one;
-      }
-      std::lock_guard<std::mutex> lk(ctx->stats_mu);
-      ctx->stats.knn_panels += 1;
-      ctx->stats.knn_score_launches += (int64_t)(n_ev / 2);
-      ctx->stats.knn_score_ms += ms;
-      ctx->stats.knn_rows += rows_scored;
-      ctx->stats.knn_second_passes += uncertified ? 1 : 0;
-      ctx->stats.knn_sketch_launches += sketch_launches;
-    }
+    run.add_stats(rows_scored, sketch_launches, uncertified != 0);
     if (ext_keys) {   // stays in HBM: what nrtgpu_dist_knn_exact exchanges
       std::vector<uint64_t> tv((size_t)nq, (uint64_t)total_vec);
       HIP_TRY(hipMemcpyAsync(ext_keys + (size_t)q0 * k_stride * 8, wb + o_xk, (size_t)nq * k_stride * 8, hipMemcpyDeviceToDevice, st));
@@ -508,30 +520,7 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
       HIP_TRY(hipStreamSynchronize(st));   // (tv is a stack vector; the workspace is reused by the next panel)
       continue;
     }
-    const uint64_t* keys = (const uint64_t*)ho;
-    const uint32_t* cnts = (const uint32_t*)(ho + oh_cnt);
-    for (int q = 0; q < nq; ++q) {
-      nrtgpu_topdocs* o = &out[q0 + q];
-      const int32_t cap = o->capacity > 0 ? o->capacity : k;
-      const int32_t m = std::min<int32_t>((int32_t)cnts[q], cap);
-      for (int32_t i = 0; i < m; ++i) {
-        if (o->docs) o->docs[i] = (int32_t)key_doc(keys[(size_t)q * k_stride + i]);
-        if (o->scores) o->scores[i] = key_score(keys[(size_t)q * k_stride + i]);
-      }
-      o->n_hits = m;
-      o->total_hits = total_vec;   // every live doc with a vector matches an exact vector query
-      o->total_hits_is_lower_bound = 0;
-      if (knn_request) {
-        o->total_hits = m;  // the rewritten knn query matches exactly the docs it returns
-        if (boost != 1.0f && o->scores) {
-          for (int32_t i = 0; i < m; ++i) o->scores[i] = o->scores[i] * boost;
-          // distinct scores can round to one product: restore (score desc, doc asc) among equals
-          if (o->docs)
-            for (int32_t i = 1; i < m; ++i)
-              for (int32_t j = i; j > 0 && o->scores[j - 1] == o->scores[j] && o->docs[j - 1] > o->docs[j]; --j) std::swap(o->docs[j - 1], o->docs[j]);
-        }
-      }
-    }
+    knn_unpack_topdocs((const uint64_t*)ho, (const uint32_t*)(ho + oh_cnt), k_stride, nq, k, false, total_vec, knn_request, boost, &out[q0]);
   }
   return NRTGPU_OK;
 }
@@ -762,41 +751,29 @@ extern "C" int nrtgpu_knn_search(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs,
   return knn_impl(ctx, segs, doc_bases, n_segs, field_id, sim, queries, n_queries, dim, k, boost, true, filter_mask, min_score, out);
 }
 
-extern "C" int nrtgpu_rescore_vectors(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
-                                      int32_t field_id, int32_t sim, const float* query, int32_t dim, float boost,
-                                      const int32_t* docs, const float* first_scores, int32_t n, double query_weight,
-                                      double rescore_weight, int32_t window, nrtgpu_topdocs* out) {
-  forget_foreign_hip_error();
-  if (!ctx || !query || !out || (n > 0 && (!docs || !first_scores)) || (n_segs > 0 && (!segs || !doc_bases)))
-    return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
-  if (n < 0 || dim <= 0 || sim < 0 || sim > 3 || window <= 0) return fail(NRTGPU_ERR_INVALID_ARG, "bad rescore arguments");
-  HIP_TRY(hipSetDevice(ctx->device));
-  PaddedQueries padded;   // (rows are resident padded to a multiple of 16 elements: the query likewise)
-  if (int rc = pad_query_vectors(segs, n_segs, field_id, query, 1, dim, &padded)) return rc;
-  query = padded.p;
-  dim = padded.dim;
-  float qn = 0.f;
-  for (int d = 0; d < dim; ++d) {
-    volatile float p2 = query[d] * query[d];
-    qn = qn + p2;
-  }
+// The two-call rescorer: QueryRescorer over a first pass's hits, for either element type (runtime_internal.h: RescoreKind).
+int nrtgpu::rt::rescore_hits_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, int32_t field_id,
+                                  const RescoreKind& kind, const int32_t* docs, const float* first_scores, int32_t n, double query_weight,
+                                  int32_t window, nrtgpu_topdocs* out) {
+  auto rows_of = [&](int si) -> const FieldData* {
+    auto fit = segs[si]->fields.find(field_id);
+    return fit != segs[si]->fields.end() && kind.rows(fit->second) ? &fit->second : nullptr;
+  };
   // hits -> (segment, vector row); per segment one gather kernel
   std::vector<int> seg_of((size_t)n, -1);
   std::vector<int64_t> row_of((size_t)n, -1);
   for (int i = 0; i < n; ++i) {
     for (int si = 0; si < n_segs; ++si) {
-      const int32_t local = docs[i] - doc_bases[si];
-      if (local < 0 || local >= segs[si]->max_doc) continue;
+      const int64_t local = (int64_t)docs[i] - (int64_t)doc_bases[si];
+      if (local < 0 || local >= (int64_t)segs[si]->max_doc) continue;
       seg_of[(size_t)i] = si;
-      auto fit = segs[si]->fields.find(field_id);
-      if (fit == segs[si]->fields.end() || !fit->second.d_vectors) break;
-      const FieldData& f = fit->second;
-      if (f.dim != dim) return fail(NRTGPU_ERR_INVALID_ARG, "vector dimension mismatch");
-      if (f.h_ord_to_doc.empty()) {
-        if (local < f.n_vec) row_of[(size_t)i] = local;
+      const FieldData* f = rows_of(si);
+      if (!f) break;
+      if (f->h_ord_to_doc.empty()) {
+        if (local < (int64_t)f->n_vec) row_of[(size_t)i] = local;
       } else {
-        auto it = std::lower_bound(f.h_ord_to_doc.begin(), f.h_ord_to_doc.end(), local);
-        if (it != f.h_ord_to_doc.end() && *it == local) row_of[(size_t)i] = it - f.h_ord_to_doc.begin();
+        auto it = std::lower_bound(f->h_ord_to_doc.begin(), f->h_ord_to_doc.end(), (int32_t)local);
+        if (it != f->h_ord_to_doc.end() && *it == (int32_t)local) row_of[(size_t)i] = it - f->h_ord_to_doc.begin();
       }
       break;
     }
@@ -804,43 +781,47 @@ extern "C" int nrtgpu_rescore_vectors(nrtgpu_ctx* ctx, const nrtgpu_seg* const* 
   }
   Slot* slot = nullptr;
   acquire_slot(ctx, &slot);
-  struct Guard { nrtgpu_ctx* c; Slot* s; ~Guard() { release_slot(c, s); } } guard{ctx, slot};
+  SlotGuard guard{ctx, slot};
   std::lock_guard<std::mutex> gpu(ctx->gpu_mu);
-  if (ctx->last_turn) HIP_TRY(hipStreamWaitEvent(slot->stream, ctx->last_turn, 0));
   hipStream_t st = slot->stream;
-  Carver wc;
-  const size_t o_q = wc.take((size_t)dim * 4), o_rows = wc.take((size_t)n * 8 + 8), o_first = wc.take((size_t)n * 4 + 4),
-               o_out = wc.take((size_t)n * 4 + 4);
-  if (int rc = slot->d_work.reserve(wc.off)) return rc;
-  char* wb = (char*)slot->d_work.p;
   std::vector<float> combined((size_t)n);
-  HIP_TRY(hipMemcpyAsync(wb + o_q, query, (size_t)dim * 4, hipMemcpyHostToDevice, st));
-  for (int si = 0; si < n_segs; ++si) {
-    std::vector<int> idx;
-    for (int i = 0; i < n; ++i)
-      if (seg_of[(size_t)i] == si) idx.push_back(i);
-    if (idx.empty()) continue;
-    auto fit = segs[si]->fields.find(field_id);
-    const FieldData* f = (fit != segs[si]->fields.end() && fit->second.d_vectors) ? &fit->second : nullptr;
-    std::vector<int64_t> rows(idx.size());
-    std::vector<float> first(idx.size()), res(idx.size());
-    for (size_t j = 0; j < idx.size(); ++j) {
-      rows[j] = row_of[(size_t)idx[j]];
-      first[j] = first_scores[idx[j]];
+  auto on_device = [&]() -> int {
+    if (ctx->last_turn) HIP_TRY(hipStreamWaitEvent(st, ctx->last_turn, 0));
+    Carver wc;
+    const size_t o_q = wc.take(kind.query_bytes), o_rows = wc.take((size_t)n * 8 + 8), o_first = wc.take((size_t)n * 4 + 4),
+                 o_out = wc.take((size_t)n * 4 + 4);
+    if (int rc = slot->d_work.reserve(wc.off)) return rc;
+    char* wb = (char*)slot->d_work.p;
+    HIP_TRY(hipMemcpyAsync(wb + o_q, kind.query, kind.query_bytes, hipMemcpyHostToDevice, st));
+    for (int si = 0; si < n_segs; ++si) {
+      std::vector<int> idx;
+      for (int i = 0; i < n; ++i)
+        if (seg_of[(size_t)i] == si) idx.push_back(i);
+      if (idx.empty()) continue;
+      const FieldData* f = rows_of(si);
+      if (!f) {  // no vectors in this leaf: the second pass matches nothing
+        for (int i : idx) combined[(size_t)i] = (float)(query_weight * (double)first_scores[i]);
+        continue;
+      }
+      std::vector<int64_t> rows(idx.size());
+      std::vector<float> first(idx.size()), res(idx.size());
+      for (size_t j = 0; j < idx.size(); ++j) {
+        rows[j] = row_of[(size_t)idx[j]];
+        first[j] = first_scores[idx[j]];
+      }
+      HIP_TRY(hipMemcpyAsync(wb + o_rows, rows.data(), rows.size() * 8, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(wb + o_first, first.data(), first.size() * 4, hipMemcpyHostToDevice, st));
+      kind.launch(st, *f, wb + o_q, (const int64_t*)(wb + o_rows), (const float*)(wb + o_first), (int32_t)idx.size(), (float*)(wb + o_out));
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(res.data(), wb + o_out, res.size() * 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));   // (the staging vectors of this leaf go out of scope)
+      for (size_t j = 0; j < idx.size(); ++j) combined[(size_t)idx[j]] = res[j];
     }
-    if (!f) {  // no vectors in this leaf: second pass matches nothing
-      for (size_t j = 0; j < idx.size(); ++j) combined[(size_t)idx[j]] = (float)(query_weight * (double)first[j]);
-      continue;
-    }
-    HIP_TRY(hipMemcpyAsync(wb + o_rows, rows.data(), rows.size() * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(wb + o_first, first.data(), first.size() * 4, hipMemcpyHostToDevice, st));
-    launch_rescore_vectors(st, f->d_vectors, f->d_vnorm2, dim, (const float*)(wb + o_q), qn, sim, boost,
-                           (const int64_t*)(wb + o_rows), (const float*)(wb + o_first), (int32_t)idx.size(), query_weight,
-                           rescore_weight, (float*)(wb + o_out));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(res.data(), wb + o_out, res.size() * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (size_t j = 0; j < idx.size(); ++j) combined[(size_t)idx[j]] = res[j];
+    return NRTGPU_OK;
+  };
+  if (int rc = on_device()) {
+    (void)hipStreamSynchronize(st);   // nothing of a failed call is in flight when the slot is released (its copies read this frame's vectors)
+    return rc;
   }
   // QueryRescorer: sort by (combined score desc, doc asc), keep the window
   std::vector<int> order((size_t)n);
@@ -859,4 +840,28 @@ extern "C" int nrtgpu_rescore_vectors(nrtgpu_ctx* ctx, const nrtgpu_seg* const* 
   out->total_hits = n;
   out->total_hits_is_lower_bound = 0;
   return NRTGPU_OK;
+}
+
+extern "C" int nrtgpu_rescore_vectors(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                      int32_t field_id, int32_t sim, const float* query, int32_t dim, float boost,
+                                      const int32_t* docs, const float* first_scores, int32_t n, double query_weight,
+                                      double rescore_weight, int32_t window, nrtgpu_topdocs* out) {
+  forget_foreign_hip_error();
+  if (!ctx || !query || !out || (n > 0 && (!docs || !first_scores)) || (n_segs > 0 && (!segs || !doc_bases)))
+    return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
+  if (n < 0 || dim <= 0 || sim < 0 || sim > 3 || window <= 0) return fail(NRTGPU_ERR_INVALID_ARG, "bad rescore arguments");
+  HIP_TRY(hipSetDevice(ctx->device));
+  for (int si = 0; si < n_segs; ++si)
+    if (!segs[si]) return fail(NRTGPU_ERR_INVALID_ARG, "segment %d is NULL", si);
+  PaddedQueries padded;   // (rows are resident padded to a multiple of 16 elements: the query likewise)
+  if (int rc = pad_query_vectors(segs, n_segs, field_id, query, 1, dim, &padded)) return rc;
+  const int32_t rdim = padded.dim;   // the RESIDENT dimension: every leaf's rows have it once pad_query_vectors has accepted the field
+  float qn = 0.f;
+  (void)stage_rescore_inputs(segs, doc_bases, n_segs, field_id, false, sim, padded.p, 1, rdim, nullptr, nullptr, &qn);
+  const RescoreKind kind{[](const FieldData& f) -> const void* { return f.d_vectors; }, padded.p, (size_t)rdim * 4,
+                         [&](hipStream_t st, const FieldData& f, const void* d_query, const int64_t* d_rows, const float* d_first, int32_t m, float* d_out) {
+                           launch_rescore_vectors(st, f.d_vectors, f.d_vnorm2, rdim, (const float*)d_query, qn, sim, boost, d_rows, d_first, m,
+                                                  query_weight, rescore_weight, d_out);
+                         }};
+  return rescore_hits_impl(ctx, segs, doc_bases, n_segs, field_id, kind, docs, first_scores, n, query_weight, window, out);
 }

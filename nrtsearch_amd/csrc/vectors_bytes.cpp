@@ -3,8 +3,8 @@
 // The host side of knn_bytes.hip, beside knn_impl (vectors.cpp) and a fraction of it: the pass over the rows returns RESULTS
 // (integers from the i8 matrix cores, mapped to score bits by plan.h: knn_byte_score), so there are no error bounds, no
 // rescoring, no certificate and no second pass here -- only the rounds that tighten theta and the selection they share with the
-// float search (knn.hip: knn_select_kernel<false>).  Workspace, stream, turn-taking, content locks, deadlines and statistics are
-// knn_impl's.
+// float search (knn.hip: knn_select_kernel<false>).  Turn-taking, the timed launches, the rounds, the statistics and the unpacking
+// are the float search's own code (runtime_internal.h: KnnRun, knn_unpack_topdocs), as is the rescorers' host path further down.
 #include "runtime_internal.h"
 
 static const uint32_t kKnnBytesCap = 1u << 18;   // candidate keys per query and round (2 MiB)
@@ -22,15 +22,7 @@ static int knn_bytes_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const 
   if (dim > 2048) return fail(NRTGPU_ERR_UNSUPPORTED, "vector dimension %d (device path takes <= 2048)", dim);
   // |q|^2 of every query; cosine refuses a zero query as the reference does (validateVectorForSearch, VectorFieldDef.java:853-861)
   std::vector<int32_t> qn2((size_t)n_queries);
-  for (int32_t q = 0; q < n_queries; ++q) {
-    int32_t s = 0;
-    for (int32_t d = 0; d < dim; ++d) {
-      const int32_t x = queries[(size_t)q * dim + d];
-      s += x * x;
-    }
-    if (sim == 0 && s == 0) return fail(NRTGPU_ERR_INVALID_ARG, "query %d is a zero vector: cosine similarity is not defined for it", q);
-    qn2[(size_t)q] = s;
-  }
+  if (int rc = byte_queries_stage(queries, n_queries, dim, sim, nullptr, qn2.data())) return rc;
   NRT_CHECK_DEADLINE("before the vector search started");
   HIP_TRY(hipSetDevice(ctx->device));
   for (int si = 0; si < n_segs; ++si)
@@ -50,20 +42,9 @@ static int knn_bytes_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const 
   const float score_boost = knn_request ? 1.0f : boost;   // the knn request: min_score tests the unboosted score, the boost comes afterwards
   Slot* slot = nullptr;
   acquire_slot(ctx, &slot);
-  struct Guard { nrtgpu_ctx* c; Slot* s; ~Guard() { release_slot(c, s); } } guard{ctx, slot};
+  SlotGuard guard{ctx, slot};
+  KnnRun run{ctx, slot};
   hipStream_t st = slot->stream;
-  auto take_turn = [&]() -> int {   // (vectors.cpp: knn_impl explains the ordering against the BM25 scorers)
-    std::lock_guard<std::mutex> gpu(ctx->gpu_mu);
-    if (ctx->last_turn) HIP_TRY(hipStreamWaitEvent(st, ctx->last_turn, 0));
-    return NRTGPU_OK;
-  };
-  auto end_turn = [&]() -> int {
-    std::lock_guard<std::mutex> gpu(ctx->gpu_mu);
-    HIP_TRY(hipEventRecord(slot->ev_turn, st));
-    ctx->last_knn_turn = slot->ev_turn;
-    return NRTGPU_OK;
-  };
-  const bool timing = ctx->cfg.collect_timing != 0;
   const size_t panel_max = knn_bytes_panel_bytes(dim, kKnnBytesMaxQ);
   Carver wc;
   // the head [o_p, o_th) is staged in pinned memory laid out alike: one copy per panel
@@ -129,100 +110,32 @@ static int knn_bytes_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const 
     memcpy(hs + o_qn, qn2.data() + q0, (size_t)nq * 4);
     HIP_TRY(hipMemcpyAsync(wb + o_p, hs + o_p, panel_bytes, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(wb + o_qn, hs + o_qn, o_th - o_qn, hipMemcpyHostToDevice, st));   // |q|^2, leaf table
-    size_t n_ev = 0;
-    // One pass over the rows of every leaf, in rounds with a selection in between (theta tightens from round to round): the first
-    // round gives every row a slot of the list; later rounds only append rows that beat theta, so they grow -- and after two
-    // selections the remaining launches run back to back with ONE selection behind them.  Rows in rising order of similarity could
-    // overflow a list: the selection flags that and the panel is redone in rounds no longer than the list (`safe`).
+    // One pass over the rows of every leaf in KnnRun::tile_rounds' rounds, always nominating.  Rows in rising order of similarity
+    // could overflow a list: the selection flags that and the panel is redone in rounds no longer than the list (`safe`).
     for (int safe = 0;; ++safe) {
-      if (int rc = take_turn()) return rc;
+      if (int rc = run.take_turn()) return rc;
       HIP_TRY(hipMemsetAsync(wb + o_th, 0, o_cd - o_th, st));  // theta, the running top-k, counters, flag
-      int64_t seen = 0, round = kFirstRound;
-      int selections = 0;
-      bool pending = false;
-      for (int64_t t = 0; t < total_tiles;) {
-        int64_t len = (safe || seen == 0) ? std::min<int64_t>(round, kKnnBytesCap >> 4) : round;
-        len = std::min<int64_t>(len, (int64_t)1 << 22);   // (a queue entry carries the padded row inside the launch in 26 bits)
-        const int64_t te = std::min<int64_t>(total_tiles, t + len);
-        const uint32_t blocks = (uint32_t)std::min<int64_t>(((te - t) * 16 + 255) / 256, (int64_t)std::max(ctx->n_cus, 1));
-        if (timing) {
-          while (slot->round_ev.size() < n_ev + 2) {
-            hipEvent_t ev = nullptr;
-            HIP_TRY(hipEventCreate(&ev));
-            slot->round_ev.push_back(ev);
-          }
-          HIP_TRY(hipEventRecord(slot->round_ev[n_ev], st));
-        }
-        const bool defer = !safe && selections >= 2;
-        const int e = launch_knn_bytes(st, blocks, (const DKnnBytesLeaf*)(wb + o_leaves), n_kleaves, dim, t, te, wb + o_p,
-                                       (const int32_t*)(wb + o_qn), nq, sim, score_boost, knn_request ? min_score : 0.0f,
-                                       (const unsigned long long*)(wb + o_th), (uint64_t*)(wb + o_cd), (uint32_t*)(wb + o_cc), kKnnBytesCap,
-                                       defer ? 1 : 0);
-        if (e) return fail(NRTGPU_ERR_HIP, "knn_bytes launch: %s", hipGetErrorString((hipError_t)e));
-        if (timing) {
-          HIP_TRY(hipEventRecord(slot->round_ev[n_ev + 1], st));
-          n_ev += 2;
-        }
-        if (defer) {
-          pending = true;
-        } else {
-          launch_knn_select(st, (uint32_t)nq, (uint64_t*)(wb + o_tk), (uint32_t*)(wb + o_tc), k_stride, (uint32_t)k,
-                            (const uint64_t*)(wb + o_cd), (uint32_t*)(wb + o_cc), kKnnBytesCap, (unsigned long long*)(wb + o_th),
-                            (uint32_t*)(wb + o_ov));
-          ++selections;
-        }
-        seen += te - t;
-        t = te;
-        round = safe ? std::min<int64_t>(round * 4, kKnnBytesCap >> 4) : std::min<int64_t>(seen * 15, (int64_t)1 << 36);
-      }
-      if (pending)
-        launch_knn_select(st, (uint32_t)nq, (uint64_t*)(wb + o_tk), (uint32_t*)(wb + o_tc), k_stride, (uint32_t)k,
-                          (const uint64_t*)(wb + o_cd), (uint32_t*)(wb + o_cc), kKnnBytesCap, (unsigned long long*)(wb + o_th),
-                          (uint32_t*)(wb + o_ov));
-      if (int rc = end_turn()) return rc;
+      auto launch = [&](int64_t t, int64_t te, uint32_t blocks, int32_t append_only) -> int {
+        return run.timed_launch("knn_bytes", [&]() {
+          return launch_knn_bytes(st, blocks, (const DKnnBytesLeaf*)(wb + o_leaves), n_kleaves, dim, t, te, wb + o_p, (const int32_t*)(wb + o_qn),
+                                  nq, sim, score_boost, knn_request ? min_score : 0.0f, (const unsigned long long*)(wb + o_th),
+                                  (uint64_t*)(wb + o_cd), (uint32_t*)(wb + o_cc), kKnnBytesCap, append_only);
+        });
+      };
+      if (int rc = run.tile_rounds(total_tiles, kFirstRound, kKnnBytesCap, true, safe, launch, [&]() {
+            launch_knn_select(st, (uint32_t)nq, (uint64_t*)(wb + o_tk), (uint32_t*)(wb + o_tc), k_stride, (uint32_t)k, (const uint64_t*)(wb + o_cd),
+                              (uint32_t*)(wb + o_cc), kKnnBytesCap, (unsigned long long*)(wb + o_th), (uint32_t*)(wb + o_ov));
+          }))
+        return rc;
+      if (int rc = run.end_turn()) return rc;
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipMemcpyAsync(ho, wb + o_tk, o_ov + 4 - o_tk, hipMemcpyDeviceToHost, st));   // the answer, its counts, the flag
       HIP_TRY(hipStreamSynchronize(st));
       if (*(const uint32_t*)(ho + oh_ov) == 0u) break;
       if (safe) return fail(NRTGPU_ERR_HIP, "knn_bytes: candidate list overflow in a bounded round");
     }
-    {
-      double ms = 0.0;
-      for (size_t i = 0; i + 1 < n_ev; i += 2) {
-        float one = 0.f;
-        (void)hipEventElapsedTime(&one, slot->round_ev[i], slot->round_ev[i + 1]);
-        ms += (double)one;
-      }
-      std::lock_guard<std::mutex> lk(ctx->stats_mu);
-      ctx->stats.knn_panels += 1;
-      ctx->stats.knn_score_launches += (int64_t)(n_ev / 2);
-      ctx->stats.knn_score_ms += ms;
-      ctx->stats.knn_rows += total_rows;
-    }
-    const uint64_t* keys = (const uint64_t*)ho;
-    const uint32_t* cnts = (const uint32_t*)(ho + oh_cnt);
-    for (int q = 0; q < nq; ++q) {
-      nrtgpu_topdocs* o = &out[q0 + q];
-      const int32_t cap = o->capacity > 0 ? o->capacity : k;
-      const int32_t m = std::min<int32_t>((int32_t)std::min<uint32_t>(cnts[q], (uint32_t)k), cap);
-      for (int32_t i = 0; i < m; ++i) {
-        if (o->docs) o->docs[i] = (int32_t)key_doc(keys[(size_t)q * k_stride + i]);
-        if (o->scores) o->scores[i] = key_score(keys[(size_t)q * k_stride + i]);
-      }
-      o->n_hits = m;
-      o->total_hits = live_vectors;   // every live doc with a vector matches an exact vector query
-      o->total_hits_is_lower_bound = 0;
-      if (knn_request) {
-        o->total_hits = m;  // the rewritten knn query matches exactly the docs it returns
-        if (boost != 1.0f && o->scores) {
-          for (int32_t i = 0; i < m; ++i) o->scores[i] = o->scores[i] * boost;
-          // distinct scores can round to one product: restore (score desc, doc asc) among equals
-          if (o->docs)
-            for (int32_t i = 1; i < m; ++i)
-              for (int32_t j = i; j > 0 && o->scores[j - 1] == o->scores[j] && o->docs[j - 1] > o->docs[j]; --j) std::swap(o->docs[j - 1], o->docs[j]);
-        }
-      }
-    }
+    run.add_stats(total_rows, 0, false);
+    knn_unpack_topdocs((const uint64_t*)ho, (const uint32_t*)(ho + oh_cnt), k_stride, nq, k, true, live_vectors, knn_request, boost, &out[q0]);
   }
   return NRTGPU_OK;
 }
@@ -243,7 +156,8 @@ extern "C" int nrtgpu_knn_search_bytes(nrtgpu_ctx* ctx, const nrtgpu_seg* const*
 
 // ---- the rescorers over a byte field: QueryRescore (rescore/QueryRescore.java:40-57) with the field's ExactByteVectorQuery
 // (VectorFieldDef.java:842) in the rescore slot -- nrtgpu_rescore_byte_vectors here, the tail of nrtgpu_search_hybrid_bytes_batch in
-// search.cpp: search_hybrid_impl, which stages its inputs through the three functions below ------------------------------------
+// search.cpp: search_hybrid_impl.  Both run the float rescorers' host code (vectors.cpp: rescore_hits_impl, stage_rescore_inputs);
+// here is what only a byte field asks: the refusals and the queries in piece order ------------------------------------------------
 // What the byte entries ask of their scalars, in knn_bytes_impl's order.
 int nrtgpu::rt::byte_rescore_check_args(int32_t sim, int32_t dim, float boost, int32_t window) {
   if (dim <= 0 || sim < 0 || sim > 3 || window <= 0) return fail(NRTGPU_ERR_INVALID_ARG, "bad rescore arguments");
@@ -270,29 +184,17 @@ int nrtgpu::rt::byte_queries_stage(const int8_t* queries, int32_t n, int32_t dim
   }
   return NRTGPU_OK;
 }
-// The field in every leaf: byte rows of the query's dimension, or absent.  `out` (may be NULL): the leaf table the kernel reads.
-int nrtgpu::rt::byte_rescore_leaves(const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, int32_t field_id, int32_t dim,
-                                    DByteVecSeg* out) {
+// The field in every leaf: byte rows of the query's dimension, or absent.
+int nrtgpu::rt::byte_rescore_check_leaves(const nrtgpu_seg* const* segs, int32_t n_segs, int32_t field_id, int32_t dim) {
   for (int si = 0; si < n_segs; ++si) {
-    DByteVecSeg v{};
     auto fit = segs[si]->fields.find(field_id);
-    if (fit != segs[si]->fields.end()) {
-      const FieldData& f = fit->second;
-      if (!f.byte_rows && (f.d_vectors || f.dim > 0))
-        return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d holds float (fp32) vectors: rescore it with nrtgpu_rescore_vectors / nrtgpu_search_hybrid_batch",
-                    si, field_id);
-      if (f.byte_rows && f.dim_user != dim)
-        return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d has dimension %d, query has %d", si, field_id, f.dim_user, dim);
-      if (f.byte_rows && f.d_btiles && f.n_vec > 0) {
-        v.tiles = f.d_btiles;
-        v.vnorm2 = f.d_bnorm2;
-        v.ord_to_doc = f.d_ord_to_doc;
-        v.n_vec = f.n_vec;
-      }
-    }
-    v.doc_base = doc_bases[si];
-    v.max_doc = segs[si]->max_doc;
-    if (out) out[si] = v;
+    if (fit == segs[si]->fields.end()) continue;
+    const FieldData& f = fit->second;
+    if (!f.byte_rows && (f.d_vectors || f.dim > 0))
+      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d holds float (fp32) vectors: rescore it with nrtgpu_rescore_vectors / nrtgpu_search_hybrid_batch",
+                  si, field_id);
+    if (f.byte_rows && f.dim_user != dim)
+      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d has dimension %d, query has %d", si, field_id, f.dim_user, dim);
   }
   return NRTGPU_OK;
 }
@@ -311,95 +213,17 @@ extern "C" int nrtgpu_rescore_byte_vectors(nrtgpu_ctx* ctx, const nrtgpu_seg* co
     return fail(NRTGPU_ERR_INVALID_ARG, "byte vector rescore: finite weights expected");
   std::vector<int8_t> qpad(byte_query_stride(dim));
   int32_t qn = 0;
-  if (int rc = byte_queries_stage(query, 1, dim, sim, qpad.data(), &qn)) return rc;
+  if (int rc = stage_rescore_inputs(segs, doc_bases, n_segs, field_id, true, sim, query, 1, dim, nullptr, qpad.data(), &qn)) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   for (int si = 0; si < n_segs; ++si)
     if (!segs[si]) return fail(NRTGPU_ERR_INVALID_ARG, "segment %d is NULL", si);
-  if (int rc = byte_rescore_leaves(segs, doc_bases, n_segs, field_id, dim, nullptr)) return rc;
-  // hits -> (segment, vector row), on the host as nrtgpu_rescore_vectors does; per segment one kernel
-  std::vector<int> seg_of((size_t)n, -1);
-  std::vector<int64_t> row_of((size_t)n, -1);
-  for (int i = 0; i < n; ++i) {
-    for (int si = 0; si < n_segs; ++si) {
-      const int64_t local = (int64_t)docs[i] - (int64_t)doc_bases[si];
-      if (local < 0 || local >= (int64_t)segs[si]->max_doc) continue;
-      seg_of[(size_t)i] = si;
-      auto fit = segs[si]->fields.find(field_id);
-      if (fit == segs[si]->fields.end() || !fit->second.d_btiles) break;
-      const FieldData& f = fit->second;
-      if (f.h_ord_to_doc.empty()) {
-        if (local < (int64_t)f.n_vec) row_of[(size_t)i] = local;
-      } else {
-        auto it = std::lower_bound(f.h_ord_to_doc.begin(), f.h_ord_to_doc.end(), (int32_t)local);
-        if (it != f.h_ord_to_doc.end() && *it == (int32_t)local) row_of[(size_t)i] = it - f.h_ord_to_doc.begin();
-      }
-      break;
-    }
-    if (seg_of[(size_t)i] < 0) return fail(NRTGPU_ERR_INVALID_ARG, "hit %d (doc %d) is outside every segment", i, docs[i]);
-  }
-  Slot* slot = nullptr;
-  acquire_slot(ctx, &slot);
-  struct Guard { nrtgpu_ctx* c; Slot* s; ~Guard() { release_slot(c, s); } } guard{ctx, slot};
-  std::lock_guard<std::mutex> gpu(ctx->gpu_mu);
-  hipStream_t st = slot->stream;
-  std::vector<float> combined((size_t)n);
-  auto on_device = [&]() -> int {
-    if (ctx->last_turn) HIP_TRY(hipStreamWaitEvent(st, ctx->last_turn, 0));
-    Carver wc;
-    const size_t o_q = wc.take(qpad.size()), o_rows = wc.take((size_t)n * 8 + 8), o_first = wc.take((size_t)n * 4 + 4),
-                 o_out = wc.take((size_t)n * 4 + 4);
-    if (int rc = slot->d_work.reserve(wc.off)) return rc;
-    char* wb = (char*)slot->d_work.p;
-    HIP_TRY(hipMemcpyAsync(wb + o_q, qpad.data(), qpad.size(), hipMemcpyHostToDevice, st));
-    for (int si = 0; si < n_segs; ++si) {
-      std::vector<int> idx;
-      for (int i = 0; i < n; ++i)
-        if (seg_of[(size_t)i] == si) idx.push_back(i);
-      if (idx.empty()) continue;
-      auto fit = segs[si]->fields.find(field_id);
-      const FieldData* f = (fit != segs[si]->fields.end() && fit->second.d_btiles) ? &fit->second : nullptr;
-      if (!f) {  // no vectors in this leaf: the second pass matches nothing
-        for (int i : idx) combined[(size_t)i] = (float)(query_weight * (double)first_scores[i]);
-        continue;
-      }
-      std::vector<int64_t> rows(idx.size());
-      std::vector<float> first(idx.size()), res(idx.size());
-      for (size_t j = 0; j < idx.size(); ++j) {
-        rows[j] = row_of[(size_t)idx[j]];
-        first[j] = first_scores[idx[j]];
-      }
-      HIP_TRY(hipMemcpyAsync(wb + o_rows, rows.data(), rows.size() * 8, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(wb + o_first, first.data(), first.size() * 4, hipMemcpyHostToDevice, st));
-      launch_rescore_byte_vectors(st, f->d_btiles, f->d_bnorm2, dim, wb + o_q, qn, sim, boost, (const int64_t*)(wb + o_rows),
-                                  (const float*)(wb + o_first), (int32_t)idx.size(), query_weight, rescore_weight, (float*)(wb + o_out));
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(res.data(), wb + o_out, res.size() * 4, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));   // (the staging vectors of this leaf go out of scope)
-      for (size_t j = 0; j < idx.size(); ++j) combined[(size_t)idx[j]] = res[j];
-    }
-    return NRTGPU_OK;
-  };
-  if (int rc = on_device()) {
-    (void)hipStreamSynchronize(st);   // nothing of a failed call is in flight when the slot is released (its copies read this frame's vectors)
-    return rc;
-  }
-  // QueryRescorer: sort by (combined score desc, doc asc), keep the window
-  std::vector<int> order((size_t)n);
-  for (int i = 0; i < n; ++i) order[(size_t)i] = i;
-  std::sort(order.begin(), order.end(), [&](int a, int b) {
-    if (combined[(size_t)a] != combined[(size_t)b]) return combined[(size_t)a] > combined[(size_t)b];
-    return docs[a] < docs[b];
-  });
-  const int32_t cap = out->capacity > 0 ? out->capacity : window;
-  const int32_t m = std::min<int32_t>(std::min<int32_t>(n, window), cap);
-  for (int32_t i = 0; i < m; ++i) {
-    if (out->docs) out->docs[i] = docs[order[(size_t)i]];
-    if (out->scores) out->scores[i] = combined[(size_t)order[(size_t)i]];
-  }
-  out->n_hits = m;
-  out->total_hits = n;
-  out->total_hits_is_lower_bound = 0;
-  return NRTGPU_OK;
+  if (int rc = byte_rescore_check_leaves(segs, n_segs, field_id, dim)) return rc;
+  const RescoreKind kind{[](const FieldData& f) -> const void* { return f.d_btiles; }, qpad.data(), qpad.size(),
+                         [&](hipStream_t st, const FieldData& f, const void* d_query, const int64_t* d_rows, const float* d_first, int32_t m, float* d_out) {
+                           launch_rescore_byte_vectors(st, f.d_btiles, f.d_bnorm2, dim, d_query, qn, sim, boost, d_rows, d_first, m, query_weight,
+                                                       rescore_weight, d_out);
+                         }};
+  return rescore_hits_impl(ctx, segs, doc_bases, n_segs, field_id, kind, docs, first_scores, n, query_weight, window, out);
 }
 
 // Needs no device: the one statement of the byte scores (plan.h), as the kernel compiles it.

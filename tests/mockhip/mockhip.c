@@ -24,6 +24,8 @@ hipError_t hipHostUnregister(void* p) { (void)p; return hipSuccess; }
 hipError_t hipHostGetDevicePointer(void** d, void* h, unsigned f) { (void)f; *d = h; return hipSuccess; }
 hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind k) { (void)k; if (n) memmove(d, s, n); return hipSuccess; }
 hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind k, hipStream_t st) { (void)k; (void)st; if (n) memmove(d, s, n); return hipSuccess; }
+hipError_t hipMemcpy2D(void* d, size_t dp, const void* s, size_t sp, size_t w, size_t h, hipMemcpyKind k) {
+  (void)k; for (size_t r = 0; r < h; ++r) memmove((char*)d + r * dp, (const char*)s + r * sp, w); return hipSuccess; }
 hipError_t hipMemset(void* d, int v, size_t n) { memset(d, v, n); return hipSuccess; }
 hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st) { (void)st; memset(d, v, n); return hipSuccess; }
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned f) { (void)f; *s = (hipStream_t)malloc(8); return hipSuccess; }
@@ -51,9 +53,26 @@ void mockhip_fail_next_launches(int n) { __atomic_store_n(&fail_launches, n, __A
 hipError_t hipGetLastError(void) { hipError_t e = sticky_error; sticky_error = hipSuccess; return e; }
 const char* hipGetErrorString(hipError_t e) { (void)e; return "mock hip"; }
 hipError_t hipFuncSetAttribute(const void* f, hipFuncAttribute a, int v) { (void)f; (void)a; (void)v; return hipSuccess; }
+// MOCKHIP_TRACE=<file>: one line per hipLaunchKernel -- the device kernel's name (remembered from __hipRegisterFunction), grid.x,
+// block.x, dynamic shared bytes -- so that a test can compare the launch schedule of two builds of the library
+static struct { const void* host; const char* name; } kernels[1024];
+static int n_kernels = 0;
+static FILE* trace_out = NULL;
+__attribute__((constructor)) static void trace_open(void) {   // (before any thread of the program exists)
+  const char* e = getenv("MOCKHIP_TRACE");
+  if (e && *e) trace_out = fopen(e, "w");
+}
+static void trace_launch(const void* f, dim3 g, dim3 b, size_t sm) {
+  if (!trace_out) return;
+  const char* name = "?";
+  for (int i = 0; i < n_kernels; ++i) if (kernels[i].host == f) { name = kernels[i].name; break; }
+  fprintf(trace_out, "%s %u %u %zu\n", name, g.x, b.x, sm);
+  fflush(trace_out);
+}
 hipError_t hipLaunchKernel(const void* f, dim3 g, dim3 b, void** args, size_t sm, hipStream_t s) {
-  (void)f; (void)g; (void)b; (void)args; (void)sm; (void)s;
+  (void)args; (void)s;
   ++n_launch;
+  trace_launch(f, g, b, sm);
   if (__atomic_load_n(&fail_launches, __ATOMIC_SEQ_CST) > 0 && __atomic_fetch_sub(&fail_launches, 1, __ATOMIC_SEQ_CST) > 0) {
     sticky_error = hipErrorLaunchFailure;
     return hipErrorLaunchFailure;
@@ -62,7 +81,10 @@ hipError_t hipLaunchKernel(const void* f, dim3 g, dim3 b, void** args, size_t sm
 }
 static void* fat_handle[4];
 void** __hipRegisterFatBinary(const void* data) { (void)data; return fat_handle; }
-void __hipRegisterFunction(void** m, const void* hf, char* df, const char* dn, unsigned tl, void* tid, void* bid, void* bd, void* gd, int* ws) { (void)m; (void)hf; (void)df; (void)dn; (void)tl; (void)tid; (void)bid; (void)bd; (void)gd; (void)ws; }
+void __hipRegisterFunction(void** m, const void* hf, char* df, const char* dn, unsigned tl, void* tid, void* bid, void* bd, void* gd, int* ws) {
+  (void)m; (void)df; (void)tl; (void)tid; (void)bid; (void)bd; (void)gd; (void)ws;
+  if (n_kernels < 1024) { kernels[n_kernels].host = hf; kernels[n_kernels].name = dn; ++n_kernels; }   // (before main: one thread)
+}
 void __hipRegisterVar(void** m, void* v, char* a, const char* b, int c, size_t d, int e, int f) { (void)m; (void)v; (void)a; (void)b; (void)c; (void)d; (void)e; (void)f; }
 void __hipUnregisterFatBinary(void** m) { (void)m; }
 static __thread dim3 cfg_g, cfg_b; static __thread size_t cfg_sm; static __thread hipStream_t cfg_s;
