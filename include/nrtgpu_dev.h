@@ -40,6 +40,12 @@ int64_t nrtgpu_debug_live_segments(nrtgpu_ctx* ctx);
  * merge's check and were run again, 1 once the library has switched speculation off for this context} -- the three
  * nrtgpu_stats.spec_* values on their own. */
 int  nrtgpu_debug_spec_counters(nrtgpu_ctx* ctx, int64_t* out3);
+/* TEST HOOK: which doc -> posting lookup structure the seal gave a term of a sealed segment (the MaxScore walk's later clauses;
+ * the policy and the budget nrtgpu_config.lookup_budget_pct: segment.cpp, build_term_aux).  *kind: 0 none (the term is searched
+ * in its cell of the tile-granular table), 1 records per 32 docs, 2 lookup cells; *shift: log2 of the docs per lookup cell
+ * (kind 2, else 0); *bytes: the structure's size.  Answers from the host's copy of the decision: no device work.
+ * NRTGPU_ERR_INVALID_ARG when the segment holds no such term. */
+int  nrtgpu_debug_term_lookup(const nrtgpu_seg* seg, int32_t field_id, int64_t term_hash, int32_t* kind, int32_t* shift, int64_t* bytes);
 
 #define NRTGPU_FLAG_PROFILE (7 << 8)  /* instrumented kernels (same results): per-item phase cycle and event counters
                                        * (nrtgpu_get_scan_profile, nrtgpu_get_maxscore_profile).  Bits 8-11 hold no other

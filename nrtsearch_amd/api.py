@@ -449,6 +449,13 @@ class GpuSegment:
     def device_bytes(self) -> int:
         return int(_lib.load().nrtgpu_segment_device_bytes(self._h))
 
+    def debug_term_lookup(self, field: int, term_id: int) -> Tuple[int, int, int]:
+        """Test hook of the development library (nrtgpu_debug_term_lookup): (kind, log2 docs per lookup cell, bytes) of the doc ->
+        posting lookup structure the seal gave the term: kind 0 none, 1 records per 32 docs, 2 lookup cells."""
+        kind, shift, nbytes = C.c_int32(-1), C.c_int32(-1), C.c_int64(-1)
+        _lib.check(_lib.load().nrtgpu_debug_term_lookup(self._h, int(field), int(term_id), C.byref(kind), C.byref(shift), C.byref(nbytes)))
+        return int(kind.value), int(shift.value), int(nbytes.value)
+
     def release(self) -> None:
         if getattr(self, "_h", None):
             _lib.load().nrtgpu_segment_release(self._h)

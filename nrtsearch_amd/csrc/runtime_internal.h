@@ -239,6 +239,12 @@ struct TermGroup {
   std::vector<uint32_t> h_count;
   bool has_freqs = false;
   uint64_t n_postings = 0;
+#ifdef NRTGPU_DEV
+  // what build_term_aux gave each term of the group (add order): kind | log2 docs per cell << 8, and the structure's bytes --
+  // the host's copy, for nrtgpu_debug_term_lookup (include/nrtgpu_dev.h)
+  std::vector<uint32_t> h_look_meta;
+  std::vector<uint64_t> h_look_cost;
+#endif
 };
 
 // Read-only open-addressing view of a field's term dictionary (built at seal): the planner does

@@ -430,6 +430,9 @@ static int build_term_aux(nrtgpu_seg* seg, TermGroup& g) {
   std::vector<uint64_t> look((size_t)nt, ~0ull);   // byte offset of the term's structure inside the group's buffer
   std::vector<uint32_t> meta((size_t)nt, 0u);      // kind | log2 docs per cell << 8
   std::vector<uint32_t> which[3];                  // per kind the terms that got it
+#ifdef NRTGPU_DEV
+  std::vector<uint64_t> cost_of((size_t)nt, 0ull); // bytes of the term's structure (nrtgpu_debug_term_lookup)
+#endif
   uint64_t look_bytes = 0;
   uint32_t max_count = 0, max_cells = 0;
   {
@@ -448,8 +451,12 @@ static int build_term_aux(nrtgpu_seg* seg, TermGroup& g) {
         // (every structure: 16-byte aligned, entry 0 readable for idle slots, one entry of slack behind the last doc's)
         if (r.kind == kLookBits) cost = (((((uint64_t)max_doc + 31ull) / 32ull + 1ull) * 8ull + 15ull) & ~15ull);
         else {
-          // cells of 2^shift docs, the largest power of two with at most one posting per cell on average
-          while (shift < 31u && (cnt << (shift + 1u)) <= (uint64_t)max_doc) ++shift;
+          // cells of 2^shift docs, the largest power of two with at most one posting per cell on average.  Packed postings: the
+          // walk's search compares doc offsets inside a 2^kPackDocBits-doc super-window (maxscore.hip: dd = d & kPackDocMask), and
+          // the offsets of a cell that spans two windows are not ascending -- a cell is one window at the most, as for the
+          // tile-granular table (kPackMaxCellShift).  Without the cap a 64-posting term of a 2^27-doc segment had cells of 2^21 docs.
+          const uint32_t max_shift = (seg->ctx->cfg.flags & NRTGPU_FLAG_PACKED_POSTINGS) ? kPackDocBits : 31u;
+          while (shift < max_shift && (cnt << (shift + 1u)) <= (uint64_t)max_doc) ++shift;
           const uint64_t n_cells = (((uint64_t)max_doc - 1ull) >> shift) + 1ull;
           cost = (((n_cells + 2ull) * 4ull + 15ull) & ~15ull);
         }
@@ -458,6 +465,9 @@ static int build_term_aux(nrtgpu_seg* seg, TermGroup& g) {
         look[t] = look_bytes;
         look_bytes += cost;
         meta[t] = r.kind | (shift << 8);
+#ifdef NRTGPU_DEV
+        cost_of[t] = cost;
+#endif
         which[r.kind].push_back(t);
         max_count = std::max(max_count, (uint32_t)cnt);
         if (r.kind == kLookCells) max_cells = std::max<uint32_t>(max_cells, (uint32_t)((((uint64_t)max_doc - 1ull) >> shift) + 2ull));
@@ -513,12 +523,34 @@ static int build_term_aux(nrtgpu_seg* seg, TermGroup& g) {
   free_tmp();
   if (e != hipSuccess) return fail(NRTGPU_ERR_HIP, "building the MaxScore lookup structures failed: %s", hipGetErrorString(e));
   for (uint32_t k = 1; k < 3; ++k) g.n_look[k] = (uint32_t)which[k].size();
+#ifdef NRTGPU_DEV
+  g.h_look_meta = std::move(meta);
+  g.h_look_cost = std::move(cost_of);
+#endif
   g.h_start.clear();
   g.h_start.shrink_to_fit();
   g.h_count.clear();
   g.h_count.shrink_to_fit();
   return NRTGPU_OK;
 }
+
+#ifdef NRTGPU_DEV
+// Test hook (include/nrtgpu_dev.h): what the seal gave a term -- host state only, no device work.
+extern "C" int nrtgpu_debug_term_lookup(const nrtgpu_seg* seg, int32_t field_id, int64_t term_hash, int32_t* kind, int32_t* shift, int64_t* bytes) {
+  if (!seg || !kind || !shift || !bytes) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
+  if (!seg->sealed) return fail(NRTGPU_ERR_STATE, "segment not sealed");
+  const auto fit = seg->fields.find(field_id);
+  const TermEntry* e = fit == seg->fields.end() ? nullptr : fit->second.flat.find(term_hash);
+  if (!e) return fail(NRTGPU_ERR_INVALID_ARG, "field %d has no term %lld in this segment", field_id, (long long)term_hash);
+  const TermGroup& g = fit->second.groups[e->group];
+  if ((size_t)e->aux_idx >= g.h_look_meta.size()) return fail(NRTGPU_ERR_STATE, "term %lld has no lookup record", (long long)term_hash);
+  const uint32_t m = g.h_look_meta[e->aux_idx];
+  *kind = (int32_t)(m & 255u);
+  *shift = (int32_t)((m >> 8) & 255u);
+  *bytes = (int64_t)g.h_look_cost[e->aux_idx];
+  return NRTGPU_OK;
+}
+#endif
 
 // NRTGPU_FLAG_PACKED_POSTINGS: the group's docid and code columns become ONE column of 32-bit words plus the group's
 // exception list (plan.h: kPack*); the two columns are freed.  From here on g.d_docids is the packed column and

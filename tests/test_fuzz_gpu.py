@@ -19,22 +19,31 @@ ROUNDS = int(os.environ.get("NRT_FUZZ_ROUNDS", "8"))
 
 
 @pytest.mark.parametrize("round_", range(ROUNDS))
-def test_fuzz_query_shapes(round_, monkeypatch):
+def test_fuzz_query_shapes(round_):
     rng = np.random.Generator(np.random.PCG64(20260925 + round_))
-    # which terms get membership records (segment.cpp: build_term_aux) decides between the two lookup paths of the MaxScore walk:
-    # a posting per 16 docs (nearly every lookup a binary search), the default, or every term (no binary search at all)
-    monkeypatch.setenv("NRTGPU_RECORD_DOCS_PER_POSTING", ["16", "128", "4096", str(1 << 30)][round_ % 4])
-    if round_ % 8 >= 4:
-        monkeypatch.setenv("NRTGPU_RECORD_MAX_TERMS", "3")
+    # which lookup structures the MaxScore walk's later clauses find (segment.cpp: build_term_aux) follows the lookup budget: none at
+    # all, records for the largest terms only, the default, every term served; and half the rounds keep their postings packed.
+    # Both from the round's number, not from rng: every round's corpus, masks and queries are what they were.
+    budget_pct = [-1, 2, 0, 100000][round_ % 4]
+    layout = _lib.NRTGPU_FLAG_PACKED_POSTINGS if round_ % 8 >= 4 else 0
     n_docs = int(rng.choice([900, 1024, 5_000, 33_000, 70_001, 200_000]))
     n_seg = int(rng.integers(1, 5))
     ranks = sorted(set(int(r) for r in np.floor(np.exp(rng.uniform(0, np.log(3000), size=14))).clip(1, 3000)))
     deletes = float(rng.choice([0.0, 0.0, 0.03, 0.3]))
     corpus = synth.build_corpus(n_docs, ranks, n_segments=n_seg, delete_fraction=deletes)
     flags = int(rng.choice([0, 0, _lib.NRTGPU_FLAG_NO_LIVE_FOLD, _lib.NRTGPU_FLAG_NO_FIXED_POINT]))
-    ctx = api.GpuContext(device_id=0, max_batch=64, flags=flags, target_items=int(rng.choice([0, 0, 64])))
+    ctx = api.GpuContext(device_id=0, max_batch=64, flags=flags | layout, target_items=int(rng.choice([0, 0, 64])), lookup_budget_pct=budget_pct)
     ix = Index(ctx, corpus)
     try:
+        if round_ % 4 in (0, 3):   # the budget is no dead knob: the same corpus weighs less with no structure (-1) than with every term served
+            other = api.GpuContext(device_id=0, max_batch=64, flags=flags | layout, lookup_budget_pct=100000 if budget_pct < 0 else -1)
+            ox = Index(other, corpus)
+            try:
+                mine, theirs = sum(l.device_bytes for l in ix.leaves), sum(l.device_bytes for l in ox.leaves)
+                assert (mine < theirs) if budget_pct < 0 else (theirs < mine), (budget_pct, mine, theirs)
+            finally:
+                ox.close()
+                other.close()
         masks = {}
         for mid in (1, 2):
             density = float(rng.choice([0.02, 0.4, 0.97]))
@@ -180,11 +189,6 @@ def test_fuzz_exact_vector_search(round_):
             hits.sort()
             return [(d, s) for _, d, s in hits[:k]], len(hits)
 
-        if dim % 16 != 0:
-            with pytest.raises(api.NrtGpuError) as e:
-                sr.knn_exact(5, "cosine", queries, 5)
-            assert e.value.code == -4      # the caller's path
-            return
         total_rows = sum(len(m[1]) for m in mats)
         checked = [int(i) for i in rng.choice(n_q, size=min(n_q, 3 if total_rows > 5000 else 6), replace=False)] + [0]
         for sim_name, sim in (("cosine", 0), ("dot_product", 1), ("l2_norm", 2), ("max_inner_product", 3)):
