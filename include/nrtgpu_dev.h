@@ -46,6 +46,17 @@ int  nrtgpu_debug_spec_counters(nrtgpu_ctx* ctx, int64_t* out3);
  * (kind 2, else 0); *bytes: the structure's size.  Answers from the host's copy of the decision: no device work.
  * NRTGPU_ERR_INVALID_ARG when the segment holds no such term. */
 int  nrtgpu_debug_term_lookup(const nrtgpu_seg* seg, int32_t field_id, int64_t term_hash, int32_t* kind, int32_t* shift, int64_t* bytes);
+/* TEST HOOK: the rounding bounds the exact float vector search certifies its answers with, from the library's own code
+ * (host_math.h: knn_bound32 / knn_bound16 / knn_sketch_scale; plan.h: knn_result_upper / knn_estimate_lower) -- no context, no
+ * device work.  sim 0-3 as in nrtgpu_knn_exact; dim: the RESIDENT dimension (the field's, rounded up to 16); q_norm2, q_l1,
+ * q_absmax: the query's |q|^2, 1-norm and largest |element|; nv_max / nv_min: the largest / smallest non-zero |v|^2 of the rows
+ * (+inf: none); rows_absmax: the rows' largest |element| (the leaf with the smallest one when there are several); score_boost:
+ * the boost inside the score (1 on the knn request path).  out10 = {E of an fp32 estimate, E of the fp16 sketch's estimate,
+ * knn_result_upper(m) under each of the two, knn_estimate_lower(s) under each of the two, the query's sketch scale, the rows',
+ * 1 when the query's scale is usable (else the panel nominates from the fp32 rows), 1 when the rows' is (else no sketch is
+ * built)}. */
+int  nrtgpu_debug_knn_bounds(int32_t sim, int32_t dim, double q_norm2, double q_l1, float q_absmax, double nv_max, double nv_min,
+                             float rows_absmax, float score_boost, double m, double s, double* out10);
 
 #define NRTGPU_FLAG_PROFILE (7 << 8)  /* instrumented kernels (same results): per-item phase cycle and event counters
                                        * (nrtgpu_get_scan_profile, nrtgpu_get_maxscore_profile).  Bits 8-11 hold no other

@@ -1009,6 +1009,20 @@ def slices(max_docs: Sequence[int], num_docs: Optional[Sequence[int]] = None, vi
     return out, sh[:n].tolist()
 
 
+def debug_knn_bounds(sim: int, dim: int, q_norm2: float, q_l1: float, q_absmax: float, nv_max: float, nv_min: float,
+                     rows_absmax: float, score_boost: float = 1.0, m: float = 0.0, s: float = 0.0) -> dict:
+    """Test hook of the development library (nrtgpu_debug_knn_bounds): the rounding bounds the exact float vector search certifies
+    its answers with, from the library's own code; `dim` is the resident dimension (a multiple of 16).  No context, no device."""
+    out = np.zeros(10, dtype=np.float64)
+    _lib.check(_lib.load().nrtgpu_debug_knn_bounds(int(sim), int(dim), float(q_norm2), float(q_l1), C.c_float(q_absmax), float(nv_max),
+                                                   float(nv_min), C.c_float(rows_absmax), C.c_float(score_boost), float(m), float(s),
+                                                   out.ctypes.data))
+    names = ("e32", "e16", "result_upper32", "result_upper16", "estimate_lower32", "estimate_lower16", "q_scale", "rows_scale")
+    d = {n: float(out[i]) for i, n in enumerate(names)}
+    d["q_scale_usable"], d["rows_scale_usable"] = bool(out[8]), bool(out[9])
+    return d
+
+
 def blend(retriever_docs: Sequence[np.ndarray], retriever_scores: Optional[Sequence[np.ndarray]] = None,
           boosts: Optional[Sequence[float]] = None, mode: str = "rrf", k: int = 60, start_hit: int = 0, top_hits: int = 10) -> TopDocs:
     """BlenderOperation.blend through the library (nrtgpu_blend): weighted RRF or score order, ties in the reference's order."""

@@ -55,3 +55,26 @@ extern "C" int nrtgpu_bench_closed_loop(nrtgpu_ctx* ctx, const nrtgpu_seg* const
   return NRTGPU_OK;
 }
 
+
+// Test hook (include/nrtgpu_dev.h): the exact vector search's certification bounds as the search computes them (host_math.h:
+// knn_bound32 / knn_bound16 / knn_sketch_scale; plan.h: knn_result_upper / knn_estimate_lower).  No context, no device work.
+extern "C" int nrtgpu_debug_knn_bounds(int32_t sim, int32_t dim, double q_norm2, double q_l1, float q_absmax, double nv_max, double nv_min,
+                                       float rows_absmax, float score_boost, double m, double s, double* out10) {
+  if (!out10 || sim < 0 || sim > 3 || dim <= 0 || (dim & 15)) return fail(NRTGPU_ERR_INVALID_ARG, "bad knn_bounds arguments");
+  float q_scale = 1.0f, rows_scale = 1.0f;
+  const bool q_ok = hostmath::knn_sketch_scale(q_absmax, &q_scale), rows_ok = hostmath::knn_sketch_scale(rows_absmax, &rows_scale);
+  const double e_rel = (double)hostmath::knn_e_rel(), b = (double)score_boost;
+  const float e32 = hostmath::knn_bound32(sim, dim, q_norm2, nv_max, b);
+  const float e16 = hostmath::knn_bound16(sim, dim, q_norm2, q_l1, 1.0 / (double)q_scale, nv_max, nv_min, 1.0 / (double)rows_scale, b);
+  out10[0] = (double)e32;
+  out10[1] = (double)e16;
+  out10[2] = knn_result_upper(sim, m, (double)e32, e_rel, b);
+  out10[3] = knn_result_upper(sim, m, (double)e16, e_rel, b);
+  out10[4] = knn_estimate_lower(sim, s, (double)e32, e_rel, b);
+  out10[5] = knn_estimate_lower(sim, s, (double)e16, e_rel, b);
+  out10[6] = (double)q_scale;
+  out10[7] = (double)rows_scale;
+  out10[8] = q_ok ? 1.0 : 0.0;
+  out10[9] = rows_ok ? 1.0 : 0.0;
+  return NRTGPU_OK;
+}

@@ -296,5 +296,65 @@ inline void plan_item_counts(const int64_t* cost, int32_t n, int64_t target_item
   for (size_t i = 0; i < frac.size() && given < target_items; ++i, ++given) items[frac[i].second]++;
 }
 
+// ---- exact vector search: the rounding bounds the answers are certified with (vectors.cpp: knn_impl) ----------------
+// |estimate - result| <= E: both are fp32 evaluations of the same length-dim sums, each within gamma = dim * 2^-24 (relative
+// to the sum of the terms' magnitudes) of the real value whatever the order; the maps to a score have slope <= 1 and add a
+// few roundings (e_rel).  Pure functions of the search's numbers -- dim is the RESIDENT dimension (a multiple of 16), nq the
+// query's |q|^2, nv_max / nv_min the largest / the smallest non-zero |v|^2 of the leaves (nv_min = +inf: none), score_boost the
+// boost inside the score (1 on the knn request path) -- so that a test can ask for them (include/nrtgpu_dev.h:
+// nrtgpu_debug_knn_bounds) and hold worst-case data against them without a device.
+constexpr double kKnnU32 = 0x1p-24;                      // fp32's unit roundoff
+inline float knn_e_rel() { return (float)(32.0 * kKnnU32); }
+inline double knn_gamma(int32_t dim) { return (double)(dim + 4) * kKnnU32; }
+// e_abs of plan.h's knn_result_upper / knn_estimate_lower for an estimate summed in fp32 in another order than the oracle's
+inline float knn_bound32(int32_t sim, int32_t dim, double nq, double nv_max, double score_boost) {
+  const double gam = knn_gamma(dim);
+  double e = 0.0;
+  if (sim == 0) e = 2.0 * gam * score_boost;
+  else if (sim == 1) e = 1.1 * gam * std::sqrt(nq * nv_max) * score_boost;
+  else if (sim == 2) e = 4.5 * gam * (nq + nv_max);   // squared-distance units, no boost
+  else e = 2.2 * gam * std::sqrt(nq * nv_max) * score_boost;
+  return std::nextafter((float)((e + 4.0 * kKnnU32) * (1.0 + 1e-6)), INFINITY);
+}
+// The fp16 sketch (knn.hip): rows and queries rounded to 11 significant bits (relative 2^-11 each), products exact in fp32,
+// fp32 accumulation; elements that fall under fp16's normal range (2^-14 after scaling: 2^-28 of the largest) may be flushed.
+//   |dot16 - q.v| <= (2^-10 + 2^-22 + 4 gamma) sum |q_i v_i|  +  |q|_1 * 2^-14 / rows' scale  +  |v|_1 * 2^-14 / query's scale
+// with sum |q_i v_i| <= |q||v| and |v|_1 <= sqrt(dim) |v|.  Cosine divides by the row's own |v|: the first term's |v| cancels,
+// the flush terms need the smallest non-zero |v| of the leaves.  On top: the fp32 bound above (the estimate's norms are fp32).
+// q_l1: the query's 1-norm; q_unit / rows_unit: 1 / the power of two the query / the rows (the largest over the leaves) were
+// multiplied by.
+inline float knn_bound16(int32_t sim, int32_t dim, double nq, double q_l1, double q_unit, double nv_max, double nv_min, double rows_unit,
+                         double score_boost) {
+  const double gam = knn_gamma(dim);
+  const double e32 = (double)knn_bound32(sim, dim, nq, nv_max, score_boost);
+  // (4 gamma for the accumulation: the matrix cores' internal summation tree is not specified to round to nearest at every node)
+  const double e16 = std::ldexp(1.0, -10) + std::ldexp(1.0, -22) + 4.0 * gam;
+  const double flush = q_l1 * std::ldexp(1.0, -14) * rows_unit + std::sqrt((double)dim * nv_max) * std::ldexp(1.0, -14) * q_unit;
+  const double e_dot = 1.01 * (e16 * std::sqrt(nq * nv_max) + flush);
+  double e = 0.0;
+  if (sim == 0) e = 0.5 * 1.01 * (e16 + (nq > 0.0 && std::isfinite(nv_min) ? flush / std::sqrt(nq * nv_min) : 0.0)) * score_boost;
+  else if (sim == 1) e = 0.5 * e_dot * score_boost;
+  else if (sim == 2) e = 2.0 * e_dot;
+  else e = e_dot * score_boost;
+  // (+ 32 u: the kernel maps the dot product to a score with hardware rsq / rcp and a handful of fp32 roundings, scores <= 1;
+  //  MAXIMUM_INNER_PRODUCT's unbounded scores take theirs from e_rel)
+  return std::nextafter((float)((e + e32 + 32.0 * kKnnU32 * (sim == 2 ? 4.0 : score_boost)) * (1.0 + 1e-6)), INFINITY);
+}
+// The power of two a field's rows (or a query) are multiplied by before they are rounded to fp16: the largest |element| lands in
+// [2^13, 2^14).  false: no sketch from this scale -- it or its reciprocal (what the estimates are multiplied back by) is not a
+// finite normal float (a largest |element| below 2^-112: 2^(14 - e) overflows or its reciprocal is subnormal), or absmax is not
+// finite; *scale is then 1 and the search nominates from the fp32 rows.  A zero field or query keeps the scale 1 and is usable.
+inline bool knn_sketch_scale(float absmax, float* scale) {
+  *scale = 1.0f;
+  if (!std::isfinite(absmax)) return false;
+  if (!(absmax > 0.f)) return true;
+  int e = 0;
+  (void)std::frexp(absmax, &e);   // absmax < 2^e
+  const float s = std::ldexp(1.0f, 14 - e);
+  if (!std::isnormal(s) || !std::isnormal(1.0f / s)) return false;
+  *scale = s;
+  return true;
+}
+
 }  // namespace hostmath
 }  // namespace nrtgpu

@@ -869,6 +869,10 @@ int nrtgpu::rt::ensure_vector_sketch(const nrtgpu_seg* seg, int32_t field_id) {
   std::lock_guard<std::mutex> lk(seg->core->sketch_mu);
   if (f.sketch_state != 0) return NRTGPU_OK;   // built already, or never
   HIP_TRY(hipSetDevice(seg->core->device));
+  if (!hostmath::knn_sketch_scale(f.absmax, &f.sketch_scale)) {   // rows too small for a finite scale: the fp32 pass serves the field
+    f.sketch_state = -1;
+    return NRTGPU_OK;
+  }
   void* p = nullptr;
   const size_t bytes = knn_sketch_bytes(f.dim, f.n_vec) + 256;
   if (hipMalloc(&p, bytes) != hipSuccess) {
@@ -876,9 +880,6 @@ int nrtgpu::rt::ensure_vector_sketch(const nrtgpu_seg* seg, int32_t field_id) {
     f.sketch_state = -1;
     return NRTGPU_OK;
   }
-  int e = 0;
-  (void)std::frexp(f.absmax, &e);   // absmax < 2^e
-  f.sketch_scale = f.absmax > 0.f ? std::ldexp(1.0f, 14 - e) : 1.0f;
   launch_knn_sketch_build(nullptr, f.d_vectors, f.dim, f.n_vec, f.sketch_scale, p);
   hipError_t he = hipGetLastError();
   if (he == hipSuccess) he = hipStreamSynchronize(nullptr);

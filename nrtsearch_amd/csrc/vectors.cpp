@@ -232,41 +232,16 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
     total_tiles += ((int64_t)f.n_vec + 15) >> 4;
     total_rows += f.n_vec;
   }
-  // |estimate - result| <= E: both are fp32 evaluations of the same length-dim sums, each within gamma = dim * 2^-24 (relative
-  // to the sum of the terms' magnitudes) of the real value whatever the order; the maps to a score have slope <= 1 and add a
-  // few roundings (erel).  DESIGN §4.5 derives the constants.
-  const double u_fp32 = std::ldexp(1.0, -24), gam = (double)(dim + 4) * u_fp32;
+  // |estimate - result| <= E, the e_abs of plan.h's knn_result_upper / knn_estimate_lower: host_math.h states the bounds
+  // (knn_bound32 for an fp32 estimate in the MFMA's order, knn_bound16 for the fp16 sketch's) and DESIGN §4.5 derives the constants.
   const float score_boost = knn_request ? 1.0f : boost;
-  const float erel = (float)(32.0 * u_fp32);
-  auto bound_of = [&](double nq) {   // e_abs of plan.h's knn_result_upper / knn_estimate_lower
-    double e = 0.0;
-    if (sim == 0) e = 2.0 * gam * (double)score_boost;
-    else if (sim == 1) e = 1.1 * gam * std::sqrt(nq * nv_max) * (double)score_boost;
-    else if (sim == 2) e = 4.5 * gam * (nq + nv_max);   // squared-distance units, no boost
-    else e = 2.2 * gam * std::sqrt(nq * nv_max) * (double)score_boost;
-    return std::nextafter((float)((e + 4.0 * u_fp32) * (1.0 + 1e-6)), INFINITY);
-  };
-  // The fp16 sketch (knn.hip): rows and queries rounded to 11 significant bits (relative 2^-11 each), products exact in fp32,
-  // fp32 accumulation; elements that fall under fp16's normal range (2^-14 after scaling: 2^-28 of the largest) may be flushed.
-  //   |dot16 - q.v| <= (2^-10 + 2^-22 + 4 gamma) sum |q_i v_i|  +  |q|_1 * 2^-14 / rows' scale  +  |v|_1 * 2^-14 / query's scale
-  // with sum |q_i v_i| <= |q||v| and |v|_1 <= sqrt(dim) |v|.  Cosine divides by the row's own |v|: the first term's |v| cancels,
-  // the flush terms need the smallest non-zero |v| of the leaves.  On top: the fp32 bound above (the estimate's norms are fp32).
+  const float erel = hostmath::knn_e_rel();
+  auto bound_of = [&](double nq) { return hostmath::knn_bound32(sim, dim, nq, nv_max, (double)score_boost); };
   // (the query panel in fp16 and at least a small nomination queue behind it must fit the CU's 160 KB of LDS)
   const bool sketch_ok = all_sketched && any_vectors && std::isfinite(nv_max) &&
                          knn_sketch_fits(dim, std::min(n_queries, dim > 1280 ? 16 : kKnnMaxQ));
-  auto bound16_of = [&](double nq, double q_l1, double q_unit, double e32) {
-    // (4 gamma for the accumulation: the matrix cores' internal summation tree is not specified to round to nearest at every node)
-    const double e16 = std::ldexp(1.0, -10) + std::ldexp(1.0, -22) + 4.0 * gam;
-    const double flush = q_l1 * std::ldexp(1.0, -14) * rows_unit + std::sqrt((double)dim * nv_max) * std::ldexp(1.0, -14) * q_unit;
-    const double e_dot = 1.01 * (e16 * std::sqrt(nq * nv_max) + flush);
-    double e = 0.0;
-    if (sim == 0) e = 0.5 * 1.01 * (e16 + (nq > 0.0 && std::isfinite(nv_min) ? flush / std::sqrt(nq * nv_min) : 0.0)) * (double)score_boost;
-    else if (sim == 1) e = 0.5 * e_dot * (double)score_boost;
-    else if (sim == 2) e = 2.0 * e_dot;
-    else e = e_dot * (double)score_boost;
-    // (+ 32 u: the kernel maps the dot product to a score with hardware rsq / rcp and a handful of fp32 roundings, scores <= 1;
-    //  MAXIMUM_INNER_PRODUCT's unbounded scores take theirs from e_rel)
-    return std::nextafter((float)((e + e32 + 32.0 * u_fp32 * (sim == 2 ? 4.0 : (double)score_boost)) * (1.0 + 1e-6)), INFINITY);
+  auto bound16_of = [&](double nq, double q_l1, double q_unit) {
+    return hostmath::knn_bound16(sim, dim, nq, q_l1, q_unit, nv_max, nv_min, rows_unit, (double)score_boost);
   };
   // Rows are scored in rounds with a selection in between (theta tightens from round to round).  The first round of
   // a panel gives every row a slot of the candidate list; later rounds only append rows that beat theta, so they can
@@ -323,11 +298,11 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
       eb[(size_t)q] = bound_of((double)s2);
       const float q_max = q_max_of[q];
       const double q_l1 = q_l1_of[q];
-      int e2 = 0;
-      (void)std::frexp(q_max, &e2);   // q_max < 2^e2: the scaled query's largest |element| is below 2^14
-      qsc[(size_t)q] = (q_max > 0.f && std::isfinite(q_max)) ? std::ldexp(1.0f, 14 - e2) : 1.0f;
-      eb16[(size_t)q] = bound16_of((double)s2, q_l1, 1.0 / (double)qsc[(size_t)q], (double)eb[(size_t)q]);
-      if (!std::isfinite(q_max) || !std::isfinite(eb16[(size_t)q])) panel_sketch = false;
+      // the scaled query's largest |element| is below 2^14; a query too small for such a scale (or not finite) sends the panel
+      // to the fp32 rows
+      const bool q_scaled = hostmath::knn_sketch_scale(q_max, &qsc[(size_t)q]);
+      eb16[(size_t)q] = bound16_of((double)s2, q_l1, 1.0 / (double)qsc[(size_t)q]);
+      if (!q_scaled || !std::isfinite(eb16[(size_t)q])) panel_sketch = false;
     }
     memcpy(hs + o_q, queries + (size_t)q0 * dim, (size_t)nq * dim * 4);
     HIP_TRY(hipMemcpyAsync(wb + o_q, hs + o_q, (size_t)nq * dim * 4, hipMemcpyHostToDevice, st));

@@ -1,9 +1,10 @@
-"""Soundness of the rounding bounds the exact vector search certifies its answers with (nrtsearch_amd/csrc/vectors.cpp:
-bound_of / bound16_of, plan.h: knn_result_upper / knn_estimate_lower), checked on the CPU: the two kinds of ESTIMATE the matrix-core
+"""Soundness of the rounding bounds the exact vector search certifies its answers with (nrtsearch_amd/csrc/host_math.h:
+knn_bound32 / knn_bound16, plan.h: knn_result_upper / knn_estimate_lower), checked on the CPU: the two kinds of ESTIMATE the matrix-core
 passes produce are emulated in numpy -- an fp32 dot product summed in another order than the oracle's, and the fp16 sketch (rows and
 query scaled by a power of two, rounded to fp16, products exact, fp32 accumulation) -- and |estimate - result| must stay inside the
 bound for every row, where the result is the oracle's scalar left-to-right fp32 sum.  The formulas are restated here from the C++;
-what the test pins is the mathematics (worst-case data included), the GPU tests pin the code."""
+what the test pins is the mathematics (worst-case data included); tests/test_knn_adversarial_host.py and tests/test_knn_adversarial_gpu.py
+pin the code."""
 import numpy as np
 import pytest
 
