@@ -75,6 +75,17 @@ int  nrtgpu_get_scan_profile(nrtgpu_ctx* ctx, double* out16);
  * [12] waves in part prologues, [13] waves walking windows, [14] the item's last wave running out of windows, [15] item
  * epilogue ([10]-[13]: summed over the item's 12 waves) */
 int  nrtgpu_get_maxscore_profile(nrtgpu_ctx* ctx, double* out16);
+/* the same flag, the MaxScore route's MEETINGS (all twelve waves of a workgroup stop: maxscore.hip, ms_compact); sums over items
+ * since the last reset: out4 = {meetings, meetings called because the candidate buffer overflowed, meetings that compacted the
+ * buffer (= nrtgpu_get_maxscore_profile [1]), speculative estimates made by ONE wave while the others walked on (ms_estimate)}.
+ * A meeting that is no overflow meeting was called for a speculative estimate alone: none in the product's walk, where the
+ * estimate has left the meeting; NRTGPU_MS_SPEC_MEET=1 (environment, this library only, read per call) brings them back for an
+ * A/B in one process. */
+int  nrtgpu_debug_maxscore_meetings(nrtgpu_ctx* ctx, int64_t* out4);
+/* TEST HOOK: the one-wave selection the estimator uses (topk.hiph: topk_kth_wave), run by a one-wave kernel over keys[0..n)
+ * held in LDS as the walk holds them: *out = the r-th largest (1-based) of the keys, a zero key being an unwritten slot (it ranks
+ * below every key).  1 <= r <= n <= the walk's candidate buffer (2304 slots). */
+int  nrtgpu_debug_wave_kth(const uint64_t* keys, int32_t n, int32_t r, uint64_t* out);
 /* the same flag: WHEN the pieces of the last MaxScore launch ran.  Per output slot eight words -- {start, end} on the device's
  * 100 MHz wall clock, the item worked on, the doc windows walked, when the workgroup's round began (persistent workgroups choose
  * work round after round), the CU (XCC << 8 | SE, SH, CU), the round, the workgroup; a slot nobody used is all zeros.  The first

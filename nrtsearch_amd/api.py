@@ -273,6 +273,12 @@ class GpuContext:
                  "waves_walk_cycles", "last_wave_out_cycles", "epilogue_cycles"]
         return dict(zip(names, out.tolist()))
 
+    def maxscore_meetings(self) -> dict:
+        """The MaxScore route's meetings since reset_stats (nrtgpu_debug_maxscore_meetings; development library, NRTGPU_FLAG_PROFILE)."""
+        out = np.zeros(4, dtype=np.int64)
+        _lib.check(_lib.load().nrtgpu_debug_maxscore_meetings(self._h, out.ctypes.data))
+        return dict(zip(["meetings", "overflow_meetings", "compactions", "wave_estimates"], (int(x) for x in out)))
+
     @staticmethod
     def set_thread_deadline(seconds_from_now: Optional[float]) -> None:
         """The calling thread's deadline for the search calls it makes from now on (nrtgpu_set_thread_deadline_ns): None = no deadline."""
@@ -1021,6 +1027,15 @@ def debug_knn_bounds(sim: int, dim: int, q_norm2: float, q_l1: float, q_absmax: 
     d = {n: float(out[i]) for i, n in enumerate(names)}
     d["q_scale_usable"], d["rows_scale_usable"] = bool(out[8]), bool(out[9])
     return d
+
+
+def debug_wave_kth(keys: np.ndarray, r: int) -> int:
+    """Test hook of the development library (nrtgpu_debug_wave_kth): the r-th largest (1-based) of the packed 64-bit keys as ONE
+    wave selects it (topk.hiph: topk_kth_wave -- the MaxScore walk's estimator); a zero key is an unwritten slot."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    out = np.zeros(1, dtype=np.uint64)
+    _lib.check(_lib.load().nrtgpu_debug_wave_kth(keys.ctypes.data, len(keys), int(r), out.ctypes.data))
+    return int(out[0])
 
 
 def blend(retriever_docs: Sequence[np.ndarray], retriever_scores: Optional[Sequence[np.ndarray]] = None,

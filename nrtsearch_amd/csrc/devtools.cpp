@@ -78,3 +78,28 @@ extern "C" int nrtgpu_debug_knn_bounds(int32_t sim, int32_t dim, double q_norm2,
   out10[9] = rows_ok ? 1.0 : 0.0;
   return NRTGPU_OK;
 }
+
+// The MaxScore route's meetings (include/nrtgpu_dev.h), from the instrumented kernels' per-item counters (search.cpp takes them
+// out of the profile rows).
+extern "C" int nrtgpu_debug_maxscore_meetings(nrtgpu_ctx* ctx, int64_t* out4) {
+  if (!ctx || !out4) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lk(ctx->stats_mu);
+  for (int i = 0; i < 4; ++i) out4[i] = ctx->ms_meetings[i];
+  return NRTGPU_OK;
+}
+
+// Test hook (include/nrtgpu_dev.h): the one-wave selection of the MaxScore walk's estimator on keys of the caller's.
+extern "C" int nrtgpu_debug_wave_kth(const uint64_t* keys, int32_t n, int32_t r, uint64_t* out) {
+  if (!keys || !out || n < 1 || n > kMsCandCap || r < 1 || r > n) return fail(NRTGPU_ERR_INVALID_ARG, "bad wave_kth arguments (1 <= r <= n <= %d)", kMsCandCap);
+  uint64_t* d = nullptr;
+  if (hipMalloc((void**)&d, ((size_t)n + 1) * sizeof(uint64_t)) != hipSuccess) return fail(NRTGPU_ERR_OOM, "hipMalloc");
+  hipError_t e = hipMemcpy(d, keys, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    launch_debug_wave_kth(nullptr, d, (uint32_t)n, (uint32_t)r, d + n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(out, d + n, sizeof(uint64_t), hipMemcpyDeviceToHost);   // (the null stream: behind the kernel)
+  (void)hipFree(d);
+  if (e != hipSuccess) return fail(NRTGPU_ERR_HIP, "wave_kth: %s", hipGetErrorString(e));
+  return NRTGPU_OK;
+}

@@ -73,8 +73,13 @@ struct alignas(16) WClause {
 };
 static_assert(sizeof(WClause) == 80, "WClause layout");
 
+// theta and thr are written in meetings (ms_compact: every wave is there) AND, since the speculative estimate left the meeting,
+// by the one wave that makes an estimate (ms_estimate) while the others walk.  Both only grow -- the estimator writes only a
+// guess above theta, meetings and estimates never run at the same time (the estimator is one of the waves a meeting waits for)
+// -- and each is a valid bound on its own: a reader that gets one new and one old value skips no more than either allows.
 struct MsSmem {
-  uint64_t cand[kMsCandCap];               // competitive hits of the item (packed keys), unordered
+  uint64_t cand[kMsCandCap];               // competitive hits of the item (packed keys), unordered; slots at and above the live
+                                           // prefix read 0 until they are written (ms_estimate reads while others append)
   uint32_t tab[kTabTerms][kTabEntries];    // fixed-point BM25 score of (freq, norm byte) for the item's densest terms
   float    cache[kLdsCaches][256];         // BM25 normInverse tables of the query's fields (division path, bounds)
   uint32_t seen[kMsWaves][kMsWinWords];    // per wave: docs of its window that have been evaluated
@@ -84,7 +89,10 @@ struct MsSmem {
   uint64_t thr;          // acc_threshold(theta): what running sums are compared with
   uint32_t cnt;          // entries in cand
   uint32_t cnt_valid;    // entries of cand that are complete when cnt ran past kMsCandCap
-  uint32_t rz_flag;      // a wave could not reserve candidate slots (or a new speculative theta is due): everybody meet
+  uint32_t rz_flag;      // a wave could not reserve candidate slots (A/B, spec_meet: or a new speculative theta is due): everybody meet
+  uint32_t spec_busy;    // speculation: a wave is making an estimate (ms_estimate; taken by compare-and-swap: one at a time)
+  uint32_t spec_meet;    // A/B (development build, plan.h: DHelp.spec_sched bit 16): estimates are made in meetings, as before
+  uint32_t n_meet, n_over, n_est;   // instrumented kernels: meetings, those called by an overflow, estimates made by one wave
   uint32_t wins_started; // doc windows this workgroup's waves have taken so far (of the item it works on)
   uint32_t spec_at;      // speculation: the next estimate is due when wins_started reaches this (0: never)
   uint32_t q_wins;       // doc windows of ALL items of the query
@@ -194,6 +202,10 @@ __device__ __noinline__ void ms_compact(__attribute__((address_space(3))) MsSmem
   const uint32_t cnt_raw = s.cnt;
   const uint32_t cnt0 = cnt_raw > (uint32_t)kMsCandCap ? s.cnt_valid : cnt_raw;  // failed reservations inflate cnt
   __syncthreads();
+  if (tid == 0) {
+    s.n_meet += 1u;
+    if (cnt_raw > (uint32_t)kMsCandCap) s.n_over += 1u;
+  }
   // Speculation (plan.h: kHitsSpecInvalid): this workgroup has taken wins_started of the query's q_wins doc windows, so about
   // m = k x that fraction of the query's final top-k are among the keys it holds -- their (m + z sqrt(m) + 1)-th best is a
   // guess at the final k-th key, z standard deviations on the safe side.  Windows that are only begun count as walked: the
@@ -213,6 +225,9 @@ __device__ __noinline__ void ms_compact(__attribute__((address_space(3))) MsSmem
     const uint64_t thr = topk_kth_union<kMsThreads>(s.cand, cnt0, k, &s.sc, [](auto&&) {}, k2);
     const uint32_t q2_hi = s.sc.q2_hi;  // (stable until the next selection)
     const uint32_t kept = topk_keep_ge<kMsThreads, kMsCandCap>(s.cand, cnt0, thr, &s.sc);
+    // (what lies behind the kept keys reads 0 again: ms_estimate takes a non-zero slot for a key of the current prefix, and a
+    //  stale copy of a kept key would push its r-th best, the guess, UP)
+    for (uint32_t i = kept + tid; i < (uint32_t)kMsCandCap; i += kMsThreads) s.cand[i] = 0ull;
     if (tid == 0) {
       s.cnt = kept;
       if (thr > s.theta) {
@@ -259,6 +274,48 @@ __device__ __forceinline__ bool ms_meet(MsSmem& s, uint32_t k, int fx_E, unsigne
   if (!__hip_atomic_load(&s.rz_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) return false;
   ms_compact((__attribute__((address_space(3))) MsSmem*)&s, k, fx_E, theta_g, xch, query);
   return true;
+}
+
+// ONE wave, no barrier: the speculative estimate (see ms_compact) made while the other waves walk on.  Called at a window's head
+// by the wave whose lane 0 found an estimate due and took s.spec_busy.  A meeting would stop twelve waves for something that
+// only READS the candidate buffer; an overflow meeting still estimates for free from its histogram.
+//   * s.sc is this wave's meanwhile: a compaction starts behind a barrier that this wave has to reach as well.
+//   * The others keep appending: a slot below s.cnt that is reserved but not yet written reads 0 (the item's prologue and every
+//     compaction zero what lies behind the live prefix), and a 64-bit store caught half-way reads at most the key.  Either
+//     makes the r-th best of what this wave sees LOWER than that of the completed buffer, never higher (topk.hiph:
+//     topk_kth_wave) -- the guess errs to the safe side.
+//   * s.cnt past the buffer's end: an overflow meeting is on its way and makes the estimate.
+__device__ __noinline__ void ms_estimate(__attribute__((address_space(3))) MsSmem* sp, uint32_t k, int fx_E,
+                                         unsigned long long* theta_g, const DExchange* xch) {
+  MsSmem& s = *(MsSmem*)sp;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t ws = (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(&s.wins_started, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+  const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(&s.spec_at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+  const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(&s.cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+  // (still due?  The estimator before me may have moved spec_at between my look at it and my taking the role)
+  if (at != 0u && ws >= at && n <= (uint32_t)kMsCandCap) {
+    const bool exchanging = xch && xch->world > 1u;
+    uint32_t r = 0;
+    if (s.spec_z16 != 0u && !exchanging && __hip_atomic_load(&s.prune_on, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0u) {   // as ms_compact
+      const float m = (float)k * fminf(1.0f, (float)ws / (float)max(s.q_wins, 1u));
+      const float rr = m + (float)s.spec_z16 * (1.0f / 16.0f) * sqrtf(m) + 2.0f;
+      r = rr < (float)k ? (uint32_t)rr : 0u;
+    }
+    uint64_t guess = 0;
+    if (r != 0u && n > r) guess = topk_kth_wave(s.cand, n, r, &s.sc);
+    if (lane == 0u) {
+      if (guess > s.theta) {   // (single 64-bit stores: the walking waves read them)
+        __hip_atomic_store(&s.theta, guess, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_store(&s.thr, acc_threshold<true>(guess, fx_E), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        atomicMax(theta_g, (unsigned long long)guess);
+        atomicMax(s.spec_slot, (unsigned long long)guess);
+      }
+      s.spec_at = ws >= s.q_wins ? 0u : max(ws * s.spec_grow16 / 16u, ws + (uint32_t)kMsWaves);   // the next estimate: ms_compact's rule
+      s.n_est += 1u;
+    }
+  }
+  wave_lds_phase();
+  if (lane == 0u) __hip_atomic_store(&s.spec_busy, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
 // Reserve room for the wave's `mine`-per-lane candidates in the shared buffer: one DPP scan and ONE LDS atomic.
@@ -469,6 +526,7 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
       const float* const caches = as_global(ap->caches);
       for (uint32_t i = tid; i < n_lds; i += kMsThreads) (&s.cache[0][0])[i] = caches[item.cache_off + i];
     }
+    for (uint32_t i = tid; i < (uint32_t)kMsCandCap; i += kMsThreads) s.cand[i] = 0ull;   // (unwritten slots read 0: ms_estimate)
     if (tid == 0) {
       const uint64_t theta0 = __hip_atomic_load(my_theta_g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       s.theta = theta0;
@@ -476,6 +534,8 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
       s.cnt = 0;
       s.cnt_valid = 0;
       s.rz_flag = 0;
+      s.spec_busy = 0;
+      s.n_meet = s.n_over = s.n_est = 0;
       if (!helper) {   // when this item began; the launch's first item: when the launch began
         const unsigned long long now0 = (unsigned long long)wall_clock64();
         __hip_atomic_store(hp.item_t0 + my_item, now0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -490,6 +550,7 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
       s.spec_slot = spec ? as_global(hp.spec_g) + item.query : nullptr;
       s.spec_at = spec ? max(hp.spec_sched & 255u, 1u) : 0u;   // the first estimate (default: when every wave has begun its second window)
       s.spec_grow16 = max((hp.spec_sched >> 8) & 255u, 17u);
+      s.spec_meet = (hp.spec_sched >> 16) & 1u;
       for (int i = 0; i < kSliceSlots; ++i) s.slot_hits[i] = s.slot_slice[i] = 0u;
       for (int i = 0; i < 16; ++i) s.prof[i] = 0;
     }
@@ -666,9 +727,18 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
         const uint32_t doc_lo = t0 * (uint32_t)kTileDocs;
         const uint32_t doc_span = min(t1 * (uint32_t)kTileDocs, part.max_doc) - doc_lo;
         if (PROF) pc_wins += 1;
-        if (lane == 0) {   // speculation: one more window begun; a new estimate is due every time their number has doubled
-          const uint32_t ws = atomicAdd(&s.wins_started, 1u) + 1u, at = s.spec_at;
-          if (at != 0u && ws >= at) __hip_atomic_store(&s.rz_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        {   // speculation: one more window begun; a new estimate is due every time their number has doubled.  The wave that finds
+            // one due makes it on its own while the others walk on (ms_estimate) -- unless somebody is at it already
+          uint32_t est = 0;
+          if (lane == 0) {
+            const uint32_t ws = atomicAdd(&s.wins_started, 1u) + 1u, at = s.spec_at;
+            if (at != 0u && ws >= at) {
+              if (s.spec_meet != 0u) __hip_atomic_store(&s.rz_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // (A/B: in a meeting)
+              else est = atomicCAS(&s.spec_busy, 0u, 1u) == 0u ? 1u : 0u;
+            }
+          }
+          if (__builtin_amdgcn_readfirstlane((int)est) != 0)
+            ms_estimate((__attribute__((address_space(3))) MsSmem*)&s, k, fx_E, my_theta_g, xch);
         }
         // my next window: taken now, so that the counter's answer is there when this one is done
         uint32_t g_new = 0;
@@ -1222,6 +1292,9 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
       if (PROF && ape->item_prof) {
   #ifndef NRT_MS_PHASE_CLOCKS
         s.prof[5] = hits;
+        // (slot 1, 16 bits each: compactions | meetings | meetings called by an overflow | estimates made by one wave --
+        //  search.cpp takes them apart: nrtgpu_debug_maxscore_meetings)
+        s.prof[1] = (s.prof[1] & 0xFFFFull) | ((uint64_t)min(s.n_meet, 0xFFFFu) << 16) | ((uint64_t)min(s.n_over, 0xFFFFu) << 32) | ((uint64_t)min(s.n_est, 0xFFFFu) << 48);
   #endif
         const uint64_t t_end = __builtin_readcyclecounter();
         s.prof[9] = t_end - t_item0;
@@ -1346,6 +1419,23 @@ void term_cells_kernel(const uint32_t* __restrict__ docids, const uint64_t* __re
     out[i] = lo;
   }
 }
+
+#ifdef NRTGPU_DEV
+// Test hook (include/nrtgpu_dev.h: nrtgpu_debug_wave_kth): topk_kth_wave on its own -- one wave, the keys in LDS as the walk holds them.
+__global__ __launch_bounds__(64)
+void debug_wave_kth_kernel(const uint64_t* __restrict__ keys, uint32_t n, uint32_t r, uint64_t* __restrict__ out) {
+  __shared__ uint64_t cand[kMsCandCap];
+  __shared__ TopkScratch sc;
+  for (uint32_t i = threadIdx.x; i < n; i += 64u) cand[i] = keys[i];
+  wave_lds_phase();
+  const uint64_t kth = topk_kth_wave(cand, n, r, &sc);
+  if (threadIdx.x == 0) *out = kth;
+}
+
+void launch_debug_wave_kth(hipStream_t stream, const uint64_t* keys, uint32_t n, uint32_t r, uint64_t* out) {
+  hipLaunchKernelGGL(debug_wave_kth_kernel, dim3(1), dim3(64), 0, stream, keys, n, r, out);
+}
+#endif
 
 // ---- launchers ---------------------------------------------------------------------------------------
 void launch_bm25_maxscore(hipStream_t stream, bool profile, bool packed, int shapes, const MsArgs& args, const MsArgs* args_d) {

@@ -326,6 +326,7 @@ extern "C" void nrtgpu_reset_stats(nrtgpu_ctx* ctx) {
   ctx->stats = nrtgpu_stats{};
   for (double& p : ctx->prof) p = 0;
   for (double& p : ctx->ms_prof) p = 0;
+  for (int64_t& p : ctx->ms_meetings) p = 0;
 }
 #ifdef NRTGPU_DEV   // include/nrtgpu_dev.h: the instrumented kernels' counters
 extern "C" int nrtgpu_get_scan_profile(nrtgpu_ctx* ctx, double* out16) {

@@ -265,9 +265,12 @@ static int enqueue_search(nrtgpu_ctx* ctx, Slot* slot, const HostPlan& hp, int32
   help.spec_g = spec ? (unsigned long long*)(wb + o_spec) : nullptr;
   help.spec_z16 = spec ? spec_z16 : 0u;
   {   // NRTGPU_MS_SPEC_FIRST / NRTGPU_MS_SPEC_GROW (x 16): when a workgroup's estimates are due (plan.h: DHelp.spec_sched)
-    static const int env_first = (int)dev_env_int("NRTGPU_MS_SPEC_FIRST", 2 * kMsWaves);
-    static const int env_grow = (int)dev_env_int("NRTGPU_MS_SPEC_GROW", 32);
-    help.spec_sched = (uint32_t)std::min(std::max(env_first, 1), 255) | ((uint32_t)std::min(std::max(env_grow, 17), 255) << 8);
+    // NRTGPU_MS_SPEC_MEET=1: estimates are made in meetings of all waves, as before the estimator wave (A/B).
+    // (development build: read per call -- tests and interleaved comparisons set them; the product build reads no environment)
+    const int env_first = (int)dev_env_int("NRTGPU_MS_SPEC_FIRST", 2 * kMsWaves);
+    const int env_grow = (int)dev_env_int("NRTGPU_MS_SPEC_GROW", 32);
+    const bool env_meet = dev_env_int("NRTGPU_MS_SPEC_MEET", 0) != 0;
+    help.spec_sched = (uint32_t)std::min(std::max(env_first, 1), 255) | ((uint32_t)std::min(std::max(env_grow, 17), 255) << 8) | (env_meet ? 1u << 16 : 0u);
   }
   MsArgs ms_args{};   // (the kernel reads the record from the plan: maxscore.hip)
   ms_args.items = (const DItem*)(db + o_items);
@@ -510,7 +513,20 @@ static int search_batch_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, con
     HIP_TRY(hipMemcpy(hp_prof.data(), run.prof, hp_prof.size() * 8, hipMemcpyDeviceToHost));
     std::lock_guard<std::mutex> lk(ctx->stats_mu);
     for (size_t i = 0; i < run.n_slots; ++i)   // (slots behind the items: helpers of the MaxScore route)
-      for (int j = 0; j < 16; ++j) ((i < run.n_ms_items || i >= run.n_items) ? ctx->ms_prof : ctx->prof)[j] += (double)hp_prof[i * 16 + j];
+      if (i < run.n_ms_items || i >= run.n_items) {
+#ifndef NRT_MS_PHASE_CLOCKS   // (that measurement build books cycles in slots 0-8)
+        // (MaxScore slot 1 holds four 16-bit counts: maxscore.hip, the item's write-out)
+        const uint64_t packed = hp_prof[i * 16 + 1];
+        hp_prof[i * 16 + 1] = packed & 0xFFFFull;
+        ctx->ms_meetings[0] += (int64_t)((packed >> 16) & 0xFFFFull);   // meetings
+        ctx->ms_meetings[1] += (int64_t)((packed >> 32) & 0xFFFFull);   // ... called by an overflow
+        ctx->ms_meetings[2] += (int64_t)(packed & 0xFFFFull);           // compactions
+        ctx->ms_meetings[3] += (int64_t)(packed >> 48);                 // estimates made by one wave
+#endif
+        for (int j = 0; j < 16; ++j) ctx->ms_prof[j] += (double)hp_prof[i * 16 + j];
+      } else {
+        for (int j = 0; j < 16; ++j) ctx->prof[j] += (double)hp_prof[i * 16 + j];
+      }
     if (run.walls) {   // the last instrumented launch's workgroups in time (nrtgpu_get_maxscore_item_walls)
       std::vector<uint64_t> w(run.n_slots * 8);
       (void)hipMemcpy(w.data(), run.walls, w.size() * 8, hipMemcpyDeviceToHost);
