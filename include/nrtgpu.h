@@ -534,6 +534,22 @@ int  nrtgpu_knn_exact_bytes(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, cons
 int  nrtgpu_knn_search_bytes(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
                              int32_t field_id, int32_t sim, const int8_t* queries, int32_t n_queries, int32_t dim, int32_t k,
                              float boost, int32_t filter_mask, float min_score, nrtgpu_topdocs* out /* n_queries */);
+/* The GATHER route of the filtered knn entries.
+ * Filtered knn requests (nrtgpu_knn_search, nrtgpu_knn_search_bytes; filter_mask != 0) whose filter accepts at most
+ * max_accept_permille / 1000 of the field's rows over the call's leaves read ONLY the accepted rows. 0 (a context's default): never --
+ * every request passes over all rows, as before.  Results are the same bits either way.
+ * The share is judged on the host before anything is launched: per leaf that holds the field min(docs of the combined set
+ * liveDocs & filter, rows of the field), summed -- an upper bound of the accepted rows (a sparse ord -> doc map accepts fewer) --
+ * against max_accept_permille x the rows of those leaves; the accepted rows must also fit one candidate list of the full pass
+ * (2^18 keys per query), else the full pass runs.  On the route the accepted rows are listed on the device once per call and every
+ * pass of 64 queries scores exactly those with final score bits (float fields: the oracle's order of summation; byte fields: the
+ * integers and the table above): no fp16 sketch is built or read, nothing is nominated, certified or passed over twice.  An
+ * upper bound of 0 returns empty hit lists without a launch.  min_score, boost, total_hits, deadlines and every refusal are the
+ * full pass's.  nrtgpu_get_stats: a pass counts as one knn_panels, adds the ACCEPTED rows to knn_rows and its scoring launch to
+ * knn_score_launches / knn_score_ms, and nothing to knn_sketch_launches or knn_second_passes.
+ * Out of scope: nrtgpu_knn_exact* (no filter argument), the coalesced and nrtgpu_dist_* entries, panels whose members have
+ * different filters, keeping the row list from one call to the next, and a default other than 0. */
+int  nrtgpu_set_knn_gather(nrtgpu_ctx* ctx, int32_t max_accept_permille);   /* 0..1000, else NRTGPU_ERR_INVALID_ARG */
 /* The score of one (query, row) pair of a byte field from its three integers (the table above), exposed for the tests like
  * nrtgpu_fixed_point_scale: needs no device; it is the very function the kernel compiles.  Writes the UNBOOSTED score; returns 0,
  * or NRTGPU_ERR_INVALID_ARG (sim outside 0..3, dim outside 1..2048, integers `dim` int8 pairs cannot produce). */

@@ -320,6 +320,11 @@ class GpuContext:
         """Speculative thresholds of the MaxScore route (nrtgpu_set_speculation): the guess's safety margin in standard deviations; 0 = off."""
         _lib.check(_lib.load().nrtgpu_set_speculation(self._h, C.c_float(float(margin))))
 
+    def set_knn_gather(self, max_accept_permille: int) -> None:
+        """The gather route of the filtered knn requests (nrtgpu_set_knn_gather): knn_search / knn_search_bytes with a filter that accepts
+        at most this many thousandths of the field's rows score only the accepted rows; 0 (the default) = never.  Same results."""
+        _lib.check(_lib.load().nrtgpu_set_knn_gather(self._h, int(max_accept_permille)))
+
     def set_shard_share(self, shard_docs: int, index_docs: int) -> None:
         """This context's share of a sharded index (nrtgpu_set_shard_share): the shard-level guesses then count the other shards'
         docs by it instead of assuming equal shards; (0, 0): equal shards."""

@@ -1192,4 +1192,100 @@ void launch_hybrid_hits(hipStream_t st, const uint64_t* first_hits, const uint32
   hipLaunchKernelGGL(hybrid_hits_kernel, dim3((n + 255) / 256), dim3(256), 0, st, first_hits, first_counts, q_k, carries, out_hits, n);
 }
 
+// ---- the GATHER route of the filtered knn entries (vectors_gather.cpp) -------------------------------------------
+// A selective filter accepts a few thousand rows of millions: instead of a pass over every row that tests the filter inside, the
+// accepted rows are LISTED (knn_accept_rows_kernel, once per call) and exactly those are scored with final score bits
+// (knn_gather_score_kernel here, knn_gather_bytes_kernel in knn_bytes.hip), every accepted row a slot of the query's candidate
+// list; knn_select_kernel<false> takes the top k of it.  No sketch, no nomination, no certificate, no second pass.
+//
+// A thread per ordinal of the call's leaves (numbered through, plan.h: DKnnGatherLeaf): its doc's bit in the leaf's accept set,
+// a ballot, one atomic per wave for the wave's run of slots.  The list's order varies from run to run; the keys made from it do
+// not.  *count: the accepted rows exactly (the host sized the list by an upper bound of it; slots behind `cap` are not written).
+__global__ __launch_bounds__(256)
+void knn_accept_rows_kernel(const DKnnGatherLeaf* __restrict__ leaves, int32_t n_leaves, int64_t total_rows, uint64_t* __restrict__ list,
+                            uint32_t* __restrict__ count, uint32_t cap) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63u;
+  bool ok = false;
+  uint64_t entry = 0ull;
+  if (g < total_rows) {
+    int32_t lo = 0, hi = n_leaves - 1;   // the last leaf that begins at or before g
+    while (lo < hi) {
+      const int32_t mid = (lo + hi + 1) >> 1;
+      if (leaves[mid].row_begin <= g) lo = mid; else hi = mid - 1;
+    }
+    const int64_t ord = g - leaves[lo].row_begin;
+    if (ord < (int64_t)leaves[lo].n_rows) {
+      const int32_t* ord_to_doc = leaves[lo].ord_to_doc;
+      const uint64_t* accept = leaves[lo].accept;
+      const int32_t doc = ord_to_doc ? ord_to_doc[ord] : (int32_t)ord;
+      if ((uint32_t)doc < (uint32_t)leaves[lo].max_doc) ok = !accept || ((accept[doc >> 6] >> (doc & 63)) & 1ull) != 0ull;
+      entry = ((uint64_t)(uint32_t)lo << 32) | (uint64_t)(uint32_t)ord;
+    }
+  }
+  const unsigned long long b = __ballot(ok);
+  if (b == 0ull) return;
+  const int leader = __ffsll((long long)b) - 1;
+  uint32_t base = 0;
+  if ((int)lane == leader) base = atomicAdd(count, (uint32_t)__popcll(b));
+  base = (uint32_t)__shfl((int)base, leader, 64);
+  if (ok) {
+    const uint32_t pos = base + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+    if (pos < cap) list[pos] = entry;
+  }
+}
+
+// One lane per (query, accepted row): blockIdx.y = the panel's query (in LDS), a lane walks its own row in the oracle's order
+// (knn_score_seq: the bits the full pass returns after rescoring) and writes the key into slot i of the query's candidate list --
+// the row's place in the call's list, so nothing is counted here: cand_cnt[q] = the list's length.  A row below min_score leaves
+// key 0, which the selection drops (as knn_select_kernel<true> does for a nomination).  The rows are read once per query; at the
+// sizes this route takes (<= cap rows) they stay in the L2 / the Infinity Cache between the panel's queries.
+constexpr int kKnnGatherThreads = 64;
+__global__ __launch_bounds__(kKnnGatherThreads)
+void knn_gather_score_kernel(const DKnnGatherLeaf* __restrict__ leaves, const uint64_t* __restrict__ list, const uint32_t* __restrict__ count,
+                             int32_t dim, const float* __restrict__ qpanel, const float* __restrict__ qnorm2, int32_t sim, float boost,
+                             float min_score, uint64_t* __restrict__ cand, uint32_t* __restrict__ cand_cnt, uint32_t cap) {
+  __shared__ __attribute__((aligned(16))) float qv[2048];
+  const uint32_t q = blockIdx.y, tid = threadIdx.x;
+  const uint32_t n = min(*count, cap);
+  if (blockIdx.x == 0 && tid == 0) cand_cnt[q] = n;
+  if (blockIdx.x * (uint32_t)kKnnGatherThreads >= n) return;
+  for (int32_t i = (int32_t)tid * 4; i < dim; i += kKnnGatherThreads * 4)   // (dim % 16 == 0: the resident dimension)
+    *(f32x4*)(qv + i) = *(const f32x4*)(qpanel + (size_t)q * dim + i);
+  __syncthreads();
+  const float nq = qnorm2[q];
+  for (uint32_t i = blockIdx.x * (uint32_t)kKnnGatherThreads + tid; i < n; i += gridDim.x * (uint32_t)kKnnGatherThreads) {
+    const uint64_t e = list[i];
+    const DKnnGatherLeaf* lf = leaves + (uint32_t)(e >> 32);
+    const uint32_t ord = (uint32_t)e;
+    const int32_t* ord_to_doc = lf->ord_to_doc;
+    const int32_t doc = ord_to_doc ? ord_to_doc[ord] : (int32_t)ord;
+    const float* v = (const float*)lf->rows + (size_t)ord * dim;
+    const float sc = knn_score_seq(sim, qv, v, dim, nq, boost);
+    uint64_t key = 0ull;
+    if (!(min_score > 0.0f) || sc >= min_score) key = pack_key(sc, (uint32_t)(lf->doc_base + doc));
+    cand[(size_t)q * cap + i] = key;
+  }
+}
+
+int launch_knn_accept_rows(hipStream_t st, const DKnnGatherLeaf* leaves, int32_t n_leaves, int64_t total_rows, uint64_t* list, uint32_t* count,
+                           uint32_t cap) {
+  if (total_rows <= 0 || n_leaves <= 0) return 0;
+  if (total_rows > (int64_t)0x7FFFFFFF * 256) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(knn_accept_rows_kernel, dim3((uint32_t)((total_rows + 255) / 256)), dim3(256), 0, st, leaves, n_leaves, total_rows, list,
+                     count, cap);
+  return 0;
+}
+// max_rows: an upper bound of *count the host knows (the grid is sized by it; the kernel reads the count itself)
+int launch_knn_gather_score(hipStream_t st, const DKnnGatherLeaf* leaves, const uint64_t* list, const uint32_t* count, uint32_t max_rows,
+                            int32_t dim, const float* qpanel, const float* qnorm2, int32_t n_q, int32_t sim, float boost, float min_score,
+                            uint64_t* cand, uint32_t* cand_cnt, uint32_t cap) {
+  if (max_rows == 0 || n_q <= 0) return 0;
+  if (n_q > 64 || dim < 16 || dim > 2048 || (dim & 15) || max_rows > cap) return (int)hipErrorInvalidValue;
+  const uint32_t blocks = (max_rows + (uint32_t)kKnnGatherThreads - 1) / (uint32_t)kKnnGatherThreads;
+  hipLaunchKernelGGL(knn_gather_score_kernel, dim3(blocks, (uint32_t)n_q), dim3(kKnnGatherThreads), 0, st, leaves, list, count, dim, qpanel,
+                     qnorm2, sim, boost, min_score, cand, cand_cnt, cap);
+  return 0;
+}
+
 }  // namespace nrtgpu

@@ -613,4 +613,68 @@ void launch_hybrid_rescore_bytes(hipStream_t st, uint32_t n_queries, const uint6
                      n_segs, knn_bytes_steps(dim), dim, (const i32x4*)qvecs, qnorm2, sim, boost, qw, rw, window, out_keys, out_counts, w_stride);
 }
 
+// ---- the GATHER route of nrtgpu_knn_search_bytes (knn.hip: knn_accept_rows_kernel lists the rows the filter accepts) -------------
+// blockIdx.y = the panel's query (piece order, in LDS); a wave per kByteRescoreRows entries of the list: the rows' integers by the
+// rescorers' routine (kb_rows_dot over the resident tiles), then a lane per row for knn_byte_score -- the bits knn_bytes_kernel
+// returns for the pair -- and the key into slot i of the query's candidate list (the row's place in the list: nothing is counted,
+// cand_cnt[q] = the list's length).  A row below min_score leaves key 0, which the selection drops.
+__global__ __launch_bounds__(256)
+void knn_gather_bytes_kernel(const DKnnGatherLeaf* __restrict__ leaves, const uint64_t* __restrict__ list, const uint32_t* __restrict__ count,
+                             int32_t steps, int32_t dim, const i32x4* __restrict__ queries, const int32_t* __restrict__ qnorm2, int32_t sim,
+                             float boost, float min_score, uint64_t* __restrict__ cand, uint32_t* __restrict__ cand_cnt, uint32_t cap) {
+  __shared__ i32x4 qs[128];
+  const uint32_t q = blockIdx.y, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  constexpr uint32_t kPerBlock = 4u * (uint32_t)kByteRescoreRows;
+  const uint32_t n = min(*count, cap);
+  if (blockIdx.x == 0 && tid == 0) cand_cnt[q] = n;
+  if (blockIdx.x * kPerBlock >= n) return;
+  const int32_t n_pieces = (dim + 15) >> 4;
+  if ((int32_t)tid < n_pieces) qs[tid] = queries[(size_t)q * (size_t)steps * 4 + tid];
+  __syncthreads();
+  const int32_t nq = qnorm2[q];
+  for (uint32_t i0 = (blockIdx.x * 4u + wave) * (uint32_t)kByteRescoreRows; i0 < n; i0 += gridDim.x * kPerBlock) {
+    const i32x4* rows[kByteRescoreRows];
+#pragma unroll
+    for (int r = 0; r < kByteRescoreRows; ++r) {
+      const i32x4* base = nullptr;
+      if (i0 + (uint32_t)r < n) {
+        const uint64_t e = list[i0 + (uint32_t)r];
+        const int64_t row = (int64_t)(uint32_t)e;
+        base = (const i32x4*)leaves[(uint32_t)(e >> 32)].rows + (row >> 4) * steps * 64 + (row & 15);
+      }
+      rows[r] = kb_uniform_row(base);
+    }
+    int32_t dot[kByteRescoreRows];
+    kb_rows_dot<kByteRescoreRows>(rows, qs, n_pieces, lane, dot);
+    int32_t my_dot = 0;   // lane r finishes row r (every lane holds every sum)
+#pragma unroll
+    for (int r = 0; r < kByteRescoreRows; ++r)
+      if (lane == (uint32_t)r) my_dot = dot[r];
+    const uint32_t i = i0 + lane;
+    if (lane < (uint32_t)kByteRescoreRows && i < n) {
+      const uint64_t e = list[i];
+      const DKnnGatherLeaf* lf = leaves + (uint32_t)(e >> 32);
+      const uint32_t ord = (uint32_t)e;
+      const int32_t* ord_to_doc = lf->ord_to_doc;
+      const int32_t doc = ord_to_doc ? ord_to_doc[ord] : (int32_t)ord;
+      const float s = knn_byte_score(sim, dim, my_dot, nq, lf->vnorm2[ord]);
+      uint64_t key = 0ull;
+      if (!(min_score > 0.0f) || s >= min_score) key = pack_key(s * boost, (uint32_t)(lf->doc_base + doc));
+      cand[(size_t)q * cap + i] = key;
+    }
+  }
+}
+
+// max_rows: an upper bound of *count the host knows (the grid is sized by it); queries: piece order, 64 x steps bytes each
+int launch_knn_gather_bytes(hipStream_t st, const DKnnGatherLeaf* leaves, const uint64_t* list, const uint32_t* count, uint32_t max_rows,
+                            int32_t dim, const void* queries, const int32_t* qnorm2, int32_t n_q, int32_t sim, float boost, float min_score,
+                            uint64_t* cand, uint32_t* cand_cnt, uint32_t cap) {
+  if (max_rows == 0 || n_q <= 0) return 0;
+  if (n_q > 64 || dim < 1 || dim > 2048 || max_rows > cap) return (int)hipErrorInvalidValue;
+  const uint32_t per_block = 4u * (uint32_t)kByteRescoreRows;
+  hipLaunchKernelGGL(knn_gather_bytes_kernel, dim3((max_rows + per_block - 1) / per_block, (uint32_t)n_q), dim3(256), 0, st, leaves, list, count,
+                     knn_bytes_steps(dim), dim, (const i32x4*)queries, qnorm2, sim, boost, min_score, cand, cand_cnt, cap);
+  return 0;
+}
+
 }  // namespace nrtgpu

@@ -394,6 +394,20 @@ struct DByteVecSeg {
 };
 static_assert(sizeof(DByteVecSeg) == 40, "DByteVecSeg layout");
 
+// The GATHER route of the filtered knn entries (knn.hip: knn_accept_rows_kernel, knn_gather_score_kernel; knn_bytes.hip:
+// knn_gather_bytes_kernel): a leaf as those kernels see it.  The leaves' ordinals are numbered through: leaf i holds
+// [row_begin, row_begin + n_rows).  An entry of the call's row list is (leaf << 32) | ordinal inside the leaf.
+struct alignas(16) DKnnGatherLeaf {
+  const void* rows;            // float field: n_rows x dim fp32, row-major; byte field: the tiles (DKnnBytesLeaf.tiles)
+  const int32_t* vnorm2;       // byte field: |v|^2 per row; float field: unused (the oracle's order sums it with the dot product)
+  const int32_t* ord_to_doc;   // nullptr: row == docid
+  const uint64_t* accept;      // liveDocs & filter bits of the leaf (never nullptr on this route)
+  int64_t row_begin;
+  int32_t n_rows, doc_base;
+  int32_t max_doc, pad[3];
+};
+static_assert(sizeof(DKnnGatherLeaf) == 64, "DKnnGatherLeaf layout");
+
 // The UNBOOSTED score of one (query, row) pair of a byte vector field from its three integers dot = sum q_i v_i, nq = sum q_i^2,
 // nv = sum v_i^2 -- ByteVectorFieldDef.similarityToScore's four shapes (VectorFieldDef.java:870-881) over what Lucene's
 // VectorSimilarityFunction.compare(byte[], byte[]) hands it [Lucene-recall].  Every operation is one fp32 (cosine: fp64, then one

@@ -120,6 +120,15 @@ void launch_hybrid_rescore_bytes(hipStream_t st, uint32_t n_queries, const uint6
                                  uint32_t k_stride, const DByteVecSeg* segs, int32_t n_segs, int32_t dim, const void* qvecs,
                                  const int32_t* qnorm2, int32_t sim, float boost, double qw, double rw, uint32_t window, uint64_t* out_keys,
                                  uint32_t* out_counts, uint32_t w_stride);
+// the gather route of the filtered knn entries (knn.hip, knn_bytes.hip; vectors_gather.cpp).  max_rows: an upper bound of *count
+int launch_knn_accept_rows(hipStream_t st, const DKnnGatherLeaf* leaves, int32_t n_leaves, int64_t total_rows, uint64_t* list, uint32_t* count,
+                           uint32_t cap);
+int launch_knn_gather_score(hipStream_t st, const DKnnGatherLeaf* leaves, const uint64_t* list, const uint32_t* count, uint32_t max_rows,
+                            int32_t dim, const float* qpanel, const float* qnorm2, int32_t n_q, int32_t sim, float boost, float min_score,
+                            uint64_t* cand, uint32_t* cand_cnt, uint32_t cap);
+int launch_knn_gather_bytes(hipStream_t st, const DKnnGatherLeaf* leaves, const uint64_t* list, const uint32_t* count, uint32_t max_rows,
+                            int32_t dim, const void* queries, const int32_t* qnorm2, int32_t n_q, int32_t sim, float boost, float min_score,
+                            uint64_t* cand, uint32_t* cand_cnt, uint32_t cap);
 }  // namespace nrtgpu
 
 namespace nrtgpu {
@@ -385,7 +394,7 @@ struct nrtgpu_seg {
   void content_unlock_shared() const;       // may free the handle (content_released)
   std::map<int32_t, std::vector<uint64_t>> masks;
   mutable std::mutex accept_mu;
-  struct AcceptSet { uint64_t* bits; uint64_t used; };        // used: the cache's clock at the last lookup (least recently used goes first)
+  struct AcceptSet { uint64_t* bits; uint64_t used; int64_t count; };   // used: the cache's clock at the last lookup (least recently used goes first); count: set bits below max_doc
   mutable std::map<std::vector<int32_t>, AcceptSet> accept;   // key: the filter mask ids ascending, 0, the must_not mask ids ascending
   mutable uint64_t accept_clock = 0;
   mutable std::vector<uint64_t*> accept_retired;              // evicted, maybe still read by a search in flight: freed by the last reader out
@@ -522,6 +531,7 @@ struct nrtgpu_ctx {
                         // overlapping two only stretches both (host-side planning/unpacking still overlap)
   std::mutex stats_mu;
   nrtgpu_stats stats{};
+  std::atomic<int32_t> knn_gather_permille{0};   // nrtgpu_set_knn_gather: filtered knn requests that accept at most this share of the rows read only those (0: never)
   std::atomic<int> knn_sketch_skip[4] = {};   // per similarity: panels that go straight to the fp32 rows (the sketch did not certify lately)
   double prof[16] = {0};
   std::vector<uint64_t> last_walls;   // NRTGPU_FLAG_PROFILE: {start, end, item, windows} per output slot of the last MaxScore launch
@@ -653,7 +663,8 @@ void release_slot(nrtgpu_ctx* ctx, Slot* s);
 // ---- segment store (segment.cpp) ---------------------------------------------------------------
 // The doc set a query's hits must lie in: liveDocs & FILTER mask & ~MUST_NOT mask, resident in HBM
 // ((0, 0): liveDocs itself, or nullptr once they are folded into the posting columns).
-int accept_set_of(const nrtgpu_seg* seg, int32_t filter_mask, int32_t must_not_mask, const uint64_t** out);
+// count (optional): the set's docs -- its bits below max_doc, counted where the set is built and kept with it
+int accept_set_of(const nrtgpu_seg* seg, int32_t filter_mask, int32_t must_not_mask, const uint64_t** out, int64_t* count = nullptr);
 int accept_set_of(const nrtgpu_seg* seg, const nrtgpu_bm25_query& q, const uint64_t** out);   // all of the query's FILTER / MUST_NOT masks
 // vectors of the field whose doc is live (the hits of an exact vector query over the segment)
 int64_t live_vector_count(const nrtgpu_seg* seg, const FieldData& f);
@@ -745,6 +756,27 @@ struct KnnRun {
 // knn_request: totalHits = the docs returned, the boost applied afterwards; else `total`.
 void knn_unpack_topdocs(const uint64_t* keys, const uint32_t* counts, uint32_t k_stride, int nq, int32_t k, bool clamp_to_k, int64_t total,
                         bool knn_request, float boost, nrtgpu_topdocs* out);
+
+// ---- the gather route of the filtered knn entries (vectors_gather.cpp) -------------------------------------------
+// A filtered knn request (nrtgpu_knn_search, nrtgpu_knn_search_bytes; filter_mask != 0) whose filter accepts few enough rows reads
+// only those: the accepted rows are listed on the device, scored with final score bits and selected (knn_select_kernel<false>).
+// Called by knn_impl / knn_bytes_impl behind their argument checks, refusals and SegReadLocks.
+struct KnnGatherCall {
+  bool bytes;                  // a byte (int8) field
+  int32_t field_id, sim, k, filter_mask;
+  int32_t dim;                 // float: the RESIDENT dimension (queries padded like the rows); byte: the field's own
+  float boost, min_score;
+  const void* queries;         // n_queries x dim floats / int8, row-major
+  const int32_t* byte_qnorm2;  // byte field: |q|^2 per query (byte_queries_stage)
+  int32_t n_queries;
+  uint32_t cap;                // keys of one candidate list of the caller's full pass
+};
+// The route decision: *gather iff the context's knob (nrtgpu_set_knn_gather) is > 0, the filter accepts at most that share of the
+// field's rows over these leaves and the accepted rows fit one candidate list.  *estimate = sum over the leaves that hold the
+// field of min(docs of the accept set, rows): an upper bound of the accepted rows (a sparse ord -> doc map accepts fewer).
+int knn_gather_route(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const KnnGatherCall& call, bool* gather, int64_t* estimate);
+int knn_gather_run(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, const KnnGatherCall& call,
+                   int64_t estimate, nrtgpu_topdocs* out);
 
 // ---- the vector rescorers (vectors.cpp; what is specific to byte fields: vectors_bytes.cpp) ----------------------------------
 // |q|^2 of a float query as the rescoring kernels' results depend on it: fp32, in element order, every product rounded before it is

@@ -755,7 +755,8 @@ extern "C" int nrtgpu_segment_set_mask(nrtgpu_seg* seg, int32_t mask_id, const u
 // The doc set a query's hits must lie in on this leaf: liveDocs AND every FILTER mask AND NOT any MUST_NOT mask (nullptr: every
 // doc, or liveDocs folded into the postings).  Combined on the host -- one pass over 64-bit words -- the first time a combination
 // is asked for, resident from then on (until liveDocs or a mask change).
-static int accept_set_of_ids(const nrtgpu_seg* seg, std::vector<int32_t> filters, std::vector<int32_t> must_nots, const uint64_t** out) {
+static int accept_set_of_ids(const nrtgpu_seg* seg, std::vector<int32_t> filters, std::vector<int32_t> must_nots, const uint64_t** out,
+                             int64_t* count = nullptr) {
   auto canon = [](std::vector<int32_t>& v) {
     std::sort(v.begin(), v.end());
     v.erase(std::unique(v.begin(), v.end()), v.end());
@@ -764,6 +765,7 @@ static int accept_set_of_ids(const nrtgpu_seg* seg, std::vector<int32_t> filters
   canon(must_nots);
   if (filters.empty() && must_nots.empty()) {
     *out = seg->live_folded ? nullptr : seg->d_live;
+    if (count) *count = (int64_t)seg->max_doc - (int64_t)seg->n_deleted;
     return 0;
   }
   std::vector<int32_t> key(filters);
@@ -774,6 +776,7 @@ static int accept_set_of_ids(const nrtgpu_seg* seg, std::vector<int32_t> filters
   if (it != seg->accept.end()) {
     it->second.used = ++seg->accept_clock;
     *out = it->second.bits;
+    if (count) *count = it->second.count;
     return 0;
   }
   // Bounded like the reference's LRUQueryCache, and like it the least recently used set makes room -- but a set
@@ -804,11 +807,14 @@ static int accept_set_of_ids(const nrtgpu_seg* seg, std::vector<int32_t> filters
   }
   const size_t need = (size_t)(seg->max_doc + 63) / 64;
   std::vector<uint64_t> w(need + kMaskPadBytes / 8, 0ull);  // padded like liveDocs
+  int64_t n_set = 0;   // the set's docs: bits below max_doc (the last word may carry bits behind it)
   for (size_t i = 0; i < need; ++i) {
     uint64_t v = seg->h_live.empty() ? ~0ull : seg->h_live[i];
     for (const std::vector<uint64_t>* m : f) v &= (*m)[i];
     for (const std::vector<uint64_t>* m : mn) v &= ~(*m)[i];
     w[i] = v;
+    if (i + 1 == need && (seg->max_doc & 63)) v &= (1ull << (seg->max_doc & 63)) - 1ull;
+    n_set += __builtin_popcountll(v);
   }
   void* p = nullptr;
   HIP_TRY(hipSetDevice(seg->ctx->device));
@@ -818,16 +824,17 @@ static int accept_set_of_ids(const nrtgpu_seg* seg, std::vector<int32_t> filters
     return fail(NRTGPU_ERR_HIP, "upload of an accept set failed");
   }
   const_cast<nrtgpu_seg*>(seg)->device_bytes += (int64_t)need * 8;
-  seg->accept[key] = nrtgpu_seg::AcceptSet{(uint64_t*)p, ++seg->accept_clock};
+  seg->accept[key] = nrtgpu_seg::AcceptSet{(uint64_t*)p, ++seg->accept_clock, n_set};
   *out = (uint64_t*)p;
+  if (count) *count = n_set;
   return 0;
 }
 
-int nrtgpu::rt::accept_set_of(const nrtgpu_seg* seg, int32_t filter_mask, int32_t must_not_mask, const uint64_t** out) {
+int nrtgpu::rt::accept_set_of(const nrtgpu_seg* seg, int32_t filter_mask, int32_t must_not_mask, const uint64_t** out, int64_t* count) {
   std::vector<int32_t> f, mn;
   if (filter_mask) f.push_back(filter_mask);
   if (must_not_mask) mn.push_back(must_not_mask);
-  return accept_set_of_ids(seg, std::move(f), std::move(mn), out);
+  return accept_set_of_ids(seg, std::move(f), std::move(mn), out, count);
 }
 
 int nrtgpu::rt::accept_set_of(const nrtgpu_seg* seg, const nrtgpu_bm25_query& q, const uint64_t** out) {

@@ -159,6 +159,13 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
   if (int rc = pad_query_vectors(segs, n_segs, field_id, queries, n_queries, dim, &padded)) return rc;
   queries = padded.p;
   dim = padded.dim;
+  if (knn_request && filter_mask != 0) {   // a selective filter: score only the rows it accepts (vectors_gather.cpp) -- no sketch is built or read
+    const KnnGatherCall call{false, field_id, sim, k, filter_mask, dim, boost, min_score, queries, nullptr, n_queries, kKnnCap};
+    bool gather = false;
+    int64_t estimate = 0;
+    if (int rc = knn_gather_route(ctx, segs, n_segs, call, &gather, &estimate)) return rc;
+    if (gather) return knn_gather_run(ctx, segs, doc_bases, n_segs, call, estimate, out);
+  }
   for (int si = 0; si < n_segs; ++si)   // the fp16 sketches this search nominates from: built on a field's first exact search
     if (int rc = ensure_vector_sketch(segs[si], field_id)) return rc;
   const uint32_t k_stride = round_up((uint32_t)k, 16);

@@ -38,6 +38,13 @@ static int knn_bytes_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const 
     if (f.byte_rows && f.dim_user != dim)
       return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d has dimension %d, query has %d", si, field_id, f.dim_user, dim);
   }
+  if (knn_request && filter_mask != 0) {   // a selective filter: score only the rows it accepts (vectors_gather.cpp)
+    const KnnGatherCall call{true, field_id, sim, k, filter_mask, dim, boost, min_score, queries, qn2.data(), n_queries, kKnnBytesCap};
+    bool gather = false;
+    int64_t estimate = 0;
+    if (int rc = knn_gather_route(ctx, segs, n_segs, call, &gather, &estimate)) return rc;
+    if (gather) return knn_gather_run(ctx, segs, doc_bases, n_segs, call, estimate, out);
+  }
   const uint32_t k_stride = round_up((uint32_t)k, 16);
   const float score_boost = knn_request ? 1.0f : boost;   // the knn request: min_score tests the unboosted score, the boost comes afterwards
   Slot* slot = nullptr;
