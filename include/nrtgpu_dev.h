@@ -86,6 +86,20 @@ int  nrtgpu_debug_maxscore_meetings(nrtgpu_ctx* ctx, int64_t* out4);
  * held in LDS as the walk holds them: *out = the r-th largest (1-based) of the keys, a zero key being an unwritten slot (it ranks
  * below every key).  1 <= r <= n <= the walk's candidate buffer (2304 slots). */
 int  nrtgpu_debug_wave_kth(const uint64_t* keys, int32_t n, int32_t r, uint64_t* out);
+/* TEST HOOK: the MaxScore route's WALK ROWS (plan.h: DWalkRow) of a batch, as the plan expansion writes them on the device: the
+ * batch is planned as a search would plan it and expanded; nothing is searched.  out_begin[q * n_segs + leaf]: the first row of
+ * (query, leaf), -1 when the leaf holds none of the query's terms (or lacks a MUST term) or the query is not on the MaxScore route;
+ * out_n[q * n_segs + leaf]: how many (the clauses the leaf holds, heaviest first).  Row r is ten 64-bit words at out_rows[10 r]:
+ * {docid column, score-code column, S_c, ub_c, weight bits | fx_scale << 32, flags, u_after_c, lookup structure, cell table, first
+ * posting} -- ub_c the clause's exact maximum score in the leaf, u_after_c what the later clauses add at most, S_c the two
+ * combined, all in the query's common fixed-point scale.  Returns the number of rows (<= cap_rows are written), < 0: -error. */
+int64_t nrtgpu_debug_walk_rows(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                               const nrtgpu_bm25_query* queries, int32_t n_queries, int32_t* out_begin, int32_t* out_n,
+                               uint64_t* out_rows, int64_t cap_rows);
+/* TEST HOOK: what ONE posting adds to a doc's fixed-point sum, computed on the device by the statement the scorers and the walk
+ * rows use: out[i] = (integer BM25 score of (weight, freq[i], table256[norm[i]]) at scale 2^fx_scale) << fx_shift. */
+int  nrtgpu_debug_walk_value(float weight, const uint32_t* freq, const uint32_t* norm, int32_t n, const float* table256, int32_t fx_scale,
+                             uint32_t fx_shift, uint64_t* out);
 /* the same flag: WHEN the pieces of the last MaxScore launch ran.  Per output slot eight words -- {start, end} on the device's
  * 100 MHz wall clock, the item worked on, the doc windows walked, when the workgroup's round began (persistent workgroups choose
  * work round after round), the CU (XCC << 8 | SE, SH, CU), the round, the workgroup; a slot nobody used is all zeros.  The first

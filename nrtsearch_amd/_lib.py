@@ -55,7 +55,7 @@ DEV_SYMBOLS = [
     "nrtgpu_bench_closed_loop", "nrtgpu_debug_hold_coalescers", "nrtgpu_debug_coalescer_pending", "nrtgpu_debug_live_segments",
     "nrtgpu_debug_spec_counters", "nrtgpu_get_scan_profile", "nrtgpu_get_maxscore_profile", "nrtgpu_get_maxscore_item_walls",
     "nrtgpu_debug_dist_inject", "nrtgpu_debug_term_lookup", "nrtgpu_debug_knn_bounds",
-    "nrtgpu_debug_maxscore_meetings", "nrtgpu_debug_wave_kth",
+    "nrtgpu_debug_maxscore_meetings", "nrtgpu_debug_wave_kth", "nrtgpu_debug_walk_rows", "nrtgpu_debug_walk_value",
 ]
 DEV_LIB_PATH = os.path.join(_HERE, "libnrtgpu_dev.so")
 
@@ -218,6 +218,10 @@ def _open(path: str) -> C.CDLL:
     if hasattr(L, "nrtgpu_debug_maxscore_meetings"):
         L.nrtgpu_debug_maxscore_meetings.argtypes = [vp, vp]
         L.nrtgpu_debug_wave_kth.argtypes = [vp, i32, i32, vp]
+    if hasattr(L, "nrtgpu_debug_walk_rows"):
+        L.nrtgpu_debug_walk_rows.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, i64]
+        L.nrtgpu_debug_walk_rows.restype = C.c_int64
+        L.nrtgpu_debug_walk_value.argtypes = [f32, vp, vp, i32, vp, i32, C.c_uint32, vp]
     if hasattr(L, "nrtgpu_debug_knn_bounds"):
         L.nrtgpu_debug_knn_bounds.argtypes = [i32, i32, C.c_double, C.c_double, f32, C.c_double, C.c_double, f32, f32, C.c_double, C.c_double, vp]
     L.nrtgpu_set_slicing.argtypes = [vp, i32, i32, i32]

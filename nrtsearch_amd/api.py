@@ -626,6 +626,26 @@ class GpuIndexSearcher:
     def search(self, query: Query, manager: TopScoreDocCollectorManager) -> TopDocs:
         return self.search_batch([query], [manager])[0]
 
+    def debug_walk_rows(self, queries: Sequence[Query], managers: Sequence[TopScoreDocCollectorManager]):
+        """Test hook of the development library (nrtgpu_debug_walk_rows): the MaxScore route's walk rows of the batch, as the
+        plan expansion writes them on the device (nothing is searched).  -> (begin[n_queries, n_leaves] (-1: none),
+        count[n_queries, n_leaves], rows: a structured array with the fields suffix (S_c), ub, weight, fx_scale, flags, u_after and
+        the four device addresses)."""
+        n, nl = len(queries), len(self.leaves)
+        m = self._marshal(queries, managers)
+        begin = np.full((n, nl), -1, dtype=np.int32)
+        count = np.zeros((n, nl), dtype=np.int32)
+        L = _lib.load()
+        total = int(L.nrtgpu_debug_walk_rows(self.ctx._h, self._segs, self._bases, nl, m.queries, n, begin.ctypes.data, count.ctypes.data, None, 0))
+        if total < 0:
+            _lib.check(-total)
+        rows = np.zeros(max(total, 1), dtype=WALK_ROW_DTYPE)
+        got = int(L.nrtgpu_debug_walk_rows(self.ctx._h, self._segs, self._bases, nl, m.queries, n, begin.ctypes.data, count.ctypes.data,
+                                           rows.ctypes.data, total))
+        if got < 0:
+            _lib.check(-got)
+        return begin, count, rows[:total]
+
     def dist_search_batch(self, queries: Sequence[Query], managers: Sequence[TopScoreDocCollectorManager],
                           mode: int = EXCHANGE_ALLGATHER) -> List[Optional[TopDocs]]:
         """The multi-GPU search through nrtgpu_dist_search_bm25_batch_mode: this rank's leaves, RCCL exchange + merge inside
@@ -1041,6 +1061,25 @@ def debug_wave_kth(keys: np.ndarray, r: int) -> int:
     out = np.zeros(1, dtype=np.uint64)
     _lib.check(_lib.load().nrtgpu_debug_wave_kth(keys.ctypes.data, len(keys), int(r), out.ctypes.data))
     return int(out[0])
+
+
+# one walk row (csrc/plan.h: DWalkRow), as nrtgpu_debug_walk_rows returns it
+WALK_ROW_DTYPE = np.dtype([("docids", "<u8"), ("fnorm", "<u8"), ("suffix", "<u8"), ("ub", "<u8"), ("weight", "<f4"), ("fx_scale", "<i4"),
+                           ("flags", "<u4"), ("pad", "<u4"), ("u_after", "<u8"), ("look", "<u8"), ("cells", "<u8"), ("start", "<u8")])
+assert WALK_ROW_DTYPE.itemsize == 80
+
+
+def debug_walk_value(weight: float, freqs, norm_bytes, table256: np.ndarray, fx_scale: int, fx_shift: int) -> np.ndarray:
+    """Test hook of the development library (nrtgpu_debug_walk_value): what a posting of (freq, norm byte) adds to a doc's
+    fixed-point sum, computed on the device by the statement the scorers use -- one uint64 per (freq, norm byte) pair."""
+    f = np.ascontiguousarray(freqs, dtype=np.uint32)
+    nb = np.ascontiguousarray(norm_bytes, dtype=np.uint32)
+    tab = np.ascontiguousarray(table256, dtype=np.float32)
+    assert f.shape == nb.shape and f.ndim == 1 and tab.shape == (256,)
+    out = np.zeros(len(f), dtype=np.uint64)
+    _lib.check(_lib.load().nrtgpu_debug_walk_value(C.c_float(float(weight)), f.ctypes.data, nb.ctypes.data, len(f), tab.ctypes.data, int(fx_scale),
+                                                  int(fx_shift), out.ctypes.data))
+    return out
 
 
 def blend(retriever_docs: Sequence[np.ndarray], retriever_scores: Optional[Sequence[np.ndarray]] = None,

@@ -103,3 +103,85 @@ extern "C" int nrtgpu_debug_wave_kth(const uint64_t* keys, int32_t n, int32_t r,
   if (e != hipSuccess) return fail(NRTGPU_ERR_HIP, "wave_kth: %s", hipGetErrorString(e));
   return NRTGPU_OK;
 }
+
+// Test hook (include/nrtgpu_dev.h): the walk rows of a batch.  The plan is the searches' own (build_plan), the expansion the
+// searches' own kernel; the buffers are this call's.
+extern "C" int64_t nrtgpu_debug_walk_rows(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                          const nrtgpu_bm25_query* queries, int32_t n_queries, int32_t* out_begin, int32_t* out_n,
+                                          uint64_t* out_rows, int64_t cap_rows) {
+  if (!ctx || !segs || !queries || !out_begin || !out_n || (!out_rows && cap_rows > 0)) return -(int64_t)fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
+  if (n_queries <= 0 || n_segs <= 0 || cap_rows < 0) return -(int64_t)fail(NRTGPU_ERR_INVALID_ARG, "n_queries and n_segs must be > 0");
+  if (hipSetDevice(ctx->device) != hipSuccess) return -(int64_t)fail(NRTGPU_ERR_HIP, "hipSetDevice");
+  for (int si = 0; si < n_segs; ++si)
+    if (!segs[si]) return -(int64_t)fail(NRTGPU_ERR_INVALID_ARG, "segment %d is NULL", si);
+  SegReadLocks content(segs, n_segs);
+  HostPlan hp;
+  if (int rc = build_plan(ctx, segs, doc_bases, n_segs, queries, n_queries, hp, 1)) return -(int64_t)rc;
+  const size_t n_pairs = (size_t)n_queries * (size_t)n_segs;
+  for (size_t i = 0; i < n_pairs; ++i) out_begin[i] = -1, out_n[i] = 0;
+  if (hp.n_dterms == 0) return 0;
+  Carver c;
+  const size_t o_qx = c.take(sizeof(DExpandHead) + hp.qexpand.size() * sizeof(DQExpand)) + sizeof(DExpandHead), o_qt = c.take(hp.qterms.size() * sizeof(DQTerm));
+  const size_t o_qsb = c.take(hp.qs_begin.size() * 4), o_caches = c.take(hp.caches.size() * sizeof(float));
+  const size_t o_queries = c.take(hp.queries.size() * sizeof(DQuery)), o_up = c.off;
+  const size_t o_terms = c.take((size_t)hp.n_dterms * sizeof(DTerm)), o_rows = c.take((size_t)hp.n_dterms * sizeof(DWalkRow));
+  std::vector<char> hb(c.off, 0);
+  memcpy(hb.data() + o_qx, hp.qexpand.data(), hp.qexpand.size() * sizeof(DQExpand));
+  if (!hp.qterms.empty()) memcpy(hb.data() + o_qt, hp.qterms.data(), hp.qterms.size() * sizeof(DQTerm));
+  memcpy(hb.data() + o_qsb, hp.qs_begin.data(), hp.qs_begin.size() * 4);
+  if (!hp.caches.empty()) memcpy(hb.data() + o_caches, hp.caches.data(), hp.caches.size() * sizeof(float));
+  memcpy(hb.data() + o_queries, hp.queries.data(), hp.queries.size() * sizeof(DQuery));
+  char* db = nullptr;
+  if (hipMalloc((void**)&db, c.off) != hipSuccess) return -(int64_t)fail(NRTGPU_ERR_OOM, "hipMalloc");
+  DExpandHead xh{};
+  xh.caches = (const float*)(db + o_caches);
+  xh.queries = (const DQuery*)(db + o_queries);
+  xh.rows = (DWalkRow*)(db + o_rows);
+  memcpy(hb.data() + o_qx - sizeof(DExpandHead), &xh, sizeof(xh));
+  hipError_t e = hipMemcpy(db, hb.data(), o_up, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(db + o_up, 0, c.off - o_up);
+  if (e == hipSuccess) {
+    launch_expand_terms(nullptr, (const DQExpand*)(db + o_qx), (const DQTerm*)(db + o_qt), (const uint32_t*)(db + o_qsb), (uint32_t)n_queries,
+                        hp.n_leaves, (DTerm*)(db + o_terms));
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(hb.data() + o_rows, db + o_rows, (size_t)hp.n_dterms * sizeof(DWalkRow), hipMemcpyDeviceToHost);   // (the null stream: behind the kernel)
+  (void)hipFree(db);
+  if (e != hipSuccess) return -(int64_t)fail(NRTGPU_ERR_HIP, "walk_rows: %s", hipGetErrorString(e));
+  static_assert(sizeof(DWalkRow) == 80, "ten words per row");
+  if (out_rows) memcpy(out_rows, hb.data() + o_rows, (size_t)std::min<int64_t>(cap_rows, (int64_t)hp.n_dterms) * sizeof(DWalkRow));
+  // the rows of (query, leaf): where the plan put them; how many: up to the next pair's (pairs are numbered in plan order)
+  std::vector<uint32_t> begins;
+  for (size_t i = 0; i < n_pairs; ++i)
+    if (hp.qs_begin[i] != 0xFFFFFFFFu) begins.push_back(hp.qs_begin[i]);
+  std::sort(begins.begin(), begins.end());
+  for (size_t i = 0; i < n_pairs; ++i) {
+    const uint32_t b = hp.qs_begin[i];
+    if (b == 0xFFFFFFFFu || hp.qexpand[i / (size_t)n_segs].by_weight == 0u) continue;
+    auto nx = std::upper_bound(begins.begin(), begins.end(), b);
+    out_begin[i] = (int32_t)b;
+    out_n[i] = (int32_t)((nx == begins.end() ? hp.n_dterms : *nx) - b);
+  }
+  return (int64_t)hp.n_dterms;
+}
+
+// Test hook (include/nrtgpu_dev.h): one posting's fixed-point value, by the device's own statement of it.
+extern "C" int nrtgpu_debug_walk_value(float weight, const uint32_t* freq, const uint32_t* norm, int32_t n, const float* table256, int32_t fx_scale,
+                                       uint32_t fx_shift, uint64_t* out) {
+  if (!freq || !norm || !table256 || !out || n < 1 || fx_shift > 31u) return fail(NRTGPU_ERR_INVALID_ARG, "bad walk_value arguments");
+  char* d = nullptr;
+  const size_t o_f = 0, o_n = (size_t)n * 4, o_t = 2 * (size_t)n * 4, o_o = o_t + 1024, bytes = o_o + (size_t)n * 8;
+  if (hipMalloc((void**)&d, bytes) != hipSuccess) return fail(NRTGPU_ERR_OOM, "hipMalloc");
+  hipError_t e = hipMemcpy(d + o_f, freq, (size_t)n * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d + o_n, norm, (size_t)n * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d + o_t, table256, 1024, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    launch_debug_walk_value(nullptr, weight, (const uint32_t*)(d + o_f), (const uint32_t*)(d + o_n), (const float*)(d + o_t), fx_scale, fx_shift, (uint32_t)n,
+                            (uint64_t*)(d + o_o));
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(out, d + o_o, (size_t)n * 8, hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  if (e != hipSuccess) return fail(NRTGPU_ERR_HIP, "walk_value: %s", hipGetErrorString(e));
+  return NRTGPU_OK;
+}

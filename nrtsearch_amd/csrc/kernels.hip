@@ -1162,6 +1162,10 @@ void pack_write_kernel(const uint32_t* __restrict__ docids, const uint32_t* __re
 // the clauses the leaf holds, ordered densest first (exhaustive scan) or heaviest first, ties sparsest first (MaxScore
 // route), written at the offset the host reserved (out_begin; ~0 = the leaf holds none of the query's terms).  The
 // position of a clause is its rank among the leaf's clauses -- at most 32, so ranking by comparison needs no scratch.
+// MaxScore route (by_weight; DExpandHead.rows != nullptr): the WALK ROW of every clause as well (plan.h: DWalkRow) -- the clause's exact
+// maximum score in the leaf from the term's impact frontier, evaluated with the functions the walk scores postings with
+// (bm25_common.hiph; this file is built with the same floating-point flags), and the suffix sums (DisjunctionMaxQuery:
+// maxima) of those, last clause first.  The thread reads its own DTerms back in rank order: no array indexed by rank.
 __global__ __launch_bounds__(256)
 void expand_terms_kernel(const DQExpand* __restrict__ qx, const DQTerm* __restrict__ qterms, const uint32_t* __restrict__ out_begin,
                          uint32_t n_queries, uint32_t n_leaves, DTerm* __restrict__ out) {
@@ -1172,6 +1176,7 @@ void expand_terms_kernel(const DQExpand* __restrict__ qx, const DQTerm* __restri
   const uint32_t q = i / n_leaves, leaf = i - q * n_leaves;
   const DQExpand x = qx[q];
   const DQTerm* const qt = qterms + x.term_begin;
+  uint32_t n_here = 0;
   for (uint32_t t = 0; t < x.n_terms; ++t) {
     DTerm d = qt[t].table[leaf];
     if (d.docids == nullptr) continue;
@@ -1194,6 +1199,49 @@ void expand_terms_kernel(const DQExpand* __restrict__ qx, const DQTerm* __restri
     d.fx_scale = qt[t].fx_scale;
     d.fx_shift = qt[t].fx_shift;
     out[ob + rank] = d;
+    n_here += 1u;
+  }
+  if (x.by_weight == 0u) return;
+  const DExpandHead head = *((const DExpandHead*)qx - 1);   // (plan.h: in front of the DQExpand array)
+  DWalkRow* const rows = head.rows;
+  if (rows == nullptr) return;
+  const float* const caches = head.caches;
+  const bool use_max = head.queries[q].combine_max != 0u;
+  uint64_t run = 0;   // S_{c+1}
+  for (uint32_t c = n_here; c-- > 0u;) {
+    const DTerm d = out[ob + c];
+    // (the term's record as two 16-byte loads, its frontier bytes taken out of the words: a byte array indexed in a loop becomes
+    //  an LDS array per thread)
+    const u32x4 a0 = ((const u32x4*)d.aux)[0], a1 = ((const u32x4*)d.aux)[1];
+    static_assert(offsetof(DTermAux, min_norm) == 8 && offsetof(DTermAux, esc_min_norm) == 20 && offsetof(DTermAux, esc_max_freq) == 24, "DTermAux layout");
+    const uint32_t mn[3] = {a0[2], a0[3], a1[0]};
+    const uint32_t esc_min_norm = a1[1] & 255u, look_kind = (a1[1] >> 8) & 255u, look_shift = (a1[1] >> 16) & 255u, esc_max_freq = a1[2];
+    const uint64_t look = ((uint64_t)a0[1] << 32) | a0[0];
+    const float* const cache = caches + x.cache_off + d.cache_slot * 256u;
+    uint32_t v = 0;
+#pragma unroll
+    for (uint32_t f = 0; f < 12u; ++f) {
+      const uint32_t nb = (mn[f >> 2] >> (8u * (f & 3u))) & 255u;
+      if (nb != 0xFFu) v = max(v, score_value<true>(bm25_score(d.weight, (float)(int32_t)(f + 1u), cache[nb]), d.fx_scale));
+    }
+    if (esc_max_freq != 0u)
+      v = max(v, score_value<true>(bm25_score(d.weight, (float)(int32_t)esc_max_freq, cache[esc_min_norm]), d.fx_scale));
+    const uint64_t ub = (uint64_t)v << d.fx_shift;
+    DWalkRow r;
+    r.docids = (uint64_t)d.docids;
+    r.fnorm = (uint64_t)d.fnorm;
+    r.ub = ub;
+    r.weight = d.weight;
+    r.fx_scale = d.fx_scale;
+    r.flags = walk_row_flags(d.tab_slot, d.fx_shift, d.cache_slot, d.shift, look_kind, look_shift, (d.tab_slot & kTabSlotRequired) != 0u);
+    r.pad = 0;
+    r.u_after = run;
+    run = use_max ? max(run, ub) : run + ub;
+    r.suffix = run;
+    r.look = look_kind != kLookNone ? look : 0ull;
+    r.cells = (uint64_t)d.cell_off;
+    r.start = d.start;
+    rows[ob + c] = r;
   }
 }
 void launch_expand_terms(hipStream_t stream, const DQExpand* qx, const DQTerm* qterms, const uint32_t* out_begin, uint32_t n_queries,
@@ -1203,6 +1251,23 @@ void launch_expand_terms(hipStream_t stream, const DQExpand* qx, const DQTerm* q
   hipLaunchKernelGGL(expand_terms_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, qx, qterms, out_begin, n_queries,
                      n_leaves, out);
 }
+
+#ifdef NRTGPU_DEV
+// Test hook (include/nrtgpu_dev.h: nrtgpu_debug_walk_value): what a posting of (freq, norm byte) adds to a doc's fixed-point sum, by
+// the statement every scorer and the walk rows' bounds use.
+__global__ __launch_bounds__(256)
+void debug_walk_value_kernel(float weight, const uint32_t* __restrict__ freq, const uint32_t* __restrict__ norm, const float* __restrict__ table,
+                             int fx_scale, uint32_t fx_shift, uint32_t n, uint64_t* __restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[i] = (uint64_t)score_value<true>(bm25_score(weight, (float)(int32_t)freq[i], table[norm[i] & 255u]), fx_scale) << fx_shift;
+}
+void launch_debug_walk_value(hipStream_t stream, float weight, const uint32_t* freq, const uint32_t* norm, const float* table, int fx_scale,
+                             uint32_t fx_shift, uint32_t n, uint64_t* out) {
+  if (n == 0) return;
+  hipLaunchKernelGGL(debug_walk_value_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, weight, freq, norm, table, fx_scale, fx_shift, n, out);
+}
+#endif
 
 // slice_relation_kernel: TotalHits.relation by the reference's rule -- GREATER_THAN_OR_EQUAL_TO iff some slice's
 // collector saw more than max(totalHitsThreshold, numHits) hits (one collector per slice, MyIndexSearcher.java:163-208;

@@ -42,6 +42,12 @@
 // seen -- a workgroup publishes a GUESS at the final k-th key from the best of the docs it has walked; the merge checks every
 // guess against the merged list and the host runs a query whose guess failed again.  A guess therefore changes what is skipped
 // and, when it fails, how often a query is run -- never what is returned.
+// Walk rows (plan.h: DWalkRow; kernels.hip: expand_terms_kernel): what a wave needs of a clause that depends on (query, segment)
+// alone -- ub_j, S_j, S_{j+1} and the clause's record (WClause) -- is worked out ONCE per (query, segment) by the plan expansion,
+// which runs beside the previous batch's launch.  A wave that enters a part copies the part's rows into its LDS table with one
+// coalesced load; it used to rebuild them -- four to five dependent global loads and 13 score evaluations per clause -- every
+// time, as did the item's other eleven waves and its helpers.  The part that holds a window is found by a ballot over per-lane
+// window prefix sums (items of up to 64 parts), not by a search part by part.
 // Roofline: HBM.  Reported both ways: effective = 9 B x the postings of the query's terms, physical
 // = what the kernel fetches (a few percent of that).
 #include <hip/hip_runtime.h>
@@ -400,7 +406,10 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
     const __attribute__((address_space(4))) DHelp& hp = ap->help;
     const DItem* const items = as_global(ap->items);
     const DPart* const parts = as_global(ap->parts);
+    const DWalkRow* const rows = as_global(ap->rows);
+  #ifdef NRTGPU_DEV   // (A/B, NRTGPU_MS_WALK_ROWS=0: a launch without rows -- the walk works a part's bounds out itself)
     const DTerm* const terms = as_global(ap->terms);
+  #endif
     const DExchange* const xch = as_global(ap->xch);
     bool helper = false;
     uint32_t my_item = 0, out_slot = 0;
@@ -620,22 +629,45 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
     uint32_t pi = 0;        // its part ...
     uint32_t win_base = 0;  // ... and the windows of the parts before that one
 
+    // Which part holds a window?  Items of up to 64 parts: lane p keeps the windows of parts 0 .. p (one load per lane and a DPP
+    // scan, once per item), and the part of window g is one ballot away -- in the scattered order nearly every window is in
+    // another part, and a search part by part was a chain of dependent loads each time.  Longer items search part by part.
+    const bool parts_by_lane = item.n_parts <= 64u;   // (uniform)
+    uint32_t part_incl = 0;
+    if (parts_by_lane) {
+      uint32_t w = 0;
+      if (lane < item.n_parts) {
+        const u32x2 tr = *(gvec2_ptr)&parts[item.part_begin + lane].tile_begin;   // {tile_begin, tile_end}
+        w = (tr[1] - (tr[0] & ~(win_tiles - 1u)) + win_tiles - 1u) / win_tiles;
+      }
+      part_incl = scan64_dpp(w);
+    }
+
     for (;;) {
       // ---- the part that holds window g
       DPart part;
       uint32_t part_wins = 0;
-      if (sc_mul != 1u) {   // (scattered order: the next window may lie before the current part)
-        pi = 0;
-        win_base = 0;
-      }
-      for (;; ++pi) {
-        if (pi >= item.n_parts) break;
+      if (parts_by_lane) {
+        const uint64_t holds = __builtin_amdgcn_ballot_w64(lane < item.n_parts && g < part_incl);
+        if (holds == 0ull) break;   // past the item
+        pi = (uint32_t)__builtin_ctzll(holds);
         part = parts[item.part_begin + pi];
         // windows start on win_tiles boundaries of the SEGMENT (the first one of a part may be short): a window never
         // spans two 2^20-doc super-windows, which is what packed doc offsets are relative to
         part_wins = (part.tile_end - (part.tile_begin & ~(win_tiles - 1u)) + win_tiles - 1u) / win_tiles;
-        if (g < win_base + part_wins) break;
-        win_base += part_wins;
+        win_base = (uint32_t)__builtin_amdgcn_readlane((int)part_incl, (int)pi) - part_wins;
+      } else {
+        if (sc_mul != 1u) {   // (scattered order: the next window may lie before the current part)
+          pi = 0;
+          win_base = 0;
+        }
+        for (;; ++pi) {
+          if (pi >= item.n_parts) break;
+          part = parts[item.part_begin + pi];
+          part_wins = (part.tile_end - (part.tile_begin & ~(win_tiles - 1u)) + win_tiles - 1u) / win_tiles;
+          if (g < win_base + part_wins) break;
+          win_base += part_wins;
+        }
       }
       if (pi >= item.n_parts) break;
       {  // hits are counted per searcher slice: a part of another slice closes my count of the previous one
@@ -648,74 +680,99 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
         if (lane == 0) s.slot_slice[p_slot] = part.slice & 0xFFFFFFu;
       }
       const uint32_t n_terms = part.n_terms;  // <= kMsMaxTerms (planner)
-      const DTerm* const part_terms = terms + part.term_begin;
-
-      // ---- per part: lane l looks after clause l: its exact maximum score in this segment, suffix sums, and the
-      //      clause's record in the wave's LDS table (what a lane needs to stream or look up clause l)
-      uint64_t my_ub = 0, my_suf = 0;
+      // ---- per part: lane l looks after clause l.  What it needs -- the clause's record in the wave's LDS table (what a lane
+      //      needs to stream or look up clause l), S_l, the cell table -- depends on (query, leaf) alone and comes ready-made: the
+      //      part's WALK ROWS (plan.h: DWalkRow; written by expand_terms_kernel, once per (query, leaf)) are the table's image.
+      //      The wave copies them, 16 bytes per lane in one coalesced load, and lane l reads clause l's facts back from LDS.
+      uint64_t my_suf = 0, my_start = 0;
+      gu32_ptr my_cells = nullptr;
+      uint32_t my_shift = 0, my_flags = 0;
       const uint64_t t_part0 = PROF ? __builtin_readcyclecounter() : 0ull;
-      const DTerm mt = part_terms[min(lane, n_terms - 1u)];
-      {
-        // 16 lanes per clause, four clauses per pass: lane (g, i) evaluates frontier entry i of clause 4 * pass + g -- two
-        // dependent loads per PASS (the clause's record, then its frontier byte) instead of two per clause
-        uint32_t ub_raw = 0;
-        for (uint32_t pass = 0; pass * 4u < n_terms; ++pass) {  // uniform
-          const uint32_t tt = pass * 4u + (lane >> 4), i = lane & 15u;
-          const DTerm* Tp = part_terms + min(tt, n_terms - 1u);
-          const DTermAux* ax = Tp->aux;
-          const float w = Tp->weight;
-          const int scale = Tp->fx_scale;
-          const float* cache = &s.cache[Tp->cache_slot][0];
-          uint32_t v = 0;
-          if (tt < n_terms) {
-            if (i < 12u) {
-              const uint32_t nb = ax->min_norm[i];
-              if (nb != 0xFFu) v = score_value<true>(bm25_score(w, (float)(int32_t)(i + 1u), cache[nb]), scale);
-            } else if (i == 12u) {
-              const uint32_t mf = ax->esc_max_freq;
-              if (mf != 0u) v = score_value<true>(bm25_score(w, (float)(int32_t)mf, cache[ax->esc_min_norm]), scale);
+  #ifdef NRTGPU_DEV
+      if (rows == nullptr) {   // (A/B: the bounds from the terms' impact frontiers, here, by every wave that enters the part)
+        const DTerm* const part_terms = terms + part.term_begin;
+        uint64_t my_ub = 0;
+        const DTerm mt = part_terms[min(lane, n_terms - 1u)];
+        {
+          // 16 lanes per clause, four clauses per pass: lane (g, i) evaluates frontier entry i of clause 4 * pass + g -- two
+          // dependent loads per PASS (the clause's record, then its frontier byte) instead of two per clause
+          uint32_t ub_raw = 0;
+          for (uint32_t pass = 0; pass * 4u < n_terms; ++pass) {  // uniform
+            const uint32_t tt = pass * 4u + (lane >> 4), i = lane & 15u;
+            const DTerm* Tp = part_terms + min(tt, n_terms - 1u);
+            const DTermAux* ax = Tp->aux;
+            const float w = Tp->weight;
+            const int scale = Tp->fx_scale;
+            const float* cache = &s.cache[Tp->cache_slot][0];
+            uint32_t v = 0;
+            if (tt < n_terms) {
+              if (i < 12u) {
+                const uint32_t nb = ax->min_norm[i];
+                if (nb != 0xFFu) v = score_value<true>(bm25_score(w, (float)(int32_t)(i + 1u), cache[nb]), scale);
+              } else if (i == 12u) {
+                const uint32_t mf = ax->esc_max_freq;
+                if (mf != 0u) v = score_value<true>(bm25_score(w, (float)(int32_t)mf, cache[ax->esc_min_norm]), scale);
+              }
             }
+    #pragma unroll
+            for (int dlt = 8; dlt > 0; dlt >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, dlt, 64));  // maximum of each 16-lane group
+            const uint32_t got = (uint32_t)__shfl((int)v, (int)((lane & 3u) * 16u), 64);            // lane L = clause L: group L & 3 of pass L >> 2
+            if ((lane >> 2) == pass) ub_raw = got;
           }
-  #pragma unroll
-          for (int dlt = 8; dlt > 0; dlt >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, dlt, 64));  // maximum of each 16-lane group
-          const uint32_t got = (uint32_t)__shfl((int)v, (int)((lane & 3u) * 16u), 64);            // lane L = clause L: group L & 3 of pass L >> 2
-          if ((lane >> 2) == pass) ub_raw = got;
+          if (lane < n_terms) my_ub = (uint64_t)ub_raw << mt.fx_shift;
         }
-        if (lane < n_terms) my_ub = (uint64_t)ub_raw << mt.fx_shift;
-      }
-      uint64_t my_after = 0;   // what the clauses after mine can add (sum) / lift a doc to (DisjunctionMaxQuery): S_{lane+1}
+        uint64_t my_after = 0;   // what the clauses after mine can add (sum) / lift a doc to (DisjunctionMaxQuery): S_{lane+1}
+        {
+          uint64_t run = 0;
+          for (int m = (int)n_terms - 1; m >= 0; --m) {
+            const uint64_t ub = readlane_u64(my_ub, (uint32_t)m);
+            if (lane == (uint32_t)m) my_after = run;
+            run = use_max ? max(run, ub) : run + ub;
+            if (lane == (uint32_t)m) my_suf = run;
+          }
+        }
+        my_cells = (gu32_ptr)mt.cell_off;
+        my_shift = mt.shift;
+        my_start = mt.start;
+        if (lane < n_terms) {
+          WClause w;
+          w.docids = (uint64_t)mt.docids;
+          w.fnorm = (uint64_t)mt.fnorm;
+          w.begin = 0;
+          w.count = w.pad0 = 0;
+          w.weight = mt.weight;
+          w.fx_scale = mt.fx_scale;
+          const DTermAux* const ax = mt.aux;
+          const uint32_t look_kind = ax->look_kind;
+          w.flags = ((mt.tab_slot & 0xFFFFu) < (uint32_t)kTabTerms ? (mt.tab_slot & 0xFFFFu) : 7u) | (TWO && (mt.tab_slot & kTabSlotRequired) ? 8u : 0u) |
+                    (mt.fx_shift << 4) | (mt.cache_slot << 8) | ((mt.shift & 31u) << 16) | ((look_kind & 7u) << 24) | (((uint32_t)ax->look_shift & 31u) << 27);
+          w.pad = 0;
+          w.u_after = my_after;
+          w.look = look_kind != kLookNone ? (uint64_t)ax->look : 0ull;
+          w.cells = (uint64_t)mt.cell_off;
+          w.start = mt.start;
+          wcl[lane] = w;
+          my_flags = w.flags;
+        }
+      } else
+  #endif
       {
-        uint64_t run = 0;
-        for (int m = (int)n_terms - 1; m >= 0; --m) {
-          const uint64_t ub = readlane_u64(my_ub, (uint32_t)m);
-          if (lane == (uint32_t)m) my_after = run;
-          run = use_max ? max(run, ub) : run + ub;
-          if (lane == (uint32_t)m) my_suf = run;
+        static_assert(sizeof(DWalkRow) == sizeof(WClause) && sizeof(WClause) % 16 == 0, "a walk row is the image of a WClause");
+        const gvec_ptr src = (gvec_ptr)(rows + part.term_begin);
+        if (lane < n_terms * (uint32_t)(sizeof(WClause) / 16)) *(u32x4*)lds_ptr(wcl_addr + lane * 16u) = src[lane];
+        wave_lds_phase();
+        if (lane < n_terms) {
+          const uint32_t rec = wcl_addr + lane * (uint32_t)sizeof(WClause);
+          my_suf = *(const uint64_t*)lds_ptr(rec + 16u);   // (S_l rides in the slot of the window's posting range, filled per window)
+          my_flags = *(const uint32_t*)lds_ptr(rec + 40u);
+          const u32x4 cs = *(const u32x4*)lds_ptr(rec + 64u);
+          my_cells = (gu32_ptr)(((uint64_t)cs[1] << 32) | cs[0]);
+          my_start = ((uint64_t)cs[3] << 32) | cs[2];
         }
-      }
-      const gu32_ptr my_cells = (gu32_ptr)mt.cell_off;
-      const uint32_t my_shift = mt.shift;
-      if (lane < n_terms) {
-        WClause w;
-        w.docids = (uint64_t)mt.docids;
-        w.fnorm = (uint64_t)mt.fnorm;
-        w.begin = 0;
-        w.count = w.pad0 = 0;
-        w.weight = mt.weight;
-        w.fx_scale = mt.fx_scale;
-        const DTermAux* const ax = mt.aux;
-        const uint32_t look_kind = ax->look_kind;
-        w.flags = ((mt.tab_slot & 0xFFFFu) < (uint32_t)kTabTerms ? (mt.tab_slot & 0xFFFFu) : 7u) | (TWO && (mt.tab_slot & kTabSlotRequired) ? 8u : 0u) |
-                  (mt.fx_shift << 4) | (mt.cache_slot << 8) | ((mt.shift & 31u) << 16) | ((look_kind & 7u) << 24) | (((uint32_t)ax->look_shift & 31u) << 27);
-        w.pad = 0;
-        w.u_after = my_after;
-        w.look = look_kind != kLookNone ? (uint64_t)ax->look : 0ull;
-        w.cells = (uint64_t)mt.cell_off;
-        w.start = mt.start;
-        wcl[lane] = w;
+        my_shift = (my_flags >> 16) & 31u;
       }
       // (uniform) the part's MUST clauses, bit c = clause c; first_req: the last clause that may start a doc
-      const uint32_t req_mask = TWO ? (uint32_t)__builtin_amdgcn_ballot_w64(lane < n_terms && (mt.tab_slot & kTabSlotRequired) != 0u) : 0u;
+      const uint32_t req_mask = TWO ? (uint32_t)__builtin_amdgcn_ballot_w64(lane < n_terms && (my_flags & 8u) != 0u) : 0u;
       const uint32_t first_req = req_mask != 0u ? (uint32_t)__builtin_ctz(req_mask) : 0xFFu;
       if (PROF) tc_part += __builtin_readcyclecounter() - t_part0;
 
@@ -768,7 +825,7 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
         uint32_t ng = 0;
         {
           const uint64_t thr_w = __hip_atomic_load(&s.prune_on, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) ? loosen(max(s.thr, thr_other)) : 0ull;
-          const uint64_t pb = mt.start + my_lo, pe = mt.start + my_hi;
+          const uint64_t pb = my_start + my_lo, pe = my_start + my_hi;
           if (lane < n_terms) {
             // (minimumNumberShouldMatch: a doc is evaluated at the first clause that holds it, so one first met at clause c matches
             //  at most n_terms - c clauses: the last msm - 1 clauses cannot start a hit and are never streamed)

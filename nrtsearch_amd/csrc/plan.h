@@ -95,9 +95,20 @@ struct alignas(16) DQExpand {
   uint32_t term_begin;       // the query's DQTerms
   uint32_t n_terms;
   uint32_t by_weight;        // order of a (query, leaf)'s DTerms: 1 = heaviest clause first (MaxScore route), 0 = densest first
-  uint32_t pad;
+  uint32_t cache_off;        // offset in floats of the query's first normInverse table (DItem.cache_off): the walk rows' bounds
 };
 static_assert(sizeof(DQExpand) == 16, "DQExpand layout");
+// What the expansion needs for the MaxScore route's walk rows (DWalkRow, below): ONE record in the plan upload, directly in front
+// of the batch's DQExpand array (expand_terms_kernel reads it in front of qx[0]; its arguments stay the compact plan's).
+struct DWalkRow;
+struct DQuery;
+struct alignas(16) DExpandHead {
+  const float* caches;       // the queries' normInverse tables (DQExpand.cache_off indexes them)
+  const DQuery* queries;     // DQuery.combine_max: suffix maxima instead of sums
+  DWalkRow* rows;            // one row per DTerm of a by_weight query, same index; nullptr: none are written
+  uint64_t pad;
+};
+static_assert(sizeof(DExpandHead) == 2 * sizeof(DQExpand), "the head takes the place of two DQExpand records");
 
 // What the MaxScore route (maxscore.hip) knows about a term besides its columns (one record per term of a segment,
 // written at seal): the term's impact frontier -- per freq the smallest norm byte it occurs with -- from which the kernel
@@ -132,6 +143,32 @@ struct alignas(16) DTermAux {
   uint32_t pad2;
 };
 static_assert(sizeof(DTermAux) == 32, "DTermAux layout");
+
+// WALK ROWS: what the MaxScore walk needs of a clause that depends only on (query, leaf) -- the part-static image of the record
+// a wave keeps per clause in LDS (maxscore.hip: WClause, the same 80 bytes) with the clause's bounds filled in: its exact maximum
+// score in the leaf under the query's statistics, ub, from the term's impact frontier (DTermAux), what the clauses after it can add
+// (sum; DisjunctionMaxQuery: lift a doc to, the maximum), u_after = S_{c+1}, and suffix = S_c.  expand_terms_kernel writes one row
+// next to every DTerm of a query on that route (same index, out_begin + rank), once per (query, leaf); a wave that enters a part
+// copies the part's rows into its LDS table instead of working them out again -- an item's 12 waves and its helpers all did.
+struct alignas(16) DWalkRow {
+  uint64_t docids, fnorm;   // column bases
+  uint64_t suffix;          // S_c = ub combined with u_after (the walk keeps a window's posting range in these two slots)
+  uint64_t ub;              // the clause's maximum score in the leaf, in the query's common fixed-point scale
+  float    weight;
+  int32_t  fx_scale;
+  uint32_t flags;           // as WClause.flags; the MUST bit is filled whatever kernel variant reads the row
+  uint32_t pad;
+  uint64_t u_after;
+  uint64_t look;            // DTermAux.look, 0 = none
+  uint64_t cells, start;    // DTerm.cell_off, DTerm.start
+};
+static_assert(sizeof(DWalkRow) == 80, "DWalkRow layout");
+// the flags word of a walk row / WClause (maxscore.hip documents the fields)
+__host__ __device__ inline uint32_t walk_row_flags(uint32_t tab_slot, uint32_t fx_shift, uint32_t cache_slot, uint32_t cell_shift,
+                                                   uint32_t look_kind, uint32_t look_shift, bool must) {
+  return ((tab_slot & 0xFFFFu) < (uint32_t)kTabTerms ? (tab_slot & 0xFFFFu) : 7u) | (must ? 8u : 0u) | (fx_shift << 4) | (cache_slot << 8) |
+         ((cell_shift & 31u) << 16) | ((look_kind & 7u) << 24) | ((look_shift & 31u) << 27);
+}
 
 // Workgroup shape of the MaxScore route: 12 autonomous waves (168 VGPRs each); a wave owns a window of kMsWinTiles
 // sub-tiles at a time (its docs' "already evaluated" bits: kMsWinDocs / 8 bytes of LDS).
@@ -303,6 +340,7 @@ struct MsArgs {
   uint64_t* item_hits;           // ... and the hits counted there
   uint64_t* item_prof;           // instrumented kernel: 16 counters per output slot, else nullptr
   const uint32_t* q_wins;        // per query: the doc windows of all its items (speculation: the denominator of "how much have I seen")
+  const DWalkRow* rows;          // the walk rows, indexed like `terms` (development build, A/B: nullptr = the walk works the bounds out itself)
   uint32_t k_stride;
   uint32_t scatter;              // != 0: an item's doc windows are handed out in a SCATTERED order (maxscore.hip): whatever a workgroup
                                  // has walked so far is spread over the item's docs like a sample -- what the speculative thresholds

@@ -429,7 +429,7 @@ static void resolve_queries(LeafSetCache& lsc, const nrtgpu_seg* const* segs, in
     DQExpand& qx = qexpand[(size_t)qi];
     qx.term_begin = (uint32_t)pc.qterms.size();
     qx.by_weight = route != kRouteScan ? 1u : 0u;
-    qx.pad = 0;
+    qx.cache_off = 0;   // (build_plan: known once the pieces are concatenated)
     const uint32_t* cnt_of[kMaxTerms];
     bool req_of[kMaxTerms];
     uint32_t n_live = 0;
@@ -589,6 +589,7 @@ int nrtgpu::rt::build_plan(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const
     for (QS& qs : pc.qs) qs.term_begin += dterm_base;
     for (int qi = chunk_begin(t); qi < chunk_begin(t + 1); ++qi) {
       cache_base[(size_t)qi] += c_base;
+      hp.qexpand[(size_t)qi].cache_off = cache_base[(size_t)qi];
       hp.qexpand[(size_t)qi].term_begin += qterm_base;
       piece_of[(size_t)qi] = t;
       if (dterm_base)

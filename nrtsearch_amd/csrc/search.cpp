@@ -130,7 +130,7 @@ static int enqueue_search(nrtgpu_ctx* ctx, Slot* slot, const HostPlan& hp, int32
   const size_t o_items = pc.take(n_items * sizeof(DItem));
   const size_t o_parts = pc.take(hp.parts.size() * sizeof(DPart));
   const size_t o_qterms = pc.take(hp.qterms.size() * sizeof(DQTerm));
-  const size_t o_qexp = pc.take(hp.qexpand.size() * sizeof(DQExpand));
+  const size_t o_qexp = pc.take(sizeof(DExpandHead) + hp.qexpand.size() * sizeof(DQExpand)) + sizeof(DExpandHead);   // (the head in front: filled in below)
   const size_t o_qsb = pc.take(hp.qs_begin.size() * 4);
   const size_t o_caches = pc.take(hp.caches.size() * sizeof(float));
   const size_t o_lidx = pc.take(hp.list_idx.size() * 4);
@@ -202,6 +202,10 @@ static int enqueue_search(nrtgpu_ctx* ctx, Slot* slot, const HostPlan& hp, int32
   const size_t o_ocnt = wc.take((size_t)n_queries * 4);
   const size_t o_ohits = wc.take((size_t)n_queries * 8);
   const size_t o_terms = wc.take((size_t)hp.n_dterms * sizeof(DTerm));  // written by expand_terms_kernel
+  // ... and the MaxScore route's walk rows beside them (plan.h: DWalkRow; same index).  NRTGPU_MS_WALK_ROWS=0 (development build,
+  // read per call): none are written and the walk works a part's bounds out itself, as it did before the rows (A/B in one process)
+  const bool walk_rows = hp.n_ms_items != 0 && dev_env_int("NRTGPU_MS_WALK_ROWS", 1) != 0;
+  const size_t o_rows = wc.take(walk_rows ? (size_t)hp.n_dterms * sizeof(DWalkRow) : 0);
   // per (query, searcher slice) the hits its items counted, per query "some item's slice has passed the floor": zeroed per call
   const size_t o_ssum = wc.take((size_t)n_queries * hp.n_slices * 4), o_qprune = wc.take((size_t)n_queries * 4);
   // the helpers' state (zeroed per call as well): per MaxScore item the window counter, the helpers that joined, the owner's
@@ -287,6 +291,14 @@ static int enqueue_search(nrtgpu_ctx* ctx, Slot* slot, const HostPlan& hp, int32
   ms_args.item_hits = (uint64_t*)(wb + o_ihits);
   ms_args.item_prof = profile ? (uint64_t*)(wb + o_prof) : nullptr;
   ms_args.q_wins = (const uint32_t*)(db + o_qwins);
+  ms_args.rows = walk_rows ? (const DWalkRow*)(wb + o_rows) : nullptr;
+  {   // ... which the plan expansion writes (plan.h: DExpandHead)
+    DExpandHead xh{};
+    xh.caches = (const float*)(db + o_caches);
+    xh.queries = (const DQuery*)(db + o_queries);
+    xh.rows = walk_rows ? (DWalkRow*)(wb + o_rows) : nullptr;
+    memcpy(hb + o_qexp - sizeof(DExpandHead), &xh, sizeof(xh));
+  }
   {   // the leaf set's window order (note_speculation); NRTGPU_MS_SCATTER = 0 / 1 (development build): forced, A/B
     const long forced = dev_env_int("NRTGPU_MS_SCATTER", -1);
     // (the leaf set's step: search.cpp: note_speculation_of; forced: the bits as given)
