@@ -603,6 +603,65 @@ int  nrtgpu_search_hybrid_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, 
                                 nrtgpu_topdocs* out /* n_queries, capacity >= window */);
 
 /* ---------------------------------------------------------------------------------------------
+ * Function-score queries: MultiFunctionScoreQuery (src/main/java/com/yelp/nrtsearch/server/query/multifunction/
+ * MultiFunctionScoreQuery.java) with WEIGHT functions over a BM25 disjunction -- "docs matching filter F score x 1.5".
+ * The reference creates the inner weight with ScoreMode.COMPLETE and its scorer answers getMaxScore = Float.MAX_VALUE
+ * (:168-174, :503-505): nothing is pruned, every live matching doc is scored, totalHits is exact.  So the inner query runs
+ * exhaustively in a kernel of its own (csrc/funcscore.hip) that applies, per doc, between "sum of the clause scores" and
+ * "key into the top-k" (MultiFunctionScoreQuery.java:445-500, WeightFilterFunction.java:66-71; one IEEE operation each):
+ *   function score fs (double)   SCORE_MODE_MULTIPLY: 1.0, then for i = 0..n-1 in order, if the doc is in set i: fs *= (double)weight_i
+ *                                SCORE_MODE_SUM:      0.0, fs += (double)weight_i for every matching i; none matched: fs = 1.0
+ *   final score                  BOOST_MODE_MULTIPLY: (float)((double)inner * fs)   BOOST_MODE_SUM: (float)((double)inner + fs)
+ *                                BOOST_MODE_REPLACE:  (float)fs                     n_functions == 0: inner itself (:449-451)
+ *   hit test                     only when min_score > 0 or min_excluded (:334-336, :60-65): a doc is a hit iff
+ *                                final > min_score || (!min_excluded && final == min_score); a doc that fails is no hit at all --
+ *                                not counted in total_hits, not in the per-slice relation counts
+ *   inner                        what nrtgpu_search_bm25 scores for the doc: (float) of the double sum of its matching clauses
+ * queries[i] keeps its meaning for k, total_hits_threshold, has_after / after_* (searchAfter compares FINAL scores), filter_mask /
+ * must_not_mask / more_* (the accept set restricts which docs match the inner query), liveDocs and slicing (nrtgpu_set_slicing,
+ * nrtgpu_set_thread_slices).  total_hits is always the exact number of hits; total_hits_is_lower_bound follows the reference's
+ * per-slice rule as on the exhaustive route; deadlines work as in nrtgpu_search_bm25_batch.
+ * Refusals, each with a reason in nrtgpu_last_error:
+ *   NRTGPU_ERR_INVALID_ARG  n_functions outside 0..NRTGPU_MAX_FUNCTIONS; modes outside their ranges; min_score < 0 or not finite;
+ *                           a weight that is NaN, infinite or 0; functions == NULL with n_functions > 0; whatever
+ *                           nrtgpu_search_bm25_batch refuses of queries[i] with that status
+ *   NRTGPU_ERR_UNSUPPORTED  a weight < 0 (the reference may or may not throw at :454-460: the caller keeps Lucene); a function mask
+ *                           that is not resident on a leaf of the call; an inner disjunction_max, any MUST clause,
+ *                           min_should_match > 1 or min_competitive_score != 0; a batch whose queries do not all pass the
+ *                           fixed-point analysis, or NRTGPU_FLAG_NO_FIXED_POINT (fixed-point sums are exact in any order, which
+ *                           the kernel relies on); a context with NRTGPU_FLAG_PACKED_POSTINGS
+ * Accounting: nrtgpu_last_diagnostics reports the call's items as items_scan (items_maxscore = 0); nrtgpu_get_stats counts the
+ * launch under scan_launches, scan_items, scan_postings, scan_ms and fixed_point_launches.
+ * Out of scope: script and decay functions (they read doc values); a match-all inner query; the coalesced, device-resident,
+ * hybrid and nrtgpu_dist_* forms; pruning by the largest possible factor; the Java shim, which does not bind this yet.
+ * --------------------------------------------------------------------------------------------- */
+#define NRTGPU_MAX_FUNCTIONS 8
+typedef struct {
+  int32_t filter_mask;  /* 0: no filter query, the function applies to every doc; else a resident mask id (nrtgpu_segment_set_mask) */
+  float   weight;       /* FilterFunction.getWeight(): finite, > 0.  The request's 0 means 1 (FilterFunction.java:83); the caller maps it */
+} nrtgpu_score_function;                       /* 8 bytes */
+typedef struct {
+  int32_t n_functions;                         /* 0..NRTGPU_MAX_FUNCTIONS */
+  const nrtgpu_score_function* functions;      /* in the request's order */
+  int32_t score_mode;                          /* 0 SCORE_MODE_MULTIPLY, 1 SCORE_MODE_SUM */
+  int32_t boost_mode;                          /* 0 BOOST_MODE_MULTIPLY, 1 BOOST_MODE_SUM, 2 BOOST_MODE_REPLACE */
+  float   min_score;                           /* >= 0 */
+  int32_t min_excluded;                        /* 0 / 1 */
+} nrtgpu_function_score;                       /* 32 bytes */
+/* n_queries function-score searches over the same leaves in one device pass; functions[i] wraps queries[i] */
+int  nrtgpu_search_function_score_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                        const nrtgpu_bm25_query* queries, const nrtgpu_function_score* functions,
+                                        int32_t n_queries, nrtgpu_topdocs* out);
+/* The eligibility test alone, as nrtgpu_query_supported: NRTGPU_OK if the search above would run (q, fs) over these leaves, else
+ * the status it would return with the reason in nrtgpu_last_error.  No device work. */
+int  nrtgpu_function_score_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query* q,
+                                     const nrtgpu_function_score* fs);
+/* The arithmetic above for one doc, exposed for the tests like nrtgpu_byte_vector_score: needs no device; it is the very function
+ * the kernel compiles.  matched: bit i set = the doc is in function i's set.  Validates fs (the refusals above). */
+int  nrtgpu_function_score_value(const nrtgpu_function_score* fs, uint32_t matched, float inner, float* out_score,
+                                 int32_t* out_is_hit);
+
+/* ---------------------------------------------------------------------------------------------
  * Host-side restatements the Java shim would otherwise take from Lucene objects
  * (BM25Similarity.scorer(boost, collectionStats, termStats); SmallFloat; slices()).
  * --------------------------------------------------------------------------------------------- */
@@ -664,7 +723,7 @@ typedef struct {
   int64_t postings;        /* postings of the call's query terms (what an exhaustive scan streams) */
   int32_t queries;         /* queries of the batch */
   int32_t items_maxscore;  /* work items on the dynamic-pruning route */
-  int32_t items_scan;      /* work items on the exhaustive route */
+  int32_t items_scan;      /* work items on the exhaustive route (a function-score call: all of its items) */
   int32_t reserved;
 } nrtgpu_diagnostics;
 int  nrtgpu_last_diagnostics(nrtgpu_diagnostics* out);
@@ -675,7 +734,7 @@ int  nrtgpu_last_diagnostics(nrtgpu_diagnostics* out);
 typedef struct {
   int64_t batches;            /* batch calls completed */
   int64_t queries;
-  int64_t scan_launches;      /* postings-scan kernel launches */
+  int64_t scan_launches;      /* postings-scan kernel launches; a function-score call's kernel counts here, and in the four scan_* / fixed_point fields below */
   double  scan_ms;            /* sum of HIP-event durations of those launches (collect_timing) */
   int64_t scan_postings;      /* sum over launches of postings in the scanned term ranges */
   int64_t scan_items;

@@ -30,6 +30,7 @@ NRTGPU_FLAG_BLOCKING_WAIT = 64
 NRTGPU_FLAG_NO_VECTOR_SKETCH = 128
 NRTGPU_FLAG_PROFILE = 7 << 8   # include/nrtgpu_dev.h: the development library only
 NRTGPU_MAX_MASKS = 8
+NRTGPU_MAX_FUNCTIONS = 8
 
 # every symbol include/nrtgpu.h declares (tests/test_abi.py checks the header against this list)
 ABI_SYMBOLS = [
@@ -49,6 +50,7 @@ ABI_SYMBOLS = [
     "nrtgpu_knn_exact_relation", "nrtgpu_set_speculation", "nrtgpu_set_shard_share", "nrtgpu_set_thread_slices",
     "nrtgpu_segment_add_byte_vectors", "nrtgpu_knn_exact_bytes", "nrtgpu_knn_search_bytes", "nrtgpu_byte_vector_score",
     "nrtgpu_rescore_byte_vectors", "nrtgpu_search_hybrid_bytes_batch", "nrtgpu_set_knn_gather",
+    "nrtgpu_search_function_score_batch", "nrtgpu_function_score_supported", "nrtgpu_function_score_value",
 ]
 # what include/nrtgpu_dev.h adds: test hooks and measurement helpers of the development library (libnrtgpu_dev.so) only
 DEV_SYMBOLS = [
@@ -80,6 +82,15 @@ class Bm25Query(C.Structure):
                 ("n_more_filters", C.c_int32), ("more_filters", C.POINTER(C.c_int32)),
                 ("n_more_must_not", C.c_int32), ("more_must_not", C.POINTER(C.c_int32)),
                 ("tie_breaker", C.c_float), ("reserved", C.c_int32)]
+
+
+class ScoreFunction(C.Structure):   # nrtgpu_score_function
+    _fields_ = [("filter_mask", C.c_int32), ("weight", C.c_float)]
+
+
+class FunctionScore(C.Structure):   # nrtgpu_function_score
+    _fields_ = [("n_functions", C.c_int32), ("functions", C.POINTER(ScoreFunction)), ("score_mode", C.c_int32),
+                ("boost_mode", C.c_int32), ("min_score", C.c_float), ("min_excluded", C.c_int32)]
 
 
 class TopDocs(C.Structure):
@@ -176,6 +187,9 @@ def _open(path: str) -> C.CDLL:
     L.nrtgpu_knn_search_bytes.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, i32, f32, i32, f32, C.POINTER(TopDocs)]
     L.nrtgpu_byte_vector_score.argtypes = [i32, i32, i32, i32, i32, vp]
     L.nrtgpu_set_knn_gather.argtypes = [vp, i32]
+    L.nrtgpu_search_function_score_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(FunctionScore), i32, C.POINTER(TopDocs)]
+    L.nrtgpu_function_score_supported.argtypes = [vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(FunctionScore)]
+    L.nrtgpu_function_score_value.argtypes = [C.POINTER(FunctionScore), C.c_uint32, f32, vp, vp]
     L.nrtgpu_rescore_vectors.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, f32, vp, vp, i32, C.c_double, C.c_double, i32,
                                          C.POINTER(TopDocs)]
     L.nrtgpu_search_hybrid_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), i32, i32, i32, vp, i32, f32,

@@ -82,6 +82,34 @@ class DisjunctionMaxQuery:
 Query = Union[TermQuery, BoostQuery, BooleanQuery, DisjunctionMaxQuery]
 
 
+@dataclasses.dataclass(frozen=True)
+class WeightFunction:
+    """One FilterFunction of a MultiFunctionScoreQuery that is a plain weight (S/query/multifunction/WeightFilterFunction.java):
+    docs in the function's filter -- a resident mask, 0 = no filter query: every doc -- get `weight`.  The request's weight 0
+    means 1 (FilterFunction.java:83): the caller maps it."""
+
+    weight: float
+    mask_id: int = 0
+
+
+@dataclasses.dataclass(frozen=True)
+class FunctionScoreQuery:
+    """MultiFunctionScoreQuery with weight functions over a BM25 disjunction (S/query/multifunction/MultiFunctionScoreQuery.java):
+    score_mode "multiply" / "sum" combines the matching functions' weights, boost_mode "multiply" / "sum" / "replace" combines
+    that with the inner score; min_score / min_excluded drop docs whose final score fails the test."""
+
+    inner: Query
+    functions: Tuple[WeightFunction, ...] = ()
+    score_mode: str = "multiply"
+    boost_mode: str = "multiply"
+    min_score: float = 0.0
+    min_excluded: bool = False
+
+
+SCORE_MODES = {"multiply": 0, "sum": 1}                  # nrtgpu_function_score.score_mode
+BOOST_MODES = {"multiply": 0, "sum": 1, "replace": 2}    # ... .boost_mode
+
+
 class UnsupportedQuery(Exception):
     """The rewritten query is not eligible for the device route: run the CPU (Lucene) path."""
 
@@ -625,6 +653,59 @@ class GpuIndexSearcher:
 
     def search(self, query: Query, manager: TopScoreDocCollectorManager) -> TopDocs:
         return self.search_batch([query], [manager])[0]
+
+    def _marshal_function_scores(self, queries: Sequence[FunctionScoreQuery], m: _Marshalled):
+        """nrtgpu_function_score per query; the ctypes arrays stay alive in m.keep."""
+        fs = (_lib.FunctionScore * len(queries))()
+        for qi, query in enumerate(queries):
+            if query.score_mode not in SCORE_MODES or query.boost_mode not in BOOST_MODES:
+                raise UnsupportedQuery(f"score_mode {query.score_mode!r} / boost_mode {query.boost_mode!r}")
+            funcs = (_lib.ScoreFunction * max(len(query.functions), 1))()
+            for i, f in enumerate(query.functions):
+                funcs[i] = _lib.ScoreFunction(int(f.mask_id), float(np.float32(f.weight)))
+            m.keep.append(funcs)
+            fs[qi].n_functions = len(query.functions)
+            fs[qi].functions = funcs
+            fs[qi].score_mode = SCORE_MODES[query.score_mode]
+            fs[qi].boost_mode = BOOST_MODES[query.boost_mode]
+            fs[qi].min_score = float(np.float32(query.min_score))
+            fs[qi].min_excluded = int(bool(query.min_excluded))
+        m.keep.append(fs)
+        return fs
+
+    def search_function_score_batch(self, queries: Sequence[FunctionScoreQuery],
+                                    managers: Sequence[TopScoreDocCollectorManager]) -> List[TopDocs]:
+        """MultiFunctionScoreQuery searches (nrtgpu_search_function_score_batch): every live doc matching the inner query is
+        scored, total_hits is exact."""
+        n = len(queries)
+        m = self._marshal([q.inner for q in queries], managers)
+        fs = self._marshal_function_scores(queries, m)
+        outs = (_lib.TopDocs * n)()
+        bufs = []
+        for qi, mgr in enumerate(managers):
+            cap = max(int(mgr.num_hits), 1)
+            d = np.zeros(cap, dtype=np.int32)
+            s = np.zeros(cap, dtype=np.float32)
+            bufs.append((d, s))
+            outs[qi].capacity = cap
+            outs[qi].docs = d.ctypes.data_as(C.POINTER(C.c_int32))
+            outs[qi].scores = s.ctypes.data_as(C.POINTER(C.c_float))
+        _lib.check(_lib.load().nrtgpu_search_function_score_batch(self.ctx._h, self._segs, self._bases, len(self.leaves),
+                                                                  m.queries, fs, n, outs))
+        return [TopDocs(bufs[qi][0][: outs[qi].n_hits].copy(), bufs[qi][1][: outs[qi].n_hits].copy(), int(outs[qi].total_hits),
+                        bool(outs[qi].total_hits_is_lower_bound)) for qi in range(n)]
+
+    def function_score_supported(self, query: FunctionScoreQuery, manager: TopScoreDocCollectorManager) -> bool:
+        """The eligibility predicate alone (nrtgpu_function_score_supported)."""
+        m = self._marshal([query.inner], [manager])
+        fs = self._marshal_function_scores([query], m)
+        rc = _lib.load().nrtgpu_function_score_supported(self.ctx._h, self._segs, len(self.leaves), m.queries, fs)
+        if rc == _lib.NRTGPU_OK:
+            return True
+        if rc == _lib.NRTGPU_ERR_UNSUPPORTED:
+            return False
+        _lib.check(rc)
+        return False
 
     def debug_walk_rows(self, queries: Sequence[Query], managers: Sequence[TopScoreDocCollectorManager]):
         """Test hook of the development library (nrtgpu_debug_walk_rows): the MaxScore route's walk rows of the batch, as the

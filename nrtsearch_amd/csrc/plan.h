@@ -466,6 +466,58 @@ __host__ __device__ inline float knn_byte_score(int sim, int32_t dim, int32_t do
   return x < 0.0f ? 1.0f / (1.0f + -1.0f * x) : x + 1.0f;
 }
 
+// Function-score queries (funcscore.hip: bm25_function_score_kernel; funcscore.cpp): MultiFunctionScoreQuery over a BM25
+// disjunction with weight functions only -- per doc a boost from the function sets it lies in.  One record per query of the call,
+// and per part of the plan (same index as DPart) the resident doc set of every function on the part's leaf.
+constexpr int kMaxFunctions = 8;
+constexpr int kFsCandCap = 3072;    // the kernel's LDS candidate slots: >= kMaxK + kTileDocs (the k kept + one wave's whole sub-tile always fit)
+static_assert(kFsCandCap >= kMaxK + kTileDocs, "function-score candidate buffer too small");
+struct alignas(16) DFuncQuery {
+  int32_t n_functions;              // 0..kMaxFunctions
+  int32_t score_mode;               // 0 SCORE_MODE_MULTIPLY, 1 SCORE_MODE_SUM
+  int32_t boost_mode;               // 0 BOOST_MODE_MULTIPLY, 1 BOOST_MODE_SUM, 2 BOOST_MODE_REPLACE
+  int32_t min_excluded;
+  float   min_score;
+  uint32_t pad[3];
+  float   weight[kMaxFunctions];    // FilterFunction.getWeight(), in the request's order
+};
+static_assert(sizeof(DFuncQuery) == 64, "DFuncQuery layout");
+struct alignas(16) DFuncMasks {
+  const uint64_t* mask[kMaxFunctions];   // liveDocs & the function's filter on the part's leaf; nullptr: every doc is in the set
+};
+static_assert(sizeof(DFuncMasks) == 64, "DFuncMasks layout");
+
+// The score of one doc under a function-score query -- MultiFunctionScoreQuery.java:445-500 (MultiFunctionScorer.score,
+// computeFunctionScore, computeFinalScore) with WeightFilterFunction.java:66-71 -- and whether the doc is a hit (the minScore
+// wrapper, :60-65 and :334-336).  matched: bit i = the doc lies in function i's set.  inner: the inner query's float score.
+// Every operation is one IEEE operation rounded once.  The ONE statement of it: bm25_function_score_kernel and
+// nrtgpu_function_score_value both call this function (f is read where it lies: no indexed copy in registers).
+__host__ __device__ inline float function_score_value(const DFuncQuery& f, uint32_t matched, float inner, bool* is_hit) {
+  float final_score = inner;
+  if (f.n_functions != 0) {
+    double fs;
+    if (f.score_mode == 0) {
+      fs = 1.0;
+      for (int i = 0; i < f.n_functions; ++i)
+        if ((matched >> i) & 1u) fs *= (double)f.weight[i];
+    } else {
+      fs = 0.0;
+      bool any = false;
+      for (int i = 0; i < f.n_functions; ++i)
+        if ((matched >> i) & 1u) {
+          fs += (double)f.weight[i];
+          any = true;
+        }
+      if (!any) fs = 1.0;
+    }
+    final_score = f.boost_mode == 0 ? (float)((double)inner * fs) : (f.boost_mode == 1 ? (float)((double)inner + fs) : (float)fs);
+  }
+  *is_hit = true;
+  if (f.min_score > 0.0f || f.min_excluded != 0)
+    *is_hit = final_score > f.min_score || (f.min_excluded == 0 && final_score == f.min_score);
+  return final_score;
+}
+
 __host__ __device__ inline uint64_t pack_key(float score, uint32_t global_doc) {
   union { float f; uint32_t u; } c;
   c.f = score;
