@@ -662,6 +662,72 @@ int  nrtgpu_function_score_value(const nrtgpu_function_score* fs, uint32_t match
                                  int32_t* out_is_hit);
 
 /* ---------------------------------------------------------------------------------------------
+ * Multi-match queries: the TWO-LEVEL shapes the reference builds for a text search over several fields that analyses to
+ * several tokens (multiMatchQuery, src/main/java/com/yelp/nrtsearch/server/query/QueryNodeMapper.java:429-528):
+ *   best_fields  (:444-496)  a DisjunctionMaxQuery over one BooleanQuery of term clauses per field    NRTGPU_GROUPS_MAX_OF_SUM
+ *   cross_fields (.../multimatch/MatchCrossFieldsQuery.java:163-192) a BooleanQuery with one clause per token, each a
+ *                BlendedTermQuery, i.e. a DisjunctionMaxQuery of the token's per-field term queries     NRTGPU_GROUPS_SUM_OF_MAX
+ * queries[i] holds ALL term clauses; groups[i] says which group (inner query) each belongs to.  The clauses run exhaustively in
+ * a kernel of its own (csrc/multimatch.hip); nothing is pruned.  Per doc, c ranging over the clauses of a group that match it,
+ * g over the groups that match it, groups and clauses in their order, every step one IEEE operation rounded once:
+ *   dismax(max, sum)            (float)((double)max + (sum - (double)max) * (double)tie_breaker), sum the double sum of ALL scores:
+ *                               DisjunctionMaxScorer's (float)(scoreMax + otherScoreSum * tieBreaker)
+ *                               NRTGPU_GROUPS_SUM_OF_MAX                            NRTGPU_GROUPS_MAX_OF_SUM
+ *   group g matches the doc     some clause of it does                              all SHOULD: >= max(1, group_min_should_match[g])
+ *                                                                                   of its clauses do; all MUST: all of them do
+ *   group score s_g             dismax(max_c score_c, sum_c (double)score_c)        (float) sum_c (double)score_c
+ *   the doc is a hit            group_occur 0: >= max(1, min_should_match) groups   some group matches
+ *                               match (more than n_groups: no hits, no error);
+ *                               group_occur 1: every group matches
+ *   score                       (float) sum_g (double)s_g                           dismax(max_g s_g, sum_g (double)s_g)
+ * Everything else of queries[i] means what it means in nrtgpu_search_function_score_batch: k, total_hits_threshold, has_after /
+ * after_* (searchAfter compares FINAL scores), filter_mask / must_not_mask / more_*, liveDocs, slicing, thread slices, deadlines.
+ * total_hits is always exact; total_hits_is_lower_bound follows the per-slice rule of the exhaustive route.
+ * Field boosts -- a BoostQuery around a per-field BooleanQuery, BlendedTermQuery's blended boosts -- are folded into the clauses'
+ * `weight` by the caller, and so are the blended document frequencies of cross_fields (the caller takes them from the rewritten
+ * query's TermStates: the library does not restate BlendedTermQuery.blend).
+ * Refusals, each with a reason in nrtgpu_last_error:
+ *   NRTGPU_ERR_INVALID_ARG  shape, n_groups, a group index or group_occur out of range; an empty group; a tie breaker outside 0..1
+ *                           or not finite; a negative group minimum; group_of_term == NULL; queries[i].disjunction_max != 0 or
+ *                           queries[i].tie_breaker != 0 (the structure lives in the groups); SUM_OF_MAX with any occur != 0;
+ *                           MAX_OF_SUM with queries[i].min_should_match != 0 or group_occur != 0; whatever nrtgpu_search_bm25_batch
+ *                           refuses of queries[i] with that status
+ *   NRTGPU_ERR_UNSUPPORTED  a MAX_OF_SUM group that mixes MUST and SHOULD clauses; min_competitive_score != 0; a batch whose
+ *                           queries do not all pass the fixed-point analysis, or NRTGPU_FLAG_NO_FIXED_POINT; a context with
+ *                           NRTGPU_FLAG_PACKED_POSTINGS; a mask that is not resident; more than 4 scored fields or more than
+ *                           NRTGPU_MAX_TERMS clauses
+ * Accounting: as a function-score call (items_scan; scan_launches, scan_items, scan_postings, scan_ms, fixed_point_launches).
+ * Out of scope: pruning (Lucene runs WAND here and reports a lower bound); MUST next to SHOULD inside a group; phrase-prefix,
+ * fuzzy and synonym clauses; deeper nesting; a function score over these shapes; the coalesced, device-resident, hybrid and
+ * nrtgpu_dist_* forms; packed postings; the Java shim, which does not bind this yet.
+ * --------------------------------------------------------------------------------------------- */
+#define NRTGPU_MAX_GROUPS 8
+#define NRTGPU_GROUPS_SUM_OF_MAX 0   /* BooleanQuery over DisjunctionMaxQuery groups: cross_fields */
+#define NRTGPU_GROUPS_MAX_OF_SUM 1   /* DisjunctionMaxQuery over BooleanQuery groups: best_fields */
+typedef struct {
+  int32_t shape;
+  int32_t n_groups;                      /* 1..NRTGPU_MAX_GROUPS; every group holds >= 1 clause */
+  const int32_t* group_of_term;          /* queries[i].n_terms entries, 0..n_groups-1 */
+  const int32_t* group_min_should_match; /* MAX_OF_SUM: n_groups entries, or NULL = all 0.  SUM_OF_MAX: not read */
+  float   tie_breaker;                   /* of the DisjunctionMax level, 0..1 */
+  int32_t group_occur;                   /* SUM_OF_MAX: 0 the groups are SHOULD clauses, 1 MUST.  MAX_OF_SUM: 0 */
+} nrtgpu_clause_groups;                  /* 32 bytes */
+/* n_queries multi-match searches over the same leaves in one device pass; groups[i] structures the clauses of queries[i] */
+int  nrtgpu_search_multi_match_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                     const nrtgpu_bm25_query* queries, const nrtgpu_clause_groups* groups, int32_t n_queries,
+                                     nrtgpu_topdocs* out);
+/* The eligibility test alone, as nrtgpu_query_supported: NRTGPU_OK if the search above would run (q, g) over these leaves, else
+ * the status it would return with the reason in nrtgpu_last_error.  No device work. */
+int  nrtgpu_multi_match_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query* q,
+                                  const nrtgpu_clause_groups* g);
+/* The arithmetic above for one doc, exposed for the tests: needs no device; it calls the very functions the kernel compiles.
+ * occur: n_terms entries of nrtgpu_term.occur, or NULL = all SHOULD; min_should_match: queries[i].min_should_match;
+ * clause_scores: n_terms float scores; matched: bit t set = clause t matches the doc.  Validates g (the refusals above).
+ * A doc that is no hit scores 0 when no group matches it, else what the groups that do match give. */
+int  nrtgpu_multi_match_value(const nrtgpu_clause_groups* g, int32_t n_terms, const int32_t* occur, int32_t min_should_match,
+                              const float* clause_scores, uint32_t matched, float* out_score, int32_t* out_is_hit);
+
+/* ---------------------------------------------------------------------------------------------
  * Host-side restatements the Java shim would otherwise take from Lucene objects
  * (BM25Similarity.scorer(boost, collectionStats, termStats); SmallFloat; slices()).
  * --------------------------------------------------------------------------------------------- */

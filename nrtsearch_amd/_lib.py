@@ -31,6 +31,9 @@ NRTGPU_FLAG_NO_VECTOR_SKETCH = 128
 NRTGPU_FLAG_PROFILE = 7 << 8   # include/nrtgpu_dev.h: the development library only
 NRTGPU_MAX_MASKS = 8
 NRTGPU_MAX_FUNCTIONS = 8
+NRTGPU_MAX_GROUPS = 8
+NRTGPU_GROUPS_SUM_OF_MAX = 0
+NRTGPU_GROUPS_MAX_OF_SUM = 1
 
 # every symbol include/nrtgpu.h declares (tests/test_abi.py checks the header against this list)
 ABI_SYMBOLS = [
@@ -51,6 +54,7 @@ ABI_SYMBOLS = [
     "nrtgpu_segment_add_byte_vectors", "nrtgpu_knn_exact_bytes", "nrtgpu_knn_search_bytes", "nrtgpu_byte_vector_score",
     "nrtgpu_rescore_byte_vectors", "nrtgpu_search_hybrid_bytes_batch", "nrtgpu_set_knn_gather",
     "nrtgpu_search_function_score_batch", "nrtgpu_function_score_supported", "nrtgpu_function_score_value",
+    "nrtgpu_search_multi_match_batch", "nrtgpu_multi_match_supported", "nrtgpu_multi_match_value",
 ]
 # what include/nrtgpu_dev.h adds: test hooks and measurement helpers of the development library (libnrtgpu_dev.so) only
 DEV_SYMBOLS = [
@@ -91,6 +95,11 @@ class ScoreFunction(C.Structure):   # nrtgpu_score_function
 class FunctionScore(C.Structure):   # nrtgpu_function_score
     _fields_ = [("n_functions", C.c_int32), ("functions", C.POINTER(ScoreFunction)), ("score_mode", C.c_int32),
                 ("boost_mode", C.c_int32), ("min_score", C.c_float), ("min_excluded", C.c_int32)]
+
+
+class ClauseGroups(C.Structure):   # nrtgpu_clause_groups
+    _fields_ = [("shape", C.c_int32), ("n_groups", C.c_int32), ("group_of_term", C.POINTER(C.c_int32)),
+                ("group_min_should_match", C.POINTER(C.c_int32)), ("tie_breaker", C.c_float), ("group_occur", C.c_int32)]
 
 
 class TopDocs(C.Structure):
@@ -190,6 +199,9 @@ def _open(path: str) -> C.CDLL:
     L.nrtgpu_search_function_score_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(FunctionScore), i32, C.POINTER(TopDocs)]
     L.nrtgpu_function_score_supported.argtypes = [vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(FunctionScore)]
     L.nrtgpu_function_score_value.argtypes = [C.POINTER(FunctionScore), C.c_uint32, f32, vp, vp]
+    L.nrtgpu_search_multi_match_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(ClauseGroups), i32, C.POINTER(TopDocs)]
+    L.nrtgpu_multi_match_supported.argtypes = [vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(ClauseGroups)]
+    L.nrtgpu_multi_match_value.argtypes = [C.POINTER(ClauseGroups), i32, vp, i32, vp, C.c_uint32, vp, vp]
     L.nrtgpu_rescore_vectors.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, f32, vp, vp, i32, C.c_double, C.c_double, i32,
                                          C.POINTER(TopDocs)]
     L.nrtgpu_search_hybrid_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), i32, i32, i32, vp, i32, f32,

@@ -110,6 +110,27 @@ SCORE_MODES = {"multiply": 0, "sum": 1}                  # nrtgpu_function_score
 BOOST_MODES = {"multiply": 0, "sum": 1, "replace": 2}    # ... .boost_mode
 
 
+@dataclasses.dataclass(frozen=True)
+class MultiMatchQuery:
+    """The two-level queries of the reference's multiMatchQuery (S/query/QueryNodeMapper.java:429-528) over term clauses:
+    shape "cross_fields": a BooleanQuery with one clause per group (a token), each group the DisjunctionMaxQuery of the token's
+    per-field term queries (MatchCrossFieldsQuery / BlendedTermQuery); operator "should" with minimum_number_should_match, or "must".
+    shape "best_fields": a DisjunctionMaxQuery with one disjunct per group (a field), each group a BooleanQuery of the field's term
+    clauses; operator "should" with a minimum per group (an int for all groups, or a tuple), or "must".
+    tie_breaker_multiplier belongs to the DisjunctionMax level.  Field boosts ride in BoostQuery clauses."""
+
+    shape: str
+    groups: Tuple[Tuple[Union[TermQuery, BoostQuery], ...], ...]
+    operator: str = "should"
+    minimum_number_should_match: Union[int, Tuple[int, ...]] = 0
+    tie_breaker_multiplier: float = 0.0
+    filter: Tuple[MaskFilter, ...] = ()
+    must_not: Tuple[MaskFilter, ...] = ()
+
+
+GROUP_SHAPES = {"cross_fields": _lib.NRTGPU_GROUPS_SUM_OF_MAX, "best_fields": _lib.NRTGPU_GROUPS_MAX_OF_SUM}   # nrtgpu_clause_groups.shape
+
+
 class UnsupportedQuery(Exception):
     """The rewritten query is not eligible for the device route: run the CPU (Lucene) path."""
 
@@ -700,6 +721,78 @@ class GpuIndexSearcher:
         m = self._marshal([query.inner], [manager])
         fs = self._marshal_function_scores([query], m)
         rc = _lib.load().nrtgpu_function_score_supported(self.ctx._h, self._segs, len(self.leaves), m.queries, fs)
+        if rc == _lib.NRTGPU_OK:
+            return True
+        if rc == _lib.NRTGPU_ERR_UNSUPPORTED:
+            return False
+        _lib.check(rc)
+        return False
+
+    def _marshal_multi_match(self, queries: Sequence[MultiMatchQuery], managers: Sequence[TopScoreDocCollectorManager]):
+        """(nrtgpu_bm25_query array holder, nrtgpu_clause_groups array): the clauses of all groups in group order."""
+        flat = []
+        for query in queries:
+            if query.shape not in GROUP_SHAPES or query.operator not in ("should", "must"):
+                raise UnsupportedQuery(f"shape {query.shape!r} / operator {query.operator!r}")
+            if not query.groups or any(len(g) == 0 for g in query.groups):
+                raise UnsupportedQuery("a multi-match query without groups, or with an empty group")
+            if len(query.groups) > _lib.NRTGPU_MAX_GROUPS:
+                raise UnsupportedQuery(f"more than {_lib.NRTGPU_MAX_GROUPS} groups")
+            # (minimumNumberShouldMatch = 1 only lets _flatten take the FILTER clauses; the real minima are set below)
+            flat.append(BooleanQuery(tuple(c for g in query.groups for c in g), 1, query.filter, query.must_not))
+        m = self._marshal(flat, managers)
+        gs = (_lib.ClauseGroups * len(queries))()
+        for qi, query in enumerate(queries):
+            best = query.shape == "best_fields"
+            must = query.operator == "must"
+            msm = query.minimum_number_should_match
+            of = (C.c_int32 * m.queries[qi].n_terms)(*[gi for gi, g in enumerate(query.groups) for _ in g])
+            m.keep.append(of)
+            gs[qi].shape = GROUP_SHAPES[query.shape]
+            gs[qi].n_groups = len(query.groups)
+            gs[qi].group_of_term = of
+            gs[qi].tie_breaker = float(np.float32(query.tie_breaker_multiplier))
+            gs[qi].group_occur = int(must and not best)
+            m.queries[qi].min_should_match = 0
+            if best:
+                for t in range(m.queries[qi].n_terms):
+                    m.queries[qi].terms[t].occur = int(must)
+                if not must:
+                    per = tuple(msm) if isinstance(msm, (tuple, list)) else (int(msm),) * len(query.groups)
+                    if len(per) != len(query.groups):
+                        raise UnsupportedQuery("minimum_number_should_match: one entry per group")
+                    mins = (C.c_int32 * len(per))(*[int(x) for x in per])
+                    m.keep.append(mins)
+                    gs[qi].group_min_should_match = mins
+            elif not must:
+                if isinstance(msm, (tuple, list)):
+                    raise UnsupportedQuery("cross_fields takes one minimum_number_should_match")
+                m.queries[qi].min_should_match = int(msm)
+        m.keep.append(gs)
+        return m, gs
+
+    def search_multi_match_batch(self, queries: Sequence[MultiMatchQuery], managers: Sequence[TopScoreDocCollectorManager]) -> List[TopDocs]:
+        """Multi-match searches (nrtgpu_search_multi_match_batch): every live doc that is a hit is scored, total_hits is exact."""
+        n = len(queries)
+        m, gs = self._marshal_multi_match(queries, managers)
+        outs = (_lib.TopDocs * n)()
+        bufs = []
+        for qi, mgr in enumerate(managers):
+            cap = max(int(mgr.num_hits), 1)
+            d = np.zeros(cap, dtype=np.int32)
+            s = np.zeros(cap, dtype=np.float32)
+            bufs.append((d, s))
+            outs[qi].capacity = cap
+            outs[qi].docs = d.ctypes.data_as(C.POINTER(C.c_int32))
+            outs[qi].scores = s.ctypes.data_as(C.POINTER(C.c_float))
+        _lib.check(_lib.load().nrtgpu_search_multi_match_batch(self.ctx._h, self._segs, self._bases, len(self.leaves), m.queries, gs, n, outs))
+        return [TopDocs(bufs[qi][0][: outs[qi].n_hits].copy(), bufs[qi][1][: outs[qi].n_hits].copy(), int(outs[qi].total_hits),
+                        bool(outs[qi].total_hits_is_lower_bound)) for qi in range(n)]
+
+    def multi_match_supported(self, query: MultiMatchQuery, manager: TopScoreDocCollectorManager) -> bool:
+        """The eligibility predicate alone (nrtgpu_multi_match_supported)."""
+        m, gs = self._marshal_multi_match([query], [manager])
+        rc = _lib.load().nrtgpu_multi_match_supported(self.ctx._h, self._segs, len(self.leaves), m.queries, gs)
         if rc == _lib.NRTGPU_OK:
             return True
         if rc == _lib.NRTGPU_ERR_UNSUPPORTED:

@@ -518,6 +518,72 @@ __host__ __device__ inline float function_score_value(const DFuncQuery& f, uint3
   return final_score;
 }
 
+// Multi-match queries (multimatch.hip: bm25_multi_match_kernel; multimatch.cpp): two-level queries over term clauses -- a
+// BooleanQuery over DisjunctionMaxQuery groups (cross_fields) or a DisjunctionMaxQuery over BooleanQuery groups (best_fields).
+// The plan is the exhaustive route's over the clauses as one SHOULD disjunction; beside it one DGroupQuery per query, and every
+// clause's group in its DQTerm.tab_slot (copied verbatim to the DTerms: bits no scorer reads).
+constexpr int kMaxGroups = 8;
+constexpr uint32_t kTabSlotGroupShift = 24, kTabSlotGroupMask = 31u;   // DTerm.tab_slot bits 24-28: the clause's group (this route only)
+constexpr uint32_t kGroupsSumOfMax = 0, kGroupsMaxOfSum = 1;           // DGroupQuery.shape (nrtgpu.h: NRTGPU_GROUPS_*)
+// The kernel's workgroup: per wave a sub-tile's u64 sums (8 KiB) AND u32 maxima (4 KiB) -- 12 waves of that leave no room for
+// the candidate buffer in 160 KiB, so 8 waves (two per SIMD: 256 VGPRs each, which hold the docs' outer state).
+constexpr int kMmWaves = 8;
+constexpr int kMmThreads = kMmWaves * 64;
+constexpr int kMmCandCap = 2048;    // == kMaxK + kTileDocs: the k kept + one wave's whole sub-tile always fit; <= 4 x kMmThreads (topk.hiph)
+static_assert(kMmCandCap >= kMaxK + kTileDocs && kMmCandCap <= 4 * kMmThreads, "multi-match candidate buffer");
+struct alignas(16) DGroupQuery {
+  uint32_t shape;                   // kGroups*
+  uint32_t n_groups;                // 1..kMaxGroups
+  float    tie_breaker;             // of the DisjunctionMax level
+  uint32_t group_occur;             // kGroupsSumOfMax: 0 the groups are SHOULD clauses, 1 MUST
+  uint32_t min_should_match;        // kGroupsSumOfMax, SHOULD groups: the query's minimumNumberShouldMatch
+  uint32_t pad[3];
+  uint8_t  occur[kMaxGroups];       // kGroupsMaxOfSum: 1 = the group's clauses are MUST
+  uint8_t  min_match[kMaxGroups];   // kGroupsMaxOfSum, SHOULD group: its minimumNumberShouldMatch (saturated at 255: more than any group holds)
+  uint8_t  n_clauses[kMaxGroups];   // the group's clauses in the QUERY (also those whose term no leaf holds)
+  uint8_t  pad2[kMaxGroups];
+};
+static_assert(sizeof(DGroupQuery) == 64, "DGroupQuery layout");
+
+// DisjunctionMaxScorer's score from the best sub-score and the double sum of ALL sub-scores: (float)(scoreMax + otherScoreSum *
+// tieBreaker) with otherScoreSum = sum - max.  The statement the flat DisjunctionMax route makes on its fixed-point pair
+// (maxscore.hip: kMsSecTieBreaker); here both levels of a multi-match query call it.
+__host__ __device__ inline float disjunction_max_value(float best, double sum, float tie_breaker) {
+  return (float)((double)best + (sum - (double)best) * (double)tie_breaker);
+}
+// What a doc has collected over the groups handled so far: folded group by group, in group order.
+struct MmOuter {
+  double sum;      // of the matching groups' scores
+  float  best;     // the largest of them
+  uint32_t n;      // matching groups
+};
+// The score of group g for a doc from the group's double sum, best clause score and number of matching clauses (> 0), and
+// whether the group matches the doc at all.  Every operation is one IEEE operation rounded once.
+__host__ __device__ inline bool multi_match_group(const DGroupQuery& r, uint32_t g, double sum, float best, uint32_t count, float* score) {
+  if (r.shape == kGroupsSumOfMax) {
+    *score = disjunction_max_value(best, sum, r.tie_breaker);
+    return count != 0u;
+  }
+  const uint32_t need = r.occur[g] != 0 ? (uint32_t)r.n_clauses[g] : (r.min_match[g] > 1 ? (uint32_t)r.min_match[g] : 1u);
+  *score = (float)sum;
+  return count >= need;
+}
+__host__ __device__ inline void multi_match_fold(MmOuter& o, float group_score) {
+  o.sum += (double)group_score;
+  o.best = group_score > o.best ? group_score : o.best;
+  o.n += 1u;
+}
+// The doc's final score from its outer state, and whether it is a hit.  The ONE statement of it: bm25_multi_match_kernel and
+// nrtgpu_multi_match_value both call these three functions.
+__host__ __device__ inline float multi_match_value(const DGroupQuery& r, const MmOuter& o, bool* is_hit) {
+  if (r.shape == kGroupsSumOfMax) {
+    *is_hit = r.group_occur != 0 ? o.n == r.n_groups : o.n >= (r.min_should_match > 1u ? r.min_should_match : 1u);
+    return (float)o.sum;
+  }
+  *is_hit = o.n != 0u;
+  return disjunction_max_value(o.best, o.sum, r.tie_breaker);
+}
+
 __host__ __device__ inline uint64_t pack_key(float score, uint32_t global_doc) {
   union { float f; uint32_t u; } c;
   c.f = score;

@@ -2,7 +2,7 @@
 //
 // The runtime is split by concern: runtime.cpp (errors, context, workspaces, statistics, exchange table, host
 // helpers), segment.cpp (the segment store: upload, seal, liveDocs, masks), planner.cpp (queries -> launch
-// plan), search.cpp (BM25 entry points, hybrid tail, request coalescing, merge), funcscore.cpp (function-score queries), vectors.cpp (exact kNN,
+// plan), search.cpp (BM25 entry points, hybrid tail, request coalescing, merge), funcscore.cpp (function-score queries), multimatch.cpp (multi-match queries), vectors.cpp (exact kNN,
 // vector rescoring).  Types the ABI names opaquely (nrtgpu_ctx, nrtgpu_seg) live in the global namespace;
 // everything else in nrtgpu::rt.
 #pragma once
@@ -51,6 +51,10 @@ void launch_bm25_function_score(hipStream_t stream, uint32_t n_items, const DIte
                                 const DQuery* queries, const float* caches, const DFuncQuery* fqueries, const DFuncMasks* fmasks,
                                 unsigned long long* theta_g, uint32_t* slice_sum, uint64_t* item_keys, uint32_t* item_counts,
                                 uint64_t* item_hits, uint32_t k_stride);
+// multi-match queries (multimatch.hip): the same, with one DGroupQuery per query and a clause's group in DTerm.tab_slot bits 24-28
+void launch_bm25_multi_match(hipStream_t stream, uint32_t n_items, const DItem* items, const DPart* parts, const DTerm* terms,
+                             const DQuery* queries, const float* caches, const DGroupQuery* gqueries, unsigned long long* theta_g,
+                             uint32_t* slice_sum, uint64_t* item_keys, uint32_t* item_counts, uint64_t* item_hits, uint32_t k_stride);
 #ifdef NRTGPU_DEV
 void launch_debug_wave_kth(hipStream_t stream, const uint64_t* keys, uint32_t n, uint32_t r, uint64_t* out);   // (maxscore.hip: topk_kth_wave on its own)
 void launch_debug_walk_value(hipStream_t stream, float weight, const uint32_t* freq, const uint32_t* norm, const float* table, int fx_scale,
