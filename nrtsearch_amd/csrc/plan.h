@@ -466,6 +466,23 @@ __host__ __device__ inline float knn_byte_score(int sim, int32_t dim, int32_t do
   return x < 0.0f ? 1.0f / (1.0f + -1.0f * x) : x + 1.0f;
 }
 
+// What a launch of either final-score kernel (finalscore.hiph; finalscore.cpp) works on besides its route's own records: the
+// exhaustive scan's plan records and item outputs.
+struct FinalScoreArgs {
+  uint32_t n_items;              // workgroups
+  const DItem* items;
+  const DPart* parts;
+  const DTerm* terms;
+  const DQuery* queries;
+  const float* caches;           // the queries' normInverse tables
+  unsigned long long* theta_g;   // per query: the best FINAL key bound any of its items has published
+  uint32_t* slice_sum;           // per (query, searcher slice): hits counted
+  uint64_t* item_keys;           // per item k_stride keys ...
+  uint32_t* item_counts;         // ... how many ...
+  uint64_t* item_hits;           // ... and the hits counted there
+  uint32_t k_stride;
+};
+
 // Function-score queries (funcscore.hip: bm25_function_score_kernel; funcscore.cpp): MultiFunctionScoreQuery over a BM25
 // disjunction with weight functions only -- per doc a boost from the function sets it lies in.  One record per query of the call,
 // and per part of the plan (same index as DPart) the resident doc set of every function on the part's leaf.

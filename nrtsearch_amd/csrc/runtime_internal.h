@@ -2,8 +2,9 @@
 //
 // The runtime is split by concern: runtime.cpp (errors, context, workspaces, statistics, exchange table, host
 // helpers), segment.cpp (the segment store: upload, seal, liveDocs, masks), planner.cpp (queries -> launch
-// plan), search.cpp (BM25 entry points, hybrid tail, request coalescing, merge), funcscore.cpp (function-score queries), multimatch.cpp (multi-match queries), vectors.cpp (exact kNN,
-// vector rescoring).  Types the ABI names opaquely (nrtgpu_ctx, nrtgpu_seg) live in the global namespace;
+// plan), search.cpp (BM25 entry points, hybrid tail, request coalescing, merge), finalscore.cpp (the host
+// path of the final-score routes), funcscore.cpp (function-score queries), multimatch.cpp (multi-match queries),
+// vectors.cpp (exact kNN, vector rescoring).  Types the ABI names opaquely (nrtgpu_ctx, nrtgpu_seg) live in the global namespace;
 // everything else in nrtgpu::rt.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -46,15 +47,11 @@ void launch_bm25_scan(hipStream_t stream, bool fixed_point, bool pipelined, bool
                       unsigned long long* quant_g, const DExchange* xch, uint32_t* slice_sum, uint64_t* item_keys, uint32_t* item_counts,
                       uint64_t* item_hits, uint32_t k_stride, uint64_t* item_prof);
 void launch_bm25_maxscore(hipStream_t stream, bool profile, bool packed, int shapes, const MsArgs& args, const MsArgs* args_d);
-// function-score queries (funcscore.hip): one workgroup per item over the scan's plan records, the scan's item outputs
-void launch_bm25_function_score(hipStream_t stream, uint32_t n_items, const DItem* items, const DPart* parts, const DTerm* terms,
-                                const DQuery* queries, const float* caches, const DFuncQuery* fqueries, const DFuncMasks* fmasks,
-                                unsigned long long* theta_g, uint32_t* slice_sum, uint64_t* item_keys, uint32_t* item_counts,
-                                uint64_t* item_hits, uint32_t k_stride);
-// multi-match queries (multimatch.hip): the same, with one DGroupQuery per query and a clause's group in DTerm.tab_slot bits 24-28
-void launch_bm25_multi_match(hipStream_t stream, uint32_t n_items, const DItem* items, const DPart* parts, const DTerm* terms,
-                             const DQuery* queries, const float* caches, const DGroupQuery* gqueries, unsigned long long* theta_g,
-                             uint32_t* slice_sum, uint64_t* item_keys, uint32_t* item_counts, uint64_t* item_hits, uint32_t k_stride);
+// the final-score kernels (finalscore.hiph): one workgroup per item over the scan's plan records, the scan's item outputs
+// function-score queries (funcscore.hip): one DFuncQuery per query, one DFuncMasks per part
+void launch_bm25_function_score(hipStream_t stream, const FinalScoreArgs& a, const DFuncQuery* fqueries, const DFuncMasks* fmasks);
+// multi-match queries (multimatch.hip): one DGroupQuery per query, a clause's group in DTerm.tab_slot bits 24-28
+void launch_bm25_multi_match(hipStream_t stream, const FinalScoreArgs& a, const DGroupQuery* gqueries);
 #ifdef NRTGPU_DEV
 void launch_debug_wave_kth(hipStream_t stream, const uint64_t* keys, uint32_t n, uint32_t r, uint64_t* out);   // (maxscore.hip: topk_kth_wave on its own)
 void launch_debug_walk_value(hipStream_t stream, float weight, const uint32_t* freq, const uint32_t* norm, const float* table, int fx_scale,
@@ -893,6 +890,28 @@ bool fixed_scale_of_term(float weight, const float* cache256, uint32_t max_norm,
 // than numHits hits, and then the relation needs the exact count)
 int build_plan(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
                const nrtgpu_bm25_query* queries, int32_t n_queries, HostPlan& hp, int prune = 0);
+
+// ---- the final-score routes (finalscore.cpp): what funcscore.cpp and multimatch.cpp share --------------------------------
+// The head of an entry point: the argument checks (null_argument: one of the route's own pointers is NULL; n_queries: the
+// batch entries', nullptr for the _supported predicates), the batch entries' first deadline check, hipSetDevice.
+int final_score_enter(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, bool null_argument, const int32_t* n_queries);
+// the context's flags neither route runs under; route: "function-score" / "multi-match", for the message
+int final_score_check_flags(const nrtgpu_ctx* ctx, const char* route);
+// the exhaustive plan (build_plan, prune = 0: nothing may be skipped), refused unless it is a fixed-point one
+int final_score_plan(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, const nrtgpu_bm25_query* queries,
+                     int32_t n_queries, const char* route, HostPlan& hp);
+struct PlanBytes {   // an array of the route's own, appended to the plan buffer
+  const void* p;
+  size_t bytes;
+};
+const int kFinalScoreExtras = 2;   // at most: one per-query record array, one per-part array
+// the route's scorer: d_extra[i] = the device address of extras[i]
+typedef void (*FinalScoreLaunch)(hipStream_t, const FinalScoreArgs&, const void* const* d_extra);
+// From "the plan and the route's records exist" to "out[], the diagnostics and the statistics are filled": workspace, plan upload,
+// expansion, the scorer in its turn on the device, merge, per-slice relation, the wait, unpacking.  queries: the CALLER's (k,
+// capacity); t0: now_ms() when planning began.  The caller holds its SegReadLocks until this returns.
+int final_score_run(nrtgpu_ctx* ctx, const HostPlan& hp, const nrtgpu_bm25_query* queries, int32_t n_queries, nrtgpu_topdocs* out, double t0,
+                    const PlanBytes* extras, int n_extras, FinalScoreLaunch launch);
 
 }  // namespace rt
 }  // namespace nrtgpu
