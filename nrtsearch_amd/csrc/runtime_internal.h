@@ -891,6 +891,70 @@ bool fixed_scale_of_term(float weight, const float* cache256, uint32_t max_norm,
 int build_plan(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
                const nrtgpu_bm25_query* queries, int32_t n_queries, HostPlan& hp, int prune = 0);
 
+// ---- the text routes' plan blob and workspace (search.cpp: enqueue_search; finalscore.cpp: enqueue_final_score) -----------------
+// One layout for every route: the twelve plan arrays of a HostPlan in upload order, and the seven workspace regions every route
+// has (per-slot outputs of the scorers, the merge's outputs, the expanded DTerm records).  A route appends what is its own with
+// plan.take() / work.take() behind them.  n_slots: output slots of the scorers (the items, and whatever the route puts behind them).
+struct PlanLayout {
+  Carver plan, work;
+  size_t queries, items, parts, qterms, qexpand, qs_begin, caches, list_idx, q_base, q_nlists, q_k, theta;
+  size_t item_keys, item_counts, item_hits, out_keys, out_counts, out_hits, terms;
+  PlanLayout(const HostPlan& hp, size_t n_slots, size_t n_queries, uint32_t k_stride_out) {
+    queries = plan.take(hp.queries.size() * sizeof(DQuery));
+    items = plan.take(hp.items.size() * sizeof(DItem));
+    parts = plan.take(hp.parts.size() * sizeof(DPart));
+    qterms = plan.take(hp.qterms.size() * sizeof(DQTerm));
+    qexpand = plan.take(sizeof(DExpandHead) + hp.qexpand.size() * sizeof(DQExpand)) + sizeof(DExpandHead);   // (the head in front: put_expand_head)
+    qs_begin = plan.take(hp.qs_begin.size() * 4);
+    caches = plan.take(hp.caches.size() * sizeof(float));
+    list_idx = plan.take(hp.list_idx.size() * 4);
+    q_base = plan.take(hp.q_base.size() * 4);
+    q_nlists = plan.take(hp.q_nlists.size() * 4);
+    q_k = plan.take(hp.q_k.size() * 4);
+    theta = plan.take(hp.theta_init.size() * 8);   // uploaded with the plan, then updated by the kernel
+    item_keys = work.take(n_slots * (size_t)hp.k_stride * 8);
+    item_counts = work.take(n_slots * 4);
+    item_hits = work.take(n_slots * 8);
+    out_keys = work.take(n_queries * k_stride_out * 8);
+    out_counts = work.take(n_queries * 4);
+    out_hits = work.take(n_queries * 8);
+    terms = work.take((size_t)hp.n_dterms * sizeof(DTerm));   // written by expand_terms_kernel
+  }
+  static void put(char* hb, size_t off, const void* src, size_t bytes) {
+    if (bytes) memcpy(hb + off, src, bytes);
+  }
+  void fill(char* hb, const HostPlan& hp) const {   // the twelve arrays into the host blob
+    put(hb, queries, hp.queries.data(), hp.queries.size() * sizeof(DQuery));
+    put(hb, items, hp.items.data(), hp.items.size() * sizeof(DItem));
+    put(hb, parts, hp.parts.data(), hp.parts.size() * sizeof(DPart));
+    put(hb, qterms, hp.qterms.data(), hp.qterms.size() * sizeof(DQTerm));
+    put(hb, qexpand, hp.qexpand.data(), hp.qexpand.size() * sizeof(DQExpand));
+    put(hb, qs_begin, hp.qs_begin.data(), hp.qs_begin.size() * 4);
+    put(hb, caches, hp.caches.data(), hp.caches.size() * sizeof(float));
+    put(hb, list_idx, hp.list_idx.data(), hp.list_idx.size() * 4);
+    put(hb, q_base, hp.q_base.data(), hp.q_base.size() * 4);
+    put(hb, q_nlists, hp.q_nlists.data(), hp.q_nlists.size() * 4);
+    put(hb, q_k, hp.q_k.data(), hp.q_k.size() * 4);
+    put(hb, theta, hp.theta_init.data(), hp.theta_init.size() * 8);
+  }
+  // what the plan expansion reads in front of the DQExpand array (plan.h: DExpandHead); rows: where it writes the MaxScore
+  // route's walk rows, nullptr: none
+  void put_expand_head(char* hb, const char* db, DWalkRow* rows) const {
+    DExpandHead xh{};
+    xh.caches = (const float*)(db + caches);
+    xh.queries = (const DQuery*)(db + queries);
+    xh.rows = rows;
+    memcpy(hb + qexpand - sizeof(DExpandHead), &xh, sizeof(xh));
+  }
+};
+// what every batch entry says of its sizes
+int check_batch_size(const nrtgpu_ctx* ctx, int32_t n_queries, int32_t n_segs);
+// `hits` as the device leaves it -> out (search.cpp): lower: the MaxScore route's certain bound (0: none); n_first: the length the
+// relation is judged by
+void unpack_topdocs(const uint64_t* keys, uint32_t n, uint64_t hits, const int32_t k, int64_t lower, uint32_t n_first, nrtgpu_topdocs* out);
+// a call's diagnostics and statistics (search.cpp); reads the slot's timing events the call recorded
+void account(nrtgpu_ctx* ctx, Slot* slot, const HostPlan& hp, int32_t n_queries, double plan_ms, double t_entry_ms = 0.0, double queue_ms = 0.0);
+
 // ---- the final-score routes (finalscore.cpp): what funcscore.cpp and multimatch.cpp share --------------------------------
 // The head of an entry point: the argument checks (null_argument: one of the route's own pointers is NULL; n_queries: the
 // batch entries', nullptr for the _supported predicates), the batch entries' first deadline check, hipSetDevice.

@@ -98,146 +98,86 @@ struct DeviceRun {
   size_t n_ms_items = 0;
 };
 
-// Enqueue plan upload + scan + merge on the slot's stream.  Merge output goes to (ext_keys,
-// ext_counts, ext_hits) when given (device-resident variant), else into the slot's scratch.
-// Everything is enqueued at once on the slot's stream and nothing waits on the host.  The kernels that want the whole
-// GPU (the two scorers) take turns ON THE DEVICE: under `gpu` (unlocked on entry and on return) the stream is made to
-// wait for the event recorded behind the previous batch's scorers, then this batch's are enqueued and their event
-// recorded behind their merge.  The plan upload and its expansion run ahead of that wait: they overlap the scorers of the
-// batch before instead of sitting between the two (before: lock -> launch -> host sync -> unlock, a host round trip plus
-// upload and expansion between any two scorer launches).
-static int enqueue_search(nrtgpu_ctx* ctx, Slot* slot, const HostPlan& hp, int32_t n_queries, uint32_t k_stride_out,
-                          uint64_t* ext_keys, uint32_t* ext_counts, uint64_t* ext_hits, DeviceRun* run,
-                          std::unique_lock<std::mutex>& gpu, int64_t epoch = -1, bool allow_spec = false, int32_t spec_world = 1,
-                          uint64_t* ext_guess = nullptr, bool follow_up = false) {
-  forget_foreign_hip_error();
-  // follow_up (round 6): the second pass of a speculative call -- the handful of queries whose guess failed the merge's check, run
-  // again (seeded: search_batch_spec).  As a launch of the usual kind it took a TURN of its own, and BEHIND whatever batch another
-  // thread had enqueued meanwhile: its caller waited a whole batch for five queries (sorted-by-length corpus at C3's size, two
-  // submitting threads: 2.6 ms per 1024-query step around a 1.05 ms kernel -- slower than with speculation off).  A follow-up takes
-  // no turn: its few persistent workgroups run on the CUs every big launch leaves alone, beside whatever batch is running.
-  // Only MaxScore items (the exhaustive scan launches a workgroup per item and wants the whole device).
-  static const bool follow_up_on = dev_env_int("NRTGPU_FOLLOW_UP", 1) != 0;   // (development build: 0 = a turn of its own, A/B)
-  const bool small = follow_up && follow_up_on && hp.n_ms_items != 0 && hp.n_ms_items == hp.items.size() && ms_persistent();
+// What a caller of enqueue_search may ask for besides the search itself.
+struct SearchOpts {
+  uint64_t* ext_keys = nullptr;   // the merge's output in the caller's device arrays (device-resident variant); nullptr: the slot's scratch
+  uint32_t* ext_counts = nullptr;
+  uint64_t* ext_hits = nullptr;
+  int64_t epoch = -1;             // >= 0: this batch's number in the context's open cross-GPU bound exchange
+  bool allow_spec = false;        // speculative thresholds: the caller can run a query again
   // spec_world > 1 (the library's multi-GPU search, dist.cpp): this call is ONE SHARD of a spec_world-way search over equal docid
   // ranges, and its speculative thresholds are guesses at the k-th score of the WHOLE search -- a shard's docs are a 1 / world
   // sample of the index, so the guess rule holds with the windows of all shards in its denominator.  Such a guess cannot be
   // checked against this shard's list: the largest one per query goes to ext_guess and the caller checks it against the list
   // merged over all shards (and runs a failed query again on every shard).
-  const size_t n_items = hp.items.size();
-  Carver pc;
-  const size_t o_queries = pc.take(hp.queries.size() * sizeof(DQuery));
-  const size_t o_items = pc.take(n_items * sizeof(DItem));
-  const size_t o_parts = pc.take(hp.parts.size() * sizeof(DPart));
-  const size_t o_qterms = pc.take(hp.qterms.size() * sizeof(DQTerm));
-  const size_t o_qexp = pc.take(sizeof(DExpandHead) + hp.qexpand.size() * sizeof(DQExpand)) + sizeof(DExpandHead);   // (the head in front: filled in below)
-  const size_t o_qsb = pc.take(hp.qs_begin.size() * 4);
-  const size_t o_caches = pc.take(hp.caches.size() * sizeof(float));
-  const size_t o_lidx = pc.take(hp.list_idx.size() * 4);
-  const size_t o_qbase = pc.take(hp.q_base.size() * 4);
-  const size_t o_qnl = pc.take(hp.q_nlists.size() * 4);
-  const size_t o_qk = pc.take(hp.q_k.size() * 4);
-  const size_t o_theta = pc.take(hp.theta_init.size() * 8);  // uploaded with the plan, then updated by the kernel
-  const size_t o_quant = pc.take(hp.list_idx.size() * 8);    // per item: published quantile bound (zeros)
-  const size_t o_lower = pc.take(ext_hits ? hp.q_lower.size() * 8 : 0);  // device-resident results: certain lower bounds
-  const bool use_xch = epoch >= 0 && ctx->xch_dev != nullptr;
-  const size_t o_xch = pc.take(use_xch ? sizeof(DExchange) : 0);
-  const size_t o_qwins = pc.take(hp.q_wins.size() * 4);
-  const size_t o_help = pc.take(sizeof(MsArgs));   // the MaxScore launch's record (plan.h); filled in below, once the workspace is carved
-  const size_t plan_bytes = pc.off;
-  if (int rc = slot->h_plan.reserve(plan_bytes)) return rc;
-  if (int rc = slot->d_plan.reserve(plan_bytes)) return rc;
-  char* hb = (char*)slot->h_plan.p;
-  memcpy(hb + o_queries, hp.queries.data(), hp.queries.size() * sizeof(DQuery));
-  if (n_items) memcpy(hb + o_items, hp.items.data(), n_items * sizeof(DItem));
-  if (!hp.parts.empty()) memcpy(hb + o_parts, hp.parts.data(), hp.parts.size() * sizeof(DPart));
-  if (!hp.qterms.empty()) memcpy(hb + o_qterms, hp.qterms.data(), hp.qterms.size() * sizeof(DQTerm));
-  memcpy(hb + o_qexp, hp.qexpand.data(), hp.qexpand.size() * sizeof(DQExpand));
-  if (!hp.qs_begin.empty()) memcpy(hb + o_qsb, hp.qs_begin.data(), hp.qs_begin.size() * 4);
-  memcpy(hb + o_caches, hp.caches.data(), hp.caches.size() * sizeof(float));
-  if (!hp.list_idx.empty()) memcpy(hb + o_lidx, hp.list_idx.data(), hp.list_idx.size() * 4);
-  memcpy(hb + o_qbase, hp.q_base.data(), hp.q_base.size() * 4);
-  memcpy(hb + o_qnl, hp.q_nlists.data(), hp.q_nlists.size() * 4);
-  memcpy(hb + o_qk, hp.q_k.data(), hp.q_k.size() * 4);
-  memcpy(hb + o_theta, hp.theta_init.data(), hp.theta_init.size() * 8);
-  if (!hp.q_wins.empty()) memcpy(hb + o_qwins, hp.q_wins.data(), hp.q_wins.size() * 4);
-  if (spec_world > 1) {   // the denominator of "how much of the query's docs have I seen": the windows of ALL shards
-    // (this shard's REAL share of the index where the caller has stated it -- nrtgpu_set_shard_share: virtual shards balance
-    //  live docs, not docid ranges, and a shard that holds 40 % of the index is no "one of two" -- else spec_world equal shards)
-    uint64_t num = (uint64_t)spec_world, den = 1;
-    const int64_t sd = ctx->shard_docs.load(std::memory_order_relaxed), id = ctx->index_docs.load(std::memory_order_relaxed);
-    if (sd > 0 && id >= sd) {
-      num = (uint64_t)id;
-      den = (uint64_t)sd;
-    }
-    uint32_t* qw = (uint32_t*)(hb + o_qwins);
-    for (size_t i = 0; i < hp.q_wins.size(); ++i) qw[i] = (uint32_t)std::min<uint64_t>(((uint64_t)qw[i] * num + den - 1) / den, 0xFFFFFFFFull);
-  }
-  memset(hb + o_quant, 0, hp.list_idx.size() * 8);
-  if (ext_hits) memcpy(hb + o_lower, hp.q_lower.data(), hp.q_lower.size() * 8);
-  if (use_xch) {
-    DExchange x{};
-    const size_t stride = (size_t)ctx->cfg.max_batch;
-    x.slot = ctx->xch_dev + (size_t)(epoch % kExchangeSlots) * (size_t)ctx->xch_world * stride;
-    x.world = (uint32_t)ctx->xch_world;
-    x.rank = (uint32_t)ctx->xch_rank;
-    x.stride = (uint32_t)stride;
-    x.tag = (uint32_t)(epoch + 1);  // never 0
-    if (x.tag == 0) x.tag = 1;
-    memcpy(hb + o_xch, &x, sizeof(x));
-  }
+  int32_t spec_world = 1;
+  uint64_t* ext_guess = nullptr;
+  bool follow_up = false;         // the second pass of a speculative call (enqueue_search: `small`)
+};
 
-  // MaxScore route: helper workgroups behind the items (plan.h: DHelp; maxscore.hip) -- each with an output slot of its own
-  // behind the items' slots.  NRTGPU_MS_HELPERS: how many (default 4 per CU; 0: none), NRTGPU_MS_HELP_MIN: an item with fewer
-  // unassigned windows is not joined.
+// MaxScore route: helper workgroups behind the items (plan.h: DHelp; maxscore.hip) -- each with an output slot of its own
+// behind the items' slots.  NRTGPU_MS_HELPERS: how many (default 4 per CU; 0: none).
+static size_t ms_helpers(const nrtgpu_ctx* ctx, const HostPlan& hp) {
   static const int env_helpers = (int)dev_env_int("NRTGPU_MS_HELPERS", -1);
-  static const int env_help_min = (int)dev_env_int("NRTGPU_MS_HELP_MIN", 16);
-  const size_t n_help = hp.n_ms_items == 0 ? 0 : (size_t)(env_helpers >= 0 ? env_helpers : 4 * std::max(ctx->n_cus, 1));
-  const size_t n_slots = n_items + n_help;
-  Carver wc;
-  const size_t o_ikeys = wc.take(n_slots * (size_t)hp.k_stride * 8);
-  const size_t o_icnt = wc.take(n_slots * 4);
-  const size_t o_ihits = wc.take(n_slots * 8);
-  const size_t o_okeys = wc.take((size_t)n_queries * k_stride_out * 8);
-  const size_t o_ocnt = wc.take((size_t)n_queries * 4);
-  const size_t o_ohits = wc.take((size_t)n_queries * 8);
-  const size_t o_terms = wc.take((size_t)hp.n_dterms * sizeof(DTerm));  // written by expand_terms_kernel
-  // ... and the MaxScore route's walk rows beside them (plan.h: DWalkRow; same index).  NRTGPU_MS_WALK_ROWS=0 (development build,
-  // read per call): none are written and the walk works a part's bounds out itself, as it did before the rows (A/B in one process)
-  const bool walk_rows = hp.n_ms_items != 0 && dev_env_int("NRTGPU_MS_WALK_ROWS", 1) != 0;
-  const size_t o_rows = wc.take(walk_rows ? (size_t)hp.n_dterms * sizeof(DWalkRow) : 0);
-  // per (query, searcher slice) the hits its items counted, per query "some item's slice has passed the floor": zeroed per call
-  const size_t o_ssum = wc.take((size_t)n_queries * hp.n_slices * 4), o_qprune = wc.take((size_t)n_queries * 4);
-  // the helpers' state (zeroed per call as well): per MaxScore item the window counter, the helpers that joined, the owner's
-  // start time; per query the head of its helper-slot list; the "nothing left to help" flag
-  const size_t o_hwin = wc.take(hp.n_ms_items * 4), o_hcnt = wc.take(hp.n_ms_items * 4), o_ht0 = wc.take(hp.n_ms_items * 8);
-  const size_t o_hhead = wc.take((size_t)n_queries * 4), o_hnext = wc.take(n_help * 4), o_hoff = wc.take(4);
-  const size_t o_hqueue = wc.take(4), o_hused = wc.take(4), o_hstart = wc.take(8);
-  // speculative thresholds (plan.h: kHitsSpecInvalid): only where the caller can run a query again (allow_spec: the batch and the
-  // hybrid entry), never next to the cross-GPU bound exchange (its quantile uses the selection's second rank)
-  const uint32_t spec_z16 = spec_margin16(ctx);
-  const bool spec = allow_spec && spec_z16 != 0u && hp.n_ms_items != 0 && !use_xch && hp.lsc && hp.lsc->spec_off.load(std::memory_order_relaxed) == 0;
-  const size_t o_spec = wc.take(spec ? (size_t)n_queries * 8 : 0);
-  const size_t zero_bytes = wc.off - o_ssum;
-  // kernel variant: clause counting (8), doc-set masks somewhere in the batch (9), else what the flags ask for
-  const int flag_variant = (ctx->cfg.flags >> 8) & 15;
-  const int ablation = hp.clause_counting ? 8 : ((hp.masked && flag_variant == 0 && !(ctx->cfg.flags & NRTGPU_FLAG_NO_MASK_VARIANT)) ? 9 : flag_variant);
-  const bool profile = flag_variant == 7;
-  const size_t o_prof = wc.take((ablation == 7 || profile) ? n_slots * 128 : 0);
-  const size_t o_walls = wc.take(profile ? n_slots * 64 : 0);
-  if (int rc = slot->d_work.reserve(wc.off)) return rc;
-  char* db = (char*)slot->d_plan.p;
-  char* wb = (char*)slot->d_work.p;
+  return hp.n_ms_items == 0 ? 0 : (size_t)(env_helpers >= 0 ? env_helpers : 4 * std::max(ctx->n_cus, 1));
+}
+
+// The common layout with this route's tails behind it, and what decides their sizes.
+struct SearchLayout : PlanLayout {
+  size_t n_items, n_help, n_slots;
+  bool use_xch, walk_rows, spec, profile;
+  uint32_t spec_z16;
+  int ablation;
+  size_t quant, lower, xch, q_wins, ms_args, plan_bytes;                                      // plan blob, behind theta
+  size_t rows, ssum, qprune, hwin, hcnt, ht0, hhead, hnext, hoff, hqueue, hused, hstart, spec_g;   // workspace, behind terms
+  size_t zero_bytes, prof, walls;
+  SearchLayout(const nrtgpu_ctx* ctx, const HostPlan& hp, int32_t n_queries, uint32_t k_stride_out, const SearchOpts& o, size_t n_help_)
+      : PlanLayout(hp, hp.items.size() + n_help_, (size_t)n_queries, k_stride_out), n_items(hp.items.size()), n_help(n_help_), n_slots(n_items + n_help_) {
+    quant = plan.take(hp.list_idx.size() * 8);    // per item: published quantile bound (zeros)
+    lower = plan.take(o.ext_hits ? hp.q_lower.size() * 8 : 0);  // device-resident results: certain lower bounds
+    use_xch = o.epoch >= 0 && ctx->xch_dev != nullptr;
+    xch = plan.take(use_xch ? sizeof(DExchange) : 0);
+    q_wins = plan.take(hp.q_wins.size() * 4);
+    ms_args = plan.take(sizeof(MsArgs));   // the MaxScore launch's record (plan.h); filled in once the workspace is carved
+    plan_bytes = plan.off;
+    // ... and the MaxScore route's walk rows beside the terms (plan.h: DWalkRow; same index).  NRTGPU_MS_WALK_ROWS=0 (development build,
+    // read per call): none are written and the walk works a part's bounds out itself, as it did before the rows (A/B in one process)
+    walk_rows = hp.n_ms_items != 0 && dev_env_int("NRTGPU_MS_WALK_ROWS", 1) != 0;
+    rows = work.take(walk_rows ? (size_t)hp.n_dterms * sizeof(DWalkRow) : 0);
+    // per (query, searcher slice) the hits its items counted, per query "some item's slice has passed the floor": zeroed per call
+    ssum = work.take((size_t)n_queries * hp.n_slices * 4), qprune = work.take((size_t)n_queries * 4);
+    // the helpers' state (zeroed per call as well): per MaxScore item the window counter, the helpers that joined, the owner's
+    // start time; per query the head of its helper-slot list; the "nothing left to help" flag
+    hwin = work.take(hp.n_ms_items * 4), hcnt = work.take(hp.n_ms_items * 4), ht0 = work.take(hp.n_ms_items * 8);
+    hhead = work.take((size_t)n_queries * 4), hnext = work.take(n_help * 4), hoff = work.take(4);
+    hqueue = work.take(4), hused = work.take(4), hstart = work.take(8);
+    // speculative thresholds (plan.h: kHitsSpecInvalid): only where the caller can run a query again (allow_spec: the batch and the
+    // hybrid entry), never next to the cross-GPU bound exchange (its quantile uses the selection's second rank)
+    spec_z16 = spec_margin16(ctx);
+    spec = o.allow_spec && spec_z16 != 0u && hp.n_ms_items != 0 && !use_xch && hp.lsc && hp.lsc->spec_off.load(std::memory_order_relaxed) == 0;
+    spec_g = work.take(spec ? (size_t)n_queries * 8 : 0);
+    zero_bytes = work.off - ssum;   // (the profile buffers behind are zeroed by the instrumented variant alone, in its turn)
+    // kernel variant: clause counting (8), doc-set masks somewhere in the batch (9), else what the flags ask for
+    const int flag_variant = (ctx->cfg.flags >> 8) & 15;
+    ablation = hp.clause_counting ? 8 : ((hp.masked && flag_variant == 0 && !(ctx->cfg.flags & NRTGPU_FLAG_NO_MASK_VARIANT)) ? 9 : flag_variant);
+    profile = flag_variant == 7;
+    prof = work.take((ablation == 7 || profile) ? n_slots * 128 : 0);
+    walls = work.take(profile ? n_slots * 64 : 0);
+  }
+};
+
+// Context + plan + the development build's knobs -> the MaxScore launch's record (plan.h: MsArgs, DHelp) over the carved buffers.
+static MsArgs ms_launch_record(const nrtgpu_ctx* ctx, const HostPlan& hp, const SearchLayout& L, const char* db, char* wb, bool small) {
   DHelp help{};
-  help.win_next = (uint32_t*)(wb + o_hwin);
-  help.help_cnt = (uint32_t*)(wb + o_hcnt);
-  help.item_t0 = (unsigned long long*)(wb + o_ht0);
-  help.help_head = (uint32_t*)(wb + o_hhead);
-  help.help_query = (uint32_t*)(wb + o_hnext);
-  help.help_off = (uint32_t*)(wb + o_hoff);
-  help.item_next = (uint32_t*)(wb + o_hqueue);
-  help.help_used = (uint32_t*)(wb + o_hused);
-  help.t_start = (unsigned long long*)(wb + o_hstart);
+  help.win_next = (uint32_t*)(wb + L.hwin);
+  help.help_cnt = (uint32_t*)(wb + L.hcnt);
+  help.item_t0 = (unsigned long long*)(wb + L.ht0);
+  help.help_head = (uint32_t*)(wb + L.hhead);
+  help.help_query = (uint32_t*)(wb + L.hnext);
+  help.help_off = (uint32_t*)(wb + L.hoff);
+  help.item_next = (uint32_t*)(wb + L.hqueue);
+  help.help_used = (uint32_t*)(wb + L.hused);
+  help.t_start = (unsigned long long*)(wb + L.hstart);
   {
     // NRTGPU_MS_HELP_ALPHA (x 16; 0: helpers only once the queue is empty): while items are queued a workgroup helps an item
     // whose expected time left exceeds alpha x what is left of the launch.  Measured at 8 spare CUs (same log): alpha 0 2.48 ms
@@ -261,13 +201,15 @@ static int enqueue_search(nrtgpu_ctx* ctx, Slot* slot, const HostPlan& hp, int32
     help.persistent = ms_persistent() ? 1u : 0u;
   }
   help.n_own = (uint32_t)hp.n_ms_items;
-  help.n_help = (uint32_t)n_help;
-  help.slot_base = (uint32_t)n_items;
+  help.n_help = (uint32_t)L.n_help;
+  help.slot_base = (uint32_t)L.n_items;
+  // NRTGPU_MS_HELP_MIN: an item with fewer unassigned windows is not joined.
+  static const int env_help_min = (int)dev_env_int("NRTGPU_MS_HELP_MIN", 16);
   static const bool env_help_greedy = dev_env_int("NRTGPU_MS_HELP_GREEDY", 0) != 0;
   help.min_rem = (uint32_t)std::min(std::max(env_help_min, 1), 0xFFFF) | (env_help_greedy ? 1u << 16 : 0u);
-  help.walls = profile ? (unsigned long long*)(wb + o_walls) : nullptr;
-  help.spec_g = spec ? (unsigned long long*)(wb + o_spec) : nullptr;
-  help.spec_z16 = spec ? spec_z16 : 0u;
+  help.walls = L.profile ? (unsigned long long*)(wb + L.walls) : nullptr;
+  help.spec_g = L.spec ? (unsigned long long*)(wb + L.spec_g) : nullptr;
+  help.spec_z16 = L.spec ? L.spec_z16 : 0u;
   {   // NRTGPU_MS_SPEC_FIRST / NRTGPU_MS_SPEC_GROW (x 16): when a workgroup's estimates are due (plan.h: DHelp.spec_sched)
     // NRTGPU_MS_SPEC_MEET=1: estimates are made in meetings of all waves, as before the estimator wave (A/B).
     // (development build: read per call -- tests and interleaved comparisons set them; the product build reads no environment)
@@ -277,46 +219,99 @@ static int enqueue_search(nrtgpu_ctx* ctx, Slot* slot, const HostPlan& hp, int32
     help.spec_sched = (uint32_t)std::min(std::max(env_first, 1), 255) | ((uint32_t)std::min(std::max(env_grow, 17), 255) << 8) | (env_meet ? 1u << 16 : 0u);
   }
   MsArgs ms_args{};   // (the kernel reads the record from the plan: maxscore.hip)
-  ms_args.items = (const DItem*)(db + o_items);
-  ms_args.parts = (const DPart*)(db + o_parts);
-  ms_args.terms = (const DTerm*)(wb + o_terms);
-  ms_args.queries = (const DQuery*)(db + o_queries);
-  ms_args.caches = (const float*)(db + o_caches);
-  ms_args.theta_g = (unsigned long long*)(db + o_theta);
-  ms_args.slice_sum = (uint32_t*)(wb + o_ssum);
-  ms_args.q_prune = (uint32_t*)(wb + o_qprune);
-  ms_args.xch = use_xch ? (const DExchange*)(db + o_xch) : nullptr;
-  ms_args.item_keys = (uint64_t*)(wb + o_ikeys);
-  ms_args.item_counts = (uint32_t*)(wb + o_icnt);
-  ms_args.item_hits = (uint64_t*)(wb + o_ihits);
-  ms_args.item_prof = profile ? (uint64_t*)(wb + o_prof) : nullptr;
-  ms_args.q_wins = (const uint32_t*)(db + o_qwins);
-  ms_args.rows = walk_rows ? (const DWalkRow*)(wb + o_rows) : nullptr;
-  {   // ... which the plan expansion writes (plan.h: DExpandHead)
-    DExpandHead xh{};
-    xh.caches = (const float*)(db + o_caches);
-    xh.queries = (const DQuery*)(db + o_queries);
-    xh.rows = walk_rows ? (DWalkRow*)(wb + o_rows) : nullptr;
-    memcpy(hb + o_qexp - sizeof(DExpandHead), &xh, sizeof(xh));
-  }
+  ms_args.items = (const DItem*)(db + L.items);
+  ms_args.parts = (const DPart*)(db + L.parts);
+  ms_args.terms = (const DTerm*)(wb + L.terms);
+  ms_args.queries = (const DQuery*)(db + L.queries);
+  ms_args.caches = (const float*)(db + L.caches);
+  ms_args.theta_g = (unsigned long long*)(db + L.theta);
+  ms_args.slice_sum = (uint32_t*)(wb + L.ssum);
+  ms_args.q_prune = (uint32_t*)(wb + L.qprune);
+  ms_args.xch = L.use_xch ? (const DExchange*)(db + L.xch) : nullptr;
+  ms_args.item_keys = (uint64_t*)(wb + L.item_keys);
+  ms_args.item_counts = (uint32_t*)(wb + L.item_counts);
+  ms_args.item_hits = (uint64_t*)(wb + L.item_hits);
+  ms_args.item_prof = L.profile ? (uint64_t*)(wb + L.prof) : nullptr;
+  ms_args.q_wins = (const uint32_t*)(db + L.q_wins);
+  ms_args.rows = L.walk_rows ? (const DWalkRow*)(wb + L.rows) : nullptr;   // ... which the plan expansion writes (plan.h: DExpandHead)
   {   // the leaf set's window order (note_speculation); NRTGPU_MS_SCATTER = 0 / 1 (development build): forced, A/B
     const long forced = dev_env_int("NRTGPU_MS_SCATTER", -1);
     // (the leaf set's step: search.cpp: note_speculation_of; forced: the bits as given)
-    ms_args.scatter = forced >= 0 ? (forced != 0 ? 1u : 0u) : ((spec && hp.lsc->spec_scattered.load(std::memory_order_relaxed) != 0) ? 1u : 0u);
+    ms_args.scatter = forced >= 0 ? (forced != 0 ? 1u : 0u) : ((L.spec && hp.lsc->spec_scattered.load(std::memory_order_relaxed) != 0) ? 1u : 0u);
   }
   ms_args.k_stride = hp.k_stride;
   ms_args.help = help;
-  memcpy(hb + o_help, &ms_args, sizeof(ms_args));
+  return ms_args;
+}
+
+// Enqueue plan upload + scan + merge on the slot's stream.  Merge output goes to o.ext_keys / ext_counts / ext_hits when given
+// (device-resident variant), else into the slot's scratch.
+// Everything is enqueued at once on the slot's stream and nothing waits on the host.  The kernels that want the whole
+// GPU (the two scorers) take turns ON THE DEVICE: under `gpu` (unlocked on entry and on return) the stream is made to
+// wait for the event recorded behind the previous batch's scorers, then this batch's are enqueued and their event
+// recorded behind their merge.  The plan upload and its expansion run ahead of that wait: they overlap the scorers of the
+// batch before instead of sitting between the two (before: lock -> launch -> host sync -> unlock, a host round trip plus
+// upload and expansion between any two scorer launches).
+static int enqueue_search(nrtgpu_ctx* ctx, Slot* slot, const HostPlan& hp, int32_t n_queries, uint32_t k_stride_out, const SearchOpts& o,
+                          DeviceRun* run, std::unique_lock<std::mutex>& gpu) {
+  forget_foreign_hip_error();
+  // follow_up (round 6): the second pass of a speculative call -- the handful of queries whose guess failed the merge's check, run
+  // again (seeded: search_batch_spec).  As a launch of the usual kind it took a TURN of its own, and BEHIND whatever batch another
+  // thread had enqueued meanwhile: its caller waited a whole batch for five queries (sorted-by-length corpus at C3's size, two
+  // submitting threads: 2.6 ms per 1024-query step around a 1.05 ms kernel -- slower than with speculation off).  A follow-up takes
+  // no turn: its few persistent workgroups run on the CUs every big launch leaves alone, beside whatever batch is running.
+  // Only MaxScore items (the exhaustive scan launches a workgroup per item and wants the whole device).
+  static const bool follow_up_on = dev_env_int("NRTGPU_FOLLOW_UP", 1) != 0;   // (development build: 0 = a turn of its own, A/B)
+  const bool small = o.follow_up && follow_up_on && hp.n_ms_items != 0 && hp.n_ms_items == hp.items.size() && ms_persistent();
+  const SearchLayout L(ctx, hp, n_queries, k_stride_out, o, ms_helpers(ctx, hp));
+  const size_t n_items = L.n_items, n_help = L.n_help, n_ms = hp.n_ms_items;   // the queries on the MaxScore route are items [0, n_ms)
+  if (int rc = slot->h_plan.reserve(L.plan_bytes)) return rc;
+  if (int rc = slot->d_plan.reserve(L.plan_bytes)) return rc;
+  if (int rc = slot->d_work.reserve(L.work.off)) return rc;
+  char* hb = (char*)slot->h_plan.p;
+  char* db = (char*)slot->d_plan.p;
+  char* wb = (char*)slot->d_work.p;
+  L.fill(hb, hp);
+  PlanLayout::put(hb, L.q_wins, hp.q_wins.data(), hp.q_wins.size() * 4);
+  if (o.spec_world > 1) {   // the denominator of "how much of the query's docs have I seen": the windows of ALL shards
+    // (this shard's REAL share of the index where the caller has stated it -- nrtgpu_set_shard_share: virtual shards balance
+    //  live docs, not docid ranges, and a shard that holds 40 % of the index is no "one of two" -- else spec_world equal shards)
+    uint64_t num = (uint64_t)o.spec_world, den = 1;
+    const int64_t sd = ctx->shard_docs.load(std::memory_order_relaxed), id = ctx->index_docs.load(std::memory_order_relaxed);
+    if (sd > 0 && id >= sd) {
+      num = (uint64_t)id;
+      den = (uint64_t)sd;
+    }
+    uint32_t* qw = (uint32_t*)(hb + L.q_wins);
+    for (size_t i = 0; i < hp.q_wins.size(); ++i) qw[i] = (uint32_t)std::min<uint64_t>(((uint64_t)qw[i] * num + den - 1) / den, 0xFFFFFFFFull);
+  }
+  memset(hb + L.quant, 0, hp.list_idx.size() * 8);
+  if (o.ext_hits) memcpy(hb + L.lower, hp.q_lower.data(), hp.q_lower.size() * 8);
+  if (L.use_xch) {
+    DExchange x{};
+    const size_t stride = (size_t)ctx->cfg.max_batch;
+    x.slot = ctx->xch_dev + (size_t)(o.epoch % kExchangeSlots) * (size_t)ctx->xch_world * stride;
+    x.world = (uint32_t)ctx->xch_world;
+    x.rank = (uint32_t)ctx->xch_rank;
+    x.stride = (uint32_t)stride;
+    x.tag = (uint32_t)(o.epoch + 1);  // never 0
+    if (x.tag == 0) x.tag = 1;
+    memcpy(hb + L.xch, &x, sizeof(x));
+  }
+  L.put_expand_head(hb, db, L.walk_rows ? (DWalkRow*)(wb + L.rows) : nullptr);
+  const MsArgs ms_args = ms_launch_record(ctx, hp, L, db, wb, small);
+  const DHelp& help = ms_args.help;
+  memcpy(hb + L.ms_args, &ms_args, sizeof(ms_args));
+  const bool profile = L.profile, use_xch = L.use_xch;
+  const int ablation = L.ablation;
 
   hipStream_t st = slot->stream;
-  HIP_TRY(hipMemcpyAsync(db, hb, plan_bytes, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemsetAsync(wb + o_ssum, 0, zero_bytes, st));
+  HIP_TRY(hipMemcpyAsync(db, hb, L.plan_bytes, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(wb + L.ssum, 0, L.zero_bytes, st));
   const bool timing = ctx->cfg.collect_timing != 0;
-  // the queries on the MaxScore route (items [0, n_ms)), then the exhaustive scan of the others
-  const size_t n_ms = hp.n_ms_items;
   // the compact plan -> the DTerm records of every (query, leaf), on the device
-  launch_expand_terms(st, (const DQExpand*)(db + o_qexp), (const DQTerm*)(db + o_qterms), (const uint32_t*)(db + o_qsb),
-                      (uint32_t)n_queries, hp.n_leaves, (DTerm*)(wb + o_terms));
+  launch_expand_terms(st, (const DQExpand*)(db + L.qexpand), (const DQTerm*)(db + L.qterms), (const uint32_t*)(db + L.qs_begin),
+                      (uint32_t)n_queries, hp.n_leaves, (DTerm*)(wb + L.terms));
   gpu.lock();
   // (experiment, off unless NRTGPU_OVERLAP_SCORERS=1: no turn between consecutive calls' scorers -- nothing but the turn itself
   //  orders them: workspaces are per slot, term tables reach the device before they become visible -- so that the next batch's
@@ -326,17 +321,17 @@ static int enqueue_search(nrtgpu_ctx* ctx, Slot* slot, const HostPlan& hp, int32
   if (ctx->last_turn && !overlap_scorers && !small) HIP_TRY(hipStreamWaitEvent(st, ctx->last_turn, 0));
   if (ctx->last_knn_turn) HIP_TRY(hipStreamWaitEvent(st, ctx->last_knn_turn, 0));   // (vector searches do not queue behind each other, the scorers queue behind them)
   if (timing) HIP_TRY(hipEventRecord(slot->ev3, st));
-  if (profile && n_help) HIP_TRY(hipMemsetAsync(wb + o_prof + n_items * 128, 0, n_help * 128, st));   // (a helper that leaves at once writes nothing)
-  if (profile) HIP_TRY(hipMemsetAsync(wb + o_walls, 0, n_slots * 64, st));
-  launch_bm25_maxscore(st, profile, (ctx->cfg.flags & NRTGPU_FLAG_PACKED_POSTINGS) != 0, hp.ms_two ? 2 : (hp.ms_shapes ? 1 : 0), ms_args, (const MsArgs*)(db + o_help));
+  if (profile && n_help) HIP_TRY(hipMemsetAsync(wb + L.prof + n_items * 128, 0, n_help * 128, st));   // (a helper that leaves at once writes nothing)
+  if (profile) HIP_TRY(hipMemsetAsync(wb + L.walls, 0, L.n_slots * 64, st));
+  launch_bm25_maxscore(st, profile, (ctx->cfg.flags & NRTGPU_FLAG_PACKED_POSTINGS) != 0, hp.ms_two ? 2 : (hp.ms_shapes ? 1 : 0), ms_args, (const MsArgs*)(db + L.ms_args));
   if (timing) HIP_TRY(hipEventRecord(slot->ev0, st));
   launch_bm25_scan(st, hp.fixed_point, (ctx->cfg.flags & NRTGPU_FLAG_NO_PREFETCH) == 0, (ctx->cfg.flags & NRTGPU_FLAG_PACKED_POSTINGS) != 0, ablation, (uint32_t)(n_items - n_ms),
-                   (const DItem*)(db + o_items) + n_ms, (const DPart*)(db + o_parts), (const DTerm*)(wb + o_terms),
-                   (const DQuery*)(db + o_queries), (const float*)(db + o_caches),
-                   (unsigned long long*)(db + o_theta), (unsigned long long*)(db + o_quant),
-                   use_xch ? (const DExchange*)(db + o_xch) : nullptr, (uint32_t*)(wb + o_ssum), (uint64_t*)(wb + o_ikeys) + n_ms * (size_t)hp.k_stride,
-                   (uint32_t*)(wb + o_icnt) + n_ms, (uint64_t*)(wb + o_ihits) + n_ms, hp.k_stride,
-                   ablation == 7 ? (uint64_t*)(wb + o_prof) + n_ms * 16 : nullptr);
+                   (const DItem*)(db + L.items) + n_ms, (const DPart*)(db + L.parts), (const DTerm*)(wb + L.terms),
+                   (const DQuery*)(db + L.queries), (const float*)(db + L.caches),
+                   (unsigned long long*)(db + L.theta), (unsigned long long*)(db + L.quant),
+                   use_xch ? (const DExchange*)(db + L.xch) : nullptr, (uint32_t*)(wb + L.ssum), (uint64_t*)(wb + L.item_keys) + n_ms * (size_t)hp.k_stride,
+                   (uint32_t*)(wb + L.item_counts) + n_ms, (uint64_t*)(wb + L.item_hits) + n_ms, hp.k_stride,
+                   ablation == 7 ? (uint64_t*)(wb + L.prof) + n_ms * 16 : nullptr);
   if (timing) HIP_TRY(hipEventRecord(slot->ev1, st));
   // The turn ends behind the SCORERS: the next batch's scorers start while this batch's merge (one workgroup per query, 0.05 ms
   // of device time per 1024 queries) runs on the CUs the persistent MaxScore launch leaves alone.  Through round 3 the merge was
@@ -349,20 +344,20 @@ static int enqueue_search(nrtgpu_ctx* ctx, Slot* slot, const HostPlan& hp, int32
     HIP_TRY(hipEventRecord(slot->ev_turn, st));
     ctx->last_turn = slot->ev_turn;
   }
-  uint64_t* okeys = ext_keys ? ext_keys : (uint64_t*)(wb + o_okeys);
-  uint32_t* ocnt = ext_counts ? ext_counts : (uint32_t*)(wb + o_ocnt);
-  uint64_t* ohits = ext_hits ? ext_hits : (uint64_t*)(wb + o_ohits);
-  launch_merge_topk(st, (uint32_t)n_queries, (const uint64_t*)(wb + o_ikeys), (const uint32_t*)(wb + o_icnt),
-                    (const uint64_t*)(wb + o_ihits), (const uint32_t*)(db + o_lidx), (const uint32_t*)(db + o_qbase),
-                    (const uint32_t*)(db + o_qnl), hp.k_stride, (const uint32_t*)(db + o_qk), okeys, ocnt, ohits,
-                    k_stride_out, n_help ? help.help_query : nullptr, (uint32_t)n_help, help.slot_base, spec_world > 1 ? nullptr : help.spec_g);
-  if (ext_guess) {   // (spec_world > 1: the guesses are checked by the caller, against the list merged over all shards)
-    if (spec) HIP_TRY(hipMemcpyAsync(ext_guess, wb + o_spec, (size_t)n_queries * 8, hipMemcpyDeviceToDevice, st));
-    else HIP_TRY(hipMemsetAsync(ext_guess, 0, (size_t)n_queries * 8, st));
+  uint64_t* okeys = o.ext_keys ? o.ext_keys : (uint64_t*)(wb + L.out_keys);
+  uint32_t* ocnt = o.ext_counts ? o.ext_counts : (uint32_t*)(wb + L.out_counts);
+  uint64_t* ohits = o.ext_hits ? o.ext_hits : (uint64_t*)(wb + L.out_hits);
+  launch_merge_topk(st, (uint32_t)n_queries, (const uint64_t*)(wb + L.item_keys), (const uint32_t*)(wb + L.item_counts),
+                    (const uint64_t*)(wb + L.item_hits), (const uint32_t*)(db + L.list_idx), (const uint32_t*)(db + L.q_base),
+                    (const uint32_t*)(db + L.q_nlists), hp.k_stride, (const uint32_t*)(db + L.q_k), okeys, ocnt, ohits,
+                    k_stride_out, n_help ? help.help_query : nullptr, (uint32_t)n_help, help.slot_base, o.spec_world > 1 ? nullptr : help.spec_g);
+  if (o.ext_guess) {   // (spec_world > 1: the guesses are checked by the caller, against the list merged over all shards)
+    if (L.spec) HIP_TRY(hipMemcpyAsync(o.ext_guess, wb + L.spec_g, (size_t)n_queries * 8, hipMemcpyDeviceToDevice, st));
+    else HIP_TRY(hipMemsetAsync(o.ext_guess, 0, (size_t)n_queries * 8, st));
   }
   // TotalHits.relation by the reference's per-slice rule, tagged into the merged counts
-  launch_slice_relation(st, (const uint32_t*)(wb + o_ssum), (const DQuery*)(db + o_queries), hp.n_slices, ohits, (uint32_t)n_queries);
-  if (ext_hits && hp.n_ms_items) launch_patch_hits(st, (const uint64_t*)(db + o_lower), ohits, (uint32_t)n_queries);
+  launch_slice_relation(st, (const uint32_t*)(wb + L.ssum), (const DQuery*)(db + L.queries), hp.n_slices, ohits, (uint32_t)n_queries);
+  if (o.ext_hits && hp.n_ms_items) launch_patch_hits(st, (const uint64_t*)(db + L.lower), ohits, (uint32_t)n_queries);
   if (timing) HIP_TRY(hipEventRecord(slot->ev2, st));
   if (!turn_before_merge && !small) {
     HIP_TRY(hipEventRecord(slot->ev_turn, st));
@@ -373,19 +368,18 @@ static int enqueue_search(nrtgpu_ctx* ctx, Slot* slot, const HostPlan& hp, int32
   run->out_keys = okeys;
   run->out_counts = ocnt;
   run->out_hits = ohits;
-  run->prof = (ablation == 7 || profile) ? (uint64_t*)(wb + o_prof) : nullptr;
+  run->prof = (ablation == 7 || profile) ? (uint64_t*)(wb + L.prof) : nullptr;
   run->n_items = n_items;
-  run->n_slots = n_slots;
-  run->walls = profile ? (uint64_t*)(wb + o_walls) : nullptr;
+  run->n_slots = L.n_slots;
+  run->walls = profile ? (uint64_t*)(wb + L.walls) : nullptr;
   run->n_ms_items = n_ms;
   return 0;
 }
 
-static void account(nrtgpu_ctx* ctx, Slot* slot, const HostPlan& hp, int32_t n_queries, double plan_ms, double t_entry_ms = 0.0,
-                    double queue_ms = 0.0) {
+void nrtgpu::rt::account(nrtgpu_ctx* ctx, Slot* slot, const HostPlan& hp, int32_t n_queries, double plan_ms, double t_entry_ms, double queue_ms) {
   float scan_ms = 0.f, merge_ms = 0.f, ms_ms = 0.f;
   if (ctx->cfg.collect_timing) {
-    (void)hipEventElapsedTime(&ms_ms, slot->ev3, slot->ev0);
+    if (hp.n_ms_items) (void)hipEventElapsedTime(&ms_ms, slot->ev3, slot->ev0);   // (ev3: recorded by enqueue_search alone, the only MaxScore route)
     (void)hipEventElapsedTime(&scan_ms, slot->ev0, slot->ev1);
     (void)hipEventElapsedTime(&merge_ms, slot->ev1, slot->ev2);
   }
@@ -426,8 +420,8 @@ static void account(nrtgpu_ctx* ctx, Slot* slot, const HostPlan& hp, int32_t n_q
 // bound; what is reported then is `lower` -- the live docs the planner knew to match, the same on every run: the
 // reference's own value there is an artefact of its traversal, SURVEY 7 hard part 3).  Either way the queue must be
 // full: a page of a searchAfter walk that returns fewer than numHits hits is EQUAL_TO.
-static void unpack_topdocs(const uint64_t* keys, uint32_t n, uint64_t hits, const int32_t k, int64_t lower, uint32_t n_first,
-                           nrtgpu_topdocs* out) {
+void nrtgpu::rt::unpack_topdocs(const uint64_t* keys, uint32_t n, uint64_t hits, const int32_t k, int64_t lower, uint32_t n_first,
+                                nrtgpu_topdocs* out) {
   const int32_t cap = out->capacity > 0 ? out->capacity : k;
   const int32_t m = std::min<int32_t>((int32_t)n, cap);
   // two plain loops (vectorisable): doc = ~low word, score = high word reinterpreted
@@ -448,6 +442,21 @@ static void unpack_topdocs(const uint64_t* keys, uint32_t n, uint64_t hits, cons
 // ------------------------------------------------------------------------------------------------
 // ABI: search
 // ------------------------------------------------------------------------------------------------
+int nrtgpu::rt::check_batch_size(const nrtgpu_ctx* ctx, int32_t n_queries, int32_t n_segs) {
+  if (n_queries <= 0 || n_segs < 0) return fail(NRTGPU_ERR_INVALID_ARG, "n_queries must be > 0");
+  if (n_queries > ctx->cfg.max_batch) return fail(NRTGPU_ERR_INVALID_ARG, "batch of %d exceeds max_batch %d", n_queries, ctx->cfg.max_batch);
+  return NRTGPU_OK;
+}
+// What the three planning entries do between their argument checks and their plan: the context's device, no NULL leaf.  (The
+// deadline check stays with each entry: nrtgpu_search_bm25_batch_device_begin makes it BEFORE the size checks, the others after,
+// and the hybrid entry has checks of its own between the two.)
+static int enter_search(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs) {
+  HIP_TRY(hipSetDevice(ctx->device));
+  for (int si = 0; si < n_segs; ++si)
+    if (!segs[si]) return fail(NRTGPU_ERR_INVALID_ARG, "segment %d is NULL", si);
+  return NRTGPU_OK;
+}
+
 // rerun: where the indices of the queries go whose speculative threshold failed the merge's check (plan.h: kHitsSpecInvalid);
 // nullptr: no speculation in this call.
 static int search_batch_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases,
@@ -455,14 +464,11 @@ static int search_batch_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, con
                              nrtgpu_topdocs* out, std::vector<int32_t>* rerun, bool content_held = false, const uint64_t* seeds = nullptr,
                              bool follow_up = false) {
   if (!ctx || !queries || !out || (n_segs > 0 && !segs)) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
-  if (n_queries <= 0 || n_segs < 0) return fail(NRTGPU_ERR_INVALID_ARG, "n_queries must be > 0");
-  if (n_queries > ctx->cfg.max_batch) return fail(NRTGPU_ERR_INVALID_ARG, "batch of %d exceeds max_batch %d", n_queries, ctx->cfg.max_batch);
+  if (int rc = check_batch_size(ctx, n_queries, n_segs)) return rc;
   NRT_CHECK_DEADLINE("before the search was planned");
-  HIP_TRY(hipSetDevice(ctx->device));
   const double t0 = now_ms();
+  if (int rc = enter_search(ctx, segs, n_segs)) return rc;
   HostPlan hp;
-  for (int si = 0; si < n_segs; ++si)
-    if (!segs[si]) return fail(NRTGPU_ERR_INVALID_ARG, "segment %d is NULL", si);
   std::optional<SegReadLocks> content;   // until this call's kernels have finished (content_held: the caller holds them over both passes)
   if (!content_held) content.emplace(segs, n_segs);
   if (int rc = build_plan(ctx, segs, doc_bases, n_segs, queries, n_queries, hp, 1)) return rc;
@@ -487,7 +493,10 @@ static int search_batch_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, con
   const double tc0 = call_trace ? now_ms() : 0.0;
   {
     std::unique_lock<std::mutex> gpu(ctx->gpu_mu, std::defer_lock);
-    if (int rc = enqueue_search(ctx, slot, hp, n_queries, hp.k_stride, nullptr, nullptr, nullptr, &run, gpu, -1, rerun != nullptr, 1, nullptr, follow_up)) return rc;
+    SearchOpts o;
+    o.allow_spec = rerun != nullptr;
+    o.follow_up = follow_up;
+    if (int rc = enqueue_search(ctx, slot, hp, n_queries, hp.k_stride, o, &run, gpu)) return rc;
   }
   // The answers come back behind the kernels on the same stream: ONE copy where the workspace lays keys, counts and hits out as the
   // host buffer does (both are carved by the same rule), and one wait for everything -- through round 5 the call waited for the
@@ -550,56 +559,76 @@ static int search_batch_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, con
   return NRTGPU_OK;
 }
 
+// The two passes of the synchronous entries (nrtgpu_search_bm25_batch, the hybrid entries).  The MaxScore route may run under
+// SPECULATIVE thresholds there (plan.h: kHitsSpecInvalid; nrtgpu_set_speculation): a query whose guess the merge could not confirm
+// comes back tagged and is run again without speculation -- for the hybrid entries first pass AND tail: its recall set may lack
+// docs.  Both passes run under ONE set of content locks (a set_mask / set_live_docs between them would show the re-run queries
+// other content than their batch mates, or evict a mask they name), and the second pass ignores the thread's deadline: its work is
+// the tail of a search that was launched in time, and every untagged query of the call already holds its answer.
+// pass(queries, n, out, rerun, idx): one pass of the entry.  rerun: where the tagged queries' indices go (nullptr: no speculation
+// in this pass); idx: nullptr for the whole batch, else which queries of the batch these n are (the second pass); the content locks
+// are the caller's unless both are nullptr.
 // after_first (the coalescer's): called between the two passes with the indices of the queries that are run again -- every OTHER
 // query of the batch holds its final answer in `out` at that moment, and its caller need not wait for the second pass.
-static int search_batch_spec(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
-                             const nrtgpu_bm25_query* queries, int32_t n_queries, nrtgpu_topdocs* out,
-                             const std::function<void(const std::vector<int32_t>&)>* after_first) {
-  // The MaxScore route may run under SPECULATIVE thresholds here (plan.h: kHitsSpecInvalid; nrtgpu_set_speculation): a query whose
-  // guess the merge could not confirm comes back tagged and is run again without speculation.  Both passes run under ONE set of
-  // content locks (a set_mask / set_live_docs between them would show the re-run queries other content than their batch mates,
-  // or evict a mask they name), and the second pass ignores the thread's deadline: its work is the tail of a search that was
-  // launched in time, and every untagged query of the call already holds its answer.
-  std::vector<int32_t> rerun;
-  const bool spec = speculating(ctx, segs, n_segs);
-  if (!spec) return search_batch_impl(ctx, segs, doc_bases, n_segs, queries, n_queries, out, nullptr);
+typedef std::function<void(const std::vector<int32_t>&)> AfterFirst;
+template <class Pass>
+static int two_pass_search(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query* queries, int32_t n_queries,
+                           nrtgpu_topdocs* out, const AfterFirst* after_first, const Pass& pass) {
+  if (!speculating(ctx, segs, n_segs)) return pass(queries, n_queries, out, nullptr, nullptr);
   if (ctx && segs)
     for (int si = 0; si < n_segs; ++si)
       if (!segs[si]) return fail(NRTGPU_ERR_INVALID_ARG, "segment %d is NULL", si);
+  std::vector<int32_t> rerun;
   SegReadLocks content(segs, n_segs);
-  const int rc = search_batch_impl(ctx, segs, doc_bases, n_segs, queries, n_queries, out, &rerun, true);
-  if (rc != 0) return rc;
-  const nrtgpu_diagnostics first = g_diag;
+  if (int rc = pass(queries, n_queries, out, &rerun, nullptr)) return rc;
   note_speculation(ctx, segs, n_segs, n_queries, (int64_t)rerun.size());
-  if (rerun.empty()) return rc;
+  if (rerun.empty()) return NRTGPU_OK;
   if (after_first) (*after_first)(rerun);
   std::vector<nrtgpu_bm25_query> rq(rerun.size());
   std::vector<nrtgpu_topdocs> ro(rerun.size());
-  // The second pass starts where the first one ended (round 6).  A guess that failed was too HIGH: the first pass skipped docs it
-  // should have kept -- but every hit it returned is a real doc with its real score, so a query that came back with k hits has k
-  // docs at or above its k-th key, and the final k-th key cannot lie below that one.  The re-run takes "the first pass's k-th key
-  // minus one" as its initial threshold (strictly below the final k-th key: keys are distinct integers, and a collector keeps only
-  // what EXCEEDS its threshold) and prunes from its first posting the way a converged walk does, where an unseeded re-run --
-  // no speculation, theta from zero -- was the slowest kind of walk there is: on the sorted-by-length corpus the five queries of
-  // a batch that are run again cost the step 1.6 ms around a 1.1 ms kernel (profiles/r05_bench_c3_sorted.json).
-  // (Only from the caller's own arrays where they hold the k-th hit: a NULL or short array seeds nothing.)
-  std::vector<uint64_t> seeds(rerun.size(), 0ull);
-  static const bool seed_reruns = dev_env_int("NRTGPU_SEED_RERUNS", 1) != 0;   // (development build: 0 = from zero, A/B)
   for (size_t i = 0; i < rerun.size(); ++i) {
     rq[i] = queries[rerun[i]];
     ro[i] = out[rerun[i]];
-    const nrtgpu_topdocs& o = out[rerun[i]];
-    const int32_t k = rq[i].k;
-    if (seed_reruns && k > 0 && o.n_hits >= k && o.docs && o.scores && (o.capacity <= 0 || o.capacity >= k)) {
-      const uint64_t kth = pack_key(o.scores[k - 1], (uint32_t)o.docs[k - 1]);
-      seeds[i] = kth > 0 ? kth - 1 : 0ull;
-    }
   }
   DeadlineScope no_deadline(true);
-  // (a few queries: a follow-up launch beside the next batch -- enqueue_search; more than that and it is a batch of its own)
-  const int rc2 = search_batch_impl(ctx, segs, doc_bases, n_segs, rq.data(), (int32_t)rq.size(), ro.data(), nullptr, true, seeds.data(), rq.size() <= 32);
-  if (rc2 != 0) return rc2;
+  if (int rc = pass(rq.data(), (int32_t)rq.size(), ro.data(), nullptr, rerun.data())) return rc;
   for (size_t i = 0; i < rerun.size(); ++i) out[rerun[i]] = ro[i];
+  return NRTGPU_OK;
+}
+
+static int search_batch_spec(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                             const nrtgpu_bm25_query* queries, int32_t n_queries, nrtgpu_topdocs* out, const AfterFirst* after_first) {
+  nrtgpu_diagnostics first{};
+  bool second = false;
+  const int rc = two_pass_search(ctx, segs, n_segs, queries, n_queries, out, after_first,
+                                 [&](const nrtgpu_bm25_query* q, int32_t n, nrtgpu_topdocs* o, std::vector<int32_t>* rerun, const int32_t* idx) {
+    if (!idx) {
+      const int rc1 = search_batch_impl(ctx, segs, doc_bases, n_segs, q, n, o, rerun, rerun != nullptr);
+      if (rerun) first = g_diag;
+      return rc1;
+    }
+    // The second pass starts where the first one ended (round 6).  A guess that failed was too HIGH: the first pass skipped docs it
+    // should have kept -- but every hit it returned is a real doc with its real score, so a query that came back with k hits has k
+    // docs at or above its k-th key, and the final k-th key cannot lie below that one.  The re-run takes "the first pass's k-th key
+    // minus one" as its initial threshold (strictly below the final k-th key: keys are distinct integers, and a collector keeps only
+    // what EXCEEDS its threshold) and prunes from its first posting the way a converged walk does, where an unseeded re-run --
+    // no speculation, theta from zero -- was the slowest kind of walk there is: on the sorted-by-length corpus the five queries of
+    // a batch that are run again cost the step 1.6 ms around a 1.1 ms kernel (profiles/r05_bench_c3_sorted.json).
+    // (Only from the caller's own arrays where they hold the k-th hit: a NULL or short array seeds nothing.)
+    std::vector<uint64_t> seeds((size_t)n, 0ull);
+    static const bool seed_reruns = dev_env_int("NRTGPU_SEED_RERUNS", 1) != 0;   // (development build: 0 = from zero, A/B)
+    for (int32_t i = 0; i < n; ++i) {
+      const int32_t k = q[i].k;
+      if (seed_reruns && k > 0 && o[i].n_hits >= k && o[i].docs && o[i].scores && (o[i].capacity <= 0 || o[i].capacity >= k)) {
+        const uint64_t kth = pack_key(o[i].scores[k - 1], (uint32_t)o[i].docs[k - 1]);
+        seeds[(size_t)i] = kth > 0 ? kth - 1 : 0ull;
+      }
+    }
+    second = true;
+    // (a few queries: a follow-up launch beside the next batch -- enqueue_search; more than that and it is a batch of its own)
+    return search_batch_impl(ctx, segs, doc_bases, n_segs, q, n, o, nullptr, true, seeds.data(), n <= 32);
+  });
+  if (rc != 0 || !second) return rc;
   nrtgpu_diagnostics d = g_diag;   // both passes
   d.total_ms += first.total_ms;
   d.plan_ms += first.plan_ms;
@@ -674,17 +703,14 @@ static int search_hybrid_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, co
   forget_foreign_hip_error();
   if (!ctx || !queries || !out || !query_vectors || (n_segs > 0 && (!segs || !doc_bases)))
     return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
-  if (n_queries <= 0 || n_segs < 0) return fail(NRTGPU_ERR_INVALID_ARG, "n_queries must be > 0");
-  if (n_queries > ctx->cfg.max_batch) return fail(NRTGPU_ERR_INVALID_ARG, "batch of %d exceeds max_batch %d", n_queries, ctx->cfg.max_batch);
+  if (int rc = check_batch_size(ctx, n_queries, n_segs)) return rc;
   if (dim <= 0 || sim < 0 || sim > 3 || window <= 0) return fail(NRTGPU_ERR_INVALID_ARG, "bad rescore arguments");
   if (!(query_weight >= 0.0) || !(rescore_weight >= 0.0) || !(boost >= 0.0f))
     return fail(NRTGPU_ERR_UNSUPPORTED, "hybrid tail: negative weights (combined scores must stay >= 0)");
   NRT_CHECK_DEADLINE("before the search was planned");
-  HIP_TRY(hipSetDevice(ctx->device));
   const double t0 = now_ms();
+  if (int rc = enter_search(ctx, segs, n_segs)) return rc;
   HostPlan hp;
-  for (int si = 0; si < n_segs; ++si)
-    if (!segs[si]) return fail(NRTGPU_ERR_INVALID_ARG, "segment %d is NULL", si);
   std::optional<SegReadLocks> content;   // until this call's kernels have finished (content_held: the caller holds them over both passes)
   if (!content_held) content.emplace(segs, n_segs);
   // the other element type (a byte tail: another dimension too) is refused before anything is planned; the float queries are padded
@@ -731,7 +757,9 @@ static int search_hybrid_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, co
   DeviceRun run;
   {
     std::unique_lock<std::mutex> gpu(ctx->gpu_mu, std::defer_lock);
-    if (int rc = enqueue_search(ctx, slot, hp, n_queries, hp.k_stride, nullptr, nullptr, nullptr, &run, gpu, -1, rerun != nullptr)) {
+    SearchOpts o;
+    o.allow_spec = rerun != nullptr;
+    if (int rc = enqueue_search(ctx, slot, hp, n_queries, hp.k_stride, o, &run, gpu)) {
       (void)hipStreamSynchronize(st);   // the upload of the query vectors reads the slot's pinned buffer: not in flight when the slot is released
       return rc;
     }
@@ -770,39 +798,18 @@ static int search_hybrid_entry(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, c
                                const nrtgpu_bm25_query* queries, int32_t n_queries, int32_t field_id, int32_t sim, const void* query_vectors,
                                bool bytes, int32_t dim, float boost, double query_weight, double rescore_weight, int32_t window,
                                nrtgpu_topdocs* out) {
-  // The first pass may run under speculative thresholds (plan.h: kHitsSpecInvalid), as in nrtgpu_search_bm25_batch: recall, tail
-  // and the copy back stay one stream with no host round trip; the merge's tags arrive with the results, and a tagged query --
-  // its recall set may lack docs -- is run again, first pass and tail, without speculation.
-  // Both passes under one set of content locks, the second one without the thread's deadline: as nrtgpu_search_bm25_batch.
-  std::vector<int32_t> rerun;
-  const bool spec = speculating(ctx, segs, n_segs);
-  if (!spec)
-    return search_hybrid_impl(ctx, segs, doc_bases, n_segs, queries, n_queries, field_id, sim, query_vectors, bytes, dim, boost, query_weight,
-                              rescore_weight, window, out, nullptr);
-  if (ctx && segs)
-    for (int si = 0; si < n_segs; ++si)
-      if (!segs[si]) return fail(NRTGPU_ERR_INVALID_ARG, "segment %d is NULL", si);
-  SegReadLocks content(segs, n_segs);
-  const int rc = search_hybrid_impl(ctx, segs, doc_bases, n_segs, queries, n_queries, field_id, sim, query_vectors, bytes, dim, boost, query_weight,
-                                    rescore_weight, window, out, &rerun, true);
-  if (rc != 0) return rc;
-  note_speculation(ctx, segs, n_segs, n_queries, (int64_t)rerun.size());
-  if (rerun.empty()) return rc;
-  std::vector<nrtgpu_bm25_query> rq(rerun.size());
-  std::vector<nrtgpu_topdocs> ro(rerun.size());
+  // (recall, tail and the copy back stay one stream with no host round trip; the merge's tags arrive with the results)
   const size_t row_bytes = (size_t)dim * (bytes ? sizeof(int8_t) : sizeof(float));
-  std::vector<float> rv((rerun.size() * row_bytes + sizeof(float) - 1) / sizeof(float));   // (the tagged queries' vectors, either element type)
-  for (size_t i = 0; i < rerun.size(); ++i) {
-    rq[i] = queries[rerun[i]];
-    ro[i] = out[rerun[i]];
-    memcpy((char*)rv.data() + i * row_bytes, (const char*)query_vectors + (size_t)rerun[i] * row_bytes, row_bytes);
-  }
-  DeadlineScope no_deadline(true);
-  const int rc2 = search_hybrid_impl(ctx, segs, doc_bases, n_segs, rq.data(), (int32_t)rq.size(), field_id, sim, rv.data(), bytes, dim, boost, query_weight,
-                                     rescore_weight, window, ro.data(), nullptr, true);
-  if (rc2 != 0) return rc2;
-  for (size_t i = 0; i < rerun.size(); ++i) out[rerun[i]] = ro[i];
-  return NRTGPU_OK;
+  return two_pass_search(ctx, segs, n_segs, queries, n_queries, out, nullptr,
+                         [&](const nrtgpu_bm25_query* q, int32_t n, nrtgpu_topdocs* o, std::vector<int32_t>* rerun, const int32_t* idx) {
+    std::vector<float> rv;   // (the tagged queries' vectors, either element type)
+    if (idx) {
+      rv.resize(((size_t)n * row_bytes + sizeof(float) - 1) / sizeof(float));
+      for (int32_t i = 0; i < n; ++i) memcpy((char*)rv.data() + (size_t)i * row_bytes, (const char*)query_vectors + (size_t)idx[i] * row_bytes, row_bytes);
+    }
+    return search_hybrid_impl(ctx, segs, doc_bases, n_segs, q, n, field_id, sim, idx ? (const void*)rv.data() : query_vectors, bytes, dim, boost, query_weight,
+                              rescore_weight, window, o, rerun, rerun != nullptr || idx != nullptr);
+  });
 }
 
 extern "C" int nrtgpu_search_hybrid_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases,
@@ -853,11 +860,11 @@ int nrtgpu::rt::hybrid_tail_on_device(nrtgpu_ctx* ctx, Slot* slot, const nrtgpu_
   return NRTGPU_OK;
 }
 
-int nrtgpu::rt::merge_lists_on_device(nrtgpu_ctx* ctx, Slot* slot, int32_t n_lists, int32_t n_queries, int32_t k_stride, const void* g_keys,
-                                      const void* g_counts, const void* g_hits, const int32_t* ks, void* d_keys, void* d_counts, void* d_hits) {
-  forget_foreign_hip_error();
-  const size_t nq = (size_t)n_queries, nl = (size_t)n_lists;
-  Carver pc;
+// TopDocs.merge of `nl` gathered lists of `nq` queries, layout [list][query]: the merge's four index arrays staged in the slot's plan
+// buffers, uploaded, merge_topk_kernel enqueued on the slot's stream.
+static int merge_gathered_lists(Slot* slot, size_t nl, size_t nq, uint32_t k_stride, const void* g_keys, const void* g_counts, const void* g_hits,
+                                const int32_t* ks, void* d_keys, void* d_counts, void* d_hits) {
+  Carver pc;   // plan blob: list_idx (n_queries * n_lists), q_base, q_nlists, q_k
   const size_t o_lidx = pc.take(nq * nl * 4), o_qbase = pc.take(nq * 4), o_qnl = pc.take(nq * 4), o_qk = pc.take(nq * 4);
   if (int rc = slot->h_plan.reserve(pc.off)) return rc;
   if (int rc = slot->d_plan.reserve(pc.off)) return rc;
@@ -874,11 +881,17 @@ int nrtgpu::rt::merge_lists_on_device(nrtgpu_ctx* ctx, Slot* slot, int32_t n_lis
   }
   char* db = (char*)slot->d_plan.p;
   HIP_TRY(hipMemcpyAsync(db, hb, pc.off, hipMemcpyHostToDevice, slot->stream));
-  launch_merge_topk(slot->stream, (uint32_t)n_queries, (const uint64_t*)g_keys, (const uint32_t*)g_counts, (const uint64_t*)g_hits,
-                    (const uint32_t*)(db + o_lidx), (const uint32_t*)(db + o_qbase), (const uint32_t*)(db + o_qnl), (uint32_t)k_stride,
-                    (const uint32_t*)(db + o_qk), (uint64_t*)d_keys, (uint32_t*)d_counts, (uint64_t*)d_hits, (uint32_t)k_stride);
+  launch_merge_topk(slot->stream, (uint32_t)nq, (const uint64_t*)g_keys, (const uint32_t*)g_counts, (const uint64_t*)g_hits,
+                    (const uint32_t*)(db + o_lidx), (const uint32_t*)(db + o_qbase), (const uint32_t*)(db + o_qnl), k_stride,
+                    (const uint32_t*)(db + o_qk), (uint64_t*)d_keys, (uint32_t*)d_counts, (uint64_t*)d_hits, k_stride);
   HIP_TRY(hipGetLastError());
   return NRTGPU_OK;
+}
+
+int nrtgpu::rt::merge_lists_on_device(nrtgpu_ctx* ctx, Slot* slot, int32_t n_lists, int32_t n_queries, int32_t k_stride, const void* g_keys,
+                                      const void* g_counts, const void* g_hits, const int32_t* ks, void* d_keys, void* d_counts, void* d_hits) {
+  forget_foreign_hip_error();
+  return merge_gathered_lists(slot, (size_t)n_lists, (size_t)n_queries, (uint32_t)k_stride, g_keys, g_counts, g_hits, ks, d_keys, d_counts, d_hits);
 }
 
 extern "C" int nrtgpu_query_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query* q) {
@@ -1088,7 +1101,7 @@ extern "C" int nrtgpu_search_bm25_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* c
   // A member whose query is run again (a speculative threshold failed the merge's check) must not hold up its batch mates: they
   // are woken between the two passes with the answer they already have.
   std::vector<char> released(batch.size(), 0);
-  const std::function<void(const std::vector<int32_t>&)> after_first = [&](const std::vector<int32_t>& rerun) {
+  const AfterFirst after_first = [&](const std::vector<int32_t>& rerun) {
     std::vector<char> again(batch.size(), 0);
     for (int32_t qi : rerun) again[(size_t)qi] = 1;
     const nrtgpu_diagnostics first_diag = g_diag;
@@ -1189,12 +1202,9 @@ static int device_begin_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, con
   if (!ctx || !queries || !d_keys || !d_counts || !d_hits || !out || (n_segs > 0 && !segs)) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
   *out = nullptr;
   NRT_CHECK_DEADLINE("before the search was planned");
-  if (n_queries <= 0 || n_segs < 0) return fail(NRTGPU_ERR_INVALID_ARG, "n_queries must be > 0");
-  if (n_queries > ctx->cfg.max_batch) return fail(NRTGPU_ERR_INVALID_ARG, "batch of %d exceeds max_batch %d", n_queries, ctx->cfg.max_batch);
-  HIP_TRY(hipSetDevice(ctx->device));
+  if (int rc = check_batch_size(ctx, n_queries, n_segs)) return rc;
   const double t0 = now_ms();
-  for (int si = 0; si < n_segs; ++si)
-    if (!segs[si]) return fail(NRTGPU_ERR_INVALID_ARG, "segment %d is NULL", si);
+  if (int rc = enter_search(ctx, segs, n_segs)) return rc;
   auto p = std::make_unique<nrtgpu_pending>();
   p->ctx = ctx;
   p->n_queries = n_queries;
@@ -1219,6 +1229,14 @@ static int device_begin_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, con
   p->d_keys = (uint64_t*)d_keys;
   p->d_counts = (uint32_t*)d_counts;
   p->d_hits = (uint64_t*)d_hits;
+  SearchOpts o;
+  o.ext_keys = p->d_keys;
+  o.ext_counts = p->d_counts;
+  o.ext_hits = p->d_hits;
+  o.epoch = epoch;
+  o.allow_spec = p->speculated;
+  o.spec_world = std::max(spec_world, 1);
+  o.ext_guess = d_guess;
   static const bool use_launcher = dev_env_int("NRTGPU_LAUNCHER", 1) != 0;   // (development build: 0 = the caller enqueues, A/B)
   if (through_launcher && use_launcher) {
     // the caller goes on planning its next batch; the launcher packs and enqueues this one (in the order of the _begin calls).
@@ -1231,14 +1249,12 @@ static int device_begin_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, con
     }
     nrtgpu_pending* pp = p.release();
     std::shared_ptr<nrtgpu_pending::Enqueue> enq = pp->enq = std::make_shared<nrtgpu_pending::Enqueue>();
-    const int32_t sw = std::max(spec_world, 1);
-    l->push([pp, enq, n_queries, k_stride, epoch, sw, d_guess] {
+    l->push([pp, enq, n_queries, k_stride, o] {
       DeviceRun run;
       int rc;
       {
         std::unique_lock<std::mutex> gpu(pp->ctx->gpu_mu, std::defer_lock);
-        rc = enqueue_search(pp->ctx, pp->slot, pp->hp, n_queries, (uint32_t)k_stride, pp->d_keys, pp->d_counts, pp->d_hits, &run, gpu, epoch,
-                            pp->speculated, sw, d_guess);
+        rc = enqueue_search(pp->ctx, pp->slot, pp->hp, n_queries, (uint32_t)k_stride, o, &run, gpu);
       }
       std::lock_guard<std::mutex> lk(enq->mu);   // (from here on `pp` may be gone)
       enq->rc = rc;
@@ -1252,8 +1268,7 @@ static int device_begin_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, con
   DeviceRun run;
   {
     std::unique_lock<std::mutex> gpu(ctx->gpu_mu, std::defer_lock);
-    if (int rc = enqueue_search(ctx, p->slot, p->hp, n_queries, (uint32_t)k_stride, (uint64_t*)d_keys, (uint32_t*)d_counts,
-                                (uint64_t*)d_hits, &run, gpu, epoch, p->speculated, std::max(spec_world, 1), d_guess)) {
+    if (int rc = enqueue_search(ctx, p->slot, p->hp, n_queries, (uint32_t)k_stride, o, &run, gpu)) {
       (void)hipStreamSynchronize(p->slot->stream);   // whatever was enqueued reads the slot's buffers
       release_slot(ctx, p->slot);
       return rc;
@@ -1343,7 +1358,11 @@ extern "C" int nrtgpu_pending_wait(nrtgpu_pending* pending) {
       if (n_bad) {
         DeviceRun run;
         std::unique_lock<std::mutex> gpu(ctx->gpu_mu, std::defer_lock);
-        if (int rc = enqueue_search(ctx, p->slot, p->hp, p->n_queries, p->k_stride, p->d_keys, p->d_counts, p->d_hits, &run, gpu, -1, false)) {
+        SearchOpts o;   // (no speculation, no exchange)
+        o.ext_keys = p->d_keys;
+        o.ext_counts = p->d_counts;
+        o.ext_hits = p->d_hits;
+        if (int rc = enqueue_search(ctx, p->slot, p->hp, p->n_queries, p->k_stride, o, &run, gpu)) {
           gpu = std::unique_lock<std::mutex>();   // (its message is this thread's g_last_error: kept)
           (void)hipStreamSynchronize(p->slot->stream);
           release_slot(ctx, p->slot);
@@ -1391,37 +1410,16 @@ int nrtgpu::rt::merge_topk_device_kth(nrtgpu_ctx* ctx, int32_t n_lists, int32_t 
   Slot* slot = nullptr;
   acquire_slot(ctx, &slot);
   SlotGuard guard{ctx, slot};
-  // plan blob: list_idx (n_queries * n_lists), q_base, q_nlists, q_k
-  const size_t nq = (size_t)n_queries, nl = (size_t)n_lists;
-  Carver pc;
-  const size_t o_lidx = pc.take(nq * nl * 4), o_qbase = pc.take(nq * 4), o_qnl = pc.take(nq * 4), o_qk = pc.take(nq * 4);
-  if (int rc = slot->h_plan.reserve(pc.off)) return rc;
-  if (int rc = slot->d_plan.reserve(pc.off)) return rc;
-  char* hb = (char*)slot->h_plan.p;
-  uint32_t* lidx = (uint32_t*)(hb + o_lidx);
-  uint32_t* qbase = (uint32_t*)(hb + o_qbase);
-  uint32_t* qnl = (uint32_t*)(hb + o_qnl);
-  uint32_t* qk = (uint32_t*)(hb + o_qk);
-  for (size_t q = 0; q < nq; ++q) {
-    qbase[q] = (uint32_t)(q * nl);
-    qnl[q] = (uint32_t)nl;
-    qk[q] = (uint32_t)ks[q];
-    for (size_t l = 0; l < nl; ++l) lidx[q * nl + l] = (uint32_t)(l * nq + q);
-  }
+  const size_t nq = (size_t)n_queries;
   Carver wc;
   const size_t o_okeys = wc.take(nq * (size_t)k_stride * 8), o_ocnt = wc.take(nq * 4), o_ohits = wc.take(nq * 8);
   if (int rc = slot->d_work.reserve(wc.off)) return rc;
   if (int rc = slot->h_out.reserve(wc.off)) return rc;
-  char* db = (char*)slot->d_plan.p;
   char* wb = (char*)slot->d_work.p;
   char* ho = (char*)slot->h_out.p;
   hipStream_t st = slot->stream;
-  HIP_TRY(hipMemcpyAsync(db, hb, pc.off, hipMemcpyHostToDevice, st));
-  launch_merge_topk(st, (uint32_t)n_queries, (const uint64_t*)d_keys_in, (const uint32_t*)d_counts_in,
-                    (const uint64_t*)d_hits_in, (const uint32_t*)(db + o_lidx), (const uint32_t*)(db + o_qbase),
-                    (const uint32_t*)(db + o_qnl), (uint32_t)k_stride, (const uint32_t*)(db + o_qk),
-                    (uint64_t*)(wb + o_okeys), (uint32_t*)(wb + o_ocnt), (uint64_t*)(wb + o_ohits), (uint32_t)k_stride);
-  HIP_TRY(hipGetLastError());
+  if (int rc = merge_gathered_lists(slot, (size_t)n_lists, nq, (uint32_t)k_stride, d_keys_in, d_counts_in, d_hits_in, ks, wb + o_okeys, wb + o_ocnt, wb + o_ohits))
+    return rc;
   HIP_TRY(hipMemcpyAsync(ho, wb, wc.off, hipMemcpyDeviceToHost, st));
   HIP_TRY(wait_for_stream((ctx->cfg.flags & NRTGPU_FLAG_BLOCKING_WAIT) != 0, st, slot->ev_wait));
   const uint64_t* keys = (const uint64_t*)(ho + o_okeys);
