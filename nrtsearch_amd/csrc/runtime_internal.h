@@ -2,7 +2,8 @@
 //
 // The runtime is split by concern: runtime.cpp (errors, context, workspaces, statistics, exchange table, host
 // helpers), segment.cpp (the segment store: upload, seal, liveDocs, masks), planner.cpp (queries -> launch
-// plan), search.cpp (BM25 entry points, hybrid tail, request coalescing, merge), finalscore.cpp (the host
+// plan), search.cpp (BM25 entry points, hybrid tail, merge), coalescer.h (request coalescing: the leader/follower mechanism behind
+// the single-query entries of search.cpp and vectors.cpp; standard library only), finalscore.cpp (the host
 // path of the final-score routes), funcscore.cpp (function-score queries), multimatch.cpp (multi-match queries),
 // vectors.cpp (exact kNN, vector rescoring).  Types the ABI names opaquely (nrtgpu_ctx, nrtgpu_seg) live in the global namespace;
 // everything else in nrtgpu::rt.
@@ -38,6 +39,7 @@
 #ifdef NRTGPU_DEV
 #include "../../include/nrtgpu_dev.h"
 #endif
+#include "coalescer.h"
 #include "host_math.h"
 #include "plan.h"
 
@@ -546,15 +548,10 @@ struct nrtgpu_ctx {
   int64_t last_walls_items = 0;       // ... whose first this-many slots are the items' owners (helpers behind the scan's slots)
   double ms_prof[16] = {0};   // the same for the items of the MaxScore route (nrtgpu_get_maxscore_profile)
   int64_t ms_meetings[4] = {0};   // ... and their meetings, overflow meetings, compactions, one-wave estimates (nrtgpu_debug_maxscore_meetings)
-  // request coalescing (nrtgpu_search_bm25_coalesced)
-  std::mutex co_mu;
-  std::condition_variable co_cv;
-  std::vector<struct CoRequest*> co_pending;  // waiting for a leader
-  struct CoRequest* co_leader = nullptr;      // the caller lingering for / about to run the next batch
-  int co_inflight = 0;                        // coalesced batches executing right now
-  int co_inflight_queries = 0;                // ... and how many queries they hold
-  int co_last_batch = 0;                      // size of the batch formed last (a lone caller does not linger)
-  int32_t co_linger_us = 150;
+  // request coalescing (coalescer.h): the single-query entries' callers merged into batches (nrtgpu_search_bm25_coalesced, search.cpp)
+  // and into panels (nrtgpu_knn_exact_coalesced, vectors.cpp)
+  nrtgpu::rt::Coalescer co, kco;
+  int32_t co_linger_us = 150;   // (under co.mu: nrtgpu_set_coalescing)
   // speculative thresholds (plan.h: kHitsSpecInvalid; nrtgpu_debug_spec_counters): queries run under speculation, queries whose guess
   // failed and were run again, and the switch the library throws itself when too many fail (docs not spread like a sample)
   std::atomic<int64_t> spec_queries{0}, spec_reruns{0};   // (sums over the context's leaf sets since nrtgpu_set_speculation: nrtgpu_stats)
@@ -564,13 +561,6 @@ struct nrtgpu_ctx {
   std::atomic<int> spec_z16{5 * 16};   // the guess's margin x 16 (nrtgpu_set_speculation)
   std::atomic<int64_t> shard_docs{0}, index_docs{0};   // nrtgpu_set_shard_share: this context's share of a sharded index (0: equal shards)
   std::atomic<int64_t> live_segments{0};   // segment handles (uploads and forks) that have not been freed yet (nrtgpu_debug_live_segments)
-  std::atomic<int> co_hold{0};                          // nrtgpu_debug_hold_coalescers: no leader (of either coalescer) leaves with less than a full batch / panel
-  // the same for exact vector searches (nrtgpu_knn_exact_coalesced, vectors.cpp)
-  std::mutex kco_mu;
-  std::vector<struct KnnCoRequest*> kco_pending;
-  struct KnnCoRequest* kco_leader = nullptr;   // the caller that will run the next panel
-  int kco_inflight = 0;                        // panels executing right now (at most two)
-  int kco_last_panel = 0;                      // members of the panel formed last (a leader that finds the device free waits for that cohort)
   // MyIndexSearcher.SlicingParams of the searcher this context serves (nrtgpu_set_slicing)
   std::atomic<int32_t> slice_max_docs{250000}, slice_max_segments{5}, virtual_shards{1};
   std::unique_ptr<nrtgpu::rt::WorkPool> pool;   // helper threads of the host side (planning, unpacking results)
@@ -979,7 +969,3 @@ int final_score_run(nrtgpu_ctx* ctx, const HostPlan& hp, const nrtgpu_bm25_query
 
 }  // namespace rt
 }  // namespace nrtgpu
-
-// test hook halves that live in vectors.cpp (nrtgpu_debug_hold_coalescers / nrtgpu_debug_coalescer_pending, search.cpp)
-void nrtgpu_debug_knn_coalescer_wake(nrtgpu_ctx* ctx);
-int nrtgpu_debug_knn_coalescer_pending(nrtgpu_ctx* ctx);

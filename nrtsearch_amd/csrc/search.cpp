@@ -911,31 +911,17 @@ extern "C" int nrtgpu_search_bm25(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs
 }
 
 // ------------------------------------------------------------------------------------------------
-// Request coalescing: concurrent single-query callers (the SEARCH pool's threads) are merged into
-// device batches leader/follower style -- no extra thread.  The first caller to find no lingering
-// leader becomes one: it waits co_linger_us (or until max_batch requests are pending), takes every
-// pending request that searches the same leaves, runs them as one batch and wakes their callers.
-// Later arrivals elect the next leader, so two batches are in flight and planning overlaps kernels.
+// Request coalescing (coalescer.h): concurrent single-query callers are merged into device batches.  Here: what a BM25 request
+// is, which requests travel together, when a leader leaves, and how the batch is run and delivered.
 // ------------------------------------------------------------------------------------------------
-struct CoRequest {
+struct CoRequest : CoQueued {
   const nrtgpu_seg* const* segs;
   const int32_t* doc_bases;
   int32_t n_segs;
   const nrtgpu_bm25_query* q;
   nrtgpu_topdocs* out;
-  int64_t deadline_ns = 0;        // the calling thread's (nrtgpu_set_thread_deadline_ns)
   std::vector<int32_t> slices;    // the calling thread's slice of every leaf (nrtgpu_set_thread_slices; empty: the library slices the leaves itself)
   nrtgpu_diagnostics diag{};      // of the batch the request travelled in
-  int rc = 0;
-  bool done = false;   // results (or the error) are in place
-  bool lead = false;   // promoted: this caller lingers for and runs the next batch
-  std::string err;
-  // Every caller sleeps on its own condition variable AND its own mutex: a finished batch wakes hundreds of
-  // callers, and if they all had to re-acquire the coalescer's lock to leave their wait (and again to submit
-  // their next request) the lock handoffs alone would cost more than the batch's kernels.  done / lead are
-  // written under `m`; the lingering leader is the one waiter that uses `cv` with the coalescer's lock.
-  std::mutex m;
-  std::condition_variable cv;
 };
 
 static bool same_leaves(const CoRequest* a, const CoRequest* b) {
@@ -953,7 +939,7 @@ static bool same_leaves(const CoRequest* a, const CoRequest* b) {
 
 extern "C" int nrtgpu_set_coalescing(nrtgpu_ctx* ctx, int32_t linger_us) {
   if (!ctx || linger_us < 0) return fail(NRTGPU_ERR_INVALID_ARG, "bad coalescing arguments");
-  std::lock_guard<std::mutex> lk(ctx->co_mu);
+  std::lock_guard<std::mutex> lk(ctx->co.mu);
   ctx->co_linger_us = linger_us;
   return NRTGPU_OK;
 }
@@ -963,21 +949,13 @@ extern "C" int nrtgpu_set_coalescing(nrtgpu_ctx* ctx, int32_t linger_us) {
 // a known set of callers and assert what batches they form by construction instead of by the host's speed.
 extern "C" int nrtgpu_debug_hold_coalescers(nrtgpu_ctx* ctx, int32_t hold) {
   if (!ctx) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
-  {
-    std::lock_guard<std::mutex> lk(ctx->co_mu);
-    ctx->co_hold = hold != 0 ? 1 : 0;   // (atomic: the kNN coalescer reads it under its own lock)
-    if (!hold && ctx->co_leader) ctx->co_leader->cv.notify_one();
-  }
-  nrtgpu_debug_knn_coalescer_wake(ctx);
+  ctx->co.set_hold(hold != 0);
+  ctx->kco.set_hold(hold != 0);
   return NRTGPU_OK;
 }
 extern "C" int nrtgpu_debug_coalescer_pending(nrtgpu_ctx* ctx, int32_t which) {
   if (!ctx) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
-  if (which == 0) {
-    std::lock_guard<std::mutex> lk(ctx->co_mu);
-    return (int)ctx->co_pending.size();
-  }
-  return nrtgpu_debug_knn_coalescer_pending(ctx);
+  return which == 0 ? ctx->co.pending_count() : ctx->kco.pending_count();
 }
 #endif
 
@@ -995,32 +973,24 @@ extern "C" int nrtgpu_search_bm25_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* c
     if (segs[si]->ctx != ctx) return fail(NRTGPU_ERR_INVALID_ARG, "segment %d belongs to another context", si);
   }
   NRT_CHECK_DEADLINE("before the request was queued");
-  CoRequest me{segs, doc_bases, n_segs, q, out};
+  CoRequest me{{}, segs, doc_bases, n_segs, q, out};
   me.deadline_ns = g_deadline_ns;
   if ((int32_t)g_thread_slices.size() == n_segs) me.slices = g_thread_slices;   // (a list of another length is ignored by the planner as well)
-  std::vector<CoRequest*> batch;
+  Coalescer& co = ctx->co;
+  constexpr int32_t kCoOverlapMin = 192;
+  const int32_t max_batch = ctx->cfg.max_batch;
+  std::vector<CoQueued*> batch;
   {
-    std::unique_lock<std::mutex> lk(ctx->co_mu);
-    ctx->co_pending.push_back(&me);
-    if (ctx->co_leader) {  // follower: the lingering leader takes this request (or a later one does)
-      // (wake it when the queue is full -- or when, with the device idle, as many callers wait as the last batch held: the cohort
-      //  of a closed loop has come back, lingering longer only adds latency)
-      if ((int32_t)ctx->co_pending.size() >= ctx->cfg.max_batch ||
-          (ctx->co_inflight == 0 && ctx->co_last_batch > 1 && ctx->co_last_batch < 192 && (int32_t)ctx->co_pending.size() >= ctx->co_last_batch))
-        ctx->co_leader->cv.notify_one();
-      lk.unlock();
-      {
-        std::unique_lock<std::mutex> mine(me.m);
-        me.cv.wait(mine, [&] { return me.done || me.lead; });
-      }
-      if (me.done) {
-        if (me.rc != 0) g_last_error = me.err;
-        else g_diag = me.diag;
-        return me.rc;
-      }
-      lk.lock();  // promoted: continue as the leader
-    } else {
-      ctx->co_leader = &me;
+    std::unique_lock<std::mutex> lk;
+    // (a follower wakes the leader when the queue is full -- or when, with the device idle, as many callers wait as the last batch
+    //  held: the cohort of a closed loop has come back, lingering longer only adds latency)
+    const bool leads = co.join(lk, &me, [&](int32_t waiting) {
+      return waiting >= max_batch || (co.inflight == 0 && co.last_batch > 1 && co.last_batch < kCoOverlapMin && waiting >= co.last_batch);
+    });
+    if (!leads) {   // travelled in a leader's batch
+      if (me.rc != 0) g_last_error = me.err;
+      else g_diag = me.diag;
+      return me.rc;
     }
     // leader: linger for company, then leave when the device is idle.  While one batch is running a second one
     // leaves only if it is big enough to be worth overlapping (planning and copies of one then hide behind the
@@ -1029,14 +999,11 @@ extern "C" int nrtgpu_search_bm25_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* c
     // falls so steeply with the batch size that one cohort of C callers beats two alternating cohorts of C / 2
     // even with the device idle between its batches (measured: 64 callers 18.2 k -> 23.9 k queries/s).  Never
     // more than two in flight.  Woken by a full queue or a finishing batch.
-    constexpr int32_t kCoOverlapMin = 192;
     // (a caller that was alone last time and is alone now does not linger: a single stream of requests pays
     // no batching latency)
-    const bool alone = ctx->co_last_batch <= 1 && ctx->co_pending.size() == 1 && ctx->co_inflight == 0;
-    const auto deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(alone ? 0 : ctx->co_linger_us);
-    for (;;) {
-      const int32_t waiting = (int32_t)ctx->co_pending.size();
-      if (waiting >= ctx->cfg.max_batch) break;
+    const bool alone = co.last_batch <= 1 && co.pending.size() == 1 && co.inflight == 0;
+    co.leader_wait(lk, &me, alone ? 0 : ctx->co_linger_us, [&](int32_t waiting, bool late) {
+      if (waiting >= max_batch) return CoWait::leave;
       // The cohort is back: with nothing in flight, as many callers wait as the last batch held -- callers in a closed loop return
       // together, within tens of microseconds of their batch's end -- so the batch leaves now instead of at the linger's end (the
       // linger stays the bound for arrivals that are no cohort).  NRTGPU_CO_COHORT=0 (development build): the linger alone, A/B.
@@ -1045,55 +1012,28 @@ extern "C" int nrtgpu_search_bm25_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* c
       // 82 k -> 98 k, 0.77 -> 0.64 ms; C2: 8 callers 19.5 k -> 38.2 k, 64 callers 128 k -> 174 k.  Cohorts of kCoOverlapMin and more
       // are the two-batches-in-flight regime below, which the rule leaves alone (512 callers: 306 k before, 298 k with the rule
       // applied to them too).
-      if (cohort_rule && !ctx->co_hold && ctx->co_inflight == 0 && ctx->co_last_batch > 1 && ctx->co_last_batch < kCoOverlapMin &&
-          waiting >= ctx->co_last_batch)
-        break;
-      const bool late = std::chrono::steady_clock::now() >= deadline;
-      if (late && !ctx->co_hold && (ctx->co_inflight == 0 ||
-                   (ctx->co_inflight == 1 && (waiting >= 2 * ctx->co_inflight_queries || waiting >= kCoOverlapMin)))) break;
-      if (late) me.cv.wait(lk);
-      else me.cv.wait_until(lk, deadline);
-    }
+      if (cohort_rule && !co.hold && co.inflight == 0 && co.last_batch > 1 && co.last_batch < kCoOverlapMin && waiting >= co.last_batch)
+        return CoWait::leave;
+      const bool go = late && !co.hold &&
+                      (co.inflight == 0 || (co.inflight == 1 && (waiting >= 2 * co.inflight_queries || waiting >= kCoOverlapMin)));
+      return go ? CoWait::leave : CoWait::until_linger_end;
+    });
     // take my request and every pending one over the same leaves (up to max_batch).  A big cohort that finds the
     // device idle is cut in two, so that from now on the host work of one half (planning, copies, waking its
     // callers) hides behind the kernels of the other.
-    int32_t cap = ctx->cfg.max_batch;
-    if (ctx->co_inflight == 0 && (int32_t)ctx->co_pending.size() >= 2 * kCoOverlapMin && (int32_t)ctx->co_pending.size() < cap)
-      cap = ((int32_t)ctx->co_pending.size() + 1) / 2;
-    std::vector<CoRequest*> rest, expired;
-    batch.push_back(&me);
-    for (CoRequest* r : ctx->co_pending) {
-      if (r == &me) continue;
-      if (deadline_passed(r->deadline_ns)) expired.push_back(r);   // waited too long: leaves without being searched
-      else if ((int32_t)batch.size() < cap && same_leaves(&me, r)) batch.push_back(r);
-      else rest.push_back(r);
-    }
-    for (CoRequest* r : expired) {
-      std::lock_guard<std::mutex> theirs(r->m);
-      r->rc = NRTGPU_ERR_TIMEOUT;
-      r->err = "deadline passed while the request waited for a batch";
-      r->done = true;
-      r->cv.notify_one();
-    }
-    ctx->co_pending.swap(rest);
-    ctx->co_leader = nullptr;
-    if (!ctx->co_pending.empty()) {  // hand the lead to the oldest request left behind
-      CoRequest* next = ctx->co_pending.front();
-      ctx->co_leader = next;
-      std::lock_guard<std::mutex> theirs(next->m);
-      next->lead = true;
-      next->cv.notify_one();
-    }
-    ctx->co_inflight++;
-    ctx->co_inflight_queries += (int)batch.size();
-    ctx->co_last_batch = (int)batch.size();
+    int32_t cap = max_batch;
+    if (co.inflight == 0 && (int32_t)co.pending.size() >= 2 * kCoOverlapMin && (int32_t)co.pending.size() < cap)
+      cap = ((int32_t)co.pending.size() + 1) / 2;
+    batch = co.form(&me, cap, [&](const CoQueued* r) { return same_leaves(&me, static_cast<const CoRequest*>(r)); }, deadline_passed,
+                    NRTGPU_ERR_TIMEOUT, "deadline passed while the request waited for a batch");
   }
   // run the batch outside the lock
+  auto member = [&](size_t i) { return static_cast<CoRequest*>(batch[i]); };
   std::vector<nrtgpu_bm25_query> qs(batch.size());
   std::vector<nrtgpu_topdocs> outs(batch.size());
   for (size_t i = 0; i < batch.size(); ++i) {
-    qs[i] = *batch[i]->q;
-    outs[i] = *batch[i]->out;
+    qs[i] = *member(i)->q;
+    outs[i] = *member(i)->out;
   }
   // (a batch of several requests is not failed for the leader's deadline: its mates have not expired -- they were checked when the
   //  batch was formed -- and a batch is a few milliseconds.  A lone request keeps its deadline.)
@@ -1107,13 +1047,11 @@ extern "C" int nrtgpu_search_bm25_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* c
     const nrtgpu_diagnostics first_diag = g_diag;
     for (size_t i = 1; i < batch.size(); ++i) {   // (batch[0] is this caller: it runs the second pass)
       if (again[i]) continue;
-      CoRequest* r = batch[i];
-      std::lock_guard<std::mutex> theirs(r->m);
-      *r->out = outs[i];
-      r->diag = first_diag;
-      r->rc = 0;
-      r->done = true;
-      r->cv.notify_one();
+      CoRequest* r = member(i);
+      Coalescer::finish(r, 0, std::string(), [&] {
+        *r->out = outs[i];
+        r->diag = first_diag;
+      });
       released[i] = 1;
     }
   };
@@ -1133,29 +1071,16 @@ extern "C" int nrtgpu_search_bm25_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* c
     rc = rcs[0];   // batch[0] is this caller
     err = errs[0];
   }
-  for (size_t i = 0; i < batch.size(); ++i) {
-    CoRequest* r = batch[i];
-    if (r == &me) {
-      if (rcs[i] == 0) *out = outs[i];
-      continue;
-    }
+  if (rc == 0) *out = outs[0];
+  for (size_t i = 1; i < batch.size(); ++i) {
     if (released[i]) continue;   // (gone already: its request object may no longer exist)
-    // (notified under the request's own lock: the woken caller cannot return -- and free its request -- before
-    // we are done with it, and it contends with nobody but us)
-    std::lock_guard<std::mutex> theirs(r->m);
-    if (rcs[i] == 0) *r->out = outs[i];
-    r->diag = batch_diag;
-    r->rc = rcs[i];
-    if (rcs[i] != 0) r->err = errs[i];
-    r->done = true;
-    r->cv.notify_one();
+    CoRequest* r = member(i);
+    Coalescer::finish(r, rcs[i], errs[i], [&] {
+      if (rcs[i] == 0) *r->out = outs[i];
+      r->diag = batch_diag;
+    });
   }
-  {
-    std::lock_guard<std::mutex> lk(ctx->co_mu);
-    ctx->co_inflight--;
-    ctx->co_inflight_queries -= (int)batch.size();
-    if (ctx->co_leader) ctx->co_leader->cv.notify_one();  // a lingering leader may be waiting for the device
-  }
+  co.retire(batch.size());
   if (rc != 0) g_last_error = err;
   return rc;
 }

@@ -136,6 +136,15 @@ int nrtgpu::rt::stage_rescore_inputs(const nrtgpu_seg* const* segs, const int32_
   return NRTGPU_OK;
 }
 
+// What the float searches ask of their scalars (knn_impl, and nrtgpu_knn_exact_coalesced before it queues a request); bad_count: the
+// caller's own count (queries, leaves) is out of range -- the same refusal.
+static int knn_check_scalars(bool bad_count, int32_t k, int32_t dim, int32_t sim) {
+  if (bad_count || k <= 0 || dim <= 0 || sim < 0 || sim > 3) return fail(NRTGPU_ERR_INVALID_ARG, "bad knn arguments");
+  if (k > NRTGPU_MAX_K) return fail(NRTGPU_ERR_UNSUPPORTED, "k %d > %d", k, NRTGPU_MAX_K);
+  if (dim > 2048) return fail(NRTGPU_ERR_UNSUPPORTED, "vector dimension %d (device path takes <= 2048)", dim);
+  return NRTGPU_OK;
+}
+
 static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
                     int32_t field_id, int32_t sim, const float* queries, int32_t n_queries, int32_t dim,
                     int32_t k, float boost, bool knn_request, int32_t filter_mask, float min_score, nrtgpu_topdocs* out,
@@ -144,9 +153,7 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
   // ext_*: device-resident results instead of `out` (the multi-GPU path): per query k_stride sorted keys, its count, and the live
   // vectors of these leaves as the hit total -- the layout the exchange stage takes
   if (!ctx || !queries || (!out && !ext_keys) || (n_segs > 0 && !segs)) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
-  if (n_queries <= 0 || k <= 0 || dim <= 0 || sim < 0 || sim > 3) return fail(NRTGPU_ERR_INVALID_ARG, "bad knn arguments");
-  if (k > NRTGPU_MAX_K) return fail(NRTGPU_ERR_UNSUPPORTED, "k %d > %d", k, NRTGPU_MAX_K);
-  if (dim > 2048) return fail(NRTGPU_ERR_UNSUPPORTED, "vector dimension %d (device path takes <= 2048)", dim);
+  if (int rc = knn_check_scalars(n_queries <= 0, k, dim, sim)) return rc;
   NRT_CHECK_DEADLINE("before the vector search started");
   HIP_TRY(hipSetDevice(ctx->device));
   for (int si = 0; si < n_segs; ++si)
@@ -523,21 +530,15 @@ extern "C" int nrtgpu_knn_exact(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// Request coalescing for exact vector searches (cf. search.cpp: nrtgpu_search_bm25_coalesced)
+// Request coalescing for exact vector searches (coalescer.h): what a kNN request is and which requests share a panel
 // ------------------------------------------------------------------------------------------------
-struct KnnCoRequest {
+struct KnnCoRequest : CoQueued {
   const nrtgpu_seg* const* segs;
   const int32_t* doc_bases;
   int32_t n_segs, field_id, sim, dim, k;
   float boost;
   const float* query;
   nrtgpu_topdocs* out;
-  int64_t deadline_ns = 0;
-  int rc = 0;
-  bool done = false, lead = false;
-  std::string err;
-  std::mutex m;   // (every caller sleeps on its own mutex + condition variable: no convoy on the coalescer's lock)
-  std::condition_variable cv;
 };
 
 static bool knn_co_compatible(const KnnCoRequest* a, const KnnCoRequest* b) {
@@ -586,23 +587,12 @@ extern "C" int nrtgpu_knn_exact_relation(nrtgpu_ctx* ctx, const nrtgpu_seg* cons
   return 0;
 }
 
-void nrtgpu_debug_knn_coalescer_wake(nrtgpu_ctx* ctx) {
-  std::lock_guard<std::mutex> lk(ctx->kco_mu);
-  if (ctx->kco_leader) ctx->kco_leader->cv.notify_one();
-}
-int nrtgpu_debug_knn_coalescer_pending(nrtgpu_ctx* ctx) {
-  std::lock_guard<std::mutex> lk(ctx->kco_mu);
-  return (int)ctx->kco_pending.size();
-}
-
 extern "C" int nrtgpu_knn_exact_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
                                           int32_t field_id, int32_t sim, const float* query, int32_t dim, int32_t k, float boost,
                                           nrtgpu_topdocs* out) {
   if (!ctx || !query || !out || (n_segs > 0 && !segs)) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
   // (what would fail the panel must fail this request alone)
-  if (k <= 0 || dim <= 0 || sim < 0 || sim > 3 || n_segs < 0) return fail(NRTGPU_ERR_INVALID_ARG, "bad knn arguments");
-  if (k > NRTGPU_MAX_K) return fail(NRTGPU_ERR_UNSUPPORTED, "k %d > %d", k, NRTGPU_MAX_K);
-  if (dim > 2048) return fail(NRTGPU_ERR_UNSUPPORTED, "vector dimension %d (device path takes <= 2048)", dim);
+  if (int rc = knn_check_scalars(n_segs < 0, k, dim, sim)) return rc;
   for (int si = 0; si < n_segs; ++si) {
     if (!segs[si] || !segs[si]->sealed) return fail(NRTGPU_ERR_STATE, "segment %d missing or not sealed", si);
     auto fit = segs[si]->fields.find(field_id);
@@ -610,33 +600,25 @@ extern "C" int nrtgpu_knn_exact_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* con
       return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d has dimension %d, query has %d", si, field_id, fit->second.dim_user, dim);
   }
   NRT_CHECK_DEADLINE("before the request was queued");
-  KnnCoRequest me{segs, doc_bases, n_segs, field_id, sim, dim, k, boost, query, out};
+  KnnCoRequest me{{}, segs, doc_bases, n_segs, field_id, sim, dim, k, boost, query, out};
   me.deadline_ns = g_deadline_ns;
-  std::vector<KnnCoRequest*> batch;
+  Coalescer& co = ctx->kco;
+  std::vector<CoQueued*> batch;
   {
-    std::unique_lock<std::mutex> lk(ctx->kco_mu);
-    ctx->kco_pending.push_back(&me);
-    if (ctx->kco_leader) {   // follower: the leader (or a later one) takes this request
-      if (ctx->kco_pending.size() >= (size_t)kKnnMaxQ ||
-          (ctx->kco_inflight == 0 && ctx->kco_last_panel > 1 && ctx->kco_pending.size() >= (size_t)ctx->kco_last_panel))
-        ctx->kco_leader->cv.notify_one();   // a whole panel waits, or (device free) the last panel's cohort is back
-      lk.unlock();
-      {
-        std::unique_lock<std::mutex> mine(me.m);
-        me.cv.wait(mine, [&] { return me.done || me.lead; });
-      }
-      if (me.done) {
-        if (me.rc != 0) g_last_error = me.err;
-        return me.rc;
-      }
-      lk.lock();   // promoted: continue as the leader
-    } else {
-      ctx->kco_leader = &me;
+    std::unique_lock<std::mutex> lk;
+    // (a follower wakes the leader when a whole panel waits, or -- device free -- when the last panel's cohort is back)
+    const bool leads = co.join(lk, &me, [&](int32_t waiting) {
+      return waiting >= kKnnMaxQ || (co.inflight == 0 && co.last_batch > 1 && waiting >= co.last_batch);
+    });
+    if (!leads) {   // travelled in a leader's panel
+      if (me.rc != 0) g_last_error = me.err;
+      return me.rc;
     }
     // leader: leave at once when the device is free; else when the running panel finishes, or -- as a second panel in flight,
     // whose launches fill the tails of the first one's -- as soon as a whole panel is waiting
-    // (NO linger: a caller that finds the device free runs alone -- company comes from the callers that arrive while a panel is
-    //  running.  co_hold: the test hook of nrtgpu_debug_hold_coalescers.)
+    // (NO linger for company: a caller that finds the device free runs alone -- company comes from the callers that arrive while a
+    //  panel is running.  The clock handed to leader_wait bounds the cohort wait below and nothing else: while a panel is in flight,
+    //  or under hold, the leader sleeps until it is woken.  hold: the test hook of nrtgpu_debug_hold_coalescers.)
     // The cohort of a closed loop: the members of a panel come back within tens of microseconds of each other, and the first one
     // back used to find the device free and leave alone -- the others then waited a whole pass (2.7 ms at C4) for theirs: 8
     // callers ran at 1.8 k queries/s with p50 5.5 ms where one panel of 8 per pass gives 2.9 k at 2.8 ms.  So a leader that finds
@@ -644,56 +626,27 @@ extern "C" int nrtgpu_knn_exact_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* con
     // stream of callers (last panel 1) never waits.  NRTGPU_KCO_COHORT=0 (development build): leave at once, A/B.
     static const bool cohort_rule = dev_env_int("NRTGPU_KCO_COHORT", 1) != 0;
     constexpr int kKnnCohortLingerUs = 150;
-    const auto cohort_deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(kKnnCohortLingerUs);
-    for (;;) {
-      const size_t waiting = ctx->kco_pending.size();
-      if ((ctx->kco_inflight == 1 || ctx->co_hold) && waiting >= (size_t)kKnnMaxQ) break;
-      if (ctx->kco_inflight == 0 && !ctx->co_hold) {
-        const bool cohort_due = cohort_rule && ctx->kco_last_panel > 1 && waiting < (size_t)std::min(ctx->kco_last_panel, kKnnMaxQ) &&
-                                std::chrono::steady_clock::now() < cohort_deadline;
-        if (!cohort_due) break;
-        me.cv.wait_until(lk, cohort_deadline);
-        continue;
-      }
-      me.cv.wait(lk);
-    }
-    std::vector<KnnCoRequest*> rest, expired;
-    batch.push_back(&me);
-    for (KnnCoRequest* r : ctx->kco_pending) {
-      if (r == &me) continue;
-      if (deadline_passed(r->deadline_ns)) expired.push_back(r);
-      else if (batch.size() < (size_t)kKnnMaxQ && knn_co_compatible(&me, r)) batch.push_back(r);
-      else rest.push_back(r);
-    }
-    for (KnnCoRequest* r : expired) {
-      std::lock_guard<std::mutex> theirs(r->m);
-      r->rc = NRTGPU_ERR_TIMEOUT;
-      r->err = "deadline passed while the request waited for a panel";
-      r->done = true;
-      r->cv.notify_one();
-    }
-    ctx->kco_pending.swap(rest);
-    ctx->kco_leader = nullptr;
-    if (!ctx->kco_pending.empty()) {   // hand the lead to the oldest request left behind
-      KnnCoRequest* next = ctx->kco_pending.front();
-      ctx->kco_leader = next;
-      std::lock_guard<std::mutex> theirs(next->m);
-      next->lead = true;
-      next->cv.notify_one();
-    }
-    ctx->kco_inflight++;
-    ctx->kco_last_panel = (int)batch.size();
+    co.leader_wait(lk, &me, kKnnCohortLingerUs, [&](int32_t waiting, bool late) {
+      if ((co.inflight == 1 || co.hold) && waiting >= kKnnMaxQ) return CoWait::leave;
+      if (co.inflight != 0 || co.hold) return CoWait::until_woken;   // (for the running panel's end, a whole panel, the release)
+      const bool cohort_due = cohort_rule && co.last_batch > 1 && waiting < std::min(co.last_batch, kKnnMaxQ) && !late;
+      return cohort_due ? CoWait::until_linger_end : CoWait::leave;
+    });
+    batch = co.form(&me, kKnnMaxQ, [&](const CoQueued* r) { return knn_co_compatible(&me, static_cast<const KnnCoRequest*>(r)); },
+                    deadline_passed, NRTGPU_ERR_TIMEOUT, "deadline passed while the request waited for a panel");
   }
   // the panel, outside the lock: the members' queries side by side, the largest k; every member's buffers take its own k
+  auto member = [&](size_t i) { return static_cast<KnnCoRequest*>(batch[i]); };
   int32_t kmax = 0;
-  for (KnnCoRequest* r : batch) kmax = std::max(kmax, r->k);
   std::vector<float> qs(batch.size() * (size_t)dim);
   std::vector<nrtgpu_topdocs> outs(batch.size());
   for (size_t i = 0; i < batch.size(); ++i) {
-    memcpy(qs.data() + i * (size_t)dim, batch[i]->query, (size_t)dim * 4);
-    outs[i] = *batch[i]->out;
-    const int32_t cap = outs[i].capacity > 0 ? outs[i].capacity : batch[i]->k;
-    outs[i].capacity = std::min(cap, batch[i]->k);
+    const KnnCoRequest* r = member(i);
+    kmax = std::max(kmax, r->k);
+    memcpy(qs.data() + i * (size_t)dim, r->query, (size_t)dim * 4);
+    outs[i] = *r->out;
+    const int32_t cap = outs[i].capacity > 0 ? outs[i].capacity : r->k;
+    outs[i].capacity = std::min(cap, r->k);
   }
   int rc;
   {
@@ -703,24 +656,17 @@ extern "C" int nrtgpu_knn_exact_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* con
   }
   const std::string err = rc ? g_last_error : std::string();
   for (size_t i = 0; i < batch.size(); ++i) {
-    KnnCoRequest* r = batch[i];
-    if (rc == 0) {
+    KnnCoRequest* r = member(i);
+    auto copy_back = [&] {   // (the caller's own capacity stays)
+      if (rc != 0) return;
       const int32_t cap = r->out->capacity;
       *r->out = outs[i];
       r->out->capacity = cap;
-    }
-    if (r == &me) continue;
-    std::lock_guard<std::mutex> theirs(r->m);   // (the woken caller cannot return -- and free its request -- before we are done with it)
-    r->rc = rc;
-    if (rc != 0) r->err = err;
-    r->done = true;
-    r->cv.notify_one();
+    };
+    if (r == &me) copy_back();
+    else Coalescer::finish(r, rc, err, copy_back);
   }
-  {
-    std::lock_guard<std::mutex> lk(ctx->kco_mu);
-    ctx->kco_inflight--;
-    if (ctx->kco_leader) ctx->kco_leader->cv.notify_one();   // a leader may be waiting for the device
-  }
+  co.retire(batch.size());
   if (rc != 0) g_last_error = err;
   return rc;
 }
