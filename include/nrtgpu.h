@@ -630,6 +630,8 @@ int  nrtgpu_search_hybrid_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, 
  *                           min_should_match > 1 or min_competitive_score != 0; a batch whose queries do not all pass the
  *                           fixed-point analysis, or NRTGPU_FLAG_NO_FIXED_POINT (fixed-point sums are exact in any order, which
  *                           the kernel relies on); a context with NRTGPU_FLAG_PACKED_POSTINGS
+ * The flat shapes refused here -- a DisjunctionMaxQuery, MUST clauses, min_should_match > 1 -- run as one group each under
+ * nrtgpu_search_function_score_multi_match_batch (below).
  * Accounting: nrtgpu_last_diagnostics reports the call's items as items_scan (items_maxscore = 0); nrtgpu_get_stats counts the
  * launch under scan_launches, scan_items, scan_postings, scan_ms and fixed_point_launches.
  * Out of scope: script and decay functions (they read doc values); a match-all inner query; the coalesced, device-resident,
@@ -698,8 +700,8 @@ int  nrtgpu_function_score_value(const nrtgpu_function_score* fs, uint32_t match
  *                           NRTGPU_MAX_TERMS clauses
  * Accounting: as a function-score call (items_scan; scan_launches, scan_items, scan_postings, scan_ms, fixed_point_launches).
  * Out of scope: pruning (Lucene runs WAND here and reports a lower bound); MUST next to SHOULD inside a group; phrase-prefix,
- * fuzzy and synonym clauses; deeper nesting; a function score over these shapes; the coalesced, device-resident, hybrid and
- * nrtgpu_dist_* forms; packed postings; the Java shim, which does not bind this yet.
+ * fuzzy and synonym clauses; deeper nesting; the coalesced, device-resident, hybrid and nrtgpu_dist_* forms; packed postings;
+ * the Java shim, which does not bind this yet.  (A function score over these shapes: the next section.)
  * --------------------------------------------------------------------------------------------- */
 #define NRTGPU_MAX_GROUPS 8
 #define NRTGPU_GROUPS_SUM_OF_MAX 0   /* BooleanQuery over DisjunctionMaxQuery groups: cross_fields */
@@ -726,6 +728,50 @@ int  nrtgpu_multi_match_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs
  * A doc that is no hit scores 0 when no group matches it, else what the groups that do match give. */
 int  nrtgpu_multi_match_value(const nrtgpu_clause_groups* g, int32_t n_terms, const int32_t* occur, int32_t min_should_match,
                               const float* clause_scores, uint32_t matched, float* out_score, int32_t* out_is_hit);
+
+/* ---------------------------------------------------------------------------------------------
+ * A function score over a multi-match query: MultiFunctionScoreQuery wraps ANY inner Query (MultiFunctionScoreQuery.java:53,
+ * :169-173, inner weight under ScoreMode.COMPLETE), and the text search a deployment sends is a multiMatchQuery wrapped in weight
+ * functions.  The two sections above composed: queries[i] and groups[i] are a multi-match query, functions[i] wraps it.  One
+ * kernel (csrc/multimatch.hip: bm25_multi_match_function_score_kernel) runs the clauses exhaustively; nothing is pruned.  Per doc:
+ *   (inner, inner_hit)   the multi-match rule above, unchanged.  A doc with !inner_hit is no hit at all -- not counted in
+ *                        total_hits, not in the per-slice relation counts -- whatever the functions say
+ *   (final, hit)         the function-score rule above applied to inner, unchanged: function score, boost mode, the min_score
+ *                        test.  n_functions == 0: final = inner, and the min_score test still applies
+ * queries[i] means what it means in nrtgpu_search_multi_match_batch: k, total_hits_threshold, has_after / after_* (searchAfter
+ * compares FINAL scores), filter_mask / must_not_mask / more_*, liveDocs, slicing, thread slices, deadlines.  total_hits is always
+ * exact; total_hits_is_lower_bound follows the per-slice rule of the exhaustive route.
+ * The grouping also expresses the flat shapes nrtgpu_search_function_score_batch refuses: a conjunction is one all-MUST
+ * MAX_OF_SUM group, minimumNumberShouldMatch is one SHOULD MAX_OF_SUM group with a minimum, a flat DisjunctionMaxQuery with a
+ * tie breaker is one SUM_OF_MAX group.
+ * Refusals, each with a reason in nrtgpu_last_error, checked in this order:
+ *   1. everything nrtgpu_search_multi_match_batch refuses of (queries[i], groups[i]), with its status, min_competitive_score != 0
+ *      included
+ *   2. everything nrtgpu_search_function_score_batch refuses of functions[i] alone, with its status (counts, modes, min_score,
+ *      weights that are NaN, infinite, 0 or negative)
+ *   3. NRTGPU_ERR_UNSUPPORTED  a context with NRTGPU_FLAG_PACKED_POSTINGS or NRTGPU_FLAG_NO_FIXED_POINT
+ *   4. NRTGPU_ERR_UNSUPPORTED  a function mask that is not resident on a leaf of the call
+ *   5. NRTGPU_ERR_UNSUPPORTED  what the planner refuses: a FILTER / MUST_NOT mask that is not resident, more than 4 scored fields,
+ *      a batch whose queries do not all pass the fixed-point analysis
+ * Accounting: as the two calls above (items_scan; scan_launches, scan_items, scan_postings, scan_ms, fixed_point_launches).
+ * Out of scope: script and decay functions; pruning; the coalesced, device-resident, hybrid and nrtgpu_dist_* forms; packed
+ * postings; the Java shim, which does not bind this yet.
+ * --------------------------------------------------------------------------------------------- */
+/* n_queries searches over the same leaves in one device pass; groups[i] structures the clauses of queries[i], functions[i] wraps it */
+int  nrtgpu_search_function_score_multi_match_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                                    const nrtgpu_bm25_query* queries, const nrtgpu_clause_groups* groups,
+                                                    const nrtgpu_function_score* functions, int32_t n_queries, nrtgpu_topdocs* out);
+/* The eligibility test alone, as nrtgpu_query_supported: NRTGPU_OK if the search above would run (q, g, fs) over these leaves, else
+ * the status it would return with the reason in nrtgpu_last_error.  No device work. */
+int  nrtgpu_function_score_multi_match_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query* q,
+                                                 const nrtgpu_clause_groups* g, const nrtgpu_function_score* fs);
+/* The arithmetic above for one doc, exposed for the tests: needs no device; it calls the very functions the kernel compiles.
+ * The first six arguments are nrtgpu_multi_match_value's (matched_clauses: bit t set = clause t matches the doc), then fs and
+ * matched_functions as in nrtgpu_function_score_value (bit i set = the doc is in function i's set).  Validates g and fs (the
+ * refusals above).  A doc the groups reject comes back with the inner score and *out_is_hit = 0. */
+int  nrtgpu_function_score_multi_match_value(const nrtgpu_clause_groups* g, int32_t n_terms, const int32_t* occur, int32_t min_should_match,
+                                             const float* clause_scores, uint32_t matched_clauses, const nrtgpu_function_score* fs,
+                                             uint32_t matched_functions, float* out_score, int32_t* out_is_hit);
 
 /* ---------------------------------------------------------------------------------------------
  * Host-side restatements the Java shim would otherwise take from Lucene objects

@@ -55,6 +55,7 @@ ABI_SYMBOLS = [
     "nrtgpu_rescore_byte_vectors", "nrtgpu_search_hybrid_bytes_batch", "nrtgpu_set_knn_gather",
     "nrtgpu_search_function_score_batch", "nrtgpu_function_score_supported", "nrtgpu_function_score_value",
     "nrtgpu_search_multi_match_batch", "nrtgpu_multi_match_supported", "nrtgpu_multi_match_value",
+    "nrtgpu_search_function_score_multi_match_batch", "nrtgpu_function_score_multi_match_supported", "nrtgpu_function_score_multi_match_value",
 ]
 # what include/nrtgpu_dev.h adds: test hooks and measurement helpers of the development library (libnrtgpu_dev.so) only
 DEV_SYMBOLS = [
@@ -202,6 +203,10 @@ def _open(path: str) -> C.CDLL:
     L.nrtgpu_search_multi_match_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(ClauseGroups), i32, C.POINTER(TopDocs)]
     L.nrtgpu_multi_match_supported.argtypes = [vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(ClauseGroups)]
     L.nrtgpu_multi_match_value.argtypes = [C.POINTER(ClauseGroups), i32, vp, i32, vp, C.c_uint32, vp, vp]
+    L.nrtgpu_search_function_score_multi_match_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(ClauseGroups), C.POINTER(FunctionScore), i32,
+                                                                 C.POINTER(TopDocs)]
+    L.nrtgpu_function_score_multi_match_supported.argtypes = [vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(ClauseGroups), C.POINTER(FunctionScore)]
+    L.nrtgpu_function_score_multi_match_value.argtypes = [C.POINTER(ClauseGroups), i32, vp, i32, vp, C.c_uint32, C.POINTER(FunctionScore), C.c_uint32, vp, vp]
     L.nrtgpu_rescore_vectors.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, f32, vp, vp, i32, C.c_double, C.c_double, i32,
                                          C.POINTER(TopDocs)]
     L.nrtgpu_search_hybrid_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), i32, i32, i32, vp, i32, f32,

@@ -96,9 +96,10 @@ class WeightFunction:
 class FunctionScoreQuery:
     """MultiFunctionScoreQuery with weight functions over a BM25 disjunction (S/query/multifunction/MultiFunctionScoreQuery.java):
     score_mode "multiply" / "sum" combines the matching functions' weights, boost_mode "multiply" / "sum" / "replace" combines
-    that with the inner score; min_score / min_excluded drop docs whose final score fails the test."""
+    that with the inner score; min_score / min_excluded drop docs whose final score fails the test.
+    `inner` may also be a MultiMatchQuery: GpuIndexSearcher.search_function_score_multi_match_batch runs that form."""
 
-    inner: Query
+    inner: Union[Query, "MultiMatchQuery"]
     functions: Tuple[WeightFunction, ...] = ()
     score_mode: str = "multiply"
     boost_mode: str = "multiply"
@@ -793,6 +794,47 @@ class GpuIndexSearcher:
         """The eligibility predicate alone (nrtgpu_multi_match_supported)."""
         m, gs = self._marshal_multi_match([query], [manager])
         rc = _lib.load().nrtgpu_multi_match_supported(self.ctx._h, self._segs, len(self.leaves), m.queries, gs)
+        if rc == _lib.NRTGPU_OK:
+            return True
+        if rc == _lib.NRTGPU_ERR_UNSUPPORTED:
+            return False
+        _lib.check(rc)
+        return False
+
+    def _marshal_function_score_multi_match(self, queries: Sequence[FunctionScoreQuery], managers: Sequence[TopScoreDocCollectorManager]):
+        """(nrtgpu_bm25_query array holder, nrtgpu_clause_groups array, nrtgpu_function_score array) of function scores whose
+        inner query is a MultiMatchQuery."""
+        for query in queries:
+            if not isinstance(query.inner, MultiMatchQuery):
+                raise UnsupportedQuery("the inner query is not a MultiMatchQuery (search_function_score_batch takes flat inner queries)")
+        m, gs = self._marshal_multi_match([q.inner for q in queries], managers)
+        return m, gs, self._marshal_function_scores(queries, m)
+
+    def search_function_score_multi_match_batch(self, queries: Sequence[FunctionScoreQuery],
+                                                managers: Sequence[TopScoreDocCollectorManager]) -> List[TopDocs]:
+        """MultiFunctionScoreQuery over MultiMatchQuery searches (nrtgpu_search_function_score_multi_match_batch): every live doc
+        that is a hit of the inner query and passes the min_score test is scored, total_hits is exact."""
+        n = len(queries)
+        m, gs, fs = self._marshal_function_score_multi_match(queries, managers)
+        outs = (_lib.TopDocs * n)()
+        bufs = []
+        for qi, mgr in enumerate(managers):
+            cap = max(int(mgr.num_hits), 1)
+            d = np.zeros(cap, dtype=np.int32)
+            s = np.zeros(cap, dtype=np.float32)
+            bufs.append((d, s))
+            outs[qi].capacity = cap
+            outs[qi].docs = d.ctypes.data_as(C.POINTER(C.c_int32))
+            outs[qi].scores = s.ctypes.data_as(C.POINTER(C.c_float))
+        _lib.check(_lib.load().nrtgpu_search_function_score_multi_match_batch(self.ctx._h, self._segs, self._bases, len(self.leaves), m.queries, gs, fs,
+                                                                              n, outs))
+        return [TopDocs(bufs[qi][0][: outs[qi].n_hits].copy(), bufs[qi][1][: outs[qi].n_hits].copy(), int(outs[qi].total_hits),
+                        bool(outs[qi].total_hits_is_lower_bound)) for qi in range(n)]
+
+    def function_score_multi_match_supported(self, query: FunctionScoreQuery, manager: TopScoreDocCollectorManager) -> bool:
+        """The eligibility predicate alone (nrtgpu_function_score_multi_match_supported)."""
+        m, gs, fs = self._marshal_function_score_multi_match([query], [manager])
+        rc = _lib.load().nrtgpu_function_score_multi_match_supported(self.ctx._h, self._segs, len(self.leaves), m.queries, gs, fs)
         if rc == _lib.NRTGPU_OK:
             return True
         if rc == _lib.NRTGPU_ERR_UNSUPPORTED:

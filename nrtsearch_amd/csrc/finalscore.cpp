@@ -1,5 +1,5 @@
-// finalscore.cpp -- the host path the two final-score routes share (funcscore.cpp: function-score queries, multimatch.cpp:
-// multi-match queries): their entry checks and refusals, the exhaustive plan, and everything from "the plan and the route's
+// finalscore.cpp -- the host path the final-score routes share (funcscore.cpp: function-score queries, multimatch.cpp:
+// multi-match queries, funcscore_multimatch.cpp: the one around the other): their entry checks and refusals, the exhaustive plan, and everything from "the plan and the route's
 // records exist" to "out[], the diagnostics and the statistics are filled".  On the device: the existing plan expansion, then the
 // route's scorer (finalscore.hiph) over all items, then the existing merge and per-slice relation.
 #include "runtime_internal.h"

@@ -5,8 +5,11 @@
 // from the plan to the caller's pages is finalscore.cpp's.
 #include "runtime_internal.h"
 
-// the record the kernel and nrtgpu_function_score_value read, from the caller's struct; refusals by the header's table
-static int function_record(const nrtgpu_function_score& fs, int qi, DFuncQuery* out) {
+namespace nrtgpu {
+namespace rt {
+
+// the record the kernels and nrtgpu_function_score_value read, from the caller's struct; refusals by the header's table
+int function_record(const nrtgpu_function_score& fs, int qi, DFuncQuery* out) {
   if (fs.n_functions < 0 || fs.n_functions > NRTGPU_MAX_FUNCTIONS)
     return fail(NRTGPU_ERR_INVALID_ARG, "query %d: n_functions %d outside 0..%d", qi, fs.n_functions, NRTGPU_MAX_FUNCTIONS);
   if (fs.n_functions > 0 && !fs.functions) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: functions is NULL", qi);
@@ -32,6 +35,20 @@ static int function_record(const nrtgpu_function_score& fs, int qi, DFuncQuery* 
   if (out) *out = r;
   return NRTGPU_OK;
 }
+
+int function_masks_resident(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_function_score& fs, int qi) {
+  for (int i = 0; i < fs.n_functions; ++i) {
+    const int32_t id = fs.functions[i].filter_mask;
+    if (id == 0) continue;
+    for (int si = 0; si < n_segs; ++si)
+      if (segs[si]->masks.find(id) == segs[si]->masks.end())
+        return fail(NRTGPU_ERR_UNSUPPORTED, "query %d function %d: mask %d is not resident on segment %d", qi, i, id, si);
+  }
+  return NRTGPU_OK;
+}
+
+}  // namespace rt
+}  // namespace nrtgpu
 
 extern "C" int nrtgpu_function_score_value(const nrtgpu_function_score* fs, uint32_t matched, float inner, float* out_score, int32_t* out_is_hit) {
   if (!fs || !out_score || !out_is_hit) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
@@ -60,13 +77,7 @@ static int check_call(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_
       if (q.terms[t].occur != 0) return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: a function score over MUST clauses", qi);
     if (q.min_should_match > 1) return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: a function score over minimumNumberShouldMatch %d", qi, q.min_should_match);
     if (q.min_competitive_score != 0.0f) return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: a function score with a min_competitive_score", qi);
-    for (int i = 0; i < functions[qi].n_functions; ++i) {
-      const int32_t id = functions[qi].functions[i].filter_mask;
-      if (id == 0) continue;
-      for (int si = 0; si < n_segs; ++si)
-        if (segs[si]->masks.find(id) == segs[si]->masks.end())
-          return fail(NRTGPU_ERR_UNSUPPORTED, "query %d function %d: mask %d is not resident on segment %d", qi, i, id, si);
-    }
+    if (int rc = function_masks_resident(segs, n_segs, functions[qi], qi)) return rc;
   }
   return NRTGPU_OK;
 }
@@ -80,9 +91,12 @@ extern "C" int nrtgpu_function_score_supported(nrtgpu_ctx* ctx, const nrtgpu_seg
   return final_score_plan(ctx, segs, nullptr, n_segs, q, 1, "function-score", hp);
 }
 
+namespace nrtgpu {
+namespace rt {
+
 // The doc sets of every function on every part's leaf.  A part names its (query, leaf) pair by its first DTerm (HostPlan.qs_begin).
-static int function_masks(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_function_score* functions, const HostPlan& hp,
-                          std::vector<DFuncMasks>* out) {
+int function_masks(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_function_score* functions, const HostPlan& hp,
+                   std::vector<DFuncMasks>* out) {
   out->assign(hp.parts.size(), DFuncMasks{});
   std::map<std::pair<int32_t, int32_t>, const uint64_t*> sets;   // (leaf, mask id) -> liveDocs & mask, resident
   for (const DItem& it : hp.items) {
@@ -111,6 +125,9 @@ static int function_masks(const nrtgpu_seg* const* segs, int32_t n_segs, const n
   }
   return NRTGPU_OK;
 }
+
+}  // namespace rt
+}  // namespace nrtgpu
 
 extern "C" int nrtgpu_search_function_score_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
                                                   const nrtgpu_bm25_query* queries, const nrtgpu_function_score* functions,

@@ -7,9 +7,12 @@
 // pages is finalscore.cpp's.
 #include "runtime_internal.h"
 
+namespace nrtgpu {
+namespace rt {
+
 // the record the kernel and nrtgpu_multi_match_value read, from the caller's struct; refusals by the header's table.
 // occur: the clauses' nrtgpu_term.occur, or nullptr = all SHOULD
-static int group_record(const nrtgpu_clause_groups& g, int qi, int32_t n_terms, const int32_t* occur, int32_t min_should_match, DGroupQuery* out) {
+int group_record(const nrtgpu_clause_groups& g, int qi, int32_t n_terms, const int32_t* occur, int32_t min_should_match, DGroupQuery* out) {
   if (g.shape != NRTGPU_GROUPS_SUM_OF_MAX && g.shape != NRTGPU_GROUPS_MAX_OF_SUM)
     return fail(NRTGPU_ERR_INVALID_ARG, "query %d: shape %d outside 0..1", qi, g.shape);
   if (g.n_groups < 1 || g.n_groups > NRTGPU_MAX_GROUPS)
@@ -60,6 +63,9 @@ static int group_record(const nrtgpu_clause_groups& g, int qi, int32_t n_terms, 
   return NRTGPU_OK;
 }
 
+}  // namespace rt
+}  // namespace nrtgpu
+
 extern "C" int nrtgpu_multi_match_value(const nrtgpu_clause_groups* g, int32_t n_terms, const int32_t* occur, int32_t min_should_match,
                                         const float* clause_scores, uint32_t matched, float* out_score, int32_t* out_is_hit) {
   if (!g || !clause_scores || !out_score || !out_is_hit) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
@@ -86,10 +92,13 @@ extern "C" int nrtgpu_multi_match_value(const nrtgpu_clause_groups* g, int32_t n
   return NRTGPU_OK;
 }
 
-// What the route refuses of a call before anything is planned; the records and the reduced copies of the queries (plain SHOULD
-// disjunctions: what is planned) on the way.
-static int check_call(nrtgpu_ctx* ctx, const nrtgpu_bm25_query* queries, const nrtgpu_clause_groups* groups, int32_t n_queries,
-                      std::vector<DGroupQuery>* records, std::vector<nrtgpu_bm25_query>* flat, std::vector<std::vector<nrtgpu_term>>* flat_terms) {
+namespace nrtgpu {
+namespace rt {
+
+// What the route refuses of the queries of a call before anything is planned; the records and the reduced copies of the queries
+// (plain SHOULD disjunctions: what is planned) on the way.
+int multi_match_check_queries(const nrtgpu_bm25_query* queries, const nrtgpu_clause_groups* groups, int32_t n_queries, std::vector<DGroupQuery>* records,
+                              std::vector<nrtgpu_bm25_query>* flat, std::vector<std::vector<nrtgpu_term>>* flat_terms) {
   for (int qi = 0; qi < n_queries; ++qi) {
     const nrtgpu_bm25_query& q = queries[qi];
     if (q.disjunction_max != 0 || q.tie_breaker != 0.0f)
@@ -115,14 +124,14 @@ static int check_call(nrtgpu_ctx* ctx, const nrtgpu_bm25_query* queries, const n
     flat->push_back(f);
   }
   for (int qi = 0; qi < n_queries; ++qi) (*flat)[(size_t)qi].terms = (*flat_terms)[(size_t)qi].data();   // (the vectors have settled)
-  return final_score_check_flags(ctx, "multi-match");
+  return NRTGPU_OK;
 }
 
 // The plan of the reduced queries, and every clause's group into its DQTerm.  hp.qterms holds one record per clause WHOSE TERM SOME
 // LEAF HOLDS, in clause order (planner.cpp: resolve_queries skips a clause of total 0): the same test on the same cache entry here.
-static int plan_call(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, const nrtgpu_bm25_query* flat,
-                     const nrtgpu_clause_groups* groups, int32_t n_queries, HostPlan& hp) {
-  if (int rc = final_score_plan(ctx, segs, doc_bases, n_segs, flat, n_queries, "multi-match", hp)) return rc;
+int multi_match_plan(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, const nrtgpu_bm25_query* flat,
+                     const nrtgpu_clause_groups* groups, int32_t n_queries, const char* route, HostPlan& hp) {
+  if (int rc = final_score_plan(ctx, segs, doc_bases, n_segs, flat, n_queries, route, hp)) return rc;
   for (int qi = 0; qi < n_queries; ++qi) {
     const DQExpand& qx = hp.qexpand[(size_t)qi];
     uint32_t at = 0;
@@ -130,13 +139,23 @@ static int plan_call(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32
       const TermLeaves* tl = hp.lsc ? hp.lsc->get(segs, n_segs, flat[qi].terms[t].field_id, flat[qi].terms[t].term_hash) : nullptr;
       if (!tl || tl->total <= 0) continue;
       if (at >= qx.n_terms || (size_t)qx.term_begin + at >= hp.qterms.size() || hp.qterms[(size_t)qx.term_begin + at].table != tl->d_table)
-        return fail(NRTGPU_ERR_STATE, "multi-match: the plan of query %d does not hold its clauses in clause order", qi);
+        return fail(NRTGPU_ERR_STATE, "%s: the plan of query %d does not hold its clauses in clause order", route, qi);
       hp.qterms[(size_t)qx.term_begin + at].tab_slot |= ((uint32_t)groups[qi].group_of_term[t] & kTabSlotGroupMask) << kTabSlotGroupShift;
       ++at;
     }
-    if (at != qx.n_terms) return fail(NRTGPU_ERR_STATE, "multi-match: the plan of query %d holds %u clauses, %u expected", qi, qx.n_terms, at);
+    if (at != qx.n_terms) return fail(NRTGPU_ERR_STATE, "%s: the plan of query %d holds %u clauses, %u expected", route, qi, qx.n_terms, at);
   }
   return NRTGPU_OK;
+}
+
+}  // namespace rt
+}  // namespace nrtgpu
+
+// the queries' refusals, then the context's flags
+static int check_call(nrtgpu_ctx* ctx, const nrtgpu_bm25_query* queries, const nrtgpu_clause_groups* groups, int32_t n_queries,
+                      std::vector<DGroupQuery>* records, std::vector<nrtgpu_bm25_query>* flat, std::vector<std::vector<nrtgpu_term>>* flat_terms) {
+  if (int rc = multi_match_check_queries(queries, groups, n_queries, records, flat, flat_terms)) return rc;
+  return final_score_check_flags(ctx, "multi-match");
 }
 
 extern "C" int nrtgpu_multi_match_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query* q,
@@ -147,7 +166,7 @@ extern "C" int nrtgpu_multi_match_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* c
   std::vector<std::vector<nrtgpu_term>> flat_terms;
   if (int rc = check_call(ctx, q, g, 1, nullptr, &flat, &flat_terms)) return rc;
   HostPlan hp;   // the planner is the predicate for the clauses, as in nrtgpu_query_supported
-  return plan_call(ctx, segs, nullptr, n_segs, flat.data(), g, 1, hp);
+  return multi_match_plan(ctx, segs, nullptr, n_segs, flat.data(), g, 1, "multi-match", hp);
 }
 
 extern "C" int nrtgpu_search_multi_match_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
@@ -164,7 +183,7 @@ extern "C" int nrtgpu_search_multi_match_batch(nrtgpu_ctx* ctx, const nrtgpu_seg
   flat_terms.reserve((size_t)n_queries);
   if (int rc = check_call(ctx, queries, groups, n_queries, &records, &flat, &flat_terms)) return rc;
   HostPlan hp;
-  if (int rc = plan_call(ctx, segs, doc_bases, n_segs, flat.data(), groups, n_queries, hp)) return rc;
+  if (int rc = multi_match_plan(ctx, segs, doc_bases, n_segs, flat.data(), groups, n_queries, "multi-match", hp)) return rc;
   const PlanBytes extras[1] = {{records.data(), records.size() * sizeof(DGroupQuery)}};
   return final_score_run(ctx, hp, queries, n_queries, out, t0, extras, 1, [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
     launch_bm25_multi_match(st, a, (const DGroupQuery*)d_extra[0]);

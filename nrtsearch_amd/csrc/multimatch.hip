@@ -4,6 +4,9 @@
 //   bm25_multi_match_kernel   postings traversal + BM25Similarity GROUP BY GROUP: per doc the group's score from the group's
 //                             clauses (plan.h: multi_match_group), folded into the doc's outer state (multi_match_fold); after
 //                             the last group the final score and the hit test (multi_match_value), the item's top-k of FINAL scores
+//   bm25_multi_match_function_score_kernel
+//                             the same body (multi_match_body<true>) for a function score over such a query: behind multi_match_value
+//                             the final sweep puts function_score_value over the doc's function sets, as bm25_function_score_kernel's
 //
 // Like bm25_function_score_kernel (funcscore.hip) nothing is pruned and theta bounds final keys only; the plan records are the
 // scan's (DItem / DPart / DTerm / DQuery over the clauses as ONE SHOULD disjunction, so the parts cover every doc any clause
@@ -36,12 +39,17 @@ static_assert(sizeof(MmSmem) <= 160 * 1024, "the workgroup owns one CU's 160 KiB
 
 constexpr uint64_t kMmSumMask = (1ull << kMsmCountShift) - 1ull;
 
-__global__ __launch_bounds__(kMmThreads, kMmWaves / 4)
-void bm25_multi_match_kernel(const DItem* __restrict__ items, const DPart* __restrict__ parts, const DTerm* __restrict__ terms,
-                             const DQuery* __restrict__ queries, const float* __restrict__ caches,
-                             const DGroupQuery* __restrict__ gqueries, unsigned long long* __restrict__ theta_g,
-                             uint32_t* __restrict__ slice_sum, uint64_t* __restrict__ item_keys, uint32_t* __restrict__ item_counts,
-                             uint64_t* __restrict__ item_hits, uint32_t k_stride) {
+// The body of both kernels.  FUNCTIONS: the final sweep also reads the doc's function sets and puts function_score_value behind
+// multi_match_value (fqueries: one DFuncQuery per query, fmasks: one DFuncMasks per part); without it neither pointer is read and
+// the instantiation is bm25_multi_match_kernel as it was written out before.
+template <bool FUNCTIONS>
+__device__ __forceinline__ void multi_match_body(const DItem* __restrict__ items, const DPart* __restrict__ parts,
+                                                 const DTerm* __restrict__ terms, const DQuery* __restrict__ queries,
+                                                 const float* __restrict__ caches, const DGroupQuery* __restrict__ gqueries,
+                                                 const DFuncQuery* __restrict__ fqueries, const DFuncMasks* __restrict__ fmasks,
+                                                 unsigned long long* __restrict__ theta_g, uint32_t* __restrict__ slice_sum,
+                                                 uint64_t* __restrict__ item_keys, uint32_t* __restrict__ item_counts,
+                                                 uint64_t* __restrict__ item_hits, uint32_t k_stride) {
   __shared__ MmSmem s;
   const uint32_t tid = threadIdx.x;
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)), lane = tid & 63u;
@@ -55,6 +63,17 @@ void bm25_multi_match_kernel(const DItem* __restrict__ items, const DPart* __res
   const DGroupQuery* const gq = gqueries + query;
   const uint32_t n_groups = min(gq->n_groups, (uint32_t)kMaxGroups);
   const bool want_best = gq->shape == kGroupsSumOfMax;
+  // The function record in LDS (this instantiation only): function_score_value reads it per doc slot inside the unrolled sweep,
+  // and out of global memory every one of those reads was a dependent scalar round trip of its own.
+  const DFuncQuery* fq = nullptr;
+  uint32_t n_functions = 0u;
+  if constexpr (FUNCTIONS) {
+    __shared__ DFuncQuery s_fq;
+    static_assert(sizeof(DFuncQuery) == 16 * sizeof(uint32_t), "copied below as 16 words");
+    if (tid < 16u) ((uint32_t*)&s_fq)[tid] = ((const uint32_t*)(fqueries + query))[tid];   // (final_prologue ends with the barrier)
+    fq = &s_fq;
+    n_functions = min((uint32_t)fqueries[query].n_functions, (uint32_t)kMaxFunctions);
+  }
   const bool multi_item = q->n_items > 1;
   unsigned long long* const my_theta_g = theta_g + query;
   // searchAfter compares FINAL scores: a hit at or above after_key was collected on an earlier page (it still counts)
@@ -87,6 +106,25 @@ void bm25_multi_match_kernel(const DItem* __restrict__ items, const DPart* __res
       if (lane < n_terms) {
         my_group = (part_terms[lane].tab_slot >> kTabSlotGroupShift) & kTabSlotGroupMask;
         final_clause_range(part_terms + lane, tile, my_lo, my_hi);
+      }
+
+      // The sub-tile's function sets, in flight while the groups are streamed: lane l holds word (l & 15) of the sub-tile's
+      // 16 mask words of function (l >> 4) in fw0 and of function (l >> 4) + 4 in fw1 (nullptr: every doc); the final sweep
+      // fetches a word from its lane.  One vector load per lane instead of a dependent scalar load per function and word.
+      uint64_t fw0 = 0ull, fw1 = 0ull;
+      if constexpr (FUNCTIONS) {
+        const DFuncMasks* const fm = fmasks + part_begin + pi;
+        const uint32_t wj = lane & 15u, f0 = lane >> 4;
+        if (64u * wj < tile_len) {   // the word exists
+          if (f0 < n_functions) {
+            const NRT_GLOBAL uint64_t* const m = (const NRT_GLOBAL uint64_t*)fm->mask[f0];
+            fw0 = m != nullptr ? m[(base >> 6) + wj] : ~0ull;
+          }
+          if (f0 + 4u < n_functions) {
+            const NRT_GLOBAL uint64_t* const m = (const NRT_GLOBAL uint64_t*)fm->mask[f0 + 4u];
+            fw1 = m != nullptr ? m[(base >> 6) + wj] : ~0ull;
+          }
+        }
       }
 
       MmOuter outer[kFinalSlots];   // registers: every loop over j below is fully unrolled
@@ -133,11 +171,29 @@ void bm25_multi_match_kernel(const DItem* __restrict__ items, const DPart* __res
       for (int j = 0; j < kFinalSlots; ++j) {
         const uint32_t i = lane + 64u * (uint32_t)j;
         uint64_t key = 0;
-        if (64u * (uint32_t)j < tile_len) {   // uniform: the word below exists
+        if (64u * (uint32_t)j < tile_len) {   // uniform: the words below exist
           bool ok = outer[j].n != 0u;
           if (live_bits != nullptr) ok = ok && ((live_bits[word0 + (uint32_t)j] >> lane) & 1ull) != 0ull;
           const MmOuter& o = outer[j];
-          key = final_candidate_key(ok, gdoc0 + i, theta, after_key, wave_hits, [gq, &o](bool* hit) { return multi_match_value(*gq, o, hit); });
+          if constexpr (FUNCTIONS) {
+            uint32_t matched = 0;   // word j of function fi sits in lane 16 (fi & 3) + j: bit `lane` of it is this doc
+#pragma unroll
+            for (uint32_t fi = 0; fi < (uint32_t)kMaxFunctions; ++fi) {
+              if (fi >= n_functions) break;   // uniform
+              const uint64_t w = fi < 4u ? fw0 : fw1;
+              const int src = (int)(16u * (fi & 3u)) + j;
+              const uint64_t mw = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)w, src) |
+                                  ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(w >> 32), src) << 32);
+              matched |= (uint32_t)((mw >> lane) & 1ull) << fi;
+            }
+            // a doc the groups reject is no hit whatever the functions say; else the function score's own hit test decides
+            key = final_candidate_key(ok, gdoc0 + i, theta, after_key, wave_hits, [gq, fq, matched, &o](bool* hit) {
+              const float inner = multi_match_value(*gq, o, hit);
+              return *hit ? function_score_value(*fq, matched, inner, hit) : inner;
+            });
+          } else {
+            key = final_candidate_key(ok, gdoc0 + i, theta, after_key, wave_hits, [gq, &o](bool* hit) { return multi_match_value(*gq, o, hit); });
+          }
         }
         acc[i] = key;
         n_cand += (uint32_t)__popcll(__ballot(key != 0ull));
@@ -177,10 +233,38 @@ void bm25_multi_match_kernel(const DItem* __restrict__ items, const DPart* __res
   final_epilogue(s.t, cnt, k, q, tid, slice_sum, item_keys, item_counts, item_hits, k_stride);
 }
 
+__global__ __launch_bounds__(kMmThreads, kMmWaves / 4)
+void bm25_multi_match_kernel(const DItem* __restrict__ items, const DPart* __restrict__ parts, const DTerm* __restrict__ terms,
+                             const DQuery* __restrict__ queries, const float* __restrict__ caches,
+                             const DGroupQuery* __restrict__ gqueries, unsigned long long* __restrict__ theta_g,
+                             uint32_t* __restrict__ slice_sum, uint64_t* __restrict__ item_keys, uint32_t* __restrict__ item_counts,
+                             uint64_t* __restrict__ item_hits, uint32_t k_stride) {
+  multi_match_body<false>(items, parts, terms, queries, caches, gqueries, nullptr, nullptr, theta_g, slice_sum, item_keys, item_counts,
+                          item_hits, k_stride);
+}
+
+__global__ __launch_bounds__(kMmThreads, kMmWaves / 4)
+void bm25_multi_match_function_score_kernel(const DItem* __restrict__ items, const DPart* __restrict__ parts, const DTerm* __restrict__ terms,
+                                            const DQuery* __restrict__ queries, const float* __restrict__ caches,
+                                            const DGroupQuery* __restrict__ gqueries, const DFuncQuery* __restrict__ fqueries,
+                                            const DFuncMasks* __restrict__ fmasks, unsigned long long* __restrict__ theta_g,
+                                            uint32_t* __restrict__ slice_sum, uint64_t* __restrict__ item_keys,
+                                            uint32_t* __restrict__ item_counts, uint64_t* __restrict__ item_hits, uint32_t k_stride) {
+  multi_match_body<true>(items, parts, terms, queries, caches, gqueries, fqueries, fmasks, theta_g, slice_sum, item_keys, item_counts,
+                         item_hits, k_stride);
+}
+
 void launch_bm25_multi_match(hipStream_t stream, const FinalScoreArgs& a, const DGroupQuery* gqueries) {
   if (a.n_items == 0) return;
   hipLaunchKernelGGL(bm25_multi_match_kernel, dim3(a.n_items), dim3(kMmThreads), 0, stream, a.items, a.parts, a.terms, a.queries, a.caches,
                      gqueries, a.theta_g, a.slice_sum, a.item_keys, a.item_counts, a.item_hits, a.k_stride);
+}
+
+void launch_bm25_multi_match_function_score(hipStream_t stream, const FinalScoreArgs& a, const DGroupQuery* gqueries, const DFuncQuery* fqueries,
+                                            const DFuncMasks* fmasks) {
+  if (a.n_items == 0) return;
+  hipLaunchKernelGGL(bm25_multi_match_function_score_kernel, dim3(a.n_items), dim3(kMmThreads), 0, stream, a.items, a.parts, a.terms, a.queries,
+                     a.caches, gqueries, fqueries, fmasks, a.theta_g, a.slice_sum, a.item_keys, a.item_counts, a.item_hits, a.k_stride);
 }
 
 }  // namespace nrtgpu

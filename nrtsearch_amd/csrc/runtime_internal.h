@@ -54,6 +54,9 @@ void launch_bm25_maxscore(hipStream_t stream, bool profile, bool packed, int sha
 void launch_bm25_function_score(hipStream_t stream, const FinalScoreArgs& a, const DFuncQuery* fqueries, const DFuncMasks* fmasks);
 // multi-match queries (multimatch.hip): one DGroupQuery per query, a clause's group in DTerm.tab_slot bits 24-28
 void launch_bm25_multi_match(hipStream_t stream, const FinalScoreArgs& a, const DGroupQuery* gqueries);
+// a function score over multi-match queries (multimatch.hip): the records of both
+void launch_bm25_multi_match_function_score(hipStream_t stream, const FinalScoreArgs& a, const DGroupQuery* gqueries, const DFuncQuery* fqueries,
+                                            const DFuncMasks* fmasks);
 #ifdef NRTGPU_DEV
 void launch_debug_wave_kth(hipStream_t stream, const uint64_t* keys, uint32_t n, uint32_t r, uint64_t* out);   // (maxscore.hip: topk_kth_wave on its own)
 void launch_debug_walk_value(hipStream_t stream, float weight, const uint32_t* freq, const uint32_t* norm, const float* table, int fx_scale,
@@ -958,7 +961,7 @@ struct PlanBytes {   // an array of the route's own, appended to the plan buffer
   const void* p;
   size_t bytes;
 };
-const int kFinalScoreExtras = 2;   // at most: one per-query record array, one per-part array
+const int kFinalScoreExtras = 3;   // at most: two per-query record arrays (the groups', the functions'), one per-part array
 // the route's scorer: d_extra[i] = the device address of extras[i]
 typedef void (*FinalScoreLaunch)(hipStream_t, const FinalScoreArgs&, const void* const* d_extra);
 // From "the plan and the route's records exist" to "out[], the diagnostics and the statistics are filled": workspace, plan upload,
@@ -966,6 +969,25 @@ typedef void (*FinalScoreLaunch)(hipStream_t, const FinalScoreArgs&, const void*
 // capacity); t0: now_ms() when planning began.  The caller holds its SegReadLocks until this returns.
 int final_score_run(nrtgpu_ctx* ctx, const HostPlan& hp, const nrtgpu_bm25_query* queries, int32_t n_queries, nrtgpu_topdocs* out, double t0,
                     const PlanBytes* extras, int n_extras, FinalScoreLaunch launch);
+
+// ---- what the routes lend each other (multimatch.cpp and funcscore.cpp define them; funcscore_multimatch.cpp uses both halves) ----
+// multimatch.cpp: the record the kernel and nrtgpu_multi_match_value read, from the caller's struct; refusals by the header's
+// table.  occur: the clauses' nrtgpu_term.occur, or nullptr = all SHOULD
+int group_record(const nrtgpu_clause_groups& g, int qi, int32_t n_terms, const int32_t* occur, int32_t min_should_match, DGroupQuery* out);
+// multimatch.cpp: what the multi-match route refuses of (queries[i], groups[i]) before anything is planned, the context's flags
+// aside; the records (optional) and the reduced copies of the queries (plain SHOULD disjunctions: what is planned) on the way
+int multi_match_check_queries(const nrtgpu_bm25_query* queries, const nrtgpu_clause_groups* groups, int32_t n_queries, std::vector<DGroupQuery>* records,
+                              std::vector<nrtgpu_bm25_query>* flat, std::vector<std::vector<nrtgpu_term>>* flat_terms);
+// multimatch.cpp: the plan of the reduced queries (final_score_plan), and every clause's group into its DQTerm
+int multi_match_plan(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, const nrtgpu_bm25_query* flat,
+                     const nrtgpu_clause_groups* groups, int32_t n_queries, const char* route, HostPlan& hp);
+// funcscore.cpp: the record the kernels and nrtgpu_function_score_value read, from the caller's struct; refusals by the header's table
+int function_record(const nrtgpu_function_score& fs, int qi, DFuncQuery* out);
+// funcscore.cpp: refuses a function mask that is not resident on a leaf of the call
+int function_masks_resident(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_function_score& fs, int qi);
+// funcscore.cpp: the doc sets of every function on every part's leaf, for any plan over these leaves (a part names its leaf via qs_begin)
+int function_masks(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_function_score* functions, const HostPlan& hp,
+                   std::vector<DFuncMasks>* out);
 
 }  // namespace rt
 }  // namespace nrtgpu
