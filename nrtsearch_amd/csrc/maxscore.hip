@@ -48,10 +48,15 @@
 // coalesced load; it used to rebuild them -- four to five dependent global loads and 13 score evaluations per clause -- every
 // time, as did the item's other eleven waves and its helpers.  The part that holds a window is found by a ballot over per-lane
 // window prefix sums (items of up to 64 parts), not by a search part by part.
+// Half groups (walk_units): a window's essential clauses are streamed 64 eight-posting units per instruction and the last
+// instruction holds whatever is left; with 32 units or fewer left the wave runs the instruction's body at FOUR postings per lane
+// (two lanes per unit) -- half the per-slot memory, LDS and ALU instructions of every phase for the same postings.
 // Roofline: HBM.  Reported both ways: effective = 9 B x the postings of the query's terms, physical
 // = what the kernel fetches (a few percent of that).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "bm25_common.hiph"
 
@@ -97,7 +102,8 @@ struct MsSmem {
   uint32_t cnt_valid;    // entries of cand that are complete when cnt ran past kMsCandCap
   uint32_t rz_flag;      // a wave could not reserve candidate slots (A/B, spec_meet: or a new speculative theta is due): everybody meet
   uint32_t spec_busy;    // speculation: a wave is making an estimate (ms_estimate; taken by compare-and-swap: one at a time)
-  uint32_t spec_meet;    // A/B (development build, plan.h: DHelp.spec_sched bit 16): estimates are made in meetings, as before
+  uint32_t spec_meet;    // A/B (development build, plan.h: DHelp.spec_sched): bit 0 (its bit 16) estimates are made in meetings, as before;
+                         // bit 1 (its bit 17) no half groups: every instruction of the walk runs the full body
   uint32_t n_meet, n_over, n_est;   // instrumented kernels: meetings, those called by an overflow, estimates made by one wave
   uint32_t wins_started; // doc windows this workgroup's waves have taken so far (of the item it works on)
   uint32_t spec_at;      // speculation: the next estimate is due when wins_started reaches this (0: never)
@@ -376,6 +382,7 @@ template <bool PROF, bool PACKED, int SHAPES>
 __global__ __launch_bounds__(kMsThreads)
 void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
   constexpr bool TWO = SHAPES == 2;
+  constexpr bool kMsHalfBody = kSl == 8;   // a window's last instruction, 32 units or fewer: the walk's body at four postings per lane
   __shared__ MsSmem s;
   // The launch record (plan.h: MsArgs) lives next to the plan; ONE pointer is the kernel's argument.  Its fields are scalar loads
   // made where they are used -- the workgroup's round, then once more in front of the item's epilogue (ms_fresh: the compiler
@@ -559,7 +566,7 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
       s.spec_slot = spec ? as_global(hp.spec_g) + item.query : nullptr;
       s.spec_at = spec ? max(hp.spec_sched & 255u, 1u) : 0u;   // the first estimate (default: when every wave has begun its second window)
       s.spec_grow16 = max((hp.spec_sched >> 8) & 255u, 17u);
-      s.spec_meet = (hp.spec_sched >> 16) & 1u;
+      s.spec_meet = (hp.spec_sched >> 16) & 3u;
       for (int i = 0; i < kSliceSlots; ++i) s.slot_hits[i] = s.slot_slice[i] = 0u;
       for (int i = 0; i < 16; ++i) s.prof[i] = 0;
     }
@@ -596,7 +603,7 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
     uint64_t ph[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, ph_t = 0;   // 0 window head, 1 columns, 2 values + bounds, 3 test-and-set, 4 records, 5 codes, 6 sums, 7 sparse clause, 8 hits + candidates
   #endif
   #ifdef NRT_MS_COUNT_ROUNDS   // experiment build: event counts instead of four of the cycle counters
-    uint64_t pc_dense = 0, pc_sparse = 0, pc_steps = 0, pc_tas = 0, pc_crounds = 0;
+    uint64_t pc_dense = 0, pc_sparse = 0, pc_steps = 0, pc_tas = 0, pc_crounds = 0, pc_half = 0, pc_half_rounds = 0;
   #endif
     // The item's windows (flattened over its parts, item_wins of them) are handed out in a SCATTERED order: the i-th window taken
     // (by anybody: the counter is shared with the item's helpers) is window (i x a) mod item_wins, a coprime to item_wins and near
@@ -790,7 +797,7 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
           if (lane == 0) {
             const uint32_t ws = atomicAdd(&s.wins_started, 1u) + 1u, at = s.spec_at;
             if (at != 0u && ws >= at) {
-              if (s.spec_meet != 0u) __hip_atomic_store(&s.rz_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // (A/B: in a meeting)
+              if ((s.spec_meet & 1u) != 0u) __hip_atomic_store(&s.rz_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // (A/B: in a meeting)
               else est = atomicCAS(&s.spec_busy, 0u, 1u) == 0u ? 1u : 0u;
             }
           }
@@ -838,14 +845,30 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
   #pragma unroll
         for (int i = 0; i < kMsMaxTerms; ++i) pre[i] = (uint32_t)__builtin_amdgcn_readlane((int)incl, i);
         const uint32_t n_groups = pre[kMsMaxTerms - 1];
+  #ifdef NRTGPU_DEV   // (A/B, NRTGPU_MS_HALF_GROUPS=0: every instruction runs the full body)
+        const bool half_on = (__builtin_amdgcn_readfirstlane((int)s.spec_meet) & 2) == 0;
+  #else
+        constexpr bool half_on = true;
+  #endif
 
   #ifdef NRT_MS_PHASE_CLOCKS
         if (PROF) ph_t = t_win0;
   #endif
         NRT_PH_MARK(0);
-        for (uint32_t v0 = 0; v0 < n_groups; v0 += 64u) {  // 64 groups = up to 512 postings per instruction
-          const uint32_t v = v0 + lane;
-          const bool act = v < n_groups;
+        // One instruction of the walk, over NS postings per lane.  Full (NS = kSl): lane l takes the kSl-posting unit v0 + l, 64
+        // units = up to 512 postings.  HALF (NS = 4, of 8): lane l takes half l & 1 of the 8-posting unit v0 + (l >> 1) -- a window's
+        // LAST instruction when 32 units or fewer are left: every per-slot step of every phase (column words, table reads,
+        // test-and-set, the later clauses' record and code gathers) is issued for four slots instead of eight, of which at least
+        // four were empty in every lane.  A clause's units start at its 16-byte aligned begin, so a half never spans two clauses
+        // and is one 16-byte load per column; the units' order over the lanes, and with it the clause-by-clause order of the
+        // test-and-set rounds, is the full body's.  Returns false when the rest of the window is non-essential.
+        auto walk_units = [&](auto ns_c, auto half_c, const uint32_t v0) __attribute__((always_inline)) -> bool {
+          constexpr int NS = decltype(ns_c)::value;
+          constexpr bool HALF = decltype(half_c)::value;
+          static_assert(!HALF || (NS == 4 && kSl == 8), "the half body: four of a unit's eight postings per lane");
+          const uint32_t n_lanes = HALF ? 2u * (n_groups - v0) : min(n_groups - v0, 64u);   // (uniform) lanes that hold postings
+          const uint32_t v = HALF ? v0 + (lane >> 1) : v0 + lane;
+          const bool act = HALF ? lane < n_lanes : v < n_groups;
           uint32_t c = 0, before = 0;
   #pragma unroll
           for (int i = 0; i < kMsMaxTerms - 1; ++i) {
@@ -858,7 +881,7 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
           const uint64_t theta = max(s.theta, theta_other), thr = loosen(max(s.thr, thr_other));
           const bool pruning = __hip_atomic_load(&s.prune_on, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0u;   // (uniform)
           const uint64_t thr_p = pruning ? thr : 0ull;   // what the bounds are compared with
-          if (readlane_u64(my_suf, c_first) < thr_p) break;
+          if (readlane_u64(my_suf, c_first) < thr_p) return false;
           if (PROF) pc_chunks += 1;
           // what my clause is: column bases, posting range, score table, scale, what the later clauses can still add
           const uint32_t rec = wcl_addr + c * (uint32_t)sizeof(WClause);
@@ -867,35 +890,35 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
           const uint64_t col_d = ((uint64_t)r0[1] << 32) | r0[0], col_c = ((uint64_t)r0[3] << 32) | r0[2];
           const uint64_t p_begin = ((uint64_t)r1[1] << 32) | r1[0];
           const uint32_t flags = r2[2];
-          const uint32_t q0 = (v - before) * (uint32_t)kSl;  // my group's first posting, counted from the clause's 16-byte aligned begin
+          const uint32_t q0 = (v - before) * (uint32_t)kSl + (HALF ? (lane & 1u) * 4u : 0u);  // my group's first posting, counted from the clause's 16-byte aligned begin
           const uint64_t mine0 = (p_begin & ~3ull) + (uint64_t)q0;
-          uint32_t d[kSl], cd[kSl];
+          uint32_t d[NS], cd[NS];
   #pragma unroll
-          for (int j = 0; j < kSl; ++j) d[j] = cd[j] = 0u;
+          for (int j = 0; j < NS; ++j) d[j] = cd[j] = 0u;
           if (act) {  // (the columns are padded: a partly valid group may read past the term)
             const u32x4 d0 = __builtin_nontemporal_load((gvec_ptr)(col_d + mine0 * 4u));
-            const u32x4 d1 = kSl > 4 ? __builtin_nontemporal_load((gvec_ptr)(col_d + mine0 * 4u) + 1) : d0;
+            const u32x4 d1 = NS > 4 ? __builtin_nontemporal_load((gvec_ptr)(col_d + mine0 * 4u) + 1) : d0;
             if (PACKED) {  // one word per posting: doc offset inside the window's super-window | code
               const uint32_t sw = doc_lo & ~kPackDocMask;
   #pragma unroll
               for (int j = 0; j < 4; ++j) {
                 d[j] = (d0[j] >> kPackCodeBits) | sw;
                 cd[j] = (d0[j] & kPackCodeMask) << 2;
-                if (kSl > 4) {
-                  d[(4 + j) % kSl] = (d1[j] >> kPackCodeBits) | sw;
-                  cd[(4 + j) % kSl] = (d1[j] & kPackCodeMask) << 2;
+                if (NS > 4) {
+                  d[(4 + j) % NS] = (d1[j] >> kPackCodeBits) | sw;
+                  cd[(4 + j) % NS] = (d1[j] & kPackCodeMask) << 2;
                 }
               }
             } else {
               const u32x4 c0 = __builtin_nontemporal_load((gvec_ptr)(col_c + mine0 * 4u));
-              const u32x4 c1 = kSl > 4 ? __builtin_nontemporal_load((gvec_ptr)(col_c + mine0 * 4u) + 1) : c0;
+              const u32x4 c1 = NS > 4 ? __builtin_nontemporal_load((gvec_ptr)(col_c + mine0 * 4u) + 1) : c0;
   #pragma unroll
               for (int j = 0; j < 4; ++j) {
                 d[j] = d0[j];
                 cd[j] = c0[j];
-                if (kSl > 4) {
-                  d[(4 + j) % kSl] = d1[j];
-                  cd[(4 + j) % kSl] = c1[j];
+                if (NS > 4) {
+                  d[(4 + j) % NS] = d1[j];
+                  cd[(4 + j) % NS] = c1[j];
                 }
               }
             }
@@ -905,17 +928,17 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
           {
             const uint32_t rel = q0 - ((uint32_t)p_begin & 3u), cnt = act ? r1[2] : 0u;
   #pragma unroll
-            for (int j = 0; j < kSl; ++j)
+            for (int j = 0; j < NS; ++j)
               if (rel + (uint32_t)j < cnt && d[j] - doc_lo < doc_span) vmask |= 1u << j;
           }
           // the values my postings add: per-lane table (lanes of one instruction may belong to different clauses)
-          uint32_t val[kSl];
+          uint32_t val[NS];
           {
             const uint32_t tab = flags & 7u;
             const char* tb = (const char*)&s.tab[tab == 7u ? 0u : tab][0];
             uint32_t cor = 0;
   #pragma unroll
-            for (int j = 0; j < kSl; ++j) {
+            for (int j = 0; j < NS; ++j) {
               val[j] = *(const uint32_t*)(tb + (cd[j] & 0x1FFCu));
               const uint32_t cn = ((vmask >> j) & 1u) ? cd[j] : 0u;
               cor = PACKED ? max(cor, cn) : (cor | cn);
@@ -926,7 +949,7 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
               const int fx_scale = (int)r2[1];
               const float* cache = &s.cache[(flags >> 8) & 255u][0];
   #pragma unroll
-              for (int j = 0; j < kSl; ++j) {
+              for (int j = 0; j < NS; ++j) {
                 uint32_t cj = cd[j];
                 if (PACKED && cj >= (kPackEscBase << 2))   // (col_c: the group's exception list; mine0 + j: the posting's index in its column)
                   cj = ((vmask >> j) & 1u) ? packed_escape_word((gu32_ptr)col_c, (uint32_t)mine0 + (uint32_t)j, cj >> 2) : 0x80000100u;
@@ -939,7 +962,7 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
               }
             }
           }
-          uint64_t run[kSl];
+          uint64_t run[NS];
           uint32_t alive = 0;
           {
             const uint32_t mult = 1u << ((flags >> 4) & 15u);  // entry << shift as one 32 x 32 -> 64 multiply
@@ -954,24 +977,24 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
             }
             uint32_t pass = 0;
   #pragma unroll
-            for (int j = 0; j < kSl; ++j) {
+            for (int j = 0; j < NS; ++j) {
               run[j] = (uint64_t)val[j] * (uint64_t)mult;
               pass |= val[j] >= need_v ? (1u << j) : 0u;
             }
             alive = vmask & pass;
             if (need_v == 0xFFFFFFFFu) {   // (per lane, practically never)
   #pragma unroll
-              for (int j = 0; j < kSl; ++j)
+              for (int j = 0; j < NS; ++j)
                 if ((use_max ? max(run[j], u_after) : run[j] + u_after) < thr_p) alive &= ~(1u << j);
             }
           }
-          uint64_t sec[TWO ? kSl : 1];
+          uint64_t sec[TWO ? NS : 1];
           if (TWO) {
             // a doc first reached at clause c is in no streamed clause before c: a MUST clause among them and it is no hit
             if ((req_mask & ((1u << c) - 1u)) != 0u) alive = 0u;
             const bool mine_counts = sec_mode == kMsSecTieBreaker || (sec_mode == kMsSecReqOpt && ((req_mask >> c) & 1u) == 0u);
   #pragma unroll
-            for (int j = 0; j < kSl; ++j) sec[j] = mine_counts ? run[j] : 0ull;
+            for (int j = 0; j < NS; ++j) sec[j] = mine_counts ? run[j] : 0ull;
           }
           if (PROF) {
             pc_post += (uint64_t)__popc(vmask);
@@ -981,7 +1004,7 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
           // first clause to reach the doc?  Test-and-set, clause by clause in order: LDS executes a wave's operations
           // in order, so of two postings of one doc in this instruction the earlier clause's wins.  (Lanes without a
           // survivor OR a zero into a word of their own.)
-          const uint32_t c_last = (uint32_t)__builtin_amdgcn_readlane((int)c, (int)(min(n_groups - v0, 64u) - 1u));
+          const uint32_t c_last = (uint32_t)__builtin_amdgcn_readlane((int)c, (int)(n_lanes - 1u));
           if (n_terms > 1u && __any(alive != 0u)) {
             for (uint32_t cc = c_first; cc <= c_last; ++cc) {
               const uint32_t am = c == cc ? alive : 0u;
@@ -989,15 +1012,15 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
   #ifdef NRT_MS_COUNT_ROUNDS
               if (PROF) pc_tas += 1;
   #endif
-              uint32_t old[kSl];
+              uint32_t old[NS];
   #pragma unroll
-              for (int j = 0; j < kSl; ++j) {
+              for (int j = 0; j < NS; ++j) {
                 const bool a = (am >> j) & 1u;
                 const uint32_t w = a ? ((d[j] - doc_lo) >> 5) : lane;
                 old[j] = atomicOr(&seen[w], a ? (1u << (d[j] & 31u)) : 0u);
               }
   #pragma unroll
-              for (int j = 0; j < kSl; ++j)
+              for (int j = 0; j < NS; ++j)
                 if (((am >> j) & 1u) && ((old[j] >> (d[j] & 31u)) & 1u)) alive &= ~(1u << j);
             }
           }
@@ -1015,11 +1038,11 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
               const uint64_t short_of = S_j < thr_p ? (use_max ? thr_p : thr_p - S_j) : 0ull;
               uint32_t kill = 0;
   #pragma unroll
-              for (int j = 0; j < kSl; ++j) kill |= run[j] < short_of ? (1u << j) : 0u;
+              for (int j = 0; j < NS; ++j) kill |= run[j] < short_of ? (1u << j) : 0u;
               if (SHAPES && msm > 1u) {   // (uniform) too few clauses left to reach minimumNumberShouldMatch: no hit, whatever it scores
                 const uint32_t left = n_terms - j2;
   #pragma unroll
-                for (int j = 0; j < kSl; ++j) kill |= ((ccnt >> (4 * j)) & 15u) + left < msm ? (1u << j) : 0u;
+                for (int j = 0; j < NS; ++j) kill |= ((ccnt >> (4 * j)) & 15u) + left < msm ? (1u << j) : 0u;
               }
               kill &= am;
               alive &= ~kill;
@@ -1033,8 +1056,8 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
             const uint32_t kind2 = (flags2 >> 24) & 7u;   // (uniform) how a doc is looked up in this clause (plan.h: kLook*)
             const uint64_t start2 = uniform_u64(w2.start);
             const gu32_ptr codes2 = (gu32_ptr)(uniform_u64(PACKED ? w2.docids : w2.fnorm) + start2 * 4u);  // packed: the code rides in the posting's word
-            uint32_t c2[kSl];
-            uint32_t pi2[kSl];  // packed postings: the looked-up postings' indices in their column (exception lookups)
+            uint32_t c2[NS];
+            uint32_t pi2[NS];  // packed postings: the looked-up postings' indices in their column (exception lookups)
             uint32_t present = 0;
   #ifdef NRT_MS_COUNT_ROUNDS
             if (PROF) { if (kind2 == kLookBits) pc_dense += 1; else pc_sparse += 1; }
@@ -1043,25 +1066,25 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
               // RECORDS: one 8-byte record per 32 docs {doc bits, postings of the term before the block} says whether the doc is
               // there and where its posting is; the code is a second, dependent gather
               const gvec2_ptr recs = (gvec2_ptr)look2;
-              u32x2 r[kSl];
+              u32x2 r[NS];
   #pragma unroll
-              for (int j = 0; j < kSl; ++j) r[j] = recs[((am >> j) & 1u) ? (d[j] >> 5) : 0u];
+              for (int j = 0; j < NS; ++j) r[j] = recs[((am >> j) & 1u) ? (d[j] >> 5) : 0u];
               __builtin_amdgcn_sched_barrier(0);   // every record load is issued before the first one is waited for
               NRT_PH_MARK(4);
-              uint32_t idx[kSl];
+              uint32_t idx[NS];
   #pragma unroll
-              for (int j = 0; j < kSl; ++j) {
+              for (int j = 0; j < NS; ++j) {
                 const uint32_t bb = d[j] & 31u;
                 const bool there = ((am >> j) & 1u) && ((r[j][0] >> bb) & 1u);
                 idx[j] = there ? r[j][1] + (uint32_t)__popc(r[j][0] & ((1u << bb) - 1u)) : 0u;
                 present |= (there ? 1u : 0u) << j;
               }
   #pragma unroll
-              for (int j = 0; j < kSl; ++j) c2[j] = codes2[idx[j]];
+              for (int j = 0; j < NS; ++j) c2[j] = codes2[idx[j]];
               __builtin_amdgcn_sched_barrier(0);   // (the same for the code loads)
               NRT_PH_MARK(5);
   #pragma unroll
-              for (int j = 0; j < kSl; ++j) pi2[j] = (uint32_t)start2 + idx[j];
+              for (int j = 0; j < NS; ++j) pi2[j] = (uint32_t)start2 + idx[j];
             } else {
               // SEARCH: the doc's cell -- a lookup cell of 2^look_shift docs holding 0.5 - 1 posting on average (kLookCells), else
               // its cell of the tile-granular table (~4 - 8 postings) -- then a binary search among the cell's postings; the 8
@@ -1069,16 +1092,16 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
               const gu32_ptr cells2 = (gu32_ptr)(kind2 == kLookCells ? look2 : uniform_u64(w2.cells));
               const gu32_ptr docs2 = (gu32_ptr)(uniform_u64(w2.docids) + start2 * 4u);
               const uint32_t cshift = kind2 == kLookCells ? (flags2 >> 27) & 31u : 10u + ((flags2 >> 16) & 31u);
-              uint32_t a[kSl], b[kSl];
+              uint32_t a[NS], b[NS];
   #pragma unroll
-              for (int j = 0; j < kSl; ++j) {
+              for (int j = 0; j < NS; ++j) {
                 const uint32_t cell = ((am >> j) & 1u) ? (d[j] >> cshift) : 0u;
                 a[j] = cells2[cell];
                 b[j] = cells2[cell + 1u];
               }
               uint32_t open = 0;
   #pragma unroll
-              for (int j = 0; j < kSl; ++j) {
+              for (int j = 0; j < NS; ++j) {
                 if (!((am >> j) & 1u)) b[j] = a[j];
                 open |= (a[j] < b[j] ? 1u : 0u) << j;
               }
@@ -1086,14 +1109,14 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
   #ifdef NRT_MS_COUNT_ROUNDS
                 if (PROF) pc_steps += 1;
   #endif
-                uint32_t mid[kSl], vv[kSl];
+                uint32_t mid[NS], vv[NS];
   #pragma unroll
-                for (int j = 0; j < kSl; ++j) {
+                for (int j = 0; j < NS; ++j) {
                   mid[j] = (a[j] + b[j]) >> 1;
                   vv[j] = docs2[((open >> j) & 1u) ? mid[j] : 0u];
                 }
   #pragma unroll
-                for (int j = 0; j < kSl; ++j)
+                for (int j = 0; j < NS; ++j)
                   if ((open >> j) & 1u) {
                     // (packed: doc offsets inside the cell's super-window -- the doc's own, a cell never spans two)
                     const uint32_t dv = PACKED ? vv[j] >> kPackCodeBits : vv[j], dd = PACKED ? d[j] & kPackDocMask : d[j];
@@ -1107,7 +1130,7 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
                   }
               }
   #pragma unroll
-              for (int j = 0; j < kSl; ++j) {
+              for (int j = 0; j < NS; ++j) {
                 c2[j] = codes2[((present >> j) & 1u) ? a[j] : 0u];   // (packed: the posting's word again -- keeping the probe's word alive
                                                                       //  through the search loop cost more than this gather)
                 pi2[j] = (uint32_t)start2 + a[j];
@@ -1115,27 +1138,27 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
               NRT_PH_MARK(7);
             }
             if (__any(present != 0u)) {
-              uint32_t v2[kSl];
+              uint32_t v2[NS];
               if (PACKED) {
   #pragma unroll
-                for (int j = 0; j < kSl; ++j) c2[j] = (c2[j] & kPackCodeMask) << 2;
+                for (int j = 0; j < NS; ++j) c2[j] = (c2[j] & kPackCodeMask) << 2;
               }
-              values_of_codes<PACKED, kSl>(s, c2, present, flags2 & 7u, w2.weight, w2.fx_scale, (flags2 >> 8) & 255u, w2.fnorm, pi2, v2);
+              values_of_codes<PACKED, NS>(s, c2, present, flags2 & 7u, w2.weight, w2.fx_scale, (flags2 >> 8) & 255u, w2.fnorm, pi2, v2);
               const uint32_t mult2 = 1u << ((flags2 >> 4) & 15u);
               if (use_max) {   // (uniform)
   #pragma unroll
-                for (int j = 0; j < kSl; ++j) run[j] = max(run[j], (uint64_t)(((present >> j) & 1u) ? v2[j] : 0u) * (uint64_t)mult2);
+                for (int j = 0; j < NS; ++j) run[j] = max(run[j], (uint64_t)(((present >> j) & 1u) ? v2[j] : 0u) * (uint64_t)mult2);
               } else if (TWO && sec_mode != kMsSecNone) {   // (uniform) the sum, and the best clause / the SHOULD clauses' sum next to it
                 const bool counts = sec_mode == kMsSecReqOpt && (flags2 & 8u) == 0u;
   #pragma unroll
-                for (int j = 0; j < kSl; ++j) {
+                for (int j = 0; j < NS; ++j) {
                   const uint64_t add = (uint64_t)(((present >> j) & 1u) ? v2[j] : 0u) * (uint64_t)mult2;
                   run[j] += add;
                   sec[j] = sec_mode == kMsSecTieBreaker ? max(sec[j], add) : sec[j] + (counts ? add : 0ull);
                 }
               } else {
   #pragma unroll
-                for (int j = 0; j < kSl; ++j) run[j] += (uint64_t)(((present >> j) & 1u) ? v2[j] : 0u) * (uint64_t)mult2;  // v_mad_u64_u32
+                for (int j = 0; j < NS; ++j) run[j] += (uint64_t)(((present >> j) & 1u) ? v2[j] : 0u) * (uint64_t)mult2;  // v_mad_u64_u32
               }
               if (SHAPES && msm > 1u) {   // (uniform) bit j of `present` -> nibble j
                 uint32_t x = present;
@@ -1155,7 +1178,7 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
           //      posting per lane and round.
           uint32_t maybe = 0;
   #pragma unroll
-          for (int j = 0; j < kSl; ++j)
+          for (int j = 0; j < NS; ++j)
             if (((alive >> j) & 1u) && run[j] >= thr) maybe |= 1u << j;
           // ---- hits.  While nothing is being skipped every live matching doc reaches this point exactly once: the count is
           //      exact.  Once bounds skip it is a lower bound, and only the docs that reach theta's score are looked at.
@@ -1165,15 +1188,15 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
             uint32_t pool = pruning ? maybe : alive;
             if (SHAPES && msm > 1u) {   // (uniform)
   #pragma unroll
-              for (int j = 0; j < kSl; ++j)
+              for (int j = 0; j < NS; ++j)
                 if (((ccnt >> (4 * j)) & 15u) < msm) pool &= ~(1u << j);
             }
             if (part.live_bits != nullptr && __any(pool != 0u)) {   // (uniform)
-              uint32_t lw[kSl];
+              uint32_t lw[NS];
   #pragma unroll
-              for (int j = 0; j < kSl; ++j) lw[j] = ((const NRT_GLOBAL uint32_t*)part.live_bits)[((pool >> j) & 1u) ? (d[j] >> 5) : 0u];
+              for (int j = 0; j < NS; ++j) lw[j] = ((const NRT_GLOBAL uint32_t*)part.live_bits)[((pool >> j) & 1u) ? (d[j] >> 5) : 0u];
   #pragma unroll
-              for (int j = 0; j < kSl; ++j)
+              for (int j = 0; j < NS; ++j)
                 if (!((lw[j] >> (d[j] & 31u)) & 1u)) pool &= ~(1u << j);
             }
             maybe &= pool;
@@ -1201,7 +1224,7 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
             uint64_t rsel = run[0], ssel = TWO ? sec[0] : 0ull;
             uint32_t dsel = d[0];
   #pragma unroll
-            for (int j = 1; j < kSl; ++j)
+            for (int j = 1; j < NS; ++j)
               if (low == (1u << j)) {
                 rsel = run[j];
                 dsel = d[j];
@@ -1233,6 +1256,26 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
           }
           }
           NRT_PH_MARK(8);
+          return true;
+        };
+        for (uint32_t v0 = 0; v0 < n_groups; v0 += 64u) {  // 64 units = up to 512 postings per instruction
+          bool more;
+          if (kMsHalfBody && n_groups - v0 <= 32u && half_on) {   // (uniform: one branch between two straight-line bodies)
+  #ifdef NRT_MS_COUNT_ROUNDS
+            const uint64_t chunks0 = pc_chunks, look0 = pc_dense + pc_sparse;
+  #endif
+            if constexpr (kMsHalfBody) more = walk_units(std::integral_constant<int, 4>{}, std::true_type{}, v0);
+            else more = false;
+  #ifdef NRT_MS_COUNT_ROUNDS
+            if (PROF) {   // (an instruction that found the rest of the window non-essential did not run)
+              pc_half += pc_chunks - chunks0;
+              pc_half_rounds += pc_dense + pc_sparse - look0;
+            }
+  #endif
+          } else {
+            more = walk_units(std::integral_constant<int, kSl>{}, std::false_type{}, v0);
+          }
+          if (!more) break;
           // somebody else asked for a compaction: join it between two instructions
           if (__hip_atomic_load(&s.rz_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) {
             const uint64_t t_m0 = PROF ? __builtin_readcyclecounter() : 0ull;
@@ -1257,8 +1300,10 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
       atomicAdd((unsigned long long*)&s.prof[11], (unsigned long long)(t_epi0 - t_idle0));
       atomicAdd((unsigned long long*)&s.prof[12], (unsigned long long)tc_part);
       atomicAdd((unsigned long long*)&s.prof[13], (unsigned long long)(tc_walk - tc_meet));
+  #ifndef NRT_MS_COUNT_ROUNDS
       atomicMax((unsigned long long*)&s.prof[14], (unsigned long long)(t_idle0 - t_item0));
-  #ifdef NRT_MS_COUNT_ROUNDS
+  #else   // (slot 14: instructions run by the half body | the later-clause rounds inside them << 32)
+      atomicAdd((unsigned long long*)&s.prof[14], (unsigned long long)pc_half | ((unsigned long long)pc_half_rounds << 32));
       atomicAdd((unsigned long long*)&s.prof[11], (unsigned long long)pc_tas - (unsigned long long)(t_epi0 - t_idle0));
       atomicAdd((unsigned long long*)&s.prof[12], (unsigned long long)pc_dense - (unsigned long long)tc_part);
       atomicAdd((unsigned long long*)&s.prof[10], (unsigned long long)pc_sparse - (unsigned long long)tc_meet);

@@ -317,6 +317,7 @@ struct DHelp {
   uint32_t spec_z16, spec_sched; // the estimate's safety margin in standard deviations x 16; when estimates are due: bits 0-7 the
                                  // first one (doc windows begun by the workgroup), bits 8-15 the factor x 16 between one and the next
                                  // bit 16 (development build, A/B): the estimate is made in a meeting of all waves, not by one wave
+                                 // bit 17 (development build, A/B): no half groups -- a window's last instruction runs the full body too
   unsigned long long* walls;     // instrumented kernel only, else nullptr: per output slot 8 words -- {start, end} on the 100 MHz
                                  // wall clock, item, windows walked, when the workgroup's round began, CU id, round, workgroup --
                                  // when every piece of the launch ran, on one time base (nrtgpu_get_maxscore_item_walls)

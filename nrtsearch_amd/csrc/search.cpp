@@ -216,7 +216,10 @@ static MsArgs ms_launch_record(const nrtgpu_ctx* ctx, const HostPlan& hp, const 
     const int env_first = (int)dev_env_int("NRTGPU_MS_SPEC_FIRST", 2 * kMsWaves);
     const int env_grow = (int)dev_env_int("NRTGPU_MS_SPEC_GROW", 32);
     const bool env_meet = dev_env_int("NRTGPU_MS_SPEC_MEET", 0) != 0;
-    help.spec_sched = (uint32_t)std::min(std::max(env_first, 1), 255) | ((uint32_t)std::min(std::max(env_grow, 17), 255) << 8) | (env_meet ? 1u << 16 : 0u);
+    // NRTGPU_MS_HALF_GROUPS=0: a window's last instruction runs the walk's full body whatever it holds (A/B; maxscore.hip: walk_units)
+    const bool env_half = dev_env_int("NRTGPU_MS_HALF_GROUPS", 1) != 0;
+    help.spec_sched = (uint32_t)std::min(std::max(env_first, 1), 255) | ((uint32_t)std::min(std::max(env_grow, 17), 255) << 8) | (env_meet ? 1u << 16 : 0u) |
+                      (env_half ? 0u : 1u << 17);
   }
   MsArgs ms_args{};   // (the kernel reads the record from the plan: maxscore.hip)
   ms_args.items = (const DItem*)(db + L.items);

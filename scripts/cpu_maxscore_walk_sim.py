@@ -13,7 +13,11 @@ Round 4: SPEC_Z=5 adds the kernel's SPECULATIVE thresholds (plan.h: kHitsSpecInv
 and whenever the number of windows begun has doubled, theta is raised to the (k w / W + z sqrt(k w / W) + 2)-th best score held
 (w of W windows begun) -- and reports how many guesses overshot the final k-th score (what the merge's check would catch).  The
 counts `rounds` (later-clause rounds as the kernel runs them: one per instruction and later clause with a live doc) and
-`queued_rounds` (the same lookups regrouped per wave, window and clause into rounds of 512: DESIGN 8 item 2) come with every run."""
+`queued_rounds` (the same lookups regrouped per wave, window and clause into rounds of 512: DESIGN 8 item 2) come with every run.
+HALF GROUPS (maxscore.hip: walk_units): `groups_le256` / `groups_le128` count the instructions that hold at most 256 / 128 posting
+slots (32 / 16 of the 64 eight-posting units: only a window's last instruction can), `rounds_le256` the later-clause rounds run
+inside the former -- what the walk's body at four postings per lane runs at half the per-slot instructions;
+the mean fill of an instruction, postings / (512 groups), is printed with the means."""
 import os
 import sys
 
@@ -38,7 +42,7 @@ class Item:
         self.theta = 0.0
         self.cand = []
         self.n = dict(groups=0, windows=0, postings=0, marked=0, survivors=0, docs=0, lookups=0, cands=0, compactions=0, rounds=0,
-                      queued_rounds=0, estimates=0)
+                      queued_rounds=0, estimates=0, groups_le256=0, groups_le128=0, rounds_le256=0)
         self.n_win, self.wins_started, self.spec_at, self.guess_max = 1, 0, 2 * WAVES, 0.0
 
     def guess(self):
@@ -164,6 +168,10 @@ def run_walk(it, D, Sc, dense, S, N, stream, mark_only=(), blk=None, win_range=N
                 run = run + np.where(live, dense[j][docs], 0.0)
             it.push(run[live])
         it.n["rounds"] += int(round_of.sum())
+        if len(cl) <= INSTR // 2:   # 32 units or fewer: the kernel runs this instruction at four postings per lane
+            it.n["groups_le256"] += 1
+            it.n["rounds_le256"] += int(round_of.sum())
+            it.n["groups_le128"] += int(len(cl) <= INSTR // 4)
         return True
 
     active = True
@@ -284,6 +292,10 @@ def main():
     overshot = tot.pop("guesses that overshot", None)
     for name, t in tot.items():
         print("MEAN per query,", name, {kk: round(v / nq, 1) for kk, v in t.items()})
+        if t.get("groups"):
+            print(f"   half groups, {name}: {100.0 * t['groups_le256'] / t['groups']:.1f} % of the instructions hold <= 256 slots "
+                  f"({100.0 * t['groups_le128'] / t['groups']:.1f} %: <= 128), {100.0 * t['rounds_le256'] / max(t['rounds'], 1):.1f} % of the later-clause rounds "
+                  f"are theirs; mean fill {100.0 * t['postings'] / (INSTR * t['groups']):.1f} %")
     if overshot is not None:
         print(f"speculation at z = {SPEC_Z}: {overshot} of {nq} queries had a guess above their final k-th score (they would be run again)")
     # A linear reading of the seed experiment: time ~ F groups + a postings + b docs + c lookups, non-negative weights fitted to
