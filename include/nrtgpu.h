@@ -496,6 +496,43 @@ int  nrtgpu_knn_search(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int
                        float boost, int32_t filter_mask, float min_score, nrtgpu_topdocs* out /* n_queries */);
 
 /* ---------------------------------------------------------------------------------------------
+ * knn requests that share a pass although each has a pre-filter, threshold, k and boost of its OWN (float fields).
+ * nrtsearch sends one `knn` request per search thread, each with its own filter (VectorFieldDef.java:580-594, run at
+ * search/KnnUtils.java:56): through nrtgpu_knn_search every one of them pays a pass over the rows alone, and a pass costs the
+ * same for 1 query as for 64.  The two entries below answer up to 64 such requests per pass.
+ * n_queries `knn` requests over the same leaves, field and similarity, each with its OWN k, pre-filter, threshold and boost,
+ * answered in passes of up to 64 queries that share one read of the rows.  Query i gets exactly what
+ * nrtgpu_knn_search(..., queries + i*dim, 1, dim, ks[i], boosts[i], filter_masks[i], min_scores[i], &out[i]) returns:
+ * same docids, ranks, score bits, total_hits (= the hits returned; liveDocs always apply).
+ * A pass is searched with the largest k of its members and scores unboosted; member i takes the first ks[i] hits of its list
+ * and its own boost when the list is unpacked.  On the device a pass brings a table of accept sets (liveDocs & the member's
+ * filter, per leaf and member) and the members' thresholds; a call whose requests are all equal is nrtgpu_knn_search itself,
+ * the gather route (nrtgpu_set_knn_gather) included.
+ * Refusals, per request, are nrtgpu_knn_search's.  NRTGPU_ERR_INVALID_ARG: k <= 0, filter_mask < 0, a min_score that is not
+ * >= 0, a boost that is not finite and > 0, a query dimension other than the field's, a byte field (these are float entry
+ * points), ks == NULL.  NRTGPU_ERR_UNSUPPORTED: k > NRTGPU_MAX_K, dim > 2048, a mask that is not resident on a leaf of the call
+ * that holds the field's rows.  NULL boosts: all 1; NULL filter_masks: none; NULL min_scores: none.  A bad request refuses the
+ * WHOLE call of the batch entry before anything is launched, and nrtgpu_last_error names it ("query <i>: ...").
+ * Thread deadlines: checked on entry and between passes.
+ * nrtgpu_get_stats: a pass counts under knn_panels / knn_rows / knn_score_launches / knn_score_ms / knn_sketch_launches /
+ * knn_second_passes like a pass of nrtgpu_knn_search.
+ * Out of scope: byte fields, the nrtgpu_dist_* forms, the gather route for a pass whose members name different filters (it
+ * always passes over all rows), MUST_NOT masks or several filters per request, and the Java shim.
+ * --------------------------------------------------------------------------------------------- */
+int  nrtgpu_knn_search_requests(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                int32_t field_id, int32_t sim, const float* queries, int32_t n_queries, int32_t dim,
+                                const int32_t* ks, const float* boosts, const int32_t* filter_masks, const float* min_scores,
+                                nrtgpu_topdocs* out /* n_queries; out[i].capacity >= ks[i] */);
+/* What a request thread calls with ONE knn request: blocks; concurrent callers over the same leaves, doc_bases, field,
+ * similarity and dimension share panels of up to 64 whatever their k, filter, threshold and boost.  The leave rule and the caps
+ * are nrtgpu_knn_exact_coalesced's (a queue of its own: the two entries' callers never share a panel).  A bad request -- the
+ * refusals above, its mask's residency on every leaf included -- fails ALONE, before it is queued; a request whose thread
+ * deadline passes in the queue returns NRTGPU_ERR_TIMEOUT ("deadline passed while the request waited for a panel"). */
+int  nrtgpu_knn_search_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                 int32_t field_id, int32_t sim, const float* query, int32_t dim, int32_t k, float boost,
+                                 int32_t filter_mask, float min_score, nrtgpu_topdocs* out);
+
+/* ---------------------------------------------------------------------------------------------
  * Exact search over BYTE (int8) vector fields (nrtgpu_segment_add_byte_vectors).
  * nrtgpu_knn_exact_bytes replaces ExactVectorQuery.ExactByteVectorQuery (query/vector/ExactVectorQuery.java:230-247) as
  * nrtgpu_knn_exact replaces the float query; nrtgpu_knn_search_bytes answers the `knn` request path over a byte field

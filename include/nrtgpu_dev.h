@@ -18,9 +18,9 @@ extern "C" {
 int  nrtgpu_bench_closed_loop(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
                               const nrtgpu_bm25_query* queries, int32_t n_queries, int32_t clients, int32_t duration_ms,
                               double* out4);
-/* TEST HOOKS for the two coalescers (this one and nrtgpu_knn_exact_coalesced).  hold != 0: no leader leaves with less than a
+/* TEST HOOKS for the coalescers (this one, nrtgpu_knn_exact_coalesced and nrtgpu_knn_search_coalesced).  hold != 0: no leader leaves with less than a
  * full batch (max_batch queries) / panel (64 queries) until the hold is released -- a test queues a known set of callers behind
- * it, waits until nrtgpu_debug_coalescer_pending (which: 0 = BM25, 1 = exact vector search) reports all of them, releases,
+ * it, waits until nrtgpu_debug_coalescer_pending (which: 0 = BM25, 1 = exact vector search, 2 = knn requests) reports all of them, releases,
  * and may then assert the batches formed BY CONSTRUCTION (what a batch is must not depend on the host's speed).  Not for
  * production callers: a held coalescer parks every request. */
 int  nrtgpu_debug_hold_coalescers(nrtgpu_ctx* ctx, int32_t hold);
@@ -57,6 +57,13 @@ int  nrtgpu_debug_term_lookup(const nrtgpu_seg* seg, int32_t field_id, int64_t t
  * built)}. */
 int  nrtgpu_debug_knn_bounds(int32_t sim, int32_t dim, double q_norm2, double q_l1, float q_absmax, double nv_max, double nv_min,
                              float rows_absmax, float score_boost, double m, double s, double* out10);
+/* TEST HOOK for the unpacking of a knn request panel (nrtgpu_knn_search_requests: a pass is searched with the largest k of its
+ * members, k_pass) -- no context, no device work.  scores / docs: n_queries lists of k_stride (>= k_pass) entries sorted by (score
+ * desc, doc asc), counts[q] of them valid (<= k_stride).  Member q gets the first min(counts[q], ks[q], out[q].capacity) hits, its
+ * scores multiplied by boosts[q] (equal products re-ordered by docid), total_hits = the hits returned.  NULL ks / boosts: k_pass / 1
+ * for all. */
+int  nrtgpu_debug_knn_unpack(const float* scores, const int32_t* docs, const uint32_t* counts, int32_t k_stride, int32_t n_queries,
+                             int32_t k_pass, const int32_t* ks, const float* boosts, nrtgpu_topdocs* out);
 
 #define NRTGPU_FLAG_PROFILE (7 << 8)  /* instrumented kernels (same results): per-item phase cycle and event counters
                                        * (nrtgpu_get_scan_profile, nrtgpu_get_maxscore_profile).  Bits 8-11 hold no other

@@ -44,7 +44,7 @@ ABI_SYMBOLS = [
     "nrtgpu_search_bm25", "nrtgpu_search_bm25_batch", "nrtgpu_search_bm25_batch_device",
     "nrtgpu_search_bm25_batch_device_epoch", "nrtgpu_exchange_open", "nrtgpu_exchange_close",
     "nrtgpu_search_bm25_coalesced", "nrtgpu_set_coalescing", "nrtgpu_query_supported",
-    "nrtgpu_merge_topk_device", "nrtgpu_knn_exact", "nrtgpu_knn_exact_coalesced", "nrtgpu_knn_search", "nrtgpu_rescore_vectors", "nrtgpu_search_hybrid_batch",
+    "nrtgpu_merge_topk_device", "nrtgpu_knn_exact", "nrtgpu_knn_exact_coalesced", "nrtgpu_knn_search", "nrtgpu_knn_search_requests", "nrtgpu_knn_search_coalesced", "nrtgpu_rescore_vectors", "nrtgpu_search_hybrid_batch",
     "nrtgpu_int_to_byte4", "nrtgpu_byte4_to_int", "nrtgpu_bm25_idf", "nrtgpu_bm25_avgdl",
     "nrtgpu_bm25_norm_cache", "nrtgpu_slices", "nrtgpu_plan_item_counts", "nrtgpu_fixed_point_scale", "nrtgpu_get_stats", "nrtgpu_reset_stats",
     "nrtgpu_set_slicing",
@@ -61,7 +61,7 @@ ABI_SYMBOLS = [
 DEV_SYMBOLS = [
     "nrtgpu_bench_closed_loop", "nrtgpu_debug_hold_coalescers", "nrtgpu_debug_coalescer_pending", "nrtgpu_debug_live_segments",
     "nrtgpu_debug_spec_counters", "nrtgpu_get_scan_profile", "nrtgpu_get_maxscore_profile", "nrtgpu_get_maxscore_item_walls",
-    "nrtgpu_debug_dist_inject", "nrtgpu_debug_term_lookup", "nrtgpu_debug_knn_bounds",
+    "nrtgpu_debug_dist_inject", "nrtgpu_debug_term_lookup", "nrtgpu_debug_knn_bounds", "nrtgpu_debug_knn_unpack",
     "nrtgpu_debug_maxscore_meetings", "nrtgpu_debug_wave_kth", "nrtgpu_debug_walk_rows", "nrtgpu_debug_walk_value",
 ]
 DEV_LIB_PATH = os.path.join(_HERE, "libnrtgpu_dev.so")
@@ -192,6 +192,9 @@ def _open(path: str) -> C.CDLL:
     L.nrtgpu_knn_exact_coalesced.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, f32, C.POINTER(TopDocs)]
     L.nrtgpu_knn_exact_coalesced.restype = i32
     L.nrtgpu_knn_search.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, i32, f32, i32, f32, C.POINTER(TopDocs)]
+    L.nrtgpu_knn_search_requests.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, C.POINTER(TopDocs)]
+    L.nrtgpu_knn_search_coalesced.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, f32, i32, f32, C.POINTER(TopDocs)]
+    L.nrtgpu_knn_search_coalesced.restype = i32
     L.nrtgpu_segment_add_byte_vectors.argtypes = [vp, i32, i32, i32, vp, vp]
     L.nrtgpu_knn_exact_bytes.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, i32, f32, C.POINTER(TopDocs)]
     L.nrtgpu_knn_search_bytes.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, i32, f32, i32, f32, C.POINTER(TopDocs)]
@@ -255,6 +258,8 @@ def _open(path: str) -> C.CDLL:
         L.nrtgpu_debug_walk_value.argtypes = [f32, vp, vp, i32, vp, i32, C.c_uint32, vp]
     if hasattr(L, "nrtgpu_debug_knn_bounds"):
         L.nrtgpu_debug_knn_bounds.argtypes = [i32, i32, C.c_double, C.c_double, f32, C.c_double, C.c_double, f32, f32, C.c_double, C.c_double, vp]
+    if hasattr(L, "nrtgpu_debug_knn_unpack"):
+        L.nrtgpu_debug_knn_unpack.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, C.POINTER(TopDocs)]
     L.nrtgpu_set_slicing.argtypes = [vp, i32, i32, i32]
     L.nrtgpu_blend.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(TopDocs)]
     L.nrtgpu_dist_unique_id.argtypes = [vp]

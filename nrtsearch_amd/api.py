@@ -396,7 +396,7 @@ class GpuContext:
         _lib.check(_lib.load().nrtgpu_debug_hold_coalescers(self._h, 1 if hold else 0))
 
     def debug_coalescer_pending(self, which: int) -> int:
-        """Requests parked in a coalescer: 0 = nrtgpu_search_bm25_coalesced, 1 = nrtgpu_knn_exact_coalesced."""
+        """Requests parked in a coalescer: 0 = nrtgpu_search_bm25_coalesced, 1 = nrtgpu_knn_exact_coalesced, 2 = nrtgpu_knn_search_coalesced."""
         return int(_lib.load().nrtgpu_debug_coalescer_pending(self._h, int(which)))
 
     def debug_dist_inject(self, step: int = -1, failed_query: int = -1) -> None:
@@ -979,6 +979,50 @@ class GpuIndexSearcher:
                                                  C.c_float(boost), int(filter.mask_id) if filter else 0,
                                                  C.c_float(min_score), outs))
         return _topdocs_lists(outs, docs, scores, nq)
+
+    def knn_search_requests(self, field: int, similarity: str, queries: np.ndarray, ks: Sequence[int], boosts: Optional[Sequence[float]] = None,
+                            filters: Optional[Sequence[Optional[MaskFilter]]] = None,
+                            min_scores: Optional[Sequence[float]] = None) -> List[TopDocs]:
+        """`knn` requests with a k, boost, filter and threshold EACH, answered in passes of up to 64 that share one read of the rows
+        (nrtgpu_knn_search_requests): query i gets what knn_search gives it alone."""
+        queries = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+        if similarity == "normalized_cosine":
+            queries = np.ascontiguousarray(queries / np.linalg.norm(queries, axis=1, keepdims=True).astype(np.float32), dtype=np.float32)
+        nq, dim = queries.shape
+        ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
+        boosts = None if boosts is None else np.ascontiguousarray(boosts, dtype=np.float32).reshape(-1)
+        masks = None if filters is None else np.array([int(f.mask_id) if f is not None else 0 for f in filters], dtype=np.int32)
+        min_scores = None if min_scores is None else np.ascontiguousarray(min_scores, dtype=np.float32).reshape(-1)
+        for name, a in (("ks", ks), ("boosts", boosts), ("filters", masks), ("min_scores", min_scores)):
+            if a is not None and a.shape[0] != nq:
+                raise ValueError(f"{name}: {a.shape[0]} values for {nq} queries")
+        outs, docs, scores = _topdocs_outputs(nq, max(int(ks.max()), 1))
+        _lib.check(_lib.load().nrtgpu_knn_search_requests(self.ctx._h, self._segs, self._bases, len(self.leaves), int(field),
+                                                          self.SIMILARITY[similarity], queries.ctypes.data, nq, dim, ks.ctypes.data,
+                                                          boosts.ctypes.data if boosts is not None else None,
+                                                          masks.ctypes.data if masks is not None else None,
+                                                          min_scores.ctypes.data if min_scores is not None else None, outs))
+        return _topdocs_lists(outs, docs, scores, nq)
+
+    def knn_search_coalesced(self, field: int, similarity: str, query: np.ndarray, k: int, boost: float = 1.0,
+                             filter: Optional[MaskFilter] = None, min_score: float = 0.0) -> TopDocs:
+        """What a request thread calls with ONE `knn` request: concurrent callers share panels of up to 64 whatever their k, filter,
+        threshold and boost (nrtgpu_knn_search_coalesced)."""
+        query = np.ascontiguousarray(query, dtype=np.float32).reshape(-1)
+        if similarity == "normalized_cosine":
+            query = np.ascontiguousarray(query / np.linalg.norm(query).astype(np.float32), dtype=np.float32)
+        k = int(k)
+        out = _lib.TopDocs()
+        docs = np.zeros(max(k, 1), dtype=np.int32)
+        scores = np.zeros(max(k, 1), dtype=np.float32)
+        out.capacity = max(k, 1)
+        out.docs = docs.ctypes.data_as(C.POINTER(C.c_int32))
+        out.scores = scores.ctypes.data_as(C.POINTER(C.c_float))
+        _lib.check(_lib.load().nrtgpu_knn_search_coalesced(self.ctx._h, self._segs, self._bases, len(self.leaves), int(field),
+                                                           self.SIMILARITY[similarity], query.ctypes.data, int(query.shape[0]), k,
+                                                           C.c_float(boost), int(filter.mask_id) if filter else 0, C.c_float(min_score),
+                                                           C.byref(out)))
+        return TopDocs(docs[: out.n_hits].copy(), scores[: out.n_hits].copy(), int(out.total_hits), bool(out.total_hits_is_lower_bound))
 
     # ---- byte (int8) vector fields: ExactByteVectorQuery / NrtKnnByteVectorQuery ---------------------
     BYTE_SIMILARITY = {"cosine": 0, "dot_product": 1, "l2_norm": 2, "max_inner_product": 3}

@@ -79,6 +79,18 @@ extern "C" int nrtgpu_debug_knn_bounds(int32_t sim, int32_t dim, double q_norm2,
   return NRTGPU_OK;
 }
 
+// Test hook (include/nrtgpu_dev.h): a panel's sorted keys -> its members' nrtgpu_topdocs as the knn request entries unpack them
+// (vectors.cpp: knn_unpack_topdocs with a k and a boost per member).  No context, no device work.
+extern "C" int nrtgpu_debug_knn_unpack(const float* scores, const int32_t* docs, const uint32_t* counts, int32_t k_stride, int32_t n_queries,
+                                       int32_t k_pass, const int32_t* ks, const float* boosts, nrtgpu_topdocs* out) {
+  if (!scores || !docs || !counts || !out || n_queries <= 0 || k_pass <= 0 || k_stride < k_pass) return fail(NRTGPU_ERR_INVALID_ARG, "bad knn_unpack arguments");
+  std::vector<uint64_t> keys((size_t)n_queries * (size_t)k_stride, 0ull);
+  for (size_t i = 0; i < keys.size(); ++i)
+    if ((uint32_t)(i % (size_t)k_stride) < counts[i / (size_t)k_stride]) keys[i] = pack_key(scores[i], (uint32_t)docs[i]);
+  knn_unpack_topdocs(keys.data(), counts, (uint32_t)k_stride, n_queries, k_pass, false, 0, true, 1.0f, out, ks, boosts);
+  return NRTGPU_OK;
+}
+
 // The MaxScore route's meetings (include/nrtgpu_dev.h), from the instrumented kernels' per-item counters (search.cpp takes them
 // out of the profile rows).
 extern "C" int nrtgpu_debug_maxscore_meetings(nrtgpu_ctx* ctx, int64_t* out4) {

@@ -237,7 +237,12 @@ void knn_score_kernel(const float* __restrict__ vecs, const float* __restrict__ 
                       int32_t dim, int64_t row_begin, int64_t row_end, int32_t doc_base,
                       const float* __restrict__ qpanel, const float* __restrict__ qnorm2, int32_t n_q, int32_t sim,
                       float boost, const unsigned long long* __restrict__ theta, uint64_t* __restrict__ cand,
-                      uint32_t* __restrict__ cand_cnt, uint32_t cap, int32_t append_only) {
+                      uint32_t* __restrict__ cand_cnt, uint32_t cap, int32_t mode) {
+  // mode & kKnnAcceptTable: live_bits is not one set but this leaf's row of the pass's accept table (plan.h: kKnnAcceptCols
+  // pointers) -- query q's rows are tested against entry q (a NULL entry: every doc); columns at or beyond n_q are never read.
+  // (The kernel's parameter list is what the recorded launch schedules of the existing entries name: the table comes in through it.)
+  const uint64_t* const* accept_of = (mode & kKnnAcceptTable) ? (const uint64_t* const*)live_bits : nullptr;
+  const int32_t append_only = mode & kKnnAppendOnly;
   // append_only: this launch is not followed by a selection (the host defers it once theta is tight): a query whose theta is
   // still unknown appends its live rows like everybody else instead of taking per-row slots a later launch would overwrite
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -256,6 +261,7 @@ void knn_score_kernel(const float* __restrict__ vecs, const float* __restrict__ 
     theta += panel * 32u;
     cand += (size_t)panel * 32u * (size_t)cap;
     cand_cnt += panel * 32u;
+    if (accept_of) accept_of += panel * 32u;
     n_q = panel ? n_q - 32 : 32;
   }
   const uint32_t j = lane & 15u, kk = lane >> 4;
@@ -308,9 +314,13 @@ void knn_score_kernel(const float* __restrict__ vecs, const float* __restrict__ 
             else est = knn_map_score(sim, dot, nq[p], nv, 1.0f);
             if (est * boost >= th_lo[p]) {
               const int32_t ldoc = ord_to_doc ? ord_to_doc[drow] : (int32_t)drow;
+              // (the query's own set where the pass has a table: read here, where few rows arrive once theta is known)
+              // (a pointer out of memory is generic to the compiler: said to be global, the bits come by a global load as before)
+              typedef const __attribute__((address_space(1))) uint64_t* gbits_ptr;
+              const gbits_ptr lb = (gbits_ptr)(accept_of ? accept_of[q] : live_bits);
               bool live = true;
-              if (live_bits) live = (live_bits[ldoc >> 6] >> (ldoc & 63)) & 1ull;
-              uint64_t key = 0;  // 0 = "nothing": never above a theta
+              if (lb) live = (lb[ldoc >> 6] >> (ldoc & 63)) & 1ull;
+              uint64_t key = 0;  // 0 = "nothing": never above a theta (a row outside the query's set still owns its slot below)
               if (live) key = pack_key(knn_map_score(sim, dot, nq[p], nv, boost), (uint32_t)(doc_base + ldoc));
               if (th[p] == 0ull && !append_only) {
                 // no theta yet (the query's first round, never longer than the list): every row is a
@@ -464,6 +474,9 @@ void knn_sketch_kernel(const DKnnLeaf* __restrict__ leaves, int32_t n_leaves, in
                        int32_t n_q, int32_t sim, float boost, const unsigned long long* __restrict__ theta,
                        uint64_t* __restrict__ cand, uint32_t* __restrict__ cand_cnt, uint32_t cap, int32_t append_only,
                        uint32_t qcap) {
+  // A leaf that brings a row of the pass's accept table (DKnnLeaf::accept_of, plan.h): a row nominated for query q is tested
+  // against entry q instead of the leaf's one set (a NULL entry: every doc).  Read where a key is made: in the flush of the
+  // queue, and where a row goes straight to its list; the stream itself knows nothing of it.
   extern __shared__ __attribute__((aligned(16))) char smem[];
   f16x8* qs = (f16x8*)smem;  // [steps][P][64]: step s, panel p, lane l -> q[(l & 15) + 16p][32s + 8(l >> 4) .. +7] * qscale
   // Behind the panel: the workgroup's queue of nominations (qcap entries: score bits << 32 | padded row << 6 | query).
@@ -521,6 +534,7 @@ void knn_sketch_kernel(const DKnnLeaf* __restrict__ leaves, int32_t n_leaves, in
     const float leaf_inv = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(lf.inv_rows_scale)));
     const int32_t* const ord_to_doc = (const int32_t*)u_o2d;
     const uint64_t* const live_bits = (const uint64_t*)u_accept;
+    const uint64_t* const* const accept_of = (const uint64_t* const*)uniform_u64((uint64_t)lf.accept_of);
     // Can any of a lane's 4 P estimates of a tile pass?  The estimate is a non-decreasing function of acc x (a per-row factor) for
     // COSINE, DOT_PRODUCT and MAXIMUM_INNER_PRODUCT, so "estimate > theta's score" has a necessary condition that costs one
     // multiply and one compare per element: acc x factor > xthr[p] -- xthr lowered by 2^-16 of the scale the estimate's own
@@ -668,8 +682,9 @@ void knn_sketch_kernel(const DKnnLeaf* __restrict__ leaves, int32_t n_leaves, in
                 uint64_t key = 0;  // 0 = "nothing": never above a theta
                 if (valid) {
                   const int32_t ldoc = ord_to_doc ? ord_to_doc[drow] : (int32_t)drow;
+                  const uint64_t* const lb = accept_of ? accept_of[qv] : live_bits;
                   bool live = true;
-                  if (live_bits) live = (live_bits[ldoc >> 6] >> (ldoc & 63)) & 1ull;
+                  if (lb) live = (lb[ldoc >> 6] >> (ldoc & 63)) & 1ull;
                   if (live) key = pack_key(sc, (uint32_t)(doc_base + ldoc));
                 }
                 if (slot_round) {
@@ -721,8 +736,9 @@ void knn_sketch_kernel(const DKnnLeaf* __restrict__ leaves, int32_t n_leaves, in
       const DKnnLeaf lf = leaves[knn_leaf_of_tile(leaves, n_leaves, tile)];
       const int64_t drow = ((tile - lf.tile_begin) << 4) + (gpos & 15);
       const int32_t ldoc = lf.ord_to_doc ? lf.ord_to_doc[drow] : (int32_t)drow;
+      const uint64_t* const lb = lf.accept_of ? lf.accept_of[q] : lf.accept;   // (q < n_q: a queue entry's query)
       bool live = true;
-      if (lf.accept) live = (lf.accept[ldoc >> 6] >> (ldoc & 63)) & 1ull;
+      if (lb) live = (lb[ldoc >> 6] >> (ldoc & 63)) & 1ull;
       const uint64_t key = pack_key(__uint_as_float((uint32_t)(e >> 32)), (uint32_t)(lf.doc_base + ldoc));
       if (live && key > theta[q]) {
         my_q[r] = q;
@@ -761,9 +777,10 @@ struct KnnRefine {
   const float* qpanel;      // the panel's queries, row-major
   const float* qnorm2;
   const float* ebound;      // per query: e_abs of knn_result_upper / knn_estimate_lower (plan.h)
+  const float* min_score;   // per query: results below it are no hits (0: no threshold)
   uint32_t* cert;
   int32_t n_segs, dim, sim, certify;
-  float boost, erel, min_score;
+  float boost, erel;
   uint32_t k_int;
 };
 
@@ -792,6 +809,8 @@ void knn_select_kernel(uint64_t* __restrict__ topk, uint32_t* __restrict__ topk_
   __syncthreads();
   const uint32_t n_prev = topk_cnt[q];
   const uint32_t n_raw = cand_cnt[q];
+  float min_score = 0.0f;   // the query's own threshold
+  if (REFINE) min_score = rf.min_score[q];
   if (n_raw > cap && tid == 0) *overflow = 1u;  // the host shrinks the round and repeats it
   const uint32_t n_cand = min(n_raw, cap);
   for (int pass = 0; pass < 2; ++pass) {
@@ -807,7 +826,7 @@ void knn_select_kernel(uint64_t* __restrict__ topk, uint32_t* __restrict__ topk_
         key = 0ull;
         if (v) {
           const float sc = knn_score_seq(rf.sim, qv, v, rf.dim, rf.qnorm2[q], rf.boost);
-          if (!(rf.min_score > 0.0f) || sc >= rf.min_score) key = pack_key(sc, gdoc);
+          if (!(min_score > 0.0f) || sc >= min_score) key = pack_key(sc, gdoc);
         }
       }
       const bool want = (i < c) && (key > s.theta);
@@ -860,7 +879,7 @@ void knn_select_kernel(uint64_t* __restrict__ topk, uint32_t* __restrict__ topk_
       if (!ok) {
         // a row of the answer scores >= the k-th rescored score (or >= min_score while fewer than k are known): the lowest key
         // its estimate can carry
-        const double base = n == k ? (double)key_score(s.cand[k - 1]) : (double)rf.min_score * b;
+        const double base = n == k ? (double)key_score(s.cand[k - 1]) : (double)min_score * b;
         const float lo = (float)knn_estimate_lower(rf.sim, base, e_abs, e_rel, b);
         th = lo > 0.0f ? pack_key(lo, 0xFFFFFFFFu) - 1ull : 0ull;
       }
@@ -1078,13 +1097,16 @@ size_t knn_score_lds_bytes(int32_t dim, int32_t n_q) { return (size_t)(dim >> 4)
 int launch_knn_score(hipStream_t st, uint32_t blocks, const float* vecs, const float* vnorm2, const int32_t* ord_to_doc,
                      const uint64_t* live_bits, int32_t dim, int64_t row_begin, int64_t row_end, int32_t doc_base,
                      const float* qpanel, const float* qnorm2, int32_t n_q, int32_t sim, float boost,
-                     const unsigned long long* theta, uint64_t* cand, uint32_t* cand_cnt, uint32_t cap, int32_t append_only) {
+                     const unsigned long long* theta, uint64_t* cand, uint32_t* cand_cnt, uint32_t cap, int32_t append_only,
+                     const uint64_t* const* accept_of) {
   if (row_end <= row_begin) return 0;
   const size_t lds = knn_score_lds_bytes(dim, n_q);
   hipError_t e = hipFuncSetAttribute((const void*)knn_score_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(knn_score_kernel, dim3(blocks), dim3(kKnnThreads), lds, st, vecs, vnorm2, ord_to_doc, live_bits, dim,
-                     row_begin, row_end, doc_base, qpanel, qnorm2, n_q, sim, boost, theta, cand, cand_cnt, cap, append_only);
+  hipLaunchKernelGGL(knn_score_kernel, dim3(blocks), dim3(kKnnThreads), lds, st, vecs, vnorm2, ord_to_doc,
+                     accept_of ? (const uint64_t*)accept_of : live_bits, dim,
+                     row_begin, row_end, doc_base, qpanel, qnorm2, n_q, sim, boost, theta, cand, cand_cnt, cap,
+                     (append_only ? kKnnAppendOnly : 0) | (accept_of ? kKnnAcceptTable : 0));
   return 0;
 }
 int32_t knn_sketch_steps(int32_t dim) { return (((dim + 31) >> 5) + 3) & ~3; }   // 32 dimensions per step, whole groups of 4 steps (zero padded)
@@ -1148,7 +1170,7 @@ void launch_knn_select(hipStream_t st, uint32_t n_q, uint64_t* topk, uint32_t* t
 void launch_knn_refine_select(hipStream_t st, uint32_t n_q, uint64_t* topk, uint32_t* topk_cnt, uint32_t k_stride, uint32_t k,
                               const uint64_t* cand, uint32_t* cand_cnt, uint32_t cap, unsigned long long* theta, uint32_t* overflow,
                               const DVecSeg* segs, int32_t n_segs, int32_t dim, int32_t sim, const float* qpanel, const float* qnorm2,
-                              float boost, const float* ebound, float erel, float min_score, uint32_t k_int, int32_t certify,
+                              float boost, const float* ebound, float erel, const float* min_score, uint32_t k_int, int32_t certify,
                               uint32_t* cert) {
   KnnRefine rf{};
   rf.segs = segs; rf.qpanel = qpanel; rf.qnorm2 = qnorm2; rf.ebound = ebound; rf.cert = cert;

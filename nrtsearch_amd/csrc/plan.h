@@ -382,9 +382,17 @@ struct alignas(16) DKnnLeaf {
   int64_t tile_begin;
   int32_t n_rows, doc_base;
   float inv_rows_scale;        // 1 / the power of two the rows were multiplied by
-  int32_t pad[3];
+  int32_t pad;
+  const uint64_t* const* accept_of;   // nullptr, or the leaf's row of the pass's accept table (kKnnAcceptCols below): `accept` per query
 };
 static_assert(sizeof(DKnnLeaf) == 64, "DKnnLeaf layout");
+// A pass whose queries carry filters of their own (nrtgpu_knn_search_requests) brings a table of accept sets next to the leaves:
+// kKnnAcceptCols pointers per leaf, entry q = liveDocs & query q's filter on that leaf (nullptr: every doc).  Columns at or beyond
+// the pass's queries hold nullptr and are never read.  Without a table (nullptr) every query takes DKnnLeaf::accept.  The sketch
+// kernel finds a leaf's row in its DKnnLeaf; the fp32 row kernel (a launch per leaf) is handed the row in place of the leaf's set,
+// said by a bit of its `mode` argument.
+constexpr int kKnnAcceptCols = 64;
+constexpr int32_t kKnnAppendOnly = 1, kKnnAcceptTable = 2;   // knn_score_kernel's mode
 
 // Exact vector search: the matrix-core ESTIMATE of a score against the RESULT (the same similarity summed in the oracle's
 // order).  e_abs bounds |estimate - result| -- for EUCLIDEAN of the squared distance (the score 1 / (1 + d2) flattens with d2: a

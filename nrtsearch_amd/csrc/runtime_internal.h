@@ -88,14 +88,15 @@ void launch_knn_row_norms(hipStream_t st, const float* vecs, int32_t dim, int64_
 int launch_knn_score(hipStream_t st, uint32_t blocks, const float* vecs, const float* vnorm2, const int32_t* ord_to_doc,
                      const uint64_t* live_bits, int32_t dim, int64_t row_begin, int64_t row_end, int32_t doc_base,
                      const float* qpanel, const float* qnorm2, int32_t n_q, int32_t sim, float boost,
-                     const unsigned long long* theta, uint64_t* cand, uint32_t* cand_cnt, uint32_t cap, int32_t append_only = 0);
+                     const unsigned long long* theta, uint64_t* cand, uint32_t* cand_cnt, uint32_t cap, int32_t append_only = 0,
+                     const uint64_t* const* accept_of = nullptr);   // this leaf's row of the pass's accept table (plan.h: kKnnAcceptCols)
 void launch_knn_select(hipStream_t st, uint32_t n_q, uint64_t* topk, uint32_t* topk_cnt, uint32_t k_stride, uint32_t k,
                        const uint64_t* cand, uint32_t* cand_cnt, uint32_t cap, unsigned long long* theta,
                        uint32_t* overflow);
 void launch_knn_refine_select(hipStream_t st, uint32_t n_q, uint64_t* topk, uint32_t* topk_cnt, uint32_t k_stride, uint32_t k,
                               const uint64_t* cand, uint32_t* cand_cnt, uint32_t cap, unsigned long long* theta, uint32_t* overflow,
                               const DVecSeg* segs, int32_t n_segs, int32_t dim, int32_t sim, const float* qpanel, const float* qnorm2,
-                              float boost, const float* ebound, float erel, float min_score, uint32_t k_int, int32_t certify,
+                              float boost, const float* ebound, float erel, const float* min_score /* per query */, uint32_t k_int, int32_t certify,
                               uint32_t* cert);
 void launch_knn_norm_max(hipStream_t st, const float* norm2, int64_t n, uint32_t* out_bits);
 void launch_knn_norm_min(hipStream_t st, const float* norm2, int64_t n, uint32_t* out_bits);
@@ -552,8 +553,8 @@ struct nrtgpu_ctx {
   double ms_prof[16] = {0};   // the same for the items of the MaxScore route (nrtgpu_get_maxscore_profile)
   int64_t ms_meetings[4] = {0};   // ... and their meetings, overflow meetings, compactions, one-wave estimates (nrtgpu_debug_maxscore_meetings)
   // request coalescing (coalescer.h): the single-query entries' callers merged into batches (nrtgpu_search_bm25_coalesced, search.cpp)
-  // and into panels (nrtgpu_knn_exact_coalesced, vectors.cpp)
-  nrtgpu::rt::Coalescer co, kco;
+  // and into panels (nrtgpu_knn_exact_coalesced on kco, nrtgpu_knn_search_coalesced on rco: vectors.cpp)
+  nrtgpu::rt::Coalescer co, kco, rco;
   int32_t co_linger_us = 150;   // (under co.mu: nrtgpu_set_coalescing)
   // speculative thresholds (plan.h: kHitsSpecInvalid; nrtgpu_debug_spec_counters): queries run under speculation, queries whose guess
   // failed and were run again, and the switch the library throws itself when too many fail (docs not spread like a sample)
@@ -754,9 +755,10 @@ struct KnnRun {
   void add_stats(int64_t rows, int64_t sketch_launches, bool second_pass);
 };
 // A panel's sorted keys -> the callers' nrtgpu_topdocs.  clamp_to_k: counts[q] may exceed k (the byte search's running list).
-// knn_request: totalHits = the docs returned, the boost applied afterwards; else `total`.
+// knn_request: totalHits = the docs returned, the boost applied afterwards; else `total`.  ks / boosts (NULL: k / boost for all): a
+// k and a boost per member of a panel that was searched with the largest k -- member q takes the first ks[q] keys of its list.
 void knn_unpack_topdocs(const uint64_t* keys, const uint32_t* counts, uint32_t k_stride, int nq, int32_t k, bool clamp_to_k, int64_t total,
-                        bool knn_request, float boost, nrtgpu_topdocs* out);
+                        bool knn_request, float boost, nrtgpu_topdocs* out, const int32_t* ks = nullptr, const float* boosts = nullptr);
 
 // ---- the gather route of the filtered knn entries (vectors_gather.cpp) -------------------------------------------
 // A filtered knn request (nrtgpu_knn_search, nrtgpu_knn_search_bytes; filter_mask != 0) whose filter accepts few enough rows reads

@@ -64,12 +64,16 @@ void nrtgpu::rt::KnnRun::add_stats(int64_t rows, int64_t sketch_launches, bool s
   ctx->stats.knn_sketch_launches += sketch_launches;
   n_ev = 0;
 }
-void nrtgpu::rt::knn_unpack_topdocs(const uint64_t* keys, const uint32_t* counts, uint32_t k_stride, int nq, int32_t k, bool clamp_to_k,
-                                    int64_t total, bool knn_request, float boost, nrtgpu_topdocs* out) {
+void nrtgpu::rt::knn_unpack_topdocs(const uint64_t* keys, const uint32_t* counts, uint32_t k_stride, int nq, int32_t k_all, bool clamp_to_k,
+                                    int64_t total, bool knn_request, float boost_all, nrtgpu_topdocs* out, const int32_t* ks,
+                                    const float* boosts) {
   for (int q = 0; q < nq; ++q) {
     nrtgpu_topdocs* o = &out[q];
+    // (a member of a pass searched with the largest k of its members takes the first k of its own: a prefix of a sorted list)
+    const int32_t k = ks ? ks[q] : k_all;
+    const float boost = boosts ? boosts[q] : boost_all;
     const int32_t cap = o->capacity > 0 ? o->capacity : k;
-    const int32_t m = std::min<int32_t>((int32_t)(clamp_to_k ? std::min<uint32_t>(counts[q], (uint32_t)k) : counts[q]), cap);
+    const int32_t m = std::min<int32_t>((int32_t)(clamp_to_k || ks ? std::min<uint32_t>(counts[q], (uint32_t)k) : counts[q]), cap);
     for (int32_t i = 0; i < m; ++i) {
       if (o->docs) o->docs[i] = (int32_t)key_doc(keys[(size_t)q * k_stride + i]);
       if (o->scores) o->scores[i] = key_score(keys[(size_t)q * k_stride + i]);
@@ -145,11 +149,22 @@ static int knn_check_scalars(bool bad_count, int32_t k, int32_t dim, int32_t sim
   return NRTGPU_OK;
 }
 
+// What differs from request to request in a call of nrtgpu_knn_search_requests: one value per query, none of them NULL here.
+struct KnnPerQuery {
+  const int32_t* ks;
+  const float* boosts;
+  const int32_t* masks;
+  const float* min_scores;
+};
+
 static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
                     int32_t field_id, int32_t sim, const float* queries, int32_t n_queries, int32_t dim,
                     int32_t k, float boost, bool knn_request, int32_t filter_mask, float min_score, nrtgpu_topdocs* out,
-                    char* ext_keys = nullptr, char* ext_cnts = nullptr, char* ext_hits = nullptr) {
+                    char* ext_keys = nullptr, char* ext_cnts = nullptr, char* ext_hits = nullptr, const KnnPerQuery* pq = nullptr) {
   forget_foreign_hip_error();
+  // pq: the queries are knn requests with a k, boost, filter and threshold EACH (nrtgpu_knn_search_requests); `k` is the largest
+  // of theirs, filter_mask / min_score / boost are not read.  The device differs in two inputs only: a table of accept sets per
+  // (leaf, query) in place of the leaf's one, and the thresholds -- an array for every caller -- hold the queries' own.
   // ext_*: device-resident results instead of `out` (the multi-GPU path): per query k_stride sorted keys, its count, and the live
   // vectors of these leaves as the hit total -- the layout the exchange stage takes
   if (!ctx || !queries || (!out && !ext_keys) || (n_segs > 0 && !segs)) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
@@ -166,7 +181,7 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
   if (int rc = pad_query_vectors(segs, n_segs, field_id, queries, n_queries, dim, &padded)) return rc;
   queries = padded.p;
   dim = padded.dim;
-  if (knn_request && filter_mask != 0) {   // a selective filter: score only the rows it accepts (vectors_gather.cpp) -- no sketch is built or read
+  if (knn_request && filter_mask != 0 && !pq) {   // a selective filter: score only the rows it accepts (vectors_gather.cpp) -- no sketch is built or read
     const KnnGatherCall call{false, field_id, sim, k, filter_mask, dim, boost, min_score, queries, nullptr, n_queries, kKnnCap};
     bool gather = false;
     int64_t estimate = 0;
@@ -191,6 +206,8 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
   const size_t o_eb16 = wc.take(kKnnMaxQ * 4), o_qs = wc.take(kKnnMaxQ * 4);
   const size_t o_segs = wc.take((size_t)std::max(n_segs, 1) * sizeof(DVecSeg));
   const size_t o_leaves = wc.take((size_t)std::max(n_segs, 1) * sizeof(DKnnLeaf));   // the sketch kernel's leaf table (plan.h)
+  const size_t o_ms = wc.take(kKnnMaxQ * 4);   // the queries' thresholds on the unboosted score (0: none)
+  const size_t o_acc = wc.take(pq ? (size_t)std::max(n_segs, 1) * kKnnAcceptCols * sizeof(uint64_t*) : 8);   // pq: the accept table (plan.h)
   const size_t o_th = wc.take(kKnnMaxQ * 8);
   const size_t o_tk = wc.take((size_t)kKnnMaxQ * ki_stride * 8), o_tc = wc.take(kKnnMaxQ * 4);
   const size_t o_cc = wc.take(kKnnMaxQ * 4), o_xk = wc.take((size_t)kKnnMaxQ * k_stride * 8);
@@ -206,6 +223,10 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
   char* ho = (char*)slot->h_out.p;
   char* hs = (char*)slot->h_aux.p;
   float *qn = (float*)(hs + o_qn), *eb = (float*)(hs + o_eb), *eb16 = (float*)(hs + o_eb16), *qsc = (float*)(hs + o_qs);
+  float* ms = (float*)(hs + o_ms);
+  const uint64_t** hacc = (const uint64_t**)(hs + o_acc);
+  const uint64_t* const* d_acc = pq ? (const uint64_t* const*)(wb + o_acc) : nullptr;
+  std::vector<int32_t> kleaf_seg, kleaf_of_seg((size_t)std::max(n_segs, 1), -1);   // the sketch kernel's leaves <-> the call's
   // the leaves' vector matrices, for docid -> row on the device (the rescoring reads rows by docid)
   (void)stage_rescore_inputs(segs, doc_bases, n_segs, field_id, false, sim, nullptr, 0, dim, hs + o_segs, nullptr, nullptr);
   double nv_max = 0.0, nv_min = INFINITY, rows_unit = 0.0;   // rows_unit: the largest 1 / scale of the leaves' sketches
@@ -231,13 +252,16 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
     const FieldData& f = fit->second;
     live_vectors += live_vector_count(segs[si], f);   // (deleted docs are masked inside the kernel and are no hits)
     const uint64_t* accept = segs[si]->d_live;        // (vectors are not re-coded for liveDocs: always the mask)
-    if (knn_request && filter_mask != 0)
+    if (knn_request && filter_mask != 0 && !pq)
       if (int rc = accept_set_of(segs[si], filter_mask, 0, &accept)) return rc;
+    kleaf_of_seg[(size_t)si] = n_kleaves;
+    kleaf_seg.push_back(si);
     DKnnLeaf l{};
     l.sketch = f.d_sketch;
     l.vnorm2 = f.d_vnorm2;
     l.ord_to_doc = f.d_ord_to_doc;
     l.accept = accept;
+    l.accept_of = d_acc ? d_acc + (size_t)n_kleaves * kKnnAcceptCols : nullptr;
     l.tile_begin = total_tiles;
     l.n_rows = f.n_vec;
     l.doc_base = doc_bases ? doc_bases[si] : 0;
@@ -318,6 +342,24 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
       eb16[(size_t)q] = bound16_of((double)s2, q_l1, 1.0 / (double)qsc[(size_t)q]);
       if (!q_scaled || !std::isfinite(eb16[(size_t)q])) panel_sketch = false;
     }
+    for (int q = 0; q < kKnnMaxQ; ++q) ms[q] = q >= nq ? 0.0f : pq ? pq->min_scores[q0 + q] : knn_request ? min_score : 0.0f;
+    if (pq) {   // liveDocs & the query's filter per (leaf, query): each distinct filter of the pass is looked up once per leaf
+      memset(hacc, 0, (size_t)std::max(n_segs, 1) * kKnnAcceptCols * sizeof(uint64_t*));
+      for (int32_t kl = 0; kl < n_kleaves; ++kl) {
+        const nrtgpu_seg* seg = segs[kleaf_seg[(size_t)kl]];
+        for (int q = 0; q < nq; ++q) {
+          const int32_t mask = pq->masks[q0 + q];
+          const uint64_t*& slot_q = hacc[(size_t)kl * kKnnAcceptCols + q];
+          slot_q = seg->d_live;
+          if (mask == 0) continue;
+          int same = -1;
+          for (int p = 0; p < q && same < 0; ++p)
+            if (pq->masks[q0 + p] == mask) same = p;
+          if (same >= 0) slot_q = hacc[(size_t)kl * kKnnAcceptCols + same];
+          else if (int rc = accept_set_of(seg, mask, 0, &slot_q)) return rc;
+        }
+      }
+    }
     memcpy(hs + o_q, queries + (size_t)q0 * dim, (size_t)nq * dim * 4);
     HIP_TRY(hipMemcpyAsync(wb + o_q, hs + o_q, (size_t)nq * dim * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(wb + o_qn, hs + o_qn, o_th - o_qn, hipMemcpyHostToDevice, st));   // |q|^2, bounds, scales, leaf table
@@ -336,7 +378,7 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
       launch_knn_refine_select(st, (uint32_t)nq, (uint64_t*)(wb + o_xk), (uint32_t*)(wb + o_xc), k_stride, (uint32_t)k,
                                (const uint64_t*)(wb + o_list), (uint32_t*)(wb + o_cnt), cap, (unsigned long long*)(wb + o_th),
                                (uint32_t*)(wb + o_ov), (const DVecSeg*)(wb + o_segs), n_segs, dim, sim, (const float*)(wb + o_q),
-                               (const float*)(wb + o_qn), score_boost, (const float*)(wb + o_bound), erel, knn_request ? min_score : 0.0f,
+                               (const float*)(wb + o_qn), score_boost, (const float*)(wb + o_bound), erel, (const float*)(wb + o_ms),
                                k_int, certify, (uint32_t*)(wb + o_cert));
     };
     auto rows_pass = [&](bool nominate, int safe) -> int {   // (the fp32 rows: a launch per leaf and round)
@@ -355,8 +397,9 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
         const FieldData& f = fit->second;
         total_vec += live_vector_count(seg, f);   // (deleted docs are masked inside the kernel and are no hits)
         const uint64_t* accept = seg->d_live;  // (vectors are not re-coded for liveDocs: always the mask)
-        if (knn_request && filter_mask != 0)
+        if (knn_request && filter_mask != 0 && !pq)
           if (int rc = accept_set_of(seg, filter_mask, 0, &accept)) return rc;
+        const uint64_t* const* leaf_acc = d_acc && kleaf_of_seg[(size_t)si] >= 0 ? d_acc + (size_t)kleaf_of_seg[(size_t)si] * kKnnAcceptCols : nullptr;
         // rounds never exceed the candidate capacity, so a list cannot overflow; theta tightens between rounds
         int64_t r = 0;
         if (seen == 0) round = kFirstRound;
@@ -372,7 +415,7 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
                 return launch_knn_score(st, blocks, f.d_vectors, f.d_vnorm2, f.d_ord_to_doc, accept, dim, r, re, doc_bases ? doc_bases[si] : 0,
                                         (const float*)(wb + o_q), (const float*)(wb + o_qn), nq, sim, score_boost,
                                         (const unsigned long long*)(wb + o_th), (uint64_t*)(wb + o_cd), (uint32_t*)(wb + o_cc), kKnnCap,
-                                        defer ? 1 : 0);
+                                        defer ? 1 : 0, leaf_acc);
               }))
             return rc;
           if (defer) {
@@ -423,10 +466,11 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
     for (int safe = 0;; ++safe) {
       if (int rc = run.take_turn()) return rc;
       HIP_TRY(hipMemsetAsync(wb + o_th, 0, o_cd - o_th, st));  // theta, lists, counters
-      if (knn_request && min_score > 0.0f) {  // start theta below the lowest key whose RESULT can still reach min_score
-        std::vector<uint64_t> th0((size_t)nq);
+      if (std::any_of(ms, ms + nq, [](float v) { return v > 0.0f; })) {  // start theta below the lowest key whose RESULT can still reach the query's min_score
+        std::vector<uint64_t> th0((size_t)nq, 0ull);
         for (int q = 0; q < nq; ++q) {
-          const float lo = (float)knn_estimate_lower(sim, (double)min_score, (double)(panel_sketch ? eb16 : eb)[(size_t)q], (double)erel, 1.0);
+          if (!(ms[q] > 0.0f)) continue;
+          const float lo = (float)knn_estimate_lower(sim, (double)ms[q], (double)(panel_sketch ? eb16 : eb)[(size_t)q], (double)erel, 1.0);
           th0[(size_t)q] = lo > 0.0f ? pack_key(lo, 0xFFFFFFFFu) - 1ull : 0ull;
         }
         HIP_TRY(hipMemcpyAsync(wb + o_th, th0.data(), (size_t)nq * 8, hipMemcpyHostToDevice, st));
@@ -458,7 +502,7 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
       for (int q = 0; q < nq; ++q) {
         if (((const uint32_t*)(ho + oh_cert))[q] != 0u) continue;
         const double base = xc[q] >= (uint32_t)k ? (double)key_score(xk[(size_t)q * k_stride + (size_t)k - 1])
-                                                 : (knn_request ? (double)min_score : 0.0);
+                                                 : (double)ms[q];
         const float lo = (float)knn_estimate_lower(sim, base, (double)bound[(size_t)q], (double)erel, (double)score_boost);
         th2[(size_t)q] = lo > 0.0f ? pack_key(lo, 0xFFFFFFFFu) - 1ull : 0ull;
       }
@@ -509,7 +553,8 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
       HIP_TRY(hipStreamSynchronize(st));   // (tv is a stack vector; the workspace is reused by the next panel)
       continue;
     }
-    knn_unpack_topdocs((const uint64_t*)ho, (const uint32_t*)(ho + oh_cnt), k_stride, nq, k, false, total_vec, knn_request, boost, &out[q0]);
+    knn_unpack_topdocs((const uint64_t*)ho, (const uint32_t*)(ho + oh_cnt), k_stride, nq, k, false, total_vec, knn_request, boost, &out[q0],
+                       pq ? pq->ks + q0 : nullptr, pq ? pq->boosts + q0 : nullptr);
   }
   return NRTGPU_OK;
 }
@@ -539,10 +584,14 @@ struct KnnCoRequest : CoQueued {
   float boost;
   const float* query;
   nrtgpu_topdocs* out;
+  int32_t filter_mask = 0;   // (the knn request entry only: nrtgpu_knn_search_coalesced)
+  float min_score = 0.0f;
 };
 
-static bool knn_co_compatible(const KnnCoRequest* a, const KnnCoRequest* b) {
-  if (a->n_segs != b->n_segs || a->field_id != b->field_id || a->sim != b->sim || a->dim != b->dim || a->boost != b->boost) return false;
+// same_boost: an ExactVectorQuery's boost is inside the scores its panel computes; a knn request's is applied when it is unpacked
+static bool knn_co_compatible(const KnnCoRequest* a, const KnnCoRequest* b, bool same_boost) {
+  if (a->n_segs != b->n_segs || a->field_id != b->field_id || a->sim != b->sim || a->dim != b->dim) return false;
+  if (same_boost && a->boost != b->boost) return false;
   if (a->n_segs && memcmp(a->segs, b->segs, (size_t)a->n_segs * sizeof(void*)) != 0) return false;
   if ((a->doc_bases == nullptr) != (b->doc_bases == nullptr)) return false;
   return !a->doc_bases || memcmp(a->doc_bases, b->doc_bases, (size_t)a->n_segs * 4) == 0;
@@ -587,23 +636,11 @@ extern "C" int nrtgpu_knn_exact_relation(nrtgpu_ctx* ctx, const nrtgpu_seg* cons
   return 0;
 }
 
-extern "C" int nrtgpu_knn_exact_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
-                                          int32_t field_id, int32_t sim, const float* query, int32_t dim, int32_t k, float boost,
-                                          nrtgpu_topdocs* out) {
-  if (!ctx || !query || !out || (n_segs > 0 && !segs)) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
-  // (what would fail the panel must fail this request alone)
-  if (int rc = knn_check_scalars(n_segs < 0, k, dim, sim)) return rc;
-  for (int si = 0; si < n_segs; ++si) {
-    if (!segs[si] || !segs[si]->sealed) return fail(NRTGPU_ERR_STATE, "segment %d missing or not sealed", si);
-    auto fit = segs[si]->fields.find(field_id);
-    if (fit != segs[si]->fields.end() && fit->second.d_vectors && fit->second.dim_user != dim)
-      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d has dimension %d, query has %d", si, field_id, fit->second.dim_user, dim);
-  }
-  NRT_CHECK_DEADLINE("before the request was queued");
-  KnnCoRequest me{{}, segs, doc_bases, n_segs, field_id, sim, dim, k, boost, query, out};
+// The wait of the two single-query vector entries (nrtgpu_knn_exact_coalesced on ctx->kco, nrtgpu_knn_search_coalesced on
+// ctx->rco): one leave rule, one cap.  false: the request travelled in a leader's panel (or expired in the queue), me.rc / me.err
+// and its results are in place.  true: this caller leads *batch -- itself first -- and runs it.
+static bool knn_co_wait(Coalescer& co, KnnCoRequest& me, bool same_boost, std::vector<CoQueued*>* batch) {
   me.deadline_ns = g_deadline_ns;
-  Coalescer& co = ctx->kco;
-  std::vector<CoQueued*> batch;
   {
     std::unique_lock<std::mutex> lk;
     // (a follower wakes the leader when a whole panel waits, or -- device free -- when the last panel's cohort is back)
@@ -612,7 +649,7 @@ extern "C" int nrtgpu_knn_exact_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* con
     });
     if (!leads) {   // travelled in a leader's panel
       if (me.rc != 0) g_last_error = me.err;
-      return me.rc;
+      return false;
     }
     // leader: leave at once when the device is free; else when the running panel finishes, or -- as a second panel in flight,
     // whose launches fill the tails of the first one's -- as soon as a whole panel is waiting
@@ -632,18 +669,24 @@ extern "C" int nrtgpu_knn_exact_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* con
       const bool cohort_due = cohort_rule && co.last_batch > 1 && waiting < std::min(co.last_batch, kKnnMaxQ) && !late;
       return cohort_due ? CoWait::until_linger_end : CoWait::leave;
     });
-    batch = co.form(&me, kKnnMaxQ, [&](const CoQueued* r) { return knn_co_compatible(&me, static_cast<const KnnCoRequest*>(r)); },
-                    deadline_passed, NRTGPU_ERR_TIMEOUT, "deadline passed while the request waited for a panel");
+    *batch = co.form(&me, kKnnMaxQ, [&](const CoQueued* r) { return knn_co_compatible(&me, static_cast<const KnnCoRequest*>(r), same_boost); },
+                     deadline_passed, NRTGPU_ERR_TIMEOUT, "deadline passed while the request waited for a panel");
   }
-  // the panel, outside the lock: the members' queries side by side, the largest k; every member's buffers take its own k
+  return true;
+}
+
+// The leader's panel, outside the lock: the members' queries side by side, the largest k; every member's buffers take its own k.
+// run(queries, kmax, outs) searches them; then every member gets its results (or the panel's error) and its caller is woken.
+template <class Run>
+static int knn_co_run_panel(Coalescer& co, const std::vector<CoQueued*>& batch, KnnCoRequest& me, Run&& run) {
   auto member = [&](size_t i) { return static_cast<KnnCoRequest*>(batch[i]); };
   int32_t kmax = 0;
-  std::vector<float> qs(batch.size() * (size_t)dim);
+  std::vector<float> qs(batch.size() * (size_t)me.dim);
   std::vector<nrtgpu_topdocs> outs(batch.size());
   for (size_t i = 0; i < batch.size(); ++i) {
     const KnnCoRequest* r = member(i);
     kmax = std::max(kmax, r->k);
-    memcpy(qs.data() + i * (size_t)dim, r->query, (size_t)dim * 4);
+    memcpy(qs.data() + i * (size_t)me.dim, r->query, (size_t)me.dim * 4);
     outs[i] = *r->out;
     const int32_t cap = outs[i].capacity > 0 ? outs[i].capacity : r->k;
     outs[i].capacity = std::min(cap, r->k);
@@ -652,7 +695,7 @@ extern "C" int nrtgpu_knn_exact_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* con
   {
     // (a panel of several requests does not run under its leader's deadline: its mates have not expired)
     DeadlineScope deadline_scope(batch.size() > 1);
-    rc = knn_impl(ctx, segs, doc_bases, n_segs, field_id, sim, qs.data(), (int32_t)batch.size(), dim, kmax, boost, false, 0, 0.0f, outs.data());
+    rc = run(qs.data(), kmax, outs.data());
   }
   const std::string err = rc ? g_last_error : std::string();
   for (size_t i = 0; i < batch.size(); ++i) {
@@ -671,12 +714,138 @@ extern "C" int nrtgpu_knn_exact_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* con
   return rc;
 }
 
+extern "C" int nrtgpu_knn_exact_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                          int32_t field_id, int32_t sim, const float* query, int32_t dim, int32_t k, float boost,
+                                          nrtgpu_topdocs* out) {
+  if (!ctx || !query || !out || (n_segs > 0 && !segs)) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
+  // (what would fail the panel must fail this request alone)
+  if (int rc = knn_check_scalars(n_segs < 0, k, dim, sim)) return rc;
+  for (int si = 0; si < n_segs; ++si) {
+    if (!segs[si] || !segs[si]->sealed) return fail(NRTGPU_ERR_STATE, "segment %d missing or not sealed", si);
+    auto fit = segs[si]->fields.find(field_id);
+    if (fit != segs[si]->fields.end() && fit->second.d_vectors && fit->second.dim_user != dim)
+      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d has dimension %d, query has %d", si, field_id, fit->second.dim_user, dim);
+  }
+  NRT_CHECK_DEADLINE("before the request was queued");
+  KnnCoRequest me{{}, segs, doc_bases, n_segs, field_id, sim, dim, k, boost, query, out};
+  std::vector<CoQueued*> batch;
+  if (!knn_co_wait(ctx->kco, me, true, &batch)) return me.rc;
+  return knn_co_run_panel(ctx->kco, batch, me, [&](const float* qs, int32_t kmax, nrtgpu_topdocs* outs) {
+    return knn_impl(ctx, segs, doc_bases, n_segs, field_id, sim, qs, (int32_t)batch.size(), dim, kmax, boost, false, 0, 0.0f, outs);
+  });
+}
+
 extern "C" int nrtgpu_knn_search(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
                                  int32_t field_id, int32_t sim, const float* queries, int32_t n_queries, int32_t dim,
                                  int32_t k, float boost, int32_t filter_mask, float min_score, nrtgpu_topdocs* out) {
   if (filter_mask < 0 || !(min_score >= 0.0f) || !(boost > 0.0f))
     return fail(NRTGPU_ERR_INVALID_ARG, "knn search: filter_mask >= 0, min_score >= 0 and boost > 0 expected");
   return knn_impl(ctx, segs, doc_bases, n_segs, field_id, sim, queries, n_queries, dim, k, boost, true, filter_mask, min_score, out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// knn requests with a k, boost, pre-filter and threshold EACH, in passes that share one read of the rows (include/nrtgpu.h)
+// ------------------------------------------------------------------------------------------------
+// What one request may ask (nrtgpu_knn_search's refusals); qi names it in the error text.
+static int knn_request_check(int32_t qi, int32_t k, float boost, int32_t filter_mask, float min_score) {
+  if (k <= 0) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: k %d (> 0 expected)", qi, k);
+  if (filter_mask < 0) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: filter_mask %d (>= 0 expected)", qi, filter_mask);
+  if (!(min_score >= 0.0f)) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: min_score >= 0 expected", qi);
+  if (!(boost > 0.0f) || !std::isfinite(boost)) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: a finite boost > 0 expected", qi);
+  if (k > NRTGPU_MAX_K) return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: k %d > %d", qi, k, NRTGPU_MAX_K);
+  return NRTGPU_OK;
+}
+// What the call asks of the field in every leaf (a float field of the queries' dimension, or absent) and of the requests' masks
+// (resident on every leaf that holds the field's rows -- the leaves a search would read them on).  Host only.
+static int knn_requests_check_leaves(const nrtgpu_seg* const* segs, int32_t n_segs, int32_t field_id, int32_t dim, const int32_t* masks,
+                                     int32_t n_queries) {
+  for (int si = 0; si < n_segs; ++si)
+    if (!segs[si]) return fail(NRTGPU_ERR_STATE, "segment %d missing or not sealed", si);
+  SegReadLocks content(segs, n_segs);   // (the handles' masks are read)
+  for (int si = 0; si < n_segs; ++si) {
+    if (!segs[si]->sealed) return fail(NRTGPU_ERR_STATE, "segment %d missing or not sealed", si);
+    auto fit = segs[si]->fields.find(field_id);
+    if (fit == segs[si]->fields.end()) continue;
+    if (fit->second.byte_rows)
+      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d holds byte (int8) vectors: search it with nrtgpu_knn_exact_bytes / nrtgpu_knn_search_bytes",
+                  si, field_id);
+    if (!fit->second.d_vectors) continue;
+    if (fit->second.dim_user != dim)
+      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d has dimension %d, query has %d", si, field_id, fit->second.dim_user, dim);
+    for (int32_t q = 0; masks && q < n_queries; ++q)
+      if (masks[q] != 0 && segs[si]->masks.find(masks[q]) == segs[si]->masks.end())
+        return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: filter mask %d is not resident on segment %d", q, masks[q], si);
+  }
+  return NRTGPU_OK;
+}
+
+// The requests are valid (knn_request_check, knn_requests_check_leaves) and none of the arrays is NULL.
+static int knn_requests_run(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, int32_t field_id, int32_t sim,
+                            const float* queries, int32_t n_queries, int32_t dim, const KnnPerQuery& pq, nrtgpu_topdocs* out) {
+  bool all_equal = true;
+  for (int32_t q = 1; q < n_queries && all_equal; ++q)
+    all_equal = pq.ks[q] == pq.ks[0] && pq.boosts[q] == pq.boosts[0] && pq.masks[q] == pq.masks[0] && pq.min_scores[q] == pq.min_scores[0];
+  if (all_equal)   // one filter, one threshold: nrtgpu_knn_search's own path, the gather route included
+    return knn_impl(ctx, segs, doc_bases, n_segs, field_id, sim, queries, n_queries, dim, pq.ks[0], pq.boosts[0], true, pq.masks[0], pq.min_scores[0], out);
+  const int32_t pass_q = dim > 1280 ? 16 : kKnnMaxQ;   // (knn_impl's: the panels that fit the LDS)
+  for (int32_t q0 = 0; q0 < n_queries; q0 += pass_q) {
+    const int32_t nq = std::min(pass_q, n_queries - q0);
+    if (q0 > 0 && deadline_passed(g_deadline_ns))
+      return fail(NRTGPU_ERR_TIMEOUT, "deadline passed between two passes over the rows (%d of %d queries answered)", q0, n_queries);
+    const KnnPerQuery pass{pq.ks + q0, pq.boosts + q0, pq.masks + q0, pq.min_scores + q0};
+    const int32_t k_pass = *std::max_element(pass.ks, pass.ks + nq);
+    if (int rc = knn_impl(ctx, segs, doc_bases, n_segs, field_id, sim, queries + (size_t)q0 * dim, nq, dim, k_pass, 1.0f, true, 0, 0.0f, out + q0,
+                          nullptr, nullptr, nullptr, &pass))
+      return rc;
+  }
+  return NRTGPU_OK;
+}
+
+extern "C" int nrtgpu_knn_search_requests(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                          int32_t field_id, int32_t sim, const float* queries, int32_t n_queries, int32_t dim,
+                                          const int32_t* ks, const float* boosts, const int32_t* filter_masks, const float* min_scores,
+                                          nrtgpu_topdocs* out) {
+  if (!ctx || !queries || !out || !ks || (n_segs > 0 && !segs)) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
+  if (int rc = knn_check_scalars(n_queries <= 0 || n_segs < 0, 1, dim, sim)) return rc;
+  // a bad request refuses the whole call before anything is launched
+  for (int32_t q = 0; q < n_queries; ++q)
+    if (int rc = knn_request_check(q, ks[q], boosts ? boosts[q] : 1.0f, filter_masks ? filter_masks[q] : 0, min_scores ? min_scores[q] : 0.0f)) return rc;
+  if (int rc = knn_requests_check_leaves(segs, n_segs, field_id, dim, filter_masks, n_queries)) return rc;
+  NRT_CHECK_DEADLINE("before the vector search started");
+  std::vector<float> one, none_f;
+  std::vector<int32_t> none_i;
+  if (!boosts) one.assign((size_t)n_queries, 1.0f);
+  if (!min_scores) none_f.assign((size_t)n_queries, 0.0f);
+  if (!filter_masks) none_i.assign((size_t)n_queries, 0);
+  const KnnPerQuery pq{ks, boosts ? boosts : one.data(), filter_masks ? filter_masks : none_i.data(), min_scores ? min_scores : none_f.data()};
+  return knn_requests_run(ctx, segs, doc_bases, n_segs, field_id, sim, queries, n_queries, dim, pq, out);
+}
+
+extern "C" int nrtgpu_knn_search_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                           int32_t field_id, int32_t sim, const float* query, int32_t dim, int32_t k, float boost,
+                                           int32_t filter_mask, float min_score, nrtgpu_topdocs* out) {
+  if (!ctx || !query || !out || (n_segs > 0 && !segs)) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
+  // (what would fail the panel must fail this request alone: its scalars, the field, its mask on every leaf)
+  if (int rc = knn_check_scalars(n_segs < 0, 1, dim, sim)) return rc;
+  if (int rc = knn_request_check(0, k, boost, filter_mask, min_score)) return rc;
+  if (int rc = knn_requests_check_leaves(segs, n_segs, field_id, dim, &filter_mask, 1)) return rc;
+  NRT_CHECK_DEADLINE("before the request was queued");
+  KnnCoRequest me{{}, segs, doc_bases, n_segs, field_id, sim, dim, k, boost, query, out, filter_mask, min_score};
+  std::vector<CoQueued*> batch;
+  if (!knn_co_wait(ctx->rco, me, false, &batch)) return me.rc;
+  return knn_co_run_panel(ctx->rco, batch, me, [&](const float* qs, int32_t, nrtgpu_topdocs* outs) {
+    std::vector<int32_t> ks(batch.size()), masks(batch.size());
+    std::vector<float> boosts(batch.size()), mins(batch.size());
+    for (size_t i = 0; i < batch.size(); ++i) {
+      const KnnCoRequest* r = static_cast<const KnnCoRequest*>(batch[i]);
+      ks[i] = r->k;
+      boosts[i] = r->boost;
+      masks[i] = r->filter_mask;
+      mins[i] = r->min_score;
+    }
+    const KnnPerQuery pq{ks.data(), boosts.data(), masks.data(), mins.data()};
+    return knn_requests_run(ctx, segs, doc_bases, n_segs, field_id, sim, qs, (int32_t)batch.size(), dim, pq, outs);
+  });
 }
 
 // The two-call rescorer: QueryRescorer over a first pass's hits, for either element type (runtime_internal.h: RescoreKind).
