@@ -89,6 +89,11 @@ int  nrtgpu_get_maxscore_profile(nrtgpu_ctx* ctx, double* out16);
  * estimate has left the meeting; NRTGPU_MS_SPEC_MEET=1 (environment, this library only, read per call) brings them back for an
  * A/B in one process. */
 int  nrtgpu_debug_maxscore_meetings(nrtgpu_ctx* ctx, int64_t* out4);
+/* ... and, over the same items, the speculative guesses that raised a workgroup's theta IN a meeting (the histogram's bucket edge
+ * of an overflow compaction, or the estimate of a meeting called for one): what decides how many of an overflow compaction's k best
+ * keys are still live.  NRTGPU_MS_KEEP_LIVE=0 (environment, this library only, read per call) makes a compaction keep the k best,
+ * dead keys included, as it used to -- for an A/B in one process. */
+int  nrtgpu_debug_maxscore_meeting_guesses(nrtgpu_ctx* ctx, int64_t* out1);
 /* TEST HOOK: the one-wave selection the estimator uses (topk.hiph: topk_kth_wave), run by a one-wave kernel over keys[0..n)
  * held in LDS as the walk holds them: *out = the r-th largest (1-based) of the keys, a zero key being an unwritten slot (it ranks
  * below every key).  1 <= r <= n <= the walk's candidate buffer (2304 slots). */

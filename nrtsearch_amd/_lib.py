@@ -63,6 +63,7 @@ DEV_SYMBOLS = [
     "nrtgpu_debug_spec_counters", "nrtgpu_get_scan_profile", "nrtgpu_get_maxscore_profile", "nrtgpu_get_maxscore_item_walls",
     "nrtgpu_debug_dist_inject", "nrtgpu_debug_term_lookup", "nrtgpu_debug_knn_bounds", "nrtgpu_debug_knn_unpack",
     "nrtgpu_debug_maxscore_meetings", "nrtgpu_debug_wave_kth", "nrtgpu_debug_walk_rows", "nrtgpu_debug_walk_value",
+    "nrtgpu_debug_maxscore_meeting_guesses",
 ]
 DEV_LIB_PATH = os.path.join(_HERE, "libnrtgpu_dev.so")
 
@@ -252,6 +253,8 @@ def _open(path: str) -> C.CDLL:
     if hasattr(L, "nrtgpu_debug_maxscore_meetings"):
         L.nrtgpu_debug_maxscore_meetings.argtypes = [vp, vp]
         L.nrtgpu_debug_wave_kth.argtypes = [vp, i32, i32, vp]
+    if hasattr(L, "nrtgpu_debug_maxscore_meeting_guesses"):
+        L.nrtgpu_debug_maxscore_meeting_guesses.argtypes = [vp, vp]
     if hasattr(L, "nrtgpu_debug_walk_rows"):
         L.nrtgpu_debug_walk_rows.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, i64]
         L.nrtgpu_debug_walk_rows.restype = C.c_int64

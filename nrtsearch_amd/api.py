@@ -327,7 +327,11 @@ class GpuContext:
         """The MaxScore route's meetings since reset_stats (nrtgpu_debug_maxscore_meetings; development library, NRTGPU_FLAG_PROFILE)."""
         out = np.zeros(4, dtype=np.int64)
         _lib.check(_lib.load().nrtgpu_debug_maxscore_meetings(self._h, out.ctypes.data))
-        return dict(zip(["meetings", "overflow_meetings", "compactions", "wave_estimates"], (int(x) for x in out)))
+        res = dict(zip(["meetings", "overflow_meetings", "compactions", "wave_estimates"], (int(x) for x in out)))
+        g = np.zeros(1, dtype=np.int64)   # (guesses that raised theta in a meeting: nrtgpu_debug_maxscore_meeting_guesses)
+        _lib.check(_lib.load().nrtgpu_debug_maxscore_meeting_guesses(self._h, g.ctypes.data))
+        res["meeting_guesses"] = int(g[0])
+        return res
 
     @staticmethod
     def set_thread_deadline(seconds_from_now: Optional[float]) -> None:

@@ -100,6 +100,13 @@ extern "C" int nrtgpu_debug_maxscore_meetings(nrtgpu_ctx* ctx, int64_t* out4) {
   return NRTGPU_OK;
 }
 
+extern "C" int nrtgpu_debug_maxscore_meeting_guesses(nrtgpu_ctx* ctx, int64_t* out1) {
+  if (!ctx || !out1) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lk(ctx->stats_mu);
+  *out1 = ctx->ms_meetings[4];
+  return NRTGPU_OK;
+}
+
 // Test hook (include/nrtgpu_dev.h): the one-wave selection of the MaxScore walk's estimator on keys of the caller's.
 extern "C" int nrtgpu_debug_wave_kth(const uint64_t* keys, int32_t n, int32_t r, uint64_t* out) {
   if (!keys || !out || n < 1 || n > kMsCandCap || r < 1 || r > n) return fail(NRTGPU_ERR_INVALID_ARG, "bad wave_kth arguments (1 <= r <= n <= %d)", kMsCandCap);

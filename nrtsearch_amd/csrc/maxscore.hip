@@ -103,8 +103,10 @@ struct MsSmem {
   uint32_t rz_flag;      // a wave could not reserve candidate slots (A/B, spec_meet: or a new speculative theta is due): everybody meet
   uint32_t spec_busy;    // speculation: a wave is making an estimate (ms_estimate; taken by compare-and-swap: one at a time)
   uint32_t spec_meet;    // A/B (development build, plan.h: DHelp.spec_sched): bit 0 (its bit 16) estimates are made in meetings, as before;
-                         // bit 1 (its bit 17) no half groups: every instruction of the walk runs the full body
-  uint32_t n_meet, n_over, n_est;   // instrumented kernels: meetings, those called by an overflow, estimates made by one wave
+                         // bit 1 (its bit 17) no half groups: every instruction of the walk runs the full body; bit 2 (its bit 18) a
+                         // compaction keeps the k best keys, dead ones included, as before (ms_compact)
+  uint32_t n_meet, n_over, n_est;   // instrumented kernels: meetings, those called by an overflow, estimates made by one wave (low half) |
+                                    // guesses that raised theta in a meeting (upper half)
   uint32_t wins_started; // doc windows this workgroup's waves have taken so far (of the item it works on)
   uint32_t spec_at;      // speculation: the next estimate is due when wins_started reaches this (0: never)
   uint32_t q_wins;       // doc windows of ALL items of the query
@@ -213,10 +215,27 @@ __device__ __noinline__ void ms_compact(__attribute__((address_space(3))) MsSmem
   const uint32_t tid = threadIdx.x;
   const uint32_t cnt_raw = s.cnt;
   const uint32_t cnt0 = cnt_raw > (uint32_t)kMsCandCap ? s.cnt_valid : cnt_raw;  // failed reservations inflate cnt
+  // What a compaction keeps: the keys that can still matter -- those that reach the LARGEST bound the workgroup holds when it
+  // is done (the k-th key, the guess this selection yields, the theta it came with, the query's theta_g), not the k best.  A key
+  // below that bound is dead: the append test admits none like it (key > theta), the item's epilogue writes none (key >= theta),
+  // and a guess that fails is caught by the merge whether or not the keys below it were carried along.  At k = 1000 an item's first
+  // overflow has r of about 120: the k best would fill 1000 of the buffer's slots with some 870 dead keys until the item ends.
+#ifdef NRTGPU_DEV   // (A/B, NRTGPU_MS_KEEP_LIVE=0: a compaction keeps the k best, as before)
+  const bool keep_live = (s.spec_meet & 4u) == 0u;
+#else
+  constexpr bool keep_live = true;
+#endif
+  // (theta_g: what the query's other items and this item's helpers have published; requested before the barrier, folded into
+  //  theta behind it -- no estimator runs then, every wave is here -- and read by everybody behind the selection's barriers)
+  const uint64_t tg_in = tid == 0 && keep_live ? (uint64_t)__hip_atomic_load(theta_g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
   __syncthreads();
   if (tid == 0) {
     s.n_meet += 1u;
     if (cnt_raw > (uint32_t)kMsCandCap) s.n_over += 1u;
+    if (tg_in > s.theta) {
+      s.theta = tg_in;
+      s.thr = acc_threshold<true>(tg_in, fx_E);
+    }
   }
   // Speculation (plan.h: kHitsSpecInvalid): this workgroup has taken wins_started of the query's q_wins doc windows, so about
   // m = k x that fraction of the query's final top-k are among the keys it holds -- their (m + z sqrt(m) + 1)-th best is a
@@ -236,7 +255,13 @@ __device__ __noinline__ void ms_compact(__attribute__((address_space(3))) MsSmem
     const uint32_t k2 = exchanging ? (k + xch->world - 2u) / (xch->world - 1u) : r;
     const uint64_t thr = topk_kth_union<kMsThreads>(s.cand, cnt0, k, &s.sc, [](auto&&) {}, k2);
     const uint32_t q2_hi = s.sc.q2_hi;  // (stable until the next selection)
-    const uint32_t kept = topk_keep_ge<kMsThreads, kMsCandCap>(s.cand, cnt0, thr, &s.sc);
+    uint64_t keep = thr;   // (uniform: theta is written by thread 0 alone, before the selection's barriers and behind topk_keep_ge's)
+    if (keep_live) {
+      const uint64_t edge = !exchanging && r != 0u && q2_hi != 0u ? (uint64_t)q2_hi << 32 : 0ull, th_in = s.theta;   // (edge: the guess, below)
+      if (edge > keep) keep = edge;
+      if (th_in > keep) keep = th_in;
+    }
+    const uint32_t kept = topk_keep_ge<kMsThreads, kMsCandCap>(s.cand, cnt0, keep, &s.sc);   // (<= k, and 0 when theta_g has passed every key)
     // (what lies behind the kept keys reads 0 again: ms_estimate takes a non-zero slot for a key of the current prefix, and a
     //  stale copy of a kept key would push its r-th best, the guess, UP)
     for (uint32_t i = kept + tid; i < (uint32_t)kMsCandCap; i += kMsThreads) s.cand[i] = 0ull;
@@ -268,6 +293,7 @@ __device__ __noinline__ void ms_compact(__attribute__((address_space(3))) MsSmem
       s.thr = acc_threshold<true>(guess, fx_E);
       atomicMax(theta_g, (unsigned long long)guess);
       atomicMax(s.spec_slot, (unsigned long long)guess);
+      s.n_est += 0x10000u;   // (instrumented kernels: guesses that a meeting published, in the count's upper half)
     }
     // the next estimate: when (by default) twice as many windows have been taken -- the guess moves with the fraction's square root
     const uint32_t ws = s.wins_started;
@@ -566,7 +592,7 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
       s.spec_slot = spec ? as_global(hp.spec_g) + item.query : nullptr;
       s.spec_at = spec ? max(hp.spec_sched & 255u, 1u) : 0u;   // the first estimate (default: when every wave has begun its second window)
       s.spec_grow16 = max((hp.spec_sched >> 8) & 255u, 17u);
-      s.spec_meet = (hp.spec_sched >> 16) & 3u;
+      s.spec_meet = (hp.spec_sched >> 16) & 7u;
       for (int i = 0; i < kSliceSlots; ++i) s.slot_hits[i] = s.slot_slice[i] = 0u;
       for (int i = 0; i < 16; ++i) s.prof[i] = 0;
     }
@@ -589,7 +615,7 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
         s.tab[slot][e] = e < (uint32_t)kTabNorms ? 0u : score_value<true>(bm25_score(w, (float)(int32_t)(e >> 7), cache[e & 127u]), scale);
     }
     __syncthreads();  // from here on the waves run on their own
-  #ifndef NRT_MS_PHASE_CLOCKS
+  #if !defined(NRT_MS_PHASE_CLOCKS) && !defined(NRT_MS_COUNT_ROUNDS)
     if (PROF && tid == 0) s.prof[8] = __builtin_readcyclecounter() - t_item0;
   #endif
 
@@ -604,6 +630,7 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
   #endif
   #ifdef NRT_MS_COUNT_ROUNDS   // experiment build: event counts instead of four of the cycle counters
     uint64_t pc_dense = 0, pc_sparse = 0, pc_steps = 0, pc_tas = 0, pc_crounds = 0, pc_half = 0, pc_half_rounds = 0;
+    uint64_t pc_cres = 0, pc_cinst = 0;   // candidate rounds that reserve slots (ms_reserve), instructions with at least one such round
   #endif
     // The item's windows (flattened over its parts, item_wins of them) are handed out in a SCATTERED order: the i-th window taken
     // (by anybody: the counter is shared with the item's helpers) is window (i x a) mod item_wins, a coprime to item_wins and near
@@ -1216,6 +1243,9 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
             }
           }
           uint64_t theta_now = theta;
+  #ifdef NRT_MS_COUNT_ROUNDS
+          const uint64_t cres0 = pc_cres;
+  #endif
           while (__any(maybe != 0u)) {
   #ifdef NRT_MS_COUNT_ROUNDS
             if (PROF) pc_crounds += 1;
@@ -1242,6 +1272,9 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
               maybe &= ~low;
               continue;
             }
+  #ifdef NRT_MS_COUNT_ROUNDS
+            if (PROF) pc_cres += 1;
+  #endif
             if (ms_reserve(s, lane, want ? 1u : 0u, pos)) {  // wave-uniform
               if (want) s.cand[pos] = key;
               if (PROF) pc_cand += want ? 1u : 0u;
@@ -1254,6 +1287,9 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
             if (PROF) tc_meet += __builtin_readcyclecounter() - t_m0;
             theta_now = max(theta_now, s.theta);
           }
+  #ifdef NRT_MS_COUNT_ROUNDS
+          if (PROF && pc_cres != cres0) pc_cinst += 1;
+  #endif
           }
           NRT_PH_MARK(8);
           return true;
@@ -1309,6 +1345,9 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
       atomicAdd((unsigned long long*)&s.prof[10], (unsigned long long)pc_sparse - (unsigned long long)tc_meet);
       atomicAdd((unsigned long long*)&s.prof[13], (unsigned long long)pc_steps - (unsigned long long)(tc_walk - tc_meet));
       atomicAdd((unsigned long long*)&s.prof[8], (unsigned long long)pc_crounds);
+      // (slots 9 and 15: candidate rounds that reserve slots, instructions with at least one such round)
+      atomicAdd((unsigned long long*)&s.prof[9], (unsigned long long)pc_cres);
+      atomicAdd((unsigned long long*)&s.prof[15], (unsigned long long)pc_cinst);
   #endif
     }
 
@@ -1394,13 +1433,16 @@ void bm25_maxscore_kernel(const MsArgs* __restrict__ launch) {
       if (PROF && ape->item_prof) {
   #ifndef NRT_MS_PHASE_CLOCKS
         s.prof[5] = hits;
-        // (slot 1, 16 bits each: compactions | meetings | meetings called by an overflow | estimates made by one wave --
-        //  search.cpp takes them apart: nrtgpu_debug_maxscore_meetings)
-        s.prof[1] = (s.prof[1] & 0xFFFFull) | ((uint64_t)min(s.n_meet, 0xFFFFu) << 16) | ((uint64_t)min(s.n_over, 0xFFFFu) << 32) | ((uint64_t)min(s.n_est, 0xFFFFu) << 48);
+        // (slot 1, 12 bits each: compactions | meetings | meetings called by an overflow | estimates made by one wave | guesses that
+        //  raised theta in a meeting -- search.cpp takes them apart: nrtgpu_debug_maxscore_meetings, nrtgpu_debug_maxscore_meeting_guesses)
+        s.prof[1] = (s.prof[1] & 0xFFFull) | ((uint64_t)min(s.n_meet, 0xFFFu) << 12) | ((uint64_t)min(s.n_over, 0xFFFu) << 24) |
+                    ((uint64_t)min(s.n_est & 0xFFFFu, 0xFFFu) << 36) | ((uint64_t)min(s.n_est >> 16, 0xFFFu) << 48);
   #endif
+  #ifndef NRT_MS_COUNT_ROUNDS
         const uint64_t t_end = __builtin_readcyclecounter();
         s.prof[9] = t_end - t_item0;
         s.prof[15] = t_end - t_epi0;
+  #endif
         for (int i = 0; i < 16; ++i) as_global(ape->item_prof)[(size_t)out_slot * 16 + i] = s.prof[i];
         if (hpe.walls) {
           unsigned long long* const wr = as_global(hpe.walls) + (size_t)out_slot * 8;

@@ -318,6 +318,7 @@ struct DHelp {
                                  // first one (doc windows begun by the workgroup), bits 8-15 the factor x 16 between one and the next
                                  // bit 16 (development build, A/B): the estimate is made in a meeting of all waves, not by one wave
                                  // bit 17 (development build, A/B): no half groups -- a window's last instruction runs the full body too
+                                 // bit 18 (development build, A/B): an overflow compaction keeps the k best keys, dead ones included
   unsigned long long* walls;     // instrumented kernel only, else nullptr: per output slot 8 words -- {start, end} on the 100 MHz
                                  // wall clock, item, windows walked, when the workgroup's round began, CU id, round, workgroup --
                                  // when every piece of the launch ran, on one time base (nrtgpu_get_maxscore_item_walls)

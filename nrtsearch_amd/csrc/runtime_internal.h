@@ -551,7 +551,8 @@ struct nrtgpu_ctx {
   std::vector<uint64_t> last_walls;   // NRTGPU_FLAG_PROFILE: {start, end, item, windows} per output slot of the last MaxScore launch
   int64_t last_walls_items = 0;       // ... whose first this-many slots are the items' owners (helpers behind the scan's slots)
   double ms_prof[16] = {0};   // the same for the items of the MaxScore route (nrtgpu_get_maxscore_profile)
-  int64_t ms_meetings[4] = {0};   // ... and their meetings, overflow meetings, compactions, one-wave estimates (nrtgpu_debug_maxscore_meetings)
+  int64_t ms_meetings[5] = {0};   // ... and their meetings, overflow meetings, compactions, one-wave estimates (nrtgpu_debug_maxscore_meetings),
+                                  // guesses that raised theta in a meeting (nrtgpu_debug_maxscore_meeting_guesses)
   // request coalescing (coalescer.h): the single-query entries' callers merged into batches (nrtgpu_search_bm25_coalesced, search.cpp)
   // and into panels (nrtgpu_knn_exact_coalesced on kco, nrtgpu_knn_search_coalesced on rco: vectors.cpp)
   nrtgpu::rt::Coalescer co, kco, rco;

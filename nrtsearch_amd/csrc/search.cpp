@@ -218,8 +218,10 @@ static MsArgs ms_launch_record(const nrtgpu_ctx* ctx, const HostPlan& hp, const 
     const bool env_meet = dev_env_int("NRTGPU_MS_SPEC_MEET", 0) != 0;
     // NRTGPU_MS_HALF_GROUPS=0: a window's last instruction runs the walk's full body whatever it holds (A/B; maxscore.hip: walk_units)
     const bool env_half = dev_env_int("NRTGPU_MS_HALF_GROUPS", 1) != 0;
+    // NRTGPU_MS_KEEP_LIVE=0: an overflow compaction keeps the k best keys, those below the workgroup's theta included (A/B; maxscore.hip: ms_compact)
+    const bool env_keep_live = dev_env_int("NRTGPU_MS_KEEP_LIVE", 1) != 0;
     help.spec_sched = (uint32_t)std::min(std::max(env_first, 1), 255) | ((uint32_t)std::min(std::max(env_grow, 17), 255) << 8) | (env_meet ? 1u << 16 : 0u) |
-                      (env_half ? 0u : 1u << 17);
+                      (env_half ? 0u : 1u << 17) | (env_keep_live ? 0u : 1u << 18);
   }
   MsArgs ms_args{};   // (the kernel reads the record from the plan: maxscore.hip)
   ms_args.items = (const DItem*)(db + L.items);
@@ -539,13 +541,14 @@ static int search_batch_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, con
     for (size_t i = 0; i < run.n_slots; ++i)   // (slots behind the items: helpers of the MaxScore route)
       if (i < run.n_ms_items || i >= run.n_items) {
 #ifndef NRT_MS_PHASE_CLOCKS   // (that measurement build books cycles in slots 0-8)
-        // (MaxScore slot 1 holds four 16-bit counts: maxscore.hip, the item's write-out)
+        // (MaxScore slot 1 holds five 12-bit counts: maxscore.hip, the item's write-out)
         const uint64_t packed = hp_prof[i * 16 + 1];
-        hp_prof[i * 16 + 1] = packed & 0xFFFFull;
-        ctx->ms_meetings[0] += (int64_t)((packed >> 16) & 0xFFFFull);   // meetings
-        ctx->ms_meetings[1] += (int64_t)((packed >> 32) & 0xFFFFull);   // ... called by an overflow
-        ctx->ms_meetings[2] += (int64_t)(packed & 0xFFFFull);           // compactions
-        ctx->ms_meetings[3] += (int64_t)(packed >> 48);                 // estimates made by one wave
+        hp_prof[i * 16 + 1] = packed & 0xFFFull;
+        ctx->ms_meetings[0] += (int64_t)((packed >> 12) & 0xFFFull);   // meetings
+        ctx->ms_meetings[1] += (int64_t)((packed >> 24) & 0xFFFull);   // ... called by an overflow
+        ctx->ms_meetings[2] += (int64_t)(packed & 0xFFFull);           // compactions
+        ctx->ms_meetings[3] += (int64_t)((packed >> 36) & 0xFFFull);   // estimates made by one wave
+        ctx->ms_meetings[4] += (int64_t)((packed >> 48) & 0xFFFull);   // guesses that raised theta in a meeting
 #endif
         for (int j = 0; j < 16; ++j) ctx->ms_prof[j] += (double)hp_prof[i * 16 + j];
       } else {

@@ -50,6 +50,8 @@ def main():
                 "windows": prof[0] / nq, "instruction_groups": prof[2] / nq, "postings_streamed": prof[3] / nq, "postings_surviving": prof[4] / nq,
                 "lookups": prof[6] / nq, "candidates": prof[7] / nq, "test_and_set_rounds": prof[11] / nq, "dense_clause_rounds": prof[12] / nq,
                 "sparse_clause_rounds": prof[10] / nq, "binary_search_steps": prof[13] / nq, "candidate_rounds": prof[8] / nq,
+                # (slots 9 and 15 of a count build: candidate rounds that reserve slots, instructions with at least one such round)
+                "reserving_candidate_rounds": prof[9] / nq, "instructions_that_append": prof[15] / nq,
                 # (slot 14 of a count build: instructions run by the half body | the later-clause rounds inside them << 32)
                 "half_groups": (int(prof[14]) & 0xFFFFFFFF) / nq, "half_group_later_clause_rounds": (int(prof[14]) >> 32) / nq}}), flush=True)
             continue
