@@ -516,8 +516,10 @@ int  nrtgpu_knn_search(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int
  * Thread deadlines: checked on entry and between passes.
  * nrtgpu_get_stats: a pass counts under knn_panels / knn_rows / knn_score_launches / knn_score_ms / knn_sketch_launches /
  * knn_second_passes like a pass of nrtgpu_knn_search.
- * Out of scope: byte fields, the nrtgpu_dist_* forms, the gather route for a pass whose members name different filters (it
- * always passes over all rows), MUST_NOT masks or several filters per request, and the Java shim.
+ * Byte fields: the twins nrtgpu_knn_search_bytes_requests / nrtgpu_knn_search_bytes_coalesced further down (these two refuse a
+ * byte field by name).
+ * Out of scope: the nrtgpu_dist_* forms, the gather route for a pass whose members name different filters (it always passes
+ * over all rows), MUST_NOT masks or several filters per request, and the Java shim.
  * --------------------------------------------------------------------------------------------- */
 int  nrtgpu_knn_search_requests(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
                                 int32_t field_id, int32_t sim, const float* queries, int32_t n_queries, int32_t dim,
@@ -562,8 +564,11 @@ int  nrtgpu_knn_search_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs,
  * the passes in knn_panels / knn_rows / knn_score_launches / knn_score_ms.  A float entry point called on a byte field, and a
  * byte entry point on a float field, return NRTGPU_ERR_INVALID_ARG naming the field's element type.
  * A byte field as a RESCORER: nrtgpu_rescore_byte_vectors and nrtgpu_search_hybrid_bytes_batch below.
- * Out of scope for byte fields (all INVALID_ARG by that rule): nrtgpu_knn_exact_coalesced and the nrtgpu_dist_* entries; the Java
- * shim does not bind the byte functions yet.
+ * The request and the coalesced entries over a byte field: nrtgpu_knn_search_bytes_requests, nrtgpu_knn_search_bytes_coalesced and
+ * nrtgpu_knn_exact_bytes_coalesced below.
+ * Out of scope for byte fields (INVALID_ARG by that rule): the nrtgpu_dist_* entries -- and the float entries themselves, which
+ * keep refusing a byte field: nrtgpu_knn_exact_coalesced, nrtgpu_knn_search_requests and nrtgpu_knn_search_coalesced are answered
+ * for byte fields by their twins, not by a switch inside them; the Java shim does not bind the byte functions yet.
  * --------------------------------------------------------------------------------------------- */
 int  nrtgpu_knn_exact_bytes(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
                             int32_t field_id, int32_t sim, const int8_t* queries, int32_t n_queries, int32_t dim, int32_t k,
@@ -571,6 +576,42 @@ int  nrtgpu_knn_exact_bytes(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, cons
 int  nrtgpu_knn_search_bytes(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
                              int32_t field_id, int32_t sim, const int8_t* queries, int32_t n_queries, int32_t dim, int32_t k,
                              float boost, int32_t filter_mask, float min_score, nrtgpu_topdocs* out /* n_queries */);
+/* knn requests over a BYTE field that share a pass although each has a pre-filter, threshold, k and boost of its OWN: the twins
+ * of nrtgpu_knn_search_requests and nrtgpu_knn_search_coalesced (above), and of nrtgpu_knn_exact_coalesced.  A byte pass costs
+ * the same for 1 query as for 64, and it is simpler than a float one: ONE pass returns final score bits -- no sketch, no
+ * certificate, no second pass.
+ * nrtgpu_knn_search_bytes_requests: query i gets exactly what
+ * nrtgpu_knn_search_bytes(..., queries + i*dim, 1, dim, ks[i], boosts[i], filter_masks[i], min_scores[i], &out[i]) returns: same
+ * docids, ranks, score bits, total_hits (= the hits returned; liveDocs always apply).  Passes of up to 64 queries at every
+ * dimension, each searched with the largest k of its members and scores unboosted; member i takes the first ks[i] hits and its
+ * own boost when the list is unpacked.  On the device a pass brings a table of accept sets (liveDocs & the member's filter, per
+ * leaf and member) and the members' thresholds; a call whose requests are all equal is nrtgpu_knn_search_bytes itself, the
+ * gather route (nrtgpu_set_knn_gather) included; requests that differ always pass over all rows.
+ * Refusals, per request, are nrtgpu_knn_search_requests' with its wording ("query <i>: ..."): NRTGPU_ERR_INVALID_ARG for k <= 0,
+ * filter_mask < 0, a min_score that is not >= 0, a boost that is not finite and > 0, a query dimension other than the field's,
+ * ks == NULL; NRTGPU_ERR_UNSUPPORTED for k > NRTGPU_MAX_K, dim > 2048, a mask that is not resident on a leaf of the call that holds
+ * the field's rows.  Two more, both NRTGPU_ERR_INVALID_ARG: a zero query under cosine ("query <i>: a zero vector ...") and a float
+ * field (the error names the element type).  NULL boosts: all 1; NULL filter_masks: none; NULL min_scores: none.  A bad request
+ * refuses the WHOLE call of the batch entry before anything is launched; in the coalesced entries it fails ALONE, before it is
+ * queued.  Thread deadlines: checked on entry and between passes; NRTGPU_ERR_TIMEOUT for a request that expires in the queue.
+ * nrtgpu_get_stats: a byte pass's counters -- knn_panels / knn_rows / knn_score_launches / knn_score_ms; nothing under
+ * knn_sketch_launches or knn_second_passes.
+ * nrtgpu_knn_search_bytes_coalesced / nrtgpu_knn_exact_bytes_coalesced: ONE request per call, blocking; the leave rule, the cohort
+ * rule and the caps are the float entries' own.  Each has a queue of its own: float and byte callers never share a panel, nor do
+ * the callers of the two byte entries.  nrtgpu_knn_exact_bytes_coalesced merges callers with one boost (finite, >= 0) and
+ * answers as nrtgpu_knn_exact_bytes with n_queries = 1.
+ * Out of scope: the nrtgpu_dist_* forms, the gather route for a pass whose members name different filters, MUST_NOT masks or
+ * several filters per request, and the Java shim. */
+int  nrtgpu_knn_search_bytes_requests(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                      int32_t field_id, int32_t sim, const int8_t* queries, int32_t n_queries, int32_t dim,
+                                      const int32_t* ks, const float* boosts, const int32_t* filter_masks, const float* min_scores,
+                                      nrtgpu_topdocs* out /* n_queries; out[i].capacity >= ks[i] */);
+int  nrtgpu_knn_search_bytes_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                       int32_t field_id, int32_t sim, const int8_t* query, int32_t dim, int32_t k, float boost,
+                                       int32_t filter_mask, float min_score, nrtgpu_topdocs* out);
+int  nrtgpu_knn_exact_bytes_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                      int32_t field_id, int32_t sim, const int8_t* query, int32_t dim, int32_t k, float boost,
+                                      nrtgpu_topdocs* out);
 /* The GATHER route of the filtered knn entries.
  * Filtered knn requests (nrtgpu_knn_search, nrtgpu_knn_search_bytes; filter_mask != 0) whose filter accepts at most
  * max_accept_permille / 1000 of the field's rows over the call's leaves read ONLY the accepted rows. 0 (a context's default): never --

@@ -18,9 +18,10 @@ extern "C" {
 int  nrtgpu_bench_closed_loop(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
                               const nrtgpu_bm25_query* queries, int32_t n_queries, int32_t clients, int32_t duration_ms,
                               double* out4);
-/* TEST HOOKS for the coalescers (this one, nrtgpu_knn_exact_coalesced and nrtgpu_knn_search_coalesced).  hold != 0: no leader leaves with less than a
+/* TEST HOOKS for the coalescers (this one, nrtgpu_knn_exact_coalesced, nrtgpu_knn_search_coalesced and their byte twins).  hold != 0: no leader leaves with less than a
  * full batch (max_batch queries) / panel (64 queries) until the hold is released -- a test queues a known set of callers behind
- * it, waits until nrtgpu_debug_coalescer_pending (which: 0 = BM25, 1 = exact vector search, 2 = knn requests) reports all of them, releases,
+ * it, waits until nrtgpu_debug_coalescer_pending (which: 0 = BM25, 1 = exact vector search, 2 = knn requests, 3 = knn requests over byte
+ * fields, 4 = exact search over byte fields) reports all of them, releases,
  * and may then assert the batches formed BY CONSTRUCTION (what a batch is must not depend on the host's speed).  Not for
  * production callers: a held coalescer parks every request. */
 int  nrtgpu_debug_hold_coalescers(nrtgpu_ctx* ctx, int32_t hold);

@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "nrtgpu_search_bm25_batch_device_begin", "nrtgpu_pending_wait", "nrtgpu_set_thread_deadline_ns", "nrtgpu_monotonic_ns", "nrtgpu_last_diagnostics", "nrtgpu_dist_close", "nrtgpu_dist_owned_range", "nrtgpu_dist_search_bm25_batch_mode", "nrtgpu_dist_exchange_merge", "nrtgpu_dist_exchange_merge_checked", "nrtgpu_search_bm25_shard_device_begin", "nrtgpu_note_shard_speculation", "nrtgpu_dist_knn_exact", "nrtgpu_dist_search_hybrid_batch",
     "nrtgpu_knn_exact_relation", "nrtgpu_set_speculation", "nrtgpu_set_shard_share", "nrtgpu_set_thread_slices",
     "nrtgpu_segment_add_byte_vectors", "nrtgpu_knn_exact_bytes", "nrtgpu_knn_search_bytes", "nrtgpu_byte_vector_score",
+    "nrtgpu_knn_search_bytes_requests", "nrtgpu_knn_search_bytes_coalesced", "nrtgpu_knn_exact_bytes_coalesced",
     "nrtgpu_rescore_byte_vectors", "nrtgpu_search_hybrid_bytes_batch", "nrtgpu_set_knn_gather",
     "nrtgpu_search_function_score_batch", "nrtgpu_function_score_supported", "nrtgpu_function_score_value",
     "nrtgpu_search_multi_match_batch", "nrtgpu_multi_match_supported", "nrtgpu_multi_match_value",
@@ -199,6 +200,11 @@ def _open(path: str) -> C.CDLL:
     L.nrtgpu_segment_add_byte_vectors.argtypes = [vp, i32, i32, i32, vp, vp]
     L.nrtgpu_knn_exact_bytes.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, i32, f32, C.POINTER(TopDocs)]
     L.nrtgpu_knn_search_bytes.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, i32, f32, i32, f32, C.POINTER(TopDocs)]
+    L.nrtgpu_knn_search_bytes_requests.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, C.POINTER(TopDocs)]
+    L.nrtgpu_knn_search_bytes_coalesced.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, f32, i32, f32, C.POINTER(TopDocs)]
+    L.nrtgpu_knn_search_bytes_coalesced.restype = i32
+    L.nrtgpu_knn_exact_bytes_coalesced.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, f32, C.POINTER(TopDocs)]
+    L.nrtgpu_knn_exact_bytes_coalesced.restype = i32
     L.nrtgpu_byte_vector_score.argtypes = [i32, i32, i32, i32, i32, vp]
     L.nrtgpu_set_knn_gather.argtypes = [vp, i32]
     L.nrtgpu_search_function_score_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(FunctionScore), i32, C.POINTER(TopDocs)]

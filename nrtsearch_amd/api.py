@@ -400,7 +400,8 @@ class GpuContext:
         _lib.check(_lib.load().nrtgpu_debug_hold_coalescers(self._h, 1 if hold else 0))
 
     def debug_coalescer_pending(self, which: int) -> int:
-        """Requests parked in a coalescer: 0 = nrtgpu_search_bm25_coalesced, 1 = nrtgpu_knn_exact_coalesced, 2 = nrtgpu_knn_search_coalesced."""
+        """Requests parked in a coalescer: 0 = nrtgpu_search_bm25_coalesced, 1 = nrtgpu_knn_exact_coalesced, 2 = nrtgpu_knn_search_coalesced,
+        3 = nrtgpu_knn_search_bytes_coalesced, 4 = nrtgpu_knn_exact_bytes_coalesced."""
         return int(_lib.load().nrtgpu_debug_coalescer_pending(self._h, int(which)))
 
     def debug_dist_inject(self, step: int = -1, failed_query: int = -1) -> None:
@@ -1057,6 +1058,56 @@ class GpuIndexSearcher:
                                                        queries.ctypes.data, nq, dim, int(k), C.c_float(boost),
                                                        int(filter.mask_id) if filter else 0, C.c_float(min_score), outs))
         return _topdocs_lists(outs, docs, scores, nq)
+
+    def knn_search_bytes_requests(self, field: int, similarity: str, queries: np.ndarray, ks: Sequence[int],
+                                  boosts: Optional[Sequence[float]] = None, filters: Optional[Sequence[Optional[MaskFilter]]] = None,
+                                  min_scores: Optional[Sequence[float]] = None) -> List[TopDocs]:
+        """`knn` requests over a byte vector field with a k, boost, filter and threshold EACH, answered in passes of up to 64 that share
+        one read of the rows (nrtgpu_knn_search_bytes_requests): query i gets what knn_search_bytes gives it alone."""
+        sim = self._byte_similarity(similarity)
+        queries = _int8_rows(queries, "queries")
+        nq, dim = queries.shape
+        ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
+        boosts = None if boosts is None else np.ascontiguousarray(boosts, dtype=np.float32).reshape(-1)
+        masks = None if filters is None else np.array([int(f.mask_id) if f is not None else 0 for f in filters], dtype=np.int32)
+        min_scores = None if min_scores is None else np.ascontiguousarray(min_scores, dtype=np.float32).reshape(-1)
+        for name, a in (("ks", ks), ("boosts", boosts), ("filters", masks), ("min_scores", min_scores)):
+            if a is not None and a.shape[0] != nq:
+                raise ValueError(f"{name}: {a.shape[0]} values for {nq} queries")
+        outs, docs, scores = _topdocs_outputs(nq, max(int(ks.max()), 1))
+        _lib.check(_lib.load().nrtgpu_knn_search_bytes_requests(self.ctx._h, self._segs, self._bases, len(self.leaves), int(field), sim,
+                                                                queries.ctypes.data, nq, dim, ks.ctypes.data,
+                                                                boosts.ctypes.data if boosts is not None else None,
+                                                                masks.ctypes.data if masks is not None else None,
+                                                                min_scores.ctypes.data if min_scores is not None else None, outs))
+        return _topdocs_lists(outs, docs, scores, nq)
+
+    def _one_byte_query(self, name: str, field: int, similarity: str, query: np.ndarray, k: int, *tail) -> TopDocs:
+        """One int8 query through a single-query (coalesced) entry; tail: the entry's scalars between k and the output."""
+        sim = self._byte_similarity(similarity)
+        query = _int8_rows(query, "query").reshape(-1)
+        k = int(k)
+        out = _lib.TopDocs()
+        docs = np.zeros(max(k, 1), dtype=np.int32)
+        scores = np.zeros(max(k, 1), dtype=np.float32)
+        out.capacity = max(k, 1)
+        out.docs = docs.ctypes.data_as(C.POINTER(C.c_int32))
+        out.scores = scores.ctypes.data_as(C.POINTER(C.c_float))
+        _lib.check(getattr(_lib.load(), name)(self.ctx._h, self._segs, self._bases, len(self.leaves), int(field), sim, query.ctypes.data,
+                                              int(query.shape[0]), k, *tail, C.byref(out)))
+        return TopDocs(docs[: out.n_hits].copy(), scores[: out.n_hits].copy(), int(out.total_hits), bool(out.total_hits_is_lower_bound))
+
+    def knn_search_bytes_coalesced(self, field: int, similarity: str, query: np.ndarray, k: int, boost: float = 1.0,
+                                   filter: Optional[MaskFilter] = None, min_score: float = 0.0) -> TopDocs:
+        """What a request thread calls with ONE `knn` request over a byte vector field: concurrent callers share panels of up to 64
+        whatever their k, filter, threshold and boost (nrtgpu_knn_search_bytes_coalesced)."""
+        return self._one_byte_query("nrtgpu_knn_search_bytes_coalesced", field, similarity, query, k, C.c_float(boost),
+                                    int(filter.mask_id) if filter else 0, C.c_float(min_score))
+
+    def knn_exact_bytes_coalesced(self, field: int, similarity: str, query: np.ndarray, k: int, boost: float = 1.0) -> TopDocs:
+        """What a request thread calls with ONE exact query over a byte vector field: concurrent callers with one boost are merged into
+        panels of up to 64 queries that share a pass over the rows (nrtgpu_knn_exact_bytes_coalesced)."""
+        return self._one_byte_query("nrtgpu_knn_exact_bytes_coalesced", field, similarity, query, k, C.c_float(boost))
 
     def rescore_vectors(self, hits: TopDocs, field: int, similarity: str, query: np.ndarray, window: int,
                         query_weight: float = 1.0, rescore_weight: float = 1.0, boost: float = 1.0) -> TopDocs:

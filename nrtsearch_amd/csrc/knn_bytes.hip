@@ -25,6 +25,7 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));   // 16 int8 of an operan
 
 constexpr int kKnnBytesThreads = 1024;   // 16 waves, one workgroup per CU (the panel takes up to 128 KiB of LDS)
 constexpr size_t kKnnBytesStaticLds = 1280;   // knn_bytes_kernel's per-query tables
+constexpr size_t kKnnBytesReqStaticLds = 1536;   // knn_bytes_requests_kernel's: the same + a threshold per query
 
 // Resident format, written at upload from a staged chunk of the caller's rows (row-major, `dim` bytes each, rows
 // [row0, row0 + n_chunk) of the field; row0 is a multiple of 16): one thread per 16-byte piece of the chunk's tiles.  Elements
@@ -155,207 +156,21 @@ __device__ inline int32_t knn_bytes_threshold(int sim, int32_t dim, int32_t nq, 
 //   qnorm2 : |q|^2 per query; dim_user: the field's own dimension (dot_product's divisor)
 //   min_score > 0: rows whose UNBOOSTED score is below it are no hits (the knn request path, which passes boost = 1)
 // C/D layout of the instruction: query col = lane & 15 (+ 16p), row in tile = 4 (lane >> 4) + reg.
-template <int P, int D>
-__global__ __launch_bounds__(kKnnBytesThreads, 1)
-void knn_bytes_kernel(const DKnnBytesLeaf* __restrict__ leaves, int32_t n_leaves, int32_t steps, int32_t dim_user, int64_t tile_begin,
-                      int64_t tile_end, const i32x4* __restrict__ panel, const int32_t* __restrict__ qnorm2, int32_t n_q, int32_t sim,
-                      float boost, float min_score, const unsigned long long* __restrict__ theta, uint64_t* __restrict__ cand,
-                      uint32_t* __restrict__ cand_cnt, uint32_t cap, int32_t append_only, uint32_t qcap) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  i32x4* qs = (i32x4*)smem;
-  // behind the panel: the workgroup's queue of rows that passed (score bits << 32 | padded row << 6 | query), written out once when
-  // the workgroup has streamed its rows -- a global atomic in the tile epilogue would have the wave wait for its whole ring
-  uint32_t* const q_n = (uint32_t*)(smem + (size_t)steps * P * 1024);
-  uint64_t* const q_e = (uint64_t*)(smem + (size_t)steps * P * 1024 + 16);
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  __shared__ int32_t kb_nq[64], kb_thr[64];
-  __shared__ float kb_thhi[64];
-  __shared__ unsigned long long kb_th[64];
-  static_assert(4 * 64 * 3 + 8 * 64 == kKnnBytesStaticLds, "launch_knn_bytes sizes the queue by this");
-  if (tid == 0) *q_n = 0u;
-  if (tid < 64u) {
-    const int32_t q = (int32_t)tid;
-    const unsigned long long th_q = q < n_q ? theta[q] : ~0ull;
-    const int32_t nq_q = q < n_q ? qnorm2[q] : 0;
-    kb_nq[q] = nq_q;
-    kb_th[q] = th_q;
-    kb_thr[q] = knn_bytes_threshold(sim, dim_user, nq_q, th_q, boost, q < n_q);
-    // a key above theta carries a score >= theta's (equal scores: the docid decides): rows strictly below are rejected on the
-    // score alone (theta = ~0 is a NaN score: every compare with it is false)
-    const uint32_t tsb = __float_as_uint(key_score(th_q));
-    kb_thhi[q] = tsb ? __uint_as_float(tsb - 1u) : -1.0f;
-  }
-  for (int32_t i = (int32_t)tid; i < steps * P * 64; i += kKnnBytesThreads) qs[i] = panel[i];
-  __syncthreads();
-  const uint32_t j = lane & 15u, kk = lane >> 4;
-  int32_t thr[P];
-#pragma unroll
-  for (int p = 0; p < P; ++p) thr[p] = kb_thr[j + 16u * (uint32_t)p];
-  auto may_pass = [&](int p, int32_t dot, int32_t nv, float rn) -> bool {   // (sim is uniform)
-    if (sim == 0) return !((float)dot * rn <= __uint_as_float((uint32_t)thr[p]));
-    if (sim == 2) return nv - 2 * dot <= thr[p];
-    return dot >= thr[p];
-  };
-  const int64_t padded_rows = (tile_end - tile_begin) << 4;   // of this launch
-  // a contiguous run of tiles per wave: one sequential stream of 1 KiB pieces per leaf it crosses
-  const int64_t n_tiles = tile_end - tile_begin;
-  const int64_t n_waves = (int64_t)gridDim.x * (kKnnBytesThreads / 64), w = (int64_t)blockIdx.x * (kKnnBytesThreads / 64) + wave;
-  int64_t t_run = tile_begin + n_tiles * w / n_waves;
-  const int64_t t_run_end = tile_begin + n_tiles * (w + 1) / n_waves;
-  int32_t li = t_run < t_run_end ? kb_leaf_of_tile(leaves, n_leaves, t_run) : 0;
-  while (t_run < t_run_end) {   // (a wave without tiles still meets the others at the queue's barrier)
-    const DKnnBytesLeaf& lf = leaves[li];
-    const uint64_t u_tiles = kb_uniform_u64((uint64_t)lf.tiles), u_norms = kb_uniform_u64((uint64_t)lf.vnorm2);
-    const uint64_t u_o2d = kb_uniform_u64((uint64_t)lf.ord_to_doc), u_accept = kb_uniform_u64((uint64_t)lf.accept);
-    const int64_t leaf_t0 = (int64_t)kb_uniform_u64((uint64_t)lf.tile_begin);
-    const int32_t leaf_rows = __builtin_amdgcn_readfirstlane(lf.n_rows), doc_base = __builtin_amdgcn_readfirstlane(lf.doc_base);
-    const int32_t* const ord_to_doc = (const int32_t*)u_o2d;
-    const uint64_t* const live_bits = (const uint64_t*)u_accept;
-    // the norms through the SCALAR cache (constant address space: s_load, counted by lgkmcnt, not by the ring's vmcnt)
-    typedef const int32_t __attribute__((address_space(4))) cint_k;
-    cint_k* const vnorm2 = (cint_k*)u_norms;
-    const int64_t t0 = t_run - leaf_t0, t1 = min(t_run_end, leaf_t0 + (((int64_t)leaf_rows + 15) >> 4)) - leaf_t0;   // local tiles
-    // the run as groups of D pieces (a tile is steps / D whole groups): ring slot i holds piece i of the current group, and the
-    // same slot of the NEXT group is requested the moment slot i has been consumed
-    const i32x4* cur = (const i32x4*)u_tiles + (t0 * steps) * 64 + lane;
-    const i32x4* const last_group = cur + ((t1 - t0) * steps - D) * 64;
-    i32x4 abuf[D];
-    kb_fill<D, 0>(abuf, cur);
-    for (int64_t tile = t0; tile < t1; ++tile) {
-      const uint32_t t_lo = __builtin_amdgcn_readfirstlane((uint32_t)(tile & 0xFFFFFFFFll));
-      const uint32_t t_hi = __builtin_amdgcn_readfirstlane((uint32_t)(tile >> 32));
-      const int64_t u_r0 = (int64_t)(((uint64_t)t_hi << 32) | t_lo) << 4;
-      int32_t nvt[16];
-#pragma unroll
-      for (int c = 0; c < 16; ++c) nvt[c] = vnorm2[u_r0 + c];
-      i32x4 acc[P];
-#pragma unroll
-      for (int p = 0; p < P; ++p) acc[p] = i32x4{0, 0, 0, 0};
-      for (int32_t s0 = 0; s0 < steps; s0 += D) {
-        const i32x4* nxt = cur < last_group ? cur + D * 64 : cur;   // (past the run's end: its last group again, never used)
-        kb_steps<P, D, 0>(abuf, acc, qs + (size_t)s0 * P * 64 + lane, nxt);
-        cur = nxt;
-      }
-      int32_t nv4[4];
-      float rn4[4];
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        nv4[reg] = kk == 0 ? nvt[reg] : kk == 1 ? nvt[4 + reg] : kk == 2 ? nvt[8 + reg] : nvt[12 + reg];
-        rn4[reg] = sim == 0 ? __builtin_amdgcn_rsqf((float)nv4[reg]) : 0.0f;
-      }
-      const int64_t r0 = tile << 4;                                   // the tile's first row in its leaf
-      const int64_t g0 = (leaf_t0 + tile - tile_begin) << 4;          // ... and its padded position in this launch
-      bool maybe = false;
-#pragma unroll
-      for (int p = 0; p < P; ++p)
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) maybe |= may_pass(p, acc[p][reg], nv4[reg], rn4[reg]);
-      if (maybe)
-#pragma unroll
-      for (int p = 0; p < P; ++p) {
-        const int32_t q = (int32_t)j + 16 * p;
-        if (q < n_q) {
-#pragma unroll
-          for (int reg = 0; reg < 4; ++reg) {
-            if (!may_pass(p, acc[p][reg], nv4[reg], rn4[reg])) continue;
-            const int32_t nq_p = kb_nq[q];
-            const unsigned long long th_p = kb_th[q];
-            const float th_hi_p = kb_thhi[q];
-            const bool slot_round = th_p == 0ull && !append_only;   // no theta yet: every padded row owns a slot
-            uint32_t qv = (uint32_t)q;
-            asm volatile("" : "+v"(qv));   // (the list's address is computed where a row is written, not hoisted out of the stream)
-            const int64_t drow = r0 + 4 * (int32_t)kk + reg;
-            const int64_t gpos = g0 + 4 * (int32_t)kk + reg;
-            bool valid = drow < (int64_t)leaf_rows;
-            float sc = 0.f;
-            if (valid) {
-              const float s = knn_byte_score(sim, dim_user, acc[p][reg], nq_p, nv4[reg]);
-              if (min_score > 0.0f && !(s >= min_score)) valid = false;
-              sc = s * boost;
-            }
-            if (slot_round || (valid && sc > th_hi_p)) {
-              uint32_t qi = 0xFFFFFFFFu;
-              if (!slot_round) qi = atomicAdd(q_n, 1u);
-              if (qi < qcap) {
-                q_e[qi] = ((uint64_t)__float_as_uint(sc) << 32) | ((uint64_t)gpos << 6) | (uint64_t)q;
-              } else {   // the first round's slots (a padding row's holds "nothing"), or a full queue: straight to the list
-                uint64_t key = 0;  // 0 = "nothing": never above a theta
-                if (valid) {
-                  const int32_t ldoc = ord_to_doc ? ord_to_doc[drow] : (int32_t)drow;
-                  bool live = true;
-                  if (live_bits) live = (live_bits[ldoc >> 6] >> (ldoc & 63)) & 1ull;
-                  if (live) key = pack_key(sc, (uint32_t)(doc_base + ldoc));
-                }
-                if (slot_round) {
-                  if ((uint64_t)gpos < (uint64_t)cap) cand[(size_t)qv * cap + (size_t)gpos] = key;
-                  if (gpos == padded_rows - 1) cand_cnt[qv] = (uint32_t)min<int64_t>(padded_rows, (int64_t)0xFFFFFFFFll);
-                } else if (key > th_p) {
-                  const uint32_t pos = atomicAdd(&cand_cnt[qv], 1u);
-                  if (pos < cap) cand[(size_t)qv * cap + pos] = key;
-                }
-                // (its loads and stores are complete here as far as the compiler's bookkeeping goes: with vector memory events
-                // pending at the next tile's loop it would wait vmcnt(0) in front of it -- the ring with them)
-                __builtin_amdgcn_s_waitcnt(0x0F70);
-              }
-            }
-          }
-        }
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the ring's last requests (never used) land before the registers are reused
-    t_run = leaf_t0 + t1;
-    ++li;
-  }
-  __syncthreads();
-  // The queue goes out: a row's place in its query's list comes from the list's counter in global memory -- ONE atomic per
-  // (workgroup, query).  A thread keeps its (<= kFlushPerThread) entries in registers between the count and the write.
-  constexpr int kFlushPerThread = 4;   // qcap <= 4096 = 4 x kKnnBytesThreads (launch_knn_bytes)
-  static_assert(kFlushPerThread * kKnnBytesThreads >= 4096, "the queue's capacity is bounded by what the flush holds in registers");
-  const uint32_t n_queued = min(*q_n, qcap);
-  uint32_t* const f_cnt = (uint32_t*)kb_nq;    // (the per-query tables are done with: their LDS holds the counts and the bases)
-  uint32_t* const f_base = (uint32_t*)kb_thr;
-  __syncthreads();
-  if (tid < 64u) f_cnt[tid] = 0u;
-  __syncthreads();
-  uint64_t my_key[kFlushPerThread];
-  uint32_t my_q[kFlushPerThread], my_rank[kFlushPerThread];
-#pragma unroll
-  for (int r = 0; r < kFlushPerThread; ++r) {
-    const uint32_t i = tid + (uint32_t)r * kKnnBytesThreads;
-    my_q[r] = 0xFFFFFFFFu;
-    my_key[r] = 0ull;
-    my_rank[r] = 0u;
-    if (i < n_queued) {
-      const uint64_t e = q_e[i];
-      const uint32_t q = (uint32_t)(e & 63ull);
-      const int64_t gpos = (int64_t)((e >> 6) & 0x3FFFFFFull);
-      const int64_t tile = tile_begin + (gpos >> 4);
-      const DKnnBytesLeaf lf = leaves[kb_leaf_of_tile(leaves, n_leaves, tile)];
-      const int64_t drow = ((tile - lf.tile_begin) << 4) + (gpos & 15);
-      const int32_t ldoc = lf.ord_to_doc ? lf.ord_to_doc[drow] : (int32_t)drow;
-      bool live = true;
-      if (lf.accept) live = (lf.accept[ldoc >> 6] >> (ldoc & 63)) & 1ull;
-      const uint64_t key = pack_key(__uint_as_float((uint32_t)(e >> 32)), (uint32_t)(lf.doc_base + ldoc));
-      if (live && key > theta[q]) {
-        my_q[r] = q;
-        my_key[r] = key;
-        my_rank[r] = atomicAdd(&f_cnt[q], 1u);
-      }
-    }
-  }
-  __syncthreads();
-  if (tid < 64u) {
-    const uint32_t c = f_cnt[tid];
-    f_base[tid] = c ? atomicAdd(&cand_cnt[tid], c) : 0u;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < kFlushPerThread; ++r)
-    if (my_q[r] != 0xFFFFFFFFu) {
-      const uint32_t pos = f_base[my_q[r]] + my_rank[r];
-      if (pos < cap) cand[(size_t)my_q[r] * cap + pos] = my_key[r];
-    }
-}
+//
+// knn_bytes_kernel and knn_bytes_requests_kernel are ONE body, knn_bytes_body.hiph, compiled twice (it says why it is a text and
+// not a __device__ template).  The second is the pass of nrtgpu_knn_search_bytes_requests, whose queries are knn requests with a
+// filter and a threshold EACH: min_scores[q] (n_q floats) in place of the launch's one min_score, and the leaves bring their rows
+// of the pass's accept table (DKnnBytesLeaf::accept_of, plan.h) in place of their one accept set.
+#define KB_KERNEL knn_bytes_kernel
+#define KB_REQUESTS 0
+#include "knn_bytes_body.hiph"
+#undef KB_KERNEL
+#undef KB_REQUESTS
+#define KB_KERNEL knn_bytes_requests_kernel
+#define KB_REQUESTS 1
+#include "knn_bytes_body.hiph"
+#undef KB_KERNEL
+#undef KB_REQUESTS
 
 // ---- the RESCORER over a byte field (QueryRescore with an ExactByteVectorQuery in the rescore slot) -------------------------
 // A first-pass hit names ONE row, and the rows have one copy: the tiles above.  Row r is not contiguous there -- it is the 16-byte
@@ -559,38 +374,46 @@ void launch_knn_bytes_pack(hipStream_t st, const int8_t* rows, int32_t dim, int6
                      (i32x4*)tiles, norm2);
 }
 
+// min_scores == nullptr: knn_bytes_kernel with the launch's one min_score.  Else a pass of knn requests (knn_bytes_requests_kernel):
+// min_scores = n_q thresholds on the device, every leaf brings its row of the accept table (accept_of), min_score is not read.
 int launch_knn_bytes(hipStream_t st, uint32_t blocks, const DKnnBytesLeaf* leaves, int32_t n_leaves, int32_t dim, int64_t tile_begin,
                      int64_t tile_end, const void* panel, const int32_t* qnorm2, int32_t n_q, int32_t sim, float boost, float min_score,
-                     const unsigned long long* theta, uint64_t* cand, uint32_t* cand_cnt, uint32_t cap, int32_t append_only) {
+                     const unsigned long long* theta, uint64_t* cand, uint32_t* cand_cnt, uint32_t cap, int32_t append_only,
+                     const float* min_scores) {
   if (tile_end <= tile_begin || n_leaves <= 0) return 0;
   if (n_q < 1 || n_q > 64 || dim < 1 || dim > 2048) return (int)hipErrorInvalidValue;
   const int32_t steps = knn_bytes_steps(dim), depth = knn_bytes_depth_of(steps);
   const size_t panel_bytes = knn_bytes_panel_bytes(dim, n_q);
-  // the queue behind the panel: what 160 KiB leave next to the panel and the static tables, 4096 entries at most
-  const uint32_t qcap = (uint32_t)std::min<size_t>(4096, (160 * 1024 - kKnnBytesStaticLds - panel_bytes - 16) / 8);
+  // the queue behind the panel: what 160 KiB leave next to the panel and the kernel's static tables, 4096 entries at most
+  const size_t static_lds = min_scores ? kKnnBytesReqStaticLds : kKnnBytesStaticLds;
+  const uint32_t qcap = (uint32_t)std::min<size_t>(4096, (160 * 1024 - static_lds - panel_bytes - 16) / 8);
   const size_t lds = panel_bytes + 16 + (size_t)qcap * 8;
-#define NRT_BYTES_LAUNCH(PANELS, DEPTH)                                                                                            \
+#define NRT_BYTES_LAUNCH(KERNEL, THRESHOLD, PANELS, DEPTH)                                                                         \
   {                                                                                                                                \
-    hipError_t e = hipFuncSetAttribute((const void*)knn_bytes_kernel<PANELS, DEPTH>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                       (int)lds);                                                                                  \
+    hipError_t e = hipFuncSetAttribute((const void*)KERNEL<PANELS, DEPTH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);  \
     if (e != hipSuccess) return (int)e;                                                                                            \
-    hipLaunchKernelGGL((knn_bytes_kernel<PANELS, DEPTH>), dim3(blocks), dim3(kKnnBytesThreads), lds, st, leaves, n_leaves, steps,  \
-                       dim, tile_begin, tile_end, (const i32x4*)panel, qnorm2, n_q, sim, boost, min_score, theta, cand, cand_cnt,  \
-                       cap, append_only, qcap);                                                                                    \
+    hipLaunchKernelGGL((KERNEL<PANELS, DEPTH>), dim3(blocks), dim3(kKnnBytesThreads), lds, st, leaves, n_leaves, steps, dim,       \
+                       tile_begin, tile_end, (const i32x4*)panel, qnorm2, n_q, sim, boost, THRESHOLD, theta, cand, cand_cnt, cap,  \
+                       append_only, qcap);                                                                                         \
   }
-#define NRT_BYTES_DEPTH(PANELS)                          \
-  switch (depth) {                                       \
-    case 1: NRT_BYTES_LAUNCH(PANELS, 1) break;           \
-    case 2: NRT_BYTES_LAUNCH(PANELS, 2) break;           \
-    case 3: NRT_BYTES_LAUNCH(PANELS, 3) break;           \
-    case 4: NRT_BYTES_LAUNCH(PANELS, 4) break;           \
-    case 5: NRT_BYTES_LAUNCH(PANELS, 5) break;           \
-    case 6: NRT_BYTES_LAUNCH(PANELS, 6) break;           \
-    case 7: NRT_BYTES_LAUNCH(PANELS, 7) break;           \
-    default: NRT_BYTES_LAUNCH(PANELS, 8) break;          \
+#define NRT_BYTES_DEPTH(KERNEL, THRESHOLD, PANELS)                          \
+  switch (depth) {                                                          \
+    case 1: NRT_BYTES_LAUNCH(KERNEL, THRESHOLD, PANELS, 1) break;           \
+    case 2: NRT_BYTES_LAUNCH(KERNEL, THRESHOLD, PANELS, 2) break;           \
+    case 3: NRT_BYTES_LAUNCH(KERNEL, THRESHOLD, PANELS, 3) break;           \
+    case 4: NRT_BYTES_LAUNCH(KERNEL, THRESHOLD, PANELS, 4) break;           \
+    case 5: NRT_BYTES_LAUNCH(KERNEL, THRESHOLD, PANELS, 5) break;           \
+    case 6: NRT_BYTES_LAUNCH(KERNEL, THRESHOLD, PANELS, 6) break;           \
+    case 7: NRT_BYTES_LAUNCH(KERNEL, THRESHOLD, PANELS, 7) break;           \
+    default: NRT_BYTES_LAUNCH(KERNEL, THRESHOLD, PANELS, 8) break;          \
   }
-  if (n_q <= 16) { NRT_BYTES_DEPTH(1) }
-  else { NRT_BYTES_DEPTH(4) }
+  if (min_scores) {
+    if (n_q <= 16) { NRT_BYTES_DEPTH(knn_bytes_requests_kernel, min_scores, 1) }
+    else { NRT_BYTES_DEPTH(knn_bytes_requests_kernel, min_scores, 4) }
+  } else {
+    if (n_q <= 16) { NRT_BYTES_DEPTH(knn_bytes_kernel, min_score, 1) }
+    else { NRT_BYTES_DEPTH(knn_bytes_kernel, min_score, 4) }
+  }
 #undef NRT_BYTES_DEPTH
 #undef NRT_BYTES_LAUNCH
   return 0;

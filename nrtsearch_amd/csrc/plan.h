@@ -429,7 +429,9 @@ struct alignas(16) DKnnBytesLeaf {
   const uint64_t* accept;      // liveDocs (& filter) bits of the leaf; nullptr: every doc
   int64_t tile_begin;
   int32_t n_rows, doc_base;
-  int32_t pad[4];
+  const uint64_t* const* accept_of;   // nullptr, or the leaf's row of the pass's accept table (kKnnAcceptCols above): `accept` per query --
+                                      // read by knn_bytes_requests_kernel only, as DKnnLeaf::accept_of by the sketch kernel
+  int32_t pad[2];
 };
 static_assert(sizeof(DKnnBytesLeaf) == 64, "DKnnBytesLeaf layout");
 // One leaf's byte vector field as the rescorers see it (knn_bytes.hip: hybrid_rescore_bytes_kernel maps a hit's doc to its row on

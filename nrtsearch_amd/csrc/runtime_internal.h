@@ -125,7 +125,8 @@ size_t knn_bytes_panel_bytes(int32_t dim, int32_t n_q);   // a query panel in op
 void launch_knn_bytes_pack(hipStream_t st, const int8_t* rows, int32_t dim, int64_t row0, int64_t n_chunk, void* tiles, int32_t* norm2);
 int launch_knn_bytes(hipStream_t st, uint32_t blocks, const DKnnBytesLeaf* leaves, int32_t n_leaves, int32_t dim, int64_t tile_begin,
                      int64_t tile_end, const void* panel, const int32_t* qnorm2, int32_t n_q, int32_t sim, float boost, float min_score,
-                     const unsigned long long* theta, uint64_t* cand, uint32_t* cand_cnt, uint32_t cap, int32_t append_only = 0);
+                     const unsigned long long* theta, uint64_t* cand, uint32_t* cand_cnt, uint32_t cap, int32_t append_only = 0,
+                     const float* min_scores = nullptr);   // a pass of knn requests: n_q thresholds; the leaves bring accept_of (plan.h)
 // the rescorers over a byte field; query / qvecs: int8 in piece order = the query, zero-padded to 64 * knn_bytes_steps(dim) bytes
 void launch_rescore_byte_vectors(hipStream_t st, const void* tiles, const int32_t* vnorm2, int32_t dim, const void* query, int32_t qnorm2,
                                  int32_t sim, float boost, const int64_t* vec_row, const float* first_scores, int32_t n, double qw, double rw,
@@ -555,7 +556,9 @@ struct nrtgpu_ctx {
                                   // guesses that raised theta in a meeting (nrtgpu_debug_maxscore_meeting_guesses)
   // request coalescing (coalescer.h): the single-query entries' callers merged into batches (nrtgpu_search_bm25_coalesced, search.cpp)
   // and into panels (nrtgpu_knn_exact_coalesced on kco, nrtgpu_knn_search_coalesced on rco: vectors.cpp)
-  nrtgpu::rt::Coalescer co, kco, rco;
+  // (the same two over byte fields: nrtgpu_knn_exact_bytes_coalesced on bkco, nrtgpu_knn_search_bytes_coalesced on brco -- queues of
+  //  their own, so float and byte callers never share a panel)
+  nrtgpu::rt::Coalescer co, kco, rco, bkco, brco;
   int32_t co_linger_us = 150;   // (under co.mu: nrtgpu_set_coalescing)
   // speculative thresholds (plan.h: kHitsSpecInvalid; nrtgpu_debug_spec_counters): queries run under speculation, queries whose guess
   // failed and were run again, and the switch the library throws itself when too many fail (docs not spread like a sample)
@@ -760,6 +763,19 @@ struct KnnRun {
 // k and a boost per member of a panel that was searched with the largest k -- member q takes the first ks[q] keys of its list.
 void knn_unpack_topdocs(const uint64_t* keys, const uint32_t* counts, uint32_t k_stride, int nq, int32_t k, bool clamp_to_k, int64_t total,
                         bool knn_request, float boost, nrtgpu_topdocs* out, const int32_t* ks = nullptr, const float* boosts = nullptr);
+// What differs from request to request in a call of nrtgpu_knn_search_requests / nrtgpu_knn_search_bytes_requests: one value per
+// query, none of them NULL.
+struct KnnPerQuery {
+  const int32_t* ks;
+  const float* boosts;
+  const int32_t* masks;
+  const float* min_scores;
+};
+// The searches over a byte field (vectors_bytes.cpp), as knn_impl is the float ones' (vectors.cpp).  pq: the queries are knn requests
+// with a k, boost, filter and threshold EACH; `k` is the largest of theirs, filter_mask / min_score / boost are not read.
+int knn_bytes_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, int32_t field_id, int32_t sim,
+                   const int8_t* queries, int32_t n_queries, int32_t dim, int32_t k, float boost, bool knn_request, int32_t filter_mask,
+                   float min_score, nrtgpu_topdocs* out, const KnnPerQuery* pq = nullptr);
 
 // ---- the gather route of the filtered knn entries (vectors_gather.cpp) -------------------------------------------
 // A filtered knn request (nrtgpu_knn_search, nrtgpu_knn_search_bytes; filter_mask != 0) whose filter accepts few enough rows reads

@@ -958,11 +958,17 @@ extern "C" int nrtgpu_debug_hold_coalescers(nrtgpu_ctx* ctx, int32_t hold) {
   ctx->co.set_hold(hold != 0);
   ctx->kco.set_hold(hold != 0);
   ctx->rco.set_hold(hold != 0);
+  ctx->bkco.set_hold(hold != 0);
+  ctx->brco.set_hold(hold != 0);
   return NRTGPU_OK;
 }
 extern "C" int nrtgpu_debug_coalescer_pending(nrtgpu_ctx* ctx, int32_t which) {
   if (!ctx) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
-  return which == 0 ? ctx->co.pending_count() : which == 2 ? ctx->rco.pending_count() : ctx->kco.pending_count();
+  return which == 0   ? ctx->co.pending_count()
+         : which == 2 ? ctx->rco.pending_count()
+         : which == 3 ? ctx->brco.pending_count()
+         : which == 4 ? ctx->bkco.pending_count()
+                      : ctx->kco.pending_count();
 }
 #endif
 

@@ -149,14 +149,6 @@ static int knn_check_scalars(bool bad_count, int32_t k, int32_t dim, int32_t sim
   return NRTGPU_OK;
 }
 
-// What differs from request to request in a call of nrtgpu_knn_search_requests: one value per query, none of them NULL here.
-struct KnnPerQuery {
-  const int32_t* ks;
-  const float* boosts;
-  const int32_t* masks;
-  const float* min_scores;
-};
-
 static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
                     int32_t field_id, int32_t sim, const float* queries, int32_t n_queries, int32_t dim,
                     int32_t k, float boost, bool knn_request, int32_t filter_mask, float min_score, nrtgpu_topdocs* out,
@@ -582,9 +574,10 @@ struct KnnCoRequest : CoQueued {
   const int32_t* doc_bases;
   int32_t n_segs, field_id, sim, dim, k;
   float boost;
-  const float* query;
+  const void* query;   // dim elements of elem_size bytes: fp32, or int8 (the byte entries, on coalescers of their own)
+  size_t elem_size;
   nrtgpu_topdocs* out;
-  int32_t filter_mask = 0;   // (the knn request entry only: nrtgpu_knn_search_coalesced)
+  int32_t filter_mask = 0;   // (the knn request entries only: nrtgpu_knn_search_coalesced, nrtgpu_knn_search_bytes_coalesced)
   float min_score = 0.0f;
 };
 
@@ -636,8 +629,8 @@ extern "C" int nrtgpu_knn_exact_relation(nrtgpu_ctx* ctx, const nrtgpu_seg* cons
   return 0;
 }
 
-// The wait of the two single-query vector entries (nrtgpu_knn_exact_coalesced on ctx->kco, nrtgpu_knn_search_coalesced on
-// ctx->rco): one leave rule, one cap.  false: the request travelled in a leader's panel (or expired in the queue), me.rc / me.err
+// The wait of the single-query vector entries (nrtgpu_knn_exact_coalesced on ctx->kco, nrtgpu_knn_search_coalesced on ctx->rco,
+// their byte twins on ctx->bkco and ctx->brco): one leave rule, one cap.  false: the request travelled in a leader's panel (or expired in the queue), me.rc / me.err
 // and its results are in place.  true: this caller leads *batch -- itself first -- and runs it.
 static bool knn_co_wait(Coalescer& co, KnnCoRequest& me, bool same_boost, std::vector<CoQueued*>* batch) {
   me.deadline_ns = g_deadline_ns;
@@ -676,17 +669,19 @@ static bool knn_co_wait(Coalescer& co, KnnCoRequest& me, bool same_boost, std::v
 }
 
 // The leader's panel, outside the lock: the members' queries side by side, the largest k; every member's buffers take its own k.
-// run(queries, kmax, outs) searches them; then every member gets its results (or the panel's error) and its caller is woken.
+// run(queries, kmax, outs) searches them (queries: the members' element type); then every member gets its results (or the panel's
+// error) and its caller is woken.
 template <class Run>
 static int knn_co_run_panel(Coalescer& co, const std::vector<CoQueued*>& batch, KnnCoRequest& me, Run&& run) {
   auto member = [&](size_t i) { return static_cast<KnnCoRequest*>(batch[i]); };
   int32_t kmax = 0;
-  std::vector<float> qs(batch.size() * (size_t)me.dim);
+  const size_t q_bytes = (size_t)me.dim * me.elem_size;
+  std::vector<char> qs(batch.size() * q_bytes);
   std::vector<nrtgpu_topdocs> outs(batch.size());
   for (size_t i = 0; i < batch.size(); ++i) {
     const KnnCoRequest* r = member(i);
     kmax = std::max(kmax, r->k);
-    memcpy(qs.data() + i * (size_t)me.dim, r->query, (size_t)me.dim * 4);
+    memcpy(qs.data() + i * q_bytes, r->query, q_bytes);
     outs[i] = *r->out;
     const int32_t cap = outs[i].capacity > 0 ? outs[i].capacity : r->k;
     outs[i].capacity = std::min(cap, r->k);
@@ -695,7 +690,7 @@ static int knn_co_run_panel(Coalescer& co, const std::vector<CoQueued*>& batch, 
   {
     // (a panel of several requests does not run under its leader's deadline: its mates have not expired)
     DeadlineScope deadline_scope(batch.size() > 1);
-    rc = run(qs.data(), kmax, outs.data());
+    rc = run((const void*)qs.data(), kmax, outs.data());
   }
   const std::string err = rc ? g_last_error : std::string();
   for (size_t i = 0; i < batch.size(); ++i) {
@@ -714,25 +709,95 @@ static int knn_co_run_panel(Coalescer& co, const std::vector<CoQueued*>& batch, 
   return rc;
 }
 
-extern "C" int nrtgpu_knn_exact_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
-                                          int32_t field_id, int32_t sim, const float* query, int32_t dim, int32_t k, float boost,
-                                          nrtgpu_topdocs* out) {
+// ------------------------------------------------------------------------------------------------
+// The element type of a vector entry.  The request and the coalesced entries over float fields and their twins over byte (int8)
+// fields are ONE code below -- the checks, the passes, the panels -- handed the kind, as the rescorers are handed a RescoreKind
+// (runtime_internal.h); what a kind brings is its search (knn_impl here, knn_bytes_impl in vectors_bytes.cpp), its refusals of the
+// other element type, and the panels that fit its kernel's LDS.
+// ------------------------------------------------------------------------------------------------
+struct KnnKind {
+  bool bytes;         // int8 rows and queries; else fp32
+  size_t elem_size;   // bytes of a query element
+  // queries per pass over the rows (float: knn_impl's, the panels that fit the LDS; byte: four panels of 16 at every dimension)
+  int32_t pass_q(int32_t dim) const { return !bytes && dim > 1280 ? 16 : kKnnMaxQ; }
+  int search(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, int32_t field_id, int32_t sim,
+             const void* queries, int32_t n_queries, int32_t dim, int32_t k, float boost, bool knn_request, int32_t filter_mask, float min_score,
+             nrtgpu_topdocs* out, const KnnPerQuery* pq = nullptr) const {
+    if (bytes)
+      return knn_bytes_impl(ctx, segs, doc_bases, n_segs, field_id, sim, (const int8_t*)queries, n_queries, dim, k, boost, knn_request, filter_mask,
+                            min_score, out, pq);
+    return knn_impl(ctx, segs, doc_bases, n_segs, field_id, sim, (const float*)queries, n_queries, dim, k, boost, knn_request, filter_mask, min_score,
+                    out, nullptr, nullptr, nullptr, pq);
+  }
+};
+static const KnnKind kKnnFloat{false, 4}, kKnnBytes{true, 1};
+
+// What an entry of `kind` asks of the field in leaf si (f: the field there): the kind's element type and the queries' dimension.
+// *has_rows: the leaf holds rows a search of the kind reads.
+static int knn_check_field(const KnnKind& kind, int si, int32_t field_id, const FieldData& f, int32_t dim, bool* has_rows) {
+  *has_rows = false;
+  if (!kind.bytes) {
+    if (f.byte_rows)
+      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d holds byte (int8) vectors: search it with nrtgpu_knn_exact_bytes / nrtgpu_knn_search_bytes",
+                  si, field_id);
+    if (!f.d_vectors) return NRTGPU_OK;
+  } else {
+    if (!f.byte_rows && (f.d_vectors || f.dim > 0))
+      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d holds float (fp32) vectors: search it with nrtgpu_knn_exact / nrtgpu_knn_search", si, field_id);
+    if (!f.byte_rows) return NRTGPU_OK;
+  }
+  if (f.dim_user != dim) return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d has dimension %d, query has %d", si, field_id, f.dim_user, dim);
+  *has_rows = kind.bytes ? (f.d_btiles && f.n_vec > 0) : true;
+  return NRTGPU_OK;
+}
+// What only a byte entry asks of its queries and its boost, in knn_bytes_impl's words: cosine refuses a zero query as the reference
+// does (validateVectorForSearch, VectorFieldDef.java:853-861), named like every other bad request.
+static int knn_check_queries(const KnnKind& kind, int32_t sim, const void* queries, int32_t n_queries, int32_t dim) {
+  if (!kind.bytes || sim != 0) return NRTGPU_OK;
+  for (int32_t q = 0; q < n_queries; ++q) {
+    const int8_t* v = (const int8_t*)queries + (size_t)q * dim;
+    if (std::all_of(v, v + dim, [](int8_t x) { return x == 0; }))
+      return fail(NRTGPU_ERR_INVALID_ARG, "query %d: a zero vector: cosine similarity is not defined for it", q);
+  }
+  return NRTGPU_OK;
+}
+
+// nrtgpu_knn_exact_coalesced and nrtgpu_knn_exact_bytes_coalesced, on the kind's own coalescer.
+static int knn_exact_coalesced(const KnnKind& kind, Coalescer& co, nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases,
+                               int32_t n_segs, int32_t field_id, int32_t sim, const void* query, int32_t dim, int32_t k, float boost,
+                               nrtgpu_topdocs* out) {
   if (!ctx || !query || !out || (n_segs > 0 && !segs)) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
   // (what would fail the panel must fail this request alone)
   if (int rc = knn_check_scalars(n_segs < 0, k, dim, sim)) return rc;
+  if (kind.bytes && (!(boost >= 0.0f) || !(boost < INFINITY))) return fail(NRTGPU_ERR_INVALID_ARG, "byte vector search: a finite boost >= 0 expected");
+  if (int rc = knn_check_queries(kind, sim, query, 1, dim)) return rc;
   for (int si = 0; si < n_segs; ++si) {
     if (!segs[si] || !segs[si]->sealed) return fail(NRTGPU_ERR_STATE, "segment %d missing or not sealed", si);
     auto fit = segs[si]->fields.find(field_id);
-    if (fit != segs[si]->fields.end() && fit->second.d_vectors && fit->second.dim_user != dim)
-      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d has dimension %d, query has %d", si, field_id, fit->second.dim_user, dim);
+    bool has_rows = false;
+    if (fit != segs[si]->fields.end())
+      if (int rc = knn_check_field(kind, si, field_id, fit->second, dim, &has_rows)) return rc;
   }
   NRT_CHECK_DEADLINE("before the request was queued");
-  KnnCoRequest me{{}, segs, doc_bases, n_segs, field_id, sim, dim, k, boost, query, out};
+  KnnCoRequest me{{}, segs, doc_bases, n_segs, field_id, sim, dim, k, boost, query, kind.elem_size, out};
   std::vector<CoQueued*> batch;
-  if (!knn_co_wait(ctx->kco, me, true, &batch)) return me.rc;
-  return knn_co_run_panel(ctx->kco, batch, me, [&](const float* qs, int32_t kmax, nrtgpu_topdocs* outs) {
-    return knn_impl(ctx, segs, doc_bases, n_segs, field_id, sim, qs, (int32_t)batch.size(), dim, kmax, boost, false, 0, 0.0f, outs);
+  if (!knn_co_wait(co, me, true, &batch)) return me.rc;
+  return knn_co_run_panel(co, batch, me, [&](const void* qs, int32_t kmax, nrtgpu_topdocs* outs) {
+    return kind.search(ctx, segs, doc_bases, n_segs, field_id, sim, qs, (int32_t)batch.size(), dim, kmax, boost, false, 0, 0.0f, outs);
   });
+}
+
+extern "C" int nrtgpu_knn_exact_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                          int32_t field_id, int32_t sim, const float* query, int32_t dim, int32_t k, float boost,
+                                          nrtgpu_topdocs* out) {
+  if (!ctx) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
+  return knn_exact_coalesced(kKnnFloat, ctx->kco, ctx, segs, doc_bases, n_segs, field_id, sim, query, dim, k, boost, out);
+}
+extern "C" int nrtgpu_knn_exact_bytes_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                                int32_t field_id, int32_t sim, const int8_t* query, int32_t dim, int32_t k, float boost,
+                                                nrtgpu_topdocs* out) {
+  if (!ctx) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
+  return knn_exact_coalesced(kKnnBytes, ctx->bkco, ctx, segs, doc_bases, n_segs, field_id, sim, query, dim, k, boost, out);
 }
 
 extern "C" int nrtgpu_knn_search(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
@@ -755,10 +820,10 @@ static int knn_request_check(int32_t qi, int32_t k, float boost, int32_t filter_
   if (k > NRTGPU_MAX_K) return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: k %d > %d", qi, k, NRTGPU_MAX_K);
   return NRTGPU_OK;
 }
-// What the call asks of the field in every leaf (a float field of the queries' dimension, or absent) and of the requests' masks
-// (resident on every leaf that holds the field's rows -- the leaves a search would read them on).  Host only.
-static int knn_requests_check_leaves(const nrtgpu_seg* const* segs, int32_t n_segs, int32_t field_id, int32_t dim, const int32_t* masks,
-                                     int32_t n_queries) {
+// What the call asks of the field in every leaf (a field of the kind's element type and of the queries' dimension, or absent) and
+// of the requests' masks (resident on every leaf that holds the field's rows -- the leaves a search would read them on).  Host only.
+static int knn_requests_check_leaves(const KnnKind& kind, const nrtgpu_seg* const* segs, int32_t n_segs, int32_t field_id, int32_t dim,
+                                     const int32_t* masks, int32_t n_queries) {
   for (int si = 0; si < n_segs; ++si)
     if (!segs[si]) return fail(NRTGPU_ERR_STATE, "segment %d missing or not sealed", si);
   SegReadLocks content(segs, n_segs);   // (the handles' masks are read)
@@ -766,12 +831,9 @@ static int knn_requests_check_leaves(const nrtgpu_seg* const* segs, int32_t n_se
     if (!segs[si]->sealed) return fail(NRTGPU_ERR_STATE, "segment %d missing or not sealed", si);
     auto fit = segs[si]->fields.find(field_id);
     if (fit == segs[si]->fields.end()) continue;
-    if (fit->second.byte_rows)
-      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d holds byte (int8) vectors: search it with nrtgpu_knn_exact_bytes / nrtgpu_knn_search_bytes",
-                  si, field_id);
-    if (!fit->second.d_vectors) continue;
-    if (fit->second.dim_user != dim)
-      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d has dimension %d, query has %d", si, field_id, fit->second.dim_user, dim);
+    bool has_rows = false;
+    if (int rc = knn_check_field(kind, si, field_id, fit->second, dim, &has_rows)) return rc;
+    if (!has_rows) continue;
     for (int32_t q = 0; masks && q < n_queries; ++q)
       if (masks[q] != 0 && segs[si]->masks.find(masks[q]) == segs[si]->masks.end())
         return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: filter mask %d is not resident on segment %d", q, masks[q], si);
@@ -780,37 +842,40 @@ static int knn_requests_check_leaves(const nrtgpu_seg* const* segs, int32_t n_se
 }
 
 // The requests are valid (knn_request_check, knn_requests_check_leaves) and none of the arrays is NULL.
-static int knn_requests_run(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, int32_t field_id, int32_t sim,
-                            const float* queries, int32_t n_queries, int32_t dim, const KnnPerQuery& pq, nrtgpu_topdocs* out) {
+static int knn_requests_run(const KnnKind& kind, nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                            int32_t field_id, int32_t sim, const void* queries, int32_t n_queries, int32_t dim, const KnnPerQuery& pq,
+                            nrtgpu_topdocs* out) {
   bool all_equal = true;
   for (int32_t q = 1; q < n_queries && all_equal; ++q)
     all_equal = pq.ks[q] == pq.ks[0] && pq.boosts[q] == pq.boosts[0] && pq.masks[q] == pq.masks[0] && pq.min_scores[q] == pq.min_scores[0];
-  if (all_equal)   // one filter, one threshold: nrtgpu_knn_search's own path, the gather route included
-    return knn_impl(ctx, segs, doc_bases, n_segs, field_id, sim, queries, n_queries, dim, pq.ks[0], pq.boosts[0], true, pq.masks[0], pq.min_scores[0], out);
-  const int32_t pass_q = dim > 1280 ? 16 : kKnnMaxQ;   // (knn_impl's: the panels that fit the LDS)
+  if (all_equal)   // one filter, one threshold: nrtgpu_knn_search's (nrtgpu_knn_search_bytes') own path, the gather route included
+    return kind.search(ctx, segs, doc_bases, n_segs, field_id, sim, queries, n_queries, dim, pq.ks[0], pq.boosts[0], true, pq.masks[0],
+                       pq.min_scores[0], out);
+  const int32_t pass_q = kind.pass_q(dim);
   for (int32_t q0 = 0; q0 < n_queries; q0 += pass_q) {
     const int32_t nq = std::min(pass_q, n_queries - q0);
     if (q0 > 0 && deadline_passed(g_deadline_ns))
       return fail(NRTGPU_ERR_TIMEOUT, "deadline passed between two passes over the rows (%d of %d queries answered)", q0, n_queries);
     const KnnPerQuery pass{pq.ks + q0, pq.boosts + q0, pq.masks + q0, pq.min_scores + q0};
     const int32_t k_pass = *std::max_element(pass.ks, pass.ks + nq);
-    if (int rc = knn_impl(ctx, segs, doc_bases, n_segs, field_id, sim, queries + (size_t)q0 * dim, nq, dim, k_pass, 1.0f, true, 0, 0.0f, out + q0,
-                          nullptr, nullptr, nullptr, &pass))
+    if (int rc = kind.search(ctx, segs, doc_bases, n_segs, field_id, sim, (const char*)queries + (size_t)q0 * dim * kind.elem_size, nq, dim, k_pass,
+                             1.0f, true, 0, 0.0f, out + q0, &pass))
       return rc;
   }
   return NRTGPU_OK;
 }
 
-extern "C" int nrtgpu_knn_search_requests(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
-                                          int32_t field_id, int32_t sim, const float* queries, int32_t n_queries, int32_t dim,
-                                          const int32_t* ks, const float* boosts, const int32_t* filter_masks, const float* min_scores,
-                                          nrtgpu_topdocs* out) {
+// nrtgpu_knn_search_requests and nrtgpu_knn_search_bytes_requests.
+static int knn_search_requests(const KnnKind& kind, nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                               int32_t field_id, int32_t sim, const void* queries, int32_t n_queries, int32_t dim, const int32_t* ks,
+                               const float* boosts, const int32_t* filter_masks, const float* min_scores, nrtgpu_topdocs* out) {
   if (!ctx || !queries || !out || !ks || (n_segs > 0 && !segs)) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
   if (int rc = knn_check_scalars(n_queries <= 0 || n_segs < 0, 1, dim, sim)) return rc;
   // a bad request refuses the whole call before anything is launched
   for (int32_t q = 0; q < n_queries; ++q)
     if (int rc = knn_request_check(q, ks[q], boosts ? boosts[q] : 1.0f, filter_masks ? filter_masks[q] : 0, min_scores ? min_scores[q] : 0.0f)) return rc;
-  if (int rc = knn_requests_check_leaves(segs, n_segs, field_id, dim, filter_masks, n_queries)) return rc;
+  if (int rc = knn_check_queries(kind, sim, queries, n_queries, dim)) return rc;
+  if (int rc = knn_requests_check_leaves(kind, segs, n_segs, field_id, dim, filter_masks, n_queries)) return rc;
   NRT_CHECK_DEADLINE("before the vector search started");
   std::vector<float> one, none_f;
   std::vector<int32_t> none_i;
@@ -818,22 +883,24 @@ extern "C" int nrtgpu_knn_search_requests(nrtgpu_ctx* ctx, const nrtgpu_seg* con
   if (!min_scores) none_f.assign((size_t)n_queries, 0.0f);
   if (!filter_masks) none_i.assign((size_t)n_queries, 0);
   const KnnPerQuery pq{ks, boosts ? boosts : one.data(), filter_masks ? filter_masks : none_i.data(), min_scores ? min_scores : none_f.data()};
-  return knn_requests_run(ctx, segs, doc_bases, n_segs, field_id, sim, queries, n_queries, dim, pq, out);
+  return knn_requests_run(kind, ctx, segs, doc_bases, n_segs, field_id, sim, queries, n_queries, dim, pq, out);
 }
 
-extern "C" int nrtgpu_knn_search_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
-                                           int32_t field_id, int32_t sim, const float* query, int32_t dim, int32_t k, float boost,
-                                           int32_t filter_mask, float min_score, nrtgpu_topdocs* out) {
+// nrtgpu_knn_search_coalesced and nrtgpu_knn_search_bytes_coalesced, on the kind's own coalescer.
+static int knn_search_coalesced(const KnnKind& kind, Coalescer& co, nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases,
+                                int32_t n_segs, int32_t field_id, int32_t sim, const void* query, int32_t dim, int32_t k, float boost,
+                                int32_t filter_mask, float min_score, nrtgpu_topdocs* out) {
   if (!ctx || !query || !out || (n_segs > 0 && !segs)) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
-  // (what would fail the panel must fail this request alone: its scalars, the field, its mask on every leaf)
+  // (what would fail the panel must fail this request alone: its scalars, its query, the field, its mask on every leaf)
   if (int rc = knn_check_scalars(n_segs < 0, 1, dim, sim)) return rc;
   if (int rc = knn_request_check(0, k, boost, filter_mask, min_score)) return rc;
-  if (int rc = knn_requests_check_leaves(segs, n_segs, field_id, dim, &filter_mask, 1)) return rc;
+  if (int rc = knn_check_queries(kind, sim, query, 1, dim)) return rc;
+  if (int rc = knn_requests_check_leaves(kind, segs, n_segs, field_id, dim, &filter_mask, 1)) return rc;
   NRT_CHECK_DEADLINE("before the request was queued");
-  KnnCoRequest me{{}, segs, doc_bases, n_segs, field_id, sim, dim, k, boost, query, out, filter_mask, min_score};
+  KnnCoRequest me{{}, segs, doc_bases, n_segs, field_id, sim, dim, k, boost, query, kind.elem_size, out, filter_mask, min_score};
   std::vector<CoQueued*> batch;
-  if (!knn_co_wait(ctx->rco, me, false, &batch)) return me.rc;
-  return knn_co_run_panel(ctx->rco, batch, me, [&](const float* qs, int32_t, nrtgpu_topdocs* outs) {
+  if (!knn_co_wait(co, me, false, &batch)) return me.rc;
+  return knn_co_run_panel(co, batch, me, [&](const void* qs, int32_t, nrtgpu_topdocs* outs) {
     std::vector<int32_t> ks(batch.size()), masks(batch.size());
     std::vector<float> boosts(batch.size()), mins(batch.size());
     for (size_t i = 0; i < batch.size(); ++i) {
@@ -844,8 +911,33 @@ extern "C" int nrtgpu_knn_search_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* co
       mins[i] = r->min_score;
     }
     const KnnPerQuery pq{ks.data(), boosts.data(), masks.data(), mins.data()};
-    return knn_requests_run(ctx, segs, doc_bases, n_segs, field_id, sim, qs, (int32_t)batch.size(), dim, pq, outs);
+    return knn_requests_run(kind, ctx, segs, doc_bases, n_segs, field_id, sim, qs, (int32_t)batch.size(), dim, pq, outs);
   });
+}
+
+extern "C" int nrtgpu_knn_search_requests(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                          int32_t field_id, int32_t sim, const float* queries, int32_t n_queries, int32_t dim,
+                                          const int32_t* ks, const float* boosts, const int32_t* filter_masks, const float* min_scores,
+                                          nrtgpu_topdocs* out) {
+  return knn_search_requests(kKnnFloat, ctx, segs, doc_bases, n_segs, field_id, sim, queries, n_queries, dim, ks, boosts, filter_masks, min_scores, out);
+}
+extern "C" int nrtgpu_knn_search_bytes_requests(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                                int32_t field_id, int32_t sim, const int8_t* queries, int32_t n_queries, int32_t dim,
+                                                const int32_t* ks, const float* boosts, const int32_t* filter_masks, const float* min_scores,
+                                                nrtgpu_topdocs* out) {
+  return knn_search_requests(kKnnBytes, ctx, segs, doc_bases, n_segs, field_id, sim, queries, n_queries, dim, ks, boosts, filter_masks, min_scores, out);
+}
+extern "C" int nrtgpu_knn_search_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                           int32_t field_id, int32_t sim, const float* query, int32_t dim, int32_t k, float boost,
+                                           int32_t filter_mask, float min_score, nrtgpu_topdocs* out) {
+  if (!ctx) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
+  return knn_search_coalesced(kKnnFloat, ctx->rco, ctx, segs, doc_bases, n_segs, field_id, sim, query, dim, k, boost, filter_mask, min_score, out);
+}
+extern "C" int nrtgpu_knn_search_bytes_coalesced(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                                 int32_t field_id, int32_t sim, const int8_t* query, int32_t dim, int32_t k, float boost,
+                                                 int32_t filter_mask, float min_score, nrtgpu_topdocs* out) {
+  if (!ctx) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
+  return knn_search_coalesced(kKnnBytes, ctx->brco, ctx, segs, doc_bases, n_segs, field_id, sim, query, dim, k, boost, filter_mask, min_score, out);
 }
 
 // The two-call rescorer: QueryRescorer over a first pass's hits, for either element type (runtime_internal.h: RescoreKind).

@@ -10,10 +10,13 @@
 static const uint32_t kKnnBytesCap = 1u << 18;   // candidate keys per query and round (2 MiB)
 static const int kKnnBytesMaxQ = 64;             // queries per pass over the rows: four panels of 16
 
-static int knn_bytes_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, int32_t field_id,
-                          int32_t sim, const int8_t* queries, int32_t n_queries, int32_t dim, int32_t k, float boost, bool knn_request,
-                          int32_t filter_mask, float min_score, nrtgpu_topdocs* out) {
+int nrtgpu::rt::knn_bytes_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, int32_t field_id,
+                               int32_t sim, const int8_t* queries, int32_t n_queries, int32_t dim, int32_t k, float boost, bool knn_request,
+                               int32_t filter_mask, float min_score, nrtgpu_topdocs* out, const KnnPerQuery* pq) {
   forget_foreign_hip_error();
+  // pq: the queries are knn requests with a k, boost, filter and threshold EACH (nrtgpu_knn_search_bytes_requests), as in knn_impl
+  // (vectors.cpp).  The device differs in two inputs: a table of accept sets per (leaf, query) in place of the leaf's one, and the
+  // queries' own thresholds in place of the launch's one (knn_bytes.hip: knn_bytes_requests_kernel).  Scores stay unboosted.
   if (!ctx || !queries || !out || (n_segs > 0 && !segs)) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
   if (n_queries <= 0 || k <= 0 || dim <= 0 || sim < 0 || sim > 3 || n_segs < 0) return fail(NRTGPU_ERR_INVALID_ARG, "bad knn arguments");
   // (hits are kept as keys whose order is the order of NON-NEGATIVE float bits: a negative boost would rank them backwards)
@@ -38,7 +41,7 @@ static int knn_bytes_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const 
     if (f.byte_rows && f.dim_user != dim)
       return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d has dimension %d, query has %d", si, field_id, f.dim_user, dim);
   }
-  if (knn_request && filter_mask != 0) {   // a selective filter: score only the rows it accepts (vectors_gather.cpp)
+  if (knn_request && filter_mask != 0 && !pq) {   // a selective filter: score only the rows it accepts (vectors_gather.cpp)
     const KnnGatherCall call{true, field_id, sim, k, filter_mask, dim, boost, min_score, queries, qn2.data(), n_queries, kKnnBytesCap};
     bool gather = false;
     int64_t estimate = 0;
@@ -57,6 +60,8 @@ static int knn_bytes_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const 
   // the head [o_p, o_th) is staged in pinned memory laid out alike: one copy per panel
   const size_t o_p = wc.take(panel_max), o_qn = wc.take(kKnnBytesMaxQ * 4);
   const size_t o_leaves = wc.take((size_t)std::max(n_segs, 1) * sizeof(DKnnBytesLeaf));
+  const size_t o_ms = wc.take(pq ? kKnnBytesMaxQ * 4 : 8);   // pq: the queries' thresholds on the unboosted score (0: none)
+  const size_t o_acc = wc.take(pq ? (size_t)std::max(n_segs, 1) * kKnnAcceptCols * sizeof(uint64_t*) : 8);   // pq: the accept table (plan.h)
   const size_t o_th = wc.take(kKnnBytesMaxQ * 8);
   const size_t o_tk = wc.take((size_t)kKnnBytesMaxQ * k_stride * 8), o_tc = wc.take(kKnnBytesMaxQ * 4);
   const size_t o_cc = wc.take(kKnnBytesMaxQ * 4), o_ov = wc.take(64);
@@ -70,6 +75,10 @@ static int knn_bytes_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const 
   char* hs = (char*)slot->h_aux.p;
   // the leaves' tiles of 16 rows, numbered through: ONE launch walks every leaf
   DKnnBytesLeaf* hleaves = (DKnnBytesLeaf*)(hs + o_leaves);
+  float* ms = (float*)(hs + o_ms);
+  const uint64_t** hacc = (const uint64_t**)(hs + o_acc);
+  const uint64_t* const* d_acc = pq ? (const uint64_t* const*)(wb + o_acc) : nullptr;
+  std::vector<int32_t> kleaf_seg;   // the kernel's leaves -> the call's
   int32_t n_kleaves = 0;
   int64_t total_tiles = 0, total_rows = 0, live_vectors = 0;
   for (int si = 0; si < n_segs; ++si) {
@@ -78,13 +87,15 @@ static int knn_bytes_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const 
     const FieldData& f = fit->second;
     live_vectors += live_vector_count(segs[si], f);   // (deleted docs are masked inside the kernel and are no hits)
     const uint64_t* accept = segs[si]->d_live;
-    if (knn_request && filter_mask != 0)
+    if (knn_request && filter_mask != 0 && !pq)
       if (int rc = accept_set_of(segs[si], filter_mask, 0, &accept)) return rc;
+    kleaf_seg.push_back(si);
     DKnnBytesLeaf l{};
     l.tiles = f.d_btiles;
     l.vnorm2 = f.d_bnorm2;
     l.ord_to_doc = f.d_ord_to_doc;
     l.accept = accept;
+    l.accept_of = d_acc ? d_acc + (size_t)n_kleaves * kKnnAcceptCols : nullptr;
     l.tile_begin = total_tiles;
     l.n_rows = f.n_vec;
     l.doc_base = doc_bases ? doc_bases[si] : 0;
@@ -115,8 +126,27 @@ static int knn_bytes_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const 
     }
     memset(hs + o_qn, 0, kKnnBytesMaxQ * 4);
     memcpy(hs + o_qn, qn2.data() + q0, (size_t)nq * 4);
+    if (pq) {   // the members' thresholds, and liveDocs & the member's filter per (leaf, member): each distinct filter of the pass is
+                // looked up once per leaf (vectors.cpp: knn_impl does the same for the float kernels)
+      for (int q = 0; q < kKnnBytesMaxQ; ++q) ms[q] = q < nq ? pq->min_scores[q0 + q] : 0.0f;
+      memset(hacc, 0, (size_t)std::max(n_segs, 1) * kKnnAcceptCols * sizeof(uint64_t*));
+      for (int32_t kl = 0; kl < n_kleaves; ++kl) {
+        const nrtgpu_seg* seg = segs[kleaf_seg[(size_t)kl]];
+        for (int q = 0; q < nq; ++q) {
+          const int32_t mask = pq->masks[q0 + q];
+          const uint64_t*& slot_q = hacc[(size_t)kl * kKnnAcceptCols + q];
+          slot_q = seg->d_live;
+          if (mask == 0) continue;
+          int same = -1;
+          for (int p = 0; p < q && same < 0; ++p)
+            if (pq->masks[q0 + p] == mask) same = p;
+          if (same >= 0) slot_q = hacc[(size_t)kl * kKnnAcceptCols + same];
+          else if (int rc = accept_set_of(seg, mask, 0, &slot_q)) return rc;
+        }
+      }
+    }
     HIP_TRY(hipMemcpyAsync(wb + o_p, hs + o_p, panel_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(wb + o_qn, hs + o_qn, o_th - o_qn, hipMemcpyHostToDevice, st));   // |q|^2, leaf table
+    HIP_TRY(hipMemcpyAsync(wb + o_qn, hs + o_qn, o_th - o_qn, hipMemcpyHostToDevice, st));   // |q|^2, leaf table (pq: thresholds, accept table)
     // One pass over the rows of every leaf in KnnRun::tile_rounds' rounds, always nominating.  Rows in rising order of similarity
     // could overflow a list: the selection flags that and the panel is redone in rounds no longer than the list (`safe`).
     for (int safe = 0;; ++safe) {
@@ -126,7 +156,8 @@ static int knn_bytes_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const 
         return run.timed_launch("knn_bytes", [&]() {
           return launch_knn_bytes(st, blocks, (const DKnnBytesLeaf*)(wb + o_leaves), n_kleaves, dim, t, te, wb + o_p, (const int32_t*)(wb + o_qn),
                                   nq, sim, score_boost, knn_request ? min_score : 0.0f, (const unsigned long long*)(wb + o_th),
-                                  (uint64_t*)(wb + o_cd), (uint32_t*)(wb + o_cc), kKnnBytesCap, append_only);
+                                  (uint64_t*)(wb + o_cd), (uint32_t*)(wb + o_cc), kKnnBytesCap, append_only,
+                                  pq ? (const float*)(wb + o_ms) : nullptr);
         });
       };
       if (int rc = run.tile_rounds(total_tiles, kFirstRound, kKnnBytesCap, true, safe, launch, [&]() {
@@ -142,7 +173,8 @@ static int knn_bytes_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const 
       if (safe) return fail(NRTGPU_ERR_HIP, "knn_bytes: candidate list overflow in a bounded round");
     }
     run.add_stats(total_rows, 0, false);
-    knn_unpack_topdocs((const uint64_t*)ho, (const uint32_t*)(ho + oh_cnt), k_stride, nq, k, true, live_vectors, knn_request, boost, &out[q0]);
+    knn_unpack_topdocs((const uint64_t*)ho, (const uint32_t*)(ho + oh_cnt), k_stride, nq, k, true, live_vectors, knn_request, boost, &out[q0],
+                       pq ? pq->ks + q0 : nullptr, pq ? pq->boosts + q0 : nullptr);
   }
   return NRTGPU_OK;
 }
