@@ -87,7 +87,23 @@ extern "C" int nrtgpu_debug_knn_unpack(const float* scores, const int32_t* docs,
   std::vector<uint64_t> keys((size_t)n_queries * (size_t)k_stride, 0ull);
   for (size_t i = 0; i < keys.size(); ++i)
     if ((uint32_t)(i % (size_t)k_stride) < counts[i / (size_t)k_stride]) keys[i] = pack_key(scores[i], (uint32_t)docs[i]);
-  knn_unpack_topdocs(keys.data(), counts, (uint32_t)k_stride, n_queries, k_pass, false, 0, true, 1.0f, out, ks, boosts);
+  const KnnUniform one{k_pass, 0, 1.0f, 0.0f};
+  std::vector<int32_t> k_of((size_t)n_queries, k_pass);
+  std::vector<float> boost_of((size_t)n_queries, 1.0f);
+  const KnnAsk each{ks ? ks : k_of.data(), boosts ? boosts : boost_of.data(), nullptr, nullptr, 1};
+  knn_unpack_topdocs(keys.data(), counts, (uint32_t)k_stride, n_queries, false, 0, true, ks || boosts ? each : one.ask(), out);
+  return NRTGPU_OK;
+}
+
+// Test hook (tests/test_knn_query_stats_host.py binds it itself: the Python bindings list the header's symbols and stay as they
+// are): the query statistics of a float pass (vectors.cpp: knn_query_stats) of n_queries x dim floats -- |q|^2, the largest
+// |element| and the 1-norm per query as the search computes them, eight queries side by side -- next to |q|^2 by the rescorers'
+// chain (float_qnorm2), one query after the other: the two must agree bit for bit.  No context, no device work.
+extern "C" int nrtgpu_debug_knn_query_stats(const float* queries, int32_t n_queries, int32_t dim, float* norm2, float* max_abs, double* l1,
+                                            float* ref_norm2) {
+  if (!queries || !norm2 || !max_abs || !l1 || !ref_norm2 || n_queries <= 0 || dim <= 0) return fail(NRTGPU_ERR_INVALID_ARG, "bad knn_query_stats arguments");
+  knn_query_stats(queries, n_queries, dim, norm2, max_abs, l1);
+  for (int32_t q = 0; q < n_queries; ++q) ref_norm2[q] = float_qnorm2(queries + (size_t)q * dim, dim);
   return NRTGPU_OK;
 }
 

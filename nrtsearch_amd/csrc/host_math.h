@@ -296,7 +296,7 @@ inline void plan_item_counts(const int64_t* cost, int32_t n, int64_t target_item
   for (size_t i = 0; i < frac.size() && given < target_items; ++i, ++given) items[frac[i].second]++;
 }
 
-// ---- exact vector search: the rounding bounds the answers are certified with (vectors.cpp: knn_impl) ----------------
+// ---- exact vector search: the rounding bounds the answers are certified with (vectors.cpp: KnnFloatSearch::stage_bounds) ----------------
 // |estimate - result| <= E: both are fp32 evaluations of the same length-dim sums, each within gamma = dim * 2^-24 (relative
 // to the sum of the terms' magnitudes) of the real value whatever the order; the maps to a score have slope <= 1 and add a
 // few roundings (e_rel).  Pure functions of the search's numbers -- dim is the RESIDENT dimension (a multiple of 16), nq the

@@ -689,8 +689,122 @@ struct SlotGuard {
   ~SlotGuard() { release_slot(c, s); }
 };
 
-// What the two exact searches (knn_impl in vectors.cpp, knn_bytes_impl in vectors_bytes.cpp) share around their kernels: the turns
-// on the device, the timed scoring launches, the rounds over the leaves' tiles, a panel's statistics and the unpacking.
+// ---- one description of a vector search, and what the float and the byte searches share around their kernels --------------------
+constexpr uint32_t kKnnCap = 1u << 18;   // candidate keys per query and round (2 MiB): the float, the byte and the gather lists alike
+constexpr int kKnnMaxQ = 64;   // queries per pass over the rows, and the widest panel a coalescer forms (float: two panels of 32 on
+                               // paired workgroups up to 1280 dimensions, knn.hip; byte: four panels of 16, knn_bytes.hip)
+// What the queries of a search ask, one value per query: query q's are at [q * stride].  stride 0 is ONE value for every query --
+// nrtgpu_knn_search's request, or an ExactVectorQuery's k and boost -- so a uniform request is an array like any other and the
+// searches read nothing else.
+struct KnnAsk {
+  const int32_t* ks;
+  const float* boosts;
+  const int32_t* masks;       // pre-filter mask ids (0: none)
+  const float* min_scores;    // thresholds on the unboosted score (0: none)
+  int32_t stride;
+  int32_t k(int q) const { return ks[(size_t)q * stride]; }
+  float boost(int q) const { return boosts[(size_t)q * stride]; }
+  int32_t mask(int q) const { return masks[(size_t)q * stride]; }
+  float min_score(int q) const { return min_scores[(size_t)q * stride]; }
+  KnnAsk from(int q0) const { return {ks + (size_t)q0 * stride, boosts + (size_t)q0 * stride, masks + (size_t)q0 * stride, min_scores + (size_t)q0 * stride, stride}; }
+};
+struct KnnUniform {   // the storage of a stride-0 view
+  int32_t k, mask;
+  float boost, min_score;
+  KnnAsk ask() const { return {&k, &boost, &mask, &min_score, 0}; }
+};
+// One vector search: the leaves, the queries, what is asked and where the answer goes.  knn_search (vectors.cpp) and
+// knn_bytes_search (vectors_bytes.cpp) take it, as do the gather route and the passes of the requests entries.
+struct KnnCall {
+  const nrtgpu_seg* const* segs;
+  const int32_t* doc_bases;   // NULL: zeros
+  int32_t n_segs, field_id;
+  bool bytes;            // int8 rows and queries; else fp32
+  const void* queries;   // n_queries x dim elements, row-major
+  int32_t n_queries, dim, sim;
+  // false: ExactVectorQuery -- every doc with a vector matches, the boost is inside the score.  true: `knn` requests -- pre-filter,
+  // threshold on the unboosted score (MinThresholdQuery's MinScoreWrapper), boost applied afterwards, totalHits = the docs returned.
+  bool knn_request;
+  KnnAsk ask;
+  nrtgpu_topdocs* out;   // one per query; or NULL and the device-resident triple of the multi-GPU path (float rows only): per query
+                         // k_stride sorted keys, its count, and the live vectors of these leaves as the hit total
+  char *ext_keys = nullptr, *ext_cnts = nullptr, *ext_hits = nullptr;
+  int32_t k_max() const {   // a pass is searched with the largest k of its members; every member takes the first k of its own
+    int32_t k = ask.ks[0];
+    for (int32_t q = 1; q < n_queries && ask.stride; ++q) k = std::max(k, ask.k(q));
+    return k;
+  }
+  // All members share one filter and one threshold: the leaf's one accept set and the launch's one threshold serve them (and the
+  // gather route may); else the pass carries an accept table per (leaf, member) and a threshold per member.
+  bool one_filter() const { return ask.stride == 0; }
+  int32_t shared_mask() const { return one_filter() ? ask.masks[0] : 0; }   // != 0: the selective filter of a uniform request
+  float score_boost() const { return knn_request ? 1.0f : ask.boosts[0]; }
+};
+
+// The leaves of a call that hold rows of its element type, in order: fn(const KnnLeaf&) -> int for each, until one fails.
+//   mask < 0: no accept set is looked up (accept = nullptr);  0: liveDocs;  > 0: liveDocs & the mask, ONE accept_set_of per leaf
+// and walk -- the walks of a search look a set up as often, and in the order, the loops they replace did.
+struct KnnLeaf {
+  const nrtgpu_seg* seg;
+  const FieldData* f;
+  int32_t si, index;              // the call's leaf; the leaves with rows before it
+  int32_t doc_base;
+  int64_t tile_begin, row_begin;  // tiles of 16 rows / rows of the leaves before it
+  int64_t live;                   // vectors whose doc is live (deleted docs are masked inside the kernels and are no hits)
+  const uint64_t* accept;         // (vectors are not re-coded for liveDocs: always the mask)
+  int64_t accept_docs;            // mask > 0: the docs of the set
+};
+template <class Fn>
+int knn_walk_leaves(const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, int32_t field_id, bool bytes, int32_t mask, Fn&& fn) {
+  KnnLeaf l{};
+  for (int si = 0; si < n_segs; ++si) {
+    auto fit = segs[si]->fields.find(field_id);
+    if (fit == segs[si]->fields.end() || fit->second.n_vec == 0) continue;
+    const FieldData& f = fit->second;
+    if (!(bytes ? f.d_btiles != nullptr : f.d_vectors != nullptr)) continue;
+    l.seg = segs[si];
+    l.f = &f;
+    l.si = si;
+    l.doc_base = doc_bases ? doc_bases[si] : 0;
+    l.live = live_vector_count(segs[si], f);
+    l.accept = mask < 0 ? nullptr : segs[si]->d_live;
+    if (mask > 0)
+      if (int rc = accept_set_of(segs[si], mask, 0, &l.accept, &l.accept_docs)) return rc;
+    if (int rc = fn((const KnnLeaf&)l)) return rc;
+    ++l.index;
+    l.tile_begin += ((int64_t)f.n_vec + 15) >> 4;
+    l.row_begin += f.n_vec;
+  }
+  return NRTGPU_OK;
+}
+template <class Fn>
+int knn_walk_leaves(const KnnCall& c, int32_t mask, Fn&& fn) {
+  return knn_walk_leaves(c.segs, c.doc_bases, c.n_segs, c.field_id, c.bytes, mask, fn);
+}
+// liveDocs & the member's filter per (leaf, member) of a pass that carries an accept table (plan.h: kKnnAcceptCols pointers per
+// leaf with rows) into `table`: each distinct mask of the pass is looked up once per leaf.
+int knn_stage_accept_table(const KnnCall& c, int q0, int nq, const uint64_t** table);
+// What a vector entry asks of the field `f` in leaf si: rows of its own element type -- the other type is refused with the
+// caller's hint of where to take it -- and of the queries' dimension (dim 0: the caller checks the dimension itself).  *has_rows:
+// the leaf holds rows a search of the kind reads.  knn_check_leaves: the same of every leaf that has the field.
+int knn_check_field(bool bytes, int si, int32_t field_id, const FieldData& f, int32_t dim, const char* hint, bool* has_rows = nullptr);
+int knn_check_leaves(const nrtgpu_seg* const* segs, int32_t n_segs, int32_t field_id, bool bytes, int32_t dim, const char* hint);
+constexpr const char* kHintSearchBytes = "search it with nrtgpu_knn_exact_bytes / nrtgpu_knn_search_bytes";
+constexpr const char* kHintSearchFloat = "search it with nrtgpu_knn_exact / nrtgpu_knn_search";
+constexpr const char* kHintRescoreFloat = "rescore it with nrtgpu_rescore_vectors / nrtgpu_search_hybrid_batch";
+constexpr const char* kHintHybridFloatOnly = "the hybrid tail rescores float vector fields only";
+// What the searches ask of their scalars; bad_count: the caller's own count (queries, leaves) is out of range -- the same refusal.
+// knn_check_byte_boost: hits are kept as keys whose order is the order of NON-NEGATIVE float bits: a negative boost would rank
+// them backwards.  byte_boost: knn_bytes_search tests its boost BEFORE k and the dimension are held against the device's limits
+// (the coalesced byte entries test theirs after knn_check_scalars: the entries' refusals keep their order).
+int knn_check_scalars(bool bad_count, int32_t k, int32_t dim, int32_t sim, const float* byte_boost = nullptr);
+int knn_check_byte_boost(float boost);
+// |q|^2 (fp32, in element order, every product rounded before it is added: float_qnorm2's chain), the largest |element| and the
+// 1-norm of nq queries of `dim` floats; max_abs / l1 may be NULL.  Each sum is a chain of dependent additions, so eight queries are
+// walked side by side -- eight independent chains, every query's own order untouched.
+void knn_query_stats(const float* queries, int nq, int dim, float* norm2, float* max_abs, double* l1);
+
+// The turns on the device, the timed scoring launches, the rounds over the leaves' tiles, a panel's statistics.
 struct KnnRun {
   nrtgpu_ctx* ctx;
   Slot* slot;
@@ -755,53 +869,44 @@ struct KnnRun {
     if (pending) select();
     return NRTGPU_OK;
   }
+  // A pass whose candidate list can overflow (rows in rising order of similarity: every row beats theta): pass(safe) runs it and
+  // leaves *overflow -- the flag it fetched -- behind; raised, the pass is redone once in rounds no longer than the list (safe = 1),
+  // and a flag still up fails with the caller's text.
+  template <class Pass>
+  int redo_on_overflow(const uint32_t* overflow, const char* text, Pass&& pass) {
+    for (int safe = 0; safe < 2; ++safe) {
+      if (int rc = pass(safe)) return rc;
+      if (*overflow == 0u) return NRTGPU_OK;
+    }
+    return fail(NRTGPU_ERR_HIP, "%s", text);
+  }
   // the panel is answered: its launches, their time and its rows into the context's statistics; n_ev starts over
   void add_stats(int64_t rows, int64_t sketch_launches, bool second_pass);
 };
 // A panel's sorted keys -> the callers' nrtgpu_topdocs.  clamp_to_k: counts[q] may exceed k (the byte search's running list).
-// knn_request: totalHits = the docs returned, the boost applied afterwards; else `total`.  ks / boosts (NULL: k / boost for all): a
-// k and a boost per member of a panel that was searched with the largest k -- member q takes the first ks[q] keys of its list.
-void knn_unpack_topdocs(const uint64_t* keys, const uint32_t* counts, uint32_t k_stride, int nq, int32_t k, bool clamp_to_k, int64_t total,
-                        bool knn_request, float boost, nrtgpu_topdocs* out, const int32_t* ks = nullptr, const float* boosts = nullptr);
-// What differs from request to request in a call of nrtgpu_knn_search_requests / nrtgpu_knn_search_bytes_requests: one value per
-// query, none of them NULL.
-struct KnnPerQuery {
-  const int32_t* ks;
-  const float* boosts;
-  const int32_t* masks;
-  const float* min_scores;
-};
-// The searches over a byte field (vectors_bytes.cpp), as knn_impl is the float ones' (vectors.cpp).  pq: the queries are knn requests
-// with a k, boost, filter and threshold EACH; `k` is the largest of theirs, filter_mask / min_score / boost are not read.
-int knn_bytes_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, int32_t field_id, int32_t sim,
-                   const int8_t* queries, int32_t n_queries, int32_t dim, int32_t k, float boost, bool knn_request, int32_t filter_mask,
-                   float min_score, nrtgpu_topdocs* out, const KnnPerQuery* pq = nullptr);
+// knn_request: totalHits = the docs returned, the boost applied afterwards; else `total`.  ask: the members' k and boost -- member
+// q of a panel that was searched with the largest k takes the first k(q) keys of its list.
+void knn_unpack_topdocs(const uint64_t* keys, const uint32_t* counts, uint32_t k_stride, int nq, bool clamp_to_k, int64_t total,
+                        bool knn_request, const KnnAsk& ask, nrtgpu_topdocs* out);
+// The searches: over float rows (vectors.cpp) and over byte rows (vectors_bytes.cpp).
+int knn_search(nrtgpu_ctx* ctx, const KnnCall& call);
+int knn_bytes_search(nrtgpu_ctx* ctx, const KnnCall& call);
 
 // ---- the gather route of the filtered knn entries (vectors_gather.cpp) -------------------------------------------
-// A filtered knn request (nrtgpu_knn_search, nrtgpu_knn_search_bytes; filter_mask != 0) whose filter accepts few enough rows reads
-// only those: the accepted rows are listed on the device, scored with final score bits and selected (knn_select_kernel<false>).
-// Called by knn_impl / knn_bytes_impl behind their argument checks, refusals and SegReadLocks.
-struct KnnGatherCall {
-  bool bytes;                  // a byte (int8) field
-  int32_t field_id, sim, k, filter_mask;
-  int32_t dim;                 // float: the RESIDENT dimension (queries padded like the rows); byte: the field's own
-  float boost, min_score;
-  const void* queries;         // n_queries x dim floats / int8, row-major
-  const int32_t* byte_qnorm2;  // byte field: |q|^2 per query (byte_queries_stage)
-  int32_t n_queries;
-  uint32_t cap;                // keys of one candidate list of the caller's full pass
-};
+// A uniform knn request with a filter (KnnCall::shared_mask() != 0) whose filter accepts few enough rows reads only those: the
+// accepted rows are listed on the device, scored with final score bits and selected (knn_select_kernel<false>).  Called by
+// knn_search / knn_bytes_search behind their argument checks, refusals and SegReadLocks; the call's float queries are padded to
+// the RESIDENT dimension.  byte_qnorm2: a byte field's |q|^2 per query (byte_queries_stage), all the route adds to the call.
 // The route decision: *gather iff the context's knob (nrtgpu_set_knn_gather) is > 0, the filter accepts at most that share of the
 // field's rows over these leaves and the accepted rows fit one candidate list.  *estimate = sum over the leaves that hold the
 // field of min(docs of the accept set, rows): an upper bound of the accepted rows (a sparse ord -> doc map accepts fewer).
-int knn_gather_route(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const KnnGatherCall& call, bool* gather, int64_t* estimate);
-int knn_gather_run(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, const KnnGatherCall& call,
-                   int64_t estimate, nrtgpu_topdocs* out);
+int knn_gather_route(nrtgpu_ctx* ctx, const KnnCall& call, bool* gather, int64_t* estimate);
+int knn_gather_run(nrtgpu_ctx* ctx, const KnnCall& call, const int32_t* byte_qnorm2, int64_t estimate);
 
 // ---- the vector rescorers (vectors.cpp; what is specific to byte fields: vectors_bytes.cpp) ----------------------------------
 // |q|^2 of a float query as the rescoring kernels' results depend on it: fp32, in element order, every product rounded before it is
-// added.  The one chain the rescoring kernels' inputs use (knn_impl stages its panels' |q|^2 with a walk of its own, eight queries side
-// by side in the same element order).
+// added.  The one chain the rescoring kernels' inputs use (the searches stage their panels' |q|^2 with knn_query_stats above: eight
+// queries side by side in the same element order).
 float float_qnorm2(const float* q, int dim);
 // The inputs of the rescoring kernels (hybrid_rescore_kernel, hybrid_rescore_bytes_kernel, knn_refine_select_kernel) into host
 // memory of the caller, each part optional (NULL):
@@ -824,9 +929,8 @@ int rescore_hits_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int3
                       const RescoreKind& kind, const int32_t* docs, const float* first_scores, int32_t n, double query_weight, int32_t window,
                       nrtgpu_topdocs* out);
 // What the byte entries (vectors_bytes.cpp; the byte tail of search_hybrid_impl, search.cpp) ask before anything is staged: of their
-// scalars, and of the field in every leaf (byte rows of the query's dimension, or absent).
+// scalars (the field in every leaf -- byte rows of the query's dimension, or absent: knn_check_leaves).
 int byte_rescore_check_args(int32_t sim, int32_t dim, float boost, int32_t window);
-int byte_rescore_check_leaves(const nrtgpu_seg* const* segs, int32_t n_segs, int32_t field_id, int32_t dim);
 size_t byte_query_stride(int32_t dim);
 // n queries of `dim` int8 -> piece order and |q|^2 as int32 (padded / qnorm2 may be NULL: check only)
 int byte_queries_stage(const int8_t* queries, int32_t n, int32_t dim, int32_t sim, int8_t* padded, int32_t* qnorm2);

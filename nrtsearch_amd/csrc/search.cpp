@@ -692,15 +692,6 @@ extern "C" int nrtgpu_debug_spec_counters(nrtgpu_ctx* ctx, int64_t* out3) {
 // entry has refused what the byte scorer does not take) -- else fp32 and hybrid_rescore_kernel.  The tail's inputs (leaf table,
 // queries, |q|^2) are staged by stage_rescore_inputs (vectors.cpp) for both; planning, first pass, slots, locks, deadlines,
 // speculation tags, the copy back and the accounting are one code path.
-static int refuse_byte_field(const nrtgpu_seg* const* segs, int32_t n_segs, int32_t field_id) {
-  for (int si = 0; si < n_segs; ++si) {
-    auto fit = segs[si]->fields.find(field_id);
-    if (fit != segs[si]->fields.end() && fit->second.byte_rows)
-      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d holds byte (int8) vectors: the hybrid tail rescores float vector fields only", si, field_id);
-  }
-  return NRTGPU_OK;
-}
-
 static int search_hybrid_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases,
                               int32_t n_segs, const nrtgpu_bm25_query* queries, int32_t n_queries,
                               int32_t field_id, int32_t sim, const void* query_vectors, bool bytes, int32_t dim, float boost,
@@ -721,7 +712,8 @@ static int search_hybrid_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, co
   if (!content_held) content.emplace(segs, n_segs);
   // the other element type (a byte tail: another dimension too) is refused before anything is planned; the float queries are padded
   // below, once the dimension is known to fit
-  if (int rc = bytes ? byte_rescore_check_leaves(segs, n_segs, field_id, dim) : refuse_byte_field(segs, n_segs, field_id)) return rc;
+  // (dim 0: the float tail holds the dimension against the rows further down, in words of its own)
+  if (int rc = knn_check_leaves(segs, n_segs, field_id, bytes, bytes ? dim : 0, bytes ? kHintRescoreFloat : kHintHybridFloatOnly)) return rc;
   if (int rc = build_plan(ctx, segs, doc_bases, n_segs, queries, n_queries, hp, 1)) return rc;
   const double plan_ms = now_ms() - t0;
   for (int si = 0; si < n_segs; ++si) {

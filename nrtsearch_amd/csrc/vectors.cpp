@@ -2,28 +2,57 @@
 #include "runtime_internal.h"
 
 // ------------------------------------------------------------------------------------------------
-// ABI: exact vector search / vector rescore
+// What the float and the byte entries share before anything is launched (runtime_internal.h): the checks, the accept table, the
+// query statistics, turn-taking, the statistics and the unpacking
 // ------------------------------------------------------------------------------------------------
-static const uint32_t kKnnCap = 1u << 18;   // candidate keys per query and round (2 MiB)
-static const int kKnnMaxQ = 64;   // queries per pass over the rows: two panels of 32 on paired workgroups (knn.hip)
+int nrtgpu::rt::knn_check_scalars(bool bad_count, int32_t k, int32_t dim, int32_t sim, const float* byte_boost) {
+  if (bad_count || k <= 0 || dim <= 0 || sim < 0 || sim > 3) return fail(NRTGPU_ERR_INVALID_ARG, "bad knn arguments");
+  if (byte_boost)
+    if (int rc = knn_check_byte_boost(*byte_boost)) return rc;
+  if (k > NRTGPU_MAX_K) return fail(NRTGPU_ERR_UNSUPPORTED, "k %d > %d", k, NRTGPU_MAX_K);
+  if (dim > 2048) return fail(NRTGPU_ERR_UNSUPPORTED, "vector dimension %d (device path takes <= 2048)", dim);
+  return NRTGPU_OK;
+}
+int nrtgpu::rt::knn_check_byte_boost(float boost) {
+  if (!(boost >= 0.0f) || !(boost < INFINITY)) return fail(NRTGPU_ERR_INVALID_ARG, "byte vector search: a finite boost >= 0 expected");
+  return NRTGPU_OK;
+}
 
-// Shared by the two vector entry points.  knn_request = false: ExactVectorQuery (every doc with a vector
-// matches, boost inside the score).  knn_request = true: the `knn` request path -- pre-filter mask, score
-// threshold on the unboosted score (MinThresholdQuery's MinScoreWrapper), boost applied afterwards,
-// totalHits = the docs returned.
+int nrtgpu::rt::knn_check_field(bool bytes, int si, int32_t field_id, const FieldData& f, int32_t dim, const char* hint, bool* has_rows) {
+  if (has_rows) *has_rows = false;
+  if (!bytes) {
+    if (f.byte_rows) return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d holds byte (int8) vectors: %s", si, field_id, hint);
+    if (!f.d_vectors) return NRTGPU_OK;
+  } else {
+    if (!f.byte_rows && (f.d_vectors || f.dim > 0))
+      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d holds float (fp32) vectors: %s", si, field_id, hint);
+    if (!f.byte_rows) return NRTGPU_OK;
+  }
+  if (dim != 0 && f.dim_user != dim)
+    return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d has dimension %d, query has %d", si, field_id, f.dim_user, dim);
+  if (has_rows) *has_rows = bytes ? (f.d_btiles && f.n_vec > 0) : true;
+  return NRTGPU_OK;
+}
+int nrtgpu::rt::knn_check_leaves(const nrtgpu_seg* const* segs, int32_t n_segs, int32_t field_id, bool bytes, int32_t dim, const char* hint) {
+  for (int si = 0; si < n_segs; ++si) {
+    auto fit = segs[si]->fields.find(field_id);
+    if (fit != segs[si]->fields.end())
+      if (int rc = knn_check_field(bytes, si, field_id, fit->second, dim, hint)) return rc;
+  }
+  return NRTGPU_OK;
+}
+
+// (nrtgpu_search_hybrid_batch refuses byte fields itself, before it plans, and pads here afterwards: search.cpp)
 int nrtgpu::rt::pad_query_vectors(const nrtgpu_seg* const* segs, int32_t n_segs, int32_t field_id, const float* queries, int32_t n,
                                   int32_t dim_user, PaddedQueries* out) {
   int32_t dim_dev = (dim_user + 15) & ~15;
   for (int si = 0; si < n_segs; ++si) {
     if (!segs[si]) continue;
     auto fit = segs[si]->fields.find(field_id);
-    if (fit != segs[si]->fields.end() && fit->second.byte_rows)   // (knn_impl, the rescorer and the multi-GPU hybrid tail pad their queries here; nrtgpu_search_hybrid_batch refuses byte fields itself, before it plans, and pads here afterwards: search.cpp)
-      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d holds byte (int8) vectors: search it with nrtgpu_knn_exact_bytes / nrtgpu_knn_search_bytes",
-                  si, field_id);
-    if (fit == segs[si]->fields.end() || !fit->second.d_vectors) continue;
-    if (fit->second.dim_user != dim_user)
-      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d has dimension %d, query has %d", si, field_id, fit->second.dim_user, dim_user);
-    dim_dev = fit->second.dim;
+    if (fit == segs[si]->fields.end()) continue;
+    bool has_rows = false;
+    if (int rc = knn_check_field(false, si, field_id, fit->second, dim_user, kHintSearchBytes, &has_rows)) return rc;
+    if (has_rows) dim_dev = fit->second.dim;
   }
   out->dim = dim_dev;
   if (dim_dev == dim_user) {
@@ -36,7 +65,64 @@ int nrtgpu::rt::pad_query_vectors(const nrtgpu_seg* const* segs, int32_t n_segs,
   return NRTGPU_OK;
 }
 
-// ---- what the float and the byte paths share (runtime_internal.h) --------------------------------------------------------------
+int nrtgpu::rt::knn_stage_accept_table(const KnnCall& c, int q0, int nq, const uint64_t** table) {
+  memset(table, 0, (size_t)std::max(c.n_segs, 1) * kKnnAcceptCols * sizeof(uint64_t*));
+  return knn_walk_leaves(c, -1, [&](const KnnLeaf& at) -> int {
+    const uint64_t** row = table + (size_t)at.index * kKnnAcceptCols;
+    for (int q = 0; q < nq; ++q) {
+      const int32_t mask = c.ask.mask(q0 + q);
+      row[q] = at.seg->d_live;
+      if (mask == 0) continue;
+      int same = -1;
+      for (int p = 0; p < q && same < 0; ++p)
+        if (c.ask.mask(q0 + p) == mask) same = p;
+      if (same >= 0) row[q] = row[same];
+      else if (int rc = accept_set_of(at.seg, mask, 0, &row[q])) return rc;
+    }
+    return NRTGPU_OK;
+  });
+}
+
+// (0.11 ms -> 0.035 ms per 64-query panel of 768 dimensions against one query after the other: a pass's staging is host time no
+// kernel runs under for one caller)
+template <bool kAll>
+static void query_stats_walk(const float* queries, int nq, int dim, float* norm2, float* max_abs, double* l1) {
+  for (int qb = 0; qb < nq; qb += 8) {
+    const int nb = std::min(8, nq - qb);
+    float s2[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, mx[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    double a1[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const float* qv0 = queries + (size_t)qb * dim;
+    {
+#pragma clang fp contract(off)   // (x * x rounded, then added: never one fused operation, whatever the build's flags)
+      auto walk = [&](const int n) {
+        for (int d = 0; d < dim; ++d)
+          for (int j = 0; j < n; ++j) {
+            const float x = qv0[(size_t)j * dim + d];
+            const float p2 = x * x;
+            s2[j] = s2[j] + p2;
+            if (kAll) {
+              mx[j] = std::max(mx[j], std::fabs(x));
+              a1[j] += std::fabs((double)x);
+            }
+          }
+      };
+      if (nb == 8) walk(8);   // (a constant trip count: unrolled, the eight sums in registers)
+      else walk(nb);
+    }
+    for (int j = 0; j < nb; ++j) {
+      norm2[qb + j] = s2[j];
+      if (kAll) {
+        max_abs[qb + j] = mx[j];
+        l1[qb + j] = a1[j];
+      }
+    }
+  }
+}
+void nrtgpu::rt::knn_query_stats(const float* queries, int nq, int dim, float* norm2, float* max_abs, double* l1) {
+  if (max_abs && l1) query_stats_walk<true>(queries, nq, dim, norm2, max_abs, l1);
+  else query_stats_walk<false>(queries, nq, dim, norm2, nullptr, nullptr);
+}
+
 int nrtgpu::rt::KnnRun::take_turn() {
   std::lock_guard<std::mutex> gpu(ctx->gpu_mu);
   if (ctx->last_turn) HIP_TRY(hipStreamWaitEvent(slot->stream, ctx->last_turn, 0));
@@ -64,16 +150,15 @@ void nrtgpu::rt::KnnRun::add_stats(int64_t rows, int64_t sketch_launches, bool s
   ctx->stats.knn_sketch_launches += sketch_launches;
   n_ev = 0;
 }
-void nrtgpu::rt::knn_unpack_topdocs(const uint64_t* keys, const uint32_t* counts, uint32_t k_stride, int nq, int32_t k_all, bool clamp_to_k,
-                                    int64_t total, bool knn_request, float boost_all, nrtgpu_topdocs* out, const int32_t* ks,
-                                    const float* boosts) {
+void nrtgpu::rt::knn_unpack_topdocs(const uint64_t* keys, const uint32_t* counts, uint32_t k_stride, int nq, bool clamp_to_k, int64_t total,
+                                    bool knn_request, const KnnAsk& ask, nrtgpu_topdocs* out) {
   for (int q = 0; q < nq; ++q) {
     nrtgpu_topdocs* o = &out[q];
     // (a member of a pass searched with the largest k of its members takes the first k of its own: a prefix of a sorted list)
-    const int32_t k = ks ? ks[q] : k_all;
-    const float boost = boosts ? boosts[q] : boost_all;
+    const int32_t k = ask.k(q);
+    const float boost = ask.boost(q);
     const int32_t cap = o->capacity > 0 ? o->capacity : k;
-    const int32_t m = std::min<int32_t>((int32_t)(clamp_to_k || ks ? std::min<uint32_t>(counts[q], (uint32_t)k) : counts[q]), cap);
+    const int32_t m = std::min<int32_t>((int32_t)(clamp_to_k || ask.stride ? std::min<uint32_t>(counts[q], (uint32_t)k) : counts[q]), cap);
     for (int32_t i = 0; i < m; ++i) {
       if (o->docs) o->docs[i] = (int32_t)key_doc(keys[(size_t)q * k_stride + i]);
       if (o->scores) o->scores[i] = key_score(keys[(size_t)q * k_stride + i]);
@@ -140,261 +225,228 @@ int nrtgpu::rt::stage_rescore_inputs(const nrtgpu_seg* const* segs, const int32_
   return NRTGPU_OK;
 }
 
-// What the float searches ask of their scalars (knn_impl, and nrtgpu_knn_exact_coalesced before it queues a request); bad_count: the
-// caller's own count (queries, leaves) is out of range -- the same refusal.
-static int knn_check_scalars(bool bad_count, int32_t k, int32_t dim, int32_t sim) {
-  if (bad_count || k <= 0 || dim <= 0 || sim < 0 || sim > 3) return fail(NRTGPU_ERR_INVALID_ARG, "bad knn arguments");
-  if (k > NRTGPU_MAX_K) return fail(NRTGPU_ERR_UNSUPPORTED, "k %d > %d", k, NRTGPU_MAX_K);
-  if (dim > 2048) return fail(NRTGPU_ERR_UNSUPPORTED, "vector dimension %d (device path takes <= 2048)", dim);
+// ------------------------------------------------------------------------------------------------
+// The element type of a vector entry.  The request and the coalesced entries over float fields and their twins over byte (int8)
+// fields are ONE code further down -- the checks, the passes, the panels -- handed the kind, as the rescorers are handed a
+// RescoreKind (runtime_internal.h); what a kind brings is its search (knn_search here, knn_bytes_search in vectors_bytes.cpp), its
+// refusals of the other element type, and the panels that fit its kernel's LDS.
+// ------------------------------------------------------------------------------------------------
+struct KnnKind {
+  bool bytes;         // int8 rows and queries; else fp32
+  size_t elem_size;   // bytes of a query element
+  const char* other_type_hint;   // where the other element type's fields are searched (knn_check_field)
+  // queries per pass over the rows: 160 KB of LDS hold the float search's two 16-query panels up to 1280 dimensions, beyond that
+  // one panel (16 queries per pass) up to 2048; the byte search's four panels of 16 fit at every dimension
+  int32_t pass_q(int32_t dim) const { return !bytes && dim > 1280 ? 16 : kKnnMaxQ; }
+  int search(nrtgpu_ctx* ctx, const KnnCall& call) const { return bytes ? knn_bytes_search(ctx, call) : knn_search(ctx, call); }
+};
+static const KnnKind kKnnFloat{false, 4, kHintSearchBytes}, kKnnBytes{true, 1, kHintSearchFloat};
+
+// ------------------------------------------------------------------------------------------------
+// The exact search over float rows
+// ------------------------------------------------------------------------------------------------
+// The workspace of a float search (the slot's d_work): offsets, built here and nowhere else.  The panel's inputs are staged in
+// pinned memory laid out like the head [o_q, o_th): two copies per panel, no sync.  The answer, its counts, the certificates and
+// the overflow flag come back into h_out at 0, oh_cnt, oh_cert, oh_ov.
+struct KnnLayout {
+  uint32_t k_stride, k_int, ki_stride;
+  size_t o_q, o_qn, o_eb, o_eb16, o_qs, o_segs, o_leaves, o_ms, o_acc, o_th, o_tk, o_tc, o_cc, o_xk, o_xc, o_cert, o_ov, o_p16, o_cd, size;
+  size_t oh_cnt, oh_cert, oh_ov;
+  KnnLayout(int32_t dim, int32_t n_segs, int32_t k, bool table) {
+    k_stride = round_up((uint32_t)k, 16);
+    // The matrix-core pass NOMINATES: it keeps the k_int best rows by its estimate of the score (an fp32 fma chain in the
+    // MFMA's order, |q|^2 + |v|^2 - 2 q.v for EUCLIDEAN).  The answer is the top k of the nominations rescored in the
+    // oracle's order (knn_score_seq), certified against the rows left outside (knn.hip: knn_select_kernel<true>).
+    k_int = std::min<uint32_t>((uint32_t)NRTGPU_MAX_K, (uint32_t)k + std::max<uint32_t>(32u, (uint32_t)k / 2u));
+    ki_stride = round_up(k_int, 16);
+    const size_t leaves = (size_t)std::max(n_segs, 1);
+    Carver wc;
+    o_q = wc.take((size_t)kKnnMaxQ * dim * 4), o_qn = wc.take(kKnnMaxQ * 4), o_eb = wc.take(kKnnMaxQ * 4);
+    o_eb16 = wc.take(kKnnMaxQ * 4), o_qs = wc.take(kKnnMaxQ * 4);
+    o_segs = wc.take(leaves * sizeof(DVecSeg));     // the leaves' vector matrices, for docid -> row on the device (the rescoring reads rows by docid)
+    o_leaves = wc.take(leaves * sizeof(DKnnLeaf));   // the sketch kernel's leaf table (plan.h)
+    o_ms = wc.take(kKnnMaxQ * 4);   // the queries' thresholds on the unboosted score (0: none)
+    o_acc = wc.take(table ? leaves * kKnnAcceptCols * sizeof(uint64_t*) : 8);   // the accept table (plan.h)
+    o_th = wc.take(kKnnMaxQ * 8);
+    o_tk = wc.take((size_t)kKnnMaxQ * ki_stride * 8), o_tc = wc.take(kKnnMaxQ * 4);
+    o_cc = wc.take(kKnnMaxQ * 4), o_xk = wc.take((size_t)kKnnMaxQ * k_stride * 8);
+    o_xc = wc.take(kKnnMaxQ * 4), o_cert = wc.take(kKnnMaxQ * 4), o_ov = wc.take(64);   // (fetched in one copy)
+    o_p16 = wc.take(160 * 1024);   // the panel in fp16, the sketch kernel's operand order (knn_panel_fp16_kernel)
+    o_cd = wc.take((size_t)kKnnMaxQ * kKnnCap * 8);
+    size = wc.off;
+    oh_cnt = (size_t)kKnnMaxQ * k_stride * 8, oh_cert = oh_cnt + (o_cert - o_xc), oh_ov = oh_cnt + (o_ov - o_xc);
+  }
+};
+
+// One float search on its slot: what the call fixes (the leaves' tables and statistics), then pass after pass of up to pass_q
+// queries -- staged, nominated from the fp16 sketch or the fp32 rows, rescored, certified, and the uncertified answered by a
+// second pass.
+struct KnnFloatSearch {
+  nrtgpu_ctx* ctx;
+  const KnnCall& call;   // (the queries padded to the RESIDENT dimension, call.dim)
+  Slot* slot;
+  const int32_t k;       // the largest of the call
+  const KnnLayout L;
+  KnnRun run{ctx, slot};   // (the turns on the device and what they order: runtime_internal.h)
+  hipStream_t st = slot->stream;
+  const bool table = !call.one_filter();
+  const int32_t dim = call.dim, sim = call.sim, n_segs = call.n_segs;
+  const float score_boost = call.score_boost(), erel = hostmath::knn_e_rel();
+  char *wb = nullptr, *ho = nullptr, *hs = nullptr;
+  // the leaves
+  int32_t n_kleaves = 0;
+  int64_t total_tiles = 0, total_rows = 0, live_vectors = 0;
+  double nv_max = 0.0, nv_min = INFINITY, rows_unit = 0.0;   // rows_unit: the largest 1 / scale of the leaves' sketches
+  bool sketch_ok = false;
+  // the pass under way
+  int q0 = 0, nq = 0;
+  bool panel_sketch = false;
+  int64_t total_vec = 0, rows_scored = 0, sketch_launches = 0;
+  float q_max_of[kKnnMaxQ];
+  double q_l1_of[kKnnMaxQ];
+
+  float* staged(size_t off) const { return (float*)(hs + off); }
+  const uint32_t* certified() const { return (const uint32_t*)(ho + L.oh_cert); }
+  const uint32_t* overflow() const { return (const uint32_t*)(ho + L.oh_ov); }
+  const uint64_t* const* d_acc() const { return table ? (const uint64_t* const*)(wb + L.o_acc) : nullptr; }
+
+  int reserve();
+  int stage_leaves(int pass_q);
+  void stage_bounds();
+  int stage_pass();
+  void select();
+  void refine(size_t o_list, size_t o_cnt, uint32_t cap, size_t o_bound, int32_t certify);
+  int rows_pass(bool nominate, int safe);
+  int sketch_pass(int safe, bool nominate);
+  int fetch();
+  int first_stage(int safe);
+  void second_theta(const float* bound, std::vector<uint64_t>& th2);
+  int second_pass(bool from_sketch, int safe, const std::vector<uint64_t>& th2);
+  int second_stage();
+  int deliver();
+  int pass(int q0_, int nq_);
+};
+
+int KnnFloatSearch::reserve() {
+  if (int rc = slot->d_work.reserve(L.size)) return rc;
+  if (int rc = slot->h_out.reserve(L.oh_ov + 64)) return rc;
+  if (int rc = slot->h_aux.reserve(L.o_th)) return rc;
+  wb = (char*)slot->d_work.p;
+  ho = (char*)slot->h_out.p;
+  hs = (char*)slot->h_aux.p;
   return NRTGPU_OK;
 }
 
-static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
-                    int32_t field_id, int32_t sim, const float* queries, int32_t n_queries, int32_t dim,
-                    int32_t k, float boost, bool knn_request, int32_t filter_mask, float min_score, nrtgpu_topdocs* out,
-                    char* ext_keys = nullptr, char* ext_cnts = nullptr, char* ext_hits = nullptr, const KnnPerQuery* pq = nullptr) {
-  forget_foreign_hip_error();
-  // pq: the queries are knn requests with a k, boost, filter and threshold EACH (nrtgpu_knn_search_requests); `k` is the largest
-  // of theirs, filter_mask / min_score / boost are not read.  The device differs in two inputs only: a table of accept sets per
-  // (leaf, query) in place of the leaf's one, and the thresholds -- an array for every caller -- hold the queries' own.
-  // ext_*: device-resident results instead of `out` (the multi-GPU path): per query k_stride sorted keys, its count, and the live
-  // vectors of these leaves as the hit total -- the layout the exchange stage takes
-  if (!ctx || !queries || (!out && !ext_keys) || (n_segs > 0 && !segs)) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
-  if (int rc = knn_check_scalars(n_queries <= 0, k, dim, sim)) return rc;
-  NRT_CHECK_DEADLINE("before the vector search started");
-  HIP_TRY(hipSetDevice(ctx->device));
-  for (int si = 0; si < n_segs; ++si)
-    if (!segs[si]) return fail(NRTGPU_ERR_STATE, "segment %d missing or not sealed", si);
-  SegReadLocks content(segs, n_segs);  // liveDocs / masks stay as they are until the kernels have finished
-  for (int si = 0; si < n_segs; ++si)
-    if (!segs[si] || !segs[si]->sealed) return fail(NRTGPU_ERR_STATE, "segment %d missing or not sealed", si);
-  // from here on `dim` is the RESIDENT dimension (a multiple of 16) and the queries are padded like the rows
-  PaddedQueries padded;
-  if (int rc = pad_query_vectors(segs, n_segs, field_id, queries, n_queries, dim, &padded)) return rc;
-  queries = padded.p;
-  dim = padded.dim;
-  if (knn_request && filter_mask != 0 && !pq) {   // a selective filter: score only the rows it accepts (vectors_gather.cpp) -- no sketch is built or read
-    const KnnGatherCall call{false, field_id, sim, k, filter_mask, dim, boost, min_score, queries, nullptr, n_queries, kKnnCap};
-    bool gather = false;
-    int64_t estimate = 0;
-    if (int rc = knn_gather_route(ctx, segs, n_segs, call, &gather, &estimate)) return rc;
-    if (gather) return knn_gather_run(ctx, segs, doc_bases, n_segs, call, estimate, out);
-  }
-  for (int si = 0; si < n_segs; ++si)   // the fp16 sketches this search nominates from: built on a field's first exact search
-    if (int rc = ensure_vector_sketch(segs[si], field_id)) return rc;
-  const uint32_t k_stride = round_up((uint32_t)k, 16);
-  // The matrix-core pass NOMINATES: it keeps the k_int best rows by its estimate of the score (an fp32 fma chain in the
-  // MFMA's order, |q|^2 + |v|^2 - 2 q.v for EUCLIDEAN).  The answer is the top k of the nominations rescored in the
-  // oracle's order (knn_score_seq), certified against the rows left outside (knn.hip: knn_select_kernel<true>).
-  const uint32_t k_int = std::min<uint32_t>((uint32_t)NRTGPU_MAX_K, (uint32_t)k + std::max<uint32_t>(32u, (uint32_t)k / 2u));
-  const uint32_t ki_stride = round_up(k_int, 16);
-  Slot* slot = nullptr;
-  acquire_slot(ctx, &slot);
-  SlotGuard guard{ctx, slot};
-  KnnRun run{ctx, slot};   // (the turns on the device and what they order: runtime_internal.h)
-  hipStream_t st = slot->stream;
-  Carver wc;
-  const size_t o_q = wc.take((size_t)kKnnMaxQ * dim * 4), o_qn = wc.take(kKnnMaxQ * 4), o_eb = wc.take(kKnnMaxQ * 4);
-  const size_t o_eb16 = wc.take(kKnnMaxQ * 4), o_qs = wc.take(kKnnMaxQ * 4);
-  const size_t o_segs = wc.take((size_t)std::max(n_segs, 1) * sizeof(DVecSeg));
-  const size_t o_leaves = wc.take((size_t)std::max(n_segs, 1) * sizeof(DKnnLeaf));   // the sketch kernel's leaf table (plan.h)
-  const size_t o_ms = wc.take(kKnnMaxQ * 4);   // the queries' thresholds on the unboosted score (0: none)
-  const size_t o_acc = wc.take(pq ? (size_t)std::max(n_segs, 1) * kKnnAcceptCols * sizeof(uint64_t*) : 8);   // pq: the accept table (plan.h)
-  const size_t o_th = wc.take(kKnnMaxQ * 8);
-  const size_t o_tk = wc.take((size_t)kKnnMaxQ * ki_stride * 8), o_tc = wc.take(kKnnMaxQ * 4);
-  const size_t o_cc = wc.take(kKnnMaxQ * 4), o_xk = wc.take((size_t)kKnnMaxQ * k_stride * 8);
-  const size_t o_xc = wc.take(kKnnMaxQ * 4), o_cert = wc.take(kKnnMaxQ * 4), o_ov = wc.take(64);   // (fetched in one copy)
-  const size_t o_p16 = wc.take(160 * 1024);   // the panel in fp16, the sketch kernel's operand order (knn_panel_fp16_kernel)
-  const size_t o_cd = wc.take((size_t)kKnnMaxQ * kKnnCap * 8);
-  if (int rc = slot->d_work.reserve(wc.off)) return rc;
-  const size_t oh_cnt = (size_t)kKnnMaxQ * k_stride * 8, oh_cert = oh_cnt + (o_cert - o_xc), oh_ov = oh_cnt + (o_ov - o_xc);
-  if (int rc = slot->h_out.reserve(oh_ov + 64)) return rc;
-  // the panel's inputs are staged in pinned memory laid out like the workspace's head [o_q, o_th): two copies per panel, no sync
-  if (int rc = slot->h_aux.reserve(o_th)) return rc;
-  char* wb = (char*)slot->d_work.p;
-  char* ho = (char*)slot->h_out.p;
-  char* hs = (char*)slot->h_aux.p;
-  float *qn = (float*)(hs + o_qn), *eb = (float*)(hs + o_eb), *eb16 = (float*)(hs + o_eb16), *qsc = (float*)(hs + o_qs);
-  float* ms = (float*)(hs + o_ms);
-  const uint64_t** hacc = (const uint64_t**)(hs + o_acc);
-  const uint64_t* const* d_acc = pq ? (const uint64_t* const*)(wb + o_acc) : nullptr;
-  std::vector<int32_t> kleaf_seg, kleaf_of_seg((size_t)std::max(n_segs, 1), -1);   // the sketch kernel's leaves <-> the call's
-  // the leaves' vector matrices, for docid -> row on the device (the rescoring reads rows by docid)
-  (void)stage_rescore_inputs(segs, doc_bases, n_segs, field_id, false, sim, nullptr, 0, dim, hs + o_segs, nullptr, nullptr);
-  double nv_max = 0.0, nv_min = INFINITY, rows_unit = 0.0;   // rows_unit: the largest 1 / scale of the leaves' sketches
-  bool all_sketched = true, any_vectors = false;
-  for (int si = 0; si < n_segs; ++si) {
-    auto fit = segs[si]->fields.find(field_id);
-    if (fit == segs[si]->fields.end() || !fit->second.d_vectors) continue;
-    nv_max = std::max(nv_max, (double)fit->second.vnorm2_max);
-    if (fit->second.n_vec > 0) {
-      if (!fit->second.d_sketch) all_sketched = false;
-      any_vectors = true;
-      if (fit->second.vnorm2_min > 0.f) nv_min = std::min(nv_min, (double)fit->second.vnorm2_min);
-      rows_unit = std::max(rows_unit, 1.0 / (double)fit->second.sketch_scale);
-    }
-  }
-  // the sketch kernel's view of the same leaves: ONE launch walks them all (tiles of 16 rows numbered through the leaves)
-  DKnnLeaf* hleaves = (DKnnLeaf*)(hs + o_leaves);
-  int32_t n_kleaves = 0;
-  int64_t total_tiles = 0, total_rows = 0, live_vectors = 0;
-  for (int si = 0; si < n_segs; ++si) {
-    auto fit = segs[si]->fields.find(field_id);
-    if (fit == segs[si]->fields.end() || !fit->second.d_vectors || fit->second.n_vec == 0) continue;
-    const FieldData& f = fit->second;
-    live_vectors += live_vector_count(segs[si], f);   // (deleted docs are masked inside the kernel and are no hits)
-    const uint64_t* accept = segs[si]->d_live;        // (vectors are not re-coded for liveDocs: always the mask)
-    if (knn_request && filter_mask != 0 && !pq)
-      if (int rc = accept_set_of(segs[si], filter_mask, 0, &accept)) return rc;
-    kleaf_of_seg[(size_t)si] = n_kleaves;
-    kleaf_seg.push_back(si);
-    DKnnLeaf l{};
-    l.sketch = f.d_sketch;
-    l.vnorm2 = f.d_vnorm2;
-    l.ord_to_doc = f.d_ord_to_doc;
-    l.accept = accept;
-    l.accept_of = d_acc ? d_acc + (size_t)n_kleaves * kKnnAcceptCols : nullptr;
-    l.tile_begin = total_tiles;
-    l.n_rows = f.n_vec;
-    l.doc_base = doc_bases ? doc_bases[si] : 0;
-    l.inv_rows_scale = 1.0f / f.sketch_scale;
-    hleaves[n_kleaves++] = l;
-    total_tiles += ((int64_t)f.n_vec + 15) >> 4;
-    total_rows += f.n_vec;
-  }
-  // |estimate - result| <= E, the e_abs of plan.h's knn_result_upper / knn_estimate_lower: host_math.h states the bounds
-  // (knn_bound32 for an fp32 estimate in the MFMA's order, knn_bound16 for the fp16 sketch's) and DESIGN §4.5 derives the constants.
-  const float score_boost = knn_request ? 1.0f : boost;
-  const float erel = hostmath::knn_e_rel();
-  auto bound_of = [&](double nq) { return hostmath::knn_bound32(sim, dim, nq, nv_max, (double)score_boost); };
+// The leaf tables (the rescoring kernel's and the sketch kernel's view of the same leaves: ONE launch walks them all, tiles of 16
+// rows numbered through the leaves) and what the bounds want of the rows.
+int KnnFloatSearch::stage_leaves(int pass_q) {
+  (void)stage_rescore_inputs(call.segs, call.doc_bases, n_segs, call.field_id, false, sim, nullptr, 0, dim, hs + L.o_segs, nullptr, nullptr);
+  DKnnLeaf* hleaves = (DKnnLeaf*)(hs + L.o_leaves);
+  bool all_sketched = true;
+  if (int rc = knn_walk_leaves(call, call.shared_mask(), [&](const KnnLeaf& at) -> int {
+        const FieldData& f = *at.f;
+        nv_max = std::max(nv_max, (double)f.vnorm2_max);
+        if (!f.d_sketch) all_sketched = false;
+        if (f.vnorm2_min > 0.f) nv_min = std::min(nv_min, (double)f.vnorm2_min);
+        rows_unit = std::max(rows_unit, 1.0 / (double)f.sketch_scale);
+        DKnnLeaf l{};
+        l.sketch = f.d_sketch;
+        l.vnorm2 = f.d_vnorm2;
+        l.ord_to_doc = f.d_ord_to_doc;
+        l.accept = at.accept;
+        l.accept_of = table ? d_acc() + (size_t)at.index * kKnnAcceptCols : nullptr;
+        l.tile_begin = at.tile_begin;
+        l.n_rows = f.n_vec;
+        l.doc_base = at.doc_base;
+        l.inv_rows_scale = 1.0f / f.sketch_scale;
+        hleaves[n_kleaves++] = l;
+        live_vectors += at.live;
+        total_tiles = at.tile_begin + (((int64_t)f.n_vec + 15) >> 4);
+        total_rows = at.row_begin + f.n_vec;
+        return NRTGPU_OK;
+      }))
+    return rc;
   // (the query panel in fp16 and at least a small nomination queue behind it must fit the CU's 160 KB of LDS)
-  const bool sketch_ok = all_sketched && any_vectors && std::isfinite(nv_max) &&
-                         knn_sketch_fits(dim, std::min(n_queries, dim > 1280 ? 16 : kKnnMaxQ));
-  auto bound16_of = [&](double nq, double q_l1, double q_unit) {
-    return hostmath::knn_bound16(sim, dim, nq, q_l1, q_unit, nv_max, nv_min, rows_unit, (double)score_boost);
-  };
-  // Rows are scored in rounds with a selection in between (theta tightens from round to round).  The first round of
-  // a panel gives every row a slot of the candidate list; later rounds only append rows that beat theta, so they can
-  // be long: with rows in no particular order a round that multiplies the rows seen by 16 appends about
-  // k * ln 16 candidates.  Rows ordered by rising similarity could overflow the list (every row beats theta): the
-  // select kernel flags that and the panel is redone with rounds no longer than the list (`safe`).
-  // 160 KB of LDS hold two 16-query panels up to 1280 dimensions; beyond that one panel (16 queries per pass) up to 2048
-  const int pass_q = dim > 1280 ? 16 : kKnnMaxQ;
-  for (int q0 = 0; q0 < n_queries; q0 += pass_q) {
-    const int nq = std::min(pass_q, n_queries - q0);
-    if (deadline_passed(g_deadline_ns)) {   // between two passes over the rows: nothing of the next one has been launched
-      (void)hipStreamSynchronize(st);
-      return fail(NRTGPU_ERR_TIMEOUT, "deadline passed between two passes over the rows (%d of %d queries answered)", q0, n_queries);
-    }
-    // nominate from the sketch unless it failed to certify lately for this similarity (then: a few panels straight from fp32)
-    bool panel_sketch = sketch_ok;
-    if (panel_sketch && ctx->knn_sketch_skip[sim].load(std::memory_order_relaxed) > 0) {
-      ctx->knn_sketch_skip[sim].fetch_sub(1, std::memory_order_relaxed);
-      panel_sketch = false;
-    }
-    // squareMagnitude (fp32, in element order), the largest |element| and the 1-norm of every query: each sum is a chain of
-    // dependent additions, so eight queries are walked side by side -- eight independent chains, every query's own order untouched
-    // (0.11 ms -> 0.035 ms per 64-query panel of 768 dimensions: a pass's staging is host time no kernel runs under for one caller)
-    float q_max_of[kKnnMaxQ];
-    double q_l1_of[kKnnMaxQ];
-    for (int qb = 0; qb < nq; qb += 8) {
-      const int nb = std::min(8, nq - qb);
-      float s2[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, mx[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      double l1[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-      const float* qv0 = queries + (size_t)(q0 + qb) * dim;
-      {
-#pragma clang fp contract(off)   // (x * x rounded, then added: never one fused operation, whatever the build's flags)
-        auto walk = [&](const int n) {
-          for (int d = 0; d < dim; ++d)
-            for (int j = 0; j < n; ++j) {
-              const float x = qv0[(size_t)j * dim + d];
-              const float p2 = x * x;
-              s2[j] = s2[j] + p2;
-              mx[j] = std::max(mx[j], std::fabs(x));
-              l1[j] += std::fabs((double)x);
-            }
-        };
-        if (nb == 8) walk(8);   // (a constant trip count: unrolled, the eight sums in registers)
-        else walk(nb);
-      }
-      for (int j = 0; j < nb; ++j) {
-        qn[(size_t)(qb + j)] = s2[j];
-        q_max_of[qb + j] = mx[j];
-        q_l1_of[qb + j] = l1[j];
-      }
-    }
-    for (int q = 0; q < nq; ++q) {
-      const float s2 = qn[(size_t)q];
-      eb[(size_t)q] = bound_of((double)s2);
-      const float q_max = q_max_of[q];
-      const double q_l1 = q_l1_of[q];
-      // the scaled query's largest |element| is below 2^14; a query too small for such a scale (or not finite) sends the panel
-      // to the fp32 rows
-      const bool q_scaled = hostmath::knn_sketch_scale(q_max, &qsc[(size_t)q]);
-      eb16[(size_t)q] = bound16_of((double)s2, q_l1, 1.0 / (double)qsc[(size_t)q]);
-      if (!q_scaled || !std::isfinite(eb16[(size_t)q])) panel_sketch = false;
-    }
-    for (int q = 0; q < kKnnMaxQ; ++q) ms[q] = q >= nq ? 0.0f : pq ? pq->min_scores[q0 + q] : knn_request ? min_score : 0.0f;
-    if (pq) {   // liveDocs & the query's filter per (leaf, query): each distinct filter of the pass is looked up once per leaf
-      memset(hacc, 0, (size_t)std::max(n_segs, 1) * kKnnAcceptCols * sizeof(uint64_t*));
-      for (int32_t kl = 0; kl < n_kleaves; ++kl) {
-        const nrtgpu_seg* seg = segs[kleaf_seg[(size_t)kl]];
-        for (int q = 0; q < nq; ++q) {
-          const int32_t mask = pq->masks[q0 + q];
-          const uint64_t*& slot_q = hacc[(size_t)kl * kKnnAcceptCols + q];
-          slot_q = seg->d_live;
-          if (mask == 0) continue;
-          int same = -1;
-          for (int p = 0; p < q && same < 0; ++p)
-            if (pq->masks[q0 + p] == mask) same = p;
-          if (same >= 0) slot_q = hacc[(size_t)kl * kKnnAcceptCols + same];
-          else if (int rc = accept_set_of(seg, mask, 0, &slot_q)) return rc;
-        }
-      }
-    }
-    memcpy(hs + o_q, queries + (size_t)q0 * dim, (size_t)nq * dim * 4);
-    HIP_TRY(hipMemcpyAsync(wb + o_q, hs + o_q, (size_t)nq * dim * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(wb + o_qn, hs + o_qn, o_th - o_qn, hipMemcpyHostToDevice, st));   // |q|^2, bounds, scales, leaf table
-    if (int rc = run.take_turn()) return rc;   // (the staging above and its copies are not part of the turn)
-    int64_t total_vec = 0, rows_scored = 0;
-    // One pass over the rows of every leaf.  nominate: the estimates' running top-k_int, theta tightening (knn_select_kernel
-    // <false>); else theta stays what the certification left and every nomination is rescored into the answer (<true>).
-    // (rows of the first round: every row takes a slot of the list and the first selection scans them all)
-    static const int64_t kFirstRound = []() { const long v = dev_env_int("NRTGPU_KNN_FIRST_ROUND", 0); return (int64_t)(v >= 1024 && v <= (1 << 18) ? (v & ~15L) : (1 << 16)); }();
-    int64_t sketch_launches = 0;
-    auto select = [&]() {   // the candidates into the running top-k_int, theta tightened
-      launch_knn_select(st, (uint32_t)nq, (uint64_t*)(wb + o_tk), (uint32_t*)(wb + o_tc), ki_stride, k_int, (const uint64_t*)(wb + o_cd),
-                        (uint32_t*)(wb + o_cc), kKnnCap, (unsigned long long*)(wb + o_th), (uint32_t*)(wb + o_ov));
-    };
-    auto refine = [&](size_t o_list, size_t o_cnt, uint32_t cap, size_t o_bound, int32_t certify) {   // a list rescored into the answer
-      launch_knn_refine_select(st, (uint32_t)nq, (uint64_t*)(wb + o_xk), (uint32_t*)(wb + o_xc), k_stride, (uint32_t)k,
-                               (const uint64_t*)(wb + o_list), (uint32_t*)(wb + o_cnt), cap, (unsigned long long*)(wb + o_th),
-                               (uint32_t*)(wb + o_ov), (const DVecSeg*)(wb + o_segs), n_segs, dim, sim, (const float*)(wb + o_q),
-                               (const float*)(wb + o_qn), score_boost, (const float*)(wb + o_bound), erel, (const float*)(wb + o_ms),
-                               k_int, certify, (uint32_t*)(wb + o_cert));
-    };
-    auto rows_pass = [&](bool nominate, int safe) -> int {   // (the fp32 rows: a launch per leaf and round)
-      int64_t seen = 0, round = kFirstRound;
-      // Nominating, theta tightens fast: after two selections (>= 1M rows seen) a later launch appends about k ln(rows / rows
-      // seen) keys per query, so the remaining launches run back to back (append_only) and ONE selection closes the pass.  A
-      // theta still unknown then (hardly any live row) makes those launches append every live row: the list overflows, the
-      // flag is raised and the panel is redone in bounded rounds with a selection after each.
-      int selections = 0;
-      bool pending = false;
-      total_vec = 0;
-      for (int si = 0; si < n_segs; ++si) {
-        const nrtgpu_seg* seg = segs[si];
-        auto fit = seg->fields.find(field_id);
-        if (fit == seg->fields.end() || !fit->second.d_vectors) continue;
-        const FieldData& f = fit->second;
-        total_vec += live_vector_count(seg, f);   // (deleted docs are masked inside the kernel and are no hits)
-        const uint64_t* accept = seg->d_live;  // (vectors are not re-coded for liveDocs: always the mask)
-        if (knn_request && filter_mask != 0 && !pq)
-          if (int rc = accept_set_of(seg, filter_mask, 0, &accept)) return rc;
-        const uint64_t* const* leaf_acc = d_acc && kleaf_of_seg[(size_t)si] >= 0 ? d_acc + (size_t)kleaf_of_seg[(size_t)si] * kKnnAcceptCols : nullptr;
+  sketch_ok = all_sketched && n_kleaves > 0 && std::isfinite(nv_max) && knn_sketch_fits(dim, std::min(call.n_queries, pass_q));
+  return NRTGPU_OK;
+}
+
+// |estimate - result| <= E, the e_abs of plan.h's knn_result_upper / knn_estimate_lower, and the scale of the fp16 panel, per query
+// of the pass: host_math.h states the bounds (knn_bound32 for an fp32 estimate in the MFMA's order, knn_bound16 for the fp16
+// sketch's) and DESIGN §4.5 derives the constants.
+void KnnFloatSearch::stage_bounds() {
+  const float* qn = staged(L.o_qn);
+  float *eb = staged(L.o_eb), *eb16 = staged(L.o_eb16), *qsc = staged(L.o_qs);
+  for (int q = 0; q < nq; ++q) {
+    eb[q] = hostmath::knn_bound32(sim, dim, (double)qn[q], nv_max, (double)score_boost);
+    // the scaled query's largest |element| is below 2^14; a query too small for such a scale (or not finite) sends the panel
+    // to the fp32 rows
+    const bool q_scaled = hostmath::knn_sketch_scale(q_max_of[q], &qsc[q]);
+    eb16[q] = hostmath::knn_bound16(sim, dim, (double)qn[q], q_l1_of[q], 1.0 / (double)qsc[q], nv_max, nv_min, rows_unit, (double)score_boost);
+    if (!q_scaled || !std::isfinite(eb16[q])) panel_sketch = false;
+  }
+}
+
+// The pass's inputs into the pinned head and from there to the device.
+int KnnFloatSearch::stage_pass() {
+  // nominate from the sketch unless it failed to certify lately for this similarity (then: a few panels straight from fp32)
+  panel_sketch = sketch_ok;
+  if (panel_sketch && ctx->knn_sketch_skip[sim].load(std::memory_order_relaxed) > 0) {
+    ctx->knn_sketch_skip[sim].fetch_sub(1, std::memory_order_relaxed);
+    panel_sketch = false;
+  }
+  const float* queries = (const float*)call.queries + (size_t)q0 * dim;
+  knn_query_stats(queries, nq, dim, staged(L.o_qn), q_max_of, q_l1_of);
+  stage_bounds();
+  float* ms = staged(L.o_ms);
+  for (int q = 0; q < kKnnMaxQ; ++q) ms[q] = q < nq ? call.ask.min_score(q0 + q) : 0.0f;
+  if (table)   // liveDocs & the member's filter per (leaf, member)
+    if (int rc = knn_stage_accept_table(call, q0, nq, (const uint64_t**)(hs + L.o_acc))) return rc;
+  memcpy(hs + L.o_q, queries, (size_t)nq * dim * 4);
+  HIP_TRY(hipMemcpyAsync(wb + L.o_q, hs + L.o_q, (size_t)nq * dim * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(wb + L.o_qn, hs + L.o_qn, L.o_th - L.o_qn, hipMemcpyHostToDevice, st));   // |q|^2, bounds, scales, leaf table
+  return NRTGPU_OK;
+}
+
+void KnnFloatSearch::select() {   // the candidates into the running top-k_int, theta tightened
+  launch_knn_select(st, (uint32_t)nq, (uint64_t*)(wb + L.o_tk), (uint32_t*)(wb + L.o_tc), L.ki_stride, L.k_int, (const uint64_t*)(wb + L.o_cd),
+                    (uint32_t*)(wb + L.o_cc), kKnnCap, (unsigned long long*)(wb + L.o_th), (uint32_t*)(wb + L.o_ov));
+}
+void KnnFloatSearch::refine(size_t o_list, size_t o_cnt, uint32_t cap, size_t o_bound, int32_t certify) {   // a list rescored into the answer
+  launch_knn_refine_select(st, (uint32_t)nq, (uint64_t*)(wb + L.o_xk), (uint32_t*)(wb + L.o_xc), L.k_stride, (uint32_t)k,
+                           (const uint64_t*)(wb + o_list), (uint32_t*)(wb + o_cnt), cap, (unsigned long long*)(wb + L.o_th),
+                           (uint32_t*)(wb + L.o_ov), (const DVecSeg*)(wb + L.o_segs), n_segs, dim, sim, (const float*)(wb + L.o_q),
+                           (const float*)(wb + L.o_qn), score_boost, (const float*)(wb + o_bound), erel, (const float*)(wb + L.o_ms),
+                           L.k_int, certify, (uint32_t*)(wb + L.o_cert));
+}
+
+// Rows are scored in rounds with a selection in between (theta tightens from round to round).  The first round of
+// a panel gives every row a slot of the candidate list; later rounds only append rows that beat theta, so they can
+// be long: with rows in no particular order a round that multiplies the rows seen by 16 appends about
+// k * ln 16 candidates.  Rows ordered by rising similarity could overflow the list (every row beats theta): the
+// select kernel flags that and the panel is redone with rounds no longer than the list (`safe`).
+// (rows of the first round: every row takes a slot of the list and the first selection scans them all)
+static const int64_t kKnnFirstRound = []() { const long v = dev_env_int("NRTGPU_KNN_FIRST_ROUND", 0); return (int64_t)(v >= 1024 && v <= (1 << 18) ? (v & ~15L) : (1 << 16)); }();
+
+// One pass over the fp32 rows of every leaf, a launch per leaf and round.  nominate: the estimates' running top-k_int, theta
+// tightening (knn_select_kernel<false>); else theta stays what the certification left and every nomination is rescored into the
+// answer (<true>).
+int KnnFloatSearch::rows_pass(bool nominate, int safe) {
+  int64_t seen = 0, round = kKnnFirstRound;
+  // Nominating, theta tightens fast: after two selections (>= 1M rows seen) a later launch appends about k ln(rows / rows
+  // seen) keys per query, so the remaining launches run back to back (append_only) and ONE selection closes the pass.  A
+  // theta still unknown then (hardly any live row) makes those launches append every live row: the list overflows, the
+  // flag is raised and the panel is redone in bounded rounds with a selection after each.
+  int selections = 0;
+  bool pending = false;
+  total_vec = 0;
+  if (int rc = knn_walk_leaves(call, call.shared_mask(), [&](const KnnLeaf& at) -> int {
+        const FieldData& f = *at.f;
+        total_vec += at.live;
+        const uint64_t* const* leaf_acc = table ? d_acc() + (size_t)at.index * kKnnAcceptCols : nullptr;
         // rounds never exceed the candidate capacity, so a list cannot overflow; theta tightens between rounds
         int64_t r = 0;
-        if (seen == 0) round = kFirstRound;
+        if (seen == 0) round = kKnnFirstRound;
         while (r < f.n_vec) {
           const int64_t rb = r;
           int64_t len = (safe || (nominate && seen == 0)) ? std::min<int64_t>(round, kKnnCap) : round;
@@ -404,9 +456,9 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
           if (nq > 32) blocks = std::max(16u, std::min((uint32_t)std::max(ctx->n_cus, 16), 2u * blocks) / 16u * 16u);   // paired workgroups
           const bool defer = nominate && !safe && selections >= 2;
           if (int rc = run.timed_launch("knn_score", [&]() {
-                return launch_knn_score(st, blocks, f.d_vectors, f.d_vnorm2, f.d_ord_to_doc, accept, dim, r, re, doc_bases ? doc_bases[si] : 0,
-                                        (const float*)(wb + o_q), (const float*)(wb + o_qn), nq, sim, score_boost,
-                                        (const unsigned long long*)(wb + o_th), (uint64_t*)(wb + o_cd), (uint32_t*)(wb + o_cc), kKnnCap,
+                return launch_knn_score(st, blocks, f.d_vectors, f.d_vnorm2, f.d_ord_to_doc, at.accept, dim, r, re, at.doc_base,
+                                        (const float*)(wb + L.o_q), (const float*)(wb + L.o_qn), nq, sim, score_boost,
+                                        (const unsigned long long*)(wb + L.o_th), (uint64_t*)(wb + L.o_cd), (uint32_t*)(wb + L.o_cc), kKnnCap,
                                         defer ? 1 : 0, leaf_acc);
               }))
             return rc;
@@ -416,137 +468,196 @@ static int knn_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_
             select();
             ++selections;
           } else
-            refine(o_cd, o_cc, kKnnCap, o_eb, 0);
+            refine(L.o_cd, L.o_cc, kKnnCap, L.o_eb, 0);
           r = re;
           seen += re - rb;
           round = safe ? std::min<int64_t>(round * 4, kKnnCap) : std::min<int64_t>(seen * 15, (int64_t)1 << 40);
         }
-      }
-      if (pending) select();
-      rows_scored += seen;
-      return NRTGPU_OK;
-    };
-    // The same from the fp16 sketch: a round is a range of the leaves' tiles, ONE launch whatever the number of leaves it crosses.
-    auto sketch_pass = [&](int safe, bool nominate) -> int {   // nominate = false: theta is fixed, every nomination is rescored into the answer
-      total_vec = live_vectors;
-      auto launch = [&](int64_t t, int64_t te, uint32_t blocks, int32_t append_only) -> int {
-        if (int rc = run.timed_launch("knn_sketch", [&]() {
-              return launch_knn_sketch(st, blocks, (const DKnnLeaf*)(wb + o_leaves), n_kleaves, dim, t, te, (const void*)(wb + o_p16),
-                                       (const float*)(wb + o_qn), (const float*)(wb + o_qs), nq, sim, score_boost,
-                                       (const unsigned long long*)(wb + o_th), (uint64_t*)(wb + o_cd), (uint32_t*)(wb + o_cc), kKnnCap, append_only);
-            }))
-          return rc;
-        ++sketch_launches;
         return NRTGPU_OK;
-      };
-      if (int rc = run.tile_rounds(total_tiles, kFirstRound >> 4, kKnnCap, nominate, safe, launch, [&]() {
-            if (nominate) select();
-            else refine(o_cd, o_cc, kKnnCap, o_eb16, 0);
-          }))
-        return rc;
-      rows_scored += total_rows;
-      return NRTGPU_OK;
-    };
-    auto fetch = [&]() -> int {   // the answer so far + the flags
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(ho, wb + o_xk, (size_t)nq * k_stride * 8, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(ho + oh_cnt, wb + o_xc, o_ov + 4 - o_xc, hipMemcpyDeviceToHost, st));   // counts, flags, overflow: one copy
-      HIP_TRY(hipStreamSynchronize(st));
-      return NRTGPU_OK;
-    };
-    // 1. nominate, rescore the nominations, certify
-    for (int safe = 0;; ++safe) {
-      if (int rc = run.take_turn()) return rc;
-      HIP_TRY(hipMemsetAsync(wb + o_th, 0, o_cd - o_th, st));  // theta, lists, counters
-      if (std::any_of(ms, ms + nq, [](float v) { return v > 0.0f; })) {  // start theta below the lowest key whose RESULT can still reach the query's min_score
-        std::vector<uint64_t> th0((size_t)nq, 0ull);
-        for (int q = 0; q < nq; ++q) {
-          if (!(ms[q] > 0.0f)) continue;
-          const float lo = (float)knn_estimate_lower(sim, (double)ms[q], (double)(panel_sketch ? eb16 : eb)[(size_t)q], (double)erel, 1.0);
-          th0[(size_t)q] = lo > 0.0f ? pack_key(lo, 0xFFFFFFFFu) - 1ull : 0ull;
-        }
-        HIP_TRY(hipMemcpyAsync(wb + o_th, th0.data(), (size_t)nq * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));  // th0 is a stack vector
-      }
-      if (panel_sketch) launch_knn_panel_fp16(st, (const float*)(wb + o_q), (const float*)(wb + o_qs), dim, nq, wb + o_p16);
-      if (int rc = panel_sketch ? sketch_pass(safe, true) : rows_pass(true, safe)) return rc;
-      refine(o_tk, o_tc, ki_stride, panel_sketch ? o_eb16 : o_eb, 1);
-      if (int rc = run.end_turn()) return rc;
-      if (int rc = fetch()) return rc;
-      if (*(const uint32_t*)(ho + oh_ov) == 0u) break;
-      if (safe) return fail(NRTGPU_ERR_HIP, "knn: candidate list overflow in a bounded round");
+      }))
+    return rc;
+  if (pending) select();
+  rows_scored += seen;
+  return NRTGPU_OK;
+}
+
+// The same from the fp16 sketch: a round is a range of the leaves' tiles, ONE launch whatever the number of leaves it crosses.
+// nominate = false: theta is fixed, every nomination is rescored into the answer.
+int KnnFloatSearch::sketch_pass(int safe, bool nominate) {
+  total_vec = live_vectors;
+  auto launch = [&](int64_t t, int64_t te, uint32_t blocks, int32_t append_only) -> int {
+    if (int rc = run.timed_launch("knn_sketch", [&]() {
+          return launch_knn_sketch(st, blocks, (const DKnnLeaf*)(wb + L.o_leaves), n_kleaves, dim, t, te, (const void*)(wb + L.o_p16),
+                                   (const float*)(wb + L.o_qn), (const float*)(wb + L.o_qs), nq, sim, score_boost,
+                                   (const unsigned long long*)(wb + L.o_th), (uint64_t*)(wb + L.o_cd), (uint32_t*)(wb + L.o_cc), kKnnCap, append_only);
+        }))
+      return rc;
+    ++sketch_launches;
+    return NRTGPU_OK;
+  };
+  if (int rc = run.tile_rounds(total_tiles, kKnnFirstRound >> 4, kKnnCap, nominate, safe, launch, [&]() {
+        if (nominate) select();
+        else refine(L.o_cd, L.o_cc, kKnnCap, L.o_eb16, 0);
+      }))
+    return rc;
+  rows_scored += total_rows;
+  return NRTGPU_OK;
+}
+
+int KnnFloatSearch::fetch() {   // the answer so far + the flags
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(ho, wb + L.o_xk, (size_t)nq * L.k_stride * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(ho + L.oh_cnt, wb + L.o_xc, L.o_ov + 4 - L.o_xc, hipMemcpyDeviceToHost, st));   // counts, flags, overflow: one copy
+  HIP_TRY(hipStreamSynchronize(st));
+  return NRTGPU_OK;
+}
+
+// 1. nominate, rescore the nominations, certify
+int KnnFloatSearch::first_stage(int safe) {
+  const float *ms = staged(L.o_ms), *bound = staged(panel_sketch ? L.o_eb16 : L.o_eb);
+  if (int rc = run.take_turn()) return rc;
+  HIP_TRY(hipMemsetAsync(wb + L.o_th, 0, L.o_cd - L.o_th, st));  // theta, lists, counters
+  if (std::any_of(ms, ms + nq, [](float v) { return v > 0.0f; })) {  // start theta below the lowest key whose RESULT can still reach the query's min_score
+    std::vector<uint64_t> th0((size_t)nq, 0ull);
+    for (int q = 0; q < nq; ++q) {
+      if (!(ms[q] > 0.0f)) continue;
+      const float lo = (float)knn_estimate_lower(sim, (double)ms[q], (double)bound[q], (double)erel, 1.0);
+      th0[(size_t)q] = lo > 0.0f ? pack_key(lo, 0xFFFFFFFFu) - 1ull : 0ull;
     }
-    // 2. queries whose answer the nominations do not certify (rows outside the list within the rounding bound of the k-th
-    //    result: near-duplicates, or k at the list's capacity): a second pass nominates every row whose estimate is within
-    //    the bound of the k-th rescored score, and rescores all of them
-    int uncertified = 0;
-    for (int q = 0; q < nq; ++q) uncertified += ((const uint32_t*)(ho + oh_cert))[q] == 0u;
-    // Where: first the sketch again (half the bytes; its bound is wider, so more rows are nominated -- all of them are rescored,
-    // which costs nothing much while they are thousands); if that overflows a list -- the bound reaches down to rows by the
-    // hundred thousand: large norms against small distances -- the fp32 rows with their tight bound, and the next panels of this
-    // similarity go there directly.
-    auto second_theta = [&](const float* bound, std::vector<uint64_t>& th2) {
-      // a row of the answer scores >= the k-th rescored score known so far (or >= min_score while fewer than k are known): the
-      // lowest key its estimate can carry; certified queries nominate nothing (theta = ~0)
-      th2.assign((size_t)nq, ~0ull);
-      const uint64_t* xk = (const uint64_t*)ho;
-      const uint32_t* xc = (const uint32_t*)(ho + oh_cnt);
-      for (int q = 0; q < nq; ++q) {
-        if (((const uint32_t*)(ho + oh_cert))[q] != 0u) continue;
-        const double base = xc[q] >= (uint32_t)k ? (double)key_score(xk[(size_t)q * k_stride + (size_t)k - 1])
-                                                 : (double)ms[q];
-        const float lo = (float)knn_estimate_lower(sim, base, (double)bound[(size_t)q], (double)erel, (double)score_boost);
-        th2[(size_t)q] = lo > 0.0f ? pack_key(lo, 0xFFFFFFFFu) - 1ull : 0ull;
-      }
-    };
-    auto second_pass = [&](bool from_sketch, int safe, const std::vector<uint64_t>& th2) -> int {
-      if (int rc = run.take_turn()) return rc;
-      HIP_TRY(hipMemcpyAsync(wb + o_th, th2.data(), (size_t)nq * 8, hipMemcpyHostToDevice, st));
-      for (int q = 0; q < nq; ++q)   // their answers start over (a nomination found again must not be counted twice)
-        if (((const uint32_t*)(ho + oh_cert))[q] == 0u) HIP_TRY(hipMemsetAsync(wb + o_xc + (size_t)q * 4, 0, 4, st));
-      HIP_TRY(hipMemsetAsync(wb + o_cc, 0, kKnnMaxQ * 4, st));
-      HIP_TRY(hipMemsetAsync(wb + o_ov, 0, 4, st));
-      if (int rc = from_sketch ? sketch_pass(safe, false) : rows_pass(false, safe)) return rc;
-      if (int rc = run.end_turn()) return rc;
-      return fetch();   // (the second pass leaves the flags as they are)
-    };
-    if (uncertified) {
-      std::vector<uint64_t> th2;
-      bool done = false;
-      if (panel_sketch) {
-        const std::vector<uint32_t> cert0((const uint32_t*)(ho + oh_cert), (const uint32_t*)(ho + oh_cert) + nq);
-        const std::vector<uint64_t> xk0((const uint64_t*)ho, (const uint64_t*)ho + (size_t)nq * k_stride);
-        const std::vector<uint32_t> xc0((const uint32_t*)(ho + oh_cnt), (const uint32_t*)(ho + oh_cnt) + nq);
-        second_theta(eb16, th2);
-        if (int rc = second_pass(true, 0, th2)) return rc;
-        done = *(const uint32_t*)(ho + oh_ov) == 0u;
-        if (!done) {   // back to what the first stage left (the flags are untouched on the device; the host's copies are restored)
-          memcpy(ho, xk0.data(), xk0.size() * 8);
-          memcpy(ho + oh_cnt, xc0.data(), xc0.size() * 4);
-          memcpy(ho + oh_cert, cert0.data(), cert0.size() * 4);
-          ctx->knn_sketch_skip[sim].store(16, std::memory_order_relaxed);
-        }
-      }
-      if (!done) {
-        second_theta(eb, th2);
-        for (int safe = 0;; ++safe) {
-          if (int rc = second_pass(false, safe, th2)) return rc;
-          if (*(const uint32_t*)(ho + oh_ov) == 0u) break;
-          if (safe) return fail(NRTGPU_ERR_HIP, "knn: candidate list overflow in a bounded round");
-        }
-      }
+    HIP_TRY(hipMemcpyAsync(wb + L.o_th, th0.data(), (size_t)nq * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));  // th0 is a stack vector
+  }
+  if (panel_sketch) launch_knn_panel_fp16(st, (const float*)(wb + L.o_q), (const float*)(wb + L.o_qs), dim, nq, wb + L.o_p16);
+  if (int rc = panel_sketch ? sketch_pass(safe, true) : rows_pass(true, safe)) return rc;
+  refine(L.o_tk, L.o_tc, L.ki_stride, panel_sketch ? L.o_eb16 : L.o_eb, 1);
+  if (int rc = run.end_turn()) return rc;
+  return fetch();
+}
+
+// a row of the answer scores >= the k-th rescored score known so far (or >= min_score while fewer than k are known): the
+// lowest key its estimate can carry; certified queries nominate nothing (theta = ~0)
+void KnnFloatSearch::second_theta(const float* bound, std::vector<uint64_t>& th2) {
+  th2.assign((size_t)nq, ~0ull);
+  const uint64_t* xk = (const uint64_t*)ho;
+  const uint32_t* xc = (const uint32_t*)(ho + L.oh_cnt);
+  const float* ms = staged(L.o_ms);
+  for (int q = 0; q < nq; ++q) {
+    if (certified()[q] != 0u) continue;
+    const double base = xc[q] >= (uint32_t)k ? (double)key_score(xk[(size_t)q * L.k_stride + (size_t)k - 1]) : (double)ms[q];
+    const float lo = (float)knn_estimate_lower(sim, base, (double)bound[q], (double)erel, (double)score_boost);
+    th2[(size_t)q] = lo > 0.0f ? pack_key(lo, 0xFFFFFFFFu) - 1ull : 0ull;
+  }
+}
+int KnnFloatSearch::second_pass(bool from_sketch, int safe, const std::vector<uint64_t>& th2) {
+  if (int rc = run.take_turn()) return rc;
+  HIP_TRY(hipMemcpyAsync(wb + L.o_th, th2.data(), (size_t)nq * 8, hipMemcpyHostToDevice, st));
+  for (int q = 0; q < nq; ++q)   // their answers start over (a nomination found again must not be counted twice)
+    if (certified()[q] == 0u) HIP_TRY(hipMemsetAsync(wb + L.o_xc + (size_t)q * 4, 0, 4, st));
+  HIP_TRY(hipMemsetAsync(wb + L.o_cc, 0, kKnnMaxQ * 4, st));
+  HIP_TRY(hipMemsetAsync(wb + L.o_ov, 0, 4, st));
+  if (int rc = from_sketch ? sketch_pass(safe, false) : rows_pass(false, safe)) return rc;
+  if (int rc = run.end_turn()) return rc;
+  return fetch();   // (the second pass leaves the flags as they are)
+}
+// 2. queries whose answer the nominations do not certify (rows outside the list within the rounding bound of the k-th
+//    result: near-duplicates, or k at the list's capacity): a second pass nominates every row whose estimate is within
+//    the bound of the k-th rescored score, and rescores all of them.
+// Where: first the sketch again (half the bytes; its bound is wider, so more rows are nominated -- all of them are rescored,
+// which costs nothing much while they are thousands); if that overflows a list -- the bound reaches down to rows by the
+// hundred thousand: large norms against small distances -- the fp32 rows with their tight bound, and the next panels of this
+// similarity go there directly.
+int KnnFloatSearch::second_stage() {
+  std::vector<uint64_t> th2;
+  bool done = false;
+  if (panel_sketch) {
+    const std::vector<uint32_t> cert0(certified(), certified() + nq);
+    const std::vector<uint64_t> xk0((const uint64_t*)ho, (const uint64_t*)ho + (size_t)nq * L.k_stride);
+    const std::vector<uint32_t> xc0((const uint32_t*)(ho + L.oh_cnt), (const uint32_t*)(ho + L.oh_cnt) + nq);
+    second_theta(staged(L.o_eb16), th2);
+    if (int rc = second_pass(true, 0, th2)) return rc;
+    done = *overflow() == 0u;
+    if (!done) {   // back to what the first stage left (the flags are untouched on the device; the host's copies are restored)
+      memcpy(ho, xk0.data(), xk0.size() * 8);
+      memcpy(ho + L.oh_cnt, xc0.data(), xc0.size() * 4);
+      memcpy(ho + L.oh_cert, cert0.data(), cert0.size() * 4);
+      ctx->knn_sketch_skip[sim].store(16, std::memory_order_relaxed);
     }
-    run.add_stats(rows_scored, sketch_launches, uncertified != 0);
-    if (ext_keys) {   // stays in HBM: what nrtgpu_dist_knn_exact exchanges
-      std::vector<uint64_t> tv((size_t)nq, (uint64_t)total_vec);
-      HIP_TRY(hipMemcpyAsync(ext_keys + (size_t)q0 * k_stride * 8, wb + o_xk, (size_t)nq * k_stride * 8, hipMemcpyDeviceToDevice, st));
-      HIP_TRY(hipMemcpyAsync(ext_cnts + (size_t)q0 * 4, wb + o_xc, (size_t)nq * 4, hipMemcpyDeviceToDevice, st));
-      HIP_TRY(hipMemcpyAsync(ext_hits + (size_t)q0 * 8, tv.data(), (size_t)nq * 8, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipStreamSynchronize(st));   // (tv is a stack vector; the workspace is reused by the next panel)
-      continue;
+  }
+  if (done) return NRTGPU_OK;
+  second_theta(staged(L.o_eb), th2);
+  return run.redo_on_overflow(overflow(), "knn: candidate list overflow in a bounded round", [&](int safe) { return second_pass(false, safe, th2); });
+}
+
+int KnnFloatSearch::deliver() {
+  if (!call.ext_keys) {
+    knn_unpack_topdocs((const uint64_t*)ho, (const uint32_t*)(ho + L.oh_cnt), L.k_stride, nq, false, total_vec, call.knn_request, call.ask.from(q0),
+                       &call.out[q0]);
+    return NRTGPU_OK;
+  }
+  // stays in HBM: what nrtgpu_dist_knn_exact exchanges
+  std::vector<uint64_t> tv((size_t)nq, (uint64_t)total_vec);
+  HIP_TRY(hipMemcpyAsync(call.ext_keys + (size_t)q0 * L.k_stride * 8, wb + L.o_xk, (size_t)nq * L.k_stride * 8, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(call.ext_cnts + (size_t)q0 * 4, wb + L.o_xc, (size_t)nq * 4, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(call.ext_hits + (size_t)q0 * 8, tv.data(), (size_t)nq * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));   // (tv is a stack vector; the workspace is reused by the next panel)
+  return NRTGPU_OK;
+}
+
+int KnnFloatSearch::pass(int q0_, int nq_) {
+  q0 = q0_, nq = nq_;
+  total_vec = rows_scored = sketch_launches = 0;
+  if (int rc = stage_pass()) return rc;
+  if (int rc = run.take_turn()) return rc;   // (the staging above and its copies are not part of the turn)
+  if (int rc = run.redo_on_overflow(overflow(), "knn: candidate list overflow in a bounded round", [&](int safe) { return first_stage(safe); })) return rc;
+  int uncertified = 0;
+  for (int q = 0; q < nq; ++q) uncertified += certified()[q] == 0u;
+  if (uncertified)
+    if (int rc = second_stage()) return rc;
+  run.add_stats(rows_scored, sketch_launches, uncertified != 0);
+  return deliver();
+}
+
+int nrtgpu::rt::knn_search(nrtgpu_ctx* ctx, const KnnCall& user) {
+  forget_foreign_hip_error();
+  const nrtgpu_seg* const* segs = user.segs;
+  const int32_t n_segs = user.n_segs, n_queries = user.n_queries;
+  if (!ctx || !user.queries || (!user.out && !user.ext_keys) || (n_segs > 0 && !segs)) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
+  const int32_t k = user.k_max();
+  if (int rc = knn_check_scalars(n_queries <= 0, k, user.dim, user.sim)) return rc;
+  NRT_CHECK_DEADLINE("before the vector search started");
+  HIP_TRY(hipSetDevice(ctx->device));
+  for (int si = 0; si < n_segs; ++si)
+    if (!segs[si]) return fail(NRTGPU_ERR_STATE, "segment %d missing or not sealed", si);
+  SegReadLocks content(segs, n_segs);  // liveDocs / masks stay as they are until the kernels have finished
+  for (int si = 0; si < n_segs; ++si)
+    if (!segs[si] || !segs[si]->sealed) return fail(NRTGPU_ERR_STATE, "segment %d missing or not sealed", si);
+  // from here on the call's `dim` is the RESIDENT dimension (a multiple of 16) and the queries are padded like the rows
+  PaddedQueries padded;
+  if (int rc = pad_query_vectors(segs, n_segs, user.field_id, (const float*)user.queries, n_queries, user.dim, &padded)) return rc;
+  KnnCall call = user;
+  call.queries = padded.p;
+  call.dim = padded.dim;
+  if (call.shared_mask() != 0) {   // a selective filter: score only the rows it accepts (vectors_gather.cpp) -- no sketch is built or read
+    bool gather = false;
+    int64_t estimate = 0;
+    if (int rc = knn_gather_route(ctx, call, &gather, &estimate)) return rc;
+    if (gather) return knn_gather_run(ctx, call, nullptr, estimate);
+  }
+  for (int si = 0; si < n_segs; ++si)   // the fp16 sketches this search nominates from: built on a field's first exact search
+    if (int rc = ensure_vector_sketch(segs[si], call.field_id)) return rc;
+  Slot* slot = nullptr;
+  acquire_slot(ctx, &slot);
+  SlotGuard guard{ctx, slot};
+  KnnFloatSearch s{ctx, call, slot, k, KnnLayout(call.dim, n_segs, k, !call.one_filter())};
+  const int pass_q = kKnnFloat.pass_q(call.dim);
+  if (int rc = s.reserve()) return rc;
+  if (int rc = s.stage_leaves(pass_q)) return rc;
+  for (int q0 = 0; q0 < n_queries; q0 += pass_q) {
+    if (deadline_passed(g_deadline_ns)) {   // between two passes over the rows: nothing of the next one has been launched
+      (void)hipStreamSynchronize(s.st);
+      return fail(NRTGPU_ERR_TIMEOUT, "deadline passed between two passes over the rows (%d of %d queries answered)", q0, n_queries);
     }
-    knn_unpack_topdocs((const uint64_t*)ho, (const uint32_t*)(ho + oh_cnt), k_stride, nq, k, false, total_vec, knn_request, boost, &out[q0],
-                       pq ? pq->ks + q0 : nullptr, pq ? pq->boosts + q0 : nullptr);
+    if (int rc = s.pass(q0, std::min(pass_q, n_queries - q0))) return rc;
   }
   return NRTGPU_OK;
 }
@@ -556,14 +667,18 @@ int nrtgpu::rt::knn_exact_device(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs,
                                  void* d_keys, void* d_counts, void* d_hits) {
   if (!d_keys || !d_counts || !d_hits) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
   if (k_stride != (int32_t)round_up((uint32_t)k, 16)) return fail(NRTGPU_ERR_INVALID_ARG, "k_stride must be numHits rounded up to 16");
-  return knn_impl(ctx, segs, doc_bases, n_segs, field_id, sim, queries, n_queries, dim, k, boost, false, 0, 0.0f, nullptr, (char*)d_keys,
-                  (char*)d_counts, (char*)d_hits);
+  const KnnUniform one{k, 0, boost, 0.0f};
+  KnnCall call{segs, doc_bases, n_segs, field_id, /*bytes*/ false, queries, n_queries, dim, sim, /*knn_request*/ false, one.ask(), /*out*/ nullptr};
+  call.ext_keys = (char*)d_keys, call.ext_cnts = (char*)d_counts, call.ext_hits = (char*)d_hits;
+  return knn_search(ctx, call);
 }
 
+// An ExactVectorQuery per query: one k and one boost for all of them -- a stride-0 view (runtime_internal.h: KnnAsk).
 extern "C" int nrtgpu_knn_exact(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
                                 int32_t field_id, int32_t sim, const float* queries, int32_t n_queries, int32_t dim,
                                 int32_t k, float boost, nrtgpu_topdocs* out) {
-  return knn_impl(ctx, segs, doc_bases, n_segs, field_id, sim, queries, n_queries, dim, k, boost, false, 0, 0.0f, out);
+  const KnnUniform one{k, 0, boost, 0.0f};
+  return knn_search(ctx, KnnCall{segs, doc_bases, n_segs, field_id, /*bytes*/ false, queries, n_queries, dim, sim, /*knn_request*/ false, one.ask(), out});
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -606,11 +721,14 @@ extern "C" int nrtgpu_knn_exact_relation(nrtgpu_ctx* ctx, const nrtgpu_seg* cons
   int32_t base = 0;
   for (int32_t i = 0; i < n_segs; ++i) {
     if (!segs[i] || !segs[i]->sealed) return fail(NRTGPU_ERR_STATE, "segment %d missing or not sealed", i);
-    auto fit = segs[i]->fields.find(field_id);
-    if (fit != segs[i]->fields.end() && (fit->second.d_vectors || fit->second.d_btiles)) live[(size_t)i] = live_vector_count(segs[i], fit->second);
     all[(size_t)i] = {i, segs[i]->max_doc, segs[i]->max_doc - segs[i]->n_deleted, doc_bases ? doc_bases[i] : base};
     base += segs[i]->max_doc;
   }
+  for (const bool bytes : {false, true})   // (a field holds float rows or byte rows)
+    (void)knn_walk_leaves(segs, doc_bases, n_segs, field_id, bytes, -1, [&](const KnnLeaf& at) -> int {
+      live[(size_t)at.si] = at.live;
+      return NRTGPU_OK;
+    });
   const int64_t floor_ = (int64_t)std::max(total_hits_threshold, k);
   if (ctx->slice_max_docs.load() <= 0 || n_segs == 0) {   // the whole search counts as one slice
     int64_t sum = 0;
@@ -709,48 +827,7 @@ static int knn_co_run_panel(Coalescer& co, const std::vector<CoQueued*>& batch, 
   return rc;
 }
 
-// ------------------------------------------------------------------------------------------------
-// The element type of a vector entry.  The request and the coalesced entries over float fields and their twins over byte (int8)
-// fields are ONE code below -- the checks, the passes, the panels -- handed the kind, as the rescorers are handed a RescoreKind
-// (runtime_internal.h); what a kind brings is its search (knn_impl here, knn_bytes_impl in vectors_bytes.cpp), its refusals of the
-// other element type, and the panels that fit its kernel's LDS.
-// ------------------------------------------------------------------------------------------------
-struct KnnKind {
-  bool bytes;         // int8 rows and queries; else fp32
-  size_t elem_size;   // bytes of a query element
-  // queries per pass over the rows (float: knn_impl's, the panels that fit the LDS; byte: four panels of 16 at every dimension)
-  int32_t pass_q(int32_t dim) const { return !bytes && dim > 1280 ? 16 : kKnnMaxQ; }
-  int search(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, int32_t field_id, int32_t sim,
-             const void* queries, int32_t n_queries, int32_t dim, int32_t k, float boost, bool knn_request, int32_t filter_mask, float min_score,
-             nrtgpu_topdocs* out, const KnnPerQuery* pq = nullptr) const {
-    if (bytes)
-      return knn_bytes_impl(ctx, segs, doc_bases, n_segs, field_id, sim, (const int8_t*)queries, n_queries, dim, k, boost, knn_request, filter_mask,
-                            min_score, out, pq);
-    return knn_impl(ctx, segs, doc_bases, n_segs, field_id, sim, (const float*)queries, n_queries, dim, k, boost, knn_request, filter_mask, min_score,
-                    out, nullptr, nullptr, nullptr, pq);
-  }
-};
-static const KnnKind kKnnFloat{false, 4}, kKnnBytes{true, 1};
-
-// What an entry of `kind` asks of the field in leaf si (f: the field there): the kind's element type and the queries' dimension.
-// *has_rows: the leaf holds rows a search of the kind reads.
-static int knn_check_field(const KnnKind& kind, int si, int32_t field_id, const FieldData& f, int32_t dim, bool* has_rows) {
-  *has_rows = false;
-  if (!kind.bytes) {
-    if (f.byte_rows)
-      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d holds byte (int8) vectors: search it with nrtgpu_knn_exact_bytes / nrtgpu_knn_search_bytes",
-                  si, field_id);
-    if (!f.d_vectors) return NRTGPU_OK;
-  } else {
-    if (!f.byte_rows && (f.d_vectors || f.dim > 0))
-      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d holds float (fp32) vectors: search it with nrtgpu_knn_exact / nrtgpu_knn_search", si, field_id);
-    if (!f.byte_rows) return NRTGPU_OK;
-  }
-  if (f.dim_user != dim) return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d has dimension %d, query has %d", si, field_id, f.dim_user, dim);
-  *has_rows = kind.bytes ? (f.d_btiles && f.n_vec > 0) : true;
-  return NRTGPU_OK;
-}
-// What only a byte entry asks of its queries and its boost, in knn_bytes_impl's words: cosine refuses a zero query as the reference
+// What only a byte entry asks of its queries and its boost, in knn_bytes_search's words: cosine refuses a zero query as the reference
 // does (validateVectorForSearch, VectorFieldDef.java:853-861), named like every other bad request.
 static int knn_check_queries(const KnnKind& kind, int32_t sim, const void* queries, int32_t n_queries, int32_t dim) {
   if (!kind.bytes || sim != 0) return NRTGPU_OK;
@@ -769,21 +846,22 @@ static int knn_exact_coalesced(const KnnKind& kind, Coalescer& co, nrtgpu_ctx* c
   if (!ctx || !query || !out || (n_segs > 0 && !segs)) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
   // (what would fail the panel must fail this request alone)
   if (int rc = knn_check_scalars(n_segs < 0, k, dim, sim)) return rc;
-  if (kind.bytes && (!(boost >= 0.0f) || !(boost < INFINITY))) return fail(NRTGPU_ERR_INVALID_ARG, "byte vector search: a finite boost >= 0 expected");
+  if (kind.bytes)
+    if (int rc = knn_check_byte_boost(boost)) return rc;
   if (int rc = knn_check_queries(kind, sim, query, 1, dim)) return rc;
   for (int si = 0; si < n_segs; ++si) {
     if (!segs[si] || !segs[si]->sealed) return fail(NRTGPU_ERR_STATE, "segment %d missing or not sealed", si);
     auto fit = segs[si]->fields.find(field_id);
-    bool has_rows = false;
     if (fit != segs[si]->fields.end())
-      if (int rc = knn_check_field(kind, si, field_id, fit->second, dim, &has_rows)) return rc;
+      if (int rc = knn_check_field(kind.bytes, si, field_id, fit->second, dim, kind.other_type_hint)) return rc;
   }
   NRT_CHECK_DEADLINE("before the request was queued");
   KnnCoRequest me{{}, segs, doc_bases, n_segs, field_id, sim, dim, k, boost, query, kind.elem_size, out};
   std::vector<CoQueued*> batch;
   if (!knn_co_wait(co, me, true, &batch)) return me.rc;
   return knn_co_run_panel(co, batch, me, [&](const void* qs, int32_t kmax, nrtgpu_topdocs* outs) {
-    return kind.search(ctx, segs, doc_bases, n_segs, field_id, sim, qs, (int32_t)batch.size(), dim, kmax, boost, false, 0, 0.0f, outs);
+    const KnnUniform one{kmax, 0, boost, 0.0f};   // (the members' buffers take their own k of the panel's largest: knn_co_run_panel)
+    return kind.search(ctx, KnnCall{segs, doc_bases, n_segs, field_id, kind.bytes, qs, (int32_t)batch.size(), dim, sim, /*knn_request*/ false, one.ask(), outs});
   });
 }
 
@@ -805,7 +883,8 @@ extern "C" int nrtgpu_knn_search(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs,
                                  int32_t k, float boost, int32_t filter_mask, float min_score, nrtgpu_topdocs* out) {
   if (filter_mask < 0 || !(min_score >= 0.0f) || !(boost > 0.0f))
     return fail(NRTGPU_ERR_INVALID_ARG, "knn search: filter_mask >= 0, min_score >= 0 and boost > 0 expected");
-  return knn_impl(ctx, segs, doc_bases, n_segs, field_id, sim, queries, n_queries, dim, k, boost, true, filter_mask, min_score, out);
+  const KnnUniform one{k, filter_mask, boost, min_score};   // one request for every query: a stride-0 view (runtime_internal.h: KnnAsk)
+  return knn_search(ctx, KnnCall{segs, doc_bases, n_segs, field_id, /*bytes*/ false, queries, n_queries, dim, sim, /*knn_request*/ true, one.ask(), out});
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -832,7 +911,7 @@ static int knn_requests_check_leaves(const KnnKind& kind, const nrtgpu_seg* cons
     auto fit = segs[si]->fields.find(field_id);
     if (fit == segs[si]->fields.end()) continue;
     bool has_rows = false;
-    if (int rc = knn_check_field(kind, si, field_id, fit->second, dim, &has_rows)) return rc;
+    if (int rc = knn_check_field(kind.bytes, si, field_id, fit->second, dim, kind.other_type_hint, &has_rows)) return rc;
     if (!has_rows) continue;
     for (int32_t q = 0; masks && q < n_queries; ++q)
       if (masks[q] != 0 && segs[si]->masks.find(masks[q]) == segs[si]->masks.end())
@@ -841,26 +920,27 @@ static int knn_requests_check_leaves(const KnnKind& kind, const nrtgpu_seg* cons
   return NRTGPU_OK;
 }
 
-// The requests are valid (knn_request_check, knn_requests_check_leaves) and none of the arrays is NULL.
-static int knn_requests_run(const KnnKind& kind, nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
-                            int32_t field_id, int32_t sim, const void* queries, int32_t n_queries, int32_t dim, const KnnPerQuery& pq,
-                            nrtgpu_topdocs* out) {
+// The requests are valid (knn_request_check, knn_requests_check_leaves); call.ask: one value per query (stride 1).
+static int knn_requests_run(const KnnKind& kind, nrtgpu_ctx* ctx, KnnCall call) {
+  const KnnAsk all = call.ask;
+  const int32_t n_queries = call.n_queries;
   bool all_equal = true;
   for (int32_t q = 1; q < n_queries && all_equal; ++q)
-    all_equal = pq.ks[q] == pq.ks[0] && pq.boosts[q] == pq.boosts[0] && pq.masks[q] == pq.masks[0] && pq.min_scores[q] == pq.min_scores[0];
-  if (all_equal)   // one filter, one threshold: nrtgpu_knn_search's (nrtgpu_knn_search_bytes') own path, the gather route included
-    return kind.search(ctx, segs, doc_bases, n_segs, field_id, sim, queries, n_queries, dim, pq.ks[0], pq.boosts[0], true, pq.masks[0],
-                       pq.min_scores[0], out);
-  const int32_t pass_q = kind.pass_q(dim);
+    all_equal = all.k(q) == all.k(0) && all.boost(q) == all.boost(0) && all.mask(q) == all.mask(0) && all.min_score(q) == all.min_score(0);
+  if (all_equal) {   // one filter, one threshold: nrtgpu_knn_search's (nrtgpu_knn_search_bytes') own path, the gather route included
+    call.ask.stride = 0;
+    return kind.search(ctx, call);
+  }
+  const int32_t pass_q = kind.pass_q(call.dim);
   for (int32_t q0 = 0; q0 < n_queries; q0 += pass_q) {
-    const int32_t nq = std::min(pass_q, n_queries - q0);
     if (q0 > 0 && deadline_passed(g_deadline_ns))
       return fail(NRTGPU_ERR_TIMEOUT, "deadline passed between two passes over the rows (%d of %d queries answered)", q0, n_queries);
-    const KnnPerQuery pass{pq.ks + q0, pq.boosts + q0, pq.masks + q0, pq.min_scores + q0};
-    const int32_t k_pass = *std::max_element(pass.ks, pass.ks + nq);
-    if (int rc = kind.search(ctx, segs, doc_bases, n_segs, field_id, sim, (const char*)queries + (size_t)q0 * dim * kind.elem_size, nq, dim, k_pass,
-                             1.0f, true, 0, 0.0f, out + q0, &pass))
-      return rc;
+    KnnCall pass = call;   // (a search of its own: its slot, its locks, the largest k of ITS members)
+    pass.queries = (const char*)call.queries + (size_t)q0 * call.dim * kind.elem_size;
+    pass.n_queries = std::min(pass_q, n_queries - q0);
+    pass.ask = all.from(q0);
+    pass.out = call.out + q0;
+    if (int rc = kind.search(ctx, pass)) return rc;
   }
   return NRTGPU_OK;
 }
@@ -882,8 +962,8 @@ static int knn_search_requests(const KnnKind& kind, nrtgpu_ctx* ctx, const nrtgp
   if (!boosts) one.assign((size_t)n_queries, 1.0f);
   if (!min_scores) none_f.assign((size_t)n_queries, 0.0f);
   if (!filter_masks) none_i.assign((size_t)n_queries, 0);
-  const KnnPerQuery pq{ks, boosts ? boosts : one.data(), filter_masks ? filter_masks : none_i.data(), min_scores ? min_scores : none_f.data()};
-  return knn_requests_run(kind, ctx, segs, doc_bases, n_segs, field_id, sim, queries, n_queries, dim, pq, out);
+  const KnnAsk ask{ks, boosts ? boosts : one.data(), filter_masks ? filter_masks : none_i.data(), min_scores ? min_scores : none_f.data(), 1};
+  return knn_requests_run(kind, ctx, KnnCall{segs, doc_bases, n_segs, field_id, kind.bytes, queries, n_queries, dim, sim, /*knn_request*/ true, ask, out});
 }
 
 // nrtgpu_knn_search_coalesced and nrtgpu_knn_search_bytes_coalesced, on the kind's own coalescer.
@@ -910,8 +990,8 @@ static int knn_search_coalesced(const KnnKind& kind, Coalescer& co, nrtgpu_ctx* 
       masks[i] = r->filter_mask;
       mins[i] = r->min_score;
     }
-    const KnnPerQuery pq{ks.data(), boosts.data(), masks.data(), mins.data()};
-    return knn_requests_run(kind, ctx, segs, doc_bases, n_segs, field_id, sim, qs, (int32_t)batch.size(), dim, pq, outs);
+    const KnnAsk ask{ks.data(), boosts.data(), masks.data(), mins.data(), 1};
+    return knn_requests_run(kind, ctx, KnnCall{segs, doc_bases, n_segs, field_id, kind.bytes, qs, (int32_t)batch.size(), dim, sim, /*knn_request*/ true, ask, outs});
   });
 }
 

@@ -1,28 +1,39 @@
 // vectors_bytes.cpp -- exact search over byte (int8) vector fields: ExactByteVectorQuery and the `knn` request path over a byte field.
 //
-// The host side of knn_bytes.hip, beside knn_impl (vectors.cpp) and a fraction of it: the pass over the rows returns RESULTS
+// The host side of knn_bytes.hip, beside knn_search (vectors.cpp) and a fraction of it: the pass over the rows returns RESULTS
 // (integers from the i8 matrix cores, mapped to score bits by plan.h: knn_byte_score), so there are no error bounds, no
 // rescoring, no certificate and no second pass here -- only the rounds that tighten theta and the selection they share with the
-// float search (knn.hip: knn_select_kernel<false>).  Turn-taking, the timed launches, the rounds, the statistics and the unpacking
-// are the float search's own code (runtime_internal.h: KnnRun, knn_unpack_topdocs), as is the rescorers' host path further down.
+// float search (knn.hip: knn_select_kernel<false>).  The call's description, the leaf walk, the accept table, the field check,
+// turn-taking, the timed launches, the rounds, the redo of an overflowed pass, the statistics and the unpacking are the float
+// search's own code (runtime_internal.h: KnnCall, knn_walk_leaves, KnnRun, ...), as is the rescorers' host path further down.
 #include "runtime_internal.h"
 
-static const uint32_t kKnnBytesCap = 1u << 18;   // candidate keys per query and round (2 MiB)
-static const int kKnnBytesMaxQ = 64;             // queries per pass over the rows: four panels of 16
+// nq queries in the matrix instruction's operand order (knn_bytes.hip): [step][panel][lane] x 16 bytes, zeros behind the field's
+// dimension and behind the last query
+static void stage_byte_panel(char* dst, const int8_t* queries, int nq, int32_t dim, int32_t steps, int panels) {
+  memset(dst, 0, (size_t)steps * panels * 1024);
+  for (int q = 0; q < nq; ++q) {
+    const int8_t* src = queries + (size_t)q * dim;
+    const int p = q >> 4, j = q & 15;
+    for (int32_t d0 = 0; d0 < dim; d0 += 16) {
+      const int32_t s = d0 >> 6, kk = (d0 >> 4) & 3;
+      memcpy(dst + (((size_t)s * panels + p) * 64 + (size_t)(kk * 16 + j)) * 16, src + d0, (size_t)std::min(16, dim - d0));
+    }
+  }
+}
 
-int nrtgpu::rt::knn_bytes_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, int32_t field_id,
-                               int32_t sim, const int8_t* queries, int32_t n_queries, int32_t dim, int32_t k, float boost, bool knn_request,
-                               int32_t filter_mask, float min_score, nrtgpu_topdocs* out, const KnnPerQuery* pq) {
+int nrtgpu::rt::knn_bytes_search(nrtgpu_ctx* ctx, const KnnCall& call) {
   forget_foreign_hip_error();
-  // pq: the queries are knn requests with a k, boost, filter and threshold EACH (nrtgpu_knn_search_bytes_requests), as in knn_impl
-  // (vectors.cpp).  The device differs in two inputs: a table of accept sets per (leaf, query) in place of the leaf's one, and the
-  // queries' own thresholds in place of the launch's one (knn_bytes.hip: knn_bytes_requests_kernel).  Scores stay unboosted.
-  if (!ctx || !queries || !out || (n_segs > 0 && !segs)) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
-  if (n_queries <= 0 || k <= 0 || dim <= 0 || sim < 0 || sim > 3 || n_segs < 0) return fail(NRTGPU_ERR_INVALID_ARG, "bad knn arguments");
-  // (hits are kept as keys whose order is the order of NON-NEGATIVE float bits: a negative boost would rank them backwards)
-  if (!(boost >= 0.0f) || !(boost < INFINITY)) return fail(NRTGPU_ERR_INVALID_ARG, "byte vector search: a finite boost >= 0 expected");
-  if (k > NRTGPU_MAX_K) return fail(NRTGPU_ERR_UNSUPPORTED, "k %d > %d", k, NRTGPU_MAX_K);
-  if (dim > 2048) return fail(NRTGPU_ERR_UNSUPPORTED, "vector dimension %d (device path takes <= 2048)", dim);
+  // Members with a filter and a threshold EACH (!call.one_filter()) change two inputs of the device: a table of accept sets per
+  // (leaf, query) in place of the leaf's one, and the queries' own thresholds in place of the launch's one (knn_bytes.hip:
+  // knn_bytes_requests_kernel).  Scores stay unboosted.
+  const nrtgpu_seg* const* segs = call.segs;
+  const int8_t* queries = (const int8_t*)call.queries;
+  const int32_t n_segs = call.n_segs, n_queries = call.n_queries, dim = call.dim, sim = call.sim;
+  if (!ctx || !queries || !call.out || (n_segs > 0 && !segs)) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
+  const int32_t k = call.k_max();
+  // (a request's boost was checked with the request; here: the boost of an ExactByteVectorQuery or of a uniform request)
+  if (int rc = knn_check_scalars(n_queries <= 0 || n_segs < 0, k, dim, sim, &call.ask.boosts[0])) return rc;
   // |q|^2 of every query; cosine refuses a zero query as the reference does (validateVectorForSearch, VectorFieldDef.java:853-861)
   std::vector<int32_t> qn2((size_t)n_queries);
   if (int rc = byte_queries_stage(queries, n_queries, dim, sim, nullptr, qn2.data())) return rc;
@@ -33,39 +44,34 @@ int nrtgpu::rt::knn_bytes_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, c
   SegReadLocks content(segs, n_segs);  // liveDocs / masks stay as they are until the kernels have finished
   for (int si = 0; si < n_segs; ++si) {
     if (!segs[si]->sealed) return fail(NRTGPU_ERR_STATE, "segment %d missing or not sealed", si);
-    auto fit = segs[si]->fields.find(field_id);
-    if (fit == segs[si]->fields.end()) continue;
-    const FieldData& f = fit->second;
-    if (!f.byte_rows && (f.d_vectors || f.dim > 0))
-      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d holds float (fp32) vectors: search it with nrtgpu_knn_exact / nrtgpu_knn_search", si, field_id);
-    if (f.byte_rows && f.dim_user != dim)
-      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d has dimension %d, query has %d", si, field_id, f.dim_user, dim);
+    auto fit = segs[si]->fields.find(call.field_id);
+    if (fit != segs[si]->fields.end())
+      if (int rc = knn_check_field(true, si, call.field_id, fit->second, dim, kHintSearchFloat)) return rc;
   }
-  if (knn_request && filter_mask != 0 && !pq) {   // a selective filter: score only the rows it accepts (vectors_gather.cpp)
-    const KnnGatherCall call{true, field_id, sim, k, filter_mask, dim, boost, min_score, queries, qn2.data(), n_queries, kKnnBytesCap};
+  if (call.shared_mask() != 0) {   // a selective filter: score only the rows it accepts (vectors_gather.cpp)
     bool gather = false;
     int64_t estimate = 0;
-    if (int rc = knn_gather_route(ctx, segs, n_segs, call, &gather, &estimate)) return rc;
-    if (gather) return knn_gather_run(ctx, segs, doc_bases, n_segs, call, estimate, out);
+    if (int rc = knn_gather_route(ctx, call, &gather, &estimate)) return rc;
+    if (gather) return knn_gather_run(ctx, call, qn2.data(), estimate);
   }
+  const bool table = !call.one_filter();
   const uint32_t k_stride = round_up((uint32_t)k, 16);
-  const float score_boost = knn_request ? 1.0f : boost;   // the knn request: min_score tests the unboosted score, the boost comes afterwards
+  const float score_boost = call.score_boost();   // the knn request: min_score tests the unboosted score, the boost comes afterwards
   Slot* slot = nullptr;
   acquire_slot(ctx, &slot);
   SlotGuard guard{ctx, slot};
   KnnRun run{ctx, slot};
   hipStream_t st = slot->stream;
-  const size_t panel_max = knn_bytes_panel_bytes(dim, kKnnBytesMaxQ);
   Carver wc;
   // the head [o_p, o_th) is staged in pinned memory laid out alike: one copy per panel
-  const size_t o_p = wc.take(panel_max), o_qn = wc.take(kKnnBytesMaxQ * 4);
+  const size_t o_p = wc.take(knn_bytes_panel_bytes(dim, kKnnMaxQ)), o_qn = wc.take(kKnnMaxQ * 4);
   const size_t o_leaves = wc.take((size_t)std::max(n_segs, 1) * sizeof(DKnnBytesLeaf));
-  const size_t o_ms = wc.take(pq ? kKnnBytesMaxQ * 4 : 8);   // pq: the queries' thresholds on the unboosted score (0: none)
-  const size_t o_acc = wc.take(pq ? (size_t)std::max(n_segs, 1) * kKnnAcceptCols * sizeof(uint64_t*) : 8);   // pq: the accept table (plan.h)
-  const size_t o_th = wc.take(kKnnBytesMaxQ * 8);
-  const size_t o_tk = wc.take((size_t)kKnnBytesMaxQ * k_stride * 8), o_tc = wc.take(kKnnBytesMaxQ * 4);
-  const size_t o_cc = wc.take(kKnnBytesMaxQ * 4), o_ov = wc.take(64);
-  const size_t o_cd = wc.take((size_t)kKnnBytesMaxQ * kKnnBytesCap * 8);
+  const size_t o_ms = wc.take(table ? kKnnMaxQ * 4 : 8);   // table: the members' thresholds on the unboosted score (0: none)
+  const size_t o_acc = wc.take(table ? (size_t)std::max(n_segs, 1) * kKnnAcceptCols * sizeof(uint64_t*) : 8);   // the accept table (plan.h)
+  const size_t o_th = wc.take(kKnnMaxQ * 8);
+  const size_t o_tk = wc.take((size_t)kKnnMaxQ * k_stride * 8), o_tc = wc.take(kKnnMaxQ * 4);
+  const size_t o_cc = wc.take(kKnnMaxQ * 4), o_ov = wc.take(64);
+  const size_t o_cd = wc.take((size_t)kKnnMaxQ * kKnnCap * 8);
   if (int rc = slot->d_work.reserve(wc.off)) return rc;
   const size_t oh_cnt = o_tc - o_tk, oh_ov = o_ov - o_tk;   // keys, counts and the overflow flag come back in one copy
   if (int rc = slot->h_out.reserve(o_cd - o_tk)) return rc;
@@ -76,113 +82,82 @@ int nrtgpu::rt::knn_bytes_impl(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, c
   // the leaves' tiles of 16 rows, numbered through: ONE launch walks every leaf
   DKnnBytesLeaf* hleaves = (DKnnBytesLeaf*)(hs + o_leaves);
   float* ms = (float*)(hs + o_ms);
-  const uint64_t** hacc = (const uint64_t**)(hs + o_acc);
-  const uint64_t* const* d_acc = pq ? (const uint64_t* const*)(wb + o_acc) : nullptr;
-  std::vector<int32_t> kleaf_seg;   // the kernel's leaves -> the call's
+  const uint64_t* const* d_acc = table ? (const uint64_t* const*)(wb + o_acc) : nullptr;
   int32_t n_kleaves = 0;
   int64_t total_tiles = 0, total_rows = 0, live_vectors = 0;
-  for (int si = 0; si < n_segs; ++si) {
-    auto fit = segs[si]->fields.find(field_id);
-    if (fit == segs[si]->fields.end() || !fit->second.d_btiles || fit->second.n_vec == 0) continue;
-    const FieldData& f = fit->second;
-    live_vectors += live_vector_count(segs[si], f);   // (deleted docs are masked inside the kernel and are no hits)
-    const uint64_t* accept = segs[si]->d_live;
-    if (knn_request && filter_mask != 0 && !pq)
-      if (int rc = accept_set_of(segs[si], filter_mask, 0, &accept)) return rc;
-    kleaf_seg.push_back(si);
-    DKnnBytesLeaf l{};
-    l.tiles = f.d_btiles;
-    l.vnorm2 = f.d_bnorm2;
-    l.ord_to_doc = f.d_ord_to_doc;
-    l.accept = accept;
-    l.accept_of = d_acc ? d_acc + (size_t)n_kleaves * kKnnAcceptCols : nullptr;
-    l.tile_begin = total_tiles;
-    l.n_rows = f.n_vec;
-    l.doc_base = doc_bases ? doc_bases[si] : 0;
-    hleaves[n_kleaves++] = l;
-    total_tiles += ((int64_t)f.n_vec + 15) >> 4;
-    total_rows += f.n_vec;
-  }
+  if (int rc = knn_walk_leaves(call, call.shared_mask(), [&](const KnnLeaf& at) -> int {
+        DKnnBytesLeaf l{};
+        l.tiles = at.f->d_btiles;
+        l.vnorm2 = at.f->d_bnorm2;
+        l.ord_to_doc = at.f->d_ord_to_doc;
+        l.accept = at.accept;
+        l.accept_of = d_acc ? d_acc + (size_t)at.index * kKnnAcceptCols : nullptr;
+        l.tile_begin = at.tile_begin;
+        l.n_rows = at.f->n_vec;
+        l.doc_base = at.doc_base;
+        hleaves[n_kleaves++] = l;
+        live_vectors += at.live;
+        total_tiles = at.tile_begin + (((int64_t)at.f->n_vec + 15) >> 4);
+        total_rows = at.row_begin + at.f->n_vec;
+        return NRTGPU_OK;
+      }))
+    return rc;
   const int32_t steps = knn_bytes_steps(dim);
   static const int64_t kFirstRound = (int64_t)(1 << 16) >> 4;   // tiles of the first round: every row takes a slot of the list
-  for (int q0 = 0; q0 < n_queries; q0 += kKnnBytesMaxQ) {
-    const int nq = std::min(kKnnBytesMaxQ, n_queries - q0);
+  for (int q0 = 0; q0 < n_queries; q0 += kKnnMaxQ) {
+    const int nq = std::min(kKnnMaxQ, n_queries - q0);
     if (deadline_passed(g_deadline_ns)) {   // between two passes over the rows: nothing of the next one has been launched
       (void)hipStreamSynchronize(st);
       return fail(NRTGPU_ERR_TIMEOUT, "deadline passed between two passes over the rows (%d of %d queries answered)", q0, n_queries);
     }
-    // the panel in the matrix instruction's operand order (knn_bytes.hip): [step][panel][lane] x 16 bytes, zeros behind the
-    // field's dimension and behind the last query
     const int panels = nq > 16 ? 4 : 1;
-    const size_t panel_bytes = (size_t)steps * panels * 1024;
-    memset(hs + o_p, 0, panel_bytes);
-    for (int q = 0; q < nq; ++q) {
-      const int8_t* src = queries + (size_t)(q0 + q) * dim;
-      const int p = q >> 4, j = q & 15;
-      for (int32_t d0 = 0; d0 < dim; d0 += 16) {
-        const int32_t s = d0 >> 6, kk = (d0 >> 4) & 3;
-        memcpy(hs + o_p + (((size_t)s * panels + p) * 64 + (size_t)(kk * 16 + j)) * 16, src + d0, (size_t)std::min(16, dim - d0));
-      }
-    }
-    memset(hs + o_qn, 0, kKnnBytesMaxQ * 4);
+    stage_byte_panel(hs + o_p, queries + (size_t)q0 * dim, nq, dim, steps, panels);
+    memset(hs + o_qn, 0, kKnnMaxQ * 4);
     memcpy(hs + o_qn, qn2.data() + q0, (size_t)nq * 4);
-    if (pq) {   // the members' thresholds, and liveDocs & the member's filter per (leaf, member): each distinct filter of the pass is
-                // looked up once per leaf (vectors.cpp: knn_impl does the same for the float kernels)
-      for (int q = 0; q < kKnnBytesMaxQ; ++q) ms[q] = q < nq ? pq->min_scores[q0 + q] : 0.0f;
-      memset(hacc, 0, (size_t)std::max(n_segs, 1) * kKnnAcceptCols * sizeof(uint64_t*));
-      for (int32_t kl = 0; kl < n_kleaves; ++kl) {
-        const nrtgpu_seg* seg = segs[kleaf_seg[(size_t)kl]];
-        for (int q = 0; q < nq; ++q) {
-          const int32_t mask = pq->masks[q0 + q];
-          const uint64_t*& slot_q = hacc[(size_t)kl * kKnnAcceptCols + q];
-          slot_q = seg->d_live;
-          if (mask == 0) continue;
-          int same = -1;
-          for (int p = 0; p < q && same < 0; ++p)
-            if (pq->masks[q0 + p] == mask) same = p;
-          if (same >= 0) slot_q = hacc[(size_t)kl * kKnnAcceptCols + same];
-          else if (int rc = accept_set_of(seg, mask, 0, &slot_q)) return rc;
-        }
-      }
+    if (table) {   // the members' thresholds, and liveDocs & the member's filter per (leaf, member)
+      for (int q = 0; q < kKnnMaxQ; ++q) ms[q] = q < nq ? call.ask.min_score(q0 + q) : 0.0f;
+      if (int rc = knn_stage_accept_table(call, q0, nq, (const uint64_t**)(hs + o_acc))) return rc;
     }
-    HIP_TRY(hipMemcpyAsync(wb + o_p, hs + o_p, panel_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(wb + o_qn, hs + o_qn, o_th - o_qn, hipMemcpyHostToDevice, st));   // |q|^2, leaf table (pq: thresholds, accept table)
+    HIP_TRY(hipMemcpyAsync(wb + o_p, hs + o_p, (size_t)steps * panels * 1024, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(wb + o_qn, hs + o_qn, o_th - o_qn, hipMemcpyHostToDevice, st));   // |q|^2, leaf table (thresholds, accept table)
     // One pass over the rows of every leaf in KnnRun::tile_rounds' rounds, always nominating.  Rows in rising order of similarity
     // could overflow a list: the selection flags that and the panel is redone in rounds no longer than the list (`safe`).
-    for (int safe = 0;; ++safe) {
+    auto pass = [&](int safe) -> int {
       if (int rc = run.take_turn()) return rc;
       HIP_TRY(hipMemsetAsync(wb + o_th, 0, o_cd - o_th, st));  // theta, the running top-k, counters, flag
       auto launch = [&](int64_t t, int64_t te, uint32_t blocks, int32_t append_only) -> int {
         return run.timed_launch("knn_bytes", [&]() {
           return launch_knn_bytes(st, blocks, (const DKnnBytesLeaf*)(wb + o_leaves), n_kleaves, dim, t, te, wb + o_p, (const int32_t*)(wb + o_qn),
-                                  nq, sim, score_boost, knn_request ? min_score : 0.0f, (const unsigned long long*)(wb + o_th),
-                                  (uint64_t*)(wb + o_cd), (uint32_t*)(wb + o_cc), kKnnBytesCap, append_only,
-                                  pq ? (const float*)(wb + o_ms) : nullptr);
+                                  nq, sim, score_boost, table ? 0.0f : call.ask.min_scores[0], (const unsigned long long*)(wb + o_th),
+                                  (uint64_t*)(wb + o_cd), (uint32_t*)(wb + o_cc), kKnnCap, append_only,
+                                  table ? (const float*)(wb + o_ms) : nullptr);
         });
       };
-      if (int rc = run.tile_rounds(total_tiles, kFirstRound, kKnnBytesCap, true, safe, launch, [&]() {
+      if (int rc = run.tile_rounds(total_tiles, kFirstRound, kKnnCap, true, safe, launch, [&]() {
             launch_knn_select(st, (uint32_t)nq, (uint64_t*)(wb + o_tk), (uint32_t*)(wb + o_tc), k_stride, (uint32_t)k, (const uint64_t*)(wb + o_cd),
-                              (uint32_t*)(wb + o_cc), kKnnBytesCap, (unsigned long long*)(wb + o_th), (uint32_t*)(wb + o_ov));
+                              (uint32_t*)(wb + o_cc), kKnnCap, (unsigned long long*)(wb + o_th), (uint32_t*)(wb + o_ov));
           }))
         return rc;
       if (int rc = run.end_turn()) return rc;
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipMemcpyAsync(ho, wb + o_tk, o_ov + 4 - o_tk, hipMemcpyDeviceToHost, st));   // the answer, its counts, the flag
       HIP_TRY(hipStreamSynchronize(st));
-      if (*(const uint32_t*)(ho + oh_ov) == 0u) break;
-      if (safe) return fail(NRTGPU_ERR_HIP, "knn_bytes: candidate list overflow in a bounded round");
-    }
+      return NRTGPU_OK;
+    };
+    if (int rc = run.redo_on_overflow((const uint32_t*)(ho + oh_ov), "knn_bytes: candidate list overflow in a bounded round", pass)) return rc;
     run.add_stats(total_rows, 0, false);
-    knn_unpack_topdocs((const uint64_t*)ho, (const uint32_t*)(ho + oh_cnt), k_stride, nq, k, true, live_vectors, knn_request, boost, &out[q0],
-                       pq ? pq->ks + q0 : nullptr, pq ? pq->boosts + q0 : nullptr);
+    knn_unpack_topdocs((const uint64_t*)ho, (const uint32_t*)(ho + oh_cnt), k_stride, nq, true, live_vectors, call.knn_request, call.ask.from(q0),
+                       &call.out[q0]);
   }
   return NRTGPU_OK;
 }
 
+// An ExactByteVectorQuery per query / one knn request for all of them: a stride-0 view of one value (runtime_internal.h: KnnAsk).
 extern "C" int nrtgpu_knn_exact_bytes(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
                                       int32_t field_id, int32_t sim, const int8_t* queries, int32_t n_queries, int32_t dim, int32_t k,
                                       float boost, nrtgpu_topdocs* out) {
-  return knn_bytes_impl(ctx, segs, doc_bases, n_segs, field_id, sim, queries, n_queries, dim, k, boost, false, 0, 0.0f, out);
+  const KnnUniform one{k, 0, boost, 0.0f};
+  return knn_bytes_search(ctx, KnnCall{segs, doc_bases, n_segs, field_id, /*bytes*/ true, queries, n_queries, dim, sim, /*knn_request*/ false, one.ask(), out});
 }
 
 extern "C" int nrtgpu_knn_search_bytes(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
@@ -190,14 +165,15 @@ extern "C" int nrtgpu_knn_search_bytes(nrtgpu_ctx* ctx, const nrtgpu_seg* const*
                                        float boost, int32_t filter_mask, float min_score, nrtgpu_topdocs* out) {
   if (filter_mask < 0 || !(min_score >= 0.0f) || !(boost > 0.0f))
     return fail(NRTGPU_ERR_INVALID_ARG, "knn search: filter_mask >= 0, min_score >= 0 and boost > 0 expected");
-  return knn_bytes_impl(ctx, segs, doc_bases, n_segs, field_id, sim, queries, n_queries, dim, k, boost, true, filter_mask, min_score, out);
+  const KnnUniform one{k, filter_mask, boost, min_score};
+  return knn_bytes_search(ctx, KnnCall{segs, doc_bases, n_segs, field_id, /*bytes*/ true, queries, n_queries, dim, sim, /*knn_request*/ true, one.ask(), out});
 }
 
 // ---- the rescorers over a byte field: QueryRescore (rescore/QueryRescore.java:40-57) with the field's ExactByteVectorQuery
 // (VectorFieldDef.java:842) in the rescore slot -- nrtgpu_rescore_byte_vectors here, the tail of nrtgpu_search_hybrid_bytes_batch in
 // search.cpp: search_hybrid_impl.  Both run the float rescorers' host code (vectors.cpp: rescore_hits_impl, stage_rescore_inputs);
 // here is what only a byte field asks: the refusals and the queries in piece order ------------------------------------------------
-// What the byte entries ask of their scalars, in knn_bytes_impl's order.
+// What the byte entries ask of their scalars, in knn_bytes_search's order.
 int nrtgpu::rt::byte_rescore_check_args(int32_t sim, int32_t dim, float boost, int32_t window) {
   if (dim <= 0 || sim < 0 || sim > 3 || window <= 0) return fail(NRTGPU_ERR_INVALID_ARG, "bad rescore arguments");
   // (the fused tail keeps hits as keys that order like NON-NEGATIVE float bits; the two-call path refuses the same boosts)
@@ -223,20 +199,6 @@ int nrtgpu::rt::byte_queries_stage(const int8_t* queries, int32_t n, int32_t dim
   }
   return NRTGPU_OK;
 }
-// The field in every leaf: byte rows of the query's dimension, or absent.
-int nrtgpu::rt::byte_rescore_check_leaves(const nrtgpu_seg* const* segs, int32_t n_segs, int32_t field_id, int32_t dim) {
-  for (int si = 0; si < n_segs; ++si) {
-    auto fit = segs[si]->fields.find(field_id);
-    if (fit == segs[si]->fields.end()) continue;
-    const FieldData& f = fit->second;
-    if (!f.byte_rows && (f.d_vectors || f.dim > 0))
-      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d holds float (fp32) vectors: rescore it with nrtgpu_rescore_vectors / nrtgpu_search_hybrid_batch",
-                  si, field_id);
-    if (f.byte_rows && f.dim_user != dim)
-      return fail(NRTGPU_ERR_INVALID_ARG, "segment %d: field %d has dimension %d, query has %d", si, field_id, f.dim_user, dim);
-  }
-  return NRTGPU_OK;
-}
 
 extern "C" int nrtgpu_rescore_byte_vectors(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
                                            int32_t field_id, int32_t sim, const int8_t* query, int32_t dim, float boost,
@@ -256,7 +218,7 @@ extern "C" int nrtgpu_rescore_byte_vectors(nrtgpu_ctx* ctx, const nrtgpu_seg* co
   HIP_TRY(hipSetDevice(ctx->device));
   for (int si = 0; si < n_segs; ++si)
     if (!segs[si]) return fail(NRTGPU_ERR_INVALID_ARG, "segment %d is NULL", si);
-  if (int rc = byte_rescore_check_leaves(segs, n_segs, field_id, dim)) return rc;
+  if (int rc = knn_check_leaves(segs, n_segs, field_id, true, dim, kHintRescoreFloat)) return rc;
   const RescoreKind kind{[](const FieldData& f) -> const void* { return f.d_btiles; }, qpad.data(), qpad.size(),
                          [&](hipStream_t st, const FieldData& f, const void* d_query, const int64_t* d_rows, const float* d_first, int32_t m, float* d_out) {
                            launch_rescore_byte_vectors(st, f.d_btiles, f.d_bnorm2, dim, d_query, qn, sim, boost, d_rows, d_first, m, query_weight,
