@@ -852,6 +852,75 @@ int  nrtgpu_function_score_multi_match_value(const nrtgpu_clause_groups* g, int3
                                              uint32_t matched_functions, float* out_score, int32_t* out_is_hit);
 
 /* ---------------------------------------------------------------------------------------------
+ * A text query beside knn clauses: a SearchRequest with `query` AND `knn`.  The reference resolves every knn query first -- each
+ * becomes a doc-and-score query over its top k -- and ORs those into the main query as further SHOULD clauses of one BooleanQuery
+ * (src/main/java/com/yelp/nrtsearch/server/search/SearchRequestProcessor.java:267-296, KnnUtils.resolveKnnQueryAndBoost).  The
+ * lists are what nrtgpu_knn_search* returned; this entry scores the combined query in a kernel of its own
+ * (csrc/knnclauses.hip: the function-score kernel's structure with a pass over the listed docs; nothing is pruned).
+ * (nrtgpu_search_hybrid_batch is another thing: a rescorer tail that never admits a doc the text did not match.)
+ * Score of a doc [Lucene-recall]; every operation is one IEEE operation:
+ *   knn_sum   the double sum, in list order, of (double)(float)(scores[i] * boost) over the lists that hold the doc
+ *   text      the doc's text clauses; they count only when the doc matches the text query AND lies in the query's accept set
+ *             (liveDocs & FILTER & ~MUST_NOT)
+ *   FLAT      text and lists: (float)(text_double_sum + knn_sum)     text only: what nrtgpu_search_bm25 scores
+ *             lists only: (float)knn_sum
+ *   NESTED    text and lists: (float)((double)(float)text_double_sum + knn_sum); the other two cases as FLAT
+ * Which form: BooleanQuery.rewrite inlines a SHOULD clause that is itself a pure disjunction (all SHOULD,
+ * minimumNumberShouldMatch <= 1) into the outer query, so a single term or a pure SHOULD disjunction is FLAT; a text query with
+ * FILTER / MUST_NOT clauses is no pure disjunction and is NESTED.  text_nested == 0 with any mask set is NRTGPU_ERR_INVALID_ARG.
+ * Hits: a doc is a hit if (the text matches and accepts it) or (it is in a list and live in its leaf).  A listed doc that is not
+ * live is no hit; a listed doc outside the text's accept set is a hit with the lists' score alone.  k, has_after / after_*
+ * (compares FINAL keys), total_hits_threshold, slicing, deadlines, total_hits (exact), the relation (per-slice rule), diagnostics
+ * and statistics: as nrtgpu_search_function_score_batch.  n_lists == 0 is the text query alone.
+ * Refusals, each with a reason in nrtgpu_last_error:
+ *   NRTGPU_ERR_INVALID_ARG  n or n_lists out of range; NULL arrays with n > 0; a boost that is not finite or <= 0; a NaN or
+ *                           infinite score; a doc twice in one list; a docid in no leaf of the call (or doc_bases == NULL with a
+ *                           listed doc); text_nested outside 0..1, or 0 with a mask; whatever nrtgpu_search_bm25_batch refuses of
+ *                           queries[i] with that status
+ *   NRTGPU_ERR_UNSUPPORTED  a clause value <= 0 (the accumulators' 0 means "no match") or one that overflows; the exactness test
+ *                           below fails; MUST clauses; disjunction_max; min_should_match > 1; min_competitive_score != 0; a
+ *                           context with NRTGPU_FLAG_PACKED_POSTINGS or NRTGPU_FLAG_NO_FIXED_POINT; a batch that fails the
+ *                           fixed-point analysis
+ * Exactness test: sums are exact in any order, and the lists must keep that true.  With the clause values x = (float)(score *
+ * boost): lo = min(-fx_E, min over x of floor(log2 x) - 23), hi = ceil(log2(sum of the text weights + sum over the lists of the
+ * list's largest value)); hi - lo <= 53 is required (tiny scores beside BM25 scores are the only realistic trigger).  fx_E: the
+ * largest nrtgpu_fixed_point_scale of the query's clauses that match anything; a query none of whose clauses matches anything is
+ * tested over its lists alone.
+ * Out of scope: the Java shim; the coalesced, device-resident and nrtgpu_dist_* forms; keeping the lists on the device between the
+ * knn pass and this one; MUST / dismax / multi-match text under knn clauses; a function score on top; pruning; a request with
+ * `knn` and no `query` (that is nrtgpu_knn_search*).
+ * --------------------------------------------------------------------------------------------- */
+#define NRTGPU_MAX_KNN_LISTS 8
+typedef struct {            /* one resolved knn clause: what nrtgpu_knn_search* returned for it */
+  const int32_t* docs;      /* global docids (doc_base + leaf doc), any order, no doc twice */
+  const float*   scores;    /* the vector scores */
+  int32_t n;                /* 0..NRTGPU_MAX_K */
+  float   boost;            /* > 0, finite; the clause's value is (float)(scores[i] * boost), one float multiply
+                               (DocAndScoreQuery under a BoostQuery); 1 when scores are already boosted */
+} nrtgpu_doc_scores;        /* 24 bytes */
+typedef struct {
+  const nrtgpu_doc_scores* lists;
+  int32_t n_lists;          /* 0..NRTGPU_MAX_KNN_LISTS */
+  int32_t text_nested;      /* 0: the text clauses are clauses of the outer BooleanQuery (FLAT);
+                               1: the text query is ONE clause whose float score is added (NESTED) */
+} nrtgpu_knn_clauses;       /* 16 bytes */
+/* n_queries text + knn searches over the same leaves in one device pass; knn[i] goes beside queries[i] */
+int  nrtgpu_search_text_knn_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                  const nrtgpu_bm25_query* queries, const nrtgpu_knn_clauses* knn, int32_t n_queries,
+                                  nrtgpu_topdocs* out);
+/* The eligibility test alone: NRTGPU_OK if the search above would run (q, kc) over these leaves, else the status it would return
+ * with the reason in nrtgpu_last_error ("a docid in no leaf of the call" aside: there are no doc_bases here).  No device work. */
+int  nrtgpu_text_knn_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query* q,
+                               const nrtgpu_knn_clauses* kc);
+/* The arithmetic above for one doc, exposed for the tests: needs no device; it is the very function the kernel compiles.
+ * text_matched: the doc matches the text query and lies in its accept set; fixed_sum: its text clauses' sum x 2^fx_E as the
+ * accumulators hold it; knn_sum: 0 = no list holds the doc. */
+int  nrtgpu_text_knn_value(int32_t text_nested, int32_t text_matched, uint64_t fixed_sum, int32_t fx_E, double knn_sum, float* out);
+/* The list checks and the exactness test above for one (q, kc) under the scale fx_E: 1 exact, 0 not, negative: the status the
+ * search would return for the lists (of q only its clauses' weights and its masks are read).  Needs no device. */
+int  nrtgpu_text_knn_exact(const nrtgpu_bm25_query* q, const nrtgpu_knn_clauses* kc, int32_t fx_E);
+
+/* ---------------------------------------------------------------------------------------------
  * Host-side restatements the Java shim would otherwise take from Lucene objects
  * (BM25Similarity.scorer(boost, collectionStats, termStats); SmallFloat; slices()).
  * --------------------------------------------------------------------------------------------- */

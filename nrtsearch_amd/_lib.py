@@ -34,6 +34,7 @@ NRTGPU_MAX_FUNCTIONS = 8
 NRTGPU_MAX_GROUPS = 8
 NRTGPU_GROUPS_SUM_OF_MAX = 0
 NRTGPU_GROUPS_MAX_OF_SUM = 1
+NRTGPU_MAX_KNN_LISTS = 8
 
 # every symbol include/nrtgpu.h declares (tests/test_abi.py checks the header against this list)
 ABI_SYMBOLS = [
@@ -57,6 +58,7 @@ ABI_SYMBOLS = [
     "nrtgpu_search_function_score_batch", "nrtgpu_function_score_supported", "nrtgpu_function_score_value",
     "nrtgpu_search_multi_match_batch", "nrtgpu_multi_match_supported", "nrtgpu_multi_match_value",
     "nrtgpu_search_function_score_multi_match_batch", "nrtgpu_function_score_multi_match_supported", "nrtgpu_function_score_multi_match_value",
+    "nrtgpu_search_text_knn_batch", "nrtgpu_text_knn_supported", "nrtgpu_text_knn_value", "nrtgpu_text_knn_exact",
 ]
 # what include/nrtgpu_dev.h adds: test hooks and measurement helpers of the development library (libnrtgpu_dev.so) only
 DEV_SYMBOLS = [
@@ -103,6 +105,14 @@ class FunctionScore(C.Structure):   # nrtgpu_function_score
 class ClauseGroups(C.Structure):   # nrtgpu_clause_groups
     _fields_ = [("shape", C.c_int32), ("n_groups", C.c_int32), ("group_of_term", C.POINTER(C.c_int32)),
                 ("group_min_should_match", C.POINTER(C.c_int32)), ("tie_breaker", C.c_float), ("group_occur", C.c_int32)]
+
+
+class DocScores(C.Structure):   # nrtgpu_doc_scores
+    _fields_ = [("docs", C.POINTER(C.c_int32)), ("scores", C.POINTER(C.c_float)), ("n", C.c_int32), ("boost", C.c_float)]
+
+
+class KnnClauses(C.Structure):   # nrtgpu_knn_clauses
+    _fields_ = [("lists", C.POINTER(DocScores)), ("n_lists", C.c_int32), ("text_nested", C.c_int32)]
 
 
 class TopDocs(C.Structure):
@@ -217,6 +227,10 @@ def _open(path: str) -> C.CDLL:
                                                                  C.POINTER(TopDocs)]
     L.nrtgpu_function_score_multi_match_supported.argtypes = [vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(ClauseGroups), C.POINTER(FunctionScore)]
     L.nrtgpu_function_score_multi_match_value.argtypes = [C.POINTER(ClauseGroups), i32, vp, i32, vp, C.c_uint32, C.POINTER(FunctionScore), C.c_uint32, vp, vp]
+    L.nrtgpu_search_text_knn_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(KnnClauses), i32, C.POINTER(TopDocs)]
+    L.nrtgpu_text_knn_supported.argtypes = [vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(KnnClauses)]
+    L.nrtgpu_text_knn_value.argtypes = [i32, i32, C.c_uint64, i32, C.c_double, vp]
+    L.nrtgpu_text_knn_exact.argtypes = [C.POINTER(Bm25Query), C.POINTER(KnnClauses), i32]
     L.nrtgpu_rescore_vectors.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, f32, vp, vp, i32, C.c_double, C.c_double, i32,
                                          C.POINTER(TopDocs)]
     L.nrtgpu_search_hybrid_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), i32, i32, i32, vp, i32, f32,

@@ -107,6 +107,17 @@ class FunctionScoreQuery:
     min_excluded: bool = False
 
 
+@dataclasses.dataclass(frozen=True, eq=False)
+class KnnClause:
+    """One resolved knn clause of a request that also carries a `query` (nrtgpu_doc_scores): the global docids and vector scores
+    a knn search returned, ORed into the text query as a SHOULD clause worth (float)(score * boost) per doc
+    (S/search/SearchRequestProcessor.java:267-296).  boost 1.0 when the scores carry the boost already."""
+
+    docs: np.ndarray
+    scores: np.ndarray
+    boost: float = 1.0
+
+
 SCORE_MODES = {"multiply": 0, "sum": 1}                  # nrtgpu_function_score.score_mode
 BOOST_MODES = {"multiply": 0, "sum": 1, "replace": 2}    # ... .boost_mode
 
@@ -733,6 +744,79 @@ class GpuIndexSearcher:
             return False
         _lib.check(rc)
         return False
+
+    def _marshal_knn_clauses(self, knn_clauses: Sequence[Sequence[KnnClause]], m: _Marshalled):
+        """nrtgpu_knn_clauses per query; the form by BooleanQuery.rewrite's rule: a text query with FILTER / MUST_NOT clauses is no
+        pure disjunction and stays ONE clause (NESTED), anything else this route takes is inlined (FLAT)."""
+        kc = (_lib.KnnClauses * len(knn_clauses))()
+        for qi, clauses in enumerate(knn_clauses):
+            lists = (_lib.DocScores * max(len(clauses), 1))()
+            for li, c in enumerate(clauses):
+                docs = np.ascontiguousarray(c.docs, dtype=np.int32).reshape(-1)
+                scores = np.ascontiguousarray(c.scores, dtype=np.float32).reshape(-1)
+                if docs.shape[0] != scores.shape[0]:
+                    raise ValueError(f"query {qi} knn clause {li}: {docs.shape[0]} docs, {scores.shape[0]} scores")
+                m.keep += [docs, scores]
+                lists[li] = _lib.DocScores(docs.ctypes.data_as(C.POINTER(C.c_int32)), scores.ctypes.data_as(C.POINTER(C.c_float)),
+                                           docs.shape[0], float(np.float32(c.boost)))
+            m.keep.append(lists)
+            q = m.queries[qi]
+            kc[qi].lists = lists
+            kc[qi].n_lists = len(clauses)
+            kc[qi].text_nested = int(q.filter_mask != 0 or q.must_not_mask != 0 or q.n_more_filters != 0 or q.n_more_must_not != 0)
+        m.keep.append(kc)
+        return kc
+
+    def search_text_knn_batch(self, queries: Sequence[Query], knn_clauses: Sequence[Sequence[KnnClause]],
+                              managers: Sequence[TopScoreDocCollectorManager]) -> List[TopDocs]:
+        """Requests with `query` AND `knn` (nrtgpu_search_text_knn_batch): knn_clauses[i], the resolved knn lists of request i, are
+        further SHOULD clauses beside queries[i] in one BooleanQuery.  Every hit is scored, total_hits is exact."""
+        n = len(queries)
+        if len(knn_clauses) != n:
+            raise ValueError(f"{len(knn_clauses)} knn clause lists for {n} queries")
+        m = self._marshal(queries, managers)
+        kc = self._marshal_knn_clauses(knn_clauses, m)
+        outs = (_lib.TopDocs * n)()
+        bufs = []
+        for qi, mgr in enumerate(managers):
+            cap = max(int(mgr.num_hits), 1)
+            d = np.zeros(cap, dtype=np.int32)
+            s = np.zeros(cap, dtype=np.float32)
+            bufs.append((d, s))
+            outs[qi].capacity = cap
+            outs[qi].docs = d.ctypes.data_as(C.POINTER(C.c_int32))
+            outs[qi].scores = s.ctypes.data_as(C.POINTER(C.c_float))
+        _lib.check(_lib.load().nrtgpu_search_text_knn_batch(self.ctx._h, self._segs, self._bases, len(self.leaves), m.queries, kc, n, outs))
+        return [TopDocs(bufs[qi][0][: outs[qi].n_hits].copy(), bufs[qi][1][: outs[qi].n_hits].copy(), int(outs[qi].total_hits),
+                        bool(outs[qi].total_hits_is_lower_bound)) for qi in range(n)]
+
+    def text_knn_supported(self, query: Query, knn_clauses: Sequence[KnnClause], manager: TopScoreDocCollectorManager) -> bool:
+        """The eligibility predicate alone (nrtgpu_text_knn_supported)."""
+        m = self._marshal([query], [manager])
+        kc = self._marshal_knn_clauses([knn_clauses], m)
+        rc = _lib.load().nrtgpu_text_knn_supported(self.ctx._h, self._segs, len(self.leaves), m.queries, kc)
+        if rc == _lib.NRTGPU_OK:
+            return True
+        if rc == _lib.NRTGPU_ERR_UNSUPPORTED:
+            return False
+        _lib.check(rc)
+        return False
+
+    def search_with_knn(self, query: Query, manager: TopScoreDocCollectorManager, knn: Sequence[tuple] = ()) -> TopDocs:
+        """The request as a caller writes it: `query` and knn = [(field, similarity, vector, k, boost, accept)], accept a MaskFilter
+        or None.  The knn clauses are resolved first, in shared passes per (field, similarity) (knn_search_requests; the scores come
+        back with the boost applied), and their lists go beside the text query (search_text_knn_batch)."""
+        clauses: List[Optional[KnnClause]] = [None] * len(knn)
+        groups: Dict[Tuple[int, str, int], List[int]] = {}
+        for i, (field, similarity, vector, _k, _boost, _accept) in enumerate(knn):
+            groups.setdefault((int(field), similarity, int(np.asarray(vector).reshape(-1).shape[0])), []).append(i)
+        for (field, similarity, _dim), idx in groups.items():
+            res = self.knn_search_requests(field, similarity, np.stack([np.asarray(knn[i][2], dtype=np.float32).reshape(-1) for i in idx]),
+                                           [int(knn[i][3]) for i in idx], boosts=[float(knn[i][4]) for i in idx],
+                                           filters=[knn[i][5] for i in idx])
+            for i, td in zip(idx, res):
+                clauses[i] = KnnClause(td.docs, td.scores, 1.0)
+        return self.search_text_knn_batch([query], [clauses], [manager])[0]
 
     def _marshal_multi_match(self, queries: Sequence[MultiMatchQuery], managers: Sequence[TopScoreDocCollectorManager]):
         """(nrtgpu_bm25_query array holder, nrtgpu_clause_groups array): the clauses of all groups in group order."""

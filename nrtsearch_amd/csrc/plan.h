@@ -547,6 +547,36 @@ __host__ __device__ inline float function_score_value(const DFuncQuery& f, uint3
   return final_score;
 }
 
+// A text query beside knn clauses (knnclauses.hip: bm25_text_knn_kernel; knnclauses.cpp): the request's `query` and its resolved
+// `knn` lists as SHOULD clauses of one BooleanQuery.  Beside the plan go the listed docs per (query, leaf) -- sorted leaf-local
+// docids and their knn_sum doubles, duplicates across lists merged, structure of arrays -- and one record per part of the plan
+// (same index as DPart).
+struct alignas(16) DKnnPart {
+  const uint64_t* live_bits;   // the LEAF's own liveDocs words (nullptr: all live): DPart.live_bits is the query's accept set, and
+                               // nullptr there when liveDocs are folded into the postings
+  uint32_t entry_begin, entry_end;   // the (query, leaf)'s entries inside the part's tile range
+  uint32_t nested;             // the query's form: 0 FLAT, 1 NESTED
+  uint32_t pad[3];
+};
+static_assert(sizeof(DKnnPart) == 32, "DKnnPart layout");
+// A slot the tag pass has finished: bit 63, and the doc's final float in the low 32 bits.  An untagged slot holds a fixed-point
+// sum: at most kMaxTerms clauses of values below 2^32 shifted left by at most 15 bits (planner.cpp: resolve_queries) -- below
+// 2^52, so bit 63 is never a sum's.
+constexpr uint64_t kKnnTag = 1ull << 63;
+static_assert(kMaxTerms <= 32, "a fixed-point sum must stay below 2^52 (32 clauses x 2^32 x 2^15): bit 63 is the tag");
+// The score of one doc under text + knn clauses [Lucene-recall].  text_matched: the doc matches the text query AND lies in its
+// accept set; fixed_sum: the double sum of its text clauses as the accumulators hold it (x 2^fx_E, exact); knn_sum: the double
+// sum, in list order, of the values of the lists that hold the doc, 0 when none does (a value is > 0).  Every operation is one
+// IEEE operation rounded once.  The ONE statement of it: bm25_text_knn_kernel and nrtgpu_text_knn_value both call this function.
+//   BooleanQuery.rewrite inlines a pure SHOULD disjunction into the outer query (FLAT: one double sum over all clauses, one
+//   cast); any other text query stays ONE clause whose float score is added (NESTED).
+__host__ __device__ inline float text_knn_value(uint32_t nested, bool text_matched, uint64_t fixed_sum, int fx_E, double knn_sum) {
+  const double text = text_matched ? ldexp((double)fixed_sum, -fx_E) : 0.0;   // fixed_sum < 2^53: exact conversion, exact scaling
+  if (!text_matched) return (float)knn_sum;
+  if (knn_sum == 0.0) return (float)text;   // the text query alone: what nrtgpu_search_bm25 scores
+  return nested != 0u ? (float)((double)(float)text + knn_sum) : (float)(text + knn_sum);
+}
+
 // Multi-match queries (multimatch.hip: bm25_multi_match_kernel; multimatch.cpp): two-level queries over term clauses -- a
 // BooleanQuery over DisjunctionMaxQuery groups (cross_fields) or a DisjunctionMaxQuery over BooleanQuery groups (best_fields).
 // The plan is the exhaustive route's over the clauses as one SHOULD disjunction; beside it one DGroupQuery per query, and every

@@ -68,7 +68,7 @@ static uint32_t sec_mode_of(const nrtgpu_bm25_query& q) {
 // accumulator sweep (in posting equivalents).
 static const int64_t kTileCostPostings = 48;
 
-struct QS { uint32_t term_begin, n_terms; int32_t seg; int64_t postings; };
+struct QS { uint32_t term_begin, n_terms; int32_t seg; int64_t postings; uint32_t tile_begin, tile_end; };   // tiles: the whole leaf, or what a kept leaf without terms is narrowed to
 struct QTabs { uint32_t n; float weight[kTabTerms]; uint32_t cache[kTabTerms]; int32_t scale[kTabTerms]; int32_t fx_E; };
 static const int32_t kNoFixed = INT32_MIN;  // QTabs.fx_E: the query needs the fp64 accumulators
 
@@ -288,7 +288,7 @@ static void resolve_queries(LeafSetCache& lsc, const nrtgpu_seg* const* segs, in
                             const int32_t* slice_of_leaf, int32_t n_slices, const nrtgpu_bm25_query* queries, int q_begin, int q_end, PlanPiece& pc, uint32_t* q_qs_begin,
                             uint32_t* q_qs_cnt, uint32_t* qs_begin, DQExpand* qexpand,
                             std::vector<uint32_t>& cache_base, std::vector<QTabs>& qtabs, int prune,
-                            std::vector<int64_t>& q_lower, std::vector<uint8_t>& q_route, std::vector<int64_t>& q_ms_key) {
+                            std::vector<int64_t>& q_lower, std::vector<uint8_t>& q_route, std::vector<int64_t>& q_ms_key, const PlanKeepLeaf* keep) {
   // (per query, on the stack: validate_query bounds n_terms by NRTGPU_MAX_TERMS)
   int64_t term_total[NRTGPU_MAX_TERMS];
   int32_t tab_of_term[NRTGPU_MAX_TERMS], term_scale[NRTGPU_MAX_TERMS];
@@ -342,6 +342,9 @@ static void resolve_queries(LeafSetCache& lsc, const nrtgpu_seg* const* segs, in
     for (int t = 0; t < q.n_terms && fx_ok; ++t)  // 32-bit entries shifted into the common scale, summed over
       if (term_total[(size_t)t] != 0 && fx_E - term_scale[(size_t)t] > 15) fx_ok = false;  // <= 32 clauses: < 2^53
     if (!fx_ok) fx_E = kNoFixed;
+    if (keep && fx_ok && fx_E == kNoFixed)   // no clause matches anything, but a leaf is kept: there are no sums, any scale serves
+      for (int si = 0; si < n_segs; ++si)
+        if (keep[(size_t)qi * (size_t)n_segs + (size_t)si].tile_end > keep[(size_t)qi * (size_t)n_segs + (size_t)si].tile_begin) fx_E = 0;
     // MaxScore route (maxscore.hip)?  Any disjunction of up to kMsMaxTerms clauses with the exact fixed-point sums -- plain,
     // with a FILTER / MUST_NOT doc set, with minimumNumberShouldMatch, or a DisjunctionMaxQuery -- unless a bound from
     // outside (min_competitive_score) makes the count's meaning the caller's business.  The mode says when bounds may skip
@@ -467,8 +470,17 @@ static void resolve_queries(LeafSetCache& lsc, const nrtgpu_seg* const* segs, in
       }
       if (lacks_must) n = 0;
       qs_begin[(size_t)qi * (size_t)n_segs + (size_t)si] = n ? pc.n_dterms : 0xFFFFFFFFu;
-      if (n == 0) continue;
-      pc.qs.push_back(QS{pc.n_dterms, n, si, postings});
+      if (n == 0) {
+        // a leaf that holds none of the query's terms is planned only when the caller keeps it: a part without clauses
+        if (!keep) continue;
+        const PlanKeepLeaf& kl = keep[(size_t)qi * (size_t)n_segs + (size_t)si];
+        const uint32_t te = std::min(kl.tile_end, segs[si]->n_tiles);
+        if (te <= kl.tile_begin) continue;
+        pc.qs.push_back(QS{pc.n_dterms, 0, si, 0, kl.tile_begin, te});
+        pc.cost += (int64_t)(te - kl.tile_begin) * kTileCostPostings;
+        continue;
+      }
+      pc.qs.push_back(QS{pc.n_dterms, n, si, postings, 0, segs[si]->n_tiles});
       pc.n_dterms += n;
       pc.postings += postings;
       pc.cost += postings + (int64_t)segs[si]->n_tiles * kTileCostPostings;
@@ -478,7 +490,7 @@ static void resolve_queries(LeafSetCache& lsc, const nrtgpu_seg* const* segs, in
 }
 
 int nrtgpu::rt::build_plan(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
-                      const nrtgpu_bm25_query* queries, int32_t n_queries, HostPlan& hp, int prune) {
+                      const nrtgpu_bm25_query* queries, int32_t n_queries, HostPlan& hp, int prune, const PlanKeepLeaf* keep) {
   const double t_entry = now_ms();
   uint32_t kmax = 1;
   for (int qi = 0; qi < n_queries; ++qi) {
@@ -529,6 +541,7 @@ int nrtgpu::rt::build_plan(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const
     // (the MaxScore route adds exact fixed-point integers: a context that asks for fp64 sums gets the exhaustive scan)
     if ((ctx->cfg.flags & (NRTGPU_FLAG_NO_PRUNE | NRTGPU_FLAG_NO_FIXED_POINT)) != 0 || !(variant == 0 || variant == 7)) prune = 0;
   }
+  if (prune != 0) keep = nullptr;   // (kept leaves are the exhaustive routes')
   hp.q_lower.assign((size_t)n_queries, 0);
   hp.q_route.assign((size_t)n_queries, kRouteScan);
   std::vector<int64_t> q_ms_key((size_t)n_queries, 0);   // (resolve_queries: launch-order key of the query's MaxScore items)
@@ -567,7 +580,7 @@ int nrtgpu::rt::build_plan(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const
   }
   auto work = [&](int t) {
     resolve_queries(*hp.lsc, segs, n_segs, n_deleted.data(), slice_of_leaf.data(), n_slices, queries, chunk_begin(t), chunk_begin(t + 1), pieces[(size_t)t],
-                    q_qs_begin.data(), q_qs_cnt.data(), hp.qs_begin.data(), hp.qexpand.data(), cache_base, qtabs, prune, hp.q_lower, hp.q_route, q_ms_key);
+                    q_qs_begin.data(), q_qs_cnt.data(), hp.qs_begin.data(), hp.qexpand.data(), cache_base, qtabs, prune, hp.q_lower, hp.q_route, q_ms_key, keep);
   };
   ctx->pool->run(n_chunks, work);
   const double tp1 = plan_trace ? now_ms() : 0.0;
@@ -652,12 +665,12 @@ int nrtgpu::rt::build_plan(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const
   for (int qi = 0; qi < n_queries; ++qi)
     for (uint32_t j = 0; j < q_qs_cnt[(size_t)qi]; ++j) {
       const QS& qs = qs_of(qi)[j];
-      q_costs[(size_t)qi] += qs.postings + (int64_t)segs[qs.seg]->n_tiles * kTileCostPostings;
+      q_costs[(size_t)qi] += qs.postings + (int64_t)(qs.tile_end - qs.tile_begin) * kTileCostPostings;
     }
   hostmath::plan_item_counts(q_costs.data(), n_queries, target_items, min_item_cost, q_items.data());  // host_math.h
   // One contiguous range of queries per worker, each into its own part / item vectors; concatenated in range order
   // below, so the plan is the one a single thread would have produced.
-  struct CutPiece { std::vector<DPart> parts; std::vector<Pending> pend; bool masked = false; int rc = 0; };
+  struct CutPiece { std::vector<DPart> parts; std::vector<Pending> pend; std::vector<int32_t> leaf; bool masked = false; int rc = 0; };
   std::vector<CutPiece> cuts((size_t)n_chunks);
   auto cut_work = [&](int t) {
     const int q0 = chunk_begin(t), q1 = chunk_begin(t + 1);
@@ -693,14 +706,14 @@ int nrtgpu::rt::build_plan(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const
         const nrtgpu_seg* seg = segs[qs.seg];
         const int32_t sl = slice_of_leaf[(size_t)qs.seg];
         if (cur.n_parts > 0 && sl != cur.last_slice && cur.n_slices == (uint32_t)kSliceSlots) close_item();  // no slot left for another slice
-        const double tile_cost = (double)qs.postings / (double)seg->n_tiles + (double)kTileCostPostings;
+        const double tile_cost = (double)qs.postings / (double)(qs.tile_end - qs.tile_begin) + (double)kTileCostPostings;
         const uint64_t* accept = nullptr;  // liveDocs, narrowed by the query's FILTER / MUST_NOT masks
         if (int rc = accept_set_of(seg, queries[qi], &accept)) { cut_rc = rc; return; }
-        uint32_t tb = 0;
-        while (tb < seg->n_tiles) {
+        uint32_t tb = qs.tile_begin;
+        while (tb < qs.tile_end) {
           double room = budget - filled;
           uint32_t take = (uint32_t)std::max(1.0, std::floor(room / tile_cost + 0.5));
-          take = std::min<uint32_t>(take, seg->n_tiles - tb);
+          take = std::min<uint32_t>(take, qs.tile_end - tb);
           if (cur.n_parts == 0) cur.first_slice = sl;
           if (sl != cur.last_slice) { cur.n_slices++; cur.last_slice = sl; }
           DPart p{};
@@ -715,6 +728,7 @@ int nrtgpu::rt::build_plan(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const
           p.tile_offset = cur.tiles;
           p.slice = (uint32_t)sl;   // (the slot is assigned once the items are final, below)
           parts.push_back(p);
+          if (keep) cuts[(size_t)t].leaf.push_back(qs.seg);   // (HostPlan.part_leaf)
           cur.n_parts++;
           cur.tiles += take;
           cur.cost += (int64_t)(take * tile_cost);
@@ -762,6 +776,7 @@ int nrtgpu::rt::build_plan(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const
       if (c.rc) return c.rc;
       const uint32_t base = (uint32_t)hp.parts.size();
       hp.parts.insert(hp.parts.end(), c.parts.begin(), c.parts.end());
+      hp.part_leaf.insert(hp.part_leaf.end(), c.leaf.begin(), c.leaf.end());
       for (Pending& a : c.pend) { a.part_begin += base; pend.push_back(a); }
       if (c.masked) hp.masked = true;
     }

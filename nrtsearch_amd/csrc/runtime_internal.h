@@ -57,6 +57,8 @@ void launch_bm25_multi_match(hipStream_t stream, const FinalScoreArgs& a, const 
 // a function score over multi-match queries (multimatch.hip): the records of both
 void launch_bm25_multi_match_function_score(hipStream_t stream, const FinalScoreArgs& a, const DGroupQuery* gqueries, const DFuncQuery* fqueries,
                                             const DFuncMasks* fmasks);
+// a text query beside knn clauses (knnclauses.hip): one DKnnPart per part, the listed docs and their knn_sum per (query, leaf)
+void launch_bm25_text_knn(hipStream_t stream, const FinalScoreArgs& a, const DKnnPart* kparts, const uint32_t* kdocs, const double* ksums);
 #ifdef NRTGPU_DEV
 void launch_debug_wave_kth(hipStream_t stream, const uint64_t* keys, uint32_t n, uint32_t r, uint64_t* out);   // (maxscore.hip: topk_kth_wave on its own)
 void launch_debug_walk_value(hipStream_t stream, float weight, const uint32_t* freq, const uint32_t* norm, const float* table, int fx_scale,
@@ -994,6 +996,12 @@ struct HostPlan {
   std::vector<int64_t> q_lower;     // per query on that route in kMsModePrune: live docs certain to match (> totalHitsThreshold), else 0
   std::vector<uint8_t> q_route;     // per query: kRouteScan (exhaustive scan) or kRouteMs + its kMsMode* (plan.h)
   int64_t ms_postings = 0;          // postings of the queries on that route (algorithmic work, as `postings`)
+  std::vector<int32_t> part_leaf;   // plans built with kept leaves (build_plan: keep) only: per part its leaf's index in the call
+};
+// A leaf the caller wants planned for a query even though it holds none of the query's terms (knnclauses.cpp: a listed doc
+// there is still a hit): the tile range to walk, as a part with n_terms == 0.  tile_end <= tile_begin: not kept.
+struct PlanKeepLeaf {
+  uint32_t tile_begin, tile_end;
 };
 
 const uint8_t kRouteScan = 0, kRouteMs = 1;   // HostPlan.q_route: kRouteMs + kMsMode*
@@ -1005,7 +1013,10 @@ bool fixed_scale_of_term(float weight, const float* cache256, uint32_t max_norm,
 // lower bound, relation GTE); 2 = the same for device-resident results: no searchAfter there (a page may hold fewer
 // than numHits hits, and then the relation needs the exact count)
 int build_plan(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
-               const nrtgpu_bm25_query* queries, int32_t n_queries, HostPlan& hp, int prune = 0);
+               const nrtgpu_bm25_query* queries, int32_t n_queries, HostPlan& hp, int prune = 0, const PlanKeepLeaf* keep = nullptr);
+// keep: nullptr, or n_queries x n_segs records (prune == 0 only): the (query, leaf) pairs to plan although the leaf holds none of
+// the query's terms; a query none of whose terms any leaf holds is then planned over its kept leaves.  Plans built without it
+// are what they were.
 
 // ---- the text routes' plan blob and workspace (search.cpp: enqueue_search; finalscore.cpp: enqueue_final_score) -----------------
 // One layout for every route: the twelve plan arrays of a HostPlan in upload order, and the seven workspace regions every route
