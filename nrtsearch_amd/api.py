@@ -181,46 +181,105 @@ def _int8_rows(a, what: str) -> np.ndarray:
     return np.ascontiguousarray(np.atleast_2d(a))
 
 
-def _topdocs_outputs(nq: int, k: int):
-    """(outs, docs, scores) for a call that returns nq lists of up to k hits: an array of nrtgpu_topdocs whose docs / scores pointers
-    address the rows of two numpy arrays.  Built once per thread and shape and used again -- 2 x nq pointer objects through
-    numpy's ctypes bridge cost 0.3 ms at 64 queries, a tenth of an exact vector search's pass; the caller copies what it returns."""
+# the scalar fields of an array of nrtgpu_topdocs as numpy sees them: a call's capacities go in and its counts come out in one statement each
+_TOPDOCS_SCALARS = np.dtype({"names": ["n_hits", "capacity", "total_hits", "total_hits_is_lower_bound"], "formats": ["<i4", "<i4", "<i8", "<i4"],
+                             "offsets": [getattr(_lib.TopDocs, n).offset for n in ("n_hits", "capacity", "total_hits", "total_hits_is_lower_bound")],
+                             "itemsize": C.sizeof(_lib.TopDocs)})
+
+
+class _Outputs:
+    """What a call that returns nq lists of up to `width` hits writes into: an array of nrtgpu_topdocs whose docs / scores pointers
+    address the rows of two numpy arrays.  What it hands out (lists, topdocs) is a copy: the holder is used again."""
+
+    def __init__(self, nq: int, width: int):
+        self.outs = (_lib.TopDocs * nq)()
+        self.docs = np.zeros((nq, width), dtype=np.int32)
+        self.scores = np.zeros((nq, width), dtype=np.float32)
+        self.outs._rows = (self.docs, self.scores)   # (what the pointers address lives as long as the array: _topdocs_outputs' callers keep only that)
+        self.scalars = np.frombuffer(self.outs, dtype=_TOPDOCS_SCALARS)
+        d0, s0 = self.docs.ctypes.data, self.scores.ctypes.data
+        for qi in range(nq):
+            self.outs[qi].docs = C.cast(d0 + qi * width * 4, C.POINTER(C.c_int32))
+            self.outs[qi].scores = C.cast(s0 + qi * width * 4, C.POINTER(C.c_float))
+
+    def begin(self, caps) -> "_Outputs":
+        """Before a call: the capacity the library is told per query (one int for all, or one each; the entries differ in what they
+        pass, and the library refuses some values on purpose), no hits yet."""
+        self.scalars["capacity"] = caps
+        self.scalars["n_hits"] = 0
+        self.scalars["total_hits"] = 0
+        return self
+
+    def lists(self, none_if_negative: bool = False) -> list:
+        """The call's answers as TopDocs: ONE copy of each array, a row's hits as a view of it; none_if_negative: None for a query the
+        call left with total_hits < 0 (a dist search delivers only this rank's slice of the batch)."""
+        dc, sc = self.docs.copy(), self.scores.copy()
+        counts = (self.scalars[name].tolist() for name in ("n_hits", "total_hits", "total_hits_is_lower_bound"))
+        return [None if none_if_negative and total < 0 else TopDocs(dc[qi, :m], sc[qi, :m], total, bool(lower))
+                for qi, (m, total, lower) in enumerate(zip(*counts))]
+
+    def topdocs(self, qi: int) -> TopDocs:
+        o = self.outs[qi]
+        return TopDocs(self.docs[qi, : o.n_hits].copy(), self.scores[qi, : o.n_hits].copy(), int(o.total_hits),
+                       bool(o.total_hits_is_lower_bound))
+
+
+def _outputs(nq: int, width: int, caps=None) -> _Outputs:
+    """The calling thread's holder of that shape, begun (caps: _Outputs.begin; None = the width).  Built once per thread and shape and
+    used again -- 2 x nq pointer objects through numpy's ctypes bridge cost 0.3 ms at 64 queries, a tenth of an exact vector search's
+    pass."""
     cache = getattr(_OUT_ARRAYS, "by_shape", None)
     if cache is None:
         cache = _OUT_ARRAYS.by_shape = {}
-    got = cache.get((nq, k))
-    if got is None:
-        outs = (_lib.TopDocs * nq)()
-        docs = np.zeros((nq, k), dtype=np.int32)
-        scores = np.zeros((nq, k), dtype=np.float32)
-        d0, s0 = docs.ctypes.data, scores.ctypes.data
-        for qi in range(nq):
-            outs[qi].capacity = k
-            outs[qi].docs = C.cast(d0 + qi * k * 4, C.POINTER(C.c_int32))
-            outs[qi].scores = C.cast(s0 + qi * k * 4, C.POINTER(C.c_float))
+    h = cache.get((nq, width))
+    if h is None:
         if len(cache) >= 8:
             cache.clear()
-        got = cache[(nq, k)] = (outs, docs, scores)
-    outs = got[0]
-    for qi in range(nq):
-        outs[qi].n_hits = 0
-        outs[qi].total_hits = 0
-    return got
+        h = cache[(nq, width)] = _Outputs(nq, width)
+    return h.begin(width if caps is None else caps)
 
 
-def _topdocs_lists(outs, docs, scores, n: int, none_if_negative: bool = False):
-    """The call's answers as TopDocs: ONE copy of each array (the arrays of _topdocs_outputs are used again), a row's hits as a view of it."""
-    dc, sc = docs.copy(), scores.copy()
-    res = []
-    for qi in range(n):
-        o = outs[qi]
-        th = int(o.total_hits)
-        if none_if_negative and th < 0:
-            res.append(None)
-            continue
-        m = o.n_hits
-        res.append(TopDocs(dc[qi, :m], sc[qi, :m], th, bool(o.total_hits_is_lower_bound)))
-    return res
+def _text_outputs(n: int, managers) -> _Outputs:
+    """The outputs of a text entry: max(num_hits, 1) hits per query."""
+    caps = [max(int(mgr.num_hits), 1) for mgr in managers]
+    return _outputs(n, max(caps, default=1), caps)
+
+
+def _topdocs_outputs(nq: int, k: int):
+    """(outs, docs, scores) of _outputs(nq, k), capacity k in every element: for a caller that makes the library call itself."""
+    h = _outputs(nq, k)
+    return h.outs, h.docs, h.scores
+
+
+def _supported(rc: int) -> bool:
+    """An eligibility predicate's answer: NRTGPU_OK -> True, NRTGPU_ERR_UNSUPPORTED -> False, anything else is an error."""
+    if rc == _lib.NRTGPU_ERR_UNSUPPORTED:
+        return False
+    _lib.check(rc)
+    return True
+
+
+def _float_queries(queries, similarity: str, one: bool = False) -> np.ndarray:
+    """float32[nq, dim] (one: float32[dim]), contiguous; unit-normalised for "normalized_cosine", which is then a dot product
+    (VectorFieldDef.java:568-573).  The norm of ONE query is numpy's vector norm, the norms of a batch its reduction along the rows:
+    the two may round differently, so a query may reach a single-query entry and a batch entry with other bits."""
+    q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1) if one else np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+    if similarity == "normalized_cosine":
+        norm = np.linalg.norm(q) if one else np.linalg.norm(q, axis=1, keepdims=True)
+        q = np.ascontiguousarray(q / norm.astype(np.float32), dtype=np.float32)
+    return q
+
+
+def _request_arrays(nq: int, ks, boosts, filters, min_scores):
+    """[ks, boosts, masks, min_scores] of a `*_requests` entry: one value per query each, None where the caller gave none."""
+    ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
+    boosts = None if boosts is None else np.ascontiguousarray(boosts, dtype=np.float32).reshape(-1)
+    masks = None if filters is None else np.array([int(f.mask_id) if f is not None else 0 for f in filters], dtype=np.int32)
+    min_scores = None if min_scores is None else np.ascontiguousarray(min_scores, dtype=np.float32).reshape(-1)
+    for name, a in (("ks", ks), ("boosts", boosts), ("filters", masks), ("min_scores", min_scores)):
+        if a is not None and a.shape[0] != nq:
+            raise ValueError(f"{name}: {a.shape[0]} values for {nq} queries")
+    return [ks, boosts, masks, min_scores]
 
 
 # ---- statistics / similarity ---------------------------------------------------------------------
@@ -666,28 +725,15 @@ class GpuIndexSearcher:
                     setattr(q, p_name, arr)
         return m
 
+    def _run_text(self, entry: str, m: _Marshalled, managers: Sequence[TopScoreDocCollectorManager], *records) -> List[TopDocs]:
+        """A text route's batch entry: entry(ctx, segs, bases, n_segs, queries, *the route's records per query, n, outs)."""
+        n = len(m.queries)
+        h = _text_outputs(n, managers)
+        _lib.check(getattr(_lib.load(), entry)(self.ctx._h, self._segs, self._bases, len(self.leaves), m.queries, *records, n, h.outs))
+        return h.lists()
+
     def search_batch(self, queries: Sequence[Query], managers: Sequence[TopScoreDocCollectorManager]) -> List[TopDocs]:
-        n = len(queries)
-        m = self._marshal(queries, managers)
-        outs = (_lib.TopDocs * n)()
-        bufs = []
-        for qi, mgr in enumerate(managers):
-            cap = max(int(mgr.num_hits), 1)
-            d = np.zeros(cap, dtype=np.int32)
-            s = np.zeros(cap, dtype=np.float32)
-            bufs.append((d, s))
-            outs[qi].capacity = cap
-            outs[qi].docs = d.ctypes.data_as(C.POINTER(C.c_int32))
-            outs[qi].scores = s.ctypes.data_as(C.POINTER(C.c_float))
-        _lib.check(_lib.load().nrtgpu_search_bm25_batch(self.ctx._h, self._segs, self._bases, len(self.leaves),
-                                                        m.queries, n, outs))
-        res = []
-        for qi in range(n):
-            nh = outs[qi].n_hits
-            d, s = bufs[qi]
-            res.append(TopDocs(d[:nh].copy(), s[:nh].copy(), int(outs[qi].total_hits),
-                               bool(outs[qi].total_hits_is_lower_bound)))
-        return res
+        return self._run_text("nrtgpu_search_bm25_batch", self._marshal(queries, managers), managers)
 
     def search(self, query: Query, manager: TopScoreDocCollectorManager) -> TopDocs:
         return self.search_batch([query], [manager])[0]
@@ -715,35 +761,14 @@ class GpuIndexSearcher:
                                     managers: Sequence[TopScoreDocCollectorManager]) -> List[TopDocs]:
         """MultiFunctionScoreQuery searches (nrtgpu_search_function_score_batch): every live doc matching the inner query is
         scored, total_hits is exact."""
-        n = len(queries)
         m = self._marshal([q.inner for q in queries], managers)
-        fs = self._marshal_function_scores(queries, m)
-        outs = (_lib.TopDocs * n)()
-        bufs = []
-        for qi, mgr in enumerate(managers):
-            cap = max(int(mgr.num_hits), 1)
-            d = np.zeros(cap, dtype=np.int32)
-            s = np.zeros(cap, dtype=np.float32)
-            bufs.append((d, s))
-            outs[qi].capacity = cap
-            outs[qi].docs = d.ctypes.data_as(C.POINTER(C.c_int32))
-            outs[qi].scores = s.ctypes.data_as(C.POINTER(C.c_float))
-        _lib.check(_lib.load().nrtgpu_search_function_score_batch(self.ctx._h, self._segs, self._bases, len(self.leaves),
-                                                                  m.queries, fs, n, outs))
-        return [TopDocs(bufs[qi][0][: outs[qi].n_hits].copy(), bufs[qi][1][: outs[qi].n_hits].copy(), int(outs[qi].total_hits),
-                        bool(outs[qi].total_hits_is_lower_bound)) for qi in range(n)]
+        return self._run_text("nrtgpu_search_function_score_batch", m, managers, self._marshal_function_scores(queries, m))
 
     def function_score_supported(self, query: FunctionScoreQuery, manager: TopScoreDocCollectorManager) -> bool:
         """The eligibility predicate alone (nrtgpu_function_score_supported)."""
         m = self._marshal([query.inner], [manager])
         fs = self._marshal_function_scores([query], m)
-        rc = _lib.load().nrtgpu_function_score_supported(self.ctx._h, self._segs, len(self.leaves), m.queries, fs)
-        if rc == _lib.NRTGPU_OK:
-            return True
-        if rc == _lib.NRTGPU_ERR_UNSUPPORTED:
-            return False
-        _lib.check(rc)
-        return False
+        return _supported(_lib.load().nrtgpu_function_score_supported(self.ctx._h, self._segs, len(self.leaves), m.queries, fs))
 
     def _marshal_knn_clauses(self, knn_clauses: Sequence[Sequence[KnnClause]], m: _Marshalled):
         """nrtgpu_knn_clauses per query; the form by BooleanQuery.rewrite's rule: a text query with FILTER / MUST_NOT clauses is no
@@ -771,36 +796,16 @@ class GpuIndexSearcher:
                               managers: Sequence[TopScoreDocCollectorManager]) -> List[TopDocs]:
         """Requests with `query` AND `knn` (nrtgpu_search_text_knn_batch): knn_clauses[i], the resolved knn lists of request i, are
         further SHOULD clauses beside queries[i] in one BooleanQuery.  Every hit is scored, total_hits is exact."""
-        n = len(queries)
-        if len(knn_clauses) != n:
-            raise ValueError(f"{len(knn_clauses)} knn clause lists for {n} queries")
+        if len(knn_clauses) != len(queries):
+            raise ValueError(f"{len(knn_clauses)} knn clause lists for {len(queries)} queries")
         m = self._marshal(queries, managers)
-        kc = self._marshal_knn_clauses(knn_clauses, m)
-        outs = (_lib.TopDocs * n)()
-        bufs = []
-        for qi, mgr in enumerate(managers):
-            cap = max(int(mgr.num_hits), 1)
-            d = np.zeros(cap, dtype=np.int32)
-            s = np.zeros(cap, dtype=np.float32)
-            bufs.append((d, s))
-            outs[qi].capacity = cap
-            outs[qi].docs = d.ctypes.data_as(C.POINTER(C.c_int32))
-            outs[qi].scores = s.ctypes.data_as(C.POINTER(C.c_float))
-        _lib.check(_lib.load().nrtgpu_search_text_knn_batch(self.ctx._h, self._segs, self._bases, len(self.leaves), m.queries, kc, n, outs))
-        return [TopDocs(bufs[qi][0][: outs[qi].n_hits].copy(), bufs[qi][1][: outs[qi].n_hits].copy(), int(outs[qi].total_hits),
-                        bool(outs[qi].total_hits_is_lower_bound)) for qi in range(n)]
+        return self._run_text("nrtgpu_search_text_knn_batch", m, managers, self._marshal_knn_clauses(knn_clauses, m))
 
     def text_knn_supported(self, query: Query, knn_clauses: Sequence[KnnClause], manager: TopScoreDocCollectorManager) -> bool:
         """The eligibility predicate alone (nrtgpu_text_knn_supported)."""
         m = self._marshal([query], [manager])
         kc = self._marshal_knn_clauses([knn_clauses], m)
-        rc = _lib.load().nrtgpu_text_knn_supported(self.ctx._h, self._segs, len(self.leaves), m.queries, kc)
-        if rc == _lib.NRTGPU_OK:
-            return True
-        if rc == _lib.NRTGPU_ERR_UNSUPPORTED:
-            return False
-        _lib.check(rc)
-        return False
+        return _supported(_lib.load().nrtgpu_text_knn_supported(self.ctx._h, self._segs, len(self.leaves), m.queries, kc))
 
     def search_with_knn(self, query: Query, manager: TopScoreDocCollectorManager, knn: Sequence[tuple] = ()) -> TopDocs:
         """The request as a caller writes it: `query` and knn = [(field, similarity, vector, k, boost, accept)], accept a MaskFilter
@@ -863,32 +868,13 @@ class GpuIndexSearcher:
 
     def search_multi_match_batch(self, queries: Sequence[MultiMatchQuery], managers: Sequence[TopScoreDocCollectorManager]) -> List[TopDocs]:
         """Multi-match searches (nrtgpu_search_multi_match_batch): every live doc that is a hit is scored, total_hits is exact."""
-        n = len(queries)
         m, gs = self._marshal_multi_match(queries, managers)
-        outs = (_lib.TopDocs * n)()
-        bufs = []
-        for qi, mgr in enumerate(managers):
-            cap = max(int(mgr.num_hits), 1)
-            d = np.zeros(cap, dtype=np.int32)
-            s = np.zeros(cap, dtype=np.float32)
-            bufs.append((d, s))
-            outs[qi].capacity = cap
-            outs[qi].docs = d.ctypes.data_as(C.POINTER(C.c_int32))
-            outs[qi].scores = s.ctypes.data_as(C.POINTER(C.c_float))
-        _lib.check(_lib.load().nrtgpu_search_multi_match_batch(self.ctx._h, self._segs, self._bases, len(self.leaves), m.queries, gs, n, outs))
-        return [TopDocs(bufs[qi][0][: outs[qi].n_hits].copy(), bufs[qi][1][: outs[qi].n_hits].copy(), int(outs[qi].total_hits),
-                        bool(outs[qi].total_hits_is_lower_bound)) for qi in range(n)]
+        return self._run_text("nrtgpu_search_multi_match_batch", m, managers, gs)
 
     def multi_match_supported(self, query: MultiMatchQuery, manager: TopScoreDocCollectorManager) -> bool:
         """The eligibility predicate alone (nrtgpu_multi_match_supported)."""
         m, gs = self._marshal_multi_match([query], [manager])
-        rc = _lib.load().nrtgpu_multi_match_supported(self.ctx._h, self._segs, len(self.leaves), m.queries, gs)
-        if rc == _lib.NRTGPU_OK:
-            return True
-        if rc == _lib.NRTGPU_ERR_UNSUPPORTED:
-            return False
-        _lib.check(rc)
-        return False
+        return _supported(_lib.load().nrtgpu_multi_match_supported(self.ctx._h, self._segs, len(self.leaves), m.queries, gs))
 
     def _marshal_function_score_multi_match(self, queries: Sequence[FunctionScoreQuery], managers: Sequence[TopScoreDocCollectorManager]):
         """(nrtgpu_bm25_query array holder, nrtgpu_clause_groups array, nrtgpu_function_score array) of function scores whose
@@ -903,33 +889,13 @@ class GpuIndexSearcher:
                                                 managers: Sequence[TopScoreDocCollectorManager]) -> List[TopDocs]:
         """MultiFunctionScoreQuery over MultiMatchQuery searches (nrtgpu_search_function_score_multi_match_batch): every live doc
         that is a hit of the inner query and passes the min_score test is scored, total_hits is exact."""
-        n = len(queries)
         m, gs, fs = self._marshal_function_score_multi_match(queries, managers)
-        outs = (_lib.TopDocs * n)()
-        bufs = []
-        for qi, mgr in enumerate(managers):
-            cap = max(int(mgr.num_hits), 1)
-            d = np.zeros(cap, dtype=np.int32)
-            s = np.zeros(cap, dtype=np.float32)
-            bufs.append((d, s))
-            outs[qi].capacity = cap
-            outs[qi].docs = d.ctypes.data_as(C.POINTER(C.c_int32))
-            outs[qi].scores = s.ctypes.data_as(C.POINTER(C.c_float))
-        _lib.check(_lib.load().nrtgpu_search_function_score_multi_match_batch(self.ctx._h, self._segs, self._bases, len(self.leaves), m.queries, gs, fs,
-                                                                              n, outs))
-        return [TopDocs(bufs[qi][0][: outs[qi].n_hits].copy(), bufs[qi][1][: outs[qi].n_hits].copy(), int(outs[qi].total_hits),
-                        bool(outs[qi].total_hits_is_lower_bound)) for qi in range(n)]
+        return self._run_text("nrtgpu_search_function_score_multi_match_batch", m, managers, gs, fs)
 
     def function_score_multi_match_supported(self, query: FunctionScoreQuery, manager: TopScoreDocCollectorManager) -> bool:
         """The eligibility predicate alone (nrtgpu_function_score_multi_match_supported)."""
         m, gs, fs = self._marshal_function_score_multi_match([query], [manager])
-        rc = _lib.load().nrtgpu_function_score_multi_match_supported(self.ctx._h, self._segs, len(self.leaves), m.queries, gs, fs)
-        if rc == _lib.NRTGPU_OK:
-            return True
-        if rc == _lib.NRTGPU_ERR_UNSUPPORTED:
-            return False
-        _lib.check(rc)
-        return False
+        return _supported(_lib.load().nrtgpu_function_score_multi_match_supported(self.ctx._h, self._segs, len(self.leaves), m.queries, gs, fs))
 
     def debug_walk_rows(self, queries: Sequence[Query], managers: Sequence[TopScoreDocCollectorManager]):
         """Test hook of the development library (nrtgpu_debug_walk_rows): the MaxScore route's walk rows of the batch, as the
@@ -958,94 +924,68 @@ class GpuIndexSearcher:
         rank gets the answers of its slice of the batch, None for the others."""
         n = len(queries)
         m = self._marshal(queries, managers)
-        outs = (_lib.TopDocs * n)()
-        bufs = []
-        for qi, mgr in enumerate(managers):
-            cap = max(int(mgr.num_hits), 1)
-            d = np.zeros(cap, dtype=np.int32)
-            s = np.zeros(cap, dtype=np.float32)
-            bufs.append((d, s))
-            outs[qi].capacity = cap
-            outs[qi].docs = d.ctypes.data_as(C.POINTER(C.c_int32))
-            outs[qi].scores = s.ctypes.data_as(C.POINTER(C.c_float))
+        h = _text_outputs(n, managers)
         _lib.check(_lib.load().nrtgpu_dist_search_bm25_batch_mode(self.ctx._h, self._segs, self._bases, len(self.leaves), m.queries, n,
-                                                                  int(mode), outs))
-        return [None if outs[qi].total_hits < 0 else
-                TopDocs(bufs[qi][0][: outs[qi].n_hits].copy(), bufs[qi][1][: outs[qi].n_hits].copy(), int(outs[qi].total_hits),
-                        bool(outs[qi].total_hits_is_lower_bound)) for qi in range(n)]
+                                                                  int(mode), h.outs))
+        return h.lists(none_if_negative=True)
 
     def dist_knn_exact(self, field: int, similarity: str, queries: np.ndarray, k: int, boost: float = 1.0,
                        mode: int = EXCHANGE_ALLGATHER) -> List[Optional[TopDocs]]:
         """Exact vector search over a row-partitioned field (nrtgpu_dist_knn_exact): this rank's leaves, exchange + merge
         inside the library; every rank passes the same queries."""
-        queries = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
-        if similarity == "normalized_cosine":
-            queries = np.ascontiguousarray(queries / np.linalg.norm(queries, axis=1, keepdims=True).astype(np.float32), dtype=np.float32)
-        nq, dim = queries.shape
-        outs, docs, scores = _topdocs_outputs(nq, int(k))
-        _lib.check(_lib.load().nrtgpu_dist_knn_exact(self.ctx._h, self._segs, self._bases, len(self.leaves), int(field),
-                                                     self.SIMILARITY[similarity], queries.ctypes.data, nq, dim, int(k),
-                                                     C.c_float(boost), int(mode), outs))
-        return _topdocs_lists(outs, docs, scores, nq, none_if_negative=True)
+        return self._knn_batch("nrtgpu_dist_knn_exact", field, self.SIMILARITY[similarity], _float_queries(queries, similarity), k,
+                               C.c_float(boost), int(mode), none_if_negative=True)
 
     def supported(self, query: Query, manager: TopScoreDocCollectorManager) -> bool:
         """The eligibility predicate alone (nrtgpu_query_supported): would the device route take this query?"""
         m = self._marshal([query], [manager])
-        rc = _lib.load().nrtgpu_query_supported(self.ctx._h, self._segs, len(self.leaves), m.queries)
-        if rc == _lib.NRTGPU_OK:
-            return True
-        if rc == _lib.NRTGPU_ERR_UNSUPPORTED:
-            return False
-        _lib.check(rc)
-        return False
+        return _supported(_lib.load().nrtgpu_query_supported(self.ctx._h, self._segs, len(self.leaves), m.queries))
 
     def search_coalesced(self, query: Query, manager: TopScoreDocCollectorManager) -> TopDocs:
         """Blocking single search meant to be called from many threads at once: the library merges
         concurrent callers into device batches (nrtgpu_search_bm25_coalesced)."""
         m = self._marshal([query], [manager])
-        cap = max(int(manager.num_hits), 1)
-        d = np.zeros(cap, dtype=np.int32)
-        s = np.zeros(cap, dtype=np.float32)
-        out = _lib.TopDocs()
-        out.capacity = cap
-        out.docs = d.ctypes.data_as(C.POINTER(C.c_int32))
-        out.scores = s.ctypes.data_as(C.POINTER(C.c_float))
-        _lib.check(_lib.load().nrtgpu_search_bm25_coalesced(self.ctx._h, self._segs, self._bases, len(self.leaves),
-                                                            m.queries, C.byref(out)))
-        return TopDocs(d[: out.n_hits].copy(), s[: out.n_hits].copy(), int(out.total_hits), bool(out.total_hits_is_lower_bound))
+        h = _text_outputs(1, [manager])
+        _lib.check(_lib.load().nrtgpu_search_bm25_coalesced(self.ctx._h, self._segs, self._bases, len(self.leaves), m.queries, h.outs))
+        return h.topdocs(0)
 
     # ---- vectors: ExactFloatVectorQuery / vector rescorer ------------------------------------------
     SIMILARITY = {"cosine": 0, "dot_product": 1, "normalized_cosine": 1, "l2_norm": 2, "max_inner_product": 3}
 
+    def _knn_batch(self, entry: str, field: int, sim: int, queries: np.ndarray, k: int, *tail, none_if_negative: bool = False) -> list:
+        """A batch of vector queries with one k through entry(ctx, segs, bases, n_segs, field, sim, queries, nq, dim, k, *tail, outs)."""
+        nq, dim = queries.shape
+        h = _outputs(nq, int(k))
+        _lib.check(getattr(_lib.load(), entry)(self.ctx._h, self._segs, self._bases, len(self.leaves), int(field), sim, queries.ctypes.data,
+                                               nq, dim, int(k), *tail, h.outs))
+        return h.lists(none_if_negative)
+
+    def _knn_requests(self, entry: str, field: int, sim: int, queries: np.ndarray, ks, boosts, filters, min_scores) -> List[TopDocs]:
+        """Vector queries with a k, boost, filter and threshold each through a `*_requests` entry."""
+        nq, dim = queries.shape
+        ks, *optional = _request_arrays(nq, ks, boosts, filters, min_scores)
+        h = _outputs(nq, max(int(ks.max()), 1))
+        _lib.check(getattr(_lib.load(), entry)(self.ctx._h, self._segs, self._bases, len(self.leaves), int(field), sim, queries.ctypes.data,
+                                               nq, dim, ks.ctypes.data, *(None if a is None else a.ctypes.data for a in optional), h.outs))
+        return h.lists()
+
+    def _one_knn_query(self, entry: str, field: int, sim: int, query: np.ndarray, k: int, cap: int, *tail) -> TopDocs:
+        """One query vector through a single-query (coalesced) entry; cap: the capacity the entry is told, tail: its scalars between
+        k and the output."""
+        h = _outputs(1, cap)
+        _lib.check(getattr(_lib.load(), entry)(self.ctx._h, self._segs, self._bases, len(self.leaves), int(field), sim, query.ctypes.data,
+                                               int(query.shape[0]), int(k), *tail, h.outs))
+        return h.topdocs(0)
+
     def knn_exact(self, field: int, similarity: str, queries: np.ndarray, k: int, boost: float = 1.0) -> List[TopDocs]:
         """Brute-force exact vector search over every doc with a vector (S/query/vector/ExactVectorQuery.java)."""
-        queries = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
-        if similarity == "normalized_cosine":  # unit-normalised query + dot product (VectorFieldDef.java:568-573)
-            queries = queries / np.linalg.norm(queries, axis=1, keepdims=True).astype(np.float32)
-            queries = np.ascontiguousarray(queries, dtype=np.float32)
-        nq, dim = queries.shape
-        outs, docs, scores = _topdocs_outputs(nq, int(k))
-        _lib.check(_lib.load().nrtgpu_knn_exact(self.ctx._h, self._segs, self._bases, len(self.leaves), int(field),
-                                                self.SIMILARITY[similarity], queries.ctypes.data, nq, dim, int(k),
-                                                C.c_float(boost), outs))
-        return _topdocs_lists(outs, docs, scores, nq)
+        return self._knn_batch("nrtgpu_knn_exact", field, self.SIMILARITY[similarity], _float_queries(queries, similarity), k, C.c_float(boost))
 
     def knn_exact_coalesced(self, field: int, similarity: str, query: np.ndarray, k: int, boost: float = 1.0) -> TopDocs:
         """What a request thread calls with ONE exact vector query: concurrent callers are merged into panels of up to 64 queries
         that share a pass over the rows (nrtgpu_knn_exact_coalesced)."""
-        query = np.ascontiguousarray(query, dtype=np.float32).reshape(-1)
-        if similarity == "normalized_cosine":
-            query = np.ascontiguousarray(query / np.linalg.norm(query).astype(np.float32), dtype=np.float32)
-        out = _lib.TopDocs()
-        docs = np.zeros(k, dtype=np.int32)
-        scores = np.zeros(k, dtype=np.float32)
-        out.capacity = k
-        out.docs = docs.ctypes.data_as(C.POINTER(C.c_int32))
-        out.scores = scores.ctypes.data_as(C.POINTER(C.c_float))
-        _lib.check(_lib.load().nrtgpu_knn_exact_coalesced(self.ctx._h, self._segs, self._bases, len(self.leaves), int(field),
-                                                          self.SIMILARITY[similarity], query.ctypes.data, int(query.shape[0]), int(k),
-                                                          C.c_float(boost), C.byref(out)))
-        return TopDocs(docs[: out.n_hits].copy(), scores[: out.n_hits].copy(), int(out.total_hits), bool(out.total_hits_is_lower_bound))
+        return self._one_knn_query("nrtgpu_knn_exact_coalesced", field, self.SIMILARITY[similarity], _float_queries(query, similarity, one=True),
+                                   k, int(k), C.c_float(boost))
 
     def knn_exact_relation(self, field: int, k: int, total_hits_threshold: int = TOTAL_HITS_THRESHOLD) -> bool:
         """TotalHits.relation of an exact vector query over these leaves by the reference's per-slice rule: True = GREATER_THAN_OR_EQUAL_TO
@@ -1058,60 +998,23 @@ class GpuIndexSearcher:
     def knn_search(self, field: int, similarity: str, queries: np.ndarray, k: int, boost: float = 1.0,
                    filter: Optional[MaskFilter] = None, min_score: float = 0.0) -> List[TopDocs]:
         """The `knn` request path (KnnQuery with filter and similarity threshold) answered by exact search."""
-        queries = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
-        if similarity == "normalized_cosine":
-            queries = np.ascontiguousarray(queries / np.linalg.norm(queries, axis=1, keepdims=True).astype(np.float32), dtype=np.float32)
-        nq, dim = queries.shape
-        outs, docs, scores = _topdocs_outputs(nq, int(k))
-        _lib.check(_lib.load().nrtgpu_knn_search(self.ctx._h, self._segs, self._bases, len(self.leaves), int(field),
-                                                 self.SIMILARITY[similarity], queries.ctypes.data, nq, dim, int(k),
-                                                 C.c_float(boost), int(filter.mask_id) if filter else 0,
-                                                 C.c_float(min_score), outs))
-        return _topdocs_lists(outs, docs, scores, nq)
+        return self._knn_batch("nrtgpu_knn_search", field, self.SIMILARITY[similarity], _float_queries(queries, similarity), k, C.c_float(boost),
+                               int(filter.mask_id) if filter else 0, C.c_float(min_score))
 
     def knn_search_requests(self, field: int, similarity: str, queries: np.ndarray, ks: Sequence[int], boosts: Optional[Sequence[float]] = None,
                             filters: Optional[Sequence[Optional[MaskFilter]]] = None,
                             min_scores: Optional[Sequence[float]] = None) -> List[TopDocs]:
         """`knn` requests with a k, boost, filter and threshold EACH, answered in passes of up to 64 that share one read of the rows
         (nrtgpu_knn_search_requests): query i gets what knn_search gives it alone."""
-        queries = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
-        if similarity == "normalized_cosine":
-            queries = np.ascontiguousarray(queries / np.linalg.norm(queries, axis=1, keepdims=True).astype(np.float32), dtype=np.float32)
-        nq, dim = queries.shape
-        ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
-        boosts = None if boosts is None else np.ascontiguousarray(boosts, dtype=np.float32).reshape(-1)
-        masks = None if filters is None else np.array([int(f.mask_id) if f is not None else 0 for f in filters], dtype=np.int32)
-        min_scores = None if min_scores is None else np.ascontiguousarray(min_scores, dtype=np.float32).reshape(-1)
-        for name, a in (("ks", ks), ("boosts", boosts), ("filters", masks), ("min_scores", min_scores)):
-            if a is not None and a.shape[0] != nq:
-                raise ValueError(f"{name}: {a.shape[0]} values for {nq} queries")
-        outs, docs, scores = _topdocs_outputs(nq, max(int(ks.max()), 1))
-        _lib.check(_lib.load().nrtgpu_knn_search_requests(self.ctx._h, self._segs, self._bases, len(self.leaves), int(field),
-                                                          self.SIMILARITY[similarity], queries.ctypes.data, nq, dim, ks.ctypes.data,
-                                                          boosts.ctypes.data if boosts is not None else None,
-                                                          masks.ctypes.data if masks is not None else None,
-                                                          min_scores.ctypes.data if min_scores is not None else None, outs))
-        return _topdocs_lists(outs, docs, scores, nq)
+        return self._knn_requests("nrtgpu_knn_search_requests", field, self.SIMILARITY[similarity], _float_queries(queries, similarity),
+                                  ks, boosts, filters, min_scores)
 
     def knn_search_coalesced(self, field: int, similarity: str, query: np.ndarray, k: int, boost: float = 1.0,
                              filter: Optional[MaskFilter] = None, min_score: float = 0.0) -> TopDocs:
         """What a request thread calls with ONE `knn` request: concurrent callers share panels of up to 64 whatever their k, filter,
         threshold and boost (nrtgpu_knn_search_coalesced)."""
-        query = np.ascontiguousarray(query, dtype=np.float32).reshape(-1)
-        if similarity == "normalized_cosine":
-            query = np.ascontiguousarray(query / np.linalg.norm(query).astype(np.float32), dtype=np.float32)
-        k = int(k)
-        out = _lib.TopDocs()
-        docs = np.zeros(max(k, 1), dtype=np.int32)
-        scores = np.zeros(max(k, 1), dtype=np.float32)
-        out.capacity = max(k, 1)
-        out.docs = docs.ctypes.data_as(C.POINTER(C.c_int32))
-        out.scores = scores.ctypes.data_as(C.POINTER(C.c_float))
-        _lib.check(_lib.load().nrtgpu_knn_search_coalesced(self.ctx._h, self._segs, self._bases, len(self.leaves), int(field),
-                                                           self.SIMILARITY[similarity], query.ctypes.data, int(query.shape[0]), k,
-                                                           C.c_float(boost), int(filter.mask_id) if filter else 0, C.c_float(min_score),
-                                                           C.byref(out)))
-        return TopDocs(docs[: out.n_hits].copy(), scores[: out.n_hits].copy(), int(out.total_hits), bool(out.total_hits_is_lower_bound))
+        return self._one_knn_query("nrtgpu_knn_search_coalesced", field, self.SIMILARITY[similarity], _float_queries(query, similarity, one=True),
+                                   k, max(int(k), 1), C.c_float(boost), int(filter.mask_id) if filter else 0, C.c_float(min_score))
 
     # ---- byte (int8) vector fields: ExactByteVectorQuery / NrtKnnByteVectorQuery ---------------------
     BYTE_SIMILARITY = {"cosine": 0, "dot_product": 1, "l2_norm": 2, "max_inner_product": 3}
@@ -1123,75 +1026,34 @@ class GpuIndexSearcher:
 
     def knn_exact_bytes(self, field: int, similarity: str, queries: np.ndarray, k: int, boost: float = 1.0) -> List[TopDocs]:
         """Brute-force exact search over a byte vector field (ExactVectorQuery.ExactByteVectorQuery); queries: int8."""
-        sim = self._byte_similarity(similarity)
-        queries = _int8_rows(queries, "queries")
-        nq, dim = queries.shape
-        outs, docs, scores = _topdocs_outputs(nq, int(k))
-        _lib.check(_lib.load().nrtgpu_knn_exact_bytes(self.ctx._h, self._segs, self._bases, len(self.leaves), int(field), sim,
-                                                      queries.ctypes.data, nq, dim, int(k), C.c_float(boost), outs))
-        return _topdocs_lists(outs, docs, scores, nq)
+        return self._knn_batch("nrtgpu_knn_exact_bytes", field, self._byte_similarity(similarity), _int8_rows(queries, "queries"), k, C.c_float(boost))
 
     def knn_search_bytes(self, field: int, similarity: str, queries: np.ndarray, k: int, boost: float = 1.0,
                          filter: Optional[MaskFilter] = None, min_score: float = 0.0) -> List[TopDocs]:
         """The `knn` request path over a byte vector field (NrtKnnByteVectorQuery with filter and similarity threshold), exact."""
-        sim = self._byte_similarity(similarity)
-        queries = _int8_rows(queries, "queries")
-        nq, dim = queries.shape
-        outs, docs, scores = _topdocs_outputs(nq, int(k))
-        _lib.check(_lib.load().nrtgpu_knn_search_bytes(self.ctx._h, self._segs, self._bases, len(self.leaves), int(field), sim,
-                                                       queries.ctypes.data, nq, dim, int(k), C.c_float(boost),
-                                                       int(filter.mask_id) if filter else 0, C.c_float(min_score), outs))
-        return _topdocs_lists(outs, docs, scores, nq)
+        return self._knn_batch("nrtgpu_knn_search_bytes", field, self._byte_similarity(similarity), _int8_rows(queries, "queries"), k, C.c_float(boost),
+                               int(filter.mask_id) if filter else 0, C.c_float(min_score))
 
     def knn_search_bytes_requests(self, field: int, similarity: str, queries: np.ndarray, ks: Sequence[int],
                                   boosts: Optional[Sequence[float]] = None, filters: Optional[Sequence[Optional[MaskFilter]]] = None,
                                   min_scores: Optional[Sequence[float]] = None) -> List[TopDocs]:
         """`knn` requests over a byte vector field with a k, boost, filter and threshold EACH, answered in passes of up to 64 that share
         one read of the rows (nrtgpu_knn_search_bytes_requests): query i gets what knn_search_bytes gives it alone."""
-        sim = self._byte_similarity(similarity)
-        queries = _int8_rows(queries, "queries")
-        nq, dim = queries.shape
-        ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
-        boosts = None if boosts is None else np.ascontiguousarray(boosts, dtype=np.float32).reshape(-1)
-        masks = None if filters is None else np.array([int(f.mask_id) if f is not None else 0 for f in filters], dtype=np.int32)
-        min_scores = None if min_scores is None else np.ascontiguousarray(min_scores, dtype=np.float32).reshape(-1)
-        for name, a in (("ks", ks), ("boosts", boosts), ("filters", masks), ("min_scores", min_scores)):
-            if a is not None and a.shape[0] != nq:
-                raise ValueError(f"{name}: {a.shape[0]} values for {nq} queries")
-        outs, docs, scores = _topdocs_outputs(nq, max(int(ks.max()), 1))
-        _lib.check(_lib.load().nrtgpu_knn_search_bytes_requests(self.ctx._h, self._segs, self._bases, len(self.leaves), int(field), sim,
-                                                                queries.ctypes.data, nq, dim, ks.ctypes.data,
-                                                                boosts.ctypes.data if boosts is not None else None,
-                                                                masks.ctypes.data if masks is not None else None,
-                                                                min_scores.ctypes.data if min_scores is not None else None, outs))
-        return _topdocs_lists(outs, docs, scores, nq)
-
-    def _one_byte_query(self, name: str, field: int, similarity: str, query: np.ndarray, k: int, *tail) -> TopDocs:
-        """One int8 query through a single-query (coalesced) entry; tail: the entry's scalars between k and the output."""
-        sim = self._byte_similarity(similarity)
-        query = _int8_rows(query, "query").reshape(-1)
-        k = int(k)
-        out = _lib.TopDocs()
-        docs = np.zeros(max(k, 1), dtype=np.int32)
-        scores = np.zeros(max(k, 1), dtype=np.float32)
-        out.capacity = max(k, 1)
-        out.docs = docs.ctypes.data_as(C.POINTER(C.c_int32))
-        out.scores = scores.ctypes.data_as(C.POINTER(C.c_float))
-        _lib.check(getattr(_lib.load(), name)(self.ctx._h, self._segs, self._bases, len(self.leaves), int(field), sim, query.ctypes.data,
-                                              int(query.shape[0]), k, *tail, C.byref(out)))
-        return TopDocs(docs[: out.n_hits].copy(), scores[: out.n_hits].copy(), int(out.total_hits), bool(out.total_hits_is_lower_bound))
+        return self._knn_requests("nrtgpu_knn_search_bytes_requests", field, self._byte_similarity(similarity), _int8_rows(queries, "queries"),
+                                  ks, boosts, filters, min_scores)
 
     def knn_search_bytes_coalesced(self, field: int, similarity: str, query: np.ndarray, k: int, boost: float = 1.0,
                                    filter: Optional[MaskFilter] = None, min_score: float = 0.0) -> TopDocs:
         """What a request thread calls with ONE `knn` request over a byte vector field: concurrent callers share panels of up to 64
         whatever their k, filter, threshold and boost (nrtgpu_knn_search_bytes_coalesced)."""
-        return self._one_byte_query("nrtgpu_knn_search_bytes_coalesced", field, similarity, query, k, C.c_float(boost),
-                                    int(filter.mask_id) if filter else 0, C.c_float(min_score))
+        return self._one_knn_query("nrtgpu_knn_search_bytes_coalesced", field, self._byte_similarity(similarity), _int8_rows(query, "query").reshape(-1),
+                                   k, max(int(k), 1), C.c_float(boost), int(filter.mask_id) if filter else 0, C.c_float(min_score))
 
     def knn_exact_bytes_coalesced(self, field: int, similarity: str, query: np.ndarray, k: int, boost: float = 1.0) -> TopDocs:
         """What a request thread calls with ONE exact query over a byte vector field: concurrent callers with one boost are merged into
         panels of up to 64 queries that share a pass over the rows (nrtgpu_knn_exact_bytes_coalesced)."""
-        return self._one_byte_query("nrtgpu_knn_exact_bytes_coalesced", field, similarity, query, k, C.c_float(boost))
+        return self._one_knn_query("nrtgpu_knn_exact_bytes_coalesced", field, self._byte_similarity(similarity), _int8_rows(query, "query").reshape(-1),
+                                   k, max(int(k), 1), C.c_float(boost))
 
     def rescore_vectors(self, hits: TopDocs, field: int, similarity: str, query: np.ndarray, window: int,
                         query_weight: float = 1.0, rescore_weight: float = 1.0, boost: float = 1.0) -> TopDocs:
@@ -1213,16 +1075,12 @@ class GpuIndexSearcher:
                  rescore_weight: float, boost: float) -> TopDocs:
         d = np.ascontiguousarray(hits.docs, dtype=np.int32)
         s = np.ascontiguousarray(hits.scores, dtype=np.float32)
-        out = _lib.TopDocs()
-        od = np.zeros(max(window, 1), dtype=np.int32)
-        os_ = np.zeros(max(window, 1), dtype=np.float32)
-        out.capacity = window
-        out.docs = od.ctypes.data_as(C.POINTER(C.c_int32))
-        out.scores = os_.ctypes.data_as(C.POINTER(C.c_float))
+        h = _outputs(1, max(int(window), 1), int(window))
         _lib.check(getattr(_lib.load(), entry)(self.ctx._h, self._segs, self._bases, len(self.leaves), int(field), sim,
                                                query.ctypes.data, len(query), C.c_float(boost), d.ctypes.data, s.ctypes.data, len(d),
-                                               float(query_weight), float(rescore_weight), int(window), C.byref(out)))
-        return TopDocs(od[: out.n_hits].copy(), os_[: out.n_hits].copy(), hits.total_hits, hits.relation_gte)
+                                               float(query_weight), float(rescore_weight), int(window), h.outs))
+        got = h.topdocs(0)
+        return TopDocs(got.docs, got.scores, hits.total_hits, hits.relation_gte)
 
     def search_hybrid_batch(self, queries: Sequence[Query], managers: Sequence[TopScoreDocCollectorManager], field: int,
                             similarity: str, query_vectors: np.ndarray, window: int, query_weight: float = 1.0,
@@ -1239,49 +1097,26 @@ class GpuIndexSearcher:
                             _int8_rows(query_vectors, "query vectors"), window, query_weight, rescore_weight, boost)
 
     def _hybrid(self, entry: str, queries: Sequence[Query], managers: Sequence[TopScoreDocCollectorManager], field: int, sim: int,
-                qv: np.ndarray, window: int, query_weight: float, rescore_weight: float, boost: float) -> List[TopDocs]:
+                qv: np.ndarray, window: int, query_weight: float, rescore_weight: float, boost: float, dist_mode: Optional[int] = None) -> list:
+        """dist_mode: the entry is the one over docid-range shards, which takes the exchange mode after the window and delivers only
+        this rank's slice of the batch (None for the others)."""
         n = len(queries)
         if qv.shape[0] != n:
             raise ValueError("one query vector per query")
         m = self._marshal(queries, managers)
-        if window >= 1:
-            outs, docs, scores = _topdocs_outputs(n, int(window))
-        else:
-            outs = (_lib.TopDocs * n)()
-            docs = np.zeros((n, 1), dtype=np.int32)
-            scores = np.zeros((n, 1), dtype=np.float32)
-            for qi in range(n):
-                outs[qi].capacity = window
-                outs[qi].docs = docs[qi].ctypes.data_as(C.POINTER(C.c_int32))
-                outs[qi].scores = scores[qi].ctypes.data_as(C.POINTER(C.c_float))
+        h = _outputs(n, max(int(window), 1), int(window))
         _lib.check(getattr(_lib.load(), entry)(
-            self.ctx._h, self._segs, self._bases, len(self.leaves), m.queries, n, int(field), sim,
-            qv.ctypes.data, qv.shape[1], C.c_float(boost), float(query_weight), float(rescore_weight), int(window), outs))
-        return _topdocs_lists(outs, docs, scores, n)
+            self.ctx._h, self._segs, self._bases, len(self.leaves), m.queries, n, int(field), sim, qv.ctypes.data, qv.shape[1],
+            C.c_float(boost), float(query_weight), float(rescore_weight), int(window), *(() if dist_mode is None else (int(dist_mode),)), h.outs))
+        return h.lists(none_if_negative=dist_mode is not None)
 
     def dist_search_hybrid_batch(self, queries: Sequence[Query], managers: Sequence[TopScoreDocCollectorManager], field: int,
                                  similarity: str, query_vectors: np.ndarray, window: int, query_weight: float = 1.0,
                                  rescore_weight: float = 1.0, boost: float = 1.0, mode: int = EXCHANGE_ALLGATHER) -> List[Optional[TopDocs]]:
         """The hybrid over docid-range shards (nrtgpu_dist_search_hybrid_batch): this rank's leaves; every rank passes the same
         queries and query vectors."""
-        n = len(queries)
-        qv = np.ascontiguousarray(np.atleast_2d(query_vectors), dtype=np.float32)
-        if qv.shape[0] != n:
-            raise ValueError("one query vector per query")
-        m = self._marshal(queries, managers)
-        outs = (_lib.TopDocs * n)()
-        docs = np.zeros((n, max(window, 1)), dtype=np.int32)
-        scores = np.zeros((n, max(window, 1)), dtype=np.float32)
-        for qi in range(n):
-            outs[qi].capacity = window
-            outs[qi].docs = docs[qi].ctypes.data_as(C.POINTER(C.c_int32))
-            outs[qi].scores = scores[qi].ctypes.data_as(C.POINTER(C.c_float))
-        _lib.check(_lib.load().nrtgpu_dist_search_hybrid_batch(
-            self.ctx._h, self._segs, self._bases, len(self.leaves), m.queries, n, int(field), self.SIMILARITY[similarity],
-            qv.ctypes.data, qv.shape[1], C.c_float(boost), float(query_weight), float(rescore_weight), int(window), int(mode), outs))
-        return [None if outs[qi].total_hits < 0 else
-                TopDocs(docs[qi, : outs[qi].n_hits].copy(), scores[qi, : outs[qi].n_hits].copy(), int(outs[qi].total_hits),
-                        bool(outs[qi].total_hits_is_lower_bound)) for qi in range(n)]
+        return self._hybrid("nrtgpu_dist_search_hybrid_batch", queries, managers, field, self.SIMILARITY[similarity],
+                            np.ascontiguousarray(np.atleast_2d(query_vectors), dtype=np.float32), window, query_weight, rescore_weight, boost, mode)
 
 
 # ---- pre-marshalled batches (bench / serving loop: no Python work inside the timed region) --------
@@ -1294,13 +1129,8 @@ class PreparedBatch:
         self.n = len(queries)
         self._m = searcher._marshal(queries, managers)
         self.k = max(int(m.num_hits) for m in managers)
-        self._outs = (_lib.TopDocs * self.n)()
-        self.docs = np.zeros((self.n, self.k), dtype=np.int32)
-        self.scores = np.zeros((self.n, self.k), dtype=np.float32)
-        for qi in range(self.n):
-            self._outs[qi].capacity = self.k
-            self._outs[qi].docs = self.docs[qi].ctypes.data_as(C.POINTER(C.c_int32))
-            self._outs[qi].scores = self.scores[qi].ctypes.data_as(C.POINTER(C.c_float))
+        self._holder = _Outputs(self.n, self.k).begin(self.k)   # this batch's own: it lives across calls
+        self._outs, self.docs, self.scores = self._holder.outs, self._holder.docs, self._holder.scores
 
     def run(self) -> None:
         s = self.searcher
@@ -1345,9 +1175,7 @@ class PreparedBatch:
         _lib.check(_lib.load().nrtgpu_pending_wait(C.c_void_p(handle)))
 
     def topdocs(self, qi: int) -> TopDocs:
-        o = self._outs[qi]
-        return TopDocs(self.docs[qi, : o.n_hits].copy(), self.scores[qi, : o.n_hits].copy(), int(o.total_hits),
-                       bool(o.total_hits_is_lower_bound))
+        return self._holder.topdocs(qi)
 
 
 class PreparedMerge:
@@ -1361,13 +1189,8 @@ class PreparedMerge:
         self._ks = np.ascontiguousarray(ks, dtype=np.int32)
         self._thr = np.ascontiguousarray(thresholds, dtype=np.int32)
         kmax = int(self._ks.max())
-        self._outs = (_lib.TopDocs * self.n)()
-        self.docs = np.zeros((self.n, kmax), dtype=np.int32)
-        self.scores = np.zeros((self.n, kmax), dtype=np.float32)
-        for qi in range(self.n):
-            self._outs[qi].capacity = kmax
-            self._outs[qi].docs = self.docs[qi].ctypes.data_as(C.POINTER(C.c_int32))
-            self._outs[qi].scores = self.scores[qi].ctypes.data_as(C.POINTER(C.c_float))
+        self._holder = _Outputs(self.n, kmax).begin(kmax)   # this merge's own: it lives across calls
+        self._outs, self.docs, self.scores = self._holder.outs, self._holder.docs, self._holder.scores
 
     def run(self, d_keys: int, d_counts: int, d_hits: int) -> None:
         _lib.check(_lib.load().nrtgpu_merge_topk_device(
@@ -1407,9 +1230,7 @@ class PreparedMerge:
         return self._outs[qi].total_hits >= 0
 
     def topdocs(self, qi: int) -> TopDocs:
-        o = self._outs[qi]
-        return TopDocs(self.docs[qi, : o.n_hits].copy(), self.scores[qi, : o.n_hits].copy(), int(o.total_hits),
-                       bool(o.total_hits_is_lower_bound))
+        return self._holder.topdocs(qi)
 
 
 def merge_topk_device(ctx: GpuContext, n_lists: int, n_queries: int, k_stride: int, d_keys: int, d_counts: int,
@@ -1491,15 +1312,10 @@ def blend(retriever_docs: Sequence[np.ndarray], retriever_scores: Optional[Seque
     sp = (C.c_void_p * max(n, 1))(*[s_.ctypes.data for s_ in scs]) if scs is not None else None
     counts = np.asarray([len(d) for d in docs], dtype=np.int32)
     b = np.ascontiguousarray(boosts, dtype=np.float32) if boosts is not None else None
-    cap = max(int(top_hits), 1)
-    od, os_ = np.zeros(cap, np.int32), np.zeros(cap, np.float32)
-    out = _lib.TopDocs()
-    out.capacity = cap
-    out.docs = od.ctypes.data_as(C.POINTER(C.c_int32))
-    out.scores = os_.ctypes.data_as(C.POINTER(C.c_float))
+    h = _outputs(1, max(int(top_hits), 1))
     _lib.check(_lib.load().nrtgpu_blend(n, dp, sp, counts.ctypes.data, b.ctypes.data if b is not None else None,
-                                        0 if mode == "rrf" else 1, int(k), int(start_hit), int(top_hits), C.byref(out)))
-    return TopDocs(od[: out.n_hits].copy(), os_[: out.n_hits].copy(), int(out.total_hits), bool(out.total_hits_is_lower_bound))
+                                        0 if mode == "rrf" else 1, int(k), int(start_hit), int(top_hits), h.outs))
+    return h.topdocs(0)
 
 
 # ---- blenders (multi-retriever; O(k) host work that stays in Java in the reference) ----------------
