@@ -124,6 +124,19 @@ int  nrtgpu_segment_add_vectors(nrtgpu_seg* seg, int32_t field_id, int32_t dim, 
  * NRTGPU_ERR_INVALID_ARG). */
 int  nrtgpu_segment_add_byte_vectors(nrtgpu_seg* seg, int32_t field_id, int32_t dim, int32_t n,
                                      const int32_t* ord_to_doc, const int8_t* row_major);
+/* A per-doc value column of one field: ONE 32-bit value per doc (IntFieldDef / FloatFieldDef doc values; for a multi-valued
+ * field the caller uploads the selector's pick -- SortedNumericSelector MIN / MAX, src/main/java/com/yelp/nrtsearch/server/field/
+ * properties/Sortable.java:34-45 -- as a column of its own field id).  docs: the n docs that have a value, ascending leaf docids
+ * (NULL: doc i = i, n == max_doc); values: n x 4 bytes of the kind.  Docs not listed have no value.  The column is independent of
+ * whatever else the field id holds (postings, norms); before the seal only (after: NRTGPU_ERR_STATE); forks share it;
+ * nrtgpu_segment_device_bytes counts it.  Resident as one order-preserving 32-bit code per doc plus one bit per doc where some
+ * doc lacks a value.  Sorting is its first reader (nrtgpu_search_sorted_batch).  NRTGPU_ERR_INVALID_ARG: kind out of range,
+ * n < 0 or n > max_doc, docs not strictly ascending or outside [0, max_doc), docs == NULL with n != max_doc, values == NULL with
+ * n > 0, a second column on the field.  Out of scope: 64-bit values, updatable doc values. */
+#define NRTGPU_DOCVALUES_INT32 0    /* IntFieldDef: SortField.Type.INT */
+#define NRTGPU_DOCVALUES_FLOAT32 1  /* FloatFieldDef: SortField.Type.FLOAT */
+int  nrtgpu_segment_add_doc_values(nrtgpu_seg* seg, int32_t field_id, int32_t kind, int32_t n, const int32_t* docs,
+                                   const void* values);
 /* builds the per-term doc-range tables; the segment becomes searchable */
 int  nrtgpu_segment_seal(nrtgpu_seg* seg);
 /* leaf.getLiveDocs() as 64-bit words, bit d set = doc d live; NULL => all live.  May be called
@@ -919,6 +932,71 @@ int  nrtgpu_text_knn_value(int32_t text_nested, int32_t text_matched, uint64_t f
 /* The list checks and the exactness test above for one (q, kc) under the scale fx_E: 1 exact, 0 not, negative: the status the
  * search would return for the lists (of q only its clauses' weights and its masks are read).  Needs no device. */
 int  nrtgpu_text_knn_exact(const nrtgpu_bm25_query* q, const nrtgpu_knn_clauses* kc, int32_t fx_E);
+
+/* ---------------------------------------------------------------------------------------------
+ * Sort by field: a text query's hits ordered by an int or float doc value column (nrtgpu_segment_add_doc_values) instead of by
+ * score -- a request with a `querySort` (src/main/java/com/yelp/nrtsearch/server/search/SearchRequestProcessor.java:610 picks
+ * search/collectors/SortFieldCollector.java:44-74: TopFieldCollectorManager(sort, topHits, searchAfter, totalHitsThreshold); the
+ * sort from search/sort/SortParser.java:54-92 and field/NumberFieldDef.java:266-278).  ONE sort level over a 32-bit column.
+ * Ranking is Sort(field) with Lucene's implicit docid tie break [Lucene-recall]: by value in the sort's direction (Integer.compare /
+ * Float.compare: -0.0 < +0.0, NaN above +inf), equal values by global docid ascending whatever `reverse` is.  A doc with no value,
+ * or in a leaf without the column, takes `missing_bits` as its value.  value_bits of a hit is the value it sorted as (for such a
+ * doc the missing value, as in FieldDoc.fields; a NaN comes back as 0x7FC00000).
+ * Matching: scores are not computed, only which docs match.  All clauses SHOULD: a doc is a hit iff at least
+ * max(1, min_should_match) clauses match it (duplicate clauses count each); all clauses MUST: all of them match it.  The accept
+ * set -- liveDocs, filter_mask / must_not_mask / more_* -- works as on the other routes.  The clauses' weights and norm caches
+ * are not read for the result but must be valid: the queries are planned through the exhaustive plan.
+ * Paging: the cursor lives in the sort (has_after, after_doc, after_bits: the last hit of the previous page); a hit is collected
+ * iff it ranks strictly behind the cursor; hits of earlier pages still count in total_hits.  queries[i].has_after must be 0.
+ * total_hits is always the exact number of hits; total_hits_is_lower_bound follows the reference's per-slice rule as on the
+ * exhaustive route (some slice collected more than max(totalHitsThreshold, numHits) hits and numHits hits were returned), which
+ * is TopFieldCollector's rule as well [Lucene-recall]; Lucene's own count under that flag is lower (it skips non-competitive
+ * docs), ours is a valid value for GREATER_THAN_OR_EQUAL_TO.  Slicing, thread slices, deadlines, diagnostics (items_scan) and
+ * statistics (scan_*, fixed_point_launches) work as in nrtgpu_search_function_score_batch.
+ * Refusals, each with a reason in nrtgpu_last_error naming the query:
+ *   NRTGPU_ERR_INVALID_ARG  NULL arguments; reverse or has_after outside 0..1; after_doc < 0; queries[i].has_after != 0; leaves of
+ *                           the call that hold the field's column under different kinds; whatever nrtgpu_search_bm25_batch
+ *                           refuses of queries[i] with that status
+ *   NRTGPU_ERR_UNSUPPORTED  the column is resident on no leaf of the call (its kind is then unknown); disjunction_max != 0 or
+ *                           tie_breaker != 0 (pass the clauses as a plain disjunction: scores are not read); MUST next to SHOULD
+ *                           clauses; min_competitive_score != 0; k > NRTGPU_MAX_K; a mask that is not resident; a context with
+ *                           NRTGPU_FLAG_PACKED_POSTINGS or NRTGPU_FLAG_NO_FIXED_POINT, a batch whose queries do not all pass
+ *                           the fixed-point analysis -- the final-score routes' refusals, kept as they are: a KNOWN LIMIT, they
+ *                           are stricter than a route that reads no score needs
+ * Out of scope: 64-bit columns (LONG / DATE_TIME / DOUBLE need keys wider than the top-k's 64 bits -- the next step, and why this
+ * cannot serve "newest first" yet); STRING ordinals; LAT_LON distance; virtual (script) fields; more than one sort level; `score`
+ * or `docid` as a sort level; scores beside the values; a match-all query under a sort; dismax / multi-match text under a sort;
+ * updatable doc values; the coalesced, device-resident and nrtgpu_dist_* forms; the Java shim, which does not bind this yet.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct {
+  int32_t  field_id;      /* the column */
+  int32_t  reverse;       /* SortField.getReverse(): 0 ascending (smallest first), 1 descending */
+  uint32_t missing_bits;  /* SortField.setMissingValue: what a doc without a value sorts AS, bits of the column's kind, taken
+                           * verbatim (NumberFieldDef.java:275-276 passes MAX_VALUE / +inf for missingLast whatever `reverse` is:
+                           * the caller does that mapping) */
+  int32_t  has_after;     /* FieldDoc searchAfter (SortParser.parseLastHitInfo, :132-144) */
+  int32_t  after_doc;     /* global docid */
+  uint32_t after_bits;    /* the last hit's sort value */
+} nrtgpu_field_sort;      /* 24 bytes */
+typedef struct {          /* nrtgpu_topdocs with the hit's sort value where the score is (TopFieldCollector leaves score NaN) */
+  int32_t   n_hits;                     /* out: hits written, <= k */
+  int32_t   capacity;                   /* in : capacity of docs / value_bits (>= k) */
+  int32_t*  docs;                       /* out: global docids, in the sort's order */
+  uint32_t* value_bits;                 /* out: the value each hit sorted as, bits of the column's kind */
+  int64_t   total_hits;                 /* out: live matching docs, exact */
+  int32_t   total_hits_is_lower_bound;  /* out: 1 == GREATER_THAN_OR_EQUAL_TO (the per-slice rule above) */
+} nrtgpu_fielddocs;
+/* n_queries sorted searches over the same leaves in one device pass; sorts[i] orders queries[i] */
+int  nrtgpu_search_sorted_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                const nrtgpu_bm25_query* queries, const nrtgpu_field_sort* sorts, int32_t n_queries,
+                                nrtgpu_fielddocs* out);
+/* The eligibility test alone: NRTGPU_OK if the search above would run (q, s) over these leaves, else the status it would return
+ * with the reason in nrtgpu_last_error.  No device work. */
+int  nrtgpu_sorted_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query* q,
+                             const nrtgpu_field_sort* s);
+/* The high word of the key a value sorts under (kind: NRTGPU_DOCVALUES_*), exposed for the tests: needs no device; it is the
+ * very function the kernel compiles.  Larger = earlier in the sort's order.  kind or reverse outside 0..1: NRTGPU_ERR_INVALID_ARG. */
+int  nrtgpu_sort_value_code(int32_t kind, int32_t reverse, uint32_t value_bits, uint32_t* out_key_high);
 
 /* ---------------------------------------------------------------------------------------------
  * Host-side restatements the Java shim would otherwise take from Lucene objects

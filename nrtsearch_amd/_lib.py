@@ -35,6 +35,8 @@ NRTGPU_MAX_GROUPS = 8
 NRTGPU_GROUPS_SUM_OF_MAX = 0
 NRTGPU_GROUPS_MAX_OF_SUM = 1
 NRTGPU_MAX_KNN_LISTS = 8
+NRTGPU_DOCVALUES_INT32 = 0
+NRTGPU_DOCVALUES_FLOAT32 = 1
 
 # every symbol include/nrtgpu.h declares (tests/test_abi.py checks the header against this list)
 ABI_SYMBOLS = [
@@ -59,6 +61,7 @@ ABI_SYMBOLS = [
     "nrtgpu_search_multi_match_batch", "nrtgpu_multi_match_supported", "nrtgpu_multi_match_value",
     "nrtgpu_search_function_score_multi_match_batch", "nrtgpu_function_score_multi_match_supported", "nrtgpu_function_score_multi_match_value",
     "nrtgpu_search_text_knn_batch", "nrtgpu_text_knn_supported", "nrtgpu_text_knn_value", "nrtgpu_text_knn_exact",
+    "nrtgpu_segment_add_doc_values", "nrtgpu_search_sorted_batch", "nrtgpu_sorted_supported", "nrtgpu_sort_value_code",
 ]
 # what include/nrtgpu_dev.h adds: test hooks and measurement helpers of the development library (libnrtgpu_dev.so) only
 DEV_SYMBOLS = [
@@ -118,6 +121,17 @@ class KnnClauses(C.Structure):   # nrtgpu_knn_clauses
 class TopDocs(C.Structure):
     _fields_ = [("n_hits", C.c_int32), ("capacity", C.c_int32), ("docs", C.POINTER(C.c_int32)),
                 ("scores", C.POINTER(C.c_float)), ("total_hits", C.c_int64),
+                ("total_hits_is_lower_bound", C.c_int32)]
+
+
+class FieldSort(C.Structure):   # nrtgpu_field_sort
+    _fields_ = [("field_id", C.c_int32), ("reverse", C.c_int32), ("missing_bits", C.c_uint32), ("has_after", C.c_int32),
+                ("after_doc", C.c_int32), ("after_bits", C.c_uint32)]
+
+
+class FieldDocs(C.Structure):   # nrtgpu_fielddocs: nrtgpu_topdocs with the hits' sort values where the scores are
+    _fields_ = [("n_hits", C.c_int32), ("capacity", C.c_int32), ("docs", C.POINTER(C.c_int32)),
+                ("value_bits", C.POINTER(C.c_uint32)), ("total_hits", C.c_int64),
                 ("total_hits_is_lower_bound", C.c_int32)]
 
 
@@ -231,6 +245,10 @@ def _open(path: str) -> C.CDLL:
     L.nrtgpu_text_knn_supported.argtypes = [vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(KnnClauses)]
     L.nrtgpu_text_knn_value.argtypes = [i32, i32, C.c_uint64, i32, C.c_double, vp]
     L.nrtgpu_text_knn_exact.argtypes = [C.POINTER(Bm25Query), C.POINTER(KnnClauses), i32]
+    L.nrtgpu_segment_add_doc_values.argtypes = [vp, i32, i32, i32, vp, vp]
+    L.nrtgpu_search_sorted_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(FieldSort), i32, C.POINTER(FieldDocs)]
+    L.nrtgpu_sorted_supported.argtypes = [vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(FieldSort)]
+    L.nrtgpu_sort_value_code.argtypes = [i32, i32, C.c_uint32, vp]
     L.nrtgpu_rescore_vectors.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, f32, vp, vp, i32, C.c_double, C.c_double, i32,
                                          C.POINTER(TopDocs)]
     L.nrtgpu_search_hybrid_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), i32, i32, i32, vp, i32, f32,

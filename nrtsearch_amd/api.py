@@ -143,6 +143,46 @@ class MultiMatchQuery:
 GROUP_SHAPES = {"cross_fields": _lib.NRTGPU_GROUPS_SUM_OF_MAX, "best_fields": _lib.NRTGPU_GROUPS_MAX_OF_SUM}   # nrtgpu_clause_groups.shape
 
 
+DOC_VALUE_KINDS = {"int": (_lib.NRTGPU_DOCVALUES_INT32, np.dtype(np.int32)), "float": (_lib.NRTGPU_DOCVALUES_FLOAT32, np.dtype(np.float32))}
+
+
+def _value_bits(kind: str, value) -> int:
+    """The 32 bits of a doc value of the kind (an int32 / a float32)."""
+    return int(np.array([value], dtype=DOC_VALUE_KINDS[kind][1]).view(np.uint32)[0])
+
+
+@dataclasses.dataclass(frozen=True)
+class SortField:
+    """SortField(field, Type.INT / Type.FLOAT, reverse) over a doc value column (GpuSegment.add_doc_values), with
+    SortField.setMissingValue: `missing` is the value a doc without one sorts AS, whatever `reverse` is (NumberFieldDef.java:275-276
+    passes MAX_VALUE / +inf for missingLast: the caller does that mapping)."""
+
+    field: int
+    kind: str = "int"
+    reverse: bool = False
+    missing: Union[int, float] = 0
+
+
+@dataclasses.dataclass
+class FieldDoc:
+    """A hit of a sorted search as a searchAfter cursor: its global docid and the value it sorted as."""
+
+    doc: int
+    value: Union[int, float]
+
+
+@dataclasses.dataclass
+class TopFieldDocs:
+    docs: np.ndarray            # int32 global docids, in the sort's order
+    values: np.ndarray          # int32 / float32: the value each hit sorted as (the missing value for a doc without one)
+    total_hits: int
+    relation_gte: bool          # True == TotalHits.Relation.GREATER_THAN_OR_EQUAL_TO
+
+    @property
+    def value_bits(self) -> np.ndarray:
+        return self.values.view(np.uint32)
+
+
 class UnsupportedQuery(Exception):
     """The rewritten query is not eligible for the device route: run the CPU (Lucene) path."""
 
@@ -549,6 +589,22 @@ class GpuSegment:
             op = ord_to_doc.ctypes.data
         _lib.check(_lib.load().nrtgpu_segment_add_byte_vectors(self._h, int(field), vectors.shape[1], vectors.shape[0],
                                                                op, vectors.ctypes.data))
+
+    def add_doc_values(self, field: int, kind: str, values: np.ndarray, docs: Optional[np.ndarray] = None) -> None:
+        """A per-doc value column of the field (nrtgpu_segment_add_doc_values): kind "int" (int32) or "float" (float32), one value
+        per listed doc (docs: ascending leaf docids; None: one value per doc of the segment).  No silent cast: the array's dtype
+        must be the kind's, or uint32 for the kind's raw bits."""
+        values = np.ascontiguousarray(values).reshape(-1)
+        if values.dtype not in (DOC_VALUE_KINDS[kind][1], np.dtype(np.uint32)):
+            raise TypeError(f"doc values of kind {kind!r} must be {DOC_VALUE_KINDS[kind][1]} (or uint32 bits), got {values.dtype}")
+        dp = None
+        if docs is not None:
+            docs = np.ascontiguousarray(docs, dtype=np.int32).reshape(-1)
+            if docs.shape[0] != values.shape[0]:
+                raise ValueError(f"{docs.shape[0]} docs, {values.shape[0]} values")
+            dp = docs.ctypes.data
+        _lib.check(_lib.load().nrtgpu_segment_add_doc_values(self._h, int(field), DOC_VALUE_KINDS[kind][0], values.shape[0], dp,
+                                                             values.ctypes.data if values.shape[0] else None))
 
     def seal(self) -> None:
         _lib.check(_lib.load().nrtgpu_segment_seal(self._h))
@@ -1258,6 +1314,56 @@ def slices(max_docs: Sequence[int], num_docs: Optional[Sequence[int]] = None, vi
     for i in range(n):
         out[sl[i]].append(i)
     return out, sh[:n].tolist()
+
+
+def _marshal_sorted(searcher: "GpuIndexSearcher", queries: Sequence[Query], managers: Sequence[TopScoreDocCollectorManager],
+                    sorts: Sequence[SortField], afters: Optional[Sequence[Optional[FieldDoc]]]):
+    """The queries and nrtgpu_field_sort per query of a sorted search.  A BooleanQuery of MUST clauses only goes down as MUST
+    clauses (the route counts them itself), not as the disjunction with minimumNumberShouldMatch = n the scoring routes take."""
+    if len(sorts) != len(queries) or (afters is not None and len(afters) != len(queries)):
+        raise ValueError(f"{len(sorts)} sorts / {None if afters is None else len(afters)} afters for {len(queries)} queries")
+    m = searcher._marshal(queries, managers)
+    fs = (_lib.FieldSort * len(queries))()
+    for qi, (query, sort) in enumerate(zip(queries, sorts)):
+        if sort.kind not in DOC_VALUE_KINDS:
+            raise UnsupportedQuery(f"a sort of kind {sort.kind!r}")
+        if isinstance(query, BooleanQuery) and query.must and not query.should and not isinstance(query.must[0], DisjunctionMaxQuery):
+            q = m.queries[qi]
+            for ti in range(q.n_terms):
+                q.terms[ti].occur = 1
+            q.min_should_match = 0
+        after = afters[qi] if afters is not None else None
+        fs[qi] = _lib.FieldSort(int(sort.field), int(bool(sort.reverse)), _value_bits(sort.kind, sort.missing), int(after is not None),
+                                int(after.doc) if after is not None else 0, _value_bits(sort.kind, after.value) if after is not None else 0)
+    m.keep.append(fs)
+    return m, fs
+
+
+def search_sorted_batch(searcher: "GpuIndexSearcher", queries: Sequence[Query], managers: Sequence[TopScoreDocCollectorManager],
+                        sorts: Sequence[SortField], afters: Optional[Sequence[Optional[FieldDoc]]] = None) -> List[TopFieldDocs]:
+    """Sorted searches (nrtgpu_search_sorted_batch): the hits of queries[i] ordered by sorts[i] (value in the sort's direction,
+    ties by docid ascending), the page behind afters[i] when that is given (managers[i].after stays None: the cursor of a sorted
+    search is a FieldDoc).  total_hits is exact; scores are not computed."""
+    m, fs = _marshal_sorted(searcher, queries, managers, sorts, afters)
+    n = len(m.queries)
+    h = _text_outputs(n, managers)
+    _lib.check(_lib.load().nrtgpu_search_sorted_batch(searcher.ctx._h, searcher._segs, searcher._bases, len(searcher.leaves), m.queries, fs, n,
+                                                      C.cast(h.outs, C.POINTER(_lib.FieldDocs))))
+    return [TopFieldDocs(t.docs, t.scores.view(DOC_VALUE_KINDS[sort.kind][1]), t.total_hits, t.relation_gte) for t, sort in zip(h.lists(), sorts)]
+
+
+def sorted_supported(searcher: "GpuIndexSearcher", query: Query, manager: TopScoreDocCollectorManager, sort: SortField,
+                     after: Optional[FieldDoc] = None) -> bool:
+    """The eligibility predicate alone (nrtgpu_sorted_supported)."""
+    m, fs = _marshal_sorted(searcher, [query], [manager], [sort], [after])
+    return _supported(_lib.load().nrtgpu_sorted_supported(searcher.ctx._h, searcher._segs, len(searcher.leaves), m.queries, fs))
+
+
+def sort_value_code(kind: str, reverse: bool, value_bits: int) -> int:
+    """The high word of the key a value sorts under (nrtgpu_sort_value_code: the function the kernel compiles).  No device."""
+    out = C.c_uint32(0)
+    _lib.check(_lib.load().nrtgpu_sort_value_code(DOC_VALUE_KINDS[kind][0], int(bool(reverse)), C.c_uint32(int(value_bits)), C.byref(out)))
+    return int(out.value)
 
 
 def debug_knn_bounds(sim: int, dim: int, q_norm2: float, q_l1: float, q_absmax: float, nv_max: float, nv_min: float,

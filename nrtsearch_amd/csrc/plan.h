@@ -655,4 +655,44 @@ __host__ __device__ inline float key_score(uint64_t key) {
 }
 __host__ __device__ inline uint32_t key_doc(uint64_t key) { return 0xFFFFFFFFu - (uint32_t)key; }
 
+// Sort by field (fieldsort.hip: bm25_field_sort_kernel; fieldsort.cpp): a text query's hits ordered by a per-doc value column of
+// the segment store (segment.cpp: nrtgpu_segment_add_doc_values) instead of by score.  The column is resident as the ascending
+// ORDER-PRESERVING CODE of the values: unsigned compares of codes order like Integer.compare / Float.compare of the values.
+//   kDocValuesInt32   : bits ^ 0x80000000
+//   kDocValuesFloat32 : NaNs canonicalised to 0x7FC00000, then negative floats ~bits, the others bits | 0x80000000:
+//                       -0.0 < +0.0, NaN above +inf (Float.compare)
+// The key of a hit is (sort_key_high << 32) | (0xFFFFFFFF - doc): the k LARGEST keys are the page, so an ascending sort
+// complements the code; equal values rank by docid ascending in both directions.  A key is never 0 (docids stay below 2^31).
+// The ONE statement of the coding: the upload, bm25_field_sort_kernel, the host's decode of the hits and
+// nrtgpu_sort_value_code all call these functions.
+constexpr int kDocValuesInt32 = 0, kDocValuesFloat32 = 1;
+__host__ __device__ inline uint32_t doc_value_code(int kind, uint32_t bits) {
+  if (kind == kDocValuesInt32) return bits ^ 0x80000000u;
+  if ((bits & 0x7FFFFFFFu) > 0x7F800000u) bits = 0x7FC00000u;
+  return (bits & 0x80000000u) != 0u ? ~bits : bits | 0x80000000u;
+}
+__host__ __device__ inline uint32_t doc_value_bits(int kind, uint32_t code) {   // the inverse (a NaN comes back canonical)
+  if (kind == kDocValuesInt32) return code ^ 0x80000000u;
+  return (code & 0x80000000u) != 0u ? code & 0x7FFFFFFFu : ~code;
+}
+__host__ __device__ inline uint32_t sort_key_high(uint32_t reverse, uint32_t code) { return reverse != 0u ? code : ~code; }
+__host__ __device__ inline uint64_t sort_key(uint32_t reverse, uint32_t code, uint32_t global_doc) {
+  return ((uint64_t)sort_key_high(reverse, code) << 32) | (uint64_t)(0xFFFFFFFFu - global_doc);
+}
+// One record per query of the call, and per part of the plan (same index as DPart) the column on the part's leaf.
+struct alignas(16) DSortQuery {
+  uint32_t reverse;        // SortField.getReverse()
+  uint32_t missing_code;   // what a doc without a value sorts as
+  uint32_t need;           // clauses a hit matches at least: max(1, minimumNumberShouldMatch), or all of them (MUST)
+  uint32_t has_after;
+  uint64_t after_key;      // searchAfter: only keys below it are collected (hits of earlier pages still count)
+  uint32_t pad[2];
+};
+static_assert(sizeof(DSortQuery) == 32, "DSortQuery layout");
+struct alignas(16) DSortPart {
+  const uint32_t* code;    // one code per doc, padded to whole sub-tiles; nullptr: the leaf lacks the column
+  const uint64_t* has;     // bit d: doc d has a value; nullptr: every doc has
+};
+static_assert(sizeof(DSortPart) == 16, "DSortPart layout");
+
 }  // namespace nrtgpu

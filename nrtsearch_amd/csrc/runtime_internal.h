@@ -5,7 +5,7 @@
 // plan), search.cpp (BM25 entry points, hybrid tail, merge), coalescer.h (request coalescing: the leader/follower mechanism behind
 // the single-query entries of search.cpp and vectors.cpp; standard library only), finalscore.cpp (the host
 // path of the final-score routes), funcscore.cpp (function-score queries), multimatch.cpp (multi-match queries),
-// vectors.cpp (exact kNN, vector rescoring).  Types the ABI names opaquely (nrtgpu_ctx, nrtgpu_seg) live in the global namespace;
+// fieldsort.cpp (a text query's hits sorted by a doc value column), vectors.cpp (exact kNN, vector rescoring).  Types the ABI names opaquely (nrtgpu_ctx, nrtgpu_seg) live in the global namespace;
 // everything else in nrtgpu::rt.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -59,6 +59,8 @@ void launch_bm25_multi_match_function_score(hipStream_t stream, const FinalScore
                                             const DFuncMasks* fmasks);
 // a text query beside knn clauses (knnclauses.hip): one DKnnPart per part, the listed docs and their knn_sum per (query, leaf)
 void launch_bm25_text_knn(hipStream_t stream, const FinalScoreArgs& a, const DKnnPart* kparts, const uint32_t* kdocs, const double* ksums);
+// sort by field (fieldsort.hip): one DSortQuery per query, one DSortPart per part
+void launch_bm25_field_sort(hipStream_t stream, const FinalScoreArgs& a, const DSortQuery* squeries, const DSortPart* sparts);
 #ifdef NRTGPU_DEV
 void launch_debug_wave_kth(hipStream_t stream, const uint64_t* keys, uint32_t n, uint32_t r, uint64_t* out);   // (maxscore.hip: topk_kth_wave on its own)
 void launch_debug_walk_value(hipStream_t stream, float weight, const uint32_t* freq, const uint32_t* norm, const float* table, int fx_scale,
@@ -336,6 +338,12 @@ struct FieldData {
   bool byte_rows = false;
   void* d_btiles = nullptr;
   int32_t* d_bnorm2 = nullptr;
+  // A per-doc value column (nrtgpu_segment_add_doc_values), independent of whatever else the field id holds: the values'
+  // order-preserving codes (plan.h: doc_value_code), one per doc, padded to whole sub-tiles, and which docs have a value
+  // (nullptr: every doc has).  dv_kind < 0: the field has no column.
+  uint32_t* d_dv_code = nullptr;
+  uint64_t* d_dv_has = nullptr;
+  int32_t dv_kind = -1;
   // rows whose doc is live under the segment's current liveDocs (what an exact vector query matches), counted on first
   // use per liveDocs version
   mutable std::atomic<int64_t> live_vec{-1};
@@ -345,7 +353,8 @@ struct FieldData {
       : d_norms(o.d_norms), max_norm(o.max_norm), dict(o.dict), flat(o.flat), groups(o.groups), d_vectors(o.d_vectors),
         d_vnorm2(o.d_vnorm2), d_ord_to_doc(o.d_ord_to_doc), h_ord_to_doc(o.h_ord_to_doc), dim(o.dim), n_vec(o.n_vec),
         vnorm2_max(o.vnorm2_max), d_sketch(o.d_sketch), sketch_state(o.sketch_state), sketch_scale(o.sketch_scale), absmax(o.absmax),
-        vnorm2_min(o.vnorm2_min), byte_rows(o.byte_rows), d_btiles(o.d_btiles), d_bnorm2(o.d_bnorm2) {}
+        vnorm2_min(o.vnorm2_min), byte_rows(o.byte_rows), d_btiles(o.d_btiles), d_bnorm2(o.d_bnorm2), d_dv_code(o.d_dv_code),
+        d_dv_has(o.d_dv_has), dv_kind(o.dv_kind) {}
 };
 
 }  // namespace rt

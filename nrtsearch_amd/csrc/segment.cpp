@@ -370,6 +370,66 @@ extern "C" int nrtgpu_segment_add_byte_vectors(nrtgpu_seg* seg, int32_t field_id
   return NRTGPU_OK;
 }
 
+// One 32-bit value per doc of a field (leaf.reader().getSortedNumericDocValues through the selector the sort names): coded on the
+// host (plan.h: doc_value_code) and resident as codes, one per doc, padded with zeros to whole sub-tiles -- the sorted-search
+// kernel reads a sub-tile's codes without a bounds test -- and the docs that have a value as 64-bit words, unless all have.
+extern "C" int nrtgpu_segment_add_doc_values(nrtgpu_seg* seg, int32_t field_id, int32_t kind, int32_t n, const int32_t* docs, const void* values) {
+  if (!seg) return fail(NRTGPU_ERR_INVALID_ARG, "seg is NULL");
+  if (seg->sealed) return fail(NRTGPU_ERR_STATE, "segment already sealed");
+  if (kind != NRTGPU_DOCVALUES_INT32 && kind != NRTGPU_DOCVALUES_FLOAT32) return fail(NRTGPU_ERR_INVALID_ARG, "doc values kind %d outside 0..1", kind);
+  if (n < 0 || n > seg->max_doc) return fail(NRTGPU_ERR_INVALID_ARG, "%d doc values for %d docs", n, seg->max_doc);
+  if (!docs && n != seg->max_doc) return fail(NRTGPU_ERR_INVALID_ARG, "docs is NULL: one value per doc (%d) expected, got %d", seg->max_doc, n);
+  if (n > 0 && !values) return fail(NRTGPU_ERR_INVALID_ARG, "values is NULL");
+  if (docs)
+    for (int32_t i = 0; i < n; ++i)
+      if (docs[i] < 0 || docs[i] >= seg->max_doc || (i > 0 && docs[i] <= docs[i - 1]))
+        return fail(NRTGPU_ERR_INVALID_ARG, "docs must be strictly ascending docids in [0,max_doc)");
+  {
+    const auto fit = seg->fields.find(field_id);
+    if (fit != seg->fields.end() && fit->second.dv_kind >= 0) return fail(NRTGPU_ERR_INVALID_ARG, "doc values of field %d already added", field_id);
+  }
+  HIP_TRY(hipSetDevice(seg->ctx->device));
+  const size_t padded = (size_t)seg->n_tiles * (size_t)kTileDocs;
+  std::vector<uint32_t> code(padded, 0u);
+  std::vector<uint64_t> has;
+  const uint32_t* v = (const uint32_t*)values;
+  if (n == seg->max_doc) {   // (ascending docids in [0, max_doc): doc i = i)
+    for (int32_t i = 0; i < n; ++i) code[(size_t)i] = doc_value_code(kind, v[i]);
+  } else {
+    has.assign(padded / 64, 0ull);
+    for (int32_t i = 0; i < n; ++i) {
+      const uint32_t d = (uint32_t)docs[i];
+      code[d] = doc_value_code(kind, v[i]);
+      has[d >> 6] |= 1ull << (d & 63u);
+    }
+  }
+  void *d_code = nullptr, *d_has = nullptr;
+  if (int rc = dev_alloc(seg, &d_code, padded * 4)) return rc;
+  hipError_t e = hipMemcpy(d_code, code.data(), padded * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess && !has.empty()) {
+    if (int rc = dev_alloc(seg, &d_has, has.size() * 8)) {
+      (void)hipFree(d_code);
+      seg->device_bytes -= (int64_t)(padded * 4);
+      return rc;
+    }
+    e = hipMemcpy(d_has, has.data(), has.size() * 8, hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess) {
+    (void)hipFree(d_code);
+    seg->device_bytes -= (int64_t)(padded * 4);
+    if (d_has) {
+      (void)hipFree(d_has);
+      seg->device_bytes -= (int64_t)(has.size() * 8);
+    }
+    return fail(NRTGPU_ERR_HIP, "upload of the doc values of field %d failed: %s", field_id, hipGetErrorString(e));
+  }
+  FieldData& f = seg->fields[field_id];   // (set when everything is resident)
+  f.d_dv_code = (uint32_t*)d_code;
+  f.d_dv_has = (uint64_t*)d_has;
+  f.dv_kind = kind;
+  return NRTGPU_OK;
+}
+
 static int fold_live_docs(nrtgpu_seg* seg);
 
 // What the MaxScore route needs per term besides the columns (plan.h: DTermAux), built on the device from the sealed
@@ -912,6 +972,8 @@ SegCore::~SegCore() {
     if (f.d_btiles) (void)hipFree(f.d_btiles);
     if (f.d_bnorm2) (void)hipFree(f.d_bnorm2);
     if (f.d_ord_to_doc) (void)hipFree(f.d_ord_to_doc);
+    if (f.d_dv_code) (void)hipFree(f.d_dv_code);
+    if (f.d_dv_has) (void)hipFree(f.d_dv_has);
     for (auto& g : f.groups) {
       if (g.d_docids) (void)hipFree(g.d_docids);
       if (g.d_dict) (void)hipFree(g.d_dict);
