@@ -999,6 +999,74 @@ int  nrtgpu_sorted_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int
 int  nrtgpu_sort_value_code(int32_t kind, int32_t reverse, uint32_t value_bits, uint32_t* out_key_high);
 
 /* ---------------------------------------------------------------------------------------------
+ * Terms aggregation: a text query's hits counted per distinct value of an int or float doc value column
+ * (nrtgpu_segment_add_doc_values) -- the per-hit half of a `TermsCollector` over a numeric field
+ * (src/main/java/com/yelp/nrtsearch/server/search/collectors/additional/TermsCollectorManager.java;
+ * IntTermsCollectorManager.java:142-152 and FloatTermsCollectorManager.java:149-150: countsMap.addTo(value, 1) for every
+ * collected doc, ScoreMode.COMPLETE_NO_SCORES).  The call returns the WHOLE count map of each query; `size` and `BucketOrder`
+ * (reduce(), TermsCollectorManager.java:430-483) stay with the caller, because the reference's own order among equal counts is
+ * its hash map's iteration order and cannot be reproduced.  The call returns no hits: a request's top-k comes from whichever
+ * search entry serves it, and the two calls are independent.
+ * Which docs count: the sorted route's matching rule, word for word.  Scores are not computed, only which docs match.  All
+ * clauses SHOULD: a doc is a hit iff at least max(1, min_should_match) clauses match it (duplicate clauses count each); all
+ * clauses MUST: all of them match it.  Everything is tested inside the accept set -- liveDocs, filter_mask / must_not_mask /
+ * more_*.  The clauses' weights and norm caches are not read for the result but must be valid: the queries are planned through
+ * the exhaustive plan.  queries[i].k, has_after and totalHitsThreshold must be valid but are not read otherwise.
+ * What is counted: a hit with a value adds 1 to the bucket of that value.  A hit without a value, or in a leaf that lacks the
+ * column, adds to no bucket (docValues.size() == 0 in the reference).  total_hits counts every hit; hits_with_value is the sum
+ * of all counts.
+ * Bucket identity is the identity of the column's code: ints are bucketed by value, floats by Float.floatToIntBits -- every NaN
+ * falls in ONE bucket and reports as 0x7FC00000, -0.0 and +0.0 are TWO buckets (fastutil's Float2IntOpenHashMap equality
+ * [Lucene-recall: never checked against a JVM run]).
+ * Output order: buckets ascending in the kind's order (Integer.compare / Float.compare: -0.0 < +0.0, NaN above +inf), whatever
+ * order the device filled its tables in.
+ * Overflow: if the hits of a query hold MORE than max_buckets distinct values, the query reports overflowed = 1, n_buckets = 0
+ * and hits_with_value = -1; its value_bits / counts are unspecified, its total_hits stays exact, the other queries of the batch
+ * are unaffected; the caller sends that request to Lucene.  overflowed is exactly "distinct values > max_buckets".
+ * Workspace bound (a design limit): a query's device table has the power of two >= 2 x max_buckets slots (at least 2); the
+ * tables of ONE call may have 2^25 slots in all (256 MiB).  A batch of 256 queries may ask for the full 65536 buckets each.
+ * Slicing, thread slices, deadlines, diagnostics (items_scan) and statistics (scan_*, fixed_point_launches) work as in
+ * nrtgpu_search_sorted_batch.
+ * Refusals, each with a reason in nrtgpu_last_error naming the query -- the sorted route's table, same statuses and precedence:
+ *   NRTGPU_ERR_INVALID_ARG  NULL arguments; max_buckets outside 1..NRTGPU_MAX_TERM_BUCKETS; capacity < max_buckets, or NULL
+ *                           value_bits / counts; leaves of the call that hold the field's column under different kinds;
+ *                           whatever nrtgpu_search_bm25_batch refuses of queries[i] with that status; a call whose tables
+ *                           exceed the workspace bound above (the reason names the limit)
+ *   NRTGPU_ERR_UNSUPPORTED  the column is resident on no leaf of the call; disjunction_max != 0 or tie_breaker != 0; MUST next
+ *                           to SHOULD clauses; min_competitive_score != 0; k > NRTGPU_MAX_K; a mask that is not resident; a
+ *                           context with NRTGPU_FLAG_PACKED_POSTINGS or NRTGPU_FLAG_NO_FIXED_POINT, a batch whose queries do
+ *                           not all pass the fixed-point analysis -- the final-score routes' refusals, the KNOWN LIMIT they are
+ *                           on the sorted route
+ * Out of scope: LONG / DOUBLE columns; multi-valued fields; string and ordinal collectors (a single-valued string facet can be
+ * uploaded as a column of its global ordinals); script and virtual sources; nested collectors and NESTED_COLLECTOR order; the
+ * Filter / Min / Max / Sum / TopHits collectors; fusing the count into a scoring route; match-all, dismax and multi-match text;
+ * the coalesced, device-resident and nrtgpu_dist_* forms; the Java shim.
+ * --------------------------------------------------------------------------------------------- */
+#define NRTGPU_MAX_TERM_BUCKETS 65536
+typedef struct {
+  int32_t field_id;      /* the column, NRTGPU_DOCVALUES_INT32 or _FLOAT32 */
+  int32_t max_buckets;   /* 1 .. NRTGPU_MAX_TERM_BUCKETS: more distinct values among the hits and the query overflows */
+} nrtgpu_terms_count;    /* 8 bytes */
+typedef struct {
+  int32_t   n_buckets;        /* out: buckets written (0 when overflowed) */
+  int32_t   capacity;         /* in : capacity of value_bits / counts, >= max_buckets */
+  uint32_t* value_bits;       /* out: the buckets' values, bits of the column's kind, ascending in the kind's order */
+  int32_t*  counts;           /* out: hits per bucket, each >= 1 */
+  int64_t   total_hits;       /* out: live matching docs, exact */
+  int64_t   hits_with_value;  /* out: the sum of counts; -1 when overflowed */
+  int32_t   overflowed;       /* out: 1 == more than max_buckets distinct values */
+  int32_t   reserved;         /* out: 0 */
+} nrtgpu_term_counts;         /* 48 bytes */
+/* n_queries count maps over the same leaves in one device pass; terms[i] names the column and the bound of queries[i] */
+int  nrtgpu_count_terms_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                              const nrtgpu_bm25_query* queries, const nrtgpu_terms_count* terms, int32_t n_queries,
+                              nrtgpu_term_counts* out);
+/* The eligibility test alone: NRTGPU_OK if the call above would run (q, t) over these leaves (with an output of sufficient
+ * capacity), else the status it would return with the reason in nrtgpu_last_error.  No device work. */
+int  nrtgpu_count_terms_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query* q,
+                                  const nrtgpu_terms_count* t);
+
+/* ---------------------------------------------------------------------------------------------
  * Host-side restatements the Java shim would otherwise take from Lucene objects
  * (BM25Similarity.scorer(boost, collectionStats, termStats); SmallFloat; slices()).
  * --------------------------------------------------------------------------------------------- */

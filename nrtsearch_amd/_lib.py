@@ -37,6 +37,7 @@ NRTGPU_GROUPS_MAX_OF_SUM = 1
 NRTGPU_MAX_KNN_LISTS = 8
 NRTGPU_DOCVALUES_INT32 = 0
 NRTGPU_DOCVALUES_FLOAT32 = 1
+NRTGPU_MAX_TERM_BUCKETS = 65536
 
 # every symbol include/nrtgpu.h declares (tests/test_abi.py checks the header against this list)
 ABI_SYMBOLS = [
@@ -62,6 +63,7 @@ ABI_SYMBOLS = [
     "nrtgpu_search_function_score_multi_match_batch", "nrtgpu_function_score_multi_match_supported", "nrtgpu_function_score_multi_match_value",
     "nrtgpu_search_text_knn_batch", "nrtgpu_text_knn_supported", "nrtgpu_text_knn_value", "nrtgpu_text_knn_exact",
     "nrtgpu_segment_add_doc_values", "nrtgpu_search_sorted_batch", "nrtgpu_sorted_supported", "nrtgpu_sort_value_code",
+    "nrtgpu_count_terms_batch", "nrtgpu_count_terms_supported",
 ]
 # what include/nrtgpu_dev.h adds: test hooks and measurement helpers of the development library (libnrtgpu_dev.so) only
 DEV_SYMBOLS = [
@@ -133,6 +135,15 @@ class FieldDocs(C.Structure):   # nrtgpu_fielddocs: nrtgpu_topdocs with the hits
     _fields_ = [("n_hits", C.c_int32), ("capacity", C.c_int32), ("docs", C.POINTER(C.c_int32)),
                 ("value_bits", C.POINTER(C.c_uint32)), ("total_hits", C.c_int64),
                 ("total_hits_is_lower_bound", C.c_int32)]
+
+
+class TermsCount(C.Structure):   # nrtgpu_terms_count
+    _fields_ = [("field_id", C.c_int32), ("max_buckets", C.c_int32)]
+
+
+class TermCounts(C.Structure):   # nrtgpu_term_counts
+    _fields_ = [("n_buckets", C.c_int32), ("capacity", C.c_int32), ("value_bits", C.POINTER(C.c_uint32)), ("counts", C.POINTER(C.c_int32)),
+                ("total_hits", C.c_int64), ("hits_with_value", C.c_int64), ("overflowed", C.c_int32), ("reserved", C.c_int32)]
 
 
 class Diagnostics(C.Structure):   # nrtgpu_diagnostics
@@ -249,6 +260,8 @@ def _open(path: str) -> C.CDLL:
     L.nrtgpu_search_sorted_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(FieldSort), i32, C.POINTER(FieldDocs)]
     L.nrtgpu_sorted_supported.argtypes = [vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(FieldSort)]
     L.nrtgpu_sort_value_code.argtypes = [i32, i32, C.c_uint32, vp]
+    L.nrtgpu_count_terms_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(TermsCount), i32, C.POINTER(TermCounts)]
+    L.nrtgpu_count_terms_supported.argtypes = [vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(TermsCount)]
     L.nrtgpu_rescore_vectors.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, f32, vp, vp, i32, C.c_double, C.c_double, i32,
                                          C.POINTER(TopDocs)]
     L.nrtgpu_search_hybrid_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), i32, i32, i32, vp, i32, f32,

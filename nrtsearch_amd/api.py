@@ -1366,6 +1366,105 @@ def sort_value_code(kind: str, reverse: bool, value_bits: int) -> int:
     return int(out.value)
 
 
+@dataclasses.dataclass(frozen=True)
+class TermsCollector:
+    """A TermsCollector over a single-valued int or float field (source FIELD, order COUNT, no nested collectors): `field` names
+    the doc value column (GpuSegment.add_doc_values) of kind `kind`; `size` and `order_desc` are what the caller's reduce() applies
+    to the returned map (fill_bucket_result), the device does not read them."""
+
+    field: int
+    size: int
+    order_desc: bool = True
+    kind: str = "int"
+
+
+@dataclasses.dataclass
+class TermCounts:
+    """The count map of one query (nrtgpu_term_counts): the distinct values of its hits, ascending in the kind's order, and the
+    hits per value.  overflowed: the hits hold more than max_buckets distinct values -- no buckets, hits_with_value -1, total_hits
+    still exact; the request goes to the CPU path."""
+
+    values: np.ndarray          # int32 / float32 (a NaN bucket reads 0x7FC00000)
+    counts: np.ndarray          # int32
+    total_hits: int
+    hits_with_value: int
+    overflowed: bool
+
+    @property
+    def value_bits(self) -> np.ndarray:
+        return self.values.view(np.uint32)
+
+
+@dataclasses.dataclass
+class BucketResult:
+    buckets: List[Tuple[Union[int, float], int]]   # (key, count), best first
+    total_buckets: int
+    total_other_counts: int
+
+
+def fill_bucket_result(values, counts, size: int, order_desc: bool = True) -> BucketResult:
+    """TermsCollectorManager.fillBucketResultByCount over a returned count map: the `size` buckets with the largest (order_desc)
+    or smallest counts, best first; total_buckets = len(map); total_other_counts = the sum of the counts left out.  An empty map
+    or size <= 0 gives the empty result, as in the reference.  Ties are broken by value ascending (the map's order).  The
+    reference's ties follow its hash map's iteration order, so ANY order among equal counts at the cut is a valid answer; away
+    from ties the results are the reference's."""
+    keys = np.asarray(values).tolist()
+    cnts = np.asarray(counts).tolist()
+    if not keys or size <= 0:
+        return BucketResult([], 0, 0)
+    order = sorted(range(len(keys)), key=lambda i: (-cnts[i] if order_desc else cnts[i], i))
+    kept = order[:size]
+    return BucketResult([(keys[i], int(cnts[i])) for i in kept], len(keys), int(sum(cnts[i] for i in order[size:])))
+
+
+def _marshal_terms(searcher: "GpuIndexSearcher", queries: Sequence[Query], collectors: Sequence[TermsCollector], max_buckets,
+                   managers: Optional[Sequence[TopScoreDocCollectorManager]]):
+    """The queries and nrtgpu_terms_count per query of a terms aggregation (MUST-only queries as in _marshal_sorted)."""
+    n = len(queries)
+    if len(collectors) != n:
+        raise ValueError(f"{len(collectors)} collectors for {n} queries")
+    bounds = [int(max_buckets)] * n if np.isscalar(max_buckets) else [int(b) for b in max_buckets]
+    if len(bounds) != n:
+        raise ValueError(f"{len(bounds)} max_buckets for {n} queries")
+    for c in collectors:
+        if c.kind not in DOC_VALUE_KINDS:
+            raise UnsupportedQuery(f"a terms collector of kind {c.kind!r}")
+    mgrs = list(managers) if managers is not None else [TopScoreDocCollectorManager(1)] * n
+    m, _ = _marshal_sorted(searcher, queries, mgrs, [SortField(c.field, c.kind) for c in collectors], None)
+    tc = (_lib.TermsCount * n)()
+    for qi, (c, b) in enumerate(zip(collectors, bounds)):
+        tc[qi] = _lib.TermsCount(int(c.field), b)
+    m.keep.append(tc)
+    return m, tc, bounds
+
+
+def count_terms_batch(searcher: "GpuIndexSearcher", queries: Sequence[Query], collectors: Sequence[TermsCollector], max_buckets=4096,
+                      managers: Optional[Sequence[TopScoreDocCollectorManager]] = None) -> List[TermCounts]:
+    """Terms aggregations (nrtgpu_count_terms_batch): per query the whole map value -> hits of collectors[i].field over the hits
+    of queries[i]; max_buckets: one bound for all, or one per query.  No hits are returned: the request's top-k comes from a
+    search entry.  Apply size and order with fill_bucket_result."""
+    m, tc, bounds = _marshal_terms(searcher, queries, collectors, max_buckets, managers)
+    n = len(queries)
+    width = max([max(b, 1) for b in bounds], default=1)
+    bits = np.zeros((n, width), dtype=np.uint32)
+    counts = np.zeros((n, width), dtype=np.int32)
+    outs = (_lib.TermCounts * n)()
+    for qi in range(n):
+        outs[qi].capacity = max(bounds[qi], 0)
+        outs[qi].value_bits = C.cast(bits.ctypes.data + qi * width * 4, C.POINTER(C.c_uint32))
+        outs[qi].counts = C.cast(counts.ctypes.data + qi * width * 4, C.POINTER(C.c_int32))
+    _lib.check(_lib.load().nrtgpu_count_terms_batch(searcher.ctx._h, searcher._segs, searcher._bases, len(searcher.leaves), m.queries, tc, n, outs))
+    return [TermCounts(bits[qi, : o.n_buckets].view(DOC_VALUE_KINDS[c.kind][1]).copy(), counts[qi, : o.n_buckets].copy(), int(o.total_hits),
+                       int(o.hits_with_value), bool(o.overflowed)) for qi, (o, c) in enumerate(zip(outs, collectors))]
+
+
+def count_terms_supported(searcher: "GpuIndexSearcher", query: Query, collector: TermsCollector, max_buckets: int = 4096,
+                          manager: Optional[TopScoreDocCollectorManager] = None) -> bool:
+    """The eligibility predicate alone (nrtgpu_count_terms_supported)."""
+    m, tc, _ = _marshal_terms(searcher, [query], [collector], max_buckets, None if manager is None else [manager])
+    return _supported(_lib.load().nrtgpu_count_terms_supported(searcher.ctx._h, searcher._segs, len(searcher.leaves), m.queries, tc))
+
+
 def debug_knn_bounds(sim: int, dim: int, q_norm2: float, q_l1: float, q_absmax: float, nv_max: float, nv_min: float,
                      rows_absmax: float, score_boost: float = 1.0, m: float = 0.0, s: float = 0.0) -> dict:
     """Test hook of the development library (nrtgpu_debug_knn_bounds): the rounding bounds the exact float vector search certifies

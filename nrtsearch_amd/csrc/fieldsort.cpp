@@ -25,16 +25,12 @@ extern "C" int nrtgpu_sort_value_code(int32_t kind, int32_t reverse, uint32_t va
   return NRTGPU_OK;
 }
 
-namespace {
+namespace nrtgpu {
+namespace rt {
 
-// What is planned for the queries of a call: plain SHOULD disjunctions (the vectors own the copies' clauses).
-struct FlatQueries {
-  std::vector<nrtgpu_bm25_query> queries;
-  std::vector<std::vector<nrtgpu_term>> terms;
-};
-
+// ---- what the routes over a doc value column share (this file: sorted searches; termscount.cpp: the terms aggregation) ----------
 // The kind of the field's column over the leaves of the call; refusals by the header's table.
-int column_kind(const nrtgpu_seg* const* segs, int32_t n_segs, int32_t field_id, int qi, int* kind) {
+int doc_values_kind(const nrtgpu_seg* const* segs, int32_t n_segs, int32_t field_id, int qi, int* kind) {
   *kind = -1;
   for (int si = 0; si < n_segs; ++si) {
     const auto fit = segs[si]->fields.find(field_id);
@@ -45,6 +41,62 @@ int column_kind(const nrtgpu_seg* const* segs, int32_t n_segs, int32_t field_id,
   }
   return NRTGPU_OK;
 }
+
+// What both routes refuse of one query as unsupported (kind: doc_values_kind's; under: "a sort" / "a terms count"); *need: the
+// clauses a hit matches at least; the copy that is planned on the way.
+int doc_values_query(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query& q, int qi, int kind, int32_t field_id, const char* under,
+                     uint32_t* need, FlatQueries* flat) {
+  if (kind < 0) return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: no leaf of the call holds doc values of field %d", qi, field_id);
+  if (q.disjunction_max != 0 || q.tie_breaker != 0.0f)
+    return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: a DisjunctionMaxQuery under %s (pass its clauses as a plain disjunction: scores are not read)", qi, under);
+  int n_must = 0;
+  for (int t = 0; t < q.n_terms; ++t) n_must += q.terms[t].occur;
+  if (n_must != 0 && n_must != q.n_terms) return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: MUST next to SHOULD clauses under %s", qi, under);
+  if (q.min_competitive_score != 0.0f) return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: a min_competitive_score under %s", qi, under);
+  auto resident = [&](int32_t id, const char* what) -> int {
+    for (int si = 0; id != 0 && si < n_segs; ++si)
+      if (segs[si]->masks.find(id) == segs[si]->masks.end())
+        return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: %s mask %d is not resident on segment %d", qi, what, id, si);
+    return NRTGPU_OK;
+  };
+  if (int rc = resident(q.filter_mask, "filter")) return rc;
+  if (int rc = resident(q.must_not_mask, "must_not")) return rc;
+  for (int i = 0; i < q.n_more_filters; ++i)
+    if (int rc = resident(q.more_filters[i], "filter")) return rc;
+  for (int i = 0; i < q.n_more_must_not; ++i)
+    if (int rc = resident(q.more_must_not[i], "must_not")) return rc;
+  *need = n_must != 0 ? (uint32_t)q.n_terms : (uint32_t)std::max(q.min_should_match, 1);
+  nrtgpu_bm25_query f = q;
+  flat->terms.emplace_back(q.terms, q.terms + q.n_terms);
+  for (nrtgpu_term& t : flat->terms.back()) t.occur = 0;
+  f.min_should_match = 0;
+  flat->queries.push_back(f);
+  return NRTGPU_OK;
+}
+
+// The column of every part's leaf (field_ids: per query).  A part names its (query, leaf) pair by its first DTerm (HostPlan.qs_begin).
+int doc_values_parts(const nrtgpu_seg* const* segs, int32_t n_segs, const int32_t* field_ids, const HostPlan& hp, const char* route,
+                     std::vector<DSortPart>* out) {
+  out->assign(hp.parts.size(), DSortPart{nullptr, nullptr});
+  for (const DItem& it : hp.items) {
+    for (uint32_t pi = 0; pi < it.n_parts; ++pi) {
+      const DPart& p = hp.parts[it.part_begin + pi];
+      int32_t leaf = -1;
+      for (int32_t si = 0; si < n_segs && leaf < 0; ++si)
+        if (hp.qs_begin[(size_t)it.query * (size_t)n_segs + (size_t)si] == p.term_begin) leaf = si;
+      if (leaf < 0 || (uint32_t)segs[leaf]->max_doc != p.max_doc) return fail(NRTGPU_ERR_STATE, "%s: a part of query %u names no leaf", route, it.query);
+      const auto fit = segs[leaf]->fields.find(field_ids[it.query]);
+      if (fit == segs[leaf]->fields.end() || fit->second.dv_kind < 0) continue;   // no doc of the leaf has a value
+      (*out)[it.part_begin + pi] = DSortPart{fit->second.d_dv_code, fit->second.d_dv_has};
+    }
+  }
+  return NRTGPU_OK;
+}
+
+}  // namespace rt
+}  // namespace nrtgpu
+
+namespace {
 
 // What the route refuses of a call before anything is planned (the segments' content is held); the records and the copies that
 // are planned on the way.
@@ -61,65 +113,22 @@ int check_call(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, c
     if (s.has_after != 0 && s.after_doc < 0) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: after_doc %d", qi, s.after_doc);
     if (q.has_after != 0) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: the query's has_after must be 0 (the cursor of a sorted search lives in the sort)", qi);
     int kind = -1;
-    if (int rc = column_kind(segs, n_segs, s.field_id, qi, &kind)) return rc;
+    if (int rc = doc_values_kind(segs, n_segs, s.field_id, qi, &kind)) return rc;
     kinds->push_back(kind);
   }
   if (int rc = final_score_check_flags(ctx, "sorted")) return rc;
   for (int qi = 0; qi < n_queries; ++qi) {
-    const nrtgpu_bm25_query& q = queries[qi];
     const nrtgpu_field_sort& s = sorts[qi];
     const int kind = (*kinds)[(size_t)qi];
-    if (kind < 0) return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: no leaf of the call holds doc values of field %d", qi, s.field_id);
-    if (q.disjunction_max != 0 || q.tie_breaker != 0.0f)
-      return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: a DisjunctionMaxQuery under a sort (pass its clauses as a plain disjunction: scores are not read)", qi);
-    int n_must = 0;
-    for (int t = 0; t < q.n_terms; ++t) n_must += q.terms[t].occur;
-    if (n_must != 0 && n_must != q.n_terms) return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: MUST next to SHOULD clauses under a sort", qi);
-    if (q.min_competitive_score != 0.0f) return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: a sorted search with a min_competitive_score", qi);
-    auto resident = [&](int32_t id, const char* what) -> int {
-      for (int si = 0; id != 0 && si < n_segs; ++si)
-        if (segs[si]->masks.find(id) == segs[si]->masks.end())
-          return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: %s mask %d is not resident on segment %d", qi, what, id, si);
-      return NRTGPU_OK;
-    };
-    if (int rc = resident(q.filter_mask, "filter")) return rc;
-    if (int rc = resident(q.must_not_mask, "must_not")) return rc;
-    for (int i = 0; i < q.n_more_filters; ++i)
-      if (int rc = resident(q.more_filters[i], "filter")) return rc;
-    for (int i = 0; i < q.n_more_must_not; ++i)
-      if (int rc = resident(q.more_must_not[i], "must_not")) return rc;
     DSortQuery r{};
+    if (int rc = doc_values_query(segs, n_segs, queries[qi], qi, kind, s.field_id, "a sort", &r.need, flat)) return rc;
     r.reverse = (uint32_t)s.reverse;
     r.missing_code = doc_value_code(kind, s.missing_bits);
-    r.need = n_must != 0 ? (uint32_t)q.n_terms : (uint32_t)std::max(q.min_should_match, 1);
     r.has_after = (uint32_t)s.has_after;
     r.after_key = s.has_after ? sort_key(r.reverse, doc_value_code(kind, s.after_bits), (uint32_t)s.after_doc) : ~0ull;
     if (records) records->push_back(r);
-    nrtgpu_bm25_query f = q;
-    flat->terms.emplace_back(q.terms, q.terms + q.n_terms);
-    for (nrtgpu_term& t : flat->terms.back()) t.occur = 0;
-    f.min_should_match = 0;
-    flat->queries.push_back(f);
   }
   for (int qi = 0; qi < n_queries; ++qi) flat->queries[(size_t)qi].terms = flat->terms[(size_t)qi].data();   // (the vectors have settled)
-  return NRTGPU_OK;
-}
-
-// The column of every part's leaf.  A part names its (query, leaf) pair by its first DTerm (HostPlan.qs_begin).
-int sort_parts(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_field_sort* sorts, const HostPlan& hp, std::vector<DSortPart>* out) {
-  out->assign(hp.parts.size(), DSortPart{nullptr, nullptr});
-  for (const DItem& it : hp.items) {
-    for (uint32_t pi = 0; pi < it.n_parts; ++pi) {
-      const DPart& p = hp.parts[it.part_begin + pi];
-      int32_t leaf = -1;
-      for (int32_t si = 0; si < n_segs && leaf < 0; ++si)
-        if (hp.qs_begin[(size_t)it.query * (size_t)n_segs + (size_t)si] == p.term_begin) leaf = si;
-      if (leaf < 0 || (uint32_t)segs[leaf]->max_doc != p.max_doc) return fail(NRTGPU_ERR_STATE, "sorted: a part of query %u names no leaf", it.query);
-      const auto fit = segs[leaf]->fields.find(sorts[it.query].field_id);
-      if (fit == segs[leaf]->fields.end() || fit->second.dv_kind < 0) continue;   // every doc of the leaf sorts as the missing value
-      (*out)[it.part_begin + pi] = DSortPart{fit->second.d_dv_code, fit->second.d_dv_has};
-    }
-  }
   return NRTGPU_OK;
 }
 
@@ -150,7 +159,9 @@ extern "C" int nrtgpu_search_sorted_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* con
   HostPlan hp;
   if (int rc = final_score_plan(ctx, segs, doc_bases, n_segs, flat.queries.data(), n_queries, "sorted", hp)) return rc;
   std::vector<DSortPart> sparts;
-  if (int rc = sort_parts(segs, n_segs, sorts, hp, &sparts)) return rc;
+  std::vector<int32_t> field_ids((size_t)n_queries);
+  for (int qi = 0; qi < n_queries; ++qi) field_ids[(size_t)qi] = sorts[qi].field_id;
+  if (int rc = doc_values_parts(segs, n_segs, field_ids.data(), hp, "sorted", &sparts)) return rc;
   const PlanBytes extras[2] = {{records.data(), records.size() * sizeof(DSortQuery)}, {sparts.data(), sparts.size() * sizeof(DSortPart)}};
   nrtgpu_topdocs* pages = reinterpret_cast<nrtgpu_topdocs*>(out);   // (the layout is the same: the static_assert above)
   if (int rc = final_score_run(ctx, hp, queries, n_queries, pages, t0, extras, 2, [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {

@@ -35,29 +35,6 @@ struct SortSmem {
 };
 static_assert(sizeof(SortSmem) <= 160 * 1024, "the workgroup owns one CU's 160 KiB LDS");
 
-// The postings [lo, hi) of clause T, 4 x 64 at a time, the eight column loads of a lane in flight together (final_stream_clause
-// without the scores): +1 in the slot of every live posting inside the sub-tile.
-__device__ __forceinline__ void sort_count_clause(const DTerm* T, uint32_t lo, uint32_t hi, uint32_t base, uint32_t tile_len, uint32_t lane,
-                                                  uint64_t* acc) {
-  const uint64_t start = T->start;
-  const gu32_ptr docids = (gu32_ptr)T->docids + start, codes = (gu32_ptr)T->fnorm + start;
-  for (uint32_t p0 = lo; p0 < hi; p0 += 256u) {
-    uint32_t doc[4], code[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const uint32_t p = p0 + 64u * (uint32_t)u + lane;
-      const bool in = p < hi;
-      doc[u] = in ? docids[p] : 0xFFFFFFFFu;   // (past the range: a doc outside every sub-tile)
-      code[u] = in ? codes[p] : 0u;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const uint32_t off = doc[u] - base;   // a coarse cell's postings may lie outside the sub-tile (unsigned: below it wraps)
-      if (off < tile_len && !decode_score_code(code[u]).dead) atomicAdd((uint32_t*)&acc[off], 1u);   // (the slot's low word)
-    }
-  }
-}
-
 // The sweep's verdict on one doc: its key when it is a hit between theta and the cursor, else 0.  totalHits counts every hit,
 // also those an earlier page returned.  All lanes of the wave call.
 __device__ __forceinline__ uint64_t sort_candidate_key(bool hit, uint64_t doc_key, uint64_t theta, bool has_after, uint64_t after_key,
@@ -139,7 +116,7 @@ void bm25_field_sort_kernel(const DItem* __restrict__ items, const DPart* __rest
       for (uint32_t t = 0; t < n_terms; ++t) {
         const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)my_lo, (int)t), hi = (uint32_t)__builtin_amdgcn_readlane((int)my_hi, (int)t);
         if (lo >= hi) continue;   // uniform
-        sort_count_clause(part_terms + t, lo, hi, base, tile_len, lane, acc);
+        final_count_clause(part_terms + t, lo, hi, base, tile_len, lane, acc);
       }
 
       // ---- (2) sweep: slot lane + 64 j is doc base + 64 j + lane, i.e. bit `lane` of word j of the sub-tile's mask words

@@ -1,7 +1,9 @@
 // finalscore.cpp -- the host path the final-score routes share (funcscore.cpp: function-score queries, multimatch.cpp:
 // multi-match queries, funcscore_multimatch.cpp: the one around the other): their entry checks and refusals, the exhaustive plan, and everything from "the plan and the route's
 // records exist" to "out[], the diagnostics and the statistics are filled".  On the device: the existing plan expansion, then the
-// route's scorer (finalscore.hiph) over all items, then the existing merge and per-slice relation.
+// route's scorer (finalscore.hiph) over all items, then the existing merge and per-slice relation.  A route whose answer is not
+// a list of hits (termscount.cpp) asks for workspace bytes of its own, zeroed with the per-slice sums, and collects them itself
+// behind the wait (FinalScoreOwn); the routes that ask for none enqueue and copy what they always did.
 #include "runtime_internal.h"
 
 namespace nrtgpu {
@@ -40,7 +42,8 @@ int final_score_plan(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32
 // Plan upload, expansion, the route's scorer over all items, merge, per-slice relation: enqueued at once on the slot's stream.
 // The scorer wants the whole GPU like the two scorers of search.cpp and takes its turn among them on the device.
 static int enqueue_final_score(nrtgpu_ctx* ctx, Slot* slot, const HostPlan& hp, int32_t n_queries, const PlanBytes* extras, int n_extras,
-                               FinalScoreLaunch launch, uint64_t** out_keys, uint32_t** out_counts, uint64_t** out_hits) {
+                               FinalScoreLaunch launch, const FinalScoreOwn* own, uint64_t** out_keys, uint32_t** out_counts, uint64_t** out_hits,
+                               const char** d_own) {
   forget_foreign_hip_error();
   const size_t n_items = hp.items.size();
   PlanLayout L(hp, n_items, (size_t)n_queries, hp.k_stride);   // theta: zeros (no min_competitive_score on these routes), then the kernel's
@@ -51,6 +54,7 @@ static int enqueue_final_score(nrtgpu_ctx* ctx, Slot* slot, const HostPlan& hp, 
   if (int rc = slot->h_plan.reserve(plan_bytes)) return rc;
   if (int rc = slot->d_plan.reserve(plan_bytes)) return rc;
   const size_t o_ssum = L.work.take((size_t)n_queries * hp.n_slices * 4);    // hits per (query, searcher slice): zeroed per call
+  const size_t o_own = own ? L.work.take(own->work_bytes) : 0;                // the route's own output: zeroed with the sums
   if (int rc = slot->d_work.reserve(L.work.off)) return rc;
   char* hb = (char*)slot->h_plan.p;
   char* db = (char*)slot->d_plan.p;
@@ -81,6 +85,8 @@ static int enqueue_final_score(nrtgpu_ctx* ctx, Slot* slot, const HostPlan& hp, 
   a.item_counts = (uint32_t*)(wb + L.item_counts);
   a.item_hits = (uint64_t*)(wb + L.item_hits);
   a.k_stride = hp.k_stride;
+  a.own = own ? wb + o_own : nullptr;
+  a.own_user = own ? own->user : nullptr;
   {
     std::unique_lock<std::mutex> gpu(ctx->gpu_mu);
     if (ctx->last_turn) HIP_TRY(hipStreamWaitEvent(st, ctx->last_turn, 0));
@@ -100,11 +106,12 @@ static int enqueue_final_score(nrtgpu_ctx* ctx, Slot* slot, const HostPlan& hp, 
   *out_keys = (uint64_t*)(wb + L.out_keys);
   *out_counts = (uint32_t*)(wb + L.out_counts);
   *out_hits = (uint64_t*)(wb + L.out_hits);
+  *d_own = own ? wb + o_own : nullptr;
   return NRTGPU_OK;
 }
 
 int final_score_run(nrtgpu_ctx* ctx, const HostPlan& hp, const nrtgpu_bm25_query* queries, int32_t n_queries, nrtgpu_topdocs* out, double t0,
-                    const PlanBytes* extras, int n_extras, FinalScoreLaunch launch) {
+                    const PlanBytes* extras, int n_extras, FinalScoreLaunch launch, const FinalScoreOwn* own) {
   const double plan_ms = now_ms() - t0;
 
   Slot* slot = nullptr;
@@ -120,7 +127,8 @@ int final_score_run(nrtgpu_ctx* ctx, const HostPlan& hp, const nrtgpu_bm25_query
   uint64_t* d_keys = nullptr;
   uint32_t* d_counts = nullptr;
   uint64_t* d_hits = nullptr;
-  if (int rc = enqueue_final_score(ctx, slot, hp, n_queries, extras, n_extras, launch, &d_keys, &d_counts, &d_hits)) return rc;
+  const char* d_own = nullptr;
+  if (int rc = enqueue_final_score(ctx, slot, hp, n_queries, extras, n_extras, launch, own, &d_keys, &d_counts, &d_hits, &d_own)) return rc;
   HIP_TRY(hipMemcpyAsync(ho + o_k, d_keys, kb, hipMemcpyDeviceToHost, slot->stream));
   HIP_TRY(hipMemcpyAsync(ho + o_c, d_counts, cb, hipMemcpyDeviceToHost, slot->stream));
   HIP_TRY(hipMemcpyAsync(ho + o_h, d_hits, hb, hipMemcpyDeviceToHost, slot->stream));
@@ -131,6 +139,8 @@ int final_score_run(nrtgpu_ctx* ctx, const HostPlan& hp, const nrtgpu_bm25_query
   // (without the MaxScore route's lower bounds: the count is exact; the high bits of `hits` carry slice_relation_kernel's tag, and a
   // page shorter than numHits is EQUAL_TO)
   for (int qi = 0; qi < n_queries; ++qi) unpack_topdocs(keys + (size_t)qi * hp.k_stride, cnts[qi], hits[qi], queries[qi].k, 0, cnts[qi], &out[qi]);
+  if (own && own->collect)
+    if (int rc = own->collect(ctx, slot, d_own, own->user)) return rc;
   account(ctx, slot, hp, n_queries, plan_ms, t0, queue_ms);
   return NRTGPU_OK;
 }

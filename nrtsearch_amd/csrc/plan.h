@@ -493,6 +493,8 @@ struct FinalScoreArgs {
   uint32_t* item_counts;         // ... how many ...
   uint64_t* item_hits;           // ... and the hits counted there
   uint32_t k_stride;
+  void* own;                     // the route's own zeroed workspace bytes (finalscore.cpp: FinalScoreOwn), nullptr: the route asked for none
+  void* own_user;                // FinalScoreOwn.user: what the route's launcher and its collect() share on the host
 };
 
 // Function-score queries (funcscore.hip: bm25_function_score_kernel; funcscore.cpp): MultiFunctionScoreQuery over a BM25
@@ -694,5 +696,42 @@ struct alignas(16) DSortPart {
   const uint64_t* has;     // bit d: doc d has a value; nullptr: every doc has
 };
 static_assert(sizeof(DSortPart) == 16, "DSortPart layout");
+
+// Terms aggregation (termscount.hip: bm25_terms_count_kernel, terms_compact_kernel; termscount.cpp): a query's hits counted per
+// distinct value of a doc value column.  A bucket is a column CODE (doc_value_code: ints by value, floats by floatToIntBits with
+// every NaN in one bucket).  Count tables are open-addressed, a slot one 64-bit word (count << 32) | code, 0 = empty (a slot
+// that is in use counts at least 1): a workgroup's table in LDS as a combiner, the query's table in global memory, which the
+// query's items share.  The home slot of a code is the top bits of code * kTermsHashMul (codes that agree in their low bits
+// spread); probing is linear and BOUNDED: kTermsLdsProbe steps in LDS (then the value goes straight to the global table), the
+// table's capacity in global memory (then the query's overflow flag is raised).  Every slot claimed in a query's global table
+// counts in DTermsState.claimed: a query overflows iff its hits hold more than max_buckets distinct values, whatever the load.
+constexpr int kTermsLdsSlots = 8192;          // 64 KiB of the workgroup's LDS
+constexpr int kTermsLdsShift = 32 - 13;       // home slot = hash >> shift
+constexpr int kTermsLdsProbe = 8;
+static_assert((1 << (32 - kTermsLdsShift)) == kTermsLdsSlots, "the LDS table's hash shift");
+constexpr uint32_t kTermsHashMul = 0x9E3779B1u;
+constexpr int kTermsMaxBuckets = 65536;                 // NRTGPU_MAX_TERM_BUCKETS
+constexpr uint64_t kTermsMaxCallSlots = 1ull << 25;     // global table slots of one call, summed over its queries (256 MiB)
+__host__ __device__ inline uint32_t terms_home_slot(uint32_t code, uint32_t shift) { return (code * kTermsHashMul) >> shift; }
+// the slots of a query's global table: the power of two >= 2 x max_buckets (at least 2), as 32 - log2
+__host__ inline uint32_t terms_table_shift(uint32_t max_buckets) {
+  uint32_t log2 = 1;
+  while ((1u << log2) < 2u * max_buckets) ++log2;
+  return 32u - log2;
+}
+struct alignas(16) DTermsQuery {
+  uint32_t need;          // clauses a hit matches at least (DSortQuery.need)
+  uint32_t max_buckets;
+  uint32_t table_off;     // the query's global table: first slot ...
+  uint32_t table_shift;   // ... and 32 - log2 of its slots
+};
+static_assert(sizeof(DTermsQuery) == 16, "DTermsQuery layout");
+struct alignas(16) DTermsState {   // per query, zeroed per call; one more behind the last query: `claimed` = compacted entries of the call
+  uint32_t claimed;       // slots claimed in the global table == distinct values seen (until the query overflows)
+  uint32_t overflow;      // 1: more than max_buckets distinct values; the query's items stop counting values
+  uint32_t n_out;         // terms_compact_kernel: the query's buckets ...
+  uint32_t out_base;      // ... and where they begin among the call's compacted entries
+};
+static_assert(sizeof(DTermsState) == 16, "DTermsState layout");
 
 }  // namespace nrtgpu

@@ -5,7 +5,7 @@
 // plan), search.cpp (BM25 entry points, hybrid tail, merge), coalescer.h (request coalescing: the leader/follower mechanism behind
 // the single-query entries of search.cpp and vectors.cpp; standard library only), finalscore.cpp (the host
 // path of the final-score routes), funcscore.cpp (function-score queries), multimatch.cpp (multi-match queries),
-// fieldsort.cpp (a text query's hits sorted by a doc value column), vectors.cpp (exact kNN, vector rescoring).  Types the ABI names opaquely (nrtgpu_ctx, nrtgpu_seg) live in the global namespace;
+// fieldsort.cpp (a text query's hits sorted by a doc value column), termscount.cpp (its hits counted per value of one), vectors.cpp (exact kNN, vector rescoring).  Types the ABI names opaquely (nrtgpu_ctx, nrtgpu_seg) live in the global namespace;
 // everything else in nrtgpu::rt.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -61,6 +61,10 @@ void launch_bm25_multi_match_function_score(hipStream_t stream, const FinalScore
 void launch_bm25_text_knn(hipStream_t stream, const FinalScoreArgs& a, const DKnnPart* kparts, const uint32_t* kdocs, const double* ksums);
 // sort by field (fieldsort.hip): one DSortQuery per query, one DSortPart per part
 void launch_bm25_field_sort(hipStream_t stream, const FinalScoreArgs& a, const DSortQuery* squeries, const DSortPart* sparts);
+// terms aggregation (termscount.hip): one DTermsQuery per query, one DSortPart per part; the scorer, then the compaction of the
+// queries' tables into `out` (out_cap entries)
+void launch_bm25_terms_count(hipStream_t stream, const FinalScoreArgs& a, const DTermsQuery* tqueries, const DSortPart* sparts, DTermsState* states,
+                             unsigned long long* tables, unsigned long long* out, uint32_t n_queries, uint32_t out_cap);
 #ifdef NRTGPU_DEV
 void launch_debug_wave_kth(hipStream_t stream, const uint64_t* keys, uint32_t n, uint32_t r, uint64_t* out);   // (maxscore.hip: topk_kth_wave on its own)
 void launch_debug_walk_value(hipStream_t stream, float weight, const uint32_t* freq, const uint32_t* norm, const float* table, int fx_scale,
@@ -1110,8 +1114,17 @@ typedef void (*FinalScoreLaunch)(hipStream_t, const FinalScoreArgs&, const void*
 // From "the plan and the route's records exist" to "out[], the diagnostics and the statistics are filled": workspace, plan upload,
 // expansion, the scorer in its turn on the device, merge, per-slice relation, the wait, unpacking.  queries: the CALLER's (k,
 // capacity); t0: now_ms() when planning began.  The caller holds its SegReadLocks until this returns.
+// own: nullptr, or a route's own device output -- work_bytes of the workspace behind the shared regions, zeroed per call by the
+// memset that zeroes the per-slice sums (their address reaches the scorer as FinalScoreArgs.own), and collect(), called behind the
+// wait and the unpacking, before the call is accounted: it copies what the route wants of them on the slot's stream.  What the
+// routes without one enqueue and copy is what it was.
+struct FinalScoreOwn {
+  size_t work_bytes;
+  int (*collect)(nrtgpu_ctx* ctx, Slot* slot, const char* d_own, void* user);
+  void* user;
+};
 int final_score_run(nrtgpu_ctx* ctx, const HostPlan& hp, const nrtgpu_bm25_query* queries, int32_t n_queries, nrtgpu_topdocs* out, double t0,
-                    const PlanBytes* extras, int n_extras, FinalScoreLaunch launch);
+                    const PlanBytes* extras, int n_extras, FinalScoreLaunch launch, const FinalScoreOwn* own = nullptr);
 
 // ---- what the routes lend each other (multimatch.cpp and funcscore.cpp define them; funcscore_multimatch.cpp uses both halves) ----
 // multimatch.cpp: the record the kernel and nrtgpu_multi_match_value read, from the caller's struct; refusals by the header's
@@ -1131,6 +1144,23 @@ int function_masks_resident(const nrtgpu_seg* const* segs, int32_t n_segs, const
 // funcscore.cpp: the doc sets of every function on every part's leaf, for any plan over these leaves (a part names its leaf via qs_begin)
 int function_masks(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_function_score* functions, const HostPlan& hp,
                    std::vector<DFuncMasks>* out);
+
+// fieldsort.cpp: what the routes over a doc value column (sorted searches, the terms aggregation of termscount.cpp) share.
+// What is planned for the queries of such a call: plain SHOULD disjunctions (the vectors own the copies' clauses; the caller
+// points queries[i].terms at terms[i] once every query has been pushed).
+struct FlatQueries {
+  std::vector<nrtgpu_bm25_query> queries;
+  std::vector<std::vector<nrtgpu_term>> terms;
+};
+// the kind of the field's column over the leaves of the call (-1: on no leaf); refuses leaves that disagree
+int doc_values_kind(const nrtgpu_seg* const* segs, int32_t n_segs, int32_t field_id, int qi, int* kind);
+// what both routes refuse of one query as unsupported, in the header's order (under: "a sort" / "a terms count"); *need: the
+// clauses a hit matches at least; the query's flat copy is pushed
+int doc_values_query(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query& q, int qi, int kind, int32_t field_id, const char* under,
+                     uint32_t* need, FlatQueries* flat);
+// the column of every part's leaf, for a plan of the flat copies (field_ids: per query)
+int doc_values_parts(const nrtgpu_seg* const* segs, int32_t n_segs, const int32_t* field_ids, const HostPlan& hp, const char* route,
+                     std::vector<DSortPart>* out);
 
 }  // namespace rt
 }  // namespace nrtgpu
