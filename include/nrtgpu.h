@@ -965,7 +965,8 @@ int  nrtgpu_text_knn_exact(const nrtgpu_bm25_query* q, const nrtgpu_knn_clauses*
  *                           are stricter than a route that reads no score needs
  * Out of scope: 64-bit columns (LONG / DATE_TIME / DOUBLE need keys wider than the top-k's 64 bits -- the next step, and why this
  * cannot serve "newest first" yet); STRING ordinals; LAT_LON distance; virtual (script) fields; more than one sort level; `score`
- * or `docid` as a sort level; scores beside the values; a match-all query under a sort; dismax / multi-match text under a sort;
+ * or `docid` as a sort level; scores beside the values; dismax / multi-match text under a sort (a match-all or filter-only query
+ * under a sort is nrtgpu_search_docset_sorted_batch);
  * updatable doc values; the coalesced, device-resident and nrtgpu_dist_* forms; the Java shim, which does not bind this yet.
  * --------------------------------------------------------------------------------------------- */
 typedef struct {
@@ -1039,7 +1040,8 @@ int  nrtgpu_sort_value_code(int32_t kind, int32_t reverse, uint32_t value_bits, 
  *                           on the sorted route
  * Out of scope: LONG / DOUBLE columns; multi-valued fields; string and ordinal collectors (a single-valued string facet can be
  * uploaded as a column of its global ordinals); script and virtual sources; nested collectors and NESTED_COLLECTOR order; the
- * Filter / Min / Max / Sum / TopHits collectors; fusing the count into a scoring route; match-all, dismax and multi-match text;
+ * Filter / Min / Max / Sum / TopHits collectors; fusing the count into a scoring route; dismax and multi-match text (a match-all
+ * or filter-only query is nrtgpu_count_docset_terms_batch);
  * the coalesced, device-resident and nrtgpu_dist_* forms; the Java shim.
  * --------------------------------------------------------------------------------------------- */
 #define NRTGPU_MAX_TERM_BUCKETS 65536
@@ -1065,6 +1067,86 @@ int  nrtgpu_count_terms_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, co
  * capacity), else the status it would return with the reason in nrtgpu_last_error.  No device work. */
 int  nrtgpu_count_terms_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query* q,
                                   const nrtgpu_terms_count* t);
+
+/* ---------------------------------------------------------------------------------------------
+ * Doc-set requests: a sort by field (nrtgpu_search_sorted_batch) or a terms count (nrtgpu_count_terms_batch) whose hit set is a
+ * DOC SET and no text clause -- the reference's MatchAllDocsQuery, a BooleanQuery of FILTER / MUST_NOT clauses only, and the
+ * numeric RangeQuery of a single-valued INT / FLOAT field with doc values
+ * (src/main/java/com/yelp/nrtsearch/server/field/IntFieldDef.java:124-160, FloatFieldDef.java:126-164:
+ * IndexOrDocValuesQuery(PointRangeQuery, SortedNumericDocValuesField.newSlowRangeQuery)) under a `querySort` or a TermsCollector:
+ * "everything in this category, rating between 4 and 5, best rated first", the facet counts of a browse page.
+ * The hit set of docsets[i] is liveDocs AND every filter mask AND no must_not mask AND every range clause; with no mask and no
+ * range it is every live doc.  filter_mask / must_not_mask / more_* have the meaning and the limits they have in
+ * nrtgpu_bm25_query.
+ * A range clause: both bounds are INCLUSIVE, bits of the column's kind (the kind is the resident column's).  The caller maps an
+ * exclusive bound as the reference does (Math.addExact(+-1) for ints, FloatPoint.nextUp / nextDown for floats).  A doc passes iff
+ * it HAS a value in the clause's column and lower <= value <= upper in the column's order [Lucene-recall]: Integer.compare for
+ * ints; for floats the order of NumericUtils.floatToSortableInt(Float.floatToIntBits(.)) -- -0.0 < +0.0, every NaN the canonical
+ * one and above +inf (so [NaN, NaN] keeps exactly the NaN docs, [-inf, +inf] drops them).  A doc without a value, or in a leaf
+ * that lacks the column, fails the clause.  lower > upper in that order is an EMPTY range that matches nothing, not an error
+ * (the reference's ensureUpperIsMoreThanLower is the caller's job).
+ * Results are nrtgpu_search_sorted_batch's and nrtgpu_count_terms_batch's, word for word, over this hit set: the order (value in
+ * the sort's direction, ties by global docid ascending), the missing value, value_bits of a hit; paging (the cursor lives in the
+ * sort, hits of earlier pages still count); the exact total_hits and the per-slice relation rule; bucket identity and ascending
+ * output order; hits_with_value; overflowed exactly when the hits hold more than max_buckets distinct values, the other queries
+ * of the batch unaffected; the 2^25-slot workspace bound.  total_hits_threshold enters the relation as on those routes.  Slicing,
+ * thread slices, deadlines, diagnostics (items_scan) and statistics (scan_*) work as there; `postings` is 0: none is read.
+ * Context flags: the route reads no posting and sums no score, so it RUNS under NRTGPU_FLAG_PACKED_POSTINGS and
+ * NRTGPU_FLAG_NO_FIXED_POINT (the text routes over a doc value column refuse both).
+ * Refusals, each with a reason in nrtgpu_last_error naming the query.  The predicates and the batch entries agree; all
+ * NRTGPU_ERR_INVALID_ARG checks of ALL queries come before any NRTGPU_ERR_UNSUPPORTED one:
+ *   NRTGPU_ERR_INVALID_ARG  NULL arguments; k outside 1..NRTGPU_MAX_K; total_hits_threshold < 0; n_ranges outside
+ *                           0..NRTGPU_MAX_RANGES; ranges NULL with n_ranges > 0; a clause's reserved != 0; negative mask ids,
+ *                           n_more_* negative or with a NULL array, more than NRTGPU_MAX_MASKS FILTER or MUST_NOT masks, a
+ *                           more_* id <= 0; reserved != 0; what nrtgpu_search_sorted_batch / nrtgpu_count_terms_batch refuse of
+ *                           sorts[i] / terms[i] / out[i] with this status; leaves of the call that hold a named column (the
+ *                           sort's, the count's, a range clause's) under different kinds; a call whose count tables exceed the
+ *                           workspace bound
+ *   NRTGPU_ERR_UNSUPPORTED  the sort or count column, or a range clause's column, is resident on no leaf of the call (its kind is
+ *                           then unknown, and a forgotten upload must not read as "no hits"); a mask that is not resident
+ * Out of scope: LONG / DOUBLE / DATE_TIME columns; multi-valued fields (a range over "any value"); ranges inside the text routes,
+ * or as resident masks for the MaxScore and kNN routes; a score-ordered match-all; skipping whole tiles by per-tile minima and
+ * maxima of a column (zone maps); the coalesced, device-resident and nrtgpu_dist_* forms; the Java shim, which keeps sending
+ * these requests to Lucene until it binds this.
+ * --------------------------------------------------------------------------------------------- */
+#define NRTGPU_MAX_RANGES 4       /* range clauses per doc-set query (a design limit) */
+typedef struct {
+  int32_t  field_id;      /* the column, NRTGPU_DOCVALUES_INT32 or _FLOAT32 */
+  uint32_t lower_bits;    /* inclusive, bits of the column's kind */
+  uint32_t upper_bits;    /* inclusive */
+  int32_t  reserved;      /* 0 */
+} nrtgpu_range_clause;    /* 16 bytes */
+typedef struct {
+  int32_t filter_mask;              /* as in nrtgpu_bm25_query: 0 = none */
+  int32_t must_not_mask;
+  int32_t n_more_filters;
+  int32_t n_more_must_not;
+  const int32_t* more_filters;
+  const int32_t* more_must_not;
+  int32_t n_ranges;                 /* 0..NRTGPU_MAX_RANGES */
+  int32_t k;                        /* numHits, 1..NRTGPU_MAX_K (a terms count reads it only to check it) */
+  const nrtgpu_range_clause* ranges;
+  int32_t total_hits_threshold;     /* >= 0; INT32_MAX: the count is never a lower bound */
+  int32_t reserved;                 /* 0 */
+} nrtgpu_docset_query;              /* 56 bytes */
+/* n_queries sorted doc-set searches over the same leaves in one device pass; sorts[i] (cursor included) orders docsets[i] */
+int  nrtgpu_search_docset_sorted_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                       const nrtgpu_docset_query* docsets, const nrtgpu_field_sort* sorts, int32_t n_queries,
+                                       nrtgpu_fielddocs* out);
+/* The eligibility test alone: NRTGPU_OK if the search above would run (d, s) over these leaves, else the status it would return
+ * with the reason in nrtgpu_last_error.  No device work. */
+int  nrtgpu_docset_sorted_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* d,
+                                    const nrtgpu_field_sort* s);
+/* n_queries count maps of doc sets over the same leaves in one device pass; terms[i] names the column and the bound of docsets[i] */
+int  nrtgpu_count_docset_terms_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                     const nrtgpu_docset_query* docsets, const nrtgpu_terms_count* terms, int32_t n_queries,
+                                     nrtgpu_term_counts* out);
+/* The eligibility test alone (with an output of sufficient capacity).  No device work. */
+int  nrtgpu_count_docset_terms_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* d,
+                                         const nrtgpu_terms_count* t);
+/* Whether a range clause keeps a doc whose value is value_bits (kind: NRTGPU_DOCVALUES_*; *out = 1 / 0), exposed for the tests:
+ * needs no device; it is the very function the kernels compile.  kind outside 0..1 or out NULL: NRTGPU_ERR_INVALID_ARG. */
+int  nrtgpu_range_accepts(int32_t kind, uint32_t lower_bits, uint32_t upper_bits, uint32_t value_bits, int32_t* out);
 
 /* ---------------------------------------------------------------------------------------------
  * Host-side restatements the Java shim would otherwise take from Lucene objects

@@ -38,6 +38,7 @@ NRTGPU_MAX_KNN_LISTS = 8
 NRTGPU_DOCVALUES_INT32 = 0
 NRTGPU_DOCVALUES_FLOAT32 = 1
 NRTGPU_MAX_TERM_BUCKETS = 65536
+NRTGPU_MAX_RANGES = 4
 
 # every symbol include/nrtgpu.h declares (tests/test_abi.py checks the header against this list)
 ABI_SYMBOLS = [
@@ -64,6 +65,8 @@ ABI_SYMBOLS = [
     "nrtgpu_search_text_knn_batch", "nrtgpu_text_knn_supported", "nrtgpu_text_knn_value", "nrtgpu_text_knn_exact",
     "nrtgpu_segment_add_doc_values", "nrtgpu_search_sorted_batch", "nrtgpu_sorted_supported", "nrtgpu_sort_value_code",
     "nrtgpu_count_terms_batch", "nrtgpu_count_terms_supported",
+    "nrtgpu_search_docset_sorted_batch", "nrtgpu_docset_sorted_supported", "nrtgpu_count_docset_terms_batch",
+    "nrtgpu_count_docset_terms_supported", "nrtgpu_range_accepts",
 ]
 # what include/nrtgpu_dev.h adds: test hooks and measurement helpers of the development library (libnrtgpu_dev.so) only
 DEV_SYMBOLS = [
@@ -144,6 +147,16 @@ class TermsCount(C.Structure):   # nrtgpu_terms_count
 class TermCounts(C.Structure):   # nrtgpu_term_counts
     _fields_ = [("n_buckets", C.c_int32), ("capacity", C.c_int32), ("value_bits", C.POINTER(C.c_uint32)), ("counts", C.POINTER(C.c_int32)),
                 ("total_hits", C.c_int64), ("hits_with_value", C.c_int64), ("overflowed", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RangeClause(C.Structure):   # nrtgpu_range_clause
+    _fields_ = [("field_id", C.c_int32), ("lower_bits", C.c_uint32), ("upper_bits", C.c_uint32), ("reserved", C.c_int32)]
+
+
+class DocsetQuery(C.Structure):   # nrtgpu_docset_query
+    _fields_ = [("filter_mask", C.c_int32), ("must_not_mask", C.c_int32), ("n_more_filters", C.c_int32), ("n_more_must_not", C.c_int32),
+                ("more_filters", C.POINTER(C.c_int32)), ("more_must_not", C.POINTER(C.c_int32)), ("n_ranges", C.c_int32), ("k", C.c_int32),
+                ("ranges", C.POINTER(RangeClause)), ("total_hits_threshold", C.c_int32), ("reserved", C.c_int32)]
 
 
 class Diagnostics(C.Structure):   # nrtgpu_diagnostics
@@ -262,6 +275,11 @@ def _open(path: str) -> C.CDLL:
     L.nrtgpu_sort_value_code.argtypes = [i32, i32, C.c_uint32, vp]
     L.nrtgpu_count_terms_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(TermsCount), i32, C.POINTER(TermCounts)]
     L.nrtgpu_count_terms_supported.argtypes = [vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(TermsCount)]
+    L.nrtgpu_search_docset_sorted_batch.argtypes = [vp, vp, vp, i32, C.POINTER(DocsetQuery), C.POINTER(FieldSort), i32, C.POINTER(FieldDocs)]
+    L.nrtgpu_docset_sorted_supported.argtypes = [vp, vp, i32, C.POINTER(DocsetQuery), C.POINTER(FieldSort)]
+    L.nrtgpu_count_docset_terms_batch.argtypes = [vp, vp, vp, i32, C.POINTER(DocsetQuery), C.POINTER(TermsCount), i32, C.POINTER(TermCounts)]
+    L.nrtgpu_count_docset_terms_supported.argtypes = [vp, vp, i32, C.POINTER(DocsetQuery), C.POINTER(TermsCount)]
+    L.nrtgpu_range_accepts.argtypes = [i32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
     L.nrtgpu_rescore_vectors.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, f32, vp, vp, i32, C.c_double, C.c_double, i32,
                                          C.POINTER(TopDocs)]
     L.nrtgpu_search_hybrid_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), i32, i32, i32, vp, i32, f32,

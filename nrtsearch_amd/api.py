@@ -1465,6 +1465,152 @@ def count_terms_supported(searcher: "GpuIndexSearcher", query: Query, collector:
     return _supported(_lib.load().nrtgpu_count_terms_supported(searcher.ctx._h, searcher._segs, len(searcher.leaves), m.queries, tc))
 
 
+@dataclasses.dataclass(frozen=True)
+class RangeClause:
+    """IntFieldDef / FloatFieldDef.getRangeQuery over a single-valued field with doc values: lower <= value <= upper, both bounds
+    INCLUSIVE, in the order of the column's kind (floats: -0.0 < +0.0, NaN above +inf).  An exclusive bound is the caller's to map
+    (lower + 1 / np.nextafter).  A doc without a value fails the clause; lower > upper matches nothing."""
+
+    field: int
+    kind: str
+    lower: Union[int, float]
+    upper: Union[int, float]
+
+
+@dataclasses.dataclass(frozen=True)
+class DocSetQuery:
+    """A query without a text clause: MatchAllDocsQuery (all three empty), or a BooleanQuery of FILTER / MUST_NOT clauses only --
+    resident masks and numeric ranges.  Its hits are the live docs inside every filter and every range and outside every must_not."""
+
+    filter: Tuple[MaskFilter, ...] = ()
+    must_not: Tuple[MaskFilter, ...] = ()
+    ranges: Tuple[RangeClause, ...] = ()
+
+
+def _marshal_docsets(docsets: Sequence[DocSetQuery], managers: Sequence[TopScoreDocCollectorManager]):
+    """nrtgpu_docset_query per query (and what keeps its arrays alive)."""
+    n = len(docsets)
+    if len(managers) != n:
+        raise ValueError(f"{len(managers)} managers for {n} doc-set queries")
+    ds = (_lib.DocsetQuery * n)()
+    keep: list = [ds]
+    for qi, (d, mgr) in enumerate(zip(docsets, managers)):
+        if mgr.after is not None or mgr.min_competitive_score != 0.0:
+            raise UnsupportedQuery("a doc-set query has no score cursor and no min_competitive_score")
+        q = ds[qi]
+        filters, must_nots = [int(f.mask_id) for f in d.filter], [int(f.mask_id) for f in d.must_not]
+        q.filter_mask = filters[0] if filters else 0
+        q.must_not_mask = must_nots[0] if must_nots else 0
+        for ids, n_name, p_name in ((filters[1:], "n_more_filters", "more_filters"), (must_nots[1:], "n_more_must_not", "more_must_not")):
+            if ids:
+                arr = (C.c_int32 * len(ids))(*ids)
+                keep.append(arr)
+                setattr(q, n_name, len(ids))
+                setattr(q, p_name, arr)
+        if d.ranges:
+            for r in d.ranges:
+                if r.kind not in DOC_VALUE_KINDS:
+                    raise UnsupportedQuery(f"a range clause of kind {r.kind!r}")
+            rc = (_lib.RangeClause * len(d.ranges))(*[_lib.RangeClause(int(r.field), _value_bits(r.kind, r.lower), _value_bits(r.kind, r.upper), 0)
+                                                      for r in d.ranges])
+            keep.append(rc)
+            q.ranges = rc
+        q.n_ranges = len(d.ranges)
+        q.k = int(mgr.num_hits)
+        q.total_hits_threshold = int(mgr.total_hits_threshold)
+    return ds, keep
+
+
+def _docset_sorts(sorts: Sequence[SortField], afters, n: int):
+    if len(sorts) != n or (afters is not None and len(afters) != n):
+        raise ValueError(f"{len(sorts)} sorts / {None if afters is None else len(afters)} afters for {n} queries")
+    fs = (_lib.FieldSort * n)()
+    for qi, sort in enumerate(sorts):
+        if sort.kind not in DOC_VALUE_KINDS:
+            raise UnsupportedQuery(f"a sort of kind {sort.kind!r}")
+        after = afters[qi] if afters is not None else None
+        fs[qi] = _lib.FieldSort(int(sort.field), int(bool(sort.reverse)), _value_bits(sort.kind, sort.missing), int(after is not None),
+                                int(after.doc) if after is not None else 0, _value_bits(sort.kind, after.value) if after is not None else 0)
+    return fs
+
+
+def search_docset_sorted_batch(searcher: "GpuIndexSearcher", docsets: Sequence[DocSetQuery], managers: Sequence[TopScoreDocCollectorManager],
+                               sorts: Sequence[SortField], afters: Optional[Sequence[Optional[FieldDoc]]] = None) -> List[TopFieldDocs]:
+    """Sorted doc-set searches (nrtgpu_search_docset_sorted_batch): the hits of docsets[i] ordered by sorts[i], the page behind
+    afters[i] when that is given -- search_sorted_batch's results over a hit set without a text clause."""
+    ds, keep = _marshal_docsets(docsets, managers)
+    n = len(docsets)
+    fs = _docset_sorts(sorts, afters, n)
+    h = _text_outputs(n, managers)
+    _lib.check(_lib.load().nrtgpu_search_docset_sorted_batch(searcher.ctx._h, searcher._segs, searcher._bases, len(searcher.leaves), ds, fs, n,
+                                                             C.cast(h.outs, C.POINTER(_lib.FieldDocs))))
+    del keep
+    return [TopFieldDocs(t.docs, t.scores.view(DOC_VALUE_KINDS[sort.kind][1]), t.total_hits, t.relation_gte) for t, sort in zip(h.lists(), sorts)]
+
+
+def docset_sorted_supported(searcher: "GpuIndexSearcher", docset: DocSetQuery, manager: TopScoreDocCollectorManager, sort: SortField,
+                            after: Optional[FieldDoc] = None) -> bool:
+    """The eligibility predicate alone (nrtgpu_docset_sorted_supported)."""
+    ds, keep = _marshal_docsets([docset], [manager])
+    fs = _docset_sorts([sort], [after], 1)
+    rc = _lib.load().nrtgpu_docset_sorted_supported(searcher.ctx._h, searcher._segs, len(searcher.leaves), ds, fs)
+    del keep
+    return _supported(rc)
+
+
+def _docset_terms(docsets, collectors: Sequence[TermsCollector], max_buckets, managers):
+    n = len(docsets)
+    if len(collectors) != n:
+        raise ValueError(f"{len(collectors)} collectors for {n} queries")
+    bounds = [int(max_buckets)] * n if np.isscalar(max_buckets) else [int(b) for b in max_buckets]
+    if len(bounds) != n:
+        raise ValueError(f"{len(bounds)} max_buckets for {n} queries")
+    for c in collectors:
+        if c.kind not in DOC_VALUE_KINDS:
+            raise UnsupportedQuery(f"a terms collector of kind {c.kind!r}")
+    mgrs = list(managers) if managers is not None else [TopScoreDocCollectorManager(1)] * n
+    ds, keep = _marshal_docsets(docsets, mgrs)
+    tc = (_lib.TermsCount * n)(*[_lib.TermsCount(int(c.field), b) for c, b in zip(collectors, bounds)])
+    return ds, keep, tc, bounds
+
+
+def count_docset_terms_batch(searcher: "GpuIndexSearcher", docsets: Sequence[DocSetQuery], collectors: Sequence[TermsCollector], max_buckets=4096,
+                             managers: Optional[Sequence[TopScoreDocCollectorManager]] = None) -> List[TermCounts]:
+    """Terms aggregations over doc sets (nrtgpu_count_docset_terms_batch): count_terms_batch's results over a hit set without a
+    text clause."""
+    ds, keep, tc, bounds = _docset_terms(docsets, collectors, max_buckets, managers)
+    n = len(docsets)
+    width = max([max(b, 1) for b in bounds], default=1)
+    bits = np.zeros((n, width), dtype=np.uint32)
+    counts = np.zeros((n, width), dtype=np.int32)
+    outs = (_lib.TermCounts * n)()
+    for qi in range(n):
+        outs[qi].capacity = max(bounds[qi], 0)
+        outs[qi].value_bits = C.cast(bits.ctypes.data + qi * width * 4, C.POINTER(C.c_uint32))
+        outs[qi].counts = C.cast(counts.ctypes.data + qi * width * 4, C.POINTER(C.c_int32))
+    _lib.check(_lib.load().nrtgpu_count_docset_terms_batch(searcher.ctx._h, searcher._segs, searcher._bases, len(searcher.leaves), ds, tc, n, outs))
+    del keep
+    return [TermCounts(bits[qi, : o.n_buckets].view(DOC_VALUE_KINDS[c.kind][1]).copy(), counts[qi, : o.n_buckets].copy(), int(o.total_hits),
+                       int(o.hits_with_value), bool(o.overflowed)) for qi, (o, c) in enumerate(zip(outs, collectors))]
+
+
+def count_docset_terms_supported(searcher: "GpuIndexSearcher", docset: DocSetQuery, collector: TermsCollector, max_buckets: int = 4096,
+                                 manager: Optional[TopScoreDocCollectorManager] = None) -> bool:
+    """The eligibility predicate alone (nrtgpu_count_docset_terms_supported)."""
+    ds, keep, tc, _ = _docset_terms([docset], [collector], max_buckets, None if manager is None else [manager])
+    rc = _lib.load().nrtgpu_count_docset_terms_supported(searcher.ctx._h, searcher._segs, len(searcher.leaves), ds, tc)
+    del keep
+    return _supported(rc)
+
+
+def range_accepts(kind: str, lower_bits: int, upper_bits: int, value_bits: int) -> bool:
+    """Whether a range clause keeps a value (nrtgpu_range_accepts: the function the kernels compile).  No device."""
+    out = C.c_int32(0)
+    _lib.check(_lib.load().nrtgpu_range_accepts(DOC_VALUE_KINDS[kind][0], C.c_uint32(int(lower_bits)), C.c_uint32(int(upper_bits)),
+                                                C.c_uint32(int(value_bits)), C.byref(out)))
+    return bool(out.value)
+
+
 def debug_knn_bounds(sim: int, dim: int, q_norm2: float, q_l1: float, q_absmax: float, nv_max: float, nv_min: float,
                      rows_absmax: float, score_boost: float = 1.0, m: float = 0.0, s: float = 0.0) -> dict:
     """Test hook of the development library (nrtgpu_debug_knn_bounds): the rounding bounds the exact float vector search certifies

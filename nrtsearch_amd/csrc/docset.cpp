@@ -1,0 +1,250 @@
+// docset.cpp -- doc-set requests (include/nrtgpu.h: nrtgpu_search_docset_sorted_batch, nrtgpu_count_docset_terms_batch): a sort by
+// field or a terms count whose hit set is a doc set -- liveDocs, FILTER / MUST_NOT masks, numeric range clauses -- and no text
+// clause.  The plan is the route's own (planner.cpp: docset_plan): parts without clauses over every tile of every leaf, the
+// query's combined accept set with liveDocs in DPart.live_bits.  Beside it go the sorted / counting route's per-query record
+// (fieldsort.cpp / termscount.cpp build them), one DRangeQuery per query, one DSortPart per part for the sort / count column and
+// kMaxRanges per part for the range clauses' columns (plan.h).  From the plan on the path is finalscore.cpp's; the count route's
+// workspace, collect() and unpacking are termscount.cpp's.
+#include <cstddef>
+
+#include "runtime_internal.h"
+
+static_assert(sizeof(nrtgpu_range_clause) == 16, "nrtgpu_range_clause layout");
+static_assert(sizeof(nrtgpu_docset_query) == 56 && offsetof(nrtgpu_docset_query, more_filters) == 16 && offsetof(nrtgpu_docset_query, n_ranges) == 32 &&
+                  offsetof(nrtgpu_docset_query, ranges) == 40 && offsetof(nrtgpu_docset_query, total_hits_threshold) == 48,
+              "nrtgpu_docset_query layout");
+static_assert(NRTGPU_MAX_RANGES == kMaxRanges, "NRTGPU_MAX_RANGES");
+
+extern "C" int nrtgpu_range_accepts(int32_t kind, uint32_t lower_bits, uint32_t upper_bits, uint32_t value_bits, int32_t* out) {
+  if (!out) return fail(NRTGPU_ERR_INVALID_ARG, "NULL argument");
+  if (kind != NRTGPU_DOCVALUES_INT32 && kind != NRTGPU_DOCVALUES_FLOAT32) return fail(NRTGPU_ERR_INVALID_ARG, "doc values kind %d outside 0..1", kind);
+  *out = range_accepts_code(doc_value_code(kind, lower_bits), doc_value_code(kind, upper_bits), doc_value_code(kind, value_bits)) ? 1 : 0;
+  return NRTGPU_OK;
+}
+
+namespace {
+
+// What is checked and built of the doc sets of a call, whichever collector they run under.
+struct DocsetCall {
+  std::vector<nrtgpu_bm25_query> masks;    // per query: k, total_hits_threshold and the mask fields (what docset_plan and final_score_run read)
+  std::vector<DRangeQuery> ranges;         // per query (the codes are filled once the columns' kinds are known)
+  std::vector<int> range_kinds;            // per (query, clause): kMaxRanges per query
+};
+
+// What the route refuses of docsets[qi] as an invalid argument, the header's table in its order.
+int check_docset(const nrtgpu_docset_query& d, int qi) {
+  if (d.k < 1 || d.k > NRTGPU_MAX_K) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: numHits %d outside 1..%d", qi, d.k, NRTGPU_MAX_K);
+  if (d.total_hits_threshold < 0) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: totalHitsThreshold must be >= 0, got %d", qi, d.total_hits_threshold);
+  if (d.n_ranges < 0 || d.n_ranges > NRTGPU_MAX_RANGES) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: n_ranges %d outside 0..%d", qi, d.n_ranges, NRTGPU_MAX_RANGES);
+  if (d.n_ranges > 0 && !d.ranges) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: ranges is NULL with n_ranges %d", qi, d.n_ranges);
+  for (int r = 0; r < d.n_ranges; ++r)
+    if (d.ranges[r].reserved != 0) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: range clause %d: reserved must be 0", qi, r);
+  if (d.filter_mask < 0 || d.must_not_mask < 0) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: mask ids must be >= 0", qi);
+  if (d.n_more_filters < 0 || d.n_more_must_not < 0 || (d.n_more_filters > 0 && !d.more_filters) || (d.n_more_must_not > 0 && !d.more_must_not))
+    return fail(NRTGPU_ERR_INVALID_ARG, "query %d: more_filters / more_must_not", qi);
+  if (d.n_more_filters + (d.filter_mask != 0) > NRTGPU_MAX_MASKS || d.n_more_must_not + (d.must_not_mask != 0) > NRTGPU_MAX_MASKS)
+    return fail(NRTGPU_ERR_INVALID_ARG, "query %d: more than %d FILTER or MUST_NOT clauses", qi, NRTGPU_MAX_MASKS);
+  for (int i = 0; i < d.n_more_filters; ++i)
+    if (d.more_filters[i] <= 0) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: more_filters[%d] must be a mask id > 0", qi, i);
+  for (int i = 0; i < d.n_more_must_not; ++i)
+    if (d.more_must_not[i] <= 0) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: more_must_not[%d] must be a mask id > 0", qi, i);
+  if (d.reserved != 0) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: reserved must be 0", qi);
+  return NRTGPU_OK;
+}
+
+// The invalid-argument half of one doc set: check_docset, then the kinds of its range clauses' columns over the leaves (leaves
+// that disagree are refused here); its records begun.
+int docset_begin(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query& d, int qi, DocsetCall* call) {
+  if (int rc = check_docset(d, qi)) return rc;
+  nrtgpu_bm25_query m{};
+  m.k = d.k;
+  m.total_hits_threshold = d.total_hits_threshold;
+  m.filter_mask = d.filter_mask;
+  m.must_not_mask = d.must_not_mask;
+  m.n_more_filters = d.n_more_filters;
+  m.more_filters = d.more_filters;
+  m.n_more_must_not = d.n_more_must_not;
+  m.more_must_not = d.more_must_not;
+  call->masks.push_back(m);
+  DRangeQuery rq{};
+  rq.n_ranges = (uint32_t)d.n_ranges;
+  for (int r = 0; r < kMaxRanges; ++r) {
+    int kind = -1;
+    if (r < d.n_ranges)
+      if (int rc = doc_values_kind(segs, n_segs, d.ranges[r].field_id, qi, &kind)) return rc;
+    call->range_kinds.push_back(kind);
+  }
+  call->ranges.push_back(rq);
+  return NRTGPU_OK;
+}
+
+// The unsupported half, behind the collector's own column: a range clause's column on no leaf, a mask that is not resident; the
+// clauses' bounds as codes.
+int docset_finish(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query& d, int qi, DocsetCall* call) {
+  DRangeQuery& rq = call->ranges[(size_t)qi];
+  for (int r = 0; r < d.n_ranges; ++r) {
+    const int kind = call->range_kinds[(size_t)qi * (size_t)kMaxRanges + (size_t)r];
+    if (kind < 0) return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: no leaf of the call holds doc values of field %d (range clause %d)", qi, d.ranges[r].field_id, r);
+    rq.lo_code[r] = doc_value_code(kind, d.ranges[r].lower_bits);
+    rq.hi_code[r] = doc_value_code(kind, d.ranges[r].upper_bits);
+  }
+  return doc_values_masks_resident(segs, n_segs, call->masks[(size_t)qi], qi);
+}
+
+int no_column(int qi, int32_t field_id) { return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: no leaf of the call holds doc values of field %d", qi, field_id); }
+
+DSortPart column_of(const nrtgpu_seg* seg, int32_t field_id) {
+  const auto fit = seg->fields.find(field_id);
+  if (fit == seg->fields.end() || fit->second.dv_kind < 0) return DSortPart{nullptr, nullptr};   // no doc of the leaf has a value
+  return DSortPart{fit->second.d_dv_code, fit->second.d_dv_has};
+}
+
+// The columns of every part's leaf (HostPlan.part_leaf): the collector's (field_ids: per query) and the range clauses'.
+void docset_parts(const nrtgpu_seg* const* segs, const nrtgpu_docset_query* docsets, const int32_t* field_ids, const HostPlan& hp, std::vector<DSortPart>* sparts,
+                  std::vector<DSortPart>* rparts) {
+  sparts->assign(hp.parts.size(), DSortPart{nullptr, nullptr});
+  rparts->assign(hp.parts.size() * (size_t)kMaxRanges, DSortPart{nullptr, nullptr});
+  for (const DItem& it : hp.items)
+    for (uint32_t pi = 0; pi < it.n_parts; ++pi) {
+      const size_t at = (size_t)it.part_begin + pi;
+      const nrtgpu_seg* seg = segs[hp.part_leaf[at]];
+      (*sparts)[at] = column_of(seg, field_ids[it.query]);
+      const nrtgpu_docset_query& d = docsets[it.query];
+      for (int r = 0; r < d.n_ranges; ++r) (*rparts)[at * (size_t)kMaxRanges + (size_t)r] = column_of(seg, d.ranges[r].field_id);
+    }
+}
+
+// What the sorted entry refuses of a call before anything is planned (the segments' content is held), and its records.
+int check_sorted(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* docsets, const nrtgpu_field_sort* sorts, int32_t n_queries,
+                 DocsetCall* call, std::vector<DSortQuery>* records, std::vector<int>* kinds) {
+  for (int qi = 0; qi < n_queries; ++qi) {
+    if (int rc = docset_begin(segs, n_segs, docsets[qi], qi, call)) return rc;
+    if (int rc = field_sort_check(sorts[qi], qi)) return rc;
+    int kind = -1;
+    if (int rc = doc_values_kind(segs, n_segs, sorts[qi].field_id, qi, &kind)) return rc;
+    kinds->push_back(kind);
+  }
+  for (int qi = 0; qi < n_queries; ++qi) {
+    const int kind = (*kinds)[(size_t)qi];
+    if (kind < 0) return no_column(qi, sorts[qi].field_id);
+    if (int rc = docset_finish(segs, n_segs, docsets[qi], qi, call)) return rc;
+    DSortQuery r{};
+    field_sort_record(sorts[qi], kind, &r);
+    records->push_back(r);
+  }
+  return NRTGPU_OK;
+}
+
+// The same of the counting entry.  out: the batch entry's outputs (their capacities), nullptr for the predicate.
+int check_terms(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* docsets, const nrtgpu_terms_count* terms,
+                const nrtgpu_term_counts* out, int32_t n_queries, DocsetCall* call, std::vector<DTermsQuery>* records, std::vector<int>* kinds, TermsWork* work) {
+  uint64_t slots = 0, cap = 0;
+  for (int qi = 0; qi < n_queries; ++qi) {
+    if (int rc = docset_begin(segs, n_segs, docsets[qi], qi, call)) return rc;
+    int kind = -1;
+    DTermsQuery r{};
+    if (int rc = terms_count_record(segs, n_segs, terms[qi], out ? &out[qi] : nullptr, qi, &slots, &cap, &r, &kind)) return rc;
+    kinds->push_back(kind);
+    records->push_back(r);
+  }
+  for (int qi = 0; qi < n_queries; ++qi) {
+    if ((*kinds)[(size_t)qi] < 0) return no_column(qi, terms[qi].field_id);
+    if (int rc = docset_finish(segs, n_segs, docsets[qi], qi, call)) return rc;
+  }
+  work->layout(n_queries, slots, cap);
+  return NRTGPU_OK;
+}
+
+}  // namespace
+
+extern "C" int nrtgpu_docset_sorted_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* d,
+                                              const nrtgpu_field_sort* s) {
+  if (int rc = final_score_enter(ctx, segs, n_segs, !d || !s, nullptr)) return rc;
+  SegReadLocks content(segs, n_segs);
+  DocsetCall call;
+  std::vector<DSortQuery> records;
+  std::vector<int> kinds;
+  if (int rc = check_sorted(segs, n_segs, d, s, 1, &call, &records, &kinds)) return rc;
+  HostPlan hp;   // the planner is the predicate for the leaves (sealed, of this context) and the accept sets
+  return docset_plan(ctx, segs, nullptr, n_segs, call.masks.data(), 1, hp);
+}
+
+extern "C" int nrtgpu_search_docset_sorted_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                                 const nrtgpu_docset_query* docsets, const nrtgpu_field_sort* sorts, int32_t n_queries,
+                                                 nrtgpu_fielddocs* out) {
+  if (int rc = final_score_enter(ctx, segs, n_segs, !docsets || !sorts || !out, &n_queries)) return rc;
+  const double t0 = now_ms();
+  SegReadLocks content(segs, n_segs);   // until this call's kernels have finished
+  DocsetCall call;
+  std::vector<DSortQuery> records;
+  std::vector<int> kinds;
+  if (int rc = check_sorted(segs, n_segs, docsets, sorts, n_queries, &call, &records, &kinds)) return rc;
+  HostPlan hp;
+  if (int rc = docset_plan(ctx, segs, doc_bases, n_segs, call.masks.data(), n_queries, hp)) return rc;
+  std::vector<DSortPart> sparts, rparts;
+  std::vector<int32_t> field_ids((size_t)n_queries);
+  for (int qi = 0; qi < n_queries; ++qi) field_ids[(size_t)qi] = sorts[qi].field_id;
+  docset_parts(segs, docsets, field_ids.data(), hp, &sparts, &rparts);
+  const PlanBytes extras[4] = {{records.data(), records.size() * sizeof(DSortQuery)},
+                               {call.ranges.data(), call.ranges.size() * sizeof(DRangeQuery)},
+                               {sparts.data(), sparts.size() * sizeof(DSortPart)},
+                               {rparts.data(), rparts.size() * sizeof(DSortPart)}};
+  nrtgpu_topdocs* pages = reinterpret_cast<nrtgpu_topdocs*>(out);   // (the layout is the same: fieldsort.cpp's static_assert)
+  if (int rc = final_score_run(ctx, hp, call.masks.data(), n_queries, pages, t0, extras, 4, [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
+        launch_docset_sort(st, a, (const DSortQuery*)d_extra[0], (const DRangeQuery*)d_extra[1], (const DSortPart*)d_extra[2], (const DSortPart*)d_extra[3]);
+      }))
+    return rc;
+  for (int qi = 0; qi < n_queries; ++qi) {   // key high words -> the values the hits sorted as
+    uint32_t* v = out[qi].value_bits;
+    const uint32_t reverse = records[(size_t)qi].reverse;
+    for (int32_t i = 0; v && i < out[qi].n_hits; ++i) v[i] = doc_value_bits(kinds[(size_t)qi], reverse != 0u ? v[i] : ~v[i]);
+  }
+  return NRTGPU_OK;
+}
+
+extern "C" int nrtgpu_count_docset_terms_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* d,
+                                                   const nrtgpu_terms_count* t) {
+  if (int rc = final_score_enter(ctx, segs, n_segs, !d || !t, nullptr)) return rc;
+  SegReadLocks content(segs, n_segs);
+  DocsetCall call;
+  std::vector<DTermsQuery> records;
+  std::vector<int> kinds;
+  TermsWork work;
+  if (int rc = check_terms(segs, n_segs, d, t, nullptr, 1, &call, &records, &kinds, &work)) return rc;
+  HostPlan hp;
+  return docset_plan(ctx, segs, nullptr, n_segs, call.masks.data(), 1, hp);
+}
+
+extern "C" int nrtgpu_count_docset_terms_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                               const nrtgpu_docset_query* docsets, const nrtgpu_terms_count* terms, int32_t n_queries,
+                                               nrtgpu_term_counts* out) {
+  if (int rc = final_score_enter(ctx, segs, n_segs, !docsets || !terms || !out, &n_queries)) return rc;
+  const double t0 = now_ms();
+  SegReadLocks content(segs, n_segs);   // until this call's kernels have finished
+  DocsetCall call;
+  std::vector<DTermsQuery> records;
+  std::vector<int> kinds;
+  TermsWork work;
+  if (int rc = check_terms(segs, n_segs, docsets, terms, out, n_queries, &call, &records, &kinds, &work)) return rc;
+  HostPlan hp;
+  if (int rc = docset_plan(ctx, segs, doc_bases, n_segs, call.masks.data(), n_queries, hp)) return rc;
+  std::vector<DSortPart> sparts, rparts;
+  std::vector<int32_t> field_ids((size_t)n_queries);
+  for (int qi = 0; qi < n_queries; ++qi) field_ids[(size_t)qi] = terms[qi].field_id;
+  docset_parts(segs, docsets, field_ids.data(), hp, &sparts, &rparts);
+  const PlanBytes extras[4] = {{records.data(), records.size() * sizeof(DTermsQuery)},
+                               {call.ranges.data(), call.ranges.size() * sizeof(DRangeQuery)},
+                               {sparts.data(), sparts.size() * sizeof(DSortPart)},
+                               {rparts.data(), rparts.size() * sizeof(DSortPart)}};
+  std::vector<nrtgpu_topdocs> pages((size_t)n_queries, nrtgpu_topdocs{});   // (no hits come back: the merge's lists are empty; total_hits is read from them)
+  const FinalScoreOwn own{work.bytes, terms_collect, &work};
+  if (int rc = final_score_run(ctx, hp, call.masks.data(), n_queries, pages.data(), t0, extras, 4, [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
+        const TermsWork* w = (const TermsWork*)a.own_user;
+        char* d_own = (char*)a.own;
+        launch_docset_terms_count(st, a, (const DTermsQuery*)d_extra[0], (const DRangeQuery*)d_extra[1], (const DSortPart*)d_extra[2], (const DSortPart*)d_extra[3],
+                                  (DTermsState*)(d_own + w->o_states), (unsigned long long*)(d_own + w->o_tables), (unsigned long long*)(d_own + w->o_out),
+                                  (uint32_t)w->n_queries, w->out_cap);
+      }, &own))
+    return rc;
+  return terms_unpack(work, kinds, pages.data(), n_queries, out);
+}

@@ -1,0 +1,326 @@
+// docset.hip -- the gfx950 kernels of the doc-set requests (include/nrtgpu.h: nrtgpu_search_docset_sorted_batch,
+// nrtgpu_count_docset_terms_batch): a sort by field or a terms count whose hit set is a DOC SET -- liveDocs, FILTER / MUST_NOT
+// masks, numeric range clauses (the reference's MatchAllDocsQuery, a BooleanQuery of FILTER clauses only, IntFieldDef /
+// FloatFieldDef.getRangeQuery) -- and no text clause.
+//
+//   docset_sort_kernel          per sub-tile the accept words, the range clauses, then keys for the accepted docs and the item's top-k
+//   docset_terms_count_kernel   the same hit set; every hit with a value adds 1 in the count table under the value's code
+//
+// The decomposition is the final-score skeleton's (finalscore.hiph): one workgroup of kScanWaves waves per item, a wave takes
+// kTileDocs-doc sub-tiles of the item's parts (final_total_tiles / final_tile), hits per slice through final_count_slice, the
+// sorted kernel's candidates through the shared buffer with the wave-by-wave compaction, theta_g and final_epilogue; the count
+// kernel's tables are termstables.hiph's and terms_compact_kernel (termscount.hip) packs them.  What the route does NOT have:
+// postings, clause counters in LDS (the 96 KiB of the text kernels), an atomic per doc.  The hit set IS the accept words:
+//   accept words  lane j loads word j of the sub-tile's 16 (DPart.live_bits: the query's combined accept set WITH liveDocs;
+//                 nullptr: every doc), cut at max_doc.  A sub-tile without an accepted doc ends there.
+//   lane's view   bit j of a lane's 16-bit mask is doc base + lane + 64 j (the words transposed by readlane).  A range clause
+//                 narrows it: the lane's codes and `has` bits of the clause's column on the part's leaf, range_accepts_code.  Only
+//                 the 64-doc words that still hold an accepted doc are loaded, and a clause is evaluated only while some doc of the
+//                 sub-tile is accepted.  Columns are padded to whole sub-tiles: no bounds test.
+//   hits          the wave sum of the masks' popcounts: total_hits reads no column but the range clauses'.
+// A candidate key waits in a REGISTER for the round's meeting (16 keys per lane) where the text kernels leave it in the
+// accumulator's slot.  All writes are vector stores and atomics in plain HIP; every loop is bounded by a count known on entry.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "finalscore.hiph"
+#include "termstables.hiph"
+
+namespace nrtgpu {
+
+static_assert(kFinalSlots <= 16 && kMaxRanges <= 8, "a lane's view of a sub-tile is a 16-bit mask");
+
+// The lane's bit of each of the sub-tile's words: lane j (< kFinalSlots) holds word j as (lo, hi); bit j of the result is bit
+// `lane` of word j, i.e. doc base + lane + 64 j.  All lanes of the wave call.
+__device__ __forceinline__ uint32_t docset_lane_bits(uint32_t w_lo, uint32_t w_hi, uint32_t lane) {
+  const uint32_t sh = lane & 31u;
+  const bool low = lane < 32u;
+  uint32_t m = 0;
+#pragma unroll
+  for (int j = 0; j < kFinalSlots; ++j) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)w_lo, j), hi = (uint32_t)__builtin_amdgcn_readlane((int)w_hi, j);
+    m |= (((low ? lo : hi) >> sh) & 1u) << j;
+  }
+  return m;
+}
+
+// The sub-tile's accept words as the lane's view; words (uniform): bit j = word j holds an accepted doc.
+__device__ __forceinline__ uint32_t docset_accept(const DPart* part, uint32_t word0, uint32_t tile_len, uint32_t lane, uint32_t& words) {
+  const NRT_GLOBAL uint64_t* const live_bits = (const NRT_GLOBAL uint64_t*)part->live_bits;
+  uint64_t w = 0ull;
+  const uint32_t first = 64u * lane;   // the first doc of the lane's word inside the sub-tile
+  if (lane < (uint32_t)kFinalSlots && first < tile_len) {
+    w = live_bits != nullptr ? live_bits[word0 + lane] : ~0ull;
+    const uint32_t n = tile_len - first;   // the word's docs below max_doc: the tail word admits nothing at or beyond it
+    if (n < 64u) w &= (1ull << n) - 1ull;
+  }
+  words = (uint32_t)__ballot(w != 0ull) & ((1u << kFinalSlots) - 1u);
+  if (words == 0u) return 0u;   // uniform
+  return docset_lane_bits((uint32_t)w, (uint32_t)(w >> 32), lane);
+}
+
+// What is left of the lane's view: which words still hold an accepted doc, and the wave's accepted docs (both uniform).
+__device__ __forceinline__ void docset_census(uint32_t m, uint32_t& words, uint32_t& hits) {
+  words = 0u;
+  hits = 0u;
+#pragma unroll
+  for (int j = 0; j < kFinalSlots; ++j) {
+    const unsigned long long b = __ballot(((m >> j) & 1u) != 0u);
+    words |= (b != 0ull ? 1u : 0u) << j;
+    hits += (uint32_t)__popcll(b);
+  }
+}
+
+// A column over the sub-tile: the lane's codes of the words in `words` (the others read 0 and are never looked at) and the
+// lane's `has` bits; false: the leaf lacks the column.
+__device__ __forceinline__ bool docset_column(const DSortPart* sp, uint32_t base, uint32_t word0, uint32_t lane, uint32_t words,
+                                              uint32_t (&cv)[kFinalSlots], uint32_t& has_bits) {
+  const NRT_GLOBAL uint32_t* const col = (const NRT_GLOBAL uint32_t*)sp->code;
+  const NRT_GLOBAL uint64_t* const has = (const NRT_GLOBAL uint64_t*)sp->has;
+  if (col == nullptr) {   // uniform
+#pragma unroll
+    for (int j = 0; j < kFinalSlots; ++j) cv[j] = 0u;
+    has_bits = 0u;
+    return false;
+  }
+  uint64_t hw = 0ull;
+  if (has != nullptr && lane < (uint32_t)kFinalSlots) hw = has[word0 + lane];
+#pragma unroll
+  for (int j = 0; j < kFinalSlots; ++j) {
+    cv[j] = 0u;
+    if (((words >> j) & 1u) != 0u) cv[j] = col[base + lane + 64u * (uint32_t)j];   // uniform: a word without an accepted doc costs no load
+  }
+  has_bits = has != nullptr ? docset_lane_bits((uint32_t)hw, (uint32_t)(hw >> 32), lane) : (1u << kFinalSlots) - 1u;
+  return true;
+}
+
+// The sub-tile's hit set as the lane's view: the accept words narrowed by every range clause of the query in turn.  rparts: the
+// part's kMaxRanges column records.  words / hits: docset_census of the result.
+__device__ __forceinline__ uint32_t docset_hit_set(const DPart* part, const DRangeQuery* rq, const DSortPart* rparts, uint32_t base, uint32_t tile_len,
+                                                   uint32_t lane, uint32_t& words, uint32_t& hits) {
+  const uint32_t word0 = base >> 6;
+  hits = 0u;
+  uint32_t m = docset_accept(part, word0, tile_len, lane, words);
+  if (words == 0u) return 0u;   // uniform
+  const uint32_t n_ranges = min(rq->n_ranges, (uint32_t)kMaxRanges);
+#pragma unroll 1
+  for (uint32_t r = 0; r < n_ranges; ++r) {
+    uint32_t cv[kFinalSlots], has_bits;
+    if (!docset_column(rparts + r, base, word0, lane, words, cv, has_bits)) {   // no doc of the leaf has a value: none passes
+      words = hits = 0u;
+      return 0u;
+    }
+    const uint32_t lo = rq->lo_code[r], hi = rq->hi_code[r];
+    uint32_t pass = 0u;
+#pragma unroll
+    for (int j = 0; j < kFinalSlots; ++j) pass |= (range_accepts_code(lo, hi, cv[j]) ? 1u : 0u) << j;
+    m &= has_bits & pass;
+    docset_census(m, words, hits);
+    if (words == 0u) return 0u;   // uniform: the later clauses load nothing
+  }
+  if (n_ranges == 0u) docset_census(m, words, hits);
+  return m;
+}
+
+// The wave's candidate keys (registers; 0: none) into cand[pos ...], slot-major -- final_push_candidates for keys that never
+// lay in LDS.
+template <class S>
+__device__ __forceinline__ void docset_push_candidates(S& s, const uint64_t (&key)[kFinalSlots], uint32_t lane, uint32_t pos) {
+#pragma unroll
+  for (int j = 0; j < kFinalSlots; ++j) {
+    const unsigned long long b = __ballot(key[j] != 0ull);
+    if (key[j] != 0ull) {
+      const uint32_t at = pos + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+      if (at < (uint32_t)S::kCandCap) s.cand[at] = key[j];   // (always true: the caller made room)
+    }
+    pos += (uint32_t)__popcll(b);
+  }
+}
+
+typedef FinalSmem<kScanWaves, kFsCandCap> DocsetSortSmem;   // (its `cache` is carried but neither written nor read: no score is computed)
+
+__global__ __launch_bounds__(kScanThreads, kScanWaves / 4)
+void docset_sort_kernel(const DItem* __restrict__ items, const DPart* __restrict__ parts, const DQuery* __restrict__ queries,
+                        const DSortQuery* __restrict__ squeries, const DRangeQuery* __restrict__ rqueries, const DSortPart* __restrict__ sparts,
+                        const DSortPart* __restrict__ rparts, unsigned long long* __restrict__ theta_g, uint32_t* __restrict__ slice_sum,
+                        uint64_t* __restrict__ item_keys, uint32_t* __restrict__ item_counts, uint64_t* __restrict__ item_hits, uint32_t k_stride) {
+  __shared__ DocsetSortSmem s;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)), lane = tid & 63u;
+  const DItem* const item = items + blockIdx.x;
+  const uint32_t query = item->query, part_begin = item->part_begin, n_parts = item->n_parts;
+  const DQuery* const q = queries + query;
+  const uint32_t k = min(q->k, (uint32_t)kMaxK);
+  const DSortQuery* const sq = squeries + query;
+  const DRangeQuery* const rq = rqueries + query;
+  const uint32_t reverse = sq->reverse, missing_code = sq->missing_code;
+  const bool has_after = sq->has_after != 0u;
+  const uint64_t after_key = sq->after_key;
+  const bool multi_item = q->n_items > 1;
+  unsigned long long* const my_theta_g = theta_g + query;
+
+  if (tid < (uint32_t)kSliceSlots) s.slot_hits[tid] = s.slot_slice[tid] = 0u;
+  __syncthreads();
+
+  const uint32_t total_tiles = final_total_tiles(parts, part_begin, n_parts);
+  uint64_t theta = 0;   // uniform: the k-th best key known (this item's compactions, the query's other items)
+  uint32_t cnt = 0;     // uniform: keys in s.cand
+  uint32_t pi = 0;      // the part of the wave's sub-tile (indices only grow)
+  uint32_t par = 0;
+
+  for (uint32_t g0 = 0; g0 < total_tiles; g0 += (uint32_t)kScanWaves, par ^= 1u) {
+    if (multi_item) {   // what the query's other items have published (at least k docs of the query exceed it)
+      const uint64_t t = __hip_atomic_load(my_theta_g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      theta = t > theta ? t : theta;
+    }
+    const uint32_t g = g0 + wave;
+    uint32_t n_cand = 0;   // wave-uniform
+    uint64_t key[kFinalSlots];
+#pragma unroll
+    for (int j = 0; j < kFinalSlots; ++j) key[j] = 0ull;
+    if (g < total_tiles) {
+      const FinalTile tl = final_tile(parts, part_begin, n_parts, g, pi);
+      const uint32_t base = tl.base, gdoc0 = tl.gdoc0;
+      uint32_t words, hits;
+      const uint32_t m = docset_hit_set(tl.part, rq, rparts + (size_t)(part_begin + pi) * (size_t)kMaxRanges, base, tl.tile_len, lane, words, hits);
+      if (words != 0u) {   // uniform
+        uint32_t cv[kFinalSlots], has_bits;
+        docset_column(sparts + part_begin + pi, base, base >> 6, lane, words, cv, has_bits);   // (a leaf without the column: every doc sorts as the missing value)
+#pragma unroll
+        for (int j = 0; j < kFinalSlots; ++j) {
+          if (((m >> j) & 1u) != 0u) {
+            const uint32_t code = ((has_bits >> j) & 1u) != 0u ? cv[j] : missing_code;
+            const uint64_t doc_key = sort_key(reverse, code, gdoc0 + lane + 64u * (uint32_t)j);
+            if (doc_key > theta && (!has_after || doc_key < after_key)) key[j] = doc_key;   // (hits of earlier pages still count: `hits`)
+          }
+          n_cand += (uint32_t)__popcll(__ballot(key[j] != 0ull));
+        }
+        final_count_slice(s, tl.part, lane, hits);
+      }
+    }
+    if (lane == 0) s.wcount[par][wave] = n_cand;
+    __syncthreads();
+
+    // ---- the round's candidates into the shared buffer (fieldsort.hip's meeting, the keys read from registers)
+    uint32_t tot = 0, before = 0;
+#pragma unroll
+    for (uint32_t w2 = 0; w2 < (uint32_t)kScanWaves; ++w2) {
+      const uint32_t c = s.wcount[par][w2];
+      tot += c;
+      before += w2 < wave ? c : 0u;
+    }
+    if (cnt + tot <= (uint32_t)kFsCandCap) {   // uniform
+      docset_push_candidates(s, key, lane, cnt + before);
+      cnt += tot;
+    } else {
+      for (uint32_t w2 = 0; w2 < (uint32_t)kScanWaves; ++w2) {
+        const uint32_t c = s.wcount[par][w2];
+        if (cnt + c > (uint32_t)kFsCandCap) {   // uniform; cnt > k here (kFsCandCap >= kMaxK + kTileDocs)
+          __syncthreads();   // the keys appended so far are in place
+          uint64_t thr = 0;
+          cnt = topk_compact<kScanThreads, kFsCandCap>(s.cand, cnt, k, &s.sc, &thr);
+          if (thr > theta) theta = thr;
+          if (tid == 0) atomicMax(my_theta_g, (unsigned long long)thr);   // LazyMaxScoreAccumulator.accumulate analogue
+        }
+        if (wave == w2) docset_push_candidates(s, key, lane, cnt);
+        cnt += c;
+      }
+    }
+  }
+
+  final_epilogue(s, cnt, k, q, tid, slice_sum, item_keys, item_counts, item_hits, k_stride);
+}
+
+struct DocsetTermsSmem {
+  unsigned long long table[kTermsLdsSlots];     // the item's count table (plan.h), shared by the waves
+  uint32_t slot_hits[kSliceSlots];              // what final_count_slice and the epilogue read (finalscore.hiph: FinalSmem)
+  uint32_t slot_slice[kSliceSlots];
+};
+
+__global__ __launch_bounds__(kScanThreads, kScanWaves / 4)
+void docset_terms_count_kernel(const DItem* __restrict__ items, const DPart* __restrict__ parts, const DQuery* __restrict__ queries,
+                               const DTermsQuery* __restrict__ tqueries, const DRangeQuery* __restrict__ rqueries,
+                               const DSortPart* __restrict__ sparts, const DSortPart* __restrict__ rparts, DTermsState* __restrict__ states,
+                               unsigned long long* __restrict__ tables, uint32_t* __restrict__ slice_sum, uint32_t* __restrict__ item_counts,
+                               uint64_t* __restrict__ item_hits) {
+  __shared__ DocsetTermsSmem s;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)), lane = tid & 63u;
+  const DItem* const item = items + blockIdx.x;
+  const uint32_t query = item->query, part_begin = item->part_begin, n_parts = item->n_parts;
+  const DQuery* const q = queries + query;
+  const DTermsQuery* const tq = tqueries + query;
+  const DRangeQuery* const rq = rqueries + query;
+  const uint32_t max_buckets = tq->max_buckets, shift = tq->table_shift;
+  const uint32_t mask = (1u << (32u - shift)) - 1u;
+  unsigned long long* const table = tables + tq->table_off;
+  DTermsState* const st = states + query;
+
+  for (uint32_t i = tid; i < (uint32_t)kTermsLdsSlots; i += (uint32_t)kScanThreads) s.table[i] = 0ull;
+  if (tid < (uint32_t)kSliceSlots) s.slot_hits[tid] = s.slot_slice[tid] = 0u;
+  __syncthreads();
+
+  const uint32_t total_tiles = final_total_tiles(parts, part_begin, n_parts);
+  uint32_t pi = 0;      // the part of the wave's sub-tile (indices only grow)
+
+  for (uint32_t g = wave; g < total_tiles; g += (uint32_t)kScanWaves) {
+    const FinalTile tl = final_tile(parts, part_begin, n_parts, g, pi);
+    const uint32_t base = tl.base;
+    uint32_t words, hits;
+    const uint32_t m = docset_hit_set(tl.part, rq, rparts + (size_t)(part_begin + pi) * (size_t)kMaxRanges, base, tl.tile_len, lane, words, hits);
+    if (words == 0u) continue;   // uniform
+    final_count_slice(s, tl.part, lane, hits);
+    // an overflowed query's buckets are void: its items go on counting hits only (a flag read once, not waited for)
+    if (__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(&st->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0) continue;
+    uint32_t cv[kFinalSlots], has_bits;
+    if (!docset_column(sparts + part_begin + pi, base, base >> 6, lane, words, cv, has_bits)) continue;   // the leaf lacks the column: its hits add to no bucket
+    const uint32_t valued = m & has_bits;
+#pragma unroll
+    for (int j = 0; j < kFinalSlots; ++j)
+      if (((valued >> j) & 1u) != 0u) terms_lds_add(s.table, table, shift, mask, max_buckets, st, cv[j], 1u);
+  }
+
+  // ---- the item's table into the query's, once
+  __syncthreads();
+  if (__hip_atomic_load(&st->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
+    for (uint32_t i = tid; i < (uint32_t)kTermsLdsSlots; i += (uint32_t)kScanThreads) {
+      const unsigned long long w = s.table[i];
+      if (w != 0ull) terms_global_add(table, shift, mask, max_buckets, st, (uint32_t)w, (uint32_t)(w >> 32));
+    }
+  }
+
+  // ---- epilogue: final_epilogue's for an item without candidates
+  if (tid == 0) {
+    item_counts[blockIdx.x] = 0u;
+    uint32_t n = 0;
+    const uint32_t gte_floor = q->gte_floor, slice_base = q->slice_base;
+    for (int i = 0; i < kSliceSlots; ++i) {
+      const uint32_t h = s.slot_hits[i];
+      n += h;
+      if (h != 0u && gte_floor != 0xFFFFFFFFu) atomicAdd(&slice_sum[slice_base + s.slot_slice[i]], h);
+    }
+    item_hits[blockIdx.x] = n;
+  }
+}
+
+// terms_compact_kernel's launch (termscount.hip): the occupied slots of every query's table packed into `out`
+void launch_terms_compact(hipStream_t stream, const DTermsQuery* tqueries, DTermsState* states, const unsigned long long* tables, unsigned long long* out,
+                          uint32_t n_queries, uint32_t out_cap);
+
+void launch_docset_sort(hipStream_t stream, const FinalScoreArgs& a, const DSortQuery* squeries, const DRangeQuery* rqueries, const DSortPart* sparts,
+                        const DSortPart* rparts) {
+  if (a.n_items == 0) return;
+  hipLaunchKernelGGL(docset_sort_kernel, dim3(a.n_items), dim3(kScanThreads), 0, stream, a.items, a.parts, a.queries, squeries, rqueries, sparts, rparts,
+                     a.theta_g, a.slice_sum, a.item_keys, a.item_counts, a.item_hits, a.k_stride);
+}
+
+void launch_docset_terms_count(hipStream_t stream, const FinalScoreArgs& a, const DTermsQuery* tqueries, const DRangeQuery* rqueries, const DSortPart* sparts,
+                               const DSortPart* rparts, DTermsState* states, unsigned long long* tables, unsigned long long* out, uint32_t n_queries,
+                               uint32_t out_cap) {
+  if (a.n_items != 0)
+    hipLaunchKernelGGL(docset_terms_count_kernel, dim3(a.n_items), dim3(kScanThreads), 0, stream, a.items, a.parts, a.queries, tqueries, rqueries, sparts,
+                       rparts, states, tables, a.slice_sum, a.item_counts, a.item_hits);
+  launch_terms_compact(stream, tqueries, states, tables, out, n_queries, out_cap);
+}
+
+}  // namespace nrtgpu

@@ -42,17 +42,7 @@ int doc_values_kind(const nrtgpu_seg* const* segs, int32_t n_segs, int32_t field
   return NRTGPU_OK;
 }
 
-// What both routes refuse of one query as unsupported (kind: doc_values_kind's; under: "a sort" / "a terms count"); *need: the
-// clauses a hit matches at least; the copy that is planned on the way.
-int doc_values_query(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query& q, int qi, int kind, int32_t field_id, const char* under,
-                     uint32_t* need, FlatQueries* flat) {
-  if (kind < 0) return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: no leaf of the call holds doc values of field %d", qi, field_id);
-  if (q.disjunction_max != 0 || q.tie_breaker != 0.0f)
-    return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: a DisjunctionMaxQuery under %s (pass its clauses as a plain disjunction: scores are not read)", qi, under);
-  int n_must = 0;
-  for (int t = 0; t < q.n_terms; ++t) n_must += q.terms[t].occur;
-  if (n_must != 0 && n_must != q.n_terms) return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: MUST next to SHOULD clauses under %s", qi, under);
-  if (q.min_competitive_score != 0.0f) return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: a min_competitive_score under %s", qi, under);
+int doc_values_masks_resident(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query& q, int qi) {
   auto resident = [&](int32_t id, const char* what) -> int {
     for (int si = 0; id != 0 && si < n_segs; ++si)
       if (segs[si]->masks.find(id) == segs[si]->masks.end())
@@ -65,6 +55,21 @@ int doc_values_query(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu
     if (int rc = resident(q.more_filters[i], "filter")) return rc;
   for (int i = 0; i < q.n_more_must_not; ++i)
     if (int rc = resident(q.more_must_not[i], "must_not")) return rc;
+  return NRTGPU_OK;
+}
+
+// What both routes refuse of one query as unsupported (kind: doc_values_kind's; under: "a sort" / "a terms count"); *need: the
+// clauses a hit matches at least; the copy that is planned on the way.
+int doc_values_query(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query& q, int qi, int kind, int32_t field_id, const char* under,
+                     uint32_t* need, FlatQueries* flat) {
+  if (kind < 0) return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: no leaf of the call holds doc values of field %d", qi, field_id);
+  if (q.disjunction_max != 0 || q.tie_breaker != 0.0f)
+    return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: a DisjunctionMaxQuery under %s (pass its clauses as a plain disjunction: scores are not read)", qi, under);
+  int n_must = 0;
+  for (int t = 0; t < q.n_terms; ++t) n_must += q.terms[t].occur;
+  if (n_must != 0 && n_must != q.n_terms) return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: MUST next to SHOULD clauses under %s", qi, under);
+  if (q.min_competitive_score != 0.0f) return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: a min_competitive_score under %s", qi, under);
+  if (int rc = doc_values_masks_resident(segs, n_segs, q, qi)) return rc;
   *need = n_must != 0 ? (uint32_t)q.n_terms : (uint32_t)std::max(q.min_should_match, 1);
   nrtgpu_bm25_query f = q;
   flat->terms.emplace_back(q.terms, q.terms + q.n_terms);
@@ -72,6 +77,21 @@ int doc_values_query(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu
   f.min_should_match = 0;
   flat->queries.push_back(f);
   return NRTGPU_OK;
+}
+
+// What the sorted routes refuse of a nrtgpu_field_sort as an invalid argument, and its side of the query's record (kind: of the
+// column over the leaves; `need` is the caller's).
+int field_sort_check(const nrtgpu_field_sort& s, int qi) {
+  if (s.reverse != 0 && s.reverse != 1) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: reverse %d outside 0..1", qi, s.reverse);
+  if (s.has_after != 0 && s.has_after != 1) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: the sort's has_after %d outside 0..1", qi, s.has_after);
+  if (s.has_after != 0 && s.after_doc < 0) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: after_doc %d", qi, s.after_doc);
+  return NRTGPU_OK;
+}
+void field_sort_record(const nrtgpu_field_sort& s, int kind, DSortQuery* r) {
+  r->reverse = (uint32_t)s.reverse;
+  r->missing_code = doc_value_code(kind, s.missing_bits);
+  r->has_after = (uint32_t)s.has_after;
+  r->after_key = s.has_after ? sort_key(r->reverse, doc_value_code(kind, s.after_bits), (uint32_t)s.after_doc) : ~0ull;
 }
 
 // The column of every part's leaf (field_ids: per query).  A part names its (query, leaf) pair by its first DTerm (HostPlan.qs_begin).
@@ -108,9 +128,7 @@ int check_call(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, c
     const nrtgpu_bm25_query& q = queries[qi];
     const nrtgpu_field_sort& s = sorts[qi];
     if (int rc = validate_query(q, qi)) return rc;
-    if (s.reverse != 0 && s.reverse != 1) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: reverse %d outside 0..1", qi, s.reverse);
-    if (s.has_after != 0 && s.has_after != 1) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: the sort's has_after %d outside 0..1", qi, s.has_after);
-    if (s.has_after != 0 && s.after_doc < 0) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: after_doc %d", qi, s.after_doc);
+    if (int rc = field_sort_check(s, qi)) return rc;
     if (q.has_after != 0) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: the query's has_after must be 0 (the cursor of a sorted search lives in the sort)", qi);
     int kind = -1;
     if (int rc = doc_values_kind(segs, n_segs, s.field_id, qi, &kind)) return rc;
@@ -122,10 +140,7 @@ int check_call(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, c
     const int kind = (*kinds)[(size_t)qi];
     DSortQuery r{};
     if (int rc = doc_values_query(segs, n_segs, queries[qi], qi, kind, s.field_id, "a sort", &r.need, flat)) return rc;
-    r.reverse = (uint32_t)s.reverse;
-    r.missing_code = doc_value_code(kind, s.missing_bits);
-    r.has_after = (uint32_t)s.has_after;
-    r.after_key = s.has_after ? sort_key(r.reverse, doc_value_code(kind, s.after_bits), (uint32_t)s.after_doc) : ~0ull;
+    field_sort_record(s, kind, &r);
     if (records) records->push_back(r);
   }
   for (int qi = 0; qi < n_queries; ++qi) flat->queries[(size_t)qi].terms = flat->terms[(size_t)qi].data();   // (the vectors have settled)

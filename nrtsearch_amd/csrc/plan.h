@@ -734,4 +734,23 @@ struct alignas(16) DTermsState {   // per query, zeroed per call; one more behin
 };
 static_assert(sizeof(DTermsState) == 16, "DTermsState layout");
 
+// Doc-set requests (docset.hip: docset_sort_kernel, docset_terms_count_kernel; docset.cpp): a sorted search or a terms count
+// whose hit set is a doc set -- liveDocs, FILTER / MUST_NOT masks, numeric range clauses -- and no text clause.  The parts of
+// such a plan have no clauses (n_terms == 0) and DPart.live_bits is the query's combined accept set WITH liveDocs (there are no
+// postings to fold them into; nullptr: every doc below max_doc).  Beside the plan go the sorted / counting route's own records
+// (DSortQuery / DTermsQuery per query, `need` unread; one DSortPart per part for the sort / count column), one DRangeQuery per
+// query and kMaxRanges DSortPart per part (entry part * kMaxRanges + clause: the clause's column on the part's leaf).
+// A range clause keeps a doc iff the doc HAS a value in the clause's column and code(lower) <= code(value) <= code(upper)
+// (doc_value_code: unsigned compares of codes are Integer.compare / Float.compare of the values).  code(lower) > code(upper)
+// keeps nothing.  The ONE statement of it: both kernels and nrtgpu_range_accepts call range_accepts_code.
+constexpr int kMaxRanges = 4;   // NRTGPU_MAX_RANGES
+__host__ __device__ inline bool range_accepts_code(uint32_t lo_code, uint32_t hi_code, uint32_t code) { return code >= lo_code && code <= hi_code; }
+struct alignas(16) DRangeQuery {
+  uint32_t n_ranges;            // 0..kMaxRanges
+  uint32_t pad[3];
+  uint32_t lo_code[kMaxRanges];
+  uint32_t hi_code[kMaxRanges];
+};
+static_assert(sizeof(DRangeQuery) == 48, "DRangeQuery layout");
+
 }  // namespace nrtgpu

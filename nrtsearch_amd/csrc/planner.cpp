@@ -489,6 +489,38 @@ static void resolve_queries(LeafSetCache& lsc, const nrtgpu_seg* const* segs, in
   }
 }
 
+// The searcher's slices over the leaves of a call (MyIndexSearcher.slices / slicesForShards): slice_of_leaf[i] for every leaf,
+// and how many there are (at least 1).
+static int32_t searcher_slices(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, std::vector<int32_t>& slice_of_leaf) {
+  slice_of_leaf.assign((size_t)std::max(n_segs, 1), 0);
+  int32_t n_slices = 1;
+  if (n_segs > 0 && (int32_t)g_thread_slices.size() == n_segs) {
+    // the caller's slices (nrtgpu_set_thread_slices: a call over a subset of the searcher's leaves counts by the WHOLE searcher's
+    // slices), renumbered densely in order of first appearance
+    std::unordered_map<int32_t, int32_t> dense;
+    for (int32_t i = 0; i < n_segs; ++i) {
+      auto it = dense.emplace(g_thread_slices[(size_t)i], (int32_t)dense.size()).first;
+      slice_of_leaf[(size_t)i] = it->second;
+    }
+    n_slices = (int32_t)std::max<size_t>(dense.size(), 1);
+  } else if (ctx->slice_max_docs.load() > 0 && n_segs > 0) {
+    std::vector<hostmath::LeafInfo> all((size_t)n_segs);
+    int32_t base = 0;
+    for (int32_t i = 0; i < n_segs; ++i) {
+      all[(size_t)i] = {i, segs[i]->max_doc, segs[i]->max_doc - segs[i]->n_deleted, doc_bases ? doc_bases[i] : base};
+      base += segs[i]->max_doc;
+    }
+    const int32_t vs = ctx->virtual_shards.load();
+    const std::vector<std::vector<int32_t>> sl = vs > 1
+        ? hostmath::slices_for_shards(all, vs, ctx->slice_max_docs.load(), ctx->slice_max_segments.load(), nullptr)
+        : hostmath::slices(all, ctx->slice_max_docs.load(), ctx->slice_max_segments.load(), all);
+    n_slices = (int32_t)std::max<size_t>(sl.size(), 1);
+    for (size_t s_ = 0; s_ < sl.size(); ++s_)
+      for (int32_t li : sl[s_]) slice_of_leaf[(size_t)li] = (int32_t)s_;
+  }
+  return n_slices;
+}
+
 int nrtgpu::rt::build_plan(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
                       const nrtgpu_bm25_query* queries, int32_t n_queries, HostPlan& hp, int prune, const PlanKeepLeaf* keep) {
   const double t_entry = now_ms();
@@ -552,32 +584,8 @@ int nrtgpu::rt::build_plan(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const
   std::vector<int32_t> n_deleted((size_t)std::max(n_segs, 1), 0);
   for (int si = 0; si < n_segs; ++si) n_deleted[(size_t)si] = segs[si]->n_deleted;
   // the searcher's slices over these leaves (MyIndexSearcher.slices / slicesForShards): relation and route depend on them
-  std::vector<int32_t> slice_of_leaf((size_t)std::max(n_segs, 1), 0);
-  int32_t n_slices = 1;
-  if (n_segs > 0 && (int32_t)g_thread_slices.size() == n_segs) {
-    // the caller's slices (nrtgpu_set_thread_slices: a call over a subset of the searcher's leaves counts by the WHOLE searcher's
-    // slices), renumbered densely in order of first appearance
-    std::unordered_map<int32_t, int32_t> dense;
-    for (int32_t i = 0; i < n_segs; ++i) {
-      auto it = dense.emplace(g_thread_slices[(size_t)i], (int32_t)dense.size()).first;
-      slice_of_leaf[(size_t)i] = it->second;
-    }
-    n_slices = (int32_t)std::max<size_t>(dense.size(), 1);
-  } else if (ctx->slice_max_docs.load() > 0 && n_segs > 0) {
-    std::vector<hostmath::LeafInfo> all((size_t)n_segs);
-    int32_t base = 0;
-    for (int32_t i = 0; i < n_segs; ++i) {
-      all[(size_t)i] = {i, segs[i]->max_doc, segs[i]->max_doc - segs[i]->n_deleted, doc_bases ? doc_bases[i] : base};
-      base += segs[i]->max_doc;
-    }
-    const int32_t vs = ctx->virtual_shards.load();
-    const std::vector<std::vector<int32_t>> sl = vs > 1
-        ? hostmath::slices_for_shards(all, vs, ctx->slice_max_docs.load(), ctx->slice_max_segments.load(), nullptr)
-        : hostmath::slices(all, ctx->slice_max_docs.load(), ctx->slice_max_segments.load(), all);
-    n_slices = (int32_t)std::max<size_t>(sl.size(), 1);
-    for (size_t s_ = 0; s_ < sl.size(); ++s_)
-      for (int32_t li : sl[s_]) slice_of_leaf[(size_t)li] = (int32_t)s_;
-  }
+  std::vector<int32_t> slice_of_leaf;
+  const int32_t n_slices = searcher_slices(ctx, segs, doc_bases, n_segs, slice_of_leaf);
   auto work = [&](int t) {
     resolve_queries(*hp.lsc, segs, n_segs, n_deleted.data(), slice_of_leaf.data(), n_slices, queries, chunk_begin(t), chunk_begin(t + 1), pieces[(size_t)t],
                     q_qs_begin.data(), q_qs_cnt.data(), hp.qs_begin.data(), hp.qexpand.data(), cache_base, qtabs, prune, hp.q_lower, hp.q_route, q_ms_key, keep);
@@ -903,5 +911,158 @@ int nrtgpu::rt::build_plan(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const
   if (plan_trace)
     fprintf(stderr, "[nrtgpu plan] %d queries: head %.3f ms, resolve %.3f ms (%d threads), concat %.3f, cut+items %.3f; %zu terms %zu parts %zu items\n",
             n_queries, tp0 - t_entry, tp1 - tp0, n_thr, tp2 - tp1, now_ms() - tp2, (size_t)hp.n_dterms, hp.parts.size(), hp.items.size());
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the plan of a doc-set call (docset.cpp)
+// ------------------------------------------------------------------------------------------------
+// A doc-set query has no clause: its parts cover every tile of every leaf, carry no DTerm (n_terms == 0: no placeholder term any
+// leaf could hold) and name the query's combined accept set WITH liveDocs in DPart.live_bits -- there are no postings they could
+// be folded into.  What final_score_run reads of a HostPlan is filled as build_plan fills it: the items in launch order, list_idx /
+// q_base / q_nlists / q_k for the merge, theta_init (zeros), the slices, part_leaf.  The cost of a query is its tiles (every
+// query of a call walks the same leaves); an item is never shorter than kDocsetMinItemTiles sub-tiles, a query is cut only when
+// it alone exceeds its fair share of the call on one CU (hostmath::plan_item_counts, the rule of the text routes).
+static const int64_t kDocsetMinItemTiles = 64;
+
+int nrtgpu::rt::docset_plan(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, const nrtgpu_bm25_query* queries,
+                            int32_t n_queries, HostPlan& hp) {
+  uint32_t kmax = 1;
+  for (int qi = 0; qi < n_queries; ++qi) kmax = std::max<uint32_t>(kmax, (uint32_t)queries[qi].k);
+  for (int si = 0; si < n_segs; ++si) {
+    if (!segs[si]) return fail(NRTGPU_ERR_INVALID_ARG, "segment %d is NULL", si);
+    if (!segs[si]->sealed) return fail(NRTGPU_ERR_STATE, "segment %d is not sealed", si);
+    if (segs[si]->ctx != ctx) return fail(NRTGPU_ERR_INVALID_ARG, "segment %d belongs to another context", si);
+  }
+  hp.k_stride = round_up(kmax, 16);
+  hp.queries.assign((size_t)n_queries, DQuery{});
+  hp.q_k.assign((size_t)n_queries, 0u);
+  hp.theta_init.assign((size_t)n_queries, 0ull);
+  hp.n_leaves = (uint32_t)n_segs;
+  hp.qexpand.assign((size_t)n_queries, DQExpand{});
+  hp.qs_begin.assign((size_t)n_queries * (size_t)std::max(n_segs, 1), 0xFFFFFFFFu);
+  hp.q_lower.assign((size_t)n_queries, 0);
+  hp.q_route.assign((size_t)n_queries, kRouteScan);
+  hp.q_wins.assign((size_t)n_queries, 0u);
+  hp.fixed_point = (ctx->cfg.flags & NRTGPU_FLAG_NO_FIXED_POINT) == 0;   // (statistics only: the route sums nothing)
+  std::vector<int32_t> slice_of_leaf;
+  const int32_t n_slices = searcher_slices(ctx, segs, doc_bases, n_segs, slice_of_leaf);
+  hp.n_slices = (uint32_t)n_slices;
+  // the leaves in visiting order: slice by slice, so that a slice's parts are neighbours
+  std::vector<int32_t> order((size_t)n_segs);
+  for (int32_t si = 0; si < n_segs; ++si) order[(size_t)si] = si;
+  if (n_slices > 1) std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return slice_of_leaf[(size_t)a] < slice_of_leaf[(size_t)b]; });
+  int64_t tiles = 0;
+  for (int32_t si = 0; si < n_segs; ++si) tiles += segs[si]->n_tiles;
+  std::vector<int64_t> q_costs((size_t)n_queries, tiles), q_items((size_t)n_queries, 0);
+  const int64_t target_items = ctx->cfg.target_items > 0 ? ctx->cfg.target_items : (int64_t)std::max(ctx->n_cus, 1);
+  hostmath::plan_item_counts(q_costs.data(), n_queries, target_items, kDocsetMinItemTiles, q_items.data());
+
+  struct Pending { int64_t cost; uint32_t query; uint32_t part_begin, n_parts; uint32_t tiles; int32_t first_slice, last_slice; uint32_t n_slices; };
+  std::vector<Pending> pend;
+  hp.parts.reserve((size_t)n_queries * (size_t)std::max(n_segs, 1));
+  for (int qi = 0; tiles > 0 && qi < n_queries; ++qi) {
+    const nrtgpu_bm25_query& q = queries[qi];
+    const bool masked = q.filter_mask != 0 || q.must_not_mask != 0 || q.n_more_filters != 0 || q.n_more_must_not != 0;
+    const double budget = (double)tiles / (double)std::max<int64_t>(q_items[(size_t)qi], 1);
+    Pending cur{0, (uint32_t)qi, (uint32_t)hp.parts.size(), 0, 0, -1, -1, 0};
+    double filled = 0.0;
+    auto close_item = [&]() {
+      pend.push_back(cur);
+      cur = Pending{0, (uint32_t)qi, (uint32_t)hp.parts.size(), 0, 0, -1, -1, 0};
+      filled = 0.0;
+    };
+    for (int32_t oi = 0; oi < n_segs; ++oi) {
+      const int32_t si = order[(size_t)oi];
+      const nrtgpu_seg* seg = segs[si];
+      if (seg->n_tiles == 0) continue;
+      const int32_t sl = slice_of_leaf[(size_t)si];
+      if (cur.n_parts > 0 && sl != cur.last_slice && cur.n_slices == (uint32_t)kSliceSlots) close_item();   // no slot left for another slice
+      const uint64_t* accept = seg->d_live;   // nullptr: every doc is live
+      if (masked)
+        if (int rc = accept_set_of(seg, q, &accept)) return rc;
+      uint32_t tb = 0;
+      while (tb < seg->n_tiles) {
+        uint32_t take = (uint32_t)std::max(1.0, std::floor(budget - filled + 0.5));
+        take = std::min<uint32_t>(take, seg->n_tiles - tb);
+        if (cur.n_parts == 0) cur.first_slice = sl;
+        if (sl != cur.last_slice) { cur.n_slices++; cur.last_slice = sl; }
+        DPart p{};
+        p.live_bits = accept;
+        p.term_begin = 0;
+        p.n_terms = 0;
+        p.tile_begin = tb;
+        p.tile_end = tb + take;
+        p.max_doc = (uint32_t)seg->max_doc;
+        p.doc_base = doc_bases ? doc_bases[si] : 0;
+        p.tile_offset = cur.tiles;
+        p.slice = (uint32_t)sl;   // (the slot is assigned once the items are final, below)
+        hp.parts.push_back(p);
+        hp.part_leaf.push_back(si);
+        cur.n_parts++;
+        cur.tiles += take;
+        cur.cost += take;
+        filled += take;
+        tb += take;
+        if (filled >= budget * 0.999) close_item();   // item full
+      }
+    }
+    if (cur.n_parts > 0) {
+      // a short remainder (the tile rounding of the items before it) joins the item before it, as in build_plan
+      if (!pend.empty() && pend.back().query == (uint32_t)qi && (double)cur.cost < 0.5 * budget &&
+          pend.back().part_begin + pend.back().n_parts == cur.part_begin &&
+          pend.back().n_slices + cur.n_slices - (pend.back().last_slice == cur.first_slice ? 1u : 0u) <= (uint32_t)kSliceSlots) {
+        Pending& prev = pend.back();
+        for (uint32_t pi2 = 0; pi2 < cur.n_parts; ++pi2) hp.parts[cur.part_begin + pi2].tile_offset += prev.tiles;
+        prev.n_slices += cur.n_slices - (prev.last_slice == cur.first_slice ? 1u : 0u);
+        prev.last_slice = cur.last_slice;
+        prev.n_parts += cur.n_parts;
+        prev.tiles += cur.tiles;
+        prev.cost += cur.cost;
+      } else {
+        pend.push_back(cur);
+      }
+    }
+  }
+  // the slot of every part: the running number of its slice among the item's slices (a slice's parts are neighbours)
+  for (const Pending& a : pend) {
+    uint32_t slot = 0;
+    for (uint32_t pi2 = 0; pi2 < a.n_parts; ++pi2) {
+      DPart& p = hp.parts[a.part_begin + pi2];
+      if (pi2 > 0 && p.slice != (hp.parts[a.part_begin + pi2 - 1].slice & 0xFFFFFFu)) ++slot;
+      p.slice |= slot << 24;
+    }
+  }
+  // longest first, as in build_plan; an item's output slot is assigned after the sort
+  std::stable_sort(pend.begin(), pend.end(), [](const Pending& a, const Pending& b) { return a.cost > b.cost; });
+  hp.items.resize(pend.size());
+  hp.q_base.assign((size_t)n_queries, 0);
+  hp.q_nlists.assign((size_t)n_queries, 0);
+  for (const Pending& a : pend) hp.q_nlists[a.query]++;
+  {
+    uint32_t run = 0;
+    for (int qi = 0; qi < n_queries; ++qi) { hp.q_base[(size_t)qi] = run; run += hp.q_nlists[(size_t)qi]; }
+  }
+  hp.list_idx.assign(pend.size(), 0);
+  std::vector<uint32_t> q_fill((size_t)n_queries, 0);
+  for (size_t i = 0; i < pend.size(); ++i) {
+    DItem it{};
+    it.query = pend[i].query;
+    it.part_begin = pend[i].part_begin;
+    it.n_parts = pend[i].n_parts;
+    it.peer_slot = hp.q_base[pend[i].query] + q_fill[pend[i].query]++;
+    hp.items[i] = it;
+    hp.list_idx[it.peer_slot] = (uint32_t)i;
+  }
+  for (int qi = 0; qi < n_queries; ++qi) {
+    const nrtgpu_bm25_query& q = queries[qi];
+    hp.q_k[(size_t)qi] = (uint32_t)q.k;
+    DQuery& dq = hp.queries[(size_t)qi];
+    dq.k = (uint32_t)q.k;
+    dq.item_begin = hp.q_base[(size_t)qi];
+    dq.n_items = hp.q_nlists[(size_t)qi];
+    dq.gte_floor = q.total_hits_threshold == INT32_MAX ? 0xFFFFFFFFu : (uint32_t)std::max(q.total_hits_threshold, q.k);
+    dq.slice_base = (uint32_t)qi * hp.n_slices;
+  }
   return 0;
 }

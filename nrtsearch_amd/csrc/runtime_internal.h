@@ -5,7 +5,8 @@
 // plan), search.cpp (BM25 entry points, hybrid tail, merge), coalescer.h (request coalescing: the leader/follower mechanism behind
 // the single-query entries of search.cpp and vectors.cpp; standard library only), finalscore.cpp (the host
 // path of the final-score routes), funcscore.cpp (function-score queries), multimatch.cpp (multi-match queries),
-// fieldsort.cpp (a text query's hits sorted by a doc value column), termscount.cpp (its hits counted per value of one), vectors.cpp (exact kNN, vector rescoring).  Types the ABI names opaquely (nrtgpu_ctx, nrtgpu_seg) live in the global namespace;
+// fieldsort.cpp (a text query's hits sorted by a doc value column), termscount.cpp (its hits counted per value of one),
+// docset.cpp (both over a doc set without a text clause), vectors.cpp (exact kNN, vector rescoring).  Types the ABI names opaquely (nrtgpu_ctx, nrtgpu_seg) live in the global namespace;
 // everything else in nrtgpu::rt.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -65,6 +66,13 @@ void launch_bm25_field_sort(hipStream_t stream, const FinalScoreArgs& a, const D
 // queries' tables into `out` (out_cap entries)
 void launch_bm25_terms_count(hipStream_t stream, const FinalScoreArgs& a, const DTermsQuery* tqueries, const DSortPart* sparts, DTermsState* states,
                              unsigned long long* tables, unsigned long long* out, uint32_t n_queries, uint32_t out_cap);
+// doc-set requests (docset.hip): the sorted / counting route's per-query record, one DRangeQuery per query, one DSortPart per part
+// for the sort / count column and kMaxRanges per part for the range clauses' columns
+void launch_docset_sort(hipStream_t stream, const FinalScoreArgs& a, const DSortQuery* squeries, const DRangeQuery* rqueries, const DSortPart* sparts,
+                        const DSortPart* rparts);
+void launch_docset_terms_count(hipStream_t stream, const FinalScoreArgs& a, const DTermsQuery* tqueries, const DRangeQuery* rqueries, const DSortPart* sparts,
+                               const DSortPart* rparts, DTermsState* states, unsigned long long* tables, unsigned long long* out, uint32_t n_queries,
+                               uint32_t out_cap);
 #ifdef NRTGPU_DEV
 void launch_debug_wave_kth(hipStream_t stream, const uint64_t* keys, uint32_t n, uint32_t r, uint64_t* out);   // (maxscore.hip: topk_kth_wave on its own)
 void launch_debug_walk_value(hipStream_t stream, float weight, const uint32_t* freq, const uint32_t* norm, const float* table, int fx_scale,
@@ -1031,6 +1039,12 @@ int build_plan(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* do
 // the query's terms; a query none of whose terms any leaf holds is then planned over its kept leaves.  Plans built without it
 // are what they were.
 
+// The plan of a doc-set call (docset.cpp): parts without clauses over every tile of every leaf, DPart.live_bits = the query's
+// combined accept set with liveDocs.  Of queries[i] only k, total_hits_threshold and the mask fields are read (the masks must be
+// resident).  Fills what final_score_run reads of a HostPlan, part_leaf included.
+int docset_plan(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, const nrtgpu_bm25_query* queries,
+                int32_t n_queries, HostPlan& hp);
+
 // ---- the text routes' plan blob and workspace (search.cpp: enqueue_search; finalscore.cpp: enqueue_final_score) -----------------
 // One layout for every route: the twelve plan arrays of a HostPlan in upload order, and the seven workspace regions every route
 // has (per-slot outputs of the scorers, the merge's outputs, the expanded DTerm records).  A route appends what is its own with
@@ -1108,7 +1122,7 @@ struct PlanBytes {   // an array of the route's own, appended to the plan buffer
   const void* p;
   size_t bytes;
 };
-const int kFinalScoreExtras = 3;   // at most: two per-query record arrays (the groups', the functions'), one per-part array
+const int kFinalScoreExtras = 4;   // at most: two per-query record arrays and two per-part arrays (docset.cpp)
 // the route's scorer: d_extra[i] = the device address of extras[i]
 typedef void (*FinalScoreLaunch)(hipStream_t, const FinalScoreArgs&, const void* const* d_extra);
 // From "the plan and the route's records exist" to "out[], the diagnostics and the statistics are filled": workspace, plan upload,
@@ -1158,9 +1172,34 @@ int doc_values_kind(const nrtgpu_seg* const* segs, int32_t n_segs, int32_t field
 // clauses a hit matches at least; the query's flat copy is pushed
 int doc_values_query(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query& q, int qi, int kind, int32_t field_id, const char* under,
                      uint32_t* need, FlatQueries* flat);
+// what the sorted routes (this one; docset.cpp) refuse of a nrtgpu_field_sort as an invalid argument, and its side of the record
+int field_sort_check(const nrtgpu_field_sort& s, int qi);
+void field_sort_record(const nrtgpu_field_sort& s, int kind, DSortQuery* r);
+// the FILTER / MUST_NOT masks of q are resident on every leaf of the call, else NRTGPU_ERR_UNSUPPORTED naming the query (what
+// doc_values_query refuses of them; docset.cpp asks the same of a doc-set query's masks)
+int doc_values_masks_resident(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query& q, int qi);
 // the column of every part's leaf, for a plan of the flat copies (field_ids: per query)
 int doc_values_parts(const nrtgpu_seg* const* segs, int32_t n_segs, const int32_t* field_ids, const HostPlan& hp, const char* route,
                      std::vector<DSortPart>* out);
+
+// termscount.cpp: what the routes that fill count tables share (a text query's hits there; a doc set's in docset.cpp).
+// Where the route's own workspace bytes lie (offsets from FinalScoreArgs.own), and what comes back from them.
+struct TermsWork {
+  int32_t n_queries = 0;
+  size_t o_states = 0, o_tables = 0, o_out = 0, bytes = 0;
+  uint32_t out_cap = 0;    // entries `out` holds: sum of max_buckets
+  std::vector<DTermsState> states;     // terms_collect(): n_queries + 1
+  std::vector<uint64_t> entries;       // terms_collect(): states[n_queries].claimed
+  void layout(int32_t n_queries, uint64_t slots, uint64_t cap);
+};
+// what both refuse of (terms[qi], out[qi]) as an invalid argument (out: nullptr for the predicates), the column's kind over the
+// leaves, the query's record with its table behind the earlier queries' (*slots, *cap: the call's running sums)
+int terms_count_record(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_terms_count& t, const nrtgpu_term_counts* out, int qi, uint64_t* slots,
+                       uint64_t* cap, DTermsQuery* record, int* kind);
+// FinalScoreOwn.collect of both (user: the call's TermsWork): the states, then the entries that exist
+int terms_collect(nrtgpu_ctx* ctx, Slot* slot, const char* d_own, void* user);
+// the call's answers from what terms_collect brought back and the merge's (empty) lists
+int terms_unpack(const TermsWork& work, const std::vector<int>& kinds, const nrtgpu_topdocs* pages, int32_t n_queries, nrtgpu_term_counts* out);
 
 }  // namespace rt
 }  // namespace nrtgpu

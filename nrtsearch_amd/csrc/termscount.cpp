@@ -18,16 +18,90 @@ static_assert(sizeof(nrtgpu_term_counts) == 48 && offsetof(nrtgpu_term_counts, v
               "nrtgpu_term_counts layout");
 static_assert(NRTGPU_MAX_TERM_BUCKETS == kTermsMaxBuckets, "NRTGPU_MAX_TERM_BUCKETS");
 
-namespace {
+namespace nrtgpu {
+namespace rt {
 
-// Where the route's own workspace bytes lie (offsets from FinalScoreArgs.own), and what comes back from them.
-struct TermsWork {
-  int32_t n_queries = 0;
-  size_t o_states = 0, o_tables = 0, o_out = 0, bytes = 0;
-  uint32_t out_cap = 0;    // entries `out` holds: sum of max_buckets
-  std::vector<DTermsState> states;     // collect(): n_queries + 1
-  std::vector<uint64_t> entries;       // collect(): states[n_queries].claimed
-};
+// ---- what the routes that fill count tables share (this file: a text query's hits; docset.cpp: a doc set) -----------------------
+void TermsWork::layout(int32_t n, uint64_t slots, uint64_t cap) {
+  Carver c;
+  n_queries = n;
+  o_states = c.take(((size_t)n + 1) * sizeof(DTermsState));
+  o_tables = c.take((size_t)slots * 8);
+  o_out = c.take((size_t)cap * 8);
+  bytes = c.off;
+  out_cap = (uint32_t)cap;   // (<= 2^24: half the slots)
+}
+
+// What the routes refuse of (terms[qi], out[qi]) as an invalid argument, the kind of the column over the leaves, and the query's
+// record with its table laid out behind the earlier queries' (*slots, *cap: the call's running sums).
+int terms_count_record(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_terms_count& t, const nrtgpu_term_counts* out, int qi, uint64_t* slots,
+                       uint64_t* cap, DTermsQuery* record, int* kind) {
+  if (t.max_buckets < 1 || t.max_buckets > NRTGPU_MAX_TERM_BUCKETS)
+    return fail(NRTGPU_ERR_INVALID_ARG, "query %d: max_buckets %d outside 1..%d", qi, t.max_buckets, NRTGPU_MAX_TERM_BUCKETS);
+  if (out && (out->capacity < t.max_buckets || !out->value_bits || !out->counts))
+    return fail(NRTGPU_ERR_INVALID_ARG, "query %d: an output of capacity %d (or NULL arrays) for max_buckets %d", qi, out->capacity, t.max_buckets);
+  if (int rc = doc_values_kind(segs, n_segs, t.field_id, qi, kind)) return rc;
+  DTermsQuery r{};
+  r.max_buckets = (uint32_t)t.max_buckets;
+  r.table_shift = terms_table_shift(r.max_buckets);
+  r.table_off = (uint32_t)*slots;
+  *slots += 1ull << (32u - r.table_shift);
+  *cap += r.max_buckets;
+  if (*slots > kTermsMaxCallSlots)
+    return fail(NRTGPU_ERR_INVALID_ARG, "query %d: the count tables of the call exceed the workspace bound of %llu slots (a query takes the power of two >= 2 x max_buckets)",
+                qi, (unsigned long long)kTermsMaxCallSlots);
+  *record = r;
+  return NRTGPU_OK;
+}
+
+// Behind the wait: the states, then the entries that exist.
+int terms_collect(nrtgpu_ctx* ctx, Slot* slot, const char* d_own, void* user) {
+  TermsWork* w = (TermsWork*)user;
+  const bool blocking = (ctx->cfg.flags & NRTGPU_FLAG_BLOCKING_WAIT) != 0;
+  w->states.resize((size_t)w->n_queries + 1);
+  HIP_TRY(hipMemcpyAsync(w->states.data(), d_own + w->o_states, w->states.size() * sizeof(DTermsState), hipMemcpyDeviceToHost, slot->stream));
+  HIP_TRY(wait_for_stream(blocking, slot->stream, slot->ev_wait));
+  const uint32_t n = std::min(w->states[(size_t)w->n_queries].claimed, w->out_cap);
+  w->entries.resize(n);
+  if (n != 0) {
+    HIP_TRY(hipMemcpyAsync(w->entries.data(), d_own + w->o_out, (size_t)n * 8, hipMemcpyDeviceToHost, slot->stream));
+    HIP_TRY(wait_for_stream(blocking, slot->stream, slot->ev_wait));
+  }
+  return NRTGPU_OK;
+}
+
+
+// The call's answers from what terms_collect brought back: a query's entries sorted by code (ascending code = ascending in the
+// kind's order) and decoded with doc_value_bits.  pages: the merge's lists (empty; total_hits is read from them).
+int terms_unpack(const TermsWork& work, const std::vector<int>& kinds, const nrtgpu_topdocs* pages, int32_t n_queries, nrtgpu_term_counts* out) {
+  std::vector<uint64_t> mine;
+  for (int qi = 0; qi < n_queries; ++qi) {
+    nrtgpu_term_counts& o = out[qi];
+    const DTermsState& st = work.states[(size_t)qi];
+    o.total_hits = pages[(size_t)qi].total_hits;
+    o.reserved = 0;
+    o.overflowed = st.overflow != 0u ? 1 : 0;
+    o.n_buckets = 0;
+    o.hits_with_value = o.overflowed ? -1 : 0;
+    if (o.overflowed) continue;
+    const size_t b = st.out_base, n = st.n_out;
+    if (b + n > work.entries.size() || (int64_t)n > (int64_t)o.capacity) return fail(NRTGPU_ERR_STATE, "terms count: query %d came back with %zu buckets at %zu", qi, n, b);
+    mine.assign(work.entries.begin() + (ptrdiff_t)b, work.entries.begin() + (ptrdiff_t)(b + n));
+    std::sort(mine.begin(), mine.end(), [](uint64_t x, uint64_t y) { return (uint32_t)x < (uint32_t)y; });   // codes are distinct
+    for (size_t i = 0; i < n; ++i) {
+      o.value_bits[i] = doc_value_bits(kinds[(size_t)qi], (uint32_t)mine[i]);
+      o.counts[i] = (int32_t)(mine[i] >> 32);
+      o.hits_with_value += o.counts[i];
+    }
+    o.n_buckets = (int32_t)n;
+  }
+  return NRTGPU_OK;
+}
+
+}  // namespace rt
+}  // namespace nrtgpu
+
+namespace {
 
 // What the route refuses of a call before anything is planned (the segments' content is held); the records and the copies that
 // are planned on the way.  out: the batch entry's outputs (their capacities), nullptr for the predicate.
@@ -42,22 +116,10 @@ int check_call(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, c
     const nrtgpu_bm25_query& q = queries[qi];
     const nrtgpu_terms_count& t = terms[qi];
     if (int rc = validate_query(q, qi)) return rc;
-    if (t.max_buckets < 1 || t.max_buckets > NRTGPU_MAX_TERM_BUCKETS)
-      return fail(NRTGPU_ERR_INVALID_ARG, "query %d: max_buckets %d outside 1..%d", qi, t.max_buckets, NRTGPU_MAX_TERM_BUCKETS);
-    if (out && (out[qi].capacity < t.max_buckets || !out[qi].value_bits || !out[qi].counts))
-      return fail(NRTGPU_ERR_INVALID_ARG, "query %d: an output of capacity %d (or NULL arrays) for max_buckets %d", qi, out[qi].capacity, t.max_buckets);
     int kind = -1;
-    if (int rc = doc_values_kind(segs, n_segs, t.field_id, qi, &kind)) return rc;
-    kinds->push_back(kind);
     DTermsQuery r{};
-    r.max_buckets = (uint32_t)t.max_buckets;
-    r.table_shift = terms_table_shift(r.max_buckets);
-    r.table_off = (uint32_t)slots;
-    slots += 1ull << (32u - r.table_shift);
-    cap += r.max_buckets;
-    if (slots > kTermsMaxCallSlots)
-      return fail(NRTGPU_ERR_INVALID_ARG, "query %d: the count tables of the call exceed the workspace bound of %llu slots (a query takes the power of two >= 2 x max_buckets)",
-                  qi, (unsigned long long)kTermsMaxCallSlots);
+    if (int rc = terms_count_record(segs, n_segs, t, out ? &out[qi] : nullptr, qi, &slots, &cap, &r, &kind)) return rc;
+    kinds->push_back(kind);
     records->push_back(r);
   }
   if (int rc = final_score_check_flags(ctx, "terms count")) return rc;
@@ -65,29 +127,7 @@ int check_call(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, c
     if (int rc = doc_values_query(segs, n_segs, queries[qi], qi, (*kinds)[(size_t)qi], terms[qi].field_id, "a terms count", &(*records)[(size_t)qi].need, flat))
       return rc;
   for (int qi = 0; qi < n_queries; ++qi) flat->queries[(size_t)qi].terms = flat->terms[(size_t)qi].data();   // (the vectors have settled)
-  Carver c;
-  work->n_queries = n_queries;
-  work->o_states = c.take(((size_t)n_queries + 1) * sizeof(DTermsState));
-  work->o_tables = c.take((size_t)slots * 8);
-  work->o_out = c.take((size_t)cap * 8);
-  work->bytes = c.off;
-  work->out_cap = (uint32_t)cap;   // (<= 2^24: half the slots)
-  return NRTGPU_OK;
-}
-
-// Behind the wait: the states, then the entries that exist.
-int collect(nrtgpu_ctx* ctx, Slot* slot, const char* d_own, void* user) {
-  TermsWork* w = (TermsWork*)user;
-  const bool blocking = (ctx->cfg.flags & NRTGPU_FLAG_BLOCKING_WAIT) != 0;
-  w->states.resize((size_t)w->n_queries + 1);
-  HIP_TRY(hipMemcpyAsync(w->states.data(), d_own + w->o_states, w->states.size() * sizeof(DTermsState), hipMemcpyDeviceToHost, slot->stream));
-  HIP_TRY(wait_for_stream(blocking, slot->stream, slot->ev_wait));
-  const uint32_t n = std::min(w->states[(size_t)w->n_queries].claimed, w->out_cap);
-  w->entries.resize(n);
-  if (n != 0) {
-    HIP_TRY(hipMemcpyAsync(w->entries.data(), d_own + w->o_out, (size_t)n * 8, hipMemcpyDeviceToHost, slot->stream));
-    HIP_TRY(wait_for_stream(blocking, slot->stream, slot->ev_wait));
-  }
+  work->layout(n_queries, slots, cap);
   return NRTGPU_OK;
 }
 
@@ -125,7 +165,7 @@ extern "C" int nrtgpu_count_terms_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const
   if (int rc = doc_values_parts(segs, n_segs, field_ids.data(), hp, "terms count", &sparts)) return rc;
   const PlanBytes extras[2] = {{records.data(), records.size() * sizeof(DTermsQuery)}, {sparts.data(), sparts.size() * sizeof(DSortPart)}};
   std::vector<nrtgpu_topdocs> pages((size_t)n_queries, nrtgpu_topdocs{});   // (no hits come back: the merge's lists are empty; total_hits is read from them)
-  const FinalScoreOwn own{work.bytes, collect, &work};
+  const FinalScoreOwn own{work.bytes, terms_collect, &work};
   if (int rc = final_score_run(ctx, hp, queries, n_queries, pages.data(), t0, extras, 2, [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
         const TermsWork* w = (const TermsWork*)a.own_user;
         char* d_own = (char*)a.own;
@@ -133,26 +173,5 @@ extern "C" int nrtgpu_count_terms_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const
                                 (unsigned long long*)(d_own + w->o_tables), (unsigned long long*)(d_own + w->o_out), (uint32_t)w->n_queries, w->out_cap);
       }, &own))
     return rc;
-  std::vector<uint64_t> mine;
-  for (int qi = 0; qi < n_queries; ++qi) {
-    nrtgpu_term_counts& o = out[qi];
-    const DTermsState& st = work.states[(size_t)qi];
-    o.total_hits = pages[(size_t)qi].total_hits;
-    o.reserved = 0;
-    o.overflowed = st.overflow != 0u ? 1 : 0;
-    o.n_buckets = 0;
-    o.hits_with_value = o.overflowed ? -1 : 0;
-    if (o.overflowed) continue;
-    const size_t b = st.out_base, n = st.n_out;
-    if (b + n > work.entries.size() || (int64_t)n > (int64_t)o.capacity) return fail(NRTGPU_ERR_STATE, "terms count: query %d came back with %zu buckets at %zu", qi, n, b);
-    mine.assign(work.entries.begin() + (ptrdiff_t)b, work.entries.begin() + (ptrdiff_t)(b + n));
-    std::sort(mine.begin(), mine.end(), [](uint64_t x, uint64_t y) { return (uint32_t)x < (uint32_t)y; });   // codes are distinct
-    for (size_t i = 0; i < n; ++i) {
-      o.value_bits[i] = doc_value_bits(kinds[(size_t)qi], (uint32_t)mine[i]);
-      o.counts[i] = (int32_t)(mine[i] >> 32);
-      o.hits_with_value += o.counts[i];
-    }
-    o.n_buckets = (int32_t)n;
-  }
-  return NRTGPU_OK;
+  return terms_unpack(work, kinds, pages.data(), n_queries, out);
 }

@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "finalscore.hiph"
+#include "termstables.hiph"   // terms_lds_add, terms_global_add
 
 namespace nrtgpu {
 
@@ -36,50 +37,6 @@ struct TermsSmem {
   uint32_t slot_slice[kSliceSlots];
 };
 static_assert(sizeof(TermsSmem) <= 160 * 1024, "the workgroup owns one CU's 160 KiB LDS");
-
-// n more docs under `code` in the query's global table.  At most `mask + 1` steps; a full table raises the flag.
-__device__ __forceinline__ void terms_global_add(unsigned long long* table, uint32_t shift, uint32_t mask, uint32_t max_buckets, DTermsState* st,
-                                                 uint32_t code, uint32_t n) {
-  if (__hip_atomic_load(&st->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return;   // (the buckets are void already)
-  const unsigned long long add = (unsigned long long)n << 32, fresh = add | (unsigned long long)code;
-  uint32_t slot = terms_home_slot(code, shift) & mask;
-  for (uint32_t step = 0; step <= mask; ++step, slot = (slot + 1u) & mask) {
-    unsigned long long cur = __hip_atomic_load(table + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == 0ull) {
-      if (__hip_atomic_compare_exchange_strong(table + slot, &cur, fresh, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-        // one more distinct value of the query
-        if (__hip_atomic_fetch_add(&st->claimed, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= max_buckets)
-          __hip_atomic_store(&st->overflow, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-      }   // (else cur is what another thread put there)
-    }
-    if ((uint32_t)cur == code) {
-      __hip_atomic_fetch_add(table + slot, add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return;
-    }
-  }
-  __hip_atomic_store(&st->overflow, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // every slot holds another value: more than max_buckets
-}
-
-// n more docs under `code` in the item's LDS table; kTermsLdsProbe steps, then the global table.
-__device__ __forceinline__ void terms_lds_add(unsigned long long* lds, unsigned long long* table, uint32_t shift, uint32_t mask, uint32_t max_buckets,
-                                              DTermsState* st, uint32_t code, uint32_t n) {
-  const unsigned long long add = (unsigned long long)n << 32, fresh = add | (unsigned long long)code;
-  uint32_t slot = terms_home_slot(code, (uint32_t)kTermsLdsShift);
-#pragma unroll 1
-  for (int step = 0; step < kTermsLdsProbe; ++step, slot = (slot + 1u) & (uint32_t)(kTermsLdsSlots - 1)) {
-    unsigned long long cur = lds[slot];
-    if (cur == 0ull) {
-      cur = atomicCAS(&lds[slot], 0ull, fresh);
-      if (cur == 0ull) return;
-    }
-    if ((uint32_t)cur == code) {
-      atomicAdd(&lds[slot], add);
-      return;
-    }
-  }
-  terms_global_add(table, shift, mask, max_buckets, st, code, n);
-}
 
 __global__ __launch_bounds__(kScanThreads, kScanWaves / 4)
 void bm25_terms_count_kernel(const DItem* __restrict__ items, const DPart* __restrict__ parts, const DTerm* __restrict__ terms,
@@ -223,13 +180,19 @@ void terms_compact_kernel(const DTermsQuery* __restrict__ tqueries, DTermsState*
   }
 }
 
+// (also behind docset.hip's counting kernel)
+void launch_terms_compact(hipStream_t stream, const DTermsQuery* tqueries, DTermsState* states, const unsigned long long* tables, unsigned long long* out,
+                          uint32_t n_queries, uint32_t out_cap) {
+  if (n_queries != 0)
+    hipLaunchKernelGGL(terms_compact_kernel, dim3(n_queries), dim3(kCompactThreads), 0, stream, tqueries, states, tables, out, n_queries, out_cap);
+}
+
 void launch_bm25_terms_count(hipStream_t stream, const FinalScoreArgs& a, const DTermsQuery* tqueries, const DSortPart* sparts, DTermsState* states,
                              unsigned long long* tables, unsigned long long* out, uint32_t n_queries, uint32_t out_cap) {
   if (a.n_items != 0)
     hipLaunchKernelGGL(bm25_terms_count_kernel, dim3(a.n_items), dim3(kScanThreads), 0, stream, a.items, a.parts, a.terms, a.queries, tqueries, sparts,
                        states, tables, a.slice_sum, a.item_counts, a.item_hits);
-  if (n_queries != 0)
-    hipLaunchKernelGGL(terms_compact_kernel, dim3(n_queries), dim3(kCompactThreads), 0, stream, tqueries, states, tables, out, n_queries, out_cap);
+  launch_terms_compact(stream, tqueries, states, tables, out, n_queries, out_cap);
 }
 
 }  // namespace nrtgpu
