@@ -132,11 +132,28 @@ int  nrtgpu_segment_add_byte_vectors(nrtgpu_seg* seg, int32_t field_id, int32_t 
  * nrtgpu_segment_device_bytes counts it.  Resident as one order-preserving 32-bit code per doc plus one bit per doc where some
  * doc lacks a value.  Sorting is its first reader (nrtgpu_search_sorted_batch).  NRTGPU_ERR_INVALID_ARG: kind out of range,
  * n < 0 or n > max_doc, docs not strictly ascending or outside [0, max_doc), docs == NULL with n != max_doc, values == NULL with
- * n > 0, a second column on the field.  Out of scope: 64-bit values, updatable doc values. */
+ * n > 0, a second column on the field -- of either arity: a field that holds a multi-valued column
+ * (nrtgpu_segment_add_doc_values_multi) takes no single-valued one.  Out of scope: 64-bit values, updatable doc values. */
 #define NRTGPU_DOCVALUES_INT32 0    /* IntFieldDef: SortField.Type.INT */
 #define NRTGPU_DOCVALUES_FLOAT32 1  /* FloatFieldDef: SortField.Type.FLOAT */
 int  nrtgpu_segment_add_doc_values(nrtgpu_seg* seg, int32_t field_id, int32_t kind, int32_t n, const int32_t* docs,
                                    const void* values);
+/* A MULTI-VALUED value column of one field: any number of 32-bit values per doc -- every value of a SORTED_NUMERIC int / float
+ * field (src/main/java/com/yelp/nrtsearch/server/field/IntFieldDef.java:62-70,83-85 through LoadedDocValues.SortedIntegers,
+ * doc/LoadedDocValues.java:483-500; floats :600-603), or the global ordinals of a SORTED_SET string field as INT32 values
+ * (search/collectors/additional/OrdinalTermsCollectorManager.java:189-226).  value_docs[i] is the leaf docid of value i,
+ * NON-DECREASING and in [0, max_doc); values: n_values x 4 bytes of the kind.  A doc that is not listed has no value, a doc
+ * listed c times has c values; duplicates inside a doc are kept and count each (docValueCount()).  n_values == 0 is a valid
+ * column: the kind is known and no doc has a value, which differs from "the leaf lacks the column".  No limit on values per doc.
+ * Readers: the terms counts (every value instance of a hit adds 1) and the range clauses of the doc-set requests (a doc passes
+ * iff SOME value is in the range); a sort refuses such a column (it names ONE value per doc: upload the selector's pick
+ * single-valued, above).  Resident as uint32 start[]: one entry per doc, padded to whole sub-tiles, plus one -- doc d's values
+ * are codes[start[d] .. start[d + 1]), every padding entry equals n_values -- and uint32 codes[]: the values' order-preserving
+ * codes in upload order.  Before the seal only (after: NRTGPU_ERR_STATE); forks share it; nrtgpu_segment_device_bytes counts it.
+ * NRTGPU_ERR_INVALID_ARG: seg NULL, kind out of range, n_values < 0, a NULL array with n_values > 0, value_docs decreasing or
+ * outside [0, max_doc), a second column of either arity on the field. */
+int  nrtgpu_segment_add_doc_values_multi(nrtgpu_seg* seg, int32_t field_id, int32_t kind, int32_t n_values,
+                                         const int32_t* value_docs, const void* values);
 /* builds the per-term doc-range tables; the segment becomes searchable */
 int  nrtgpu_segment_seal(nrtgpu_seg* seg);
 /* leaf.getLiveDocs() as 64-bit words, bit d set = doc d live; NULL => all live.  May be called
@@ -955,9 +972,11 @@ int  nrtgpu_text_knn_exact(const nrtgpu_bm25_query* q, const nrtgpu_knn_clauses*
  * statistics (scan_*, fixed_point_launches) work as in nrtgpu_search_function_score_batch.
  * Refusals, each with a reason in nrtgpu_last_error naming the query:
  *   NRTGPU_ERR_INVALID_ARG  NULL arguments; reverse or has_after outside 0..1; after_doc < 0; queries[i].has_after != 0; leaves of
- *                           the call that hold the field's column under different kinds; whatever nrtgpu_search_bm25_batch
+ *                           the call that hold the field's column under different kinds or arities; whatever nrtgpu_search_bm25_batch
  *                           refuses of queries[i] with that status
- *   NRTGPU_ERR_UNSUPPORTED  the column is resident on no leaf of the call (its kind is then unknown); disjunction_max != 0 or
+ *   NRTGPU_ERR_UNSUPPORTED  the column is resident on no leaf of the call (its kind is then unknown), or it is MULTI-VALUED
+ *                           (nrtgpu_segment_add_doc_values_multi: a sort names ONE value per doc -- upload the selector's pick
+ *                           as a single-valued column of its own); disjunction_max != 0 or
  *                           tie_breaker != 0 (pass the clauses as a plain disjunction: scores are not read); MUST next to SHOULD
  *                           clauses; min_competitive_score != 0; k > NRTGPU_MAX_K; a mask that is not resident; a context with
  *                           NRTGPU_FLAG_PACKED_POSTINGS or NRTGPU_FLAG_NO_FIXED_POINT, a batch whose queries do not all pass
@@ -1016,6 +1035,12 @@ int  nrtgpu_sort_value_code(int32_t kind, int32_t reverse, uint32_t value_bits, 
  * What is counted: a hit with a value adds 1 to the bucket of that value.  A hit without a value, or in a leaf that lacks the
  * column, adds to no bucket (docValues.size() == 0 in the reference).  total_hits counts every hit; hits_with_value is the sum
  * of all counts.
+ * A MULTI-VALUED column (nrtgpu_segment_add_doc_values_multi): EVERY value instance of every hit adds 1 to its value's bucket
+ * (for (i < docValues.size()) countsMap.addTo(docValues.get(i), 1), IntTermsCollectorManager.java:142-152; the float and the
+ * ordinal collector alike, OrdinalTermsCollectorManager.java:189-226) -- a doc that holds a value twice counts it twice.
+ * total_hits is unchanged; hits_with_value stays "the sum of all counts" and is then the number of value INSTANCES counted, which
+ * may exceed total_hits.  Bucket identity, output order and overflowed ("distinct values > max_buckets") are as above.  A batch
+ * may mix queries over columns of either arity.
  * Bucket identity is the identity of the column's code: ints are bucketed by value, floats by Float.floatToIntBits -- every NaN
  * falls in ONE bucket and reports as 0x7FC00000, -0.0 and +0.0 are TWO buckets (fastutil's Float2IntOpenHashMap equality
  * [Lucene-recall: never checked against a JVM run]).
@@ -1030,16 +1055,18 @@ int  nrtgpu_sort_value_code(int32_t kind, int32_t reverse, uint32_t value_bits, 
  * nrtgpu_search_sorted_batch.
  * Refusals, each with a reason in nrtgpu_last_error naming the query -- the sorted route's table, same statuses and precedence:
  *   NRTGPU_ERR_INVALID_ARG  NULL arguments; max_buckets outside 1..NRTGPU_MAX_TERM_BUCKETS; capacity < max_buckets, or NULL
- *                           value_bits / counts; leaves of the call that hold the field's column under different kinds;
- *                           whatever nrtgpu_search_bm25_batch refuses of queries[i] with that status; a call whose tables
+ *                           value_bits / counts; leaves of the call that hold the field's column under different kinds, or
+ *                           single-valued on one and multi-valued on another; whatever nrtgpu_search_bm25_batch refuses of
+ *                           queries[i] with that status; a call whose tables
  *                           exceed the workspace bound above (the reason names the limit)
  *   NRTGPU_ERR_UNSUPPORTED  the column is resident on no leaf of the call; disjunction_max != 0 or tie_breaker != 0; MUST next
  *                           to SHOULD clauses; min_competitive_score != 0; k > NRTGPU_MAX_K; a mask that is not resident; a
  *                           context with NRTGPU_FLAG_PACKED_POSTINGS or NRTGPU_FLAG_NO_FIXED_POINT, a batch whose queries do
  *                           not all pass the fixed-point analysis -- the final-score routes' refusals, the KNOWN LIMIT they are
  *                           on the sorted route
- * Out of scope: LONG / DOUBLE columns; multi-valued fields; string and ordinal collectors (a single-valued string facet can be
- * uploaded as a column of its global ordinals); script and virtual sources; nested collectors and NESTED_COLLECTOR order; the
+ * Out of scope: LONG / DOUBLE columns; string collectors as such (a string facet, SORTED_SET or single-valued, is uploaded as an
+ * INT32 column of its global ordinals -- multi-valued where the field is -- and its keys mapped back by the caller); script and
+ * virtual sources; nested collectors and NESTED_COLLECTOR order; the
  * Filter / Min / Max / Sum / TopHits collectors; fusing the count into a scoring route; dismax and multi-match text (a match-all
  * or filter-only query is nrtgpu_count_docset_terms_batch);
  * the coalesced, device-resident and nrtgpu_dist_* forms; the Java shim.
@@ -1071,7 +1098,7 @@ int  nrtgpu_count_terms_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs
 /* ---------------------------------------------------------------------------------------------
  * Doc-set requests: a sort by field (nrtgpu_search_sorted_batch) or a terms count (nrtgpu_count_terms_batch) whose hit set is a
  * DOC SET and no text clause -- the reference's MatchAllDocsQuery, a BooleanQuery of FILTER / MUST_NOT clauses only, and the
- * numeric RangeQuery of a single-valued INT / FLOAT field with doc values
+ * numeric RangeQuery of an INT / FLOAT field with doc values, single- or multi-valued
  * (src/main/java/com/yelp/nrtsearch/server/field/IntFieldDef.java:124-160, FloatFieldDef.java:126-164:
  * IndexOrDocValuesQuery(PointRangeQuery, SortedNumericDocValuesField.newSlowRangeQuery)) under a `querySort` or a TermsCollector:
  * "everything in this category, rating between 4 and 5, best rated first", the facet counts of a browse page.
@@ -1085,6 +1112,11 @@ int  nrtgpu_count_terms_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs
  * one and above +inf (so [NaN, NaN] keeps exactly the NaN docs, [-inf, +inf] drops them).  A doc without a value, or in a leaf
  * that lacks the column, fails the clause.  lower > upper in that order is an EMPTY range that matches nothing, not an error
  * (the reference's ensureUpperIsMoreThanLower is the caller's job).
+ * A clause over a MULTI-VALUED column (nrtgpu_segment_add_doc_values_multi) keeps a doc iff SOME value of it passes that test
+ * (SortedNumericDocValuesField.newSlowRangeQuery / IntPoint.newRangeQuery, IntFieldDef.java:124-158, FloatFieldDef.java:126-164);
+ * a doc with no value fails.  A query may mix clauses over columns of either arity, and count or sort by a column of the other
+ * arity; a count over a multi-valued column adds 1 per value instance (nrtgpu_count_terms_batch).  The SORT column must be
+ * single-valued.
  * Results are nrtgpu_search_sorted_batch's and nrtgpu_count_terms_batch's, word for word, over this hit set: the order (value in
  * the sort's direction, ties by global docid ascending), the missing value, value_bits of a hit; paging (the cursor lives in the
  * sort, hits of earlier pages still count); the exact total_hits and the per-slice relation rule; bucket identity and ascending
@@ -1100,11 +1132,12 @@ int  nrtgpu_count_terms_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs
  *                           n_more_* negative or with a NULL array, more than NRTGPU_MAX_MASKS FILTER or MUST_NOT masks, a
  *                           more_* id <= 0; reserved != 0; what nrtgpu_search_sorted_batch / nrtgpu_count_terms_batch refuse of
  *                           sorts[i] / terms[i] / out[i] with this status; leaves of the call that hold a named column (the
- *                           sort's, the count's, a range clause's) under different kinds; a call whose count tables exceed the
- *                           workspace bound
+ *                           sort's, the count's, a range clause's) under different kinds, or single-valued on one leaf and
+ *                           multi-valued on another; a call whose count tables exceed the workspace bound
  *   NRTGPU_ERR_UNSUPPORTED  the sort or count column, or a range clause's column, is resident on no leaf of the call (its kind is
- *                           then unknown, and a forgotten upload must not read as "no hits"); a mask that is not resident
- * Out of scope: LONG / DOUBLE / DATE_TIME columns; multi-valued fields (a range over "any value"); ranges inside the text routes,
+ *                           then unknown, and a forgotten upload must not read as "no hits"); a sort column that is multi-valued
+ *                           (upload the selector's pick); a mask that is not resident
+ * Out of scope: LONG / DOUBLE / DATE_TIME columns; sorting by a multi-valued column; TermInSetQuery filters; ranges inside the text routes,
  * or as resident masks for the MaxScore and kNN routes; a score-ordered match-all; skipping whole tiles by per-tile minima and
  * maxima of a column (zone maps); the coalesced, device-resident and nrtgpu_dist_* forms; the Java shim, which keeps sending
  * these requests to Lucene until it binds this.

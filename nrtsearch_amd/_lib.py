@@ -67,6 +67,7 @@ ABI_SYMBOLS = [
     "nrtgpu_count_terms_batch", "nrtgpu_count_terms_supported",
     "nrtgpu_search_docset_sorted_batch", "nrtgpu_docset_sorted_supported", "nrtgpu_count_docset_terms_batch",
     "nrtgpu_count_docset_terms_supported", "nrtgpu_range_accepts",
+    "nrtgpu_segment_add_doc_values_multi",
 ]
 # what include/nrtgpu_dev.h adds: test hooks and measurement helpers of the development library (libnrtgpu_dev.so) only
 DEV_SYMBOLS = [
@@ -270,6 +271,7 @@ def _open(path: str) -> C.CDLL:
     L.nrtgpu_text_knn_value.argtypes = [i32, i32, C.c_uint64, i32, C.c_double, vp]
     L.nrtgpu_text_knn_exact.argtypes = [C.POINTER(Bm25Query), C.POINTER(KnnClauses), i32]
     L.nrtgpu_segment_add_doc_values.argtypes = [vp, i32, i32, i32, vp, vp]
+    L.nrtgpu_segment_add_doc_values_multi.argtypes = [vp, i32, i32, i32, vp, vp]
     L.nrtgpu_search_sorted_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(FieldSort), i32, C.POINTER(FieldDocs)]
     L.nrtgpu_sorted_supported.argtypes = [vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(FieldSort)]
     L.nrtgpu_sort_value_code.argtypes = [i32, i32, C.c_uint32, vp]

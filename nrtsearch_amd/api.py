@@ -606,6 +606,21 @@ class GpuSegment:
         _lib.check(_lib.load().nrtgpu_segment_add_doc_values(self._h, int(field), DOC_VALUE_KINDS[kind][0], values.shape[0], dp,
                                                              values.ctypes.data if values.shape[0] else None))
 
+    def add_doc_values_multi(self, field: int, kind: str, values: np.ndarray, value_docs: np.ndarray) -> None:
+        """A multi-valued value column of the field (nrtgpu_segment_add_doc_values_multi): values[i] belongs to leaf doc
+        value_docs[i] (non-decreasing; a doc listed c times has c values, duplicates count each; a doc not listed has none).
+        Terms counts and doc-set range clauses read it as they read a single-valued column; a sort refuses it.  No silent cast,
+        as in add_doc_values."""
+        values = np.ascontiguousarray(values).reshape(-1)
+        if values.dtype not in (DOC_VALUE_KINDS[kind][1], np.dtype(np.uint32)):
+            raise TypeError(f"doc values of kind {kind!r} must be {DOC_VALUE_KINDS[kind][1]} (or uint32 bits), got {values.dtype}")
+        value_docs = np.ascontiguousarray(value_docs, dtype=np.int32).reshape(-1)
+        if value_docs.shape[0] != values.shape[0]:
+            raise ValueError(f"{value_docs.shape[0]} value_docs, {values.shape[0]} values")
+        n = values.shape[0]
+        _lib.check(_lib.load().nrtgpu_segment_add_doc_values_multi(self._h, int(field), DOC_VALUE_KINDS[kind][0], n,
+                                                                   value_docs.ctypes.data if n else None, values.ctypes.data if n else None))
+
     def seal(self) -> None:
         _lib.check(_lib.load().nrtgpu_segment_seal(self._h))
 
@@ -1368,8 +1383,9 @@ def sort_value_code(kind: str, reverse: bool, value_bits: int) -> int:
 
 @dataclasses.dataclass(frozen=True)
 class TermsCollector:
-    """A TermsCollector over a single-valued int or float field (source FIELD, order COUNT, no nested collectors): `field` names
-    the doc value column (GpuSegment.add_doc_values) of kind `kind`; `size` and `order_desc` are what the caller's reduce() applies
+    """A TermsCollector over an int or float field (source FIELD, order COUNT, no nested collectors): `field` names the doc value
+    column of kind `kind` -- single-valued (GpuSegment.add_doc_values) or multi-valued (add_doc_values_multi: every value instance
+    of a hit counts, as for a SORTED_SET facet uploaded as its global ordinals); `size` and `order_desc` are what the caller's reduce() applies
     to the returned map (fill_bucket_result), the device does not read them."""
 
     field: int
@@ -1467,7 +1483,7 @@ def count_terms_supported(searcher: "GpuIndexSearcher", query: Query, collector:
 
 @dataclasses.dataclass(frozen=True)
 class RangeClause:
-    """IntFieldDef / FloatFieldDef.getRangeQuery over a single-valued field with doc values: lower <= value <= upper, both bounds
+    """IntFieldDef / FloatFieldDef.getRangeQuery over a field with doc values (a multi-valued column: SOME value of the doc): lower <= value <= upper, both bounds
     INCLUSIVE, in the order of the column's kind (floats: -0.0 < +0.0, NaN above +inf).  An exclusive bound is the caller's to map
     (lower + 1 / np.nextafter).  A doc without a value fails the clause; lower > upper matches nothing."""
 

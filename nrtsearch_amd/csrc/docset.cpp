@@ -29,6 +29,7 @@ struct DocsetCall {
   std::vector<nrtgpu_bm25_query> masks;    // per query: k, total_hits_threshold and the mask fields (what docset_plan and final_score_run read)
   std::vector<DRangeQuery> ranges;         // per query (the codes are filled once the columns' kinds are known)
   std::vector<int> range_kinds;            // per (query, clause): kMaxRanges per query
+  bool any_multi = false;                  // some named column of the call (a range clause's, the count's) is multi-valued: the *_multi kernels
 };
 
 // What the route refuses of docsets[qi] as an invalid argument, the header's table in its order.
@@ -70,9 +71,14 @@ int docset_begin(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_doc
   rq.n_ranges = (uint32_t)d.n_ranges;
   for (int r = 0; r < kMaxRanges; ++r) {
     int kind = -1;
+    bool multi = false;
     if (r < d.n_ranges)
-      if (int rc = doc_values_kind(segs, n_segs, d.ranges[r].field_id, qi, &kind)) return rc;
+      if (int rc = doc_values_kind(segs, n_segs, d.ranges[r].field_id, qi, &kind, &multi)) return rc;
     call->range_kinds.push_back(kind);
+    if (multi) {
+      rq.multi |= 1u << r;
+      call->any_multi = true;
+    }
   }
   call->ranges.push_back(rq);
   return NRTGPU_OK;
@@ -93,12 +99,6 @@ int docset_finish(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_do
 
 int no_column(int qi, int32_t field_id) { return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: no leaf of the call holds doc values of field %d", qi, field_id); }
 
-DSortPart column_of(const nrtgpu_seg* seg, int32_t field_id) {
-  const auto fit = seg->fields.find(field_id);
-  if (fit == seg->fields.end() || fit->second.dv_kind < 0) return DSortPart{nullptr, nullptr};   // no doc of the leaf has a value
-  return DSortPart{fit->second.d_dv_code, fit->second.d_dv_has};
-}
-
 // The columns of every part's leaf (HostPlan.part_leaf): the collector's (field_ids: per query) and the range clauses'.
 void docset_parts(const nrtgpu_seg* const* segs, const nrtgpu_docset_query* docsets, const int32_t* field_ids, const HostPlan& hp, std::vector<DSortPart>* sparts,
                   std::vector<DSortPart>* rparts) {
@@ -108,25 +108,29 @@ void docset_parts(const nrtgpu_seg* const* segs, const nrtgpu_docset_query* docs
     for (uint32_t pi = 0; pi < it.n_parts; ++pi) {
       const size_t at = (size_t)it.part_begin + pi;
       const nrtgpu_seg* seg = segs[hp.part_leaf[at]];
-      (*sparts)[at] = column_of(seg, field_ids[it.query]);
+      (*sparts)[at] = doc_values_column(seg, field_ids[it.query]);
       const nrtgpu_docset_query& d = docsets[it.query];
-      for (int r = 0; r < d.n_ranges; ++r) (*rparts)[at * (size_t)kMaxRanges + (size_t)r] = column_of(seg, d.ranges[r].field_id);
+      for (int r = 0; r < d.n_ranges; ++r) (*rparts)[at * (size_t)kMaxRanges + (size_t)r] = doc_values_column(seg, d.ranges[r].field_id);
     }
 }
 
 // What the sorted entry refuses of a call before anything is planned (the segments' content is held), and its records.
 int check_sorted(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* docsets, const nrtgpu_field_sort* sorts, int32_t n_queries,
                  DocsetCall* call, std::vector<DSortQuery>* records, std::vector<int>* kinds) {
+  std::vector<char> sort_multi;
   for (int qi = 0; qi < n_queries; ++qi) {
     if (int rc = docset_begin(segs, n_segs, docsets[qi], qi, call)) return rc;
     if (int rc = field_sort_check(sorts[qi], qi)) return rc;
     int kind = -1;
-    if (int rc = doc_values_kind(segs, n_segs, sorts[qi].field_id, qi, &kind)) return rc;
+    bool multi = false;
+    if (int rc = doc_values_kind(segs, n_segs, sorts[qi].field_id, qi, &kind, &multi)) return rc;
     kinds->push_back(kind);
+    sort_multi.push_back(multi ? 1 : 0);
   }
   for (int qi = 0; qi < n_queries; ++qi) {
     const int kind = (*kinds)[(size_t)qi];
     if (kind < 0) return no_column(qi, sorts[qi].field_id);
+    if (sort_multi[(size_t)qi] != 0) return field_sort_multi(qi, sorts[qi].field_id);
     if (int rc = docset_finish(segs, n_segs, docsets[qi], qi, call)) return rc;
     DSortQuery r{};
     field_sort_record(sorts[qi], kind, &r);
@@ -142,10 +146,12 @@ int check_terms(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docs
   for (int qi = 0; qi < n_queries; ++qi) {
     if (int rc = docset_begin(segs, n_segs, docsets[qi], qi, call)) return rc;
     int kind = -1;
+    bool multi = false;
     DTermsQuery r{};
-    if (int rc = terms_count_record(segs, n_segs, terms[qi], out ? &out[qi] : nullptr, qi, &slots, &cap, &r, &kind)) return rc;
+    if (int rc = terms_count_record(segs, n_segs, terms[qi], out ? &out[qi] : nullptr, qi, &slots, &cap, &r, &kind, &multi)) return rc;
     kinds->push_back(kind);
     records->push_back(r);
+    call->any_multi = call->any_multi || multi;
   }
   for (int qi = 0; qi < n_queries; ++qi) {
     if ((*kinds)[(size_t)qi] < 0) return no_column(qi, terms[qi].field_id);
@@ -190,10 +196,14 @@ extern "C" int nrtgpu_search_docset_sorted_batch(nrtgpu_ctx* ctx, const nrtgpu_s
                                {sparts.data(), sparts.size() * sizeof(DSortPart)},
                                {rparts.data(), rparts.size() * sizeof(DSortPart)}};
   nrtgpu_topdocs* pages = reinterpret_cast<nrtgpu_topdocs*>(out);   // (the layout is the same: fieldsort.cpp's static_assert)
-  if (int rc = final_score_run(ctx, hp, call.masks.data(), n_queries, pages, t0, extras, 4, [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
-        launch_docset_sort(st, a, (const DSortQuery*)d_extra[0], (const DRangeQuery*)d_extra[1], (const DSortPart*)d_extra[2], (const DSortPart*)d_extra[3]);
-      }))
-    return rc;
+  // the dispatch: a call whose range columns are all single-valued launches what it always launched
+  const FinalScoreLaunch single = [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
+    launch_docset_sort(st, a, (const DSortQuery*)d_extra[0], (const DRangeQuery*)d_extra[1], (const DSortPart*)d_extra[2], (const DSortPart*)d_extra[3]);
+  };
+  const FinalScoreLaunch multi = [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
+    launch_docset_sort_multi(st, a, (const DSortQuery*)d_extra[0], (const DRangeQuery*)d_extra[1], (const DSortPart*)d_extra[2], (const DSortPart*)d_extra[3]);
+  };
+  if (int rc = final_score_run(ctx, hp, call.masks.data(), n_queries, pages, t0, extras, 4, call.any_multi ? multi : single)) return rc;
   for (int qi = 0; qi < n_queries; ++qi) {   // key high words -> the values the hits sorted as
     uint32_t* v = out[qi].value_bits;
     const uint32_t reverse = records[(size_t)qi].reverse;
@@ -238,13 +248,21 @@ extern "C" int nrtgpu_count_docset_terms_batch(nrtgpu_ctx* ctx, const nrtgpu_seg
                                {rparts.data(), rparts.size() * sizeof(DSortPart)}};
   std::vector<nrtgpu_topdocs> pages((size_t)n_queries, nrtgpu_topdocs{});   // (no hits come back: the merge's lists are empty; total_hits is read from them)
   const FinalScoreOwn own{work.bytes, terms_collect, &work};
-  if (int rc = final_score_run(ctx, hp, call.masks.data(), n_queries, pages.data(), t0, extras, 4, [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
-        const TermsWork* w = (const TermsWork*)a.own_user;
-        char* d_own = (char*)a.own;
-        launch_docset_terms_count(st, a, (const DTermsQuery*)d_extra[0], (const DRangeQuery*)d_extra[1], (const DSortPart*)d_extra[2], (const DSortPart*)d_extra[3],
-                                  (DTermsState*)(d_own + w->o_states), (unsigned long long*)(d_own + w->o_tables), (unsigned long long*)(d_own + w->o_out),
-                                  (uint32_t)w->n_queries, w->out_cap);
-      }, &own))
-    return rc;
+  // the dispatch: a call whose count and range columns are all single-valued launches what it always launched
+  const FinalScoreLaunch single = [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
+    const TermsWork* w = (const TermsWork*)a.own_user;
+    char* d_own = (char*)a.own;
+    launch_docset_terms_count(st, a, (const DTermsQuery*)d_extra[0], (const DRangeQuery*)d_extra[1], (const DSortPart*)d_extra[2], (const DSortPart*)d_extra[3],
+                              (DTermsState*)(d_own + w->o_states), (unsigned long long*)(d_own + w->o_tables), (unsigned long long*)(d_own + w->o_out),
+                              (uint32_t)w->n_queries, w->out_cap);
+  };
+  const FinalScoreLaunch multi = [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
+    const TermsWork* w = (const TermsWork*)a.own_user;
+    char* d_own = (char*)a.own;
+    launch_docset_terms_count_multi(st, a, (const DTermsQuery*)d_extra[0], (const DRangeQuery*)d_extra[1], (const DSortPart*)d_extra[2],
+                                    (const DSortPart*)d_extra[3], (DTermsState*)(d_own + w->o_states), (unsigned long long*)(d_own + w->o_tables),
+                                    (unsigned long long*)(d_own + w->o_out), (uint32_t)w->n_queries, w->out_cap);
+  };
+  if (int rc = final_score_run(ctx, hp, call.masks.data(), n_queries, pages.data(), t0, extras, 4, call.any_multi ? multi : single, &own)) return rc;
   return terms_unpack(work, kinds, pages.data(), n_queries, out);
 }

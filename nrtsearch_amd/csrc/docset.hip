@@ -5,6 +5,7 @@
 //
 //   docset_sort_kernel          per sub-tile the accept words, the range clauses, then keys for the accepted docs and the item's top-k
 //   docset_terms_count_kernel   the same hit set; every hit with a value adds 1 in the count table under the value's code
+//   docset_sort_multi_kernel, docset_terms_count_multi_kernel   the two for calls that name a MULTI-VALUED column (at the end)
 //
 // The decomposition is the final-score skeleton's (finalscore.hiph): one workgroup of kScanWaves waves per item, a wave takes
 // kTileDocs-doc sub-tiles of the item's parts (final_total_tiles / final_tile), hits per slice through final_count_slice, the
@@ -303,6 +304,253 @@ void docset_terms_count_kernel(const DItem* __restrict__ items, const DPart* __r
   }
 }
 
+// ---- calls that name a MULTI-VALUED column (plan.h: DSortPart: codes[] behind start[]) ------------------------------------------
+// The two kernels above for calls in which a range clause's column or the count column is multi-valued.  The arity is a wave-
+// uniform flag -- per clause (DRangeQuery.multi), per query for the count column (DTermsQuery.need bit 31) -- so a batch that mixes
+// arities is one launch, and a single-valued column goes through the functions above.  The reference's rules: a range clause
+// keeps a doc iff ANY of its values lies in the range (SortedNumericDocValuesField.newSlowRangeQuery); every value instance of a
+// hit adds 1 (IntTermsCollectorManager.java:142-152).  The kernels above keep their text: what follows repeats their frames.
+
+// A lane's start[d] and start[d + 1] for the words in `words` (the others read 0: no value).  start[] is padded to whole
+// sub-tiles plus one: no bounds test.
+__device__ __forceinline__ void docset_value_spans(const DSortPart* sp, uint32_t base, uint32_t lane, uint32_t words, uint32_t (&s0)[kFinalSlots],
+                                                   uint32_t (&s1)[kFinalSlots]) {
+  const NRT_GLOBAL uint32_t* const start = (const NRT_GLOBAL uint32_t*)sp->has;
+#pragma unroll
+  for (int j = 0; j < kFinalSlots; ++j) {
+    s0[j] = s1[j] = 0u;
+    if (((words >> j) & 1u) != 0u) {   // uniform: a word without an accepted doc costs no load
+      s0[j] = start[base + lane + 64u * (uint32_t)j];
+      s1[j] = start[base + lane + 64u * (uint32_t)j + 1u];
+    }
+  }
+}
+
+// A multi-valued range clause over the lane's view m: the docs of m with SOME value in [lo, hi].  A lane walks the values of its
+// accepted docs only and stops at the first that passes; the walk's bound is the doc's count, read on entry.
+__device__ __forceinline__ uint32_t docset_range_any(const DSortPart* sp, uint32_t base, uint32_t lane, uint32_t words, uint32_t m, uint32_t lo, uint32_t hi) {
+  const NRT_GLOBAL uint32_t* const codes = (const NRT_GLOBAL uint32_t*)sp->code;
+  uint32_t s0[kFinalSlots], s1[kFinalSlots];
+  docset_value_spans(sp, base, lane, words, s0, s1);
+  uint32_t pass = 0u;
+#pragma unroll
+  for (int j = 0; j < kFinalSlots; ++j) {
+    const uint32_t n = ((m >> j) & 1u) != 0u ? s1[j] - s0[j] : 0u;
+    bool any = false;
+#pragma unroll 1
+    for (uint32_t v = 0; v < n && !any; ++v) any = range_accepts_code(lo, hi, codes[s0[j] + v]);
+    pass |= (any ? 1u : 0u) << j;
+  }
+  return pass;
+}
+
+// docset_hit_set with the clause's arity read from rq->multi.
+__device__ __forceinline__ uint32_t docset_hit_set_multi(const DPart* part, const DRangeQuery* rq, const DSortPart* rparts, uint32_t base, uint32_t tile_len,
+                                                         uint32_t lane, uint32_t& words, uint32_t& hits) {
+  const uint32_t word0 = base >> 6;
+  hits = 0u;
+  uint32_t m = docset_accept(part, word0, tile_len, lane, words);
+  if (words == 0u) return 0u;   // uniform
+  const uint32_t n_ranges = min(rq->n_ranges, (uint32_t)kMaxRanges), multi = rq->multi;
+#pragma unroll 1
+  for (uint32_t r = 0; r < n_ranges; ++r) {
+    const uint32_t lo = rq->lo_code[r], hi = rq->hi_code[r];
+    if (rparts[r].code == nullptr) {   // uniform: no doc of the leaf has a value: none passes
+      words = hits = 0u;
+      return 0u;
+    }
+    if (((multi >> r) & 1u) != 0u) {   // uniform
+      m &= docset_range_any(rparts + r, base, lane, words, m, lo, hi);
+    } else {
+      uint32_t cv[kFinalSlots], has_bits;
+      docset_column(rparts + r, base, word0, lane, words, cv, has_bits);
+      uint32_t pass = 0u;
+#pragma unroll
+      for (int j = 0; j < kFinalSlots; ++j) pass |= (range_accepts_code(lo, hi, cv[j]) ? 1u : 0u) << j;
+      m &= has_bits & pass;
+    }
+    docset_census(m, words, hits);
+    if (words == 0u) return 0u;   // uniform: the later clauses load nothing
+  }
+  if (n_ranges == 0u) docset_census(m, words, hits);
+  return m;
+}
+
+// docset_sort_kernel over docset_hit_set_multi (the sort's own column is single-valued: a sort names one value per doc).
+__global__ __launch_bounds__(kScanThreads, kScanWaves / 4)
+void docset_sort_multi_kernel(const DItem* __restrict__ items, const DPart* __restrict__ parts, const DQuery* __restrict__ queries,
+                              const DSortQuery* __restrict__ squeries, const DRangeQuery* __restrict__ rqueries, const DSortPart* __restrict__ sparts,
+                              const DSortPart* __restrict__ rparts, unsigned long long* __restrict__ theta_g, uint32_t* __restrict__ slice_sum,
+                              uint64_t* __restrict__ item_keys, uint32_t* __restrict__ item_counts, uint64_t* __restrict__ item_hits, uint32_t k_stride) {
+  __shared__ DocsetSortSmem s;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)), lane = tid & 63u;
+  const DItem* const item = items + blockIdx.x;
+  const uint32_t query = item->query, part_begin = item->part_begin, n_parts = item->n_parts;
+  const DQuery* const q = queries + query;
+  const uint32_t k = min(q->k, (uint32_t)kMaxK);
+  const DSortQuery* const sq = squeries + query;
+  const DRangeQuery* const rq = rqueries + query;
+  const uint32_t reverse = sq->reverse, missing_code = sq->missing_code;
+  const bool has_after = sq->has_after != 0u;
+  const uint64_t after_key = sq->after_key;
+  const bool multi_item = q->n_items > 1;
+  unsigned long long* const my_theta_g = theta_g + query;
+
+  if (tid < (uint32_t)kSliceSlots) s.slot_hits[tid] = s.slot_slice[tid] = 0u;
+  __syncthreads();
+
+  const uint32_t total_tiles = final_total_tiles(parts, part_begin, n_parts);
+  uint64_t theta = 0;   // uniform: the k-th best key known (this item's compactions, the query's other items)
+  uint32_t cnt = 0;     // uniform: keys in s.cand
+  uint32_t pi = 0;      // the part of the wave's sub-tile (indices only grow)
+  uint32_t par = 0;
+
+  for (uint32_t g0 = 0; g0 < total_tiles; g0 += (uint32_t)kScanWaves, par ^= 1u) {
+    if (multi_item) {
+      const uint64_t t = __hip_atomic_load(my_theta_g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      theta = t > theta ? t : theta;
+    }
+    const uint32_t g = g0 + wave;
+    uint32_t n_cand = 0;   // wave-uniform
+    uint64_t key[kFinalSlots];
+#pragma unroll
+    for (int j = 0; j < kFinalSlots; ++j) key[j] = 0ull;
+    if (g < total_tiles) {
+      const FinalTile tl = final_tile(parts, part_begin, n_parts, g, pi);
+      const uint32_t base = tl.base, gdoc0 = tl.gdoc0;
+      uint32_t words, hits;
+      const uint32_t m = docset_hit_set_multi(tl.part, rq, rparts + (size_t)(part_begin + pi) * (size_t)kMaxRanges, base, tl.tile_len, lane, words, hits);
+      if (words != 0u) {   // uniform
+        uint32_t cv[kFinalSlots], has_bits;
+        docset_column(sparts + part_begin + pi, base, base >> 6, lane, words, cv, has_bits);
+#pragma unroll
+        for (int j = 0; j < kFinalSlots; ++j) {
+          if (((m >> j) & 1u) != 0u) {
+            const uint32_t code = ((has_bits >> j) & 1u) != 0u ? cv[j] : missing_code;
+            const uint64_t doc_key = sort_key(reverse, code, gdoc0 + lane + 64u * (uint32_t)j);
+            if (doc_key > theta && (!has_after || doc_key < after_key)) key[j] = doc_key;
+          }
+          n_cand += (uint32_t)__popcll(__ballot(key[j] != 0ull));
+        }
+        final_count_slice(s, tl.part, lane, hits);
+      }
+    }
+    if (lane == 0) s.wcount[par][wave] = n_cand;
+    __syncthreads();
+
+    // ---- the round's candidates into the shared buffer (docset_sort_kernel's meeting)
+    uint32_t tot = 0, before = 0;
+#pragma unroll
+    for (uint32_t w2 = 0; w2 < (uint32_t)kScanWaves; ++w2) {
+      const uint32_t c = s.wcount[par][w2];
+      tot += c;
+      before += w2 < wave ? c : 0u;
+    }
+    if (cnt + tot <= (uint32_t)kFsCandCap) {   // uniform
+      docset_push_candidates(s, key, lane, cnt + before);
+      cnt += tot;
+    } else {
+      for (uint32_t w2 = 0; w2 < (uint32_t)kScanWaves; ++w2) {
+        const uint32_t c = s.wcount[par][w2];
+        if (cnt + c > (uint32_t)kFsCandCap) {   // uniform; cnt > k here (kFsCandCap >= kMaxK + kTileDocs)
+          __syncthreads();   // the keys appended so far are in place
+          uint64_t thr = 0;
+          cnt = topk_compact<kScanThreads, kFsCandCap>(s.cand, cnt, k, &s.sc, &thr);
+          if (thr > theta) theta = thr;
+          if (tid == 0) atomicMax(my_theta_g, (unsigned long long)thr);
+        }
+        if (wave == w2) docset_push_candidates(s, key, lane, cnt);
+        cnt += c;
+      }
+    }
+  }
+
+  final_epilogue(s, cnt, k, q, tid, slice_sum, item_keys, item_counts, item_hits, k_stride);
+}
+
+// docset_terms_count_kernel over docset_hit_set_multi, with the count column's arity read from the query's record: every value
+// of a hit adds 1, each hit lane walking its own codes[start[d] .. start[d + 1]).
+__global__ __launch_bounds__(kScanThreads, kScanWaves / 4)
+void docset_terms_count_multi_kernel(const DItem* __restrict__ items, const DPart* __restrict__ parts, const DQuery* __restrict__ queries,
+                                     const DTermsQuery* __restrict__ tqueries, const DRangeQuery* __restrict__ rqueries,
+                                     const DSortPart* __restrict__ sparts, const DSortPart* __restrict__ rparts, DTermsState* __restrict__ states,
+                                     unsigned long long* __restrict__ tables, uint32_t* __restrict__ slice_sum, uint32_t* __restrict__ item_counts,
+                                     uint64_t* __restrict__ item_hits) {
+  __shared__ DocsetTermsSmem s;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)), lane = tid & 63u;
+  const DItem* const item = items + blockIdx.x;
+  const uint32_t query = item->query, part_begin = item->part_begin, n_parts = item->n_parts;
+  const DQuery* const q = queries + query;
+  const DTermsQuery* const tq = tqueries + query;
+  const DRangeQuery* const rq = rqueries + query;
+  const uint32_t max_buckets = tq->max_buckets, shift = tq->table_shift;
+  const bool multi = (tq->need & kTermsQueryMulti) != 0u;   // uniform: the query's count column is multi-valued
+  const uint32_t mask = (1u << (32u - shift)) - 1u;
+  unsigned long long* const table = tables + tq->table_off;
+  DTermsState* const st = states + query;
+
+  for (uint32_t i = tid; i < (uint32_t)kTermsLdsSlots; i += (uint32_t)kScanThreads) s.table[i] = 0ull;
+  if (tid < (uint32_t)kSliceSlots) s.slot_hits[tid] = s.slot_slice[tid] = 0u;
+  __syncthreads();
+
+  const uint32_t total_tiles = final_total_tiles(parts, part_begin, n_parts);
+  uint32_t pi = 0;      // the part of the wave's sub-tile (indices only grow)
+
+  for (uint32_t g = wave; g < total_tiles; g += (uint32_t)kScanWaves) {
+    const FinalTile tl = final_tile(parts, part_begin, n_parts, g, pi);
+    const uint32_t base = tl.base;
+    uint32_t words, hits;
+    const uint32_t m = docset_hit_set_multi(tl.part, rq, rparts + (size_t)(part_begin + pi) * (size_t)kMaxRanges, base, tl.tile_len, lane, words, hits);
+    if (words == 0u) continue;   // uniform
+    final_count_slice(s, tl.part, lane, hits);
+    if (__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(&st->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0) continue;
+    const DSortPart* const sp = sparts + part_begin + pi;
+    if (multi) {   // uniform
+      const NRT_GLOBAL uint32_t* const codes = (const NRT_GLOBAL uint32_t*)sp->code;
+      if (codes == nullptr) continue;   // uniform: the leaf lacks the column (or the column holds no value)
+      uint32_t s0[kFinalSlots], s1[kFinalSlots];
+      docset_value_spans(sp, base, lane, words, s0, s1);
+#pragma unroll
+      for (int j = 0; j < kFinalSlots; ++j) {
+        const uint32_t n = ((m >> j) & 1u) != 0u ? s1[j] - s0[j] : 0u;   // the lane's count bounds its walk
+#pragma unroll 1
+        for (uint32_t v = 0; v < n; ++v) terms_lds_add(s.table, table, shift, mask, max_buckets, st, codes[s0[j] + v], 1u);
+      }
+    } else {
+      uint32_t cv[kFinalSlots], has_bits;
+      if (!docset_column(sp, base, base >> 6, lane, words, cv, has_bits)) continue;
+      const uint32_t valued = m & has_bits;
+#pragma unroll
+      for (int j = 0; j < kFinalSlots; ++j)
+        if (((valued >> j) & 1u) != 0u) terms_lds_add(s.table, table, shift, mask, max_buckets, st, cv[j], 1u);
+    }
+  }
+
+  // ---- the item's table into the query's, once
+  __syncthreads();
+  if (__hip_atomic_load(&st->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
+    for (uint32_t i = tid; i < (uint32_t)kTermsLdsSlots; i += (uint32_t)kScanThreads) {
+      const unsigned long long w = s.table[i];
+      if (w != 0ull) terms_global_add(table, shift, mask, max_buckets, st, (uint32_t)w, (uint32_t)(w >> 32));
+    }
+  }
+
+  // ---- epilogue: final_epilogue's for an item without candidates
+  if (tid == 0) {
+    item_counts[blockIdx.x] = 0u;
+    uint32_t n = 0;
+    const uint32_t gte_floor = q->gte_floor, slice_base = q->slice_base;
+    for (int i = 0; i < kSliceSlots; ++i) {
+      const uint32_t h = s.slot_hits[i];
+      n += h;
+      if (h != 0u && gte_floor != 0xFFFFFFFFu) atomicAdd(&slice_sum[slice_base + s.slot_slice[i]], h);
+    }
+    item_hits[blockIdx.x] = n;
+  }
+}
+
 // terms_compact_kernel's launch (termscount.hip): the occupied slots of every query's table packed into `out`
 void launch_terms_compact(hipStream_t stream, const DTermsQuery* tqueries, DTermsState* states, const unsigned long long* tables, unsigned long long* out,
                           uint32_t n_queries, uint32_t out_cap);
@@ -320,6 +568,22 @@ void launch_docset_terms_count(hipStream_t stream, const FinalScoreArgs& a, cons
   if (a.n_items != 0)
     hipLaunchKernelGGL(docset_terms_count_kernel, dim3(a.n_items), dim3(kScanThreads), 0, stream, a.items, a.parts, a.queries, tqueries, rqueries, sparts,
                        rparts, states, tables, a.slice_sum, a.item_counts, a.item_hits);
+  launch_terms_compact(stream, tqueries, states, tables, out, n_queries, out_cap);
+}
+
+void launch_docset_sort_multi(hipStream_t stream, const FinalScoreArgs& a, const DSortQuery* squeries, const DRangeQuery* rqueries, const DSortPart* sparts,
+                              const DSortPart* rparts) {
+  if (a.n_items == 0) return;
+  hipLaunchKernelGGL(docset_sort_multi_kernel, dim3(a.n_items), dim3(kScanThreads), 0, stream, a.items, a.parts, a.queries, squeries, rqueries, sparts,
+                     rparts, a.theta_g, a.slice_sum, a.item_keys, a.item_counts, a.item_hits, a.k_stride);
+}
+
+void launch_docset_terms_count_multi(hipStream_t stream, const FinalScoreArgs& a, const DTermsQuery* tqueries, const DRangeQuery* rqueries,
+                                     const DSortPart* sparts, const DSortPart* rparts, DTermsState* states, unsigned long long* tables, unsigned long long* out,
+                                     uint32_t n_queries, uint32_t out_cap) {
+  if (a.n_items != 0)
+    hipLaunchKernelGGL(docset_terms_count_multi_kernel, dim3(a.n_items), dim3(kScanThreads), 0, stream, a.items, a.parts, a.queries, tqueries, rqueries,
+                       sparts, rparts, states, tables, a.slice_sum, a.item_counts, a.item_hits);
   launch_terms_compact(stream, tqueries, states, tables, out, n_queries, out_cap);
 }
 

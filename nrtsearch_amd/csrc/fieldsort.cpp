@@ -29,17 +29,35 @@ namespace nrtgpu {
 namespace rt {
 
 // ---- what the routes over a doc value column share (this file: sorted searches; termscount.cpp: the terms aggregation) ----------
-// The kind of the field's column over the leaves of the call; refusals by the header's table.
-int doc_values_kind(const nrtgpu_seg* const* segs, int32_t n_segs, int32_t field_id, int qi, int* kind) {
+// The kind and the arity of the field's column over the leaves of the call; refusals by the header's table.
+int doc_values_kind(const nrtgpu_seg* const* segs, int32_t n_segs, int32_t field_id, int qi, int* kind, bool* multi) {
   *kind = -1;
+  *multi = false;
   for (int si = 0; si < n_segs; ++si) {
     const auto fit = segs[si]->fields.find(field_id);
     if (fit == segs[si]->fields.end() || fit->second.dv_kind < 0) continue;
+    const bool m = fit->second.d_dv_start != nullptr;
     if (*kind >= 0 && *kind != fit->second.dv_kind)
       return fail(NRTGPU_ERR_INVALID_ARG, "query %d: the leaves of the call hold the doc values of field %d under different kinds (segment %d)", qi, field_id, si);
+    if (*kind >= 0 && *multi != m)
+      return fail(NRTGPU_ERR_INVALID_ARG, "query %d: the leaves of the call hold the doc values of field %d single-valued and multi-valued (segment %d)", qi, field_id, si);
     *kind = fit->second.dv_kind;
+    *multi = m;
   }
   return NRTGPU_OK;
+}
+
+DSortPart doc_values_column(const nrtgpu_seg* seg, int32_t field_id) {
+  const auto fit = seg->fields.find(field_id);
+  if (fit == seg->fields.end() || fit->second.dv_kind < 0) return DSortPart{nullptr, nullptr};
+  const FieldData& f = fit->second;
+  return f.d_dv_start != nullptr ? DSortPart{f.d_dv_code, (const uint64_t*)f.d_dv_start} : DSortPart{f.d_dv_code, f.d_dv_has};
+}
+
+// What the sorted routes refuse of a sort over a multi-valued column (beside "resident on no leaf": the column names no ONE value).
+int field_sort_multi(int qi, int32_t field_id) {
+  return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: the doc values of field %d are multi-valued: a sort names one value per doc (upload the selector's pick, "
+              "SortedNumericSelector MIN / MAX, as a single-valued column of its own)", qi, field_id);
 }
 
 int doc_values_masks_resident(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query& q, int qi) {
@@ -105,9 +123,7 @@ int doc_values_parts(const nrtgpu_seg* const* segs, int32_t n_segs, const int32_
       for (int32_t si = 0; si < n_segs && leaf < 0; ++si)
         if (hp.qs_begin[(size_t)it.query * (size_t)n_segs + (size_t)si] == p.term_begin) leaf = si;
       if (leaf < 0 || (uint32_t)segs[leaf]->max_doc != p.max_doc) return fail(NRTGPU_ERR_STATE, "%s: a part of query %u names no leaf", route, it.query);
-      const auto fit = segs[leaf]->fields.find(field_ids[it.query]);
-      if (fit == segs[leaf]->fields.end() || fit->second.dv_kind < 0) continue;   // no doc of the leaf has a value
-      (*out)[it.part_begin + pi] = DSortPart{fit->second.d_dv_code, fit->second.d_dv_has};
+      (*out)[it.part_begin + pi] = doc_values_column(segs[leaf], field_ids[it.query]);
     }
   }
   return NRTGPU_OK;
@@ -124,6 +140,7 @@ int check_call(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, c
                int32_t n_queries, std::vector<DSortQuery>* records, std::vector<int>* kinds, FlatQueries* flat) {
   flat->queries.reserve((size_t)n_queries);
   flat->terms.reserve((size_t)n_queries);
+  std::vector<char> multi;
   for (int qi = 0; qi < n_queries; ++qi) {
     const nrtgpu_bm25_query& q = queries[qi];
     const nrtgpu_field_sort& s = sorts[qi];
@@ -131,14 +148,17 @@ int check_call(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, c
     if (int rc = field_sort_check(s, qi)) return rc;
     if (q.has_after != 0) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: the query's has_after must be 0 (the cursor of a sorted search lives in the sort)", qi);
     int kind = -1;
-    if (int rc = doc_values_kind(segs, n_segs, s.field_id, qi, &kind)) return rc;
+    bool m = false;
+    if (int rc = doc_values_kind(segs, n_segs, s.field_id, qi, &kind, &m)) return rc;
     kinds->push_back(kind);
+    multi.push_back(m ? 1 : 0);
   }
   if (int rc = final_score_check_flags(ctx, "sorted")) return rc;
   for (int qi = 0; qi < n_queries; ++qi) {
     const nrtgpu_field_sort& s = sorts[qi];
     const int kind = (*kinds)[(size_t)qi];
     DSortQuery r{};
+    if (multi[(size_t)qi] != 0) return field_sort_multi(qi, s.field_id);
     if (int rc = doc_values_query(segs, n_segs, queries[qi], qi, kind, s.field_id, "a sort", &r.need, flat)) return rc;
     field_sort_record(s, kind, &r);
     if (records) records->push_back(r);

@@ -694,6 +694,10 @@ static_assert(sizeof(DSortQuery) == 32, "DSortQuery layout");
 struct alignas(16) DSortPart {
   const uint32_t* code;    // one code per doc, padded to whole sub-tiles; nullptr: the leaf lacks the column
   const uint64_t* has;     // bit d: doc d has a value; nullptr: every doc has
+                           // A MULTI-VALUED column (below: kTermsQueryMulti / DRangeQuery.multi say which are; the *_multi kernels
+                           // alone read one): `code` is codes[], the values' codes in upload order, and `has` is the uint32 start[]
+                           // -- one entry per doc, padded to whole sub-tiles, plus one; doc d's values are codes[start[d] ..
+                           // start[d + 1]); every padding entry equals the number of values
 };
 static_assert(sizeof(DSortPart) == 16, "DSortPart layout");
 
@@ -719,8 +723,12 @@ __host__ inline uint32_t terms_table_shift(uint32_t max_buckets) {
   while ((1u << log2) < 2u * max_buckets) ++log2;
   return 32u - log2;
 }
+constexpr uint32_t kTermsQueryMulti = 1u << 31;   // DTermsQuery.need: the count column is multi-valued
+static_assert((uint32_t)kMaxTerms < kTermsQueryMulti, "a clause count leaves DTermsQuery.need's top bit free");
 struct alignas(16) DTermsQuery {
-  uint32_t need;          // clauses a hit matches at least (DSortQuery.need)
+  uint32_t need;          // clauses a hit matches at least (DSortQuery.need); bit 31 (kTermsQueryMulti): the count column is
+                          // multi-valued -- set in calls that launch the *_multi kernels only, which mask it off; a call whose
+                          // named columns are all single-valued sets it nowhere, and its kernels read the word whole
   uint32_t max_buckets;
   uint32_t table_off;     // the query's global table: first slot ...
   uint32_t table_shift;   // ... and 32 - log2 of its slots
@@ -747,7 +755,9 @@ constexpr int kMaxRanges = 4;   // NRTGPU_MAX_RANGES
 __host__ __device__ inline bool range_accepts_code(uint32_t lo_code, uint32_t hi_code, uint32_t code) { return code >= lo_code && code <= hi_code; }
 struct alignas(16) DRangeQuery {
   uint32_t n_ranges;            // 0..kMaxRanges
-  uint32_t pad[3];
+  uint32_t multi;               // bit r: clause r's column is multi-valued -- the doc passes iff SOME value of it is in the range
+                                // (read by the *_multi kernels only: a call that sets a bit launches them)
+  uint32_t pad[2];
   uint32_t lo_code[kMaxRanges];
   uint32_t hi_code[kMaxRanges];
 };

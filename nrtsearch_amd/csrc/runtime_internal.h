@@ -73,6 +73,16 @@ void launch_docset_sort(hipStream_t stream, const FinalScoreArgs& a, const DSort
 void launch_docset_terms_count(hipStream_t stream, const FinalScoreArgs& a, const DTermsQuery* tqueries, const DRangeQuery* rqueries, const DSortPart* sparts,
                                const DSortPart* rparts, DTermsState* states, unsigned long long* tables, unsigned long long* out, uint32_t n_queries,
                                uint32_t out_cap);
+// the same three over calls that name a multi-valued column (termscount.hip: bm25_terms_count_multi_kernel; docset.hip:
+// docset_sort_multi_kernel, docset_terms_count_multi_kernel): a column's arity is the query's / the clause's flag (plan.h:
+// kTermsQueryMulti, DRangeQuery.multi), so a batch that mixes arities is one launch
+void launch_bm25_terms_count_multi(hipStream_t stream, const FinalScoreArgs& a, const DTermsQuery* tqueries, const DSortPart* sparts, DTermsState* states,
+                                   unsigned long long* tables, unsigned long long* out, uint32_t n_queries, uint32_t out_cap);
+void launch_docset_sort_multi(hipStream_t stream, const FinalScoreArgs& a, const DSortQuery* squeries, const DRangeQuery* rqueries, const DSortPart* sparts,
+                              const DSortPart* rparts);
+void launch_docset_terms_count_multi(hipStream_t stream, const FinalScoreArgs& a, const DTermsQuery* tqueries, const DRangeQuery* rqueries,
+                                     const DSortPart* sparts, const DSortPart* rparts, DTermsState* states, unsigned long long* tables, unsigned long long* out,
+                                     uint32_t n_queries, uint32_t out_cap);
 #ifdef NRTGPU_DEV
 void launch_debug_wave_kth(hipStream_t stream, const uint64_t* keys, uint32_t n, uint32_t r, uint64_t* out);   // (maxscore.hip: topk_kth_wave on its own)
 void launch_debug_walk_value(hipStream_t stream, float weight, const uint32_t* freq, const uint32_t* norm, const float* table, int fx_scale,
@@ -353,8 +363,13 @@ struct FieldData {
   // A per-doc value column (nrtgpu_segment_add_doc_values), independent of whatever else the field id holds: the values'
   // order-preserving codes (plan.h: doc_value_code), one per doc, padded to whole sub-tiles, and which docs have a value
   // (nullptr: every doc has).  dv_kind < 0: the field has no column.
+  // A MULTI-VALUED column (nrtgpu_segment_add_doc_values_multi; a field holds a column of one arity): d_dv_start != nullptr --
+  // one uint32 per doc, padded to whole sub-tiles, plus one; doc d's values are d_dv_code[d_dv_start[d] .. d_dv_start[d + 1]),
+  // their codes in upload order; the padding entries hold the number of values.  d_dv_code is nullptr when the column holds no
+  // value; d_dv_has is unused.
   uint32_t* d_dv_code = nullptr;
   uint64_t* d_dv_has = nullptr;
+  uint32_t* d_dv_start = nullptr;
   int32_t dv_kind = -1;
   // rows whose doc is live under the segment's current liveDocs (what an exact vector query matches), counted on first
   // use per liveDocs version
@@ -366,7 +381,7 @@ struct FieldData {
         d_vnorm2(o.d_vnorm2), d_ord_to_doc(o.d_ord_to_doc), h_ord_to_doc(o.h_ord_to_doc), dim(o.dim), n_vec(o.n_vec),
         vnorm2_max(o.vnorm2_max), d_sketch(o.d_sketch), sketch_state(o.sketch_state), sketch_scale(o.sketch_scale), absmax(o.absmax),
         vnorm2_min(o.vnorm2_min), byte_rows(o.byte_rows), d_btiles(o.d_btiles), d_bnorm2(o.d_bnorm2), d_dv_code(o.d_dv_code),
-        d_dv_has(o.d_dv_has), dv_kind(o.dv_kind) {}
+        d_dv_has(o.d_dv_has), d_dv_start(o.d_dv_start), dv_kind(o.dv_kind) {}
 };
 
 }  // namespace rt
@@ -1166,8 +1181,11 @@ struct FlatQueries {
   std::vector<nrtgpu_bm25_query> queries;
   std::vector<std::vector<nrtgpu_term>> terms;
 };
-// the kind of the field's column over the leaves of the call (-1: on no leaf); refuses leaves that disagree
-int doc_values_kind(const nrtgpu_seg* const* segs, int32_t n_segs, int32_t field_id, int qi, int* kind);
+// the kind of the field's column over the leaves of the call (-1: on no leaf) and whether it is multi-valued; refuses leaves
+// that disagree in either
+int doc_values_kind(const nrtgpu_seg* const* segs, int32_t n_segs, int32_t field_id, int qi, int* kind, bool* multi);
+// the field's column on one leaf as the kernels read it (plan.h: DSortPart, either arity); {nullptr, nullptr}: no doc of the leaf has a value
+DSortPart doc_values_column(const nrtgpu_seg* seg, int32_t field_id);
 // what both routes refuse of one query as unsupported, in the header's order (under: "a sort" / "a terms count"); *need: the
 // clauses a hit matches at least; the query's flat copy is pushed
 int doc_values_query(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query& q, int qi, int kind, int32_t field_id, const char* under,
@@ -1175,6 +1193,8 @@ int doc_values_query(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu
 // what the sorted routes (this one; docset.cpp) refuse of a nrtgpu_field_sort as an invalid argument, and its side of the record
 int field_sort_check(const nrtgpu_field_sort& s, int qi);
 void field_sort_record(const nrtgpu_field_sort& s, int kind, DSortQuery* r);
+// NRTGPU_ERR_UNSUPPORTED with the reason: the sort's column is multi-valued (both sorted routes, where they refuse "on no leaf")
+int field_sort_multi(int qi, int32_t field_id);
 // the FILTER / MUST_NOT masks of q are resident on every leaf of the call, else NRTGPU_ERR_UNSUPPORTED naming the query (what
 // doc_values_query refuses of them; docset.cpp asks the same of a doc-set query's masks)
 int doc_values_masks_resident(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query& q, int qi);
@@ -1195,7 +1215,7 @@ struct TermsWork {
 // what both refuse of (terms[qi], out[qi]) as an invalid argument (out: nullptr for the predicates), the column's kind over the
 // leaves, the query's record with its table behind the earlier queries' (*slots, *cap: the call's running sums)
 int terms_count_record(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_terms_count& t, const nrtgpu_term_counts* out, int qi, uint64_t* slots,
-                       uint64_t* cap, DTermsQuery* record, int* kind);
+                       uint64_t* cap, DTermsQuery* record, int* kind, bool* multi);
 // FinalScoreOwn.collect of both (user: the call's TermsWork): the states, then the entries that exist
 int terms_collect(nrtgpu_ctx* ctx, Slot* slot, const char* d_own, void* user);
 // the call's answers from what terms_collect brought back and the merge's (empty) lists

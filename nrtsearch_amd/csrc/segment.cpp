@@ -430,6 +430,60 @@ extern "C" int nrtgpu_segment_add_doc_values(nrtgpu_seg* seg, int32_t field_id, 
   return NRTGPU_OK;
 }
 
+// Any number of 32-bit values per doc of a field (every value of leaf.reader().getSortedNumericDocValues, or the global ordinals
+// of a SORTED_SET field): coded on the host by the same doc_value_code and resident as codes[] in upload order behind a uint32
+// start[] -- one entry per doc, padded to whole sub-tiles, plus one: a kernel reads start[d] and start[d + 1] of a sub-tile's docs
+// without a bounds test.
+extern "C" int nrtgpu_segment_add_doc_values_multi(nrtgpu_seg* seg, int32_t field_id, int32_t kind, int32_t n_values, const int32_t* value_docs,
+                                                   const void* values) {
+  if (!seg) return fail(NRTGPU_ERR_INVALID_ARG, "seg is NULL");
+  if (seg->sealed) return fail(NRTGPU_ERR_STATE, "segment already sealed");
+  if (kind != NRTGPU_DOCVALUES_INT32 && kind != NRTGPU_DOCVALUES_FLOAT32) return fail(NRTGPU_ERR_INVALID_ARG, "doc values kind %d outside 0..1", kind);
+  if (n_values < 0) return fail(NRTGPU_ERR_INVALID_ARG, "n_values %d", n_values);
+  if (n_values > 0 && (!value_docs || !values)) return fail(NRTGPU_ERR_INVALID_ARG, "value_docs or values is NULL with n_values %d", n_values);
+  for (int32_t i = 0; i < n_values; ++i)
+    if (value_docs[i] < 0 || value_docs[i] >= seg->max_doc || (i > 0 && value_docs[i] < value_docs[i - 1]))
+      return fail(NRTGPU_ERR_INVALID_ARG, "value_docs must be non-decreasing docids in [0,max_doc)");
+  {
+    const auto fit = seg->fields.find(field_id);
+    if (fit != seg->fields.end() && fit->second.dv_kind >= 0) return fail(NRTGPU_ERR_INVALID_ARG, "doc values of field %d already added", field_id);
+  }
+  HIP_TRY(hipSetDevice(seg->ctx->device));
+  const size_t n_start = (size_t)seg->n_tiles * (size_t)kTileDocs + 1, start_bytes = n_start * 4, code_bytes = (size_t)n_values * 4;
+  std::vector<uint32_t> start(n_start, (uint32_t)n_values), code((size_t)n_values);
+  const uint32_t* v = (const uint32_t*)values;
+  int32_t d = 0;   // start[d] = values of the docs below d
+  for (int32_t i = 0; i < n_values; ++i) {
+    for (; d <= value_docs[i]; ++d) start[(size_t)d] = (uint32_t)i;
+    code[(size_t)i] = doc_value_code(kind, v[i]);
+  }
+  void *d_start = nullptr, *d_code = nullptr;
+  if (int rc = dev_alloc(seg, &d_start, start_bytes)) return rc;
+  hipError_t e = hipMemcpy(d_start, start.data(), start_bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess && n_values > 0) {
+    if (int rc = dev_alloc(seg, &d_code, code_bytes)) {
+      (void)hipFree(d_start);
+      seg->device_bytes -= (int64_t)start_bytes;
+      return rc;
+    }
+    e = hipMemcpy(d_code, code.data(), code_bytes, hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess) {
+    (void)hipFree(d_start);
+    seg->device_bytes -= (int64_t)start_bytes;
+    if (d_code) {
+      (void)hipFree(d_code);
+      seg->device_bytes -= (int64_t)code_bytes;
+    }
+    return fail(NRTGPU_ERR_HIP, "upload of the doc values of field %d failed: %s", field_id, hipGetErrorString(e));
+  }
+  FieldData& f = seg->fields[field_id];   // (set when everything is resident)
+  f.d_dv_start = (uint32_t*)d_start;
+  f.d_dv_code = (uint32_t*)d_code;
+  f.dv_kind = kind;
+  return NRTGPU_OK;
+}
+
 static int fold_live_docs(nrtgpu_seg* seg);
 
 // What the MaxScore route needs per term besides the columns (plan.h: DTermAux), built on the device from the sealed
@@ -974,6 +1028,7 @@ SegCore::~SegCore() {
     if (f.d_ord_to_doc) (void)hipFree(f.d_ord_to_doc);
     if (f.d_dv_code) (void)hipFree(f.d_dv_code);
     if (f.d_dv_has) (void)hipFree(f.d_dv_has);
+    if (f.d_dv_start) (void)hipFree(f.d_dv_start);
     for (auto& g : f.groups) {
       if (g.d_docids) (void)hipFree(g.d_docids);
       if (g.d_dict) (void)hipFree(g.d_dict);

@@ -35,13 +35,14 @@ void TermsWork::layout(int32_t n, uint64_t slots, uint64_t cap) {
 // What the routes refuse of (terms[qi], out[qi]) as an invalid argument, the kind of the column over the leaves, and the query's
 // record with its table laid out behind the earlier queries' (*slots, *cap: the call's running sums).
 int terms_count_record(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_terms_count& t, const nrtgpu_term_counts* out, int qi, uint64_t* slots,
-                       uint64_t* cap, DTermsQuery* record, int* kind) {
+                       uint64_t* cap, DTermsQuery* record, int* kind, bool* multi) {
   if (t.max_buckets < 1 || t.max_buckets > NRTGPU_MAX_TERM_BUCKETS)
     return fail(NRTGPU_ERR_INVALID_ARG, "query %d: max_buckets %d outside 1..%d", qi, t.max_buckets, NRTGPU_MAX_TERM_BUCKETS);
   if (out && (out->capacity < t.max_buckets || !out->value_bits || !out->counts))
     return fail(NRTGPU_ERR_INVALID_ARG, "query %d: an output of capacity %d (or NULL arrays) for max_buckets %d", qi, out->capacity, t.max_buckets);
-  if (int rc = doc_values_kind(segs, n_segs, t.field_id, qi, kind)) return rc;
+  if (int rc = doc_values_kind(segs, n_segs, t.field_id, qi, kind, multi)) return rc;
   DTermsQuery r{};
+  r.need = *multi ? kTermsQueryMulti : 0u;
   r.max_buckets = (uint32_t)t.max_buckets;
   r.table_shift = terms_table_shift(r.max_buckets);
   r.table_off = (uint32_t)*slots;
@@ -104,10 +105,12 @@ int terms_unpack(const TermsWork& work, const std::vector<int>& kinds, const nrt
 namespace {
 
 // What the route refuses of a call before anything is planned (the segments' content is held); the records and the copies that
-// are planned on the way.  out: the batch entry's outputs (their capacities), nullptr for the predicate.
+// are planned on the way.  out: the batch entry's outputs (their capacities), nullptr for the predicate.  *any_multi: some query
+// counts a multi-valued column (the call launches bm25_terms_count_multi_kernel).
 int check_call(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query* queries, const nrtgpu_terms_count* terms,
                const nrtgpu_term_counts* out, int32_t n_queries, std::vector<DTermsQuery>* records, std::vector<int>* kinds, FlatQueries* flat,
-               TermsWork* work) {
+               TermsWork* work, bool* any_multi) {
+  *any_multi = false;
   flat->queries.reserve((size_t)n_queries);
   flat->terms.reserve((size_t)n_queries);
   records->reserve((size_t)n_queries);
@@ -117,15 +120,20 @@ int check_call(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, c
     const nrtgpu_terms_count& t = terms[qi];
     if (int rc = validate_query(q, qi)) return rc;
     int kind = -1;
+    bool multi = false;
     DTermsQuery r{};
-    if (int rc = terms_count_record(segs, n_segs, t, out ? &out[qi] : nullptr, qi, &slots, &cap, &r, &kind)) return rc;
+    if (int rc = terms_count_record(segs, n_segs, t, out ? &out[qi] : nullptr, qi, &slots, &cap, &r, &kind, &multi)) return rc;
     kinds->push_back(kind);
     records->push_back(r);
+    *any_multi = *any_multi || multi;
   }
   if (int rc = final_score_check_flags(ctx, "terms count")) return rc;
-  for (int qi = 0; qi < n_queries; ++qi)
-    if (int rc = doc_values_query(segs, n_segs, queries[qi], qi, (*kinds)[(size_t)qi], terms[qi].field_id, "a terms count", &(*records)[(size_t)qi].need, flat))
-      return rc;
+  for (int qi = 0; qi < n_queries; ++qi) {
+    DTermsQuery& r = (*records)[(size_t)qi];
+    uint32_t need = 0;
+    if (int rc = doc_values_query(segs, n_segs, queries[qi], qi, (*kinds)[(size_t)qi], terms[qi].field_id, "a terms count", &need, flat)) return rc;
+    r.need |= need;   // (beside kTermsQueryMulti)
+  }
   for (int qi = 0; qi < n_queries; ++qi) flat->queries[(size_t)qi].terms = flat->terms[(size_t)qi].data();   // (the vectors have settled)
   work->layout(n_queries, slots, cap);
   return NRTGPU_OK;
@@ -141,7 +149,8 @@ extern "C" int nrtgpu_count_terms_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* c
   std::vector<int> kinds;
   FlatQueries flat;
   TermsWork work;
-  if (int rc = check_call(ctx, segs, n_segs, q, t, nullptr, 1, &records, &kinds, &flat, &work)) return rc;
+  bool any_multi = false;
+  if (int rc = check_call(ctx, segs, n_segs, q, t, nullptr, 1, &records, &kinds, &flat, &work, &any_multi)) return rc;
   HostPlan hp;   // the planner is the predicate for the clauses, as in nrtgpu_query_supported
   return final_score_plan(ctx, segs, nullptr, n_segs, flat.queries.data(), 1, "terms count", hp);
 }
@@ -156,7 +165,8 @@ extern "C" int nrtgpu_count_terms_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const
   std::vector<int> kinds;
   FlatQueries flat;
   TermsWork work;
-  if (int rc = check_call(ctx, segs, n_segs, queries, terms, out, n_queries, &records, &kinds, &flat, &work)) return rc;
+  bool any_multi = false;
+  if (int rc = check_call(ctx, segs, n_segs, queries, terms, out, n_queries, &records, &kinds, &flat, &work, &any_multi)) return rc;
   HostPlan hp;
   if (int rc = final_score_plan(ctx, segs, doc_bases, n_segs, flat.queries.data(), n_queries, "terms count", hp)) return rc;
   std::vector<DSortPart> sparts;
@@ -166,12 +176,19 @@ extern "C" int nrtgpu_count_terms_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const
   const PlanBytes extras[2] = {{records.data(), records.size() * sizeof(DTermsQuery)}, {sparts.data(), sparts.size() * sizeof(DSortPart)}};
   std::vector<nrtgpu_topdocs> pages((size_t)n_queries, nrtgpu_topdocs{});   // (no hits come back: the merge's lists are empty; total_hits is read from them)
   const FinalScoreOwn own{work.bytes, terms_collect, &work};
-  if (int rc = final_score_run(ctx, hp, queries, n_queries, pages.data(), t0, extras, 2, [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
-        const TermsWork* w = (const TermsWork*)a.own_user;
-        char* d_own = (char*)a.own;
-        launch_bm25_terms_count(st, a, (const DTermsQuery*)d_extra[0], (const DSortPart*)d_extra[1], (DTermsState*)(d_own + w->o_states),
-                                (unsigned long long*)(d_own + w->o_tables), (unsigned long long*)(d_own + w->o_out), (uint32_t)w->n_queries, w->out_cap);
-      }, &own))
-    return rc;
+  // the dispatch: a call whose count columns are all single-valued launches what it always launched
+  const FinalScoreLaunch single = [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
+    const TermsWork* w = (const TermsWork*)a.own_user;
+    char* d_own = (char*)a.own;
+    launch_bm25_terms_count(st, a, (const DTermsQuery*)d_extra[0], (const DSortPart*)d_extra[1], (DTermsState*)(d_own + w->o_states),
+                            (unsigned long long*)(d_own + w->o_tables), (unsigned long long*)(d_own + w->o_out), (uint32_t)w->n_queries, w->out_cap);
+  };
+  const FinalScoreLaunch multi = [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
+    const TermsWork* w = (const TermsWork*)a.own_user;
+    char* d_own = (char*)a.own;
+    launch_bm25_terms_count_multi(st, a, (const DTermsQuery*)d_extra[0], (const DSortPart*)d_extra[1], (DTermsState*)(d_own + w->o_states),
+                                  (unsigned long long*)(d_own + w->o_tables), (unsigned long long*)(d_own + w->o_out), (uint32_t)w->n_queries, w->out_cap);
+  };
+  if (int rc = final_score_run(ctx, hp, queries, n_queries, pages.data(), t0, extras, 2, any_multi ? multi : single, &own)) return rc;
   return terms_unpack(work, kinds, pages.data(), n_queries, out);
 }
