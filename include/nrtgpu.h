@@ -161,7 +161,7 @@ int  nrtgpu_segment_seal(nrtgpu_seg* seg);
  * pass over the segment's postings: the postings of deleted docs are re-coded to score the neutral
  * element, so searches pay nothing per query for deletes.  Thread-safe against searches: the call waits for
  * the searches running over this segment and later ones wait for it (they see the new liveDocs; one
- * liveDocs version per segment handle at a time). */
+ * liveDocs version per segment handle at a time).  Bits at or beyond max_doc are ignored. */
 int  nrtgpu_segment_set_live_docs(nrtgpu_seg* seg, const uint64_t* bits, int32_t n_words);
 /* A new reader version of a sealed segment (what a refresh produces when only liveDocs changed): a handle that SHARES
  * the segment's postings, norms and vectors (nothing is copied or re-uploaded) and carries its own liveDocs (bits as
@@ -176,7 +176,7 @@ int  nrtgpu_segment_fork(nrtgpu_seg* seg, const uint64_t* live_bits, int32_t n_w
  * clause's per-leaf DocIdSet (what LRUQueryCache caches) as 64-bit words, bit d set = doc d matches,
  * and registers it under an id > 0 of its choosing; queries name ids (nrtgpu_bm25_query.filter_mask /
  * must_not_mask).  bits == NULL drops the mask.  Like set_live_docs: excludes itself from the searches
- * running over this segment. */
+ * running over this segment.  Bits at or beyond max_doc are ignored. */
 int  nrtgpu_segment_set_mask(nrtgpu_seg* seg, int32_t mask_id, const uint64_t* bits, int32_t n_words);
 void nrtgpu_segment_release(nrtgpu_seg* seg);
 /* bytes of HBM held by the segment (diagnostics) */

@@ -15,6 +15,10 @@ def keys_of(kind: str, n: int, rng) -> np.ndarray:
     docs = rng.choice(1 << 24, size=n, replace=False).astype(np.uint64)
     if kind == "full":        # scores over the whole range of positive floats: wide buckets
         bits = rng.integers(1, 0x7F7FFFFF, size=n, dtype=np.uint64)
+    elif kind == "unsigned":  # the sort routes' keys: order-preserving codes of a column over the whole unsigned range, top bit set too
+        bits = rng.integers(0, 1 << 32, size=n, dtype=np.uint64)
+        bits[:: 2] |= np.uint64(0x80000000)
+        bits[0] = np.uint64(0xFFFFFFFF)
     elif kind == "equal":     # one score: every key in one bucket -- the byte radix once there are more than 64 of them
         bits = np.full(n, np.float32(7.25).view(np.uint32), dtype=np.uint64)
     else:                     # scores of one query: a narrow range, the one-histogram path
@@ -25,7 +29,7 @@ def keys_of(kind: str, n: int, rng) -> np.ndarray:
     return keys
 
 
-@pytest.mark.parametrize("kind", ["narrow", "full", "equal", "third_zero"])
+@pytest.mark.parametrize("kind", ["narrow", "full", "unsigned", "equal", "third_zero"])
 def test_one_wave_finds_the_rth_largest_key(dev_lib, kind):
     rng = np.random.Generator(np.random.PCG64(2024))
     for n in SIZES:
