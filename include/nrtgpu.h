@@ -178,6 +178,60 @@ int  nrtgpu_segment_fork(nrtgpu_seg* seg, const uint64_t* live_bits, int32_t n_w
  * must_not_mask).  bits == NULL drops the mask.  Like set_live_docs: excludes itself from the searches
  * running over this segment.  Bits at or beyond max_doc are ignored. */
 int  nrtgpu_segment_set_mask(nrtgpu_seg* seg, int32_t mask_id, const uint64_t* bits, int32_t n_words);
+/* A mask BUILT ON THE DEVICE from the segment's resident doc value columns (nrtgpu_segment_add_doc_values / _multi), where the
+ * shim would otherwise materialise the clause's DocIdSet on the CPU and upload it: numeric range filters beside a text query
+ * ("pizza, rating >= 4"), a kNN pre-filter by a price range, "category in {a, b, c}" over a facet's ordinals (TermInSetQuery /
+ * IntPoint.newSetQuery), "has a photo" (FieldExistsQuery).  The mask is the set of docs of this leaf that pass EVERY clause; after
+ * the call mask_id behaves exactly as if the caller had computed those words and passed them to nrtgpu_segment_set_mask: usable
+ * as filter_mask / must_not_mask / more_* on every route, as a knn pre-filter and a function's filter_mask; replaced by either
+ * call and dropped by nrtgpu_segment_set_mask(seg, id, NULL, 0); private to the handle (a fork builds its own, over the shared
+ * column).  It does NOT contain liveDocs -- like a cached DocIdSet it is independent of deletes, the routes apply liveDocs
+ * themselves.  Bits at or beyond max_doc are 0; *out_count (may be NULL) is the number of set bits.
+ * Clauses.  "The column's order" is Integer.compare for ints; for floats the order of
+ * NumericUtils.floatToSortableInt(Float.floatToIntBits(.)): -0.0 < +0.0, every NaN the canonical one and above +inf.
+ *   NRTGPU_CLAUSE_RANGE   the doc-set range rule, word for word (nrtgpu_range_accepts): the doc has a value with
+ *                         lower <= value <= upper, both inclusive; lower > upper matches nothing and is not an error
+ *   NRTGPU_CLAUSE_EXISTS  the doc has at least one value; a float NaN is a value
+ *   NRTGPU_CLAUSE_IN_SET  the doc has a value whose code equals the code of a listed value [Lucene-recall]: for floats -0.0 and
+ *                         +0.0 are different members and any NaN in the list matches every NaN value -- how
+ *                         FloatPoint.newSetQuery / IntPoint.newSetQuery compare encoded points (src/main/java/com/yelp/nrtsearch/
+ *                         server/field/FloatFieldDef.java:180-182, IntFieldDef.java:174-176).  The values come in any order,
+ *                         duplicates allowed
+ * Over a MULTI-VALUED column a doc passes a clause iff SOME value of it passes; a doc with no value fails every clause kind.
+ * Lifetime and locking are nrtgpu_segment_set_mask's: the call excludes itself from the searches running over this segment and
+ * drops the segment's combined accept sets.  It is synchronous: one kernel launch over the columns, the words copied back to the
+ * host (where the accept sets are combined, as for every mask); nrtgpu_segment_device_bytes is unchanged by it.  Under
+ * nrtgpu_config.collect_timing the kernel's own time is nrtgpu_last_diagnostics' device_ms (total_ms: the call).
+ * Refusals, each with a reason in nrtgpu_last_error; all NRTGPU_ERR_INVALID_ARG checks come before any NRTGPU_ERR_UNSUPPORTED
+ * one, and a failed call leaves the previous mask under mask_id, if any, untouched:
+ *   NRTGPU_ERR_INVALID_ARG  seg or clauses NULL; mask_id <= 0; n_clauses outside 1..NRTGPU_MAX_RANGES; a clause kind outside
+ *                           0..2; reserved != 0; IN_SET with n_values outside 1..NRTGPU_MAX_SET_VALUES or value_bits NULL; RANGE
+ *                           or EXISTS with n_values != 0 or value_bits non-NULL
+ *   NRTGPU_ERR_STATE        the segment is not sealed
+ *   NRTGPU_ERR_UNSUPPORTED  a clause's column is not resident on this segment (its kind is then unknown, and a forgotten upload
+ *                           must not read as "no doc matches"; a caller who knows the leaf has no value registers zero words
+ *                           through nrtgpu_segment_set_mask)
+ * Out of scope: 64-bit columns; OR / NOT inside one mask (NOT is must_not_mask at the use site); clauses over postings; zone
+ * maps; combining accept sets on the device; the shim's eligibility logic. */
+#define NRTGPU_CLAUSE_RANGE  0   /* has a value with lower <= value <= upper (the doc-set range rule, word for word) */
+#define NRTGPU_CLAUSE_EXISTS 1   /* has a value (FieldExistsQuery over the doc values) */
+#define NRTGPU_CLAUSE_IN_SET 2   /* has a value equal to one of n_values given values (TermInSetQuery) */
+#define NRTGPU_MAX_SET_VALUES 4096   /* a design limit: the sorted set is staged in LDS (16 KiB) */
+typedef struct {
+  int32_t  kind;          /* NRTGPU_CLAUSE_* */
+  int32_t  field_id;      /* the column, INT32 or FLOAT32, single- or multi-valued */
+  uint32_t lower_bits;    /* RANGE: inclusive, bits of the column's kind; else 0 */
+  uint32_t upper_bits;
+  int32_t  n_values;      /* IN_SET: 1..NRTGPU_MAX_SET_VALUES; else 0 */
+  int32_t  reserved;      /* 0 */
+  const uint32_t* value_bits; /* IN_SET: n_values values, bits of the column's kind, any order, duplicates allowed; else NULL */
+} nrtgpu_value_clause;    /* 32 bytes */
+int  nrtgpu_segment_set_mask_from_values(nrtgpu_seg* seg, int32_t mask_id, const nrtgpu_value_clause* clauses,
+                                         int32_t n_clauses /* 1..NRTGPU_MAX_RANGES */, int64_t* out_count /* may be NULL */);
+/* The (max_doc + 63) / 64 words of a registered mask, however it was set (a shim persists a built mask across a fork with it).
+ * NRTGPU_ERR_INVALID_ARG: seg or bits NULL, mask_id <= 0, n_words below the need; NRTGPU_ERR_UNSUPPORTED: no mask is registered
+ * under the id. */
+int  nrtgpu_segment_get_mask(const nrtgpu_seg* seg, int32_t mask_id, uint64_t* bits, int32_t n_words);
 void nrtgpu_segment_release(nrtgpu_seg* seg);
 /* bytes of HBM held by the segment (diagnostics) */
 int64_t nrtgpu_segment_device_bytes(const nrtgpu_seg* seg);
@@ -1137,10 +1191,10 @@ int  nrtgpu_count_terms_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs
  *   NRTGPU_ERR_UNSUPPORTED  the sort or count column, or a range clause's column, is resident on no leaf of the call (its kind is
  *                           then unknown, and a forgotten upload must not read as "no hits"); a sort column that is multi-valued
  *                           (upload the selector's pick); a mask that is not resident
- * Out of scope: LONG / DOUBLE / DATE_TIME columns; sorting by a multi-valued column; TermInSetQuery filters; ranges inside the text routes,
- * or as resident masks for the MaxScore and kNN routes; a score-ordered match-all; skipping whole tiles by per-tile minima and
- * maxima of a column (zone maps); the coalesced, device-resident and nrtgpu_dist_* forms; the Java shim, which keeps sending
- * these requests to Lucene until it binds this.
+ * Out of scope: LONG / DOUBLE / DATE_TIME columns; sorting by a multi-valued column; a score-ordered match-all; skipping whole
+ * tiles by per-tile minima and maxima of a column (zone maps); the coalesced, device-resident and nrtgpu_dist_* forms; the Java
+ * shim, which keeps sending these requests to Lucene until it binds this.  (A range, an in-set or an exists clause beside a text
+ * query, a kNN query or any other route is a resident mask built from the column: nrtgpu_segment_set_mask_from_values.)
  * --------------------------------------------------------------------------------------------- */
 #define NRTGPU_MAX_RANGES 4       /* range clauses per doc-set query (a design limit) */
 typedef struct {

@@ -78,6 +78,15 @@ final class NrtGpu {
   static final MethodHandle SET_LIVE = h("nrtgpu_segment_set_live_docs", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT));
   static final MethodHandle FORK = h("nrtgpu_segment_fork", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, ADDRESS));
   static final MethodHandle SET_MASK = h("nrtgpu_segment_set_mask", FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT));
+  /**
+   * A mask built on the device from the segment's resident doc value columns (range / exists / in-set clauses, nrtgpu_value_clause:
+   * 32 bytes each), registered under the id like SET_MASK registers one; the last argument receives the number of its docs (may be
+   * NULL).  GpuMaskCache would call it where it materialises a numeric clause's DocIdSet today.
+   */
+  static final MethodHandle SET_MASK_FROM_VALUES =
+      h("nrtgpu_segment_set_mask_from_values", FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS));
+  /** The words of a registered mask, however it was set: what persists a built mask across a fork. */
+  static final MethodHandle GET_MASK = h("nrtgpu_segment_get_mask", FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT));
   static final MethodHandle RELEASE = h("nrtgpu_segment_release", FunctionDescriptor.ofVoid(ADDRESS));
   static final MethodHandle SUPPORTED = h("nrtgpu_query_supported", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, ADDRESS));
   /** What a request thread calls: one query, blocks; concurrent callers are merged into device batches inside the library. */

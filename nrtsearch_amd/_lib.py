@@ -39,6 +39,10 @@ NRTGPU_DOCVALUES_INT32 = 0
 NRTGPU_DOCVALUES_FLOAT32 = 1
 NRTGPU_MAX_TERM_BUCKETS = 65536
 NRTGPU_MAX_RANGES = 4
+NRTGPU_CLAUSE_RANGE = 0
+NRTGPU_CLAUSE_EXISTS = 1
+NRTGPU_CLAUSE_IN_SET = 2
+NRTGPU_MAX_SET_VALUES = 4096
 
 # every symbol include/nrtgpu.h declares (tests/test_abi.py checks the header against this list)
 ABI_SYMBOLS = [
@@ -68,6 +72,7 @@ ABI_SYMBOLS = [
     "nrtgpu_search_docset_sorted_batch", "nrtgpu_docset_sorted_supported", "nrtgpu_count_docset_terms_batch",
     "nrtgpu_count_docset_terms_supported", "nrtgpu_range_accepts",
     "nrtgpu_segment_add_doc_values_multi",
+    "nrtgpu_segment_set_mask_from_values", "nrtgpu_segment_get_mask",
 ]
 # what include/nrtgpu_dev.h adds: test hooks and measurement helpers of the development library (libnrtgpu_dev.so) only
 DEV_SYMBOLS = [
@@ -154,6 +159,11 @@ class RangeClause(C.Structure):   # nrtgpu_range_clause
     _fields_ = [("field_id", C.c_int32), ("lower_bits", C.c_uint32), ("upper_bits", C.c_uint32), ("reserved", C.c_int32)]
 
 
+class ValueClause(C.Structure):   # nrtgpu_value_clause
+    _fields_ = [("kind", C.c_int32), ("field_id", C.c_int32), ("lower_bits", C.c_uint32), ("upper_bits", C.c_uint32), ("n_values", C.c_int32),
+                ("reserved", C.c_int32), ("value_bits", C.POINTER(C.c_uint32))]
+
+
 class DocsetQuery(C.Structure):   # nrtgpu_docset_query
     _fields_ = [("filter_mask", C.c_int32), ("must_not_mask", C.c_int32), ("n_more_filters", C.c_int32), ("n_more_must_not", C.c_int32),
                 ("more_filters", C.POINTER(C.c_int32)), ("more_must_not", C.POINTER(C.c_int32)), ("n_ranges", C.c_int32), ("k", C.c_int32),
@@ -222,6 +232,8 @@ def _open(path: str) -> C.CDLL:
     L.nrtgpu_segment_seal.argtypes = [vp]
     L.nrtgpu_segment_set_live_docs.argtypes = [vp, vp, i32]
     L.nrtgpu_segment_set_mask.argtypes = [vp, i32, vp, i32]
+    L.nrtgpu_segment_set_mask_from_values.argtypes = [vp, i32, C.POINTER(ValueClause), i32, vp]
+    L.nrtgpu_segment_get_mask.argtypes = [vp, i32, vp, i32]
     L.nrtgpu_segment_release.argtypes = [vp]
     L.nrtgpu_segment_release.restype = None
     L.nrtgpu_segment_device_bytes.argtypes = [vp]

@@ -652,6 +652,22 @@ class GpuSegment:
         bits = np.ascontiguousarray(bits, dtype=np.uint64)
         _lib.check(_lib.load().nrtgpu_segment_set_mask(self._h, int(mask_id), bits.ctypes.data, len(bits)))
 
+    def set_mask_from_values(self, mask_id: int, clauses: Sequence["ValueClause"]) -> int:
+        """The mask of the docs that pass EVERY clause, built on the device from the segment's resident doc value columns
+        (nrtgpu_segment_set_mask_from_values) and registered under mask_id as set_mask registers one -> the number of its docs.
+        liveDocs are not part of it."""
+        vc, keep = _marshal_value_clauses(clauses)
+        count = C.c_int64(0)
+        _lib.check(_lib.load().nrtgpu_segment_set_mask_from_values(self._h, int(mask_id), vc, len(clauses), C.byref(count)))
+        del keep
+        return int(count.value)
+
+    def get_mask(self, mask_id: int) -> np.ndarray:
+        """The uint64 words of a registered mask, however it was set (nrtgpu_segment_get_mask)."""
+        bits = np.zeros((self.max_doc + 63) // 64, dtype=np.uint64)
+        _lib.check(_lib.load().nrtgpu_segment_get_mask(self._h, int(mask_id), bits.ctypes.data, len(bits)))
+        return bits
+
     @property
     def device_bytes(self) -> int:
         return int(_lib.load().nrtgpu_segment_device_bytes(self._h))
@@ -1501,6 +1517,76 @@ class DocSetQuery:
     filter: Tuple[MaskFilter, ...] = ()
     must_not: Tuple[MaskFilter, ...] = ()
     ranges: Tuple[RangeClause, ...] = ()
+
+
+@dataclasses.dataclass(frozen=True)
+class ValueClause:
+    """One clause of a mask built on the device from a doc value column (GpuSegment.set_mask_from_values; nrtgpu_value_clause):
+    range_ (RangeClause's rule: lower <= value <= upper, inclusive, in the kind's order), exists (FieldExistsQuery: the doc has a
+    value; a NaN is one) or in_set (TermInSetQuery / IntPoint.newSetQuery: a value equal to a listed one; floats compare as
+    encoded points: -0.0 and +0.0 are different members, any NaN matches every NaN).  Over a multi-valued column SOME value of
+    the doc passes; a doc without a value fails every clause.  `kind` says how lower / upper / values become bits -- the column's
+    own kind is the resident column's.  Use the constructors."""
+
+    clause: str                          # "range" | "exists" | "in_set"
+    field: int
+    kind: str = "int"
+    lower_bits: int = 0
+    upper_bits: int = 0
+    value_bits: bytes = b""             # in_set: the values' bits, uint32 after uint32 in native order (np.frombuffer(.., np.uint32))
+
+    @classmethod
+    def range_(cls, field: int, kind: str, lower, upper) -> "ValueClause":
+        if kind not in DOC_VALUE_KINDS:
+            raise UnsupportedQuery(f"a range clause of kind {kind!r}")
+        return cls("range", int(field), kind, _value_bits(kind, lower), _value_bits(kind, upper))
+
+    @classmethod
+    def exists(cls, field: int) -> "ValueClause":
+        return cls("exists", int(field))
+
+    @classmethod
+    def in_set(cls, field: int, kind: str, values) -> "ValueClause":
+        """values: any order, duplicates allowed; an array of the kind's dtype, or uint32 for the kind's raw bits (a NaN with a
+        payload), or a sequence of Python numbers.  No silent cast of an array of another dtype."""
+        if kind not in DOC_VALUE_KINDS:
+            raise UnsupportedQuery(f"an in-set clause of kind {kind!r}")
+        if isinstance(values, np.ndarray):
+            if values.dtype not in (DOC_VALUE_KINDS[kind][1], np.dtype(np.uint32)):
+                raise TypeError(f"values of kind {kind!r} must be {DOC_VALUE_KINDS[kind][1]} (or uint32 bits), got {values.dtype}")
+            bits = np.ascontiguousarray(values).reshape(-1).view(np.uint32)
+        else:
+            bits = np.array(list(values), dtype=DOC_VALUE_KINDS[kind][1]).reshape(-1).view(np.uint32)
+        if not 1 <= len(bits) <= _lib.NRTGPU_MAX_SET_VALUES:
+            raise ValueError(f"{len(bits)} values in a set: 1..{_lib.NRTGPU_MAX_SET_VALUES}")
+        return cls("in_set", int(field), kind, 0, 0, bits.tobytes())
+
+
+_VALUE_CLAUSE_KINDS = {"range": _lib.NRTGPU_CLAUSE_RANGE, "exists": _lib.NRTGPU_CLAUSE_EXISTS, "in_set": _lib.NRTGPU_CLAUSE_IN_SET}
+
+
+def _marshal_value_clauses(clauses: Sequence[ValueClause]):
+    """nrtgpu_value_clause per clause (and what keeps the sets' arrays alive)."""
+    n = len(clauses)
+    if not 1 <= n <= _lib.NRTGPU_MAX_RANGES:
+        raise ValueError(f"{n} clauses: 1..{_lib.NRTGPU_MAX_RANGES}")
+    vc = (_lib.ValueClause * n)()
+    keep: list = [vc]
+    for i, c in enumerate(clauses):
+        if c.clause not in _VALUE_CLAUSE_KINDS:
+            raise UnsupportedQuery(f"a value clause {c.clause!r}")
+        r = vc[i]
+        r.kind, r.field_id = _VALUE_CLAUSE_KINDS[c.clause], int(c.field)
+        if c.clause == "range":
+            r.lower_bits, r.upper_bits = int(c.lower_bits), int(c.upper_bits)
+        elif c.clause == "in_set":
+            n_values = len(c.value_bits) // 4
+            if len(c.value_bits) % 4 or not 1 <= n_values <= _lib.NRTGPU_MAX_SET_VALUES:
+                raise ValueError(f"{len(c.value_bits)} bytes of values in a set: 1..{_lib.NRTGPU_MAX_SET_VALUES} values of 4 bytes")
+            arr = (C.c_uint32 * n_values).from_buffer_copy(c.value_bits)
+            keep.append(arr)
+            r.n_values, r.value_bits = n_values, arr
+    return vc, keep
 
 
 def _marshal_docsets(docsets: Sequence[DocSetQuery], managers: Sequence[TopScoreDocCollectorManager]):

@@ -763,4 +763,36 @@ struct alignas(16) DRangeQuery {
 };
 static_assert(sizeof(DRangeQuery) == 48, "DRangeQuery layout");
 
+// Filter masks built from doc value columns (valuemask.hip: value_mask_kernel; valuemask.cpp:
+// nrtgpu_segment_set_mask_from_values): the docs of ONE leaf that pass every clause of a call, as 64-bit words.  A clause tests the
+// codes of one column of the leaf: a doc passes iff it HAS a value whose code passes; over a multi-valued column iff SOME value
+// of it does.  The three clause kinds of the ABI are two tests here:
+//   range    range_accepts_code(lo_code, hi_code, code) -- NRTGPU_CLAUSE_RANGE; NRTGPU_CLAUSE_EXISTS is the range of every code
+//   in set   the code is one of set_len > 0 codes, sorted ascending without duplicates, at sets[set_off ...] of the call's code
+//            array (NRTGPU_CLAUSE_IN_SET; lo_code / hi_code are the set's first and last code: one compare drops most values
+//            before the search).  The ONE statement of the search: value_set_has, over the workgroup's LDS copy in the kernel.
+constexpr int kMaxSetValues = 4096;      // NRTGPU_MAX_SET_VALUES: kMaxRanges sets fill the 64 KiB a launch may ask for
+constexpr int kValueMaskThreads = 256;   // 4 waves; a wave owns whole 64-doc words
+struct alignas(16) DValueClause {
+  const uint32_t* code;    // DSortPart.code of the column; nullptr: the column holds no value, no doc passes
+  const void* has;         // DSortPart.has: the uint64 `has` words (nullptr: every doc has) / multi != 0: the uint32 start[]
+  uint32_t lo_code, hi_code;
+  uint32_t set_off, set_len;   // set_len == 0: a range test
+  uint32_t multi;          // the column is multi-valued
+  uint32_t pad[3];
+};
+static_assert(sizeof(DValueClause) == 48, "DValueClause layout");
+// whether the sorted, duplicate-free set[0 .. len), len >= 1, holds code: a lower-bound search whose step count depends on len
+// alone (the lanes of a wave stay together); every index read lies below len
+template <class P>
+__host__ __device__ inline bool value_set_has(P set, uint32_t len, uint32_t code) {
+  uint32_t base = 0, n = len;
+  while (n > 1u) {   // if the code is in the set, its index lies in [base, base + n)
+    const uint32_t half = n >> 1;
+    if (set[base + half] <= code) base += half;
+    n -= half;
+  }
+  return set[base] == code;
+}
+
 }  // namespace nrtgpu

@@ -6,7 +6,7 @@
 // the single-query entries of search.cpp and vectors.cpp; standard library only), finalscore.cpp (the host
 // path of the final-score routes), funcscore.cpp (function-score queries), multimatch.cpp (multi-match queries),
 // fieldsort.cpp (a text query's hits sorted by a doc value column), termscount.cpp (its hits counted per value of one),
-// docset.cpp (both over a doc set without a text clause), vectors.cpp (exact kNN, vector rescoring).  Types the ABI names opaquely (nrtgpu_ctx, nrtgpu_seg) live in the global namespace;
+// docset.cpp (both over a doc set without a text clause), valuemask.cpp (filter masks built from doc value columns), vectors.cpp (exact kNN, vector rescoring).  Types the ABI names opaquely (nrtgpu_ctx, nrtgpu_seg) live in the global namespace;
 // everything else in nrtgpu::rt.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -83,6 +83,10 @@ void launch_docset_sort_multi(hipStream_t stream, const FinalScoreArgs& a, const
 void launch_docset_terms_count_multi(hipStream_t stream, const FinalScoreArgs& a, const DTermsQuery* tqueries, const DRangeQuery* rqueries,
                                      const DSortPart* sparts, const DSortPart* rparts, DTermsState* states, unsigned long long* tables, unsigned long long* out,
                                      uint32_t n_queries, uint32_t out_cap);
+// a filter mask of one leaf from its doc value columns (valuemask.hip): n_clauses DValueClause, the IN_SET clauses' code sets
+// (n_set_codes codes in all, staged in LDS), n_words words out
+void launch_value_mask(hipStream_t stream, const DValueClause* clauses, uint32_t n_clauses, const uint32_t* sets, uint32_t n_set_codes, uint64_t* out,
+                       uint32_t n_words, uint32_t max_doc);
 #ifdef NRTGPU_DEV
 void launch_debug_wave_kth(hipStream_t stream, const uint64_t* keys, uint32_t n, uint32_t r, uint64_t* out);   // (maxscore.hip: topk_kth_wave on its own)
 void launch_debug_walk_value(hipStream_t stream, float weight, const uint32_t* freq, const uint32_t* norm, const float* table, int fx_scale,
@@ -710,6 +714,9 @@ void release_slot(nrtgpu_ctx* ctx, Slot* s);
 // count (optional): the set's docs -- its bits below max_doc, counted where the set is built and kept with it
 int accept_set_of(const nrtgpu_seg* seg, int32_t filter_mask, int32_t must_not_mask, const uint64_t** out, int64_t* count = nullptr);
 int accept_set_of(const nrtgpu_seg* seg, const nrtgpu_bm25_query& q, const uint64_t** out);   // all of the query's FILTER / MUST_NOT masks
+// segment.cpp: every combined accept set of the handle freed -- a mask or liveDocs changed.  The caller holds the content
+// exclusively (SegWriteLock), is its last reader, or destroys the handle.
+void drop_accept_sets(nrtgpu_seg* seg);
 // vectors of the field whose doc is live (the hits of an exact vector query over the segment)
 int64_t live_vector_count(const nrtgpu_seg* seg, const FieldData& f);
 int ensure_vector_sketch(const nrtgpu_seg* seg, int32_t field_id);

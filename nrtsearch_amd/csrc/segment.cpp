@@ -54,7 +54,7 @@ static const size_t kMaskPadBytes = 256;  // doc-set masks are readable one sub-
 static const size_t kMaxRetiredAcceptSets = 64;   // evicted sets that wait for the searches in flight to end (then: refuse instead of evict)
 
 // (no search is in flight over the handle: the caller holds the content exclusively, or is its last reader, or destroys it)
-static void drop_accept_sets(nrtgpu_seg* seg) {
+void nrtgpu::rt::drop_accept_sets(nrtgpu_seg* seg) {
   std::lock_guard<std::mutex> lk(seg->accept_mu);
   const int64_t set_bytes = (int64_t)((seg->max_doc + 63) / 64) * 8;
   for (auto& kv : seg->accept) {
