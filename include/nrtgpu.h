@@ -133,7 +133,8 @@ int  nrtgpu_segment_add_byte_vectors(nrtgpu_seg* seg, int32_t field_id, int32_t 
  * doc lacks a value.  Sorting is its first reader (nrtgpu_search_sorted_batch).  NRTGPU_ERR_INVALID_ARG: kind out of range,
  * n < 0 or n > max_doc, docs not strictly ascending or outside [0, max_doc), docs == NULL with n != max_doc, values == NULL with
  * n > 0, a second column on the field -- of either arity: a field that holds a multi-valued column
- * (nrtgpu_segment_add_doc_values_multi) takes no single-valued one.  Out of scope: 64-bit values, updatable doc values. */
+ * (nrtgpu_segment_add_doc_values_multi) takes no single-valued one.  64-bit values are nrtgpu_segment_add_doc_values64's.  Out of
+ * scope: updatable doc values. */
 #define NRTGPU_DOCVALUES_INT32 0    /* IntFieldDef: SortField.Type.INT */
 #define NRTGPU_DOCVALUES_FLOAT32 1  /* FloatFieldDef: SortField.Type.FLOAT */
 int  nrtgpu_segment_add_doc_values(nrtgpu_seg* seg, int32_t field_id, int32_t kind, int32_t n, const int32_t* docs,
@@ -154,6 +155,27 @@ int  nrtgpu_segment_add_doc_values(nrtgpu_seg* seg, int32_t field_id, int32_t ki
  * outside [0, max_doc), a second column of either arity on the field. */
 int  nrtgpu_segment_add_doc_values_multi(nrtgpu_seg* seg, int32_t field_id, int32_t kind, int32_t n_values,
                                          const int32_t* value_docs, const void* values);
+/* A per-doc value column of 64-BIT values: LongFieldDef, DateTimeFieldDef (epoch milliseconds) and DoubleFieldDef doc values,
+ * which the reference sorts as SortField.Type.LONG / DOUBLE (src/main/java/com/yelp/nrtsearch/server/field/DateTimeFieldDef.java:
+ * 108-125, LongFieldDef.java:103-105, DoubleFieldDef.java:105-107) and filters with SortedNumericDocValuesField.newSlowRangeQuery
+ * over 64-bit values (LongFieldDef.java:124-154, DateTimeFieldDef.java:133-167).  nrtgpu_segment_add_doc_values' contract, word
+ * for word, with values of n x 8 bytes: the column is single-valued (the selector's pick for a multi-valued field); docs strictly
+ * ascending, or NULL with n == max_doc; before the seal only (after: NRTGPU_ERR_STATE); forks share it;
+ * nrtgpu_segment_device_bytes counts it; a field holds ONE column of any width or arity (a second one: NRTGPU_ERR_INVALID_ARG,
+ * like every other argument error listed there; kind outside 2..3 is one).  Resident as one order-preserving uint64 code per doc,
+ * padded to whole sub-tiles, plus the `has` words where some doc lacks a value; the least and the greatest code of the column
+ * stay on the segment (a column with n == 0 has none): the window a sort packs its keys in.  Codes compare like Long.compare /
+ * Double.compare: -0.0 < +0.0, every NaN the canonical 0x7FF8000000000000 and above +inf.
+ * Readers: nrtgpu_search_sorted64_batch, nrtgpu_search_docset_sorted64_batch, nrtgpu_segment_set_mask_from_values64.  The 32-bit
+ * entries (nrtgpu_search_sorted_batch, nrtgpu_count_terms_batch, the doc-set entries' sort, count and range clauses,
+ * nrtgpu_segment_set_mask_from_values) refuse a field that holds a 64-bit column with NRTGPU_ERR_UNSUPPORTED, the reason naming
+ * the 64-bit entry (terms counts: 64-bit buckets are not built); the 64-bit entries refuse a 32-bit or multi-valued column the
+ * same way.  Neither reads a column at the other width.  Out of scope: multi-valued 64-bit columns, terms counts and doc-set
+ * range CLAUSES over 64-bit columns (a range over one is a built mask), updatable doc values. */
+#define NRTGPU_DOCVALUES_INT64   2  /* LongFieldDef, DateTimeFieldDef (epoch millis): SortField.Type.LONG */
+#define NRTGPU_DOCVALUES_FLOAT64 3  /* DoubleFieldDef: SortField.Type.DOUBLE */
+int  nrtgpu_segment_add_doc_values64(nrtgpu_seg* seg, int32_t field_id, int32_t kind, int32_t n, const int32_t* docs,
+                                     const void* values /* n x 8 bytes */);
 /* builds the per-term doc-range tables; the segment becomes searchable */
 int  nrtgpu_segment_seal(nrtgpu_seg* seg);
 /* leaf.getLiveDocs() as 64-bit words, bit d set = doc d live; NULL => all live.  May be called
@@ -211,7 +233,8 @@ int  nrtgpu_segment_set_mask(nrtgpu_seg* seg, int32_t mask_id, const uint64_t* b
  *   NRTGPU_ERR_UNSUPPORTED  a clause's column is not resident on this segment (its kind is then unknown, and a forgotten upload
  *                           must not read as "no doc matches"; a caller who knows the leaf has no value registers zero words
  *                           through nrtgpu_segment_set_mask)
- * Out of scope: 64-bit columns; OR / NOT inside one mask (NOT is must_not_mask at the use site); clauses over postings; zone
+ * 64-bit columns: nrtgpu_segment_set_mask_from_values64 below (this entry refuses them: NRTGPU_ERR_UNSUPPORTED).
+ * Out of scope: OR / NOT inside one mask (NOT is must_not_mask at the use site); clauses over postings; zone
  * maps; combining accept sets on the device; the shim's eligibility logic. */
 #define NRTGPU_CLAUSE_RANGE  0   /* has a value with lower <= value <= upper (the doc-set range rule, word for word) */
 #define NRTGPU_CLAUSE_EXISTS 1   /* has a value (FieldExistsQuery over the doc values) */
@@ -228,6 +251,33 @@ typedef struct {
 } nrtgpu_value_clause;    /* 32 bytes */
 int  nrtgpu_segment_set_mask_from_values(nrtgpu_seg* seg, int32_t mask_id, const nrtgpu_value_clause* clauses,
                                          int32_t n_clauses /* 1..NRTGPU_MAX_RANGES */, int64_t* out_count /* may be NULL */);
+/* The same over 64-BIT columns (nrtgpu_segment_add_doc_values64): "in the last 30 days" over a DATE_TIME column, a price range
+ * over a DOUBLE one (LongFieldDef.java:124-154, DateTimeFieldDef.java:133-167: SortedNumericDocValuesField.newSlowRangeQuery).
+ * nrtgpu_segment_set_mask_from_values' contract, word for word: the registered mask is usable on every route, independent of
+ * liveDocs, bits at or beyond max_doc are 0, a failed call leaves the old mask in place, all NRTGPU_ERR_INVALID_ARG checks come
+ * before any NRTGPU_ERR_UNSUPPORTED one, the call is synchronous and reports device_ms under collect_timing.
+ *   NRTGPU_CLAUSE_RANGE   the doc has a value with lower <= value <= upper, both inclusive, in the kind's order (Long.compare;
+ *                         for doubles the order of NumericUtils.doubleToSortableLong [Lucene-recall]: -0.0 < +0.0, every NaN the
+ *                         canonical one and above +inf, so [-inf, +inf] drops the NaN docs and [NaN, NaN] keeps only them);
+ *                         lower > upper matches nothing (nrtgpu_range_accepts64)
+ *   NRTGPU_CLAUSE_EXISTS  the doc has a value
+ * NRTGPU_ERR_INVALID_ARG: seg or clauses NULL; mask_id <= 0; n_clauses outside 1..NRTGPU_MAX_RANGES; a clause kind outside 0..1
+ * (no IN_SET); reserved != 0.  NRTGPU_ERR_STATE: the segment is not sealed.  NRTGPU_ERR_UNSUPPORTED: a clause's column is not
+ * resident on this segment, or is a 32-bit or multi-valued column (nrtgpu_segment_set_mask_from_values).  "Rating >= 4 AND in
+ * the last 30 days" is two masks, named as filter_mask and more_filters. */
+typedef struct {
+  int32_t  kind;          /* NRTGPU_CLAUSE_RANGE | NRTGPU_CLAUSE_EXISTS */
+  int32_t  field_id;      /* the column, INT64 or FLOAT64 */
+  uint64_t lower_bits;    /* RANGE: inclusive, bits of the column's kind; else 0 */
+  uint64_t upper_bits;
+  int64_t  reserved;      /* 0 */
+} nrtgpu_value_clause64;  /* 32 bytes */
+int  nrtgpu_segment_set_mask_from_values64(nrtgpu_seg* seg, int32_t mask_id, const nrtgpu_value_clause64* clauses,
+                                           int32_t n_clauses /* 1..NRTGPU_MAX_RANGES */, int64_t* out_count /* may be NULL */);
+/* Whether a 64-bit range clause keeps a doc whose value is value_bits (kind: NRTGPU_DOCVALUES_INT64 / _FLOAT64; *out = 1 / 0),
+ * exposed for the tests: needs no device; it is the very function the kernel compiles.  kind outside 2..3 or out NULL:
+ * NRTGPU_ERR_INVALID_ARG. */
+int  nrtgpu_range_accepts64(int32_t kind, uint64_t lower_bits, uint64_t upper_bits, uint64_t value_bits, int32_t* out);
 /* The (max_doc + 63) / 64 words of a registered mask, however it was set (a shim persists a built mask across a fork with it).
  * NRTGPU_ERR_INVALID_ARG: seg or bits NULL, mask_id <= 0, n_words below the need; NRTGPU_ERR_UNSUPPORTED: no mask is registered
  * under the id. */
@@ -1036,8 +1086,8 @@ int  nrtgpu_text_knn_exact(const nrtgpu_bm25_query* q, const nrtgpu_knn_clauses*
  *                           NRTGPU_FLAG_PACKED_POSTINGS or NRTGPU_FLAG_NO_FIXED_POINT, a batch whose queries do not all pass
  *                           the fixed-point analysis -- the final-score routes' refusals, kept as they are: a KNOWN LIMIT, they
  *                           are stricter than a route that reads no score needs
- * Out of scope: 64-bit columns (LONG / DATE_TIME / DOUBLE need keys wider than the top-k's 64 bits -- the next step, and why this
- * cannot serve "newest first" yet); STRING ordinals; LAT_LON distance; virtual (script) fields; more than one sort level; `score`
+ * 64-bit columns (LONG / DATE_TIME / DOUBLE, "newest first") are nrtgpu_search_sorted64_batch's, below; this entry refuses them.
+ * Out of scope: STRING ordinals; LAT_LON distance; virtual (script) fields; more than one sort level; `score`
  * or `docid` as a sort level; scores beside the values; dismax / multi-match text under a sort (a match-all or filter-only query
  * under a sort is nrtgpu_search_docset_sorted_batch);
  * updatable doc values; the coalesced, device-resident and nrtgpu_dist_* forms; the Java shim, which does not bind this yet.
@@ -1071,6 +1121,67 @@ int  nrtgpu_sorted_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int
 /* The high word of the key a value sorts under (kind: NRTGPU_DOCVALUES_*), exposed for the tests: needs no device; it is the
  * very function the kernel compiles.  Larger = earlier in the sort's order.  kind or reverse outside 0..1: NRTGPU_ERR_INVALID_ARG. */
 int  nrtgpu_sort_value_code(int32_t kind, int32_t reverse, uint32_t value_bits, uint32_t* out_key_high);
+
+/* ---------------------------------------------------------------------------------------------
+ * Sort by a 64-BIT field: "newest first" over a DATE_TIME column (epoch milliseconds as INT64: DateTimeFieldDef.getSortField,
+ * src/main/java/com/yelp/nrtsearch/server/field/DateTimeFieldDef.java:108-125, sorts SortField.Type.LONG), ids, counters and
+ * prices (LongFieldDef / DoubleFieldDef).  Semantics are nrtgpu_search_sorted_batch's, word for word, with 64-bit values and
+ * Long.compare / Double.compare where it has Integer.compare / Float.compare [Lucene-recall]: matching (clause counts, MUST /
+ * min_should_match, duplicates counting each, accept sets), the exact total_hits and the per-slice relation rule, slicing, thread
+ * slices, deadlines, items_scan, scan_*; a doc without a value, or in a leaf without the column, sorts AS and reports
+ * missing_bits (the reference's missing values are Long.MIN_VALUE / MAX_VALUE and -+inf: LongFieldDef.java:103-105,
+ * DoubleFieldDef.java:105-107); a NaN comes back as 0x7FF8000000000000.  The cursor (has_after, after_doc, after_bits) is tested
+ * on values: a hit is collected iff (its value, its docid) ranks strictly behind (after_bits, after_doc) in the sort's order.
+ * ONE PASS through the unchanged top-k: the keys stay 64 bits.  Per query, D is the maximum of doc_bases[i] + max_doc[i] over the
+ * leaves, db = max(1, bit_length(D - 1)) the bits its global docids need, [lo, hi] the least and the greatest CODE of the sort's
+ * column over the leaves of the call that hold a value (both the missing value's code if none does), span = hi - lo.  A key
+ * packs the value's ordinal in that window -- 0 below lo, 1 + (code - lo) inside, span + 2 above hi; only the missing value can
+ * lie outside -- above a db-bit docid field (nrtgpu_sort_key64).  THE SORT FITS iff span + 3 <= 2^(64 - db) - 1: with 10 M docs
+ * 40 bits are left for values -- 34 years of milliseconds, any seconds column, any realistic id range.  A sort that does not fit
+ * is refused with the reason, not widened.
+ * The predicates have no doc_bases: they derive db from the leaves in order, with base 0 for the first (base[i + 1] = base[i] +
+ * max_doc[i]); the batch entries use the caller's doc_bases (NULL: every leaf at base 0).  With the bases a searcher passes --
+ * the leaves in order -- the two agree.
+ * Refusals: nrtgpu_search_sorted_batch's table with the same statuses and precedence, and
+ *   NRTGPU_ERR_INVALID_ARG  leaves that hold the field under different kinds
+ *   NRTGPU_ERR_UNSUPPORTED  the column is resident on no leaf; it is a 32-bit or multi-valued column (the reason names
+ *                           nrtgpu_search_sorted_batch); the sort does not fit -- the reason names the query, the field, the
+ *                           bits the column's span needs and the bits the call's docids leave ("span needs 41 bits, 26-bit docids
+ *                           leave 38"); a doc_bases[i] + max_doc[i] beyond 2^31
+ * The text route keeps the final-score routes' flag and fixed-point refusals (the known limit).
+ * Out of scope: DOUBLE columns whose values span more than the key leaves (two doubles of different sign never fit); a second
+ * sort level; terms counts over 64-bit columns; multi-valued 64-bit columns; the Java shim, which does not bind this yet.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct {
+  int32_t  field_id;      /* the column */
+  int32_t  reverse;       /* 0 ascending, 1 descending */
+  uint64_t missing_bits;  /* what a doc without a value sorts AS, bits of the column's kind, taken verbatim */
+  int32_t  has_after;     /* FieldDoc searchAfter */
+  int32_t  after_doc;     /* global docid */
+  uint64_t after_bits;    /* the last hit's sort value */
+} nrtgpu_field_sort64;    /* 32 bytes */
+typedef struct {
+  int32_t   n_hits;                     /* out: hits written, <= k */
+  int32_t   capacity;                   /* in : capacity of docs / value_bits (>= k) */
+  int32_t*  docs;                       /* out: global docids, in the sort's order */
+  uint64_t* value_bits;                 /* out: the value each hit sorted as, bits of the column's kind */
+  int64_t   total_hits;                 /* out: live matching docs, exact */
+  int32_t   total_hits_is_lower_bound;  /* out: 1 == GREATER_THAN_OR_EQUAL_TO (the per-slice rule) */
+} nrtgpu_fielddocs64;                   /* 40 bytes */
+int  nrtgpu_search_sorted64_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                  const nrtgpu_bm25_query* queries, const nrtgpu_field_sort64* sorts, int32_t n_queries,
+                                  nrtgpu_fielddocs64* out);
+/* The eligibility test alone (db from the leaves in order, above).  No device work. */
+int  nrtgpu_sorted64_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query* q,
+                               const nrtgpu_field_sort64* s);
+/* (The doc-set form, nrtgpu_search_docset_sorted64_batch, is declared with the doc-set requests below.) */
+/* The key of one doc, exposed for the tests: needs no device; it is the very function the kernels compile.  (lo_bits, hi_bits):
+ * the column's window as VALUES of the kind; has_value == 0: the doc sorts as missing_bits (value_bits is not read).  Larger =
+ * earlier in the sort's order.  NRTGPU_ERR_UNSUPPORTED when (lo, hi, doc_bits) do not fit; NRTGPU_ERR_INVALID_ARG: out_key NULL,
+ * kind outside 2..3, reverse / has_value outside 0..1, doc_bits outside 1..31, global_doc outside [0, 2^doc_bits), lo > hi in
+ * the kind's order, a value outside [lo, hi].  The argument checks come first. */
+int  nrtgpu_sort_key64(int32_t kind, int32_t reverse, uint64_t lo_bits, uint64_t hi_bits, uint64_t missing_bits, int32_t doc_bits,
+                       int32_t has_value, uint64_t value_bits, int32_t global_doc, uint64_t* out_key);
 
 /* ---------------------------------------------------------------------------------------------
  * Terms aggregation: a text query's hits counted per distinct value of an int or float doc value column
@@ -1191,7 +1302,8 @@ int  nrtgpu_count_terms_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs
  *   NRTGPU_ERR_UNSUPPORTED  the sort or count column, or a range clause's column, is resident on no leaf of the call (its kind is
  *                           then unknown, and a forgotten upload must not read as "no hits"); a sort column that is multi-valued
  *                           (upload the selector's pick); a mask that is not resident
- * Out of scope: LONG / DOUBLE / DATE_TIME columns; sorting by a multi-valued column; a score-ordered match-all; skipping whole
+ * A sort by a LONG / DATE_TIME / DOUBLE column is nrtgpu_search_docset_sorted64_batch below; range clauses and counts over such
+ * columns stay out of scope (a range over one is a built mask).  Out of scope: sorting by a multi-valued column; a score-ordered match-all; skipping whole
  * tiles by per-tile minima and maxima of a column (zone maps); the coalesced, device-resident and nrtgpu_dist_* forms; the Java
  * shim, which keeps sending these requests to Lucene until it binds this.  (A range, an in-set or an exists clause beside a text
  * query, a kNN query or any other route is a resident mask built from the column: nrtgpu_segment_set_mask_from_values.)
@@ -1224,6 +1336,15 @@ int  nrtgpu_search_docset_sorted_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const*
  * with the reason in nrtgpu_last_error.  No device work. */
 int  nrtgpu_docset_sorted_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* d,
                                     const nrtgpu_field_sort* s);
+/* The sorted doc-set search over a 64-BIT sort column (nrtgpu_search_sorted64_batch: the packed key, the fit rule, the predicate's
+ * doc bases): nrtgpu_search_docset_sorted_batch's semantics, word for word.  The doc set's own
+ * `ranges` stay 32-bit clauses over 32-bit columns (a range over a 64-bit column is a mask built by
+ * nrtgpu_segment_set_mask_from_values64, named as a filter).  Runs under both context flags, as its 32-bit form does. */
+int  nrtgpu_search_docset_sorted64_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                         const nrtgpu_docset_query* docsets, const nrtgpu_field_sort64* sorts, int32_t n_queries,
+                                         nrtgpu_fielddocs64* out);
+int  nrtgpu_docset_sorted64_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs,
+                                      const nrtgpu_docset_query* d, const nrtgpu_field_sort64* s);
 /* n_queries count maps of doc sets over the same leaves in one device pass; terms[i] names the column and the bound of docsets[i] */
 int  nrtgpu_count_docset_terms_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
                                      const nrtgpu_docset_query* docsets, const nrtgpu_terms_count* terms, int32_t n_queries,

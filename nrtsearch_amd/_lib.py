@@ -37,6 +37,8 @@ NRTGPU_GROUPS_MAX_OF_SUM = 1
 NRTGPU_MAX_KNN_LISTS = 8
 NRTGPU_DOCVALUES_INT32 = 0
 NRTGPU_DOCVALUES_FLOAT32 = 1
+NRTGPU_DOCVALUES_INT64 = 2
+NRTGPU_DOCVALUES_FLOAT64 = 3
 NRTGPU_MAX_TERM_BUCKETS = 65536
 NRTGPU_MAX_RANGES = 4
 NRTGPU_CLAUSE_RANGE = 0
@@ -73,6 +75,8 @@ ABI_SYMBOLS = [
     "nrtgpu_count_docset_terms_supported", "nrtgpu_range_accepts",
     "nrtgpu_segment_add_doc_values_multi",
     "nrtgpu_segment_set_mask_from_values", "nrtgpu_segment_get_mask",
+    "nrtgpu_segment_add_doc_values64", "nrtgpu_sort_key64", "nrtgpu_search_sorted64_batch", "nrtgpu_sorted64_supported",
+    "nrtgpu_search_docset_sorted64_batch", "nrtgpu_docset_sorted64_supported", "nrtgpu_segment_set_mask_from_values64", "nrtgpu_range_accepts64",
 ]
 # what include/nrtgpu_dev.h adds: test hooks and measurement helpers of the development library (libnrtgpu_dev.so) only
 DEV_SYMBOLS = [
@@ -144,6 +148,21 @@ class FieldDocs(C.Structure):   # nrtgpu_fielddocs: nrtgpu_topdocs with the hits
     _fields_ = [("n_hits", C.c_int32), ("capacity", C.c_int32), ("docs", C.POINTER(C.c_int32)),
                 ("value_bits", C.POINTER(C.c_uint32)), ("total_hits", C.c_int64),
                 ("total_hits_is_lower_bound", C.c_int32)]
+
+
+class FieldSort64(C.Structure):   # nrtgpu_field_sort64
+    _fields_ = [("field_id", C.c_int32), ("reverse", C.c_int32), ("missing_bits", C.c_uint64), ("has_after", C.c_int32),
+                ("after_doc", C.c_int32), ("after_bits", C.c_uint64)]
+
+
+class FieldDocs64(C.Structure):   # nrtgpu_fielddocs64
+    _fields_ = [("n_hits", C.c_int32), ("capacity", C.c_int32), ("docs", C.POINTER(C.c_int32)),
+                ("value_bits", C.POINTER(C.c_uint64)), ("total_hits", C.c_int64),
+                ("total_hits_is_lower_bound", C.c_int32)]
+
+
+class ValueClause64(C.Structure):   # nrtgpu_value_clause64
+    _fields_ = [("kind", C.c_int32), ("field_id", C.c_int32), ("lower_bits", C.c_uint64), ("upper_bits", C.c_uint64), ("reserved", C.c_int64)]
 
 
 class TermsCount(C.Structure):   # nrtgpu_terms_count
@@ -294,6 +313,15 @@ def _open(path: str) -> C.CDLL:
     L.nrtgpu_count_docset_terms_batch.argtypes = [vp, vp, vp, i32, C.POINTER(DocsetQuery), C.POINTER(TermsCount), i32, C.POINTER(TermCounts)]
     L.nrtgpu_count_docset_terms_supported.argtypes = [vp, vp, i32, C.POINTER(DocsetQuery), C.POINTER(TermsCount)]
     L.nrtgpu_range_accepts.argtypes = [i32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+    u64 = C.c_uint64
+    L.nrtgpu_segment_add_doc_values64.argtypes = [vp, i32, i32, i32, vp, vp]
+    L.nrtgpu_sort_key64.argtypes = [i32, i32, u64, u64, u64, i32, i32, u64, i32, vp]
+    L.nrtgpu_search_sorted64_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(FieldSort64), i32, C.POINTER(FieldDocs64)]
+    L.nrtgpu_sorted64_supported.argtypes = [vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(FieldSort64)]
+    L.nrtgpu_search_docset_sorted64_batch.argtypes = [vp, vp, vp, i32, C.POINTER(DocsetQuery), C.POINTER(FieldSort64), i32, C.POINTER(FieldDocs64)]
+    L.nrtgpu_docset_sorted64_supported.argtypes = [vp, vp, i32, C.POINTER(DocsetQuery), C.POINTER(FieldSort64)]
+    L.nrtgpu_segment_set_mask_from_values64.argtypes = [vp, i32, C.POINTER(ValueClause64), i32, vp]
+    L.nrtgpu_range_accepts64.argtypes = [i32, u64, u64, u64, vp]
     L.nrtgpu_rescore_vectors.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, f32, vp, vp, i32, C.c_double, C.c_double, i32,
                                          C.POINTER(TopDocs)]
     L.nrtgpu_search_hybrid_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), i32, i32, i32, vp, i32, f32,

@@ -151,6 +151,15 @@ def _value_bits(kind: str, value) -> int:
     return int(np.array([value], dtype=DOC_VALUE_KINDS[kind][1]).view(np.uint32)[0])
 
 
+# 64-bit columns (GpuSegment.add_doc_values64): LONG / DATE_TIME (epoch millis) and DOUBLE doc values
+DOC_VALUE_KINDS64 = {"long": (_lib.NRTGPU_DOCVALUES_INT64, np.dtype(np.int64)), "double": (_lib.NRTGPU_DOCVALUES_FLOAT64, np.dtype(np.float64))}
+
+
+def _value_bits64(kind: str, value) -> int:
+    """The 64 bits of a doc value of the kind (an int64 / a float64)."""
+    return int(np.array([value], dtype=DOC_VALUE_KINDS64[kind][1]).view(np.uint64)[0])
+
+
 @dataclasses.dataclass(frozen=True)
 class SortField:
     """SortField(field, Type.INT / Type.FLOAT, reverse) over a doc value column (GpuSegment.add_doc_values), with
@@ -606,6 +615,22 @@ class GpuSegment:
         _lib.check(_lib.load().nrtgpu_segment_add_doc_values(self._h, int(field), DOC_VALUE_KINDS[kind][0], values.shape[0], dp,
                                                              values.ctypes.data if values.shape[0] else None))
 
+    def add_doc_values64(self, field: int, kind: str, values: np.ndarray, docs: Optional[np.ndarray] = None) -> None:
+        """A per-doc column of 64-bit values (nrtgpu_segment_add_doc_values64): kind "long" (int64: LONG, DATE_TIME as epoch
+        millis) or "double" (float64); add_doc_values' contract otherwise.  No silent cast: the array's dtype must be the kind's,
+        or uint64 for the kind's raw bits."""
+        values = np.ascontiguousarray(values).reshape(-1)
+        if values.dtype not in (DOC_VALUE_KINDS64[kind][1], np.dtype(np.uint64)):
+            raise TypeError(f"doc values of kind {kind!r} must be {DOC_VALUE_KINDS64[kind][1]} (or uint64 bits), got {values.dtype}")
+        dp = None
+        if docs is not None:
+            docs = np.ascontiguousarray(docs, dtype=np.int32).reshape(-1)
+            if docs.shape[0] != values.shape[0]:
+                raise ValueError(f"{docs.shape[0]} docs, {values.shape[0]} values")
+            dp = docs.ctypes.data
+        _lib.check(_lib.load().nrtgpu_segment_add_doc_values64(self._h, int(field), DOC_VALUE_KINDS64[kind][0], values.shape[0], dp,
+                                                               values.ctypes.data if values.shape[0] else None))
+
     def add_doc_values_multi(self, field: int, kind: str, values: np.ndarray, value_docs: np.ndarray) -> None:
         """A multi-valued value column of the field (nrtgpu_segment_add_doc_values_multi): values[i] belongs to leaf doc
         value_docs[i] (non-decreasing; a doc listed c times has c values, duplicates count each; a doc not listed has none).
@@ -660,6 +685,21 @@ class GpuSegment:
         count = C.c_int64(0)
         _lib.check(_lib.load().nrtgpu_segment_set_mask_from_values(self._h, int(mask_id), vc, len(clauses), C.byref(count)))
         del keep
+        return int(count.value)
+
+    def set_mask_from_values64(self, mask_id: int, clauses: Sequence["ValueClause64"]) -> int:
+        """set_mask_from_values over 64-bit columns (nrtgpu_segment_set_mask_from_values64): range and exists clauses -> the number
+        of docs of the registered mask."""
+        n = len(clauses)
+        if not 1 <= n <= _lib.NRTGPU_MAX_RANGES:
+            raise ValueError(f"{n} clauses: 1..{_lib.NRTGPU_MAX_RANGES}")
+        vc = (_lib.ValueClause64 * n)()
+        for i, c in enumerate(clauses):
+            if c.clause not in ("range", "exists"):
+                raise UnsupportedQuery(f"a 64-bit value clause {c.clause!r}")
+            vc[i] = _lib.ValueClause64(_VALUE_CLAUSE_KINDS[c.clause], int(c.field), int(c.lower_bits), int(c.upper_bits), 0)
+        count = C.c_int64(0)
+        _lib.check(_lib.load().nrtgpu_segment_set_mask_from_values64(self._h, int(mask_id), vc, n, C.byref(count)))
         return int(count.value)
 
     def get_mask(self, mask_id: int) -> np.ndarray:
@@ -1710,6 +1750,152 @@ def range_accepts(kind: str, lower_bits: int, upper_bits: int, value_bits: int) 
     out = C.c_int32(0)
     _lib.check(_lib.load().nrtgpu_range_accepts(DOC_VALUE_KINDS[kind][0], C.c_uint32(int(lower_bits)), C.c_uint32(int(upper_bits)),
                                                 C.c_uint32(int(value_bits)), C.byref(out)))
+    return bool(out.value)
+
+
+# ---- 64-bit columns: sort by a LONG / DATE_TIME / DOUBLE field, masks from such columns ----------------------------------------
+@dataclasses.dataclass(frozen=True)
+class SortField64:
+    """SortField(field, Type.LONG / Type.DOUBLE, reverse) over a 64-bit doc value column (GpuSegment.add_doc_values64); `missing`
+    as in SortField (the reference passes Long.MIN_VALUE / MAX_VALUE or -+inf)."""
+
+    field: int
+    kind: str = "long"
+    reverse: bool = False
+    missing: Union[int, float] = 0
+
+
+@dataclasses.dataclass
+class TopFieldDocs64:
+    docs: np.ndarray            # int32 global docids, in the sort's order
+    values: np.ndarray          # int64 / float64: the value each hit sorted as (the missing value for a doc without one)
+    total_hits: int
+    relation_gte: bool
+
+    @property
+    def value_bits(self) -> np.ndarray:
+        return self.values.view(np.uint64)
+
+
+@dataclasses.dataclass(frozen=True)
+class ValueClause64:
+    """One clause of a mask built from a 64-bit column (GpuSegment.set_mask_from_values64; nrtgpu_value_clause64): range_ (lower
+    <= value <= upper, inclusive, Long.compare / the order of doubleToSortableLong) or exists.  Use the constructors."""
+
+    clause: str                          # "range" | "exists"
+    field: int
+    kind: str = "long"
+    lower_bits: int = 0
+    upper_bits: int = 0
+
+    @classmethod
+    def range_(cls, field: int, kind: str, lower, upper) -> "ValueClause64":
+        if kind not in DOC_VALUE_KINDS64:
+            raise UnsupportedQuery(f"a 64-bit range clause of kind {kind!r}")
+        return cls("range", int(field), kind, _value_bits64(kind, lower), _value_bits64(kind, upper))
+
+    @classmethod
+    def exists(cls, field: int) -> "ValueClause64":
+        return cls("exists", int(field))
+
+
+def _field_sorts64(sorts: Sequence[SortField64], afters, n: int):
+    if len(sorts) != n or (afters is not None and len(afters) != n):
+        raise ValueError(f"{len(sorts)} sorts / {None if afters is None else len(afters)} afters for {n} queries")
+    fs = (_lib.FieldSort64 * n)()
+    for qi, sort in enumerate(sorts):
+        if sort.kind not in DOC_VALUE_KINDS64:
+            raise UnsupportedQuery(f"a 64-bit sort of kind {sort.kind!r}")
+        after = afters[qi] if afters is not None else None
+        fs[qi] = _lib.FieldSort64(int(sort.field), int(bool(sort.reverse)), _value_bits64(sort.kind, sort.missing), int(after is not None),
+                                  int(after.doc) if after is not None else 0, _value_bits64(sort.kind, after.value) if after is not None else 0)
+    return fs
+
+
+class _Outputs64:
+    """The nrtgpu_fielddocs64 of a call: rows of an int32 and a uint64 array."""
+
+    def __init__(self, managers):
+        caps = [max(int(mgr.num_hits), 1) for mgr in managers]
+        n, width = len(caps), max(caps, default=1)
+        self.outs = (_lib.FieldDocs64 * n)()
+        self.docs = np.zeros((n, width), dtype=np.int32)
+        self.bits = np.zeros((n, width), dtype=np.uint64)
+        for qi in range(n):
+            self.outs[qi].capacity = caps[qi]
+            self.outs[qi].docs = C.cast(self.docs.ctypes.data + qi * width * 4, C.POINTER(C.c_int32))
+            self.outs[qi].value_bits = C.cast(self.bits.ctypes.data + qi * width * 8, C.POINTER(C.c_uint64))
+
+    def lists(self, sorts) -> List[TopFieldDocs64]:
+        return [TopFieldDocs64(self.docs[qi, : o.n_hits].copy(), self.bits[qi, : o.n_hits].copy().view(DOC_VALUE_KINDS64[sort.kind][1]), int(o.total_hits),
+                               bool(o.total_hits_is_lower_bound)) for qi, (o, sort) in enumerate(zip(self.outs, sorts))]
+
+
+def _marshal_sorted64(searcher: "GpuIndexSearcher", queries: Sequence[Query], managers: Sequence[TopScoreDocCollectorManager],
+                      sorts: Sequence[SortField64], afters):
+    """_marshal_sorted's queries (a BooleanQuery of MUST clauses only goes down as MUST clauses) beside nrtgpu_field_sort64 records."""
+    fs = _field_sorts64(sorts, afters, len(queries))
+    m, _ = _marshal_sorted(searcher, queries, managers, [SortField(int(s.field)) for s in sorts], None)
+    m.keep.append(fs)
+    return m, fs
+
+
+def search_sorted64_batch(searcher: "GpuIndexSearcher", queries: Sequence[Query], managers: Sequence[TopScoreDocCollectorManager],
+                          sorts: Sequence[SortField64], afters: Optional[Sequence[Optional[FieldDoc]]] = None) -> List[TopFieldDocs64]:
+    """Sorted searches over 64-bit columns (nrtgpu_search_sorted64_batch): search_sorted_batch's results with int64 / float64
+    values ("newest first" over epoch millis)."""
+    m, fs = _marshal_sorted64(searcher, queries, managers, sorts, afters)
+    n = len(m.queries)
+    h = _Outputs64(managers)
+    _lib.check(_lib.load().nrtgpu_search_sorted64_batch(searcher.ctx._h, searcher._segs, searcher._bases, len(searcher.leaves), m.queries, fs, n, h.outs))
+    return h.lists(sorts)
+
+
+def sorted64_supported(searcher: "GpuIndexSearcher", query: Query, manager: TopScoreDocCollectorManager, sort: SortField64,
+                       after: Optional[FieldDoc] = None) -> bool:
+    """The eligibility predicate alone (nrtgpu_sorted64_supported)."""
+    m, fs = _marshal_sorted64(searcher, [query], [manager], [sort], [after])
+    return _supported(_lib.load().nrtgpu_sorted64_supported(searcher.ctx._h, searcher._segs, len(searcher.leaves), m.queries, fs))
+
+
+def search_docset_sorted64_batch(searcher: "GpuIndexSearcher", docsets: Sequence[DocSetQuery], managers: Sequence[TopScoreDocCollectorManager],
+                                 sorts: Sequence[SortField64], afters: Optional[Sequence[Optional[FieldDoc]]] = None) -> List[TopFieldDocs64]:
+    """Sorted doc-set searches over 64-bit columns (nrtgpu_search_docset_sorted64_batch)."""
+    ds, keep = _marshal_docsets(docsets, managers)
+    n = len(docsets)
+    fs = _field_sorts64(sorts, afters, n)
+    h = _Outputs64(managers)
+    _lib.check(_lib.load().nrtgpu_search_docset_sorted64_batch(searcher.ctx._h, searcher._segs, searcher._bases, len(searcher.leaves), ds, fs, n, h.outs))
+    del keep
+    return h.lists(sorts)
+
+
+def docset_sorted64_supported(searcher: "GpuIndexSearcher", docset: DocSetQuery, manager: TopScoreDocCollectorManager, sort: SortField64,
+                              after: Optional[FieldDoc] = None) -> bool:
+    """The eligibility predicate alone (nrtgpu_docset_sorted64_supported)."""
+    ds, keep = _marshal_docsets([docset], [manager])
+    fs = _field_sorts64([sort], [after], 1)
+    rc = _lib.load().nrtgpu_docset_sorted64_supported(searcher.ctx._h, searcher._segs, len(searcher.leaves), ds, fs)
+    del keep
+    return _supported(rc)
+
+
+def sort_key64(kind: str, reverse: bool, lo_bits: int, hi_bits: int, missing_bits: int, doc_bits: int, has_value: bool, value_bits: int,
+               global_doc: int) -> int:
+    """The packed key of one doc (nrtgpu_sort_key64: the function the kernels compile).  No device.  NrtGpuError with code
+    NRTGPU_ERR_UNSUPPORTED when the window does not fit beside doc_bits docid bits."""
+    out = C.c_uint64(0)
+    _lib.check(_lib.load().nrtgpu_sort_key64(DOC_VALUE_KINDS64[kind][0], int(bool(reverse)), C.c_uint64(int(lo_bits)), C.c_uint64(int(hi_bits)),
+                                             C.c_uint64(int(missing_bits)), int(doc_bits), int(bool(has_value)), C.c_uint64(int(value_bits)),
+                                             int(global_doc), C.byref(out)))
+    return int(out.value)
+
+
+def range_accepts64(kind: str, lower_bits: int, upper_bits: int, value_bits: int) -> bool:
+    """Whether a 64-bit range clause keeps a value (nrtgpu_range_accepts64: the function the kernel compiles).  No device."""
+    out = C.c_int32(0)
+    _lib.check(_lib.load().nrtgpu_range_accepts64(DOC_VALUE_KINDS64[kind][0], C.c_uint64(int(lower_bits)), C.c_uint64(int(upper_bits)),
+                                                  C.c_uint64(int(value_bits)), C.byref(out)))
     return bool(out.value)
 
 

@@ -91,6 +91,8 @@ int docset_finish(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_do
   for (int r = 0; r < d.n_ranges; ++r) {
     const int kind = call->range_kinds[(size_t)qi * (size_t)kMaxRanges + (size_t)r];
     if (kind < 0) return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: no leaf of the call holds doc values of field %d (range clause %d)", qi, d.ranges[r].field_id, r);
+    if (kind >= kDocValuesInt64)
+      return doc_values_wide(qi, d.ranges[r].field_id, "a range over it is a mask built by nrtgpu_segment_set_mask_from_values64, named as a filter");
     rq.lo_code[r] = doc_value_code(kind, d.ranges[r].lower_bits);
     rq.hi_code[r] = doc_value_code(kind, d.ranges[r].upper_bits);
   }
@@ -130,10 +132,39 @@ int check_sorted(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_doc
   for (int qi = 0; qi < n_queries; ++qi) {
     const int kind = (*kinds)[(size_t)qi];
     if (kind < 0) return no_column(qi, sorts[qi].field_id);
+    if (kind >= kDocValuesInt64) return doc_values_wide(qi, sorts[qi].field_id, "sort by it with nrtgpu_search_docset_sorted64_batch");
     if (sort_multi[(size_t)qi] != 0) return field_sort_multi(qi, sorts[qi].field_id);
     if (int rc = docset_finish(segs, n_segs, docsets[qi], qi, call)) return rc;
     DSortQuery r{};
     field_sort_record(sorts[qi], kind, &r);
+    records->push_back(r);
+  }
+  return NRTGPU_OK;
+}
+
+// check_sorted for a sort by a 64-bit column (fieldsort64.cpp's records; in_order: the predicate's doc bases).
+int check_sorted64(const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, bool in_order, const nrtgpu_docset_query* docsets,
+                   const nrtgpu_field_sort64* sorts, int32_t n_queries, DocsetCall* call, std::vector<DSort64Query>* records, std::vector<int>* kinds) {
+  std::vector<char> sort_multi;
+  for (int qi = 0; qi < n_queries; ++qi) {
+    if (int rc = docset_begin(segs, n_segs, docsets[qi], qi, call)) return rc;
+    if (int rc = field_sort64_check(sorts[qi], qi)) return rc;
+    int kind = -1;
+    bool multi = false;
+    if (int rc = doc_values_kind(segs, n_segs, sorts[qi].field_id, qi, &kind, &multi)) return rc;
+    kinds->push_back(kind);
+    sort_multi.push_back(multi ? 1 : 0);
+  }
+  uint32_t db = 1;
+  for (int qi = 0; qi < n_queries; ++qi) {
+    const int kind = (*kinds)[(size_t)qi];
+    if (kind < 0) return no_column(qi, sorts[qi].field_id);
+    if (kind < kDocValuesInt64) return field_sort64_narrow(qi, sorts[qi].field_id, sort_multi[(size_t)qi] != 0, "nrtgpu_search_docset_sorted_batch");
+    if (int rc = docset_finish(segs, n_segs, docsets[qi], qi, call)) return rc;
+    if (qi == 0)
+      if (int rc = sort64_doc_bits(segs, doc_bases, n_segs, in_order, &db)) return rc;
+    DSort64Query r{};
+    if (int rc = field_sort64_record(segs, n_segs, sorts[qi], kind, db, qi, &r)) return rc;
     records->push_back(r);
   }
   return NRTGPU_OK;
@@ -155,6 +186,7 @@ int check_terms(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docs
   }
   for (int qi = 0; qi < n_queries; ++qi) {
     if ((*kinds)[(size_t)qi] < 0) return no_column(qi, terms[qi].field_id);
+    if ((*kinds)[(size_t)qi] >= kDocValuesInt64) return doc_values_wide(qi, terms[qi].field_id, kTermsCountWide);
     if (int rc = docset_finish(segs, n_segs, docsets[qi], qi, call)) return rc;
   }
   work->layout(n_queries, slots, cap);
@@ -209,6 +241,57 @@ extern "C" int nrtgpu_search_docset_sorted_batch(nrtgpu_ctx* ctx, const nrtgpu_s
     const uint32_t reverse = records[(size_t)qi].reverse;
     for (int32_t i = 0; v && i < out[qi].n_hits; ++i) v[i] = doc_value_bits(kinds[(size_t)qi], reverse != 0u ? v[i] : ~v[i]);
   }
+  return NRTGPU_OK;
+}
+
+extern "C" int nrtgpu_docset_sorted64_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* d,
+                                                const nrtgpu_field_sort64* s) {
+  if (int rc = final_score_enter(ctx, segs, n_segs, !d || !s, nullptr)) return rc;
+  SegReadLocks content(segs, n_segs);
+  DocsetCall call;
+  std::vector<DSort64Query> records;
+  std::vector<int> kinds;
+  if (int rc = check_sorted64(segs, nullptr, n_segs, true, d, s, 1, &call, &records, &kinds)) return rc;
+  HostPlan hp;
+  return docset_plan(ctx, segs, nullptr, n_segs, call.masks.data(), 1, hp);
+}
+
+extern "C" int nrtgpu_search_docset_sorted64_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                                   const nrtgpu_docset_query* docsets, const nrtgpu_field_sort64* sorts, int32_t n_queries,
+                                                   nrtgpu_fielddocs64* out) {
+  if (int rc = final_score_enter(ctx, segs, n_segs, !docsets || !sorts || !out, &n_queries)) return rc;
+  const double t0 = now_ms();
+  SegReadLocks content(segs, n_segs);   // until this call's kernels have finished
+  DocsetCall call;
+  std::vector<DSort64Query> records;
+  std::vector<int> kinds;
+  if (int rc = check_sorted64(segs, doc_bases, n_segs, false, docsets, sorts, n_queries, &call, &records, &kinds)) return rc;
+  HostPlan hp;
+  if (int rc = docset_plan(ctx, segs, doc_bases, n_segs, call.masks.data(), n_queries, hp)) return rc;
+  std::vector<DSortPart> unused, rparts;   // (the range clauses' columns are 32-bit ones: docset_parts' walk; the sort's are read below)
+  std::vector<int32_t> no_field((size_t)n_queries, -1);
+  docset_parts(segs, docsets, no_field.data(), hp, &unused, &rparts);
+  std::vector<DSort64Part> sparts(hp.parts.size(), DSort64Part{nullptr, nullptr});
+  for (const DItem& it : hp.items)
+    for (uint32_t pi = 0; pi < it.n_parts; ++pi) {
+      const size_t at = (size_t)it.part_begin + pi;
+      sparts[at] = doc_values_column64(segs[hp.part_leaf[at]], sorts[it.query].field_id);
+    }
+  const PlanBytes extras[4] = {{records.data(), records.size() * sizeof(DSort64Query)},
+                               {call.ranges.data(), call.ranges.size() * sizeof(DRangeQuery)},
+                               {sparts.data(), sparts.size() * sizeof(DSort64Part)},
+                               {rparts.data(), rparts.size() * sizeof(DSortPart)}};
+  const FinalScoreLaunch single = [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
+    launch_docset_sort64(st, a, (const DSort64Query*)d_extra[0], (const DRangeQuery*)d_extra[1], (const DSort64Part*)d_extra[2], (const DSortPart*)d_extra[3]);
+  };
+  const FinalScoreLaunch multi = [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
+    launch_docset_sort64_multi(st, a, (const DSort64Query*)d_extra[0], (const DRangeQuery*)d_extra[1], (const DSort64Part*)d_extra[2], (const DSortPart*)d_extra[3]);
+  };
+  std::vector<int32_t> ks((size_t)n_queries);
+  for (int qi = 0; qi < n_queries; ++qi) ks[(size_t)qi] = docsets[qi].k;
+  Sort64Pages pages(ks.data(), out, n_queries);
+  if (int rc = final_score_run(ctx, hp, call.masks.data(), n_queries, pages.pages.data(), t0, extras, 4, call.any_multi ? multi : single)) return rc;
+  pages.decode(records, kinds, sorts, out);
   return NRTGPU_OK;
 }
 

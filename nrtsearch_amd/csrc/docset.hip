@@ -6,6 +6,7 @@
 //   docset_sort_kernel          per sub-tile the accept words, the range clauses, then keys for the accepted docs and the item's top-k
 //   docset_terms_count_kernel   the same hit set; every hit with a value adds 1 in the count table under the value's code
 //   docset_sort_multi_kernel, docset_terms_count_multi_kernel   the two for calls that name a MULTI-VALUED column (at the end)
+//   docset_sort64_kernel<MULTI> docset_sort_kernel / docset_sort_multi_kernel over a 64-BIT sort column (plan.h: sort_key64; behind them)
 //
 // The decomposition is the final-score skeleton's (finalscore.hiph): one workgroup of kScanWaves waves per item, a wave takes
 // kTileDocs-doc sub-tiles of the item's parts (final_total_tiles / final_tile), hits per slice through final_count_slice, the
@@ -549,6 +550,145 @@ void docset_terms_count_multi_kernel(const DItem* __restrict__ items, const DPar
     }
     item_hits[blockIdx.x] = n;
   }
+}
+
+// ---- a sort by a 64-BIT column (plan.h: DSort64Query / DSort64Part, sort_key64; nrtgpu_search_docset_sorted64_batch) --------------
+// docset_column over a column of 64-bit codes: the lane's 8-byte codes of the words in `words` and its `has` bits.
+__device__ __forceinline__ bool docset_column64(const DSort64Part* sp, uint32_t base, uint32_t word0, uint32_t lane, uint32_t words,
+                                                uint64_t (&cv)[kFinalSlots], uint32_t& has_bits) {
+  const NRT_GLOBAL uint64_t* const col = (const NRT_GLOBAL uint64_t*)sp->code64;
+  const NRT_GLOBAL uint64_t* const has = (const NRT_GLOBAL uint64_t*)sp->has;
+  if (col == nullptr) {   // uniform
+#pragma unroll
+    for (int j = 0; j < kFinalSlots; ++j) cv[j] = 0ull;
+    has_bits = 0u;
+    return false;
+  }
+  uint64_t hw = 0ull;
+  if (has != nullptr && lane < (uint32_t)kFinalSlots) hw = has[word0 + lane];
+#pragma unroll
+  for (int j = 0; j < kFinalSlots; ++j) {
+    cv[j] = 0ull;
+    if (((words >> j) & 1u) != 0u) cv[j] = col[base + lane + 64u * (uint32_t)j];   // uniform: a word without an accepted doc costs no load
+  }
+  has_bits = has != nullptr ? docset_lane_bits((uint32_t)hw, (uint32_t)(hw >> 32), lane) : (1u << kFinalSlots) - 1u;
+  return true;
+}
+
+// docset_sort_kernel (MULTI: docset_sort_multi_kernel -- the doc set's 32-bit range clauses may name multi-valued columns) with
+// the sort's column read as 64-bit codes, the packed key and the cursor test on (code, doc).  Everything else is that kernel's.
+template <bool MULTI>
+__global__ __launch_bounds__(kScanThreads, kScanWaves / 4)
+void docset_sort64_kernel(const DItem* __restrict__ items, const DPart* __restrict__ parts, const DQuery* __restrict__ queries,
+                          const DSort64Query* __restrict__ squeries, const DRangeQuery* __restrict__ rqueries, const DSort64Part* __restrict__ sparts,
+                          const DSortPart* __restrict__ rparts, unsigned long long* __restrict__ theta_g, uint32_t* __restrict__ slice_sum,
+                          uint64_t* __restrict__ item_keys, uint32_t* __restrict__ item_counts, uint64_t* __restrict__ item_hits, uint32_t k_stride) {
+  __shared__ DocsetSortSmem s;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)), lane = tid & 63u;
+  const DItem* const item = items + blockIdx.x;
+  const uint32_t query = item->query, part_begin = item->part_begin, n_parts = item->n_parts;
+  const DQuery* const q = queries + query;
+  const uint32_t k = min(q->k, (uint32_t)kMaxK);
+  const DSort64Query* const sq = squeries + query;
+  const DRangeQuery* const rq = rqueries + query;
+  const uint64_t lo = sq->lo, span = sq->span, missing_code = sq->missing_code, after_code = sq->after_code;
+  const uint32_t reverse = sq->reverse, after_doc = sq->after_doc;
+  const uint32_t db = min(max(sq->db, 1u), 31u);
+  const bool has_after = sq->has_after != 0u;
+  const bool multi_item = q->n_items > 1;
+  unsigned long long* const my_theta_g = theta_g + query;
+
+  if (tid < (uint32_t)kSliceSlots) s.slot_hits[tid] = s.slot_slice[tid] = 0u;
+  __syncthreads();
+
+  const uint32_t total_tiles = final_total_tiles(parts, part_begin, n_parts);
+  uint64_t theta = 0;   // uniform: the k-th best key known (this item's compactions, the query's other items)
+  uint32_t cnt = 0;     // uniform: keys in s.cand
+  uint32_t pi = 0;      // the part of the wave's sub-tile (indices only grow)
+  uint32_t par = 0;
+
+  for (uint32_t g0 = 0; g0 < total_tiles; g0 += (uint32_t)kScanWaves, par ^= 1u) {
+    if (multi_item) {
+      const uint64_t t = __hip_atomic_load(my_theta_g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      theta = t > theta ? t : theta;
+    }
+    const uint32_t g = g0 + wave;
+    uint32_t n_cand = 0;   // wave-uniform
+    uint64_t key[kFinalSlots];
+#pragma unroll
+    for (int j = 0; j < kFinalSlots; ++j) key[j] = 0ull;
+    if (g < total_tiles) {
+      const FinalTile tl = final_tile(parts, part_begin, n_parts, g, pi);
+      const uint32_t base = tl.base, gdoc0 = tl.gdoc0;
+      uint32_t words, hits;
+      const DSortPart* const my_rparts = rparts + (size_t)(part_begin + pi) * (size_t)kMaxRanges;
+      const uint32_t m = MULTI ? docset_hit_set_multi(tl.part, rq, my_rparts, base, tl.tile_len, lane, words, hits)
+                               : docset_hit_set(tl.part, rq, my_rparts, base, tl.tile_len, lane, words, hits);
+      if (words != 0u) {   // uniform
+        uint64_t cv[kFinalSlots];
+        uint32_t has_bits;
+        docset_column64(sparts + part_begin + pi, base, base >> 6, lane, words, cv, has_bits);   // (a leaf without the column: every doc sorts as the missing value)
+#pragma unroll
+        for (int j = 0; j < kFinalSlots; ++j) {
+          // Every lane computes its key and ONE select keeps or drops it (a doc outside the hit set reads code 0; hits of earlier
+          // pages still count: `hits`).  Written as docset_sort_kernel writes it -- a store under two nested conditions -- the built
+          // kernel kept no key at all behind a cursor and held 143 VGPRs; as a select it holds 95.
+          const uint64_t code = ((has_bits >> j) & 1u) != 0u ? cv[j] : missing_code;
+          const uint32_t gdoc = gdoc0 + lane + 64u * (uint32_t)j;
+          const uint64_t doc_key = sort_key64(reverse, lo, span, db, code, gdoc);
+          const bool behind = !has_after || sort64_behind(reverse, code, gdoc, after_code, after_doc);
+          key[j] = (((m >> j) & 1u) != 0u && behind && doc_key > theta) ? doc_key : 0ull;
+          n_cand += (uint32_t)__popcll(__ballot(key[j] != 0ull));
+        }
+        final_count_slice(s, tl.part, lane, hits);
+      }
+    }
+    if (lane == 0) s.wcount[par][wave] = n_cand;
+    __syncthreads();
+
+    // ---- the round's candidates into the shared buffer (docset_sort_kernel's meeting)
+    uint32_t tot = 0, before = 0;
+#pragma unroll
+    for (uint32_t w2 = 0; w2 < (uint32_t)kScanWaves; ++w2) {
+      const uint32_t c = s.wcount[par][w2];
+      tot += c;
+      before += w2 < wave ? c : 0u;
+    }
+    if (cnt + tot <= (uint32_t)kFsCandCap) {   // uniform
+      docset_push_candidates(s, key, lane, cnt + before);
+      cnt += tot;
+    } else {
+      for (uint32_t w2 = 0; w2 < (uint32_t)kScanWaves; ++w2) {
+        const uint32_t c = s.wcount[par][w2];
+        if (cnt + c > (uint32_t)kFsCandCap) {   // uniform; cnt > k here (kFsCandCap >= kMaxK + kTileDocs)
+          __syncthreads();   // the keys appended so far are in place
+          uint64_t thr = 0;
+          cnt = topk_compact<kScanThreads, kFsCandCap>(s.cand, cnt, k, &s.sc, &thr);
+          if (thr > theta) theta = thr;
+          if (tid == 0) atomicMax(my_theta_g, (unsigned long long)thr);
+        }
+        if (wave == w2) docset_push_candidates(s, key, lane, cnt);
+        cnt += c;
+      }
+    }
+  }
+
+  final_epilogue(s, cnt, k, q, tid, slice_sum, item_keys, item_counts, item_hits, k_stride);
+}
+
+void launch_docset_sort64(hipStream_t stream, const FinalScoreArgs& a, const DSort64Query* squeries, const DRangeQuery* rqueries, const DSort64Part* sparts,
+                          const DSortPart* rparts) {
+  if (a.n_items == 0) return;
+  hipLaunchKernelGGL(docset_sort64_kernel<false>, dim3(a.n_items), dim3(kScanThreads), 0, stream, a.items, a.parts, a.queries, squeries, rqueries, sparts,
+                     rparts, a.theta_g, a.slice_sum, a.item_keys, a.item_counts, a.item_hits, a.k_stride);
+}
+
+void launch_docset_sort64_multi(hipStream_t stream, const FinalScoreArgs& a, const DSort64Query* squeries, const DRangeQuery* rqueries,
+                                const DSort64Part* sparts, const DSortPart* rparts) {
+  if (a.n_items == 0) return;
+  hipLaunchKernelGGL(docset_sort64_kernel<true>, dim3(a.n_items), dim3(kScanThreads), 0, stream, a.items, a.parts, a.queries, squeries, rqueries, sparts,
+                     rparts, a.theta_g, a.slice_sum, a.item_keys, a.item_counts, a.item_hits, a.k_stride);
 }
 
 // terms_compact_kernel's launch (termscount.hip): the occupied slots of every query's table packed into `out`

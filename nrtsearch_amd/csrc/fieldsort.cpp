@@ -54,6 +54,10 @@ DSortPart doc_values_column(const nrtgpu_seg* seg, int32_t field_id) {
   return f.d_dv_start != nullptr ? DSortPart{f.d_dv_code, (const uint64_t*)f.d_dv_start} : DSortPart{f.d_dv_code, f.d_dv_has};
 }
 
+int doc_values_wide(int qi, int32_t field_id, const char* instead) {
+  return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: the doc values of field %d are a 64-bit column: %s", qi, field_id, instead);
+}
+
 // What the sorted routes refuse of a sort over a multi-valued column (beside "resident on no leaf": the column names no ONE value).
 int field_sort_multi(int qi, int32_t field_id) {
   return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: the doc values of field %d are multi-valued: a sort names one value per doc (upload the selector's pick, "
@@ -112,10 +116,9 @@ void field_sort_record(const nrtgpu_field_sort& s, int kind, DSortQuery* r) {
   r->after_key = s.has_after ? sort_key(r->reverse, doc_value_code(kind, s.after_bits), (uint32_t)s.after_doc) : ~0ull;
 }
 
-// The column of every part's leaf (field_ids: per query).  A part names its (query, leaf) pair by its first DTerm (HostPlan.qs_begin).
-int doc_values_parts(const nrtgpu_seg* const* segs, int32_t n_segs, const int32_t* field_ids, const HostPlan& hp, const char* route,
-                     std::vector<DSortPart>* out) {
-  out->assign(hp.parts.size(), DSortPart{nullptr, nullptr});
+// The leaf of every part.  A part names its (query, leaf) pair by its first DTerm (HostPlan.qs_begin).
+int doc_values_part_leaves(const nrtgpu_seg* const* segs, int32_t n_segs, const HostPlan& hp, const char* route, std::vector<int32_t>* out) {
+  out->assign(hp.parts.size(), -1);
   for (const DItem& it : hp.items) {
     for (uint32_t pi = 0; pi < it.n_parts; ++pi) {
       const DPart& p = hp.parts[it.part_begin + pi];
@@ -123,9 +126,20 @@ int doc_values_parts(const nrtgpu_seg* const* segs, int32_t n_segs, const int32_
       for (int32_t si = 0; si < n_segs && leaf < 0; ++si)
         if (hp.qs_begin[(size_t)it.query * (size_t)n_segs + (size_t)si] == p.term_begin) leaf = si;
       if (leaf < 0 || (uint32_t)segs[leaf]->max_doc != p.max_doc) return fail(NRTGPU_ERR_STATE, "%s: a part of query %u names no leaf", route, it.query);
-      (*out)[it.part_begin + pi] = doc_values_column(segs[leaf], field_ids[it.query]);
+      (*out)[it.part_begin + pi] = leaf;
     }
   }
+  return NRTGPU_OK;
+}
+
+// The column of every part's leaf (field_ids: per query).
+int doc_values_parts(const nrtgpu_seg* const* segs, int32_t n_segs, const int32_t* field_ids, const HostPlan& hp, const char* route,
+                     std::vector<DSortPart>* out) {
+  std::vector<int32_t> leaves;
+  if (int rc = doc_values_part_leaves(segs, n_segs, hp, route, &leaves)) return rc;
+  out->assign(hp.parts.size(), DSortPart{nullptr, nullptr});
+  for (const DItem& it : hp.items)
+    for (uint32_t pi = 0; pi < it.n_parts; ++pi) (*out)[it.part_begin + pi] = doc_values_column(segs[leaves[it.part_begin + pi]], field_ids[it.query]);
   return NRTGPU_OK;
 }
 
@@ -158,6 +172,7 @@ int check_call(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, c
     const nrtgpu_field_sort& s = sorts[qi];
     const int kind = (*kinds)[(size_t)qi];
     DSortQuery r{};
+    if (kind >= kDocValuesInt64) return doc_values_wide(qi, s.field_id, "sort by it with nrtgpu_search_sorted64_batch");
     if (multi[(size_t)qi] != 0) return field_sort_multi(qi, s.field_id);
     if (int rc = doc_values_query(segs, n_segs, queries[qi], qi, kind, s.field_id, "a sort", &r.need, flat)) return rc;
     field_sort_record(s, kind, &r);

@@ -701,6 +701,83 @@ struct alignas(16) DSortPart {
 };
 static_assert(sizeof(DSortPart) == 16, "DSortPart layout");
 
+// Sort by a 64-BIT column (fieldsort64.hip: bm25_field_sort64_kernel; docset.hip: docset_sort64_kernel; fieldsort64.cpp): LONG /
+// DATE_TIME (epoch millis) / DOUBLE doc values.  The column is resident as 64-bit order-preserving codes -- unsigned compares of
+// codes order like Long.compare / Double.compare of the values:
+//   kDocValuesInt64   : bits ^ 1 << 63
+//   kDocValuesFloat64 : NaNs canonicalised to 0x7FF8000000000000, then negative doubles ~bits, the others bits | 1 << 63:
+//                       -0.0 < +0.0, NaN above +inf (Double.compare)
+// The top-k's keys stay 64 bits: a call's global docids need db bits (the leaves' bases and sizes say how many), the codes of
+// the sort's column over the call's leaves lie in [lo, lo + span] (recorded at upload), and a key packs a value's ORDINAL in that
+// window above a db-bit docid field -- lossless whenever the ordinals fit the 64 - db bits the docids leave (sort64_fits; a sort
+// that does not fit is refused, not widened).  Ascending ordinal u of a code c: 0 below lo, 1 + (c - lo) inside, span + 2 above
+// hi.  Only the sort's MISSING value can lie outside the window (its code stands for the docs without a value), so the two
+// sentinels lose nothing.  The key's value field is f = reverse ? u + 1 : (span + 2 - u) + 1, in [1, span + 3]; key =
+// (f << db) | ((1 << db) - 1 - global_doc): the k LARGEST keys are the page, equal values rank by docid ascending in both
+// directions, a key is never 0.  The searchAfter cursor is tested on (code, doc), NOT on keys: a cursor value outside the window
+// that is not the missing value would collapse onto a sentinel (sort64_behind).
+// The ONE statement of all of it: the upload, both kernels, the host's decode of the hits, nrtgpu_sort_key64 and
+// nrtgpu_range_accepts64 call these functions.
+constexpr int kDocValuesInt64 = 2, kDocValuesFloat64 = 3;
+__host__ __device__ inline uint64_t doc_value_code64(int kind, uint64_t bits) {
+  if (kind == kDocValuesInt64) return bits ^ 0x8000000000000000ull;
+  if ((bits & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull) bits = 0x7FF8000000000000ull;
+  return (bits & 0x8000000000000000ull) != 0ull ? ~bits : bits | 0x8000000000000000ull;
+}
+__host__ __device__ inline uint64_t doc_value_bits64(int kind, uint64_t code) {   // the inverse (a NaN comes back canonical)
+  if (kind == kDocValuesInt64) return code ^ 0x8000000000000000ull;
+  return (code & 0x8000000000000000ull) != 0ull ? code & 0x7FFFFFFFFFFFFFFFull : ~code;
+}
+__host__ __device__ inline bool range_accepts_code64(uint64_t lo_code, uint64_t hi_code, uint64_t code) { return code >= lo_code && code <= hi_code; }
+// span + 3 <= 2^(64 - db) - 1, without overflow (span may be 2^64 - 1); db in 1..31
+__host__ __device__ inline bool sort64_fits(uint64_t span, uint32_t db) { return span <= (1ull << (64u - db)) - 4ull; }
+// the bits the value field of a window needs: bit_length(span + 3), 65 where that overflows (for the refusal's reason)
+__host__ inline int sort64_value_bits(uint64_t span) {
+  if (span > ~0ull - 3ull) return 65;
+  int b = 0;
+  for (uint64_t f = span + 3ull; f != 0ull; f >>= 1) ++b;
+  return b;
+}
+__host__ __device__ inline uint64_t sort64_ordinal(uint64_t lo, uint64_t span, uint64_t code) {
+  if (code < lo) return 0ull;
+  const uint64_t off = code - lo;
+  return off <= span ? 1ull + off : span + 2ull;
+}
+__host__ __device__ inline uint64_t sort_key64(uint32_t reverse, uint64_t lo, uint64_t span, uint32_t db, uint64_t code, uint32_t global_doc) {
+  const uint64_t u = sort64_ordinal(lo, span, code);
+  const uint64_t f = (reverse != 0u ? u : span + 2ull - u) + 1ull;
+  return (f << db) | (uint64_t)(((1u << db) - 1u) - global_doc);
+}
+// whether (code, doc) ranks strictly behind the cursor (after_code, after_doc) in the sort's order
+__host__ __device__ inline bool sort64_behind(uint32_t reverse, uint64_t code, uint32_t global_doc, uint64_t after_code, uint32_t after_doc) {
+  if (code != after_code) return (reverse != 0u) == (code < after_code);
+  return global_doc > after_doc;
+}
+// the host's decode of a returned key: the doc, and the ascending ordinal of the value it sorted as
+__host__ inline void sort_key64_decode(uint32_t reverse, uint64_t span, uint32_t db, uint64_t key, uint32_t* global_doc, uint64_t* ordinal) {
+  const uint64_t f = (key >> db) - 1ull;
+  *global_doc = ((1u << db) - 1u) - (uint32_t)(key & (uint64_t)((1u << db) - 1u));
+  *ordinal = reverse != 0u ? f : span + 2ull - f;
+}
+// One record per query of the call, and per part of the plan (same index as DPart) the 64-bit column on the part's leaf.
+struct alignas(16) DSort64Query {
+  uint64_t lo, span;       // the window of the column's codes over the call's leaves
+  uint64_t missing_code;   // what a doc without a value sorts as
+  uint64_t after_code;     // searchAfter: the cursor's code ...
+  uint32_t after_doc;      // ... and global docid; only docs behind it are collected (hits of earlier pages still count)
+  uint32_t has_after;
+  uint32_t reverse;        // SortField.getReverse()
+  uint32_t need;           // DSortQuery.need
+  uint32_t db;             // bits of the key's docid field
+  uint32_t pad[3];
+};
+static_assert(sizeof(DSort64Query) == 64, "DSort64Query layout");
+struct alignas(16) DSort64Part {
+  const uint64_t* code64;  // one 64-bit code per doc, padded to whole sub-tiles; nullptr: the leaf lacks the column
+  const uint64_t* has;     // bit d: doc d has a value; nullptr: every doc has
+};
+static_assert(sizeof(DSort64Part) == 16, "DSort64Part layout");
+
 // Terms aggregation (termscount.hip: bm25_terms_count_kernel, terms_compact_kernel; termscount.cpp): a query's hits counted per
 // distinct value of a doc value column.  A bucket is a column CODE (doc_value_code: ints by value, floats by floatToIntBits with
 // every NaN in one bucket).  Count tables are open-addressed, a slot one 64-bit word (count << 32) | code, 0 = empty (a slot
@@ -782,6 +859,14 @@ struct alignas(16) DValueClause {
   uint32_t pad[3];
 };
 static_assert(sizeof(DValueClause) == 48, "DValueClause layout");
+// The same over 64-BIT columns (valuemask.hip: value_mask64_kernel; nrtgpu_segment_set_mask_from_values64): range and exists
+// clauses only, single-valued columns only; range_accepts_code64 over the column's 64-bit codes.
+struct alignas(16) DValueClause64 {
+  const uint64_t* code64;  // DSort64Part.code64 of the column; nullptr: no doc passes
+  const uint64_t* has;     // DSort64Part.has (nullptr: every doc has)
+  uint64_t lo_code, hi_code;
+};
+static_assert(sizeof(DValueClause64) == 32, "DValueClause64 layout");
 // whether the sorted, duplicate-free set[0 .. len), len >= 1, holds code: a lower-bound search whose step count depends on len
 // alone (the lanes of a wave stay together); every index read lies below len
 template <class P>

@@ -5,7 +5,7 @@
 // plan), search.cpp (BM25 entry points, hybrid tail, merge), coalescer.h (request coalescing: the leader/follower mechanism behind
 // the single-query entries of search.cpp and vectors.cpp; standard library only), finalscore.cpp (the host
 // path of the final-score routes), funcscore.cpp (function-score queries), multimatch.cpp (multi-match queries),
-// fieldsort.cpp (a text query's hits sorted by a doc value column), termscount.cpp (its hits counted per value of one),
+// fieldsort.cpp (a text query's hits sorted by a doc value column), fieldsort64.cpp (by a 64-bit one), termscount.cpp (its hits counted per value of one),
 // docset.cpp (both over a doc set without a text clause), valuemask.cpp (filter masks built from doc value columns), vectors.cpp (exact kNN, vector rescoring).  Types the ABI names opaquely (nrtgpu_ctx, nrtgpu_seg) live in the global namespace;
 // everything else in nrtgpu::rt.
 #pragma once
@@ -87,6 +87,15 @@ void launch_docset_terms_count_multi(hipStream_t stream, const FinalScoreArgs& a
 // (n_set_codes codes in all, staged in LDS), n_words words out
 void launch_value_mask(hipStream_t stream, const DValueClause* clauses, uint32_t n_clauses, const uint32_t* sets, uint32_t n_set_codes, uint64_t* out,
                        uint32_t n_words, uint32_t max_doc);
+// the same over 64-bit columns (valuemask.hip: value_mask64_kernel): range / exists clauses, no sets
+void launch_value_mask64(hipStream_t stream, const DValueClause64* clauses, uint32_t n_clauses, uint64_t* out, uint32_t n_words, uint32_t max_doc);
+// sort by a 64-bit column (fieldsort64.hip, docset.hip): one DSort64Query per query, one DSort64Part per part; the doc-set form
+// with the doc set's DRangeQuery per query and its kMaxRanges 32-bit DSortPart per part
+void launch_bm25_field_sort64(hipStream_t stream, const FinalScoreArgs& a, const DSort64Query* squeries, const DSort64Part* sparts);
+void launch_docset_sort64(hipStream_t stream, const FinalScoreArgs& a, const DSort64Query* squeries, const DRangeQuery* rqueries, const DSort64Part* sparts,
+                          const DSortPart* rparts);
+void launch_docset_sort64_multi(hipStream_t stream, const FinalScoreArgs& a, const DSort64Query* squeries, const DRangeQuery* rqueries,
+                                const DSort64Part* sparts, const DSortPart* rparts);
 #ifdef NRTGPU_DEV
 void launch_debug_wave_kth(hipStream_t stream, const uint64_t* keys, uint32_t n, uint32_t r, uint64_t* out);   // (maxscore.hip: topk_kth_wave on its own)
 void launch_debug_walk_value(hipStream_t stream, float weight, const uint32_t* freq, const uint32_t* norm, const float* table, int fx_scale,
@@ -375,6 +384,13 @@ struct FieldData {
   uint64_t* d_dv_has = nullptr;
   uint32_t* d_dv_start = nullptr;
   int32_t dv_kind = -1;
+  // A 64-BIT column (nrtgpu_segment_add_doc_values64; dv_kind is kDocValuesInt64 / kDocValuesFloat64, single-valued): the codes
+  // (plan.h: doc_value_code64) live in d_dv_code64, d_dv_has says which docs have a value, and d_dv_code stays nullptr -- what
+  // reads 32-bit codes (doc_values_column) finds no column to read at the wrong width.  dv_min_code / dv_max_code: the least and
+  // the greatest code among the dv_n values uploaded (dv_n == 0: no bound): the window a sort's packed keys are built in.
+  uint64_t* d_dv_code64 = nullptr;
+  uint64_t dv_min_code = 0, dv_max_code = 0;
+  int32_t dv_n = 0;
   // rows whose doc is live under the segment's current liveDocs (what an exact vector query matches), counted on first
   // use per liveDocs version
   mutable std::atomic<int64_t> live_vec{-1};
@@ -385,7 +401,8 @@ struct FieldData {
         d_vnorm2(o.d_vnorm2), d_ord_to_doc(o.d_ord_to_doc), h_ord_to_doc(o.h_ord_to_doc), dim(o.dim), n_vec(o.n_vec),
         vnorm2_max(o.vnorm2_max), d_sketch(o.d_sketch), sketch_state(o.sketch_state), sketch_scale(o.sketch_scale), absmax(o.absmax),
         vnorm2_min(o.vnorm2_min), byte_rows(o.byte_rows), d_btiles(o.d_btiles), d_bnorm2(o.d_bnorm2), d_dv_code(o.d_dv_code),
-        d_dv_has(o.d_dv_has), d_dv_start(o.d_dv_start), dv_kind(o.dv_kind) {}
+        d_dv_has(o.d_dv_has), d_dv_start(o.d_dv_start), dv_kind(o.dv_kind), d_dv_code64(o.d_dv_code64), dv_min_code(o.dv_min_code),
+        dv_max_code(o.dv_max_code), dv_n(o.dv_n) {}
 };
 
 }  // namespace rt
@@ -1205,9 +1222,40 @@ int field_sort_multi(int qi, int32_t field_id);
 // the FILTER / MUST_NOT masks of q are resident on every leaf of the call, else NRTGPU_ERR_UNSUPPORTED naming the query (what
 // doc_values_query refuses of them; docset.cpp asks the same of a doc-set query's masks)
 int doc_values_masks_resident(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query& q, int qi);
+// NRTGPU_ERR_UNSUPPORTED with the reason: a 32-bit entry named a field that holds a 64-bit column (kind >= kDocValuesInt64);
+// instead: what serves such a column, or that nothing does
+int doc_values_wide(int qi, int32_t field_id, const char* instead);
+constexpr const char* kTermsCountWide = "terms counts read 32-bit columns, 64-bit buckets are not built";
+// the leaf (index into segs) of every part of a plan of the flat copies: a part names its (query, leaf) pair by its first DTerm
+int doc_values_part_leaves(const nrtgpu_seg* const* segs, int32_t n_segs, const HostPlan& hp, const char* route, std::vector<int32_t>* out);
 // the column of every part's leaf, for a plan of the flat copies (field_ids: per query)
 int doc_values_parts(const nrtgpu_seg* const* segs, int32_t n_segs, const int32_t* field_ids, const HostPlan& hp, const char* route,
                      std::vector<DSortPart>* out);
+
+// fieldsort64.cpp: what the sorted routes over a 64-bit column share (the text route there; the doc-set form in docset.cpp).
+// what they refuse of a nrtgpu_field_sort64 as an invalid argument (field_sort_check's table)
+int field_sort64_check(const nrtgpu_field_sort64& s, int qi);
+// NRTGPU_ERR_UNSUPPORTED with the reason: the sort's column is a 32-bit one (multi: multi-valued); entry32: the entry that serves it
+int field_sort64_narrow(int qi, int32_t field_id, bool multi, const char* entry32);
+// the bits the call's global docids need: max(1, bit_length(D - 1)), D = max over the leaves of base + max_doc; doc_bases NULL:
+// in_order ? the leaves in order, base 0 for the first (the predicates) : every leaf at base 0 (what the plans do).
+// NRTGPU_ERR_UNSUPPORTED: D beyond 2^31
+int sort64_doc_bits(const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, bool in_order, uint32_t* db);
+// the sort's side of the query's record (`need` is the caller's): the window of the column's codes over the leaves that hold a
+// value, the cursor as a code; NRTGPU_ERR_UNSUPPORTED naming the bits when the window does not fit beside db docid bits
+int field_sort64_record(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_field_sort64& s, int kind, uint32_t db, int qi, DSort64Query* r);
+// the field's 64-bit column on one leaf ({nullptr, nullptr}: the leaf lacks it -- or holds a 32-bit one, which the checks refused)
+DSort64Part doc_values_column64(const nrtgpu_seg* seg, int32_t field_id);
+// The internal pages final_score_run fills for such a call (ks: the queries' numHits; capacities: the caller's) and their decode
+// into the caller's pages: key = high << 32 | (0xFFFFFFFF - doc), then plan.h: sort_key64_decode; a sentinel ordinal is the
+// sort's missing_bits verbatim.
+struct Sort64Pages {
+  std::vector<nrtgpu_topdocs> pages;
+  std::vector<int32_t> docs;
+  std::vector<float> highs;
+  Sort64Pages(const int32_t* ks, const nrtgpu_fielddocs64* out, int32_t n_queries);
+  void decode(const std::vector<DSort64Query>& records, const std::vector<int>& kinds, const nrtgpu_field_sort64* sorts, nrtgpu_fielddocs64* out) const;
+};
 
 // termscount.cpp: what the routes that fill count tables share (a text query's hits there; a doc set's in docset.cpp).
 // Where the route's own workspace bytes lie (offsets from FinalScoreArgs.own), and what comes back from them.

@@ -430,6 +430,73 @@ extern "C" int nrtgpu_segment_add_doc_values(nrtgpu_seg* seg, int32_t field_id, 
   return NRTGPU_OK;
 }
 
+// One 64-bit value per doc of a field (LongFieldDef / DateTimeFieldDef / DoubleFieldDef doc values): the contract above with
+// 8-byte values -- coded on the host (plan.h: doc_value_code64), resident as one uint64 code per doc, padded with zeros to whole
+// sub-tiles, and the `has` words unless every doc has a value.  The least and the greatest code and the number of values stay on
+// the segment: the window a sort packs its keys in (plan.h: sort_key64).
+extern "C" int nrtgpu_segment_add_doc_values64(nrtgpu_seg* seg, int32_t field_id, int32_t kind, int32_t n, const int32_t* docs, const void* values) {
+  if (!seg) return fail(NRTGPU_ERR_INVALID_ARG, "seg is NULL");
+  if (seg->sealed) return fail(NRTGPU_ERR_STATE, "segment already sealed");
+  if (kind != NRTGPU_DOCVALUES_INT64 && kind != NRTGPU_DOCVALUES_FLOAT64) return fail(NRTGPU_ERR_INVALID_ARG, "64-bit doc values kind %d outside 2..3", kind);
+  if (n < 0 || n > seg->max_doc) return fail(NRTGPU_ERR_INVALID_ARG, "%d doc values for %d docs", n, seg->max_doc);
+  if (!docs && n != seg->max_doc) return fail(NRTGPU_ERR_INVALID_ARG, "docs is NULL: one value per doc (%d) expected, got %d", seg->max_doc, n);
+  if (n > 0 && !values) return fail(NRTGPU_ERR_INVALID_ARG, "values is NULL");
+  if (docs)
+    for (int32_t i = 0; i < n; ++i)
+      if (docs[i] < 0 || docs[i] >= seg->max_doc || (i > 0 && docs[i] <= docs[i - 1]))
+        return fail(NRTGPU_ERR_INVALID_ARG, "docs must be strictly ascending docids in [0,max_doc)");
+  {
+    const auto fit = seg->fields.find(field_id);
+    if (fit != seg->fields.end() && fit->second.dv_kind >= 0) return fail(NRTGPU_ERR_INVALID_ARG, "doc values of field %d already added", field_id);
+  }
+  HIP_TRY(hipSetDevice(seg->ctx->device));
+  const size_t padded = (size_t)seg->n_tiles * (size_t)kTileDocs;
+  std::vector<uint64_t> code(padded, 0ull);
+  std::vector<uint64_t> has;
+  if (n != seg->max_doc) has.assign(padded / 64, 0ull);
+  uint64_t min_code = ~0ull, max_code = 0ull;
+  for (int32_t i = 0; i < n; ++i) {   // (n == max_doc: ascending docids in [0, max_doc), doc i = i)
+    uint64_t bits;
+    memcpy(&bits, (const char*)values + (size_t)i * 8, 8);   // (the caller's array need not be 8-byte aligned)
+    const uint64_t c = doc_value_code64(kind, bits);
+    const uint32_t d = has.empty() ? (uint32_t)i : (uint32_t)docs[i];
+    code[d] = c;
+    if (!has.empty()) has[d >> 6] |= 1ull << (d & 63u);
+    min_code = std::min(min_code, c);
+    max_code = std::max(max_code, c);
+  }
+  void *d_code = nullptr, *d_has = nullptr;
+  if (int rc = dev_alloc(seg, &d_code, padded * 8)) return rc;
+  hipError_t e = hipMemcpy(d_code, code.data(), padded * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess && !has.empty()) {
+    if (int rc = dev_alloc(seg, &d_has, has.size() * 8)) {
+      (void)hipFree(d_code);
+      seg->device_bytes -= (int64_t)(padded * 8);
+      return rc;
+    }
+    e = hipMemcpy(d_has, has.data(), has.size() * 8, hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess) {
+    (void)hipFree(d_code);
+    seg->device_bytes -= (int64_t)(padded * 8);
+    if (d_has) {
+      (void)hipFree(d_has);
+      seg->device_bytes -= (int64_t)(has.size() * 8);
+    }
+    return fail(NRTGPU_ERR_HIP, "upload of the doc values of field %d failed: %s", field_id, hipGetErrorString(e));
+  }
+  FieldData& f = seg->fields[field_id];   // (set when everything is resident)
+  f.d_dv_code64 = (uint64_t*)d_code;
+  f.d_dv_has = (uint64_t*)d_has;
+  f.dv_kind = kind;
+  f.dv_n = n;
+  if (n > 0) {
+    f.dv_min_code = min_code;
+    f.dv_max_code = max_code;
+  }
+  return NRTGPU_OK;
+}
+
 // Any number of 32-bit values per doc of a field (every value of leaf.reader().getSortedNumericDocValues, or the global ordinals
 // of a SORTED_SET field): coded on the host by the same doc_value_code and resident as codes[] in upload order behind a uint32
 // start[] -- one entry per doc, padded to whole sub-tiles, plus one: a kernel reads start[d] and start[d + 1] of a sub-tile's docs
@@ -1027,6 +1094,7 @@ SegCore::~SegCore() {
     if (f.d_bnorm2) (void)hipFree(f.d_bnorm2);
     if (f.d_ord_to_doc) (void)hipFree(f.d_ord_to_doc);
     if (f.d_dv_code) (void)hipFree(f.d_dv_code);
+    if (f.d_dv_code64) (void)hipFree(f.d_dv_code64);
     if (f.d_dv_has) (void)hipFree(f.d_dv_has);
     if (f.d_dv_start) (void)hipFree(f.d_dv_start);
     for (auto& g : f.groups) {

@@ -131,6 +131,7 @@ int check_call(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, c
   for (int qi = 0; qi < n_queries; ++qi) {
     DTermsQuery& r = (*records)[(size_t)qi];
     uint32_t need = 0;
+    if ((*kinds)[(size_t)qi] >= kDocValuesInt64) return doc_values_wide(qi, terms[qi].field_id, kTermsCountWide);
     if (int rc = doc_values_query(segs, n_segs, queries[qi], qi, (*kinds)[(size_t)qi], terms[qi].field_id, "a terms count", &need, flat)) return rc;
     r.need |= need;   // (beside kTermsQueryMulti)
   }

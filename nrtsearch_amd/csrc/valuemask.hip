@@ -13,6 +13,8 @@
 //                       only lanes whose doc is still in the word walk; the bound is the doc's count, read on entry.
 //   in set              the call's code sets (sorted, duplicate-free: the host) are copied into the workgroup's LDS once; a
 //                       value is looked up by value_set_has (plan.h), whose step count is the set's length's alone.
+//   value_mask64_kernel the same walk over 64-BIT columns (nrtgpu_segment_set_mask_from_values64): range / exists clauses, one
+//                       coalesced 8-byte load per lane and clause, no sets
 // All writes are vector stores in plain HIP; every loop is bounded by a count known on entry.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -71,6 +73,45 @@ void value_mask_kernel(const DValueClause* __restrict__ clauses, uint32_t n_clau
     }
     if (lane == 0u) out[w] = word;
   }
+}
+
+// value_mask_kernel's wave-per-word walk over 64-BIT columns (nrtgpu_segment_set_mask_from_values64; plan.h: DValueClause64):
+// range / exists clauses over single-valued columns -- per clause one coalesced 8-byte load per lane, the `has` word, the test
+// through range_accepts_code64.  No sets, no LDS.
+__global__ __launch_bounds__(kValueMaskThreads)
+void value_mask64_kernel(const DValueClause64* __restrict__ clauses, uint32_t n_clauses, uint64_t* __restrict__ out, uint32_t n_words, uint32_t max_doc) {
+  const uint32_t tid = threadIdx.x;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)), lane = tid & 63u;
+  constexpr uint32_t kWaves = (uint32_t)kValueMaskThreads / 64u;
+  const uint32_t stride = gridDim.x * kWaves;
+  n_clauses = min(n_clauses, (uint32_t)kMaxRanges);
+  for (uint32_t w = blockIdx.x * kWaves + wave; w < n_words; w += stride) {   // (uniform)
+    const uint32_t doc = 64u * w + lane;
+    const uint32_t below = max_doc - 64u * w;   // the word's docs below max_doc (>= 1: w < n_words)
+    uint64_t word = below < 64u ? (1ull << below) - 1ull : ~0ull;
+#pragma unroll 1
+    for (uint32_t c = 0; c < n_clauses && word != 0ull; ++c) {   // (uniform: a word that is empty reads no further column)
+      const DValueClause64* const cl = clauses + c;
+      const NRT_GLOBAL uint64_t* const codes = (const NRT_GLOBAL uint64_t*)cl->code64;
+      const NRT_GLOBAL uint64_t* const has = (const NRT_GLOBAL uint64_t*)cl->has;
+      if (codes == nullptr) {   // uniform: the column holds no value
+        word = 0ull;
+        break;
+      }
+      const uint64_t code = codes[doc];   // (the column is padded to whole sub-tiles, a multiple of 64 docs: no bounds test)
+      const uint64_t hw = has != nullptr ? has[w] : ~0ull;   // uniform
+      const bool pass = ((hw >> lane) & 1ull) != 0ull && range_accepts_code64(cl->lo_code, cl->hi_code, code);
+      word &= __ballot(pass);
+    }
+    if (lane == 0u) out[w] = word;
+  }
+}
+
+void launch_value_mask64(hipStream_t stream, const DValueClause64* clauses, uint32_t n_clauses, uint64_t* out, uint32_t n_words, uint32_t max_doc) {
+  if (n_words == 0) return;
+  constexpr uint32_t kWaves = (uint32_t)kValueMaskThreads / 64u;
+  const uint32_t blocks = std::min<uint32_t>((n_words + kWaves - 1u) / kWaves, 2048u);
+  hipLaunchKernelGGL(value_mask64_kernel, dim3(blocks), dim3(kValueMaskThreads), 0, stream, clauses, n_clauses, out, n_words, max_doc);
 }
 
 void launch_value_mask(hipStream_t stream, const DValueClause* clauses, uint32_t n_clauses, const uint32_t* sets, uint32_t n_set_codes, uint64_t* out,
