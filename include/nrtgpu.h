@@ -1357,6 +1357,88 @@ int  nrtgpu_count_docset_terms_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* cons
 int  nrtgpu_range_accepts(int32_t kind, uint32_t lower_bits, uint32_t upper_bits, uint32_t value_bits, int32_t* out);
 
 /* ---------------------------------------------------------------------------------------------
+ * Numeric range facets: a query's hits counted per requested value range of a single-valued doc value column -- "under 10,
+ * 10-25, 25-50, over 50", "rated 4+, 3+, 2+", "added in the last day / week / month" (the last two overlap).  The reference's
+ * Facet.numericRange (clientlib/src/main/proto/yelp/nrtsearch/search.proto:1285-1327), served by DrillSidewaysImpl.java:334-409:
+ * INT and LONG fields become LongRange[] -> LongRangeFacetCounts, DOUBLE fields DoubleRange[] -> DoubleRangeFacetCounts.
+ * Per query of a batch: a column and n_ranges (1..NRTGPU_MAX_COUNT_RANGES) ranges [lower, upper], BOTH bounds INCLUSIVE, bits
+ * of the column's kind -- nrtgpu_range_clause's convention; the caller maps an exclusive bound (+-1, Math.nextUp / nextDown).
+ * All four single-valued kinds are accepted: INT32, FLOAT32, INT64 (LONG, DATE_TIME), FLOAT64.  FLOAT32 has no counterpart in the
+ * reference, which refuses FLOAT fields (DrillSidewaysImpl.java:367-371); the rule for it is the 32-bit range clause's order.
+ * Which docs are hits.  nrtgpu_count_ranges_batch: nrtgpu_count_terms_batch's matching rule, word for word (all SHOULD: at least
+ * max(1, min_should_match) clauses; all MUST: all of them; inside the accept set).  nrtgpu_count_docset_ranges_batch:
+ * nrtgpu_count_docset_terms_batch's hit set, word for word (liveDocs, FILTER / MUST_NOT masks, the doc set's own 32-bit range
+ * clauses over single- or multi-valued columns).
+ * What is counted.  A hit that has a value v adds 1 to EVERY range with lower <= v <= upper in the column's code order: ints by
+ * Integer.compare / Long.compare; floats and doubles in sortable-bits order -- -0.0 < +0.0, every NaN the canonical one and above
+ * +inf.  Ranges may overlap, nest, repeat or touch; each is counted independently.  A hit without a value, or in a leaf that
+ * lacks the column, adds to no range.  lower > upper in that order is an EMPTY range with count 0, not an error.
+ * [Lucene-recall] a range facet counts a doc once per range that contains its value; DoubleRange compares through
+ * NumericUtils.doubleToSortableLong; totCount is the number of hits that have a value.
+ * Output per query: counts[n_ranges] in request order; total_hits, exact, with the per-slice relation machinery of the other
+ * routes untouched; hits_with_value, the reference's totCount behind FacetResult.value.  topN, labels and the order of the
+ * result stay with the caller.
+ * How: the device counts per ELEMENTARY INTERVAL between the ranges' cut points (nrtgpu_range_cuts / nrtgpu_range_interval
+ * below), the host sums the intervals a range covers -- exact integer sums; there is no bucket bound and no overflow state.
+ * One call's queries must all name columns of ONE width: a batch that mixes 32- and 64-bit columns is NRTGPU_ERR_UNSUPPORTED
+ * (split it).  The one entry serves both widths.
+ * Context flags: the doc-set entry runs under NRTGPU_FLAG_PACKED_POSTINGS / NRTGPU_FLAG_NO_FIXED_POINT, the text entry refuses
+ * both -- as their terms-count siblings do.  Slicing, thread slices, deadlines, diagnostics and statistics work as there.
+ * Refusals, each with a reason in nrtgpu_last_error naming the query: the tables of nrtgpu_count_terms_batch /
+ * nrtgpu_count_docset_terms_batch with the same statuses and precedence (max_buckets and the workspace bound aside); every
+ * NRTGPU_ERR_INVALID_ARG check of EVERY query comes before any NRTGPU_ERR_UNSUPPORTED one; the predicates and the entries agree.
+ * They add:
+ *   NRTGPU_ERR_INVALID_ARG  n_ranges outside 1..NRTGPU_MAX_COUNT_RANGES; ranges NULL; a non-zero high word of a bound for a
+ *                           32-bit kind; capacity < n_ranges or counts NULL; reserved != 0
+ *   NRTGPU_ERR_UNSUPPORTED  a multi-valued count column (the reference counts a doc once per range there, which needs a per-doc
+ *                           range mask instead of intervals); a batch that mixes 32- and 64-bit columns
+ * Out of scope: multi-valued count columns; sampleTopDocs; facet scripts and virtual fields; drill-sideways per-dimension hit
+ * sets (the call counts ONE hit set, the shim picks it); fusing the count into a scoring route; the coalesced, device-resident
+ * and nrtgpu_dist_* forms; the Java shim, which keeps sending facet requests to Lucene until it binds this.
+ * --------------------------------------------------------------------------------------------- */
+#define NRTGPU_MAX_COUNT_RANGES 64
+typedef struct {
+  uint64_t lower_bits;    /* inclusive, bits of the column's kind; a 32-bit kind uses the low word, the high word is 0 */
+  uint64_t upper_bits;    /* inclusive */
+} nrtgpu_value_range;     /* 16 bytes */
+typedef struct {
+  int32_t field_id;       /* the column: a single-valued one of any NRTGPU_DOCVALUES_* kind */
+  int32_t n_ranges;       /* 1 .. NRTGPU_MAX_COUNT_RANGES */
+  const nrtgpu_value_range* ranges;
+} nrtgpu_range_count;     /* 16 bytes */
+typedef struct {
+  int64_t* counts;           /* out: hits per range, in request order */
+  int32_t  capacity;         /* in : capacity of counts, >= n_ranges */
+  int32_t  reserved;         /* in : 0 */
+  int64_t  total_hits;       /* out: live matching docs, exact */
+  int64_t  hits_with_value;  /* out: hits that have a value in the column */
+} nrtgpu_range_counts;       /* 32 bytes */
+/* n_queries range facets over the same leaves in one device pass; ranges[i] names the column and the ranges of queries[i] */
+int  nrtgpu_count_ranges_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                               const nrtgpu_bm25_query* queries, const nrtgpu_range_count* ranges, int32_t n_queries,
+                               nrtgpu_range_counts* out);
+/* The eligibility test alone (with an output of sufficient capacity).  No device work. */
+int  nrtgpu_count_ranges_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query* q,
+                                   const nrtgpu_range_count* r);
+/* The same over doc sets: ranges[i] names the column and the ranges counted over the hits of docsets[i] */
+int  nrtgpu_count_docset_ranges_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                      const nrtgpu_docset_query* docsets, const nrtgpu_range_count* ranges, int32_t n_queries,
+                                      nrtgpu_range_counts* out);
+int  nrtgpu_count_docset_ranges_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* d,
+                                          const nrtgpu_range_count* r);
+/* The cut points of a range list and the interval of a value, exposed for the tests: no device; they are the very functions the
+ * host plans with and the kernels compile.  kind: NRTGPU_DOCVALUES_* (all four).
+ * nrtgpu_range_cuts: the cuts of ranges[0 .. n_ranges), n_ranges in 0..NRTGPU_MAX_COUNT_RANGES, as CODES of the kind (a 32-bit
+ * kind: in the low words), ascending without duplicates, into out_cuts[2 x NRTGPU_MAX_COUNT_RANGES]; *out_n_cuts of them.  Each
+ * non-empty range gives its lower bound and the code behind its upper bound, the latter unless the upper bound is the kind's
+ * greatest value.
+ * nrtgpu_range_interval: the number of cuts[0 .. n_cuts) that are <= the code of value_bits, in 0..n_cuts; a range covers the
+ * intervals from its lower bound's to its upper bound's.
+ * NRTGPU_ERR_INVALID_ARG: a kind outside 0..3, NULL arguments, counts out of bounds, a non-zero high word for a 32-bit kind. */
+int  nrtgpu_range_cuts(int32_t kind, const nrtgpu_value_range* ranges, int32_t n_ranges, uint64_t* out_cuts, int32_t* out_n_cuts);
+int  nrtgpu_range_interval(int32_t kind, const uint64_t* cuts, int32_t n_cuts, uint64_t value_bits, int32_t* out_interval);
+
+/* ---------------------------------------------------------------------------------------------
  * Host-side restatements the Java shim would otherwise take from Lucene objects
  * (BM25Similarity.scorer(boost, collectionStats, termStats); SmallFloat; slices()).
  * --------------------------------------------------------------------------------------------- */

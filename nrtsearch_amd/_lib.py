@@ -41,6 +41,7 @@ NRTGPU_DOCVALUES_INT64 = 2
 NRTGPU_DOCVALUES_FLOAT64 = 3
 NRTGPU_MAX_TERM_BUCKETS = 65536
 NRTGPU_MAX_RANGES = 4
+NRTGPU_MAX_COUNT_RANGES = 64
 NRTGPU_CLAUSE_RANGE = 0
 NRTGPU_CLAUSE_EXISTS = 1
 NRTGPU_CLAUSE_IN_SET = 2
@@ -77,6 +78,8 @@ ABI_SYMBOLS = [
     "nrtgpu_segment_set_mask_from_values", "nrtgpu_segment_get_mask",
     "nrtgpu_segment_add_doc_values64", "nrtgpu_sort_key64", "nrtgpu_search_sorted64_batch", "nrtgpu_sorted64_supported",
     "nrtgpu_search_docset_sorted64_batch", "nrtgpu_docset_sorted64_supported", "nrtgpu_segment_set_mask_from_values64", "nrtgpu_range_accepts64",
+    "nrtgpu_count_ranges_batch", "nrtgpu_count_ranges_supported", "nrtgpu_count_docset_ranges_batch", "nrtgpu_count_docset_ranges_supported",
+    "nrtgpu_range_cuts", "nrtgpu_range_interval",
 ]
 # what include/nrtgpu_dev.h adds: test hooks and measurement helpers of the development library (libnrtgpu_dev.so) only
 DEV_SYMBOLS = [
@@ -172,6 +175,19 @@ class TermsCount(C.Structure):   # nrtgpu_terms_count
 class TermCounts(C.Structure):   # nrtgpu_term_counts
     _fields_ = [("n_buckets", C.c_int32), ("capacity", C.c_int32), ("value_bits", C.POINTER(C.c_uint32)), ("counts", C.POINTER(C.c_int32)),
                 ("total_hits", C.c_int64), ("hits_with_value", C.c_int64), ("overflowed", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ValueRange(C.Structure):   # nrtgpu_value_range
+    _fields_ = [("lower_bits", C.c_uint64), ("upper_bits", C.c_uint64)]
+
+
+class RangeCount(C.Structure):   # nrtgpu_range_count
+    _fields_ = [("field_id", C.c_int32), ("n_ranges", C.c_int32), ("ranges", C.POINTER(ValueRange))]
+
+
+class RangeCounts(C.Structure):   # nrtgpu_range_counts
+    _fields_ = [("counts", C.POINTER(C.c_int64)), ("capacity", C.c_int32), ("reserved", C.c_int32), ("total_hits", C.c_int64),
+                ("hits_with_value", C.c_int64)]
 
 
 class RangeClause(C.Structure):   # nrtgpu_range_clause
@@ -322,6 +338,12 @@ def _open(path: str) -> C.CDLL:
     L.nrtgpu_docset_sorted64_supported.argtypes = [vp, vp, i32, C.POINTER(DocsetQuery), C.POINTER(FieldSort64)]
     L.nrtgpu_segment_set_mask_from_values64.argtypes = [vp, i32, C.POINTER(ValueClause64), i32, vp]
     L.nrtgpu_range_accepts64.argtypes = [i32, u64, u64, u64, vp]
+    L.nrtgpu_count_ranges_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(RangeCount), i32, C.POINTER(RangeCounts)]
+    L.nrtgpu_count_ranges_supported.argtypes = [vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(RangeCount)]
+    L.nrtgpu_count_docset_ranges_batch.argtypes = [vp, vp, vp, i32, C.POINTER(DocsetQuery), C.POINTER(RangeCount), i32, C.POINTER(RangeCounts)]
+    L.nrtgpu_count_docset_ranges_supported.argtypes = [vp, vp, i32, C.POINTER(DocsetQuery), C.POINTER(RangeCount)]
+    L.nrtgpu_range_cuts.argtypes = [i32, C.POINTER(ValueRange), i32, vp, vp]
+    L.nrtgpu_range_interval.argtypes = [i32, vp, i32, u64, vp]
     L.nrtgpu_rescore_vectors.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, f32, vp, vp, i32, C.c_double, C.c_double, i32,
                                          C.POINTER(TopDocs)]
     L.nrtgpu_search_hybrid_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), i32, i32, i32, vp, i32, f32,

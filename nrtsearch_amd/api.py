@@ -1387,22 +1387,30 @@ def slices(max_docs: Sequence[int], num_docs: Optional[Sequence[int]] = None, vi
     return out, sh[:n].tolist()
 
 
+def _marshal_counted(searcher: "GpuIndexSearcher", queries: Sequence[Query], managers: Sequence[TopScoreDocCollectorManager]) -> _Marshalled:
+    """The queries of a route that counts matching clauses itself (sorted searches, terms and range counts): a BooleanQuery of MUST
+    clauses only goes down as MUST clauses, not as the disjunction with minimumNumberShouldMatch = n the scoring routes take."""
+    m = searcher._marshal(queries, managers)
+    for qi, query in enumerate(queries):
+        if isinstance(query, BooleanQuery) and query.must and not query.should and not isinstance(query.must[0], DisjunctionMaxQuery):
+            q = m.queries[qi]
+            for ti in range(q.n_terms):
+                q.terms[ti].occur = 1
+            q.min_should_match = 0
+    return m
+
+
 def _marshal_sorted(searcher: "GpuIndexSearcher", queries: Sequence[Query], managers: Sequence[TopScoreDocCollectorManager],
                     sorts: Sequence[SortField], afters: Optional[Sequence[Optional[FieldDoc]]]):
     """The queries and nrtgpu_field_sort per query of a sorted search.  A BooleanQuery of MUST clauses only goes down as MUST
     clauses (the route counts them itself), not as the disjunction with minimumNumberShouldMatch = n the scoring routes take."""
     if len(sorts) != len(queries) or (afters is not None and len(afters) != len(queries)):
         raise ValueError(f"{len(sorts)} sorts / {None if afters is None else len(afters)} afters for {len(queries)} queries")
-    m = searcher._marshal(queries, managers)
+    m = _marshal_counted(searcher, queries, managers)
     fs = (_lib.FieldSort * len(queries))()
-    for qi, (query, sort) in enumerate(zip(queries, sorts)):
+    for qi, sort in enumerate(sorts):
         if sort.kind not in DOC_VALUE_KINDS:
             raise UnsupportedQuery(f"a sort of kind {sort.kind!r}")
-        if isinstance(query, BooleanQuery) and query.must and not query.should and not isinstance(query.must[0], DisjunctionMaxQuery):
-            q = m.queries[qi]
-            for ti in range(q.n_terms):
-                q.terms[ti].occur = 1
-            q.min_should_match = 0
         after = afters[qi] if afters is not None else None
         fs[qi] = _lib.FieldSort(int(sort.field), int(bool(sort.reverse)), _value_bits(sort.kind, sort.missing), int(after is not None),
                                 int(after.doc) if after is not None else 0, _value_bits(sort.kind, after.value) if after is not None else 0)
@@ -1897,6 +1905,184 @@ def range_accepts64(kind: str, lower_bits: int, upper_bits: int, value_bits: int
     _lib.check(_lib.load().nrtgpu_range_accepts64(DOC_VALUE_KINDS64[kind][0], C.c_uint64(int(lower_bits)), C.c_uint64(int(upper_bits)),
                                                   C.c_uint64(int(value_bits)), C.byref(out)))
     return bool(out.value)
+
+
+# ---- numeric range facets: a query's hits counted per requested value range (all four single-valued kinds) -----------------------
+ALL_DOC_VALUE_KINDS = {**DOC_VALUE_KINDS, **DOC_VALUE_KINDS64}
+_INT_LIMITS = {"int": (-2**31, 2**31 - 1), "long": (-2**63, 2**63 - 1)}
+
+
+def _any_value_bits(kind: str, value) -> int:
+    return _value_bits64(kind, value) if kind in DOC_VALUE_KINDS64 else _value_bits(kind, value)
+
+
+@dataclasses.dataclass(frozen=True)
+class NumericRange:
+    """One NumericRangeType of a Facet.numericRange request (search.proto:1285-1327): label, min, minInclusive, max, maxInclusive;
+    min and max are the proto's int64.  bounds(kind) restates the constructors of LongRange (INT / LONG fields) and DoubleRange
+    (DOUBLE fields) [Lucene-recall: read from memory of Lucene 10, never from a run]: it yields the INCLUSIVE bounds the device call
+    takes."""
+
+    label: str
+    min: Union[int, float]
+    min_inclusive: bool
+    max: Union[int, float]
+    max_inclusive: bool
+
+    def bounds(self, kind: str) -> Tuple[Union[int, float], Union[int, float]]:
+        """-> (lower, upper), both inclusive, values of the kind.  ValueError where the reference's constructor throws: an exclusive
+        bound at the type's extreme (LongRange), a NaN bound (DoubleRange), min > max after the adjustment.  An INT field's bounds
+        are longs in the reference; what lies outside int32 is cut to it here (a range no int lies in comes back as the empty (1, 0)).
+        "float" has no counterpart in the reference (it refuses FLOAT fields): DoubleRange's rule in float32 steps."""
+        if kind not in ALL_DOC_VALUE_KINDS:
+            raise UnsupportedQuery(f"a numeric range over a column of kind {kind!r}")
+        if kind in _INT_LIMITS:
+            lo, hi = int(self.min), int(self.max)
+            if not self.min_inclusive:
+                if lo == 2**63 - 1:
+                    raise ValueError(f"range {self.label!r}: an exclusive min at Long.MAX_VALUE matches nothing")
+                lo += 1
+            if not self.max_inclusive:
+                if hi == -2**63:
+                    raise ValueError(f"range {self.label!r}: an exclusive max at Long.MIN_VALUE matches nothing")
+                hi -= 1
+            if lo > hi:
+                raise ValueError(f"range {self.label!r}: min {lo} > max {hi}")
+            least, greatest = _INT_LIMITS[kind]
+            lo, hi = max(lo, least), min(hi, greatest)
+            return (lo, hi) if lo <= hi else (1, 0)
+        dt = np.float64 if kind == "double" else np.float32
+        lo, hi = dt(self.min), dt(self.max)   # (the proto's int64 widened, as Java's implicit conversion does)
+        if np.isnan(lo) or np.isnan(hi):
+            raise ValueError(f"range {self.label!r}: a NaN bound")
+        if not self.min_inclusive:
+            lo = np.nextafter(lo, dt(np.inf))      # Math.nextUp
+        if not self.max_inclusive:
+            hi = np.nextafter(hi, dt(-np.inf))     # Math.nextDown
+        if lo > hi:
+            raise ValueError(f"range {self.label!r}: min {lo} > max {hi}")
+        return float(lo), float(hi)
+
+
+@dataclasses.dataclass(frozen=True)
+class RangeCounter:
+    """A numeric range facet over the single-valued doc value column `field` of kind `kind` ("int", "float", "long", "double").
+    ranges: NumericRange records, or (lower_bits, upper_bits) pairs -- the inclusive bounds as bits of the kind, what the C call
+    takes (lower above upper in the kind's order: an empty range, counted as 0).  topN, labels and the order of the result stay
+    with the caller."""
+
+    field: int
+    kind: str
+    ranges: Tuple[Union[NumericRange, Tuple[int, int]], ...]
+
+
+@dataclasses.dataclass
+class RangeCounts:
+    """The facet of one query (nrtgpu_range_counts): hits per range in request order; hits_with_value is the reference's totCount
+    behind FacetResult.value."""
+
+    counts: np.ndarray          # int64
+    total_hits: int
+    hits_with_value: int
+
+
+def _marshal_range_counters(counters: Sequence[RangeCounter]):
+    """nrtgpu_range_count per query, the outputs, and what keeps the arrays alive."""
+    n = len(counters)
+    rc = (_lib.RangeCount * n)()
+    outs = (_lib.RangeCounts * n)()
+    width = max([max(len(c.ranges), 1) for c in counters], default=1)
+    counts = np.zeros((n, width), dtype=np.int64)
+    keep: list = [rc, outs, counts]
+    for qi, c in enumerate(counters):
+        if c.kind not in ALL_DOC_VALUE_KINDS:
+            raise UnsupportedQuery(f"a range counter of kind {c.kind!r}")
+        vr = (_lib.ValueRange * max(len(c.ranges), 1))()
+        for i, r in enumerate(c.ranges):
+            if isinstance(r, NumericRange):
+                lo, hi = r.bounds(c.kind)
+                vr[i] = _lib.ValueRange(_any_value_bits(c.kind, lo), _any_value_bits(c.kind, hi))
+            else:
+                vr[i] = _lib.ValueRange(int(r[0]), int(r[1]))
+        keep.append(vr)
+        rc[qi] = _lib.RangeCount(int(c.field), len(c.ranges), vr)
+        outs[qi].counts = C.cast(counts.ctypes.data + qi * width * 8, C.POINTER(C.c_int64))
+        outs[qi].capacity = width
+    return rc, outs, counts, keep
+
+
+def _range_counts(counters, outs, counts) -> List[RangeCounts]:
+    return [RangeCounts(counts[qi, : len(c.ranges)].copy(), int(o.total_hits), int(o.hits_with_value)) for qi, (c, o) in enumerate(zip(counters, outs))]
+
+
+def _marshal_range_queries(searcher: "GpuIndexSearcher", queries: Sequence[Query], counters: Sequence[RangeCounter], managers):
+    if len(counters) != len(queries):
+        raise ValueError(f"{len(counters)} range counters for {len(queries)} queries")
+    mgrs = list(managers) if managers is not None else [TopScoreDocCollectorManager(1)] * len(queries)
+    return _marshal_counted(searcher, queries, mgrs)
+
+
+def count_ranges_batch(searcher: "GpuIndexSearcher", queries: Sequence[Query], counters: Sequence[RangeCounter],
+                       managers: Optional[Sequence[TopScoreDocCollectorManager]] = None) -> List[RangeCounts]:
+    """Numeric range facets (nrtgpu_count_ranges_batch): per query the hits of queries[i] counted per range of counters[i].  The
+    columns of one call must be of one width ("int" / "float", or "long" / "double").  No hits are returned."""
+    m = _marshal_range_queries(searcher, queries, counters, managers)
+    rc, outs, counts, keep = _marshal_range_counters(counters)
+    _lib.check(_lib.load().nrtgpu_count_ranges_batch(searcher.ctx._h, searcher._segs, searcher._bases, len(searcher.leaves), m.queries, rc, len(queries), outs))
+    del keep
+    return _range_counts(counters, outs, counts)
+
+
+def count_ranges_supported(searcher: "GpuIndexSearcher", query: Query, counter: RangeCounter, manager: Optional[TopScoreDocCollectorManager] = None) -> bool:
+    """The eligibility predicate alone (nrtgpu_count_ranges_supported)."""
+    m = _marshal_range_queries(searcher, [query], [counter], None if manager is None else [manager])
+    rc, _, _, keep = _marshal_range_counters([counter])
+    r = _lib.load().nrtgpu_count_ranges_supported(searcher.ctx._h, searcher._segs, len(searcher.leaves), m.queries, rc)
+    del keep
+    return _supported(r)
+
+
+def count_docset_ranges_batch(searcher: "GpuIndexSearcher", docsets: Sequence[DocSetQuery], counters: Sequence[RangeCounter],
+                              managers: Optional[Sequence[TopScoreDocCollectorManager]] = None) -> List[RangeCounts]:
+    """Numeric range facets over doc sets (nrtgpu_count_docset_ranges_batch): count_ranges_batch's results over a hit set without
+    a text clause."""
+    if len(counters) != len(docsets):
+        raise ValueError(f"{len(counters)} range counters for {len(docsets)} queries")
+    ds, dkeep = _marshal_docsets(docsets, list(managers) if managers is not None else [TopScoreDocCollectorManager(1)] * len(docsets))
+    rc, outs, counts, keep = _marshal_range_counters(counters)
+    _lib.check(_lib.load().nrtgpu_count_docset_ranges_batch(searcher.ctx._h, searcher._segs, searcher._bases, len(searcher.leaves), ds, rc, len(docsets), outs))
+    del keep, dkeep
+    return _range_counts(counters, outs, counts)
+
+
+def count_docset_ranges_supported(searcher: "GpuIndexSearcher", docset: DocSetQuery, counter: RangeCounter,
+                                  manager: Optional[TopScoreDocCollectorManager] = None) -> bool:
+    """The eligibility predicate alone (nrtgpu_count_docset_ranges_supported)."""
+    ds, dkeep = _marshal_docsets([docset], [manager if manager is not None else TopScoreDocCollectorManager(1)])
+    rc, _, _, keep = _marshal_range_counters([counter])
+    r = _lib.load().nrtgpu_count_docset_ranges_supported(searcher.ctx._h, searcher._segs, len(searcher.leaves), ds, rc)
+    del keep, dkeep
+    return _supported(r)
+
+
+def range_cuts(kind: str, ranges: Sequence[Tuple[int, int]]) -> List[int]:
+    """The cut points, as codes of the kind, of a list of (lower_bits, upper_bits) ranges (nrtgpu_range_cuts: the function the host
+    plans with).  No device."""
+    n = len(ranges)
+    vr = (_lib.ValueRange * max(n, 1))(*[_lib.ValueRange(int(lo), int(hi)) for lo, hi in ranges])
+    out = (C.c_uint64 * (2 * _lib.NRTGPU_MAX_COUNT_RANGES))()
+    n_cuts = C.c_int32(0)
+    _lib.check(_lib.load().nrtgpu_range_cuts(ALL_DOC_VALUE_KINDS[kind][0], vr, n, out, C.byref(n_cuts)))
+    return [int(out[i]) for i in range(n_cuts.value)]
+
+
+def range_interval(kind: str, cuts: Sequence[int], value_bits: int) -> int:
+    """The elementary interval of a value among cut points: the number of cuts <= its code (nrtgpu_range_interval: the search the
+    kernels compile).  No device."""
+    arr = (C.c_uint64 * max(len(cuts), 1))(*[int(c) for c in cuts])
+    out = C.c_int32(0)
+    _lib.check(_lib.load().nrtgpu_range_interval(ALL_DOC_VALUE_KINDS[kind][0], arr, len(cuts), C.c_uint64(int(value_bits)), C.byref(out)))
+    return int(out.value)
 
 
 def debug_knn_bounds(sim: int, dim: int, q_norm2: float, q_l1: float, q_absmax: float, nv_max: float, nv_min: float,

@@ -193,7 +193,76 @@ int check_terms(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docs
   return NRTGPU_OK;
 }
 
+// The same of the range-counting entry (rangecount.cpp's records).  out: the batch entry's outputs, nullptr for the predicate.
+int check_ranges(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* docsets, const nrtgpu_range_count* ranges,
+                 const nrtgpu_range_counts* out, int32_t n_queries, DocsetCall* call, RangeWork* work) {
+  for (int qi = 0; qi < n_queries; ++qi) {
+    if (int rc = docset_begin(segs, n_segs, docsets[qi], qi, call)) return rc;
+    if (int rc = range_count_begin(segs, n_segs, ranges[qi], out ? &out[qi] : nullptr, qi, work)) return rc;
+  }
+  for (int qi = 0; qi < n_queries; ++qi) {
+    if (work->kinds[(size_t)qi] < 0) return no_column(qi, ranges[qi].field_id);
+    if (int rc = range_count_column(*work, ranges, qi)) return rc;
+    if (int rc = docset_finish(segs, n_segs, docsets[qi], qi, call)) return rc;
+  }
+  work->layout(ranges, n_queries);
+  work->seal();
+  return NRTGPU_OK;
+}
+
 }  // namespace
+
+extern "C" int nrtgpu_count_docset_ranges_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* d,
+                                                    const nrtgpu_range_count* r) {
+  if (int rc = final_score_enter(ctx, segs, n_segs, !d || !r, nullptr)) return rc;
+  SegReadLocks content(segs, n_segs);
+  DocsetCall call;
+  RangeWork work;
+  if (int rc = check_ranges(segs, n_segs, d, r, nullptr, 1, &call, &work)) return rc;
+  HostPlan hp;
+  return docset_plan(ctx, segs, nullptr, n_segs, call.masks.data(), 1, hp);
+}
+
+extern "C" int nrtgpu_count_docset_ranges_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                                const nrtgpu_docset_query* docsets, const nrtgpu_range_count* ranges, int32_t n_queries,
+                                                nrtgpu_range_counts* out) {
+  if (int rc = final_score_enter(ctx, segs, n_segs, !docsets || !ranges || !out, &n_queries)) return rc;
+  const double t0 = now_ms();
+  SegReadLocks content(segs, n_segs);   // until this call's kernels have finished
+  DocsetCall call;
+  RangeWork work;
+  if (int rc = check_ranges(segs, n_segs, docsets, ranges, out, n_queries, &call, &work)) return rc;
+  HostPlan hp;
+  if (int rc = docset_plan(ctx, segs, doc_bases, n_segs, call.masks.data(), n_queries, hp)) return rc;
+  std::vector<DSortPart> sparts, rparts;   // (the doc set's range clauses' columns are 32-bit ones: docset_parts' walk; the count's are read below)
+  std::vector<int32_t> no_field((size_t)n_queries, -1);
+  docset_parts(segs, docsets, no_field.data(), hp, &sparts, &rparts);
+  for (const DItem& it : hp.items)
+    for (uint32_t pi = 0; pi < it.n_parts; ++pi) {
+      const size_t at = (size_t)it.part_begin + pi;
+      sparts[at] = range_count_column_of(segs[hp.part_leaf[at]], ranges[it.query].field_id, work.wide);
+    }
+  const PlanBytes extras[4] = {{work.plan_bytes.data(), work.plan_bytes.size()},
+                               {call.ranges.data(), call.ranges.size() * sizeof(DRangeQuery)},
+                               {sparts.data(), sparts.size() * sizeof(DSortPart)},
+                               {rparts.data(), rparts.size() * sizeof(DSortPart)}};
+  std::vector<nrtgpu_topdocs> pages((size_t)n_queries, nrtgpu_topdocs{});   // (no hits come back: the merge's lists are empty; total_hits is read from them)
+  const FinalScoreOwn own{work.bytes, range_collect, &work};
+  const FinalScoreLaunch single = [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
+    const RangeWork* w = (const RangeWork*)a.own_user;
+    const char* d_plan = (const char*)d_extra[0];
+    launch_docset_range_count(st, w->wide, false, a, (const DRangeCountQuery*)d_plan, (const DRangeQuery*)d_extra[1], (const DSortPart*)d_extra[2],
+                              (const DSortPart*)d_extra[3], d_plan + (size_t)w->n_queries * sizeof(DRangeCountQuery), (uint32_t*)a.own);
+  };
+  const FinalScoreLaunch multi = [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
+    const RangeWork* w = (const RangeWork*)a.own_user;
+    const char* d_plan = (const char*)d_extra[0];
+    launch_docset_range_count(st, w->wide, true, a, (const DRangeCountQuery*)d_plan, (const DRangeQuery*)d_extra[1], (const DSortPart*)d_extra[2],
+                              (const DSortPart*)d_extra[3], d_plan + (size_t)w->n_queries * sizeof(DRangeCountQuery), (uint32_t*)a.own);
+  };
+  if (int rc = final_score_run(ctx, hp, call.masks.data(), n_queries, pages.data(), t0, extras, 4, call.any_multi ? multi : single, &own)) return rc;
+  return range_unpack(work, ranges, pages.data(), n_queries, out);
+}
 
 extern "C" int nrtgpu_docset_sorted_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* d,
                                               const nrtgpu_field_sort* s) {

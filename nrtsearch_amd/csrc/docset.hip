@@ -7,6 +7,8 @@
 //   docset_terms_count_kernel   the same hit set; every hit with a value adds 1 in the count table under the value's code
 //   docset_sort_multi_kernel, docset_terms_count_multi_kernel   the two for calls that name a MULTI-VALUED column (at the end)
 //   docset_sort64_kernel<MULTI> docset_sort_kernel / docset_sort_multi_kernel over a 64-BIT sort column (plan.h: sort_key64; behind them)
+//   docset_range_count_kernel<WIDE, MULTI>   the same hit set; every hit with a value adds 1 to the elementary interval of its
+//                               code among the query's cut points (nrtgpu_count_docset_ranges_batch; behind the 64-bit sort)
 //
 // The decomposition is the final-score skeleton's (finalscore.hiph): one workgroup of kScanWaves waves per item, a wave takes
 // kTileDocs-doc sub-tiles of the item's parts (final_total_tiles / final_tile), hits per slice through final_count_slice, the
@@ -24,6 +26,8 @@
 // accumulator's slot.  All writes are vector stores and atomics in plain HIP; every loop is bounded by a count known on entry.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "finalscore.hiph"
 #include "termstables.hiph"
@@ -675,6 +679,108 @@ void docset_sort64_kernel(const DItem* __restrict__ items, const DPart* __restri
   }
 
   final_epilogue(s, cnt, k, q, tid, slice_sum, item_keys, item_counts, item_hits, k_stride);
+}
+
+// ---- a numeric range facet over a doc set (plan.h: DRangeCountQuery, range_interval; nrtgpu_count_docset_ranges_batch) -------------
+// docset_terms_count_kernel's frame with rangecount.hip's three replacements: the LDS holds the query's cuts and its n_cuts + 1
+// four-byte interval counters instead of the 64 KiB table; a valued hit's lane searches its code among the LDS cuts and does one
+// 4-byte LDS add; the flush is one global atomicAdd per non-zero counter behind the one barrier.  WIDE: the count column holds
+// 64-bit codes (docset_column64) and the cuts are 64-bit.  MULTI concerns only the doc set's own 32-bit range clauses
+// (docset_hit_set_multi), as in docset_sort64_kernel<MULTI>: the count column is single-valued.  A word without an accepted doc
+// costs no load.
+template <class CODE>
+struct DocsetRangeSmem {
+  CODE cuts[kMaxRangeCuts];                     // the query's cut points, ascending
+  uint32_t counters[kMaxRangeCuts + 1];         // the item's hits per elementary interval, shared by the waves
+  uint32_t slot_hits[kSliceSlots];              // what final_count_slice and the epilogue read (finalscore.hiph: FinalSmem)
+  uint32_t slot_slice[kSliceSlots];
+};
+static_assert(sizeof(DSort64Part) == sizeof(DSortPart), "the count column's record is read as either");
+
+template <bool WIDE, bool MULTI>
+__global__ __launch_bounds__(kScanThreads, kScanWaves / 4)
+void docset_range_count_kernel(const DItem* __restrict__ items, const DPart* __restrict__ parts, const DQuery* __restrict__ queries,
+                               const DRangeCountQuery* __restrict__ cqueries, const DRangeQuery* __restrict__ rqueries,
+                               const DSortPart* __restrict__ sparts, const DSortPart* __restrict__ rparts, const void* __restrict__ cuts_g,
+                               uint32_t* __restrict__ counters_g, uint32_t* __restrict__ slice_sum, uint32_t* __restrict__ item_counts,
+                               uint64_t* __restrict__ item_hits) {
+  typedef typename std::conditional<WIDE, uint64_t, uint32_t>::type CODE;
+  __shared__ DocsetRangeSmem<CODE> s;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)), lane = tid & 63u;
+  const DItem* const item = items + blockIdx.x;
+  const uint32_t query = item->query, part_begin = item->part_begin, n_parts = item->n_parts;
+  const DQuery* const q = queries + query;
+  const DRangeCountQuery* const cq = cqueries + query;
+  const DRangeQuery* const rq = rqueries + query;
+  const uint32_t n_cuts = min(cq->n_cuts, (uint32_t)kMaxRangeCuts);
+  const CODE* const my_cuts = (const CODE*)cuts_g + cq->cut_off;
+  uint32_t* const my_counters = counters_g + cq->counter_off;
+
+  if (tid < n_cuts) s.cuts[tid] = my_cuts[tid];
+  if (tid <= (uint32_t)kMaxRangeCuts) s.counters[tid] = 0u;
+  if (tid < (uint32_t)kSliceSlots) s.slot_hits[tid] = s.slot_slice[tid] = 0u;
+  __syncthreads();
+
+  const uint32_t total_tiles = final_total_tiles(parts, part_begin, n_parts);
+  uint32_t pi = 0;      // the part of the wave's sub-tile (indices only grow)
+
+  for (uint32_t g = wave; g < total_tiles; g += (uint32_t)kScanWaves) {
+    const FinalTile tl = final_tile(parts, part_begin, n_parts, g, pi);
+    const uint32_t base = tl.base;
+    uint32_t words, hits;
+    const DSortPart* const my_rparts = rparts + (size_t)(part_begin + pi) * (size_t)kMaxRanges;
+    const uint32_t m = MULTI ? docset_hit_set_multi(tl.part, rq, my_rparts, base, tl.tile_len, lane, words, hits)
+                             : docset_hit_set(tl.part, rq, my_rparts, base, tl.tile_len, lane, words, hits);
+    if (words == 0u) continue;   // uniform
+    final_count_slice(s, tl.part, lane, hits);
+    CODE cv[kFinalSlots];
+    uint32_t has_bits;
+    bool there;
+    if constexpr (WIDE) there = docset_column64((const DSort64Part*)(sparts + part_begin + pi), base, base >> 6, lane, words, cv, has_bits);
+    else there = docset_column(sparts + part_begin + pi, base, base >> 6, lane, words, cv, has_bits);
+    if (!there) continue;   // uniform: the leaf lacks the column: its hits add to no range
+    const uint32_t valued = m & has_bits;
+#pragma unroll
+    for (int j = 0; j < kFinalSlots; ++j) {
+      if (__ballot(((valued >> j) & 1u) != 0u) == 0ull) continue;   // uniform: no valued hit in the word
+      const uint32_t iv = range_interval(s.cuts, n_cuts, cv[j]);     // (every lane of the word searches: measured against the hit lanes alone, rangecount.hip)
+      if (((valued >> j) & 1u) != 0u) atomicAdd(&s.counters[iv], 1u);
+    }
+  }
+
+  // ---- the item's counters into the query's, once
+  __syncthreads();
+  if (tid <= n_cuts) {
+    const uint32_t c = s.counters[tid];
+    if (c != 0u) atomicAdd(&my_counters[tid], c);
+  }
+
+  // ---- epilogue: final_epilogue's for an item without candidates
+  if (tid == 0) {
+    item_counts[blockIdx.x] = 0u;
+    uint32_t n = 0;
+    const uint32_t gte_floor = q->gte_floor, slice_base = q->slice_base;
+    for (int i = 0; i < kSliceSlots; ++i) {
+      const uint32_t h = s.slot_hits[i];
+      n += h;
+      if (h != 0u && gte_floor != 0xFFFFFFFFu) atomicAdd(&slice_sum[slice_base + s.slot_slice[i]], h);
+    }
+    item_hits[blockIdx.x] = n;
+  }
+}
+
+void launch_docset_range_count(hipStream_t stream, bool wide, bool multi, const FinalScoreArgs& a, const DRangeCountQuery* cqueries,
+                               const DRangeQuery* rqueries, const DSortPart* sparts, const DSortPart* rparts, const void* cuts, uint32_t* counters) {
+  if (a.n_items == 0) return;
+#define NRT_LAUNCH_DOCSET_RANGE_COUNT(W, M)                                                                                                          \
+  hipLaunchKernelGGL((docset_range_count_kernel<W, M>), dim3(a.n_items), dim3(kScanThreads), 0, stream, a.items, a.parts, a.queries, cqueries, rqueries, \
+                     sparts, rparts, cuts, counters, a.slice_sum, a.item_counts, a.item_hits)
+  if (wide && multi) NRT_LAUNCH_DOCSET_RANGE_COUNT(true, true);
+  else if (wide) NRT_LAUNCH_DOCSET_RANGE_COUNT(true, false);
+  else if (multi) NRT_LAUNCH_DOCSET_RANGE_COUNT(false, true);
+  else NRT_LAUNCH_DOCSET_RANGE_COUNT(false, false);
+#undef NRT_LAUNCH_DOCSET_RANGE_COUNT
 }
 
 void launch_docset_sort64(hipStream_t stream, const FinalScoreArgs& a, const DSort64Query* squeries, const DRangeQuery* rqueries, const DSort64Part* sparts,

@@ -880,4 +880,65 @@ __host__ __device__ inline bool value_set_has(P set, uint32_t len, uint32_t code
   return set[base] == code;
 }
 
+// Numeric range facets (rangecount.hip: bm25_range_count_kernel; docset.hip: docset_range_count_kernel; rangecount.cpp): a
+// query's hits counted per requested value range [lower, upper], both inclusive, of a single-valued column of any of the four
+// kinds.  Ranges may overlap, nest, repeat or touch, so the device does not count per range: it counts per ELEMENTARY INTERVAL
+// (Lucene's LongRangeCounter construction [Lucene-recall]).  In code space (doc_value_code / doc_value_code64) the cut points of
+// a query are every non-empty range's lo, and hi + 1 unless hi is the kind's greatest code (range_greatest_code: nothing lies
+// above it), sorted without duplicates: n_cuts <= kMaxRangeCuts.  The interval of a code c is the number of cuts <= c, in
+// 0..n_cuts; a range covers exactly the intervals interval(lo) .. interval(hi), and the host sums their counters.  The per-hit
+// work -- one search, one 4-byte add -- does not depend on how the ranges lie.
+// The ONE statement of the search and of the cut list: both kernels, the host's roll-up, nrtgpu_range_cuts and
+// nrtgpu_range_interval call range_interval / range_cuts.
+constexpr int kMaxCountRanges = 64;                    // NRTGPU_MAX_COUNT_RANGES
+constexpr int kMaxRangeCuts = 2 * kMaxCountRanges;
+// the number of cuts <= code among the ascending, duplicate-free cuts[0 .. n_cuts): a search whose step count depends on n_cuts
+// alone; every index read lies below n_cuts.  A BOUND ends it, not a sentinel: a real code
+// may equal the greatest code, so padding the list with it would miscount.
+template <class P, class T>
+__host__ __device__ inline uint32_t range_interval(P cuts, uint32_t n_cuts, T code) {
+  uint32_t base = 0, n = n_cuts;   // cuts[0 .. base) are all <= code; the answer lies in [base, base + n]; base + n <= n_cuts
+  while (n > 0u) {
+    const uint32_t half = (n + 1u) >> 1;
+    if (cuts[base + half - 1u] <= code) base += half;
+    n -= half;
+  }
+  return base;
+}
+// the greatest code a value of the kind can have: INT_MAX / LONG_MAX for ints, the canonical NaN for floats
+__host__ __device__ inline uint64_t range_greatest_code(int kind) {
+  if (kind == kDocValuesInt32) return 0xFFFFFFFFull;
+  if (kind == kDocValuesFloat32) return 0xFFC00000ull;
+  if (kind == kDocValuesInt64) return 0xFFFFFFFFFFFFFFFFull;
+  return 0xFFF8000000000000ull;
+}
+// the cut list of n_ranges ranges given as codes (lo[i] > hi[i]: an empty range, no cut): out[0 .. return), ascending without
+// duplicates; out holds 2 x n_ranges entries
+template <class T>
+__host__ inline uint32_t range_cuts(const T* lo, const T* hi, uint32_t n_ranges, T greatest, T* out) {
+  uint32_t n = 0;
+  for (uint32_t i = 0; i < n_ranges; ++i) {
+    if (lo[i] > hi[i]) continue;
+    out[n++] = lo[i];
+    if (hi[i] < greatest) out[n++] = (T)(hi[i] + 1);
+  }
+  for (uint32_t i = 1; i < n; ++i) {   // (insertion sort: at most 128 entries)
+    const T v = out[i];
+    uint32_t j = i;
+    for (; j > 0 && out[j - 1] > v; --j) out[j] = out[j - 1];
+    out[j] = v;
+  }
+  uint32_t m = 0;
+  for (uint32_t i = 0; i < n; ++i)
+    if (m == 0 || out[m - 1] != out[i]) out[m++] = out[i];
+  return m;
+}
+struct alignas(16) DRangeCountQuery {
+  uint32_t need;          // clauses a hit matches at least (DSortQuery.need; unread by the doc-set kernel)
+  uint32_t n_cuts;        // 0..kMaxRangeCuts
+  uint32_t cut_off;       // the query's cuts in the call's cut array (uint32 codes, or uint64 for a call over 64-bit columns)
+  uint32_t counter_off;   // the query's n_cuts + 1 interval counters among the call's uint32 counters
+};
+static_assert(sizeof(DRangeCountQuery) == 16, "DRangeCountQuery layout");
+
 }  // namespace nrtgpu

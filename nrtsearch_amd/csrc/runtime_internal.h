@@ -96,6 +96,12 @@ void launch_docset_sort64(hipStream_t stream, const FinalScoreArgs& a, const DSo
                           const DSortPart* rparts);
 void launch_docset_sort64_multi(hipStream_t stream, const FinalScoreArgs& a, const DSort64Query* squeries, const DRangeQuery* rqueries,
                                 const DSort64Part* sparts, const DSortPart* rparts);
+// numeric range facets (rangecount.hip, docset.hip): one DRangeCountQuery per query, the call's cut array (uint32 codes, or uint64
+// when `wide`), one DSortPart per part whose `code` is the count column at that width, the call's uint32 interval counters
+void launch_bm25_range_count(hipStream_t stream, bool wide, const FinalScoreArgs& a, const DRangeCountQuery* rqueries, const DSortPart* sparts,
+                             const void* cuts, uint32_t* counters);
+void launch_docset_range_count(hipStream_t stream, bool wide, bool multi, const FinalScoreArgs& a, const DRangeCountQuery* cqueries,
+                               const DRangeQuery* rqueries, const DSortPart* sparts, const DSortPart* rparts, const void* cuts, uint32_t* counters);
 #ifdef NRTGPU_DEV
 void launch_debug_wave_kth(hipStream_t stream, const uint64_t* keys, uint32_t n, uint32_t r, uint64_t* out);   // (maxscore.hip: topk_kth_wave on its own)
 void launch_debug_walk_value(hipStream_t stream, float weight, const uint32_t* freq, const uint32_t* norm, const float* table, int fx_scale,
@@ -1275,6 +1281,35 @@ int terms_count_record(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtg
 int terms_collect(nrtgpu_ctx* ctx, Slot* slot, const char* d_own, void* user);
 // the call's answers from what terms_collect brought back and the merge's (empty) lists
 int terms_unpack(const TermsWork& work, const std::vector<int>& kinds, const nrtgpu_topdocs* pages, int32_t n_queries, nrtgpu_term_counts* out);
+
+// rangecount.cpp: what the routes that count value ranges share (a text query's hits there; a doc set's in docset.cpp).
+// The call's records, cut array and interval counters: what goes into the plan buffer (the DRangeCountQuery records, then the
+// queries' cuts at the call's column width), the route's own workspace bytes (the uint32 counters), and what comes back from them.
+struct RangeWork {
+  int32_t n_queries = 0;
+  bool wide = false;                        // the call's columns hold 64-bit codes
+  size_t bytes = 0;                         // FinalScoreOwn.work_bytes: 4 per counter
+  std::vector<int> kinds;                   // per query: range_count_begin()
+  std::vector<char> multi;
+  std::vector<DRangeCountQuery> records;    // layout(); the caller fills `need`, then seal() copies them into plan_bytes
+  std::vector<char> plan_bytes;
+  std::vector<uint32_t> counters;           // range_collect()
+  void layout(const nrtgpu_range_count* ranges, int32_t n_queries);
+  void seal();
+  uint32_t interval_of(const DRangeCountQuery& r, uint64_t code) const;   // among r's cuts, at the call's width
+};
+// what both refuse of (ranges[qi], out[qi]) as an invalid argument (out: nullptr for the predicates); the column's kind and arity
+// over the leaves are pushed
+int range_count_begin(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_range_count& r, const nrtgpu_range_counts* out, int qi, RangeWork* work);
+// what both refuse of query qi's count column as unsupported, where it is on some leaf: a multi-valued one, a width other than
+// an earlier query's
+int range_count_column(const RangeWork& work, const nrtgpu_range_count* ranges, int qi);
+// the count column on one leaf as the kernels read it (DSortPart.code: the column at the call's width)
+DSortPart range_count_column_of(const nrtgpu_seg* seg, int32_t field_id, bool wide);
+// FinalScoreOwn.collect of both (user: the call's RangeWork): exactly the counters that exist
+int range_collect(nrtgpu_ctx* ctx, Slot* slot, const char* d_own, void* user);
+// the roll-up of the interval counters into the ranges, total_hits from the merge's (empty) lists
+int range_unpack(const RangeWork& work, const nrtgpu_range_count* ranges, const nrtgpu_topdocs* pages, int32_t n_queries, nrtgpu_range_counts* out);
 
 }  // namespace rt
 }  // namespace nrtgpu
