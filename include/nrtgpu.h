@@ -1130,7 +1130,9 @@ int  nrtgpu_sort_value_code(int32_t kind, int32_t reverse, uint32_t value_bits, 
  * min_should_match, duplicates counting each, accept sets), the exact total_hits and the per-slice relation rule, slicing, thread
  * slices, deadlines, items_scan, scan_*; a doc without a value, or in a leaf without the column, sorts AS and reports
  * missing_bits (the reference's missing values are Long.MIN_VALUE / MAX_VALUE and -+inf: LongFieldDef.java:103-105,
- * DoubleFieldDef.java:105-107); a NaN comes back as 0x7FF8000000000000.  The cursor (has_after, after_doc, after_bits) is tested
+ * DoubleFieldDef.java:105-107); EVERY NaN a sort reports is 0x7FF8000000000000, a column's and a NaN missing value's alike, whatever
+ * its payload and whether or not the column holds a NaN (the 32-bit route's rule: its key holds the whole code).
+ * The cursor (has_after, after_doc, after_bits) is tested
  * on values: a hit is collected iff (its value, its docid) ranks strictly behind (after_bits, after_doc) in the sort's order.
  * ONE PASS through the unchanged top-k: the keys stay 64 bits.  Per query, D is the maximum of doc_bases[i] + max_doc[i] over the
  * leaves, db = max(1, bit_length(D - 1)) the bits its global docids need, [lo, hi] the least and the greatest CODE of the sort's
@@ -1149,13 +1151,14 @@ int  nrtgpu_sort_value_code(int32_t kind, int32_t reverse, uint32_t value_bits, 
  *                           bits the column's span needs and the bits the call's docids leave ("span needs 41 bits, 26-bit docids
  *                           leave 38"); a doc_bases[i] + max_doc[i] beyond 2^31
  * The text route keeps the final-score routes' flag and fixed-point refusals (the known limit).
- * Out of scope: DOUBLE columns whose values span more than the key leaves (two doubles of different sign never fit); a second
- * sort level; terms counts over 64-bit columns; multi-valued 64-bit columns; the Java shim, which does not bind this yet.
+ * Out of scope: DOUBLE columns whose values span more than the key leaves (two doubles of different sign do not fit, but for
+ * -0.0 beside +0.0: a span of 1); a second sort level; terms counts over 64-bit columns; multi-valued 64-bit columns; the Java shim, which does not bind this yet.
  * --------------------------------------------------------------------------------------------- */
 typedef struct {
   int32_t  field_id;      /* the column */
   int32_t  reverse;       /* 0 ascending, 1 descending */
-  uint64_t missing_bits;  /* what a doc without a value sorts AS, bits of the column's kind, taken verbatim */
+  uint64_t missing_bits;  /* what a doc without a value sorts AS, bits of the column's kind: any value of the kind, inside the
+                           * column's window or not; reported as given, a NaN as the canonical one */
   int32_t  has_after;     /* FieldDoc searchAfter */
   int32_t  after_doc;     /* global docid */
   uint64_t after_bits;    /* the last hit's sort value */

@@ -360,7 +360,7 @@ extern "C" int nrtgpu_search_docset_sorted64_batch(nrtgpu_ctx* ctx, const nrtgpu
   for (int qi = 0; qi < n_queries; ++qi) ks[(size_t)qi] = docsets[qi].k;
   Sort64Pages pages(ks.data(), out, n_queries);
   if (int rc = final_score_run(ctx, hp, call.masks.data(), n_queries, pages.pages.data(), t0, extras, 4, call.any_multi ? multi : single)) return rc;
-  pages.decode(records, kinds, sorts, out);
+  pages.decode(records, kinds, out);
   return NRTGPU_OK;
 }
 

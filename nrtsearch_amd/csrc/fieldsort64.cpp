@@ -112,7 +112,7 @@ Sort64Pages::Sort64Pages(const int32_t* ks, const nrtgpu_fielddocs64* out, int32
   }
 }
 
-void Sort64Pages::decode(const std::vector<DSort64Query>& records, const std::vector<int>& kinds, const nrtgpu_field_sort64* sorts, nrtgpu_fielddocs64* out) const {
+void Sort64Pages::decode(const std::vector<DSort64Query>& records, const std::vector<int>& kinds, nrtgpu_fielddocs64* out) const {
   for (size_t qi = 0; qi < pages.size(); ++qi) {
     const nrtgpu_topdocs& p = pages[qi];
     const DSort64Query& r = records[qi];
@@ -128,7 +128,7 @@ void Sort64Pages::decode(const std::vector<DSort64Query>& records, const std::ve
       uint64_t u;
       sort_key64_decode(r.reverse, r.span, r.db, key, &doc, &u);
       if (o.docs) o.docs[i] = (int32_t)doc;
-      if (o.value_bits) o.value_bits[i] = (u == 0ull || u == r.span + 2ull) ? sorts[qi].missing_bits : doc_value_bits64(kinds[qi], r.lo + (u - 1ull));
+      if (o.value_bits) o.value_bits[i] = doc_value_bits64(kinds[qi], (u == 0ull || u == r.span + 2ull) ? r.missing_code : r.lo + (u - 1ull));
     }
   }
 }
@@ -213,6 +213,6 @@ extern "C" int nrtgpu_search_sorted64_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* c
         launch_bm25_field_sort64(st, a, (const DSort64Query*)d_extra[0], (const DSort64Part*)d_extra[1]);
       }))
     return rc;
-  pages.decode(records, kinds, sorts, out);
+  pages.decode(records, kinds, out);
   return NRTGPU_OK;
 }

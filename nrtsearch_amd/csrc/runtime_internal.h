@@ -1254,13 +1254,13 @@ int field_sort64_record(const nrtgpu_seg* const* segs, int32_t n_segs, const nrt
 DSort64Part doc_values_column64(const nrtgpu_seg* seg, int32_t field_id);
 // The internal pages final_score_run fills for such a call (ks: the queries' numHits; capacities: the caller's) and their decode
 // into the caller's pages: key = high << 32 | (0xFFFFFFFF - doc), then plan.h: sort_key64_decode; a sentinel ordinal is the
-// sort's missing_bits verbatim.
+// sort's missing value, reported like every value through doc_value_bits64 (a NaN comes back canonical).
 struct Sort64Pages {
   std::vector<nrtgpu_topdocs> pages;
   std::vector<int32_t> docs;
   std::vector<float> highs;
   Sort64Pages(const int32_t* ks, const nrtgpu_fielddocs64* out, int32_t n_queries);
-  void decode(const std::vector<DSort64Query>& records, const std::vector<int>& kinds, const nrtgpu_field_sort64* sorts, nrtgpu_fielddocs64* out) const;
+  void decode(const std::vector<DSort64Query>& records, const std::vector<int>& kinds, nrtgpu_fielddocs64* out) const;
 };
 
 // termscount.cpp: what the routes that fill count tables share (a text query's hits there; a doc set's in docset.cpp).

@@ -3,7 +3,8 @@ independent of the library's coding of the values and of its packed keys: the or
 on Python / NumPy integers, which docs match is counted from the corpus postings (tests/_field_sort_ref.py: clause_counts) or
 taken from a doc set's accept words and 32-bit range clauses, the relation follows the per-slice rule over api.slices.
 
-  value     the doc's column value; a doc without one, or in a leaf without the column, takes the sort's missing value
+  value     the doc's column value; a doc without one, or in a leaf without the column, takes the sort's missing value; every NaN
+            is reported as 0x7FF8000000000000, a NaN missing value included
   order     value ascending (reverse: descending), equal values by global docid ascending in both directions
   page      the first k hits strictly behind the cursor (after value, after doc); total_hits counts the hits of every page
   relation  GREATER_THAN_OR_EQUAL_TO iff some slice holds more than max(total_hits_threshold, k) hits and k hits were returned
@@ -112,6 +113,7 @@ def search(corpus, hits: Sequence[np.ndarray], columns: Sequence[Optional[Tuple[
     """-> (docs int32, value_bits uint64, total_hits, relation_gte).  hits[leaf]: bool per doc; columns[leaf]: None (the leaf
     lacks the column) or (docs or None = every doc, value bits uint64); after: (global doc, value bits)."""
     all_docs, all_bits, per_leaf = [], [], []
+    missing_bits = int(canonical_bits(kind, [missing_bits])[0])   # (every NaN a sort reports is canonical, the missing value included)
     for si, seg in enumerate(corpus.segments):
         vals = np.full(seg.max_doc, missing_bits, dtype=np.uint64)
         if columns[si] is not None:
