@@ -166,11 +166,13 @@ int  nrtgpu_segment_add_doc_values_multi(nrtgpu_seg* seg, int32_t field_id, int3
  * padded to whole sub-tiles, plus the `has` words where some doc lacks a value; the least and the greatest code of the column
  * stay on the segment (a column with n == 0 has none): the window a sort packs its keys in.  Codes compare like Long.compare /
  * Double.compare: -0.0 < +0.0, every NaN the canonical 0x7FF8000000000000 and above +inf.
- * Readers: nrtgpu_search_sorted64_batch, nrtgpu_search_docset_sorted64_batch, nrtgpu_segment_set_mask_from_values64.  The 32-bit
+ * Readers: nrtgpu_search_sorted64_batch, nrtgpu_search_docset_sorted64_batch, nrtgpu_segment_set_mask_from_values64,
+ * nrtgpu_count_ranges_batch, nrtgpu_count_terms64_batch, nrtgpu_count_docset_terms64_batch.  The 32-bit
  * entries (nrtgpu_search_sorted_batch, nrtgpu_count_terms_batch, the doc-set entries' sort, count and range clauses,
  * nrtgpu_segment_set_mask_from_values) refuse a field that holds a 64-bit column with NRTGPU_ERR_UNSUPPORTED, the reason naming
- * the 64-bit entry (terms counts: 64-bit buckets are not built); the 64-bit entries refuse a 32-bit or multi-valued column the
- * same way.  Neither reads a column at the other width.  Out of scope: multi-valued 64-bit columns, terms counts and doc-set
+ * the 64-bit entry (terms counts: 64-bit buckets are not built by the 32-bit entries, nrtgpu_count_terms64_batch /
+ * nrtgpu_count_docset_terms64_batch build them); the 64-bit entries refuse a 32-bit or multi-valued column the
+ * same way.  Neither reads a column at the other width.  Out of scope: multi-valued 64-bit columns, doc-set
  * range CLAUSES over 64-bit columns (a range over one is a built mask), updatable doc values. */
 #define NRTGPU_DOCVALUES_INT64   2  /* LongFieldDef, DateTimeFieldDef (epoch millis): SortField.Type.LONG */
 #define NRTGPU_DOCVALUES_FLOAT64 3  /* DoubleFieldDef: SortField.Type.DOUBLE */
@@ -1232,7 +1234,8 @@ int  nrtgpu_sort_key64(int32_t kind, int32_t reverse, uint64_t lo_bits, uint64_t
  *                           context with NRTGPU_FLAG_PACKED_POSTINGS or NRTGPU_FLAG_NO_FIXED_POINT, a batch whose queries do
  *                           not all pass the fixed-point analysis -- the final-score routes' refusals, the KNOWN LIMIT they are
  *                           on the sorted route
- * Out of scope: LONG / DOUBLE columns; string collectors as such (a string facet, SORTED_SET or single-valued, is uploaded as an
+ * A LONG / DATE_TIME / DOUBLE column is counted by nrtgpu_count_terms64_batch below.
+ * Out of scope: string collectors as such (a string facet, SORTED_SET or single-valued, is uploaded as an
  * INT32 column of its global ordinals -- multi-valued where the field is -- and its keys mapped back by the caller); script and
  * virtual sources; nested collectors and NESTED_COLLECTOR order; the
  * Filter / Min / Max / Sum / TopHits collectors; fusing the count into a scoring route; dismax and multi-match text (a match-all
@@ -1305,8 +1308,8 @@ int  nrtgpu_count_terms_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs
  *   NRTGPU_ERR_UNSUPPORTED  the sort or count column, or a range clause's column, is resident on no leaf of the call (its kind is
  *                           then unknown, and a forgotten upload must not read as "no hits"); a sort column that is multi-valued
  *                           (upload the selector's pick); a mask that is not resident
- * A sort by a LONG / DATE_TIME / DOUBLE column is nrtgpu_search_docset_sorted64_batch below; range clauses and counts over such
- * columns stay out of scope (a range over one is a built mask).  Out of scope: sorting by a multi-valued column; a score-ordered match-all; skipping whole
+ * A sort by a LONG / DATE_TIME / DOUBLE column is nrtgpu_search_docset_sorted64_batch below, a count over one
+ * nrtgpu_count_docset_terms64_batch; range clauses over such columns stay out of scope (a range over one is a built mask).  Out of scope: sorting by a multi-valued column; a score-ordered match-all; skipping whole
  * tiles by per-tile minima and maxima of a column (zone maps); the coalesced, device-resident and nrtgpu_dist_* forms; the Java
  * shim, which keeps sending these requests to Lucene until it binds this.  (A range, an in-set or an exists clause beside a text
  * query, a kNN query or any other route is a resident mask built from the column: nrtgpu_segment_set_mask_from_values.)
@@ -1358,6 +1361,69 @@ int  nrtgpu_count_docset_terms_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* cons
 /* Whether a range clause keeps a doc whose value is value_bits (kind: NRTGPU_DOCVALUES_*; *out = 1 / 0), exposed for the tests:
  * needs no device; it is the very function the kernels compile.  kind outside 0..1 or out NULL: NRTGPU_ERR_INVALID_ARG. */
 int  nrtgpu_range_accepts(int32_t kind, uint32_t lower_bits, uint32_t upper_bits, uint32_t value_bits, int32_t* out);
+
+/* ---------------------------------------------------------------------------------------------
+ * Terms aggregation over a 64-BIT column: a query's hits counted per distinct value of a LONG / DATE_TIME (epoch millis) /
+ * DOUBLE doc value column (nrtgpu_segment_add_doc_values64) -- a facet on a business id, on a price stored as a double, on a day
+ * bucket kept as a long.  The reference's TermsCollectorManager.buildManager (TermsCollectorManager.java:116-152) picks
+ * LongTermsCollectorManager / DoubleTermsCollectorManager for such a field; their per-hit half is countsMap.addTo(value, 1) for
+ * every value of every collected doc (LongTermsCollectorManager.java:145-148, DoubleTermsCollectorManager.java:147-150).
+ * nrtgpu_count_terms64_batch is nrtgpu_count_terms_batch, and nrtgpu_count_docset_terms64_batch is
+ * nrtgpu_count_docset_terms_batch, word for word over the same hit sets: the matching rule; a hit without a value, or in a leaf
+ * that lacks the column, adds to no bucket; the exact total_hits; hits_with_value; overflowed exactly when the hits hold more than
+ * max_buckets distinct values, the other queries of the batch unaffected; slicing, thread slices, deadlines, diagnostics and
+ * statistics; the context flags each form runs under; the refusal tables with their statuses, and every NRTGPU_ERR_INVALID_ARG
+ * check of ALL queries before any NRTGPU_ERR_UNSUPPORTED one.  nrtgpu_terms_count (field id, max_buckets in
+ * 1..NRTGPU_MAX_TERM_BUCKETS) is reused as it is.  The count column is single-valued (no multi-valued 64-bit upload exists); the
+ * doc set's own `ranges` stay 32-bit clauses over 32-bit columns of either arity.
+ * Bucket identity is the identity of the column's code: LONG / DATE_TIME are bucketed by value, DOUBLE by
+ * Double.doubleToLongBits -- every NaN, whatever its payload or sign, falls in ONE bucket and reports as 0x7FF8000000000000,
+ * -0.0 and +0.0 are TWO buckets (fastutil's Double2IntOpenHashMap equality [Lucene-recall: never checked against a JVM run]).
+ * Output order: buckets ascending in the kind's order (Long.compare / Double.compare: -0.0 < +0.0, NaN above +inf), whatever
+ * order the device filled its tables in.  A batch may mix LONG and DOUBLE columns among its queries.
+ * Every 64-bit pattern is a value here: Long.MIN_VALUE and Long.MAX_VALUE are buckets like any other.
+ * Workspace bound (a design limit): a query's device table has the power of two >= 2 x max_buckets slots (at least 2); a slot
+ * is 12 bytes (an 8-byte key and a 4-byte count), and the tables of ONE call keep the 32-bit entry's 256 MiB:
+ * NRTGPU_TERMS64_MAX_CALL_SLOTS = 2^28 / 12 = 22369621 slots in all -- 170 queries may ask for the full 65536 buckets each.  A
+ * call beyond it is NRTGPU_ERR_INVALID_ARG, the reason naming the limit.
+ * Width refusals: these entries over a 32-bit column, single- or multi-valued, return NRTGPU_ERR_UNSUPPORTED with a reason that
+ * names nrtgpu_count_terms_batch / nrtgpu_count_docset_terms_batch; the 32-bit entries over a 64-bit column keep refusing with
+ * NRTGPU_ERR_UNSUPPORTED and now name these.
+ * Out of scope: multi-valued 64-bit columns; range clauses over 64-bit columns inside a doc set (a built mask serves them);
+ * nested collectors and NESTED_COLLECTOR order; script and virtual sources; the coalesced, device-resident and nrtgpu_dist_*
+ * forms; the Java shim, which keeps sending these requests to Lucene.
+ * --------------------------------------------------------------------------------------------- */
+#define NRTGPU_TERMS64_LDS_SLOTS 8192              /* slots of a workgroup's LDS table (nrtgpu_terms_home_slots64) */
+#define NRTGPU_TERMS64_MAX_CALL_SLOTS 22369621     /* table slots of one call, summed over its queries: 2^28 / 12 */
+typedef struct {
+  int32_t   n_buckets;        /* out: buckets written (0 when overflowed) */
+  int32_t   capacity;         /* in : capacity of value_bits / counts, >= max_buckets */
+  uint64_t* value_bits;       /* out: the buckets' values, bits of the column's kind, ascending in the kind's order */
+  int32_t*  counts;           /* out: hits per bucket, each >= 1 */
+  int64_t   total_hits;       /* out: live matching docs, exact */
+  int64_t   hits_with_value;  /* out: the sum of counts; -1 when overflowed */
+  int32_t   overflowed;       /* out: 1 == more than max_buckets distinct values */
+  int32_t   reserved;         /* out: 0 */
+} nrtgpu_term_counts64;       /* 48 bytes */
+/* n_queries count maps over the same leaves in one device pass; terms[i] names the 64-bit column and the bound of queries[i] */
+int  nrtgpu_count_terms64_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                const nrtgpu_bm25_query* queries, const nrtgpu_terms_count* terms, int32_t n_queries,
+                                nrtgpu_term_counts64* out);
+/* The eligibility test alone (with an output of sufficient capacity).  No device work. */
+int  nrtgpu_count_terms64_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query* q,
+                                    const nrtgpu_terms_count* t);
+/* the same over doc sets */
+int  nrtgpu_count_docset_terms64_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                       const nrtgpu_docset_query* docsets, const nrtgpu_terms_count* terms, int32_t n_queries,
+                                       nrtgpu_term_counts64* out);
+int  nrtgpu_count_docset_terms64_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* d,
+                                           const nrtgpu_terms_count* t);
+/* The home slots of a value in the device's count tables, exposed for the tests: needs no device; it is the very function the
+ * kernels compile.  *lds_slot: in a workgroup's table, below NRTGPU_TERMS64_LDS_SLOTS; *table_slot: in a query's table of
+ * max_buckets, below the power of two >= 2 x max_buckets.  Probing from there is linear: 8 slots in the workgroup's table (then
+ * the value goes to the query's table), the whole table in the query's.  The hash mixes both halves of the value's code.
+ * kind outside 2..3, max_buckets outside 1..NRTGPU_MAX_TERM_BUCKETS or a NULL output: NRTGPU_ERR_INVALID_ARG. */
+int  nrtgpu_terms_home_slots64(int32_t kind, uint64_t value_bits, int32_t max_buckets, uint32_t* lds_slot, uint32_t* table_slot);
 
 /* ---------------------------------------------------------------------------------------------
  * Numeric range facets: a query's hits counted per requested value range of a single-valued doc value column -- "under 10,

@@ -40,6 +40,8 @@ NRTGPU_DOCVALUES_FLOAT32 = 1
 NRTGPU_DOCVALUES_INT64 = 2
 NRTGPU_DOCVALUES_FLOAT64 = 3
 NRTGPU_MAX_TERM_BUCKETS = 65536
+NRTGPU_TERMS64_LDS_SLOTS = 8192
+NRTGPU_TERMS64_MAX_CALL_SLOTS = (1 << 28) // 12
 NRTGPU_MAX_RANGES = 4
 NRTGPU_MAX_COUNT_RANGES = 64
 NRTGPU_CLAUSE_RANGE = 0
@@ -80,6 +82,8 @@ ABI_SYMBOLS = [
     "nrtgpu_search_docset_sorted64_batch", "nrtgpu_docset_sorted64_supported", "nrtgpu_segment_set_mask_from_values64", "nrtgpu_range_accepts64",
     "nrtgpu_count_ranges_batch", "nrtgpu_count_ranges_supported", "nrtgpu_count_docset_ranges_batch", "nrtgpu_count_docset_ranges_supported",
     "nrtgpu_range_cuts", "nrtgpu_range_interval",
+    "nrtgpu_count_terms64_batch", "nrtgpu_count_terms64_supported", "nrtgpu_count_docset_terms64_batch",
+    "nrtgpu_count_docset_terms64_supported", "nrtgpu_terms_home_slots64",
 ]
 # what include/nrtgpu_dev.h adds: test hooks and measurement helpers of the development library (libnrtgpu_dev.so) only
 DEV_SYMBOLS = [
@@ -174,6 +178,11 @@ class TermsCount(C.Structure):   # nrtgpu_terms_count
 
 class TermCounts(C.Structure):   # nrtgpu_term_counts
     _fields_ = [("n_buckets", C.c_int32), ("capacity", C.c_int32), ("value_bits", C.POINTER(C.c_uint32)), ("counts", C.POINTER(C.c_int32)),
+                ("total_hits", C.c_int64), ("hits_with_value", C.c_int64), ("overflowed", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TermCounts64(C.Structure):   # nrtgpu_term_counts64
+    _fields_ = [("n_buckets", C.c_int32), ("capacity", C.c_int32), ("value_bits", C.POINTER(C.c_uint64)), ("counts", C.POINTER(C.c_int32)),
                 ("total_hits", C.c_int64), ("hits_with_value", C.c_int64), ("overflowed", C.c_int32), ("reserved", C.c_int32)]
 
 
@@ -344,6 +353,11 @@ def _open(path: str) -> C.CDLL:
     L.nrtgpu_count_docset_ranges_supported.argtypes = [vp, vp, i32, C.POINTER(DocsetQuery), C.POINTER(RangeCount)]
     L.nrtgpu_range_cuts.argtypes = [i32, C.POINTER(ValueRange), i32, vp, vp]
     L.nrtgpu_range_interval.argtypes = [i32, vp, i32, u64, vp]
+    L.nrtgpu_count_terms64_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(TermsCount), i32, C.POINTER(TermCounts64)]
+    L.nrtgpu_count_terms64_supported.argtypes = [vp, vp, i32, C.POINTER(Bm25Query), C.POINTER(TermsCount)]
+    L.nrtgpu_count_docset_terms64_batch.argtypes = [vp, vp, vp, i32, C.POINTER(DocsetQuery), C.POINTER(TermsCount), i32, C.POINTER(TermCounts64)]
+    L.nrtgpu_count_docset_terms64_supported.argtypes = [vp, vp, i32, C.POINTER(DocsetQuery), C.POINTER(TermsCount)]
+    L.nrtgpu_terms_home_slots64.argtypes = [i32, u64, i32, vp, vp]
     L.nrtgpu_rescore_vectors.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, f32, vp, vp, i32, C.c_double, C.c_double, i32,
                                          C.POINTER(TopDocs)]
     L.nrtgpu_search_hybrid_batch.argtypes = [vp, vp, vp, i32, C.POINTER(Bm25Query), i32, i32, i32, vp, i32, f32,

@@ -1450,7 +1450,8 @@ class TermsCollector:
     """A TermsCollector over an int or float field (source FIELD, order COUNT, no nested collectors): `field` names the doc value
     column of kind `kind` -- single-valued (GpuSegment.add_doc_values) or multi-valued (add_doc_values_multi: every value instance
     of a hit counts, as for a SORTED_SET facet uploaded as its global ordinals); `size` and `order_desc` are what the caller's reduce() applies
-    to the returned map (fill_bucket_result), the device does not read them."""
+    to the returned map (fill_bucket_result), the device does not read them.  kind "long" / "double": a collector over a single-valued
+    64-bit column (add_doc_values64), for count_terms64_batch / count_docset_terms64_batch."""
 
     field: int
     size: int
@@ -1905,6 +1906,111 @@ def range_accepts64(kind: str, lower_bits: int, upper_bits: int, value_bits: int
     _lib.check(_lib.load().nrtgpu_range_accepts64(DOC_VALUE_KINDS64[kind][0], C.c_uint64(int(lower_bits)), C.c_uint64(int(upper_bits)),
                                                   C.c_uint64(int(value_bits)), C.byref(out)))
     return bool(out.value)
+
+
+# ---- terms aggregation over 64-bit columns: TermsCollector(kind="long" / "double") ---------------------------------------------
+@dataclasses.dataclass
+class TermCounts64:
+    """TermCounts over a LONG / DATE_TIME / DOUBLE column (nrtgpu_term_counts64): the distinct values of the hits, ascending in
+    the kind's order (Long.compare / Double.compare), and the hits per value; overflowed as there."""
+
+    values: np.ndarray          # int64 / float64 (a NaN bucket reads 0x7FF8000000000000)
+    counts: np.ndarray          # int32
+    total_hits: int
+    hits_with_value: int
+    overflowed: bool
+
+    @property
+    def value_bits(self) -> np.ndarray:
+        return self.values.view(np.uint64)
+
+
+class _TermOutputs64:
+    """The nrtgpu_term_counts64 of a call: rows of a uint64 and an int32 array."""
+
+    def __init__(self, bounds):
+        n, width = len(bounds), max([max(b, 1) for b in bounds], default=1)
+        self.outs = (_lib.TermCounts64 * n)()
+        self.bits = np.zeros((n, width), dtype=np.uint64)
+        self.counts = np.zeros((n, width), dtype=np.int32)
+        for qi in range(n):
+            self.outs[qi].capacity = max(bounds[qi], 0)
+            self.outs[qi].value_bits = C.cast(self.bits.ctypes.data + qi * width * 8, C.POINTER(C.c_uint64))
+            self.outs[qi].counts = C.cast(self.counts.ctypes.data + qi * width * 4, C.POINTER(C.c_int32))
+
+    def lists(self, collectors) -> List[TermCounts64]:
+        return [TermCounts64(self.bits[qi, : o.n_buckets].copy().view(DOC_VALUE_KINDS64[c.kind][1]), self.counts[qi, : o.n_buckets].copy(),
+                             int(o.total_hits), int(o.hits_with_value), bool(o.overflowed)) for qi, (o, c) in enumerate(zip(self.outs, collectors))]
+
+
+def _terms64(collectors: Sequence[TermsCollector], max_buckets, n: int):
+    """The nrtgpu_terms_count per query of a count over 64-bit columns, and the bounds."""
+    if len(collectors) != n:
+        raise ValueError(f"{len(collectors)} collectors for {n} queries")
+    bounds = [int(max_buckets)] * n if np.isscalar(max_buckets) else [int(b) for b in max_buckets]
+    if len(bounds) != n:
+        raise ValueError(f"{len(bounds)} max_buckets for {n} queries")
+    for c in collectors:
+        if c.kind not in DOC_VALUE_KINDS64:
+            raise UnsupportedQuery(f"a 64-bit terms collector of kind {c.kind!r}")
+    tc = (_lib.TermsCount * n)(*[_lib.TermsCount(int(c.field), b) for c, b in zip(collectors, bounds)])
+    return tc, bounds
+
+
+def _marshal_terms64(searcher: "GpuIndexSearcher", queries: Sequence[Query], collectors: Sequence[TermsCollector], max_buckets, managers):
+    n = len(queries)
+    tc, bounds = _terms64(collectors, max_buckets, n)
+    mgrs = list(managers) if managers is not None else [TopScoreDocCollectorManager(1)] * n
+    m = _marshal_counted(searcher, queries, mgrs)
+    m.keep.append(tc)
+    return m, tc, bounds
+
+
+def count_terms64_batch(searcher: "GpuIndexSearcher", queries: Sequence[Query], collectors: Sequence[TermsCollector], max_buckets=4096,
+                        managers: Optional[Sequence[TopScoreDocCollectorManager]] = None) -> List[TermCounts64]:
+    """Terms aggregations over 64-bit columns (nrtgpu_count_terms64_batch): count_terms_batch's results with int64 / float64
+    values; collectors[i].kind is "long" (LONG, DATE_TIME as epoch millis) or "double".  A batch may mix the two."""
+    m, tc, bounds = _marshal_terms64(searcher, queries, collectors, max_buckets, managers)
+    h = _TermOutputs64(bounds)
+    _lib.check(_lib.load().nrtgpu_count_terms64_batch(searcher.ctx._h, searcher._segs, searcher._bases, len(searcher.leaves), m.queries, tc, len(queries), h.outs))
+    return h.lists(collectors)
+
+
+def count_terms64_supported(searcher: "GpuIndexSearcher", query: Query, collector: TermsCollector, max_buckets: int = 4096,
+                            manager: Optional[TopScoreDocCollectorManager] = None) -> bool:
+    """The eligibility predicate alone (nrtgpu_count_terms64_supported)."""
+    m, tc, _ = _marshal_terms64(searcher, [query], [collector], max_buckets, None if manager is None else [manager])
+    return _supported(_lib.load().nrtgpu_count_terms64_supported(searcher.ctx._h, searcher._segs, len(searcher.leaves), m.queries, tc))
+
+
+def count_docset_terms64_batch(searcher: "GpuIndexSearcher", docsets: Sequence[DocSetQuery], collectors: Sequence[TermsCollector], max_buckets=4096,
+                               managers: Optional[Sequence[TopScoreDocCollectorManager]] = None) -> List[TermCounts64]:
+    """Terms aggregations over 64-bit columns and doc sets (nrtgpu_count_docset_terms64_batch)."""
+    n = len(docsets)
+    tc, bounds = _terms64(collectors, max_buckets, n)
+    ds, keep = _marshal_docsets(docsets, list(managers) if managers is not None else [TopScoreDocCollectorManager(1)] * n)
+    h = _TermOutputs64(bounds)
+    _lib.check(_lib.load().nrtgpu_count_docset_terms64_batch(searcher.ctx._h, searcher._segs, searcher._bases, len(searcher.leaves), ds, tc, n, h.outs))
+    del keep
+    return h.lists(collectors)
+
+
+def count_docset_terms64_supported(searcher: "GpuIndexSearcher", docset: DocSetQuery, collector: TermsCollector, max_buckets: int = 4096,
+                                   manager: Optional[TopScoreDocCollectorManager] = None) -> bool:
+    """The eligibility predicate alone (nrtgpu_count_docset_terms64_supported)."""
+    tc, _ = _terms64([collector], max_buckets, 1)
+    ds, keep = _marshal_docsets([docset], [manager if manager is not None else TopScoreDocCollectorManager(1)])
+    rc = _lib.load().nrtgpu_count_docset_terms64_supported(searcher.ctx._h, searcher._segs, len(searcher.leaves), ds, tc)
+    del keep
+    return _supported(rc)
+
+
+def terms_home_slots64(kind: str, value_bits: int, max_buckets: int) -> Tuple[int, int]:
+    """The home slots of a value in a workgroup's count table and in a query's table of max_buckets (nrtgpu_terms_home_slots64:
+    the function the kernels compile).  No device."""
+    lds, table = C.c_uint32(0), C.c_uint32(0)
+    _lib.check(_lib.load().nrtgpu_terms_home_slots64(DOC_VALUE_KINDS64[kind][0], C.c_uint64(int(value_bits)), int(max_buckets), C.byref(lds), C.byref(table)))
+    return int(lds.value), int(table.value)
 
 
 # ---- numeric range facets: a query's hits counted per requested value range (all four single-valued kinds) -----------------------

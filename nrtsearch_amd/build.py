@@ -8,8 +8,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libnrtgpu.so")
-SOURCES = ["kernels.hip", "maxscore.hip", "knn.hip", "knn_bytes.hip", "funcscore.hip", "multimatch.hip", "knnclauses.hip", "fieldsort.hip", "fieldsort64.hip", "termscount.hip", "rangecount.hip", "docset.hip", "valuemask.hip", "runtime.cpp", "segment.cpp", "planner.cpp", "search.cpp", "finalscore.cpp", "funcscore.cpp", "multimatch.cpp", "funcscore_multimatch.cpp", "knnclauses.cpp", "fieldsort.cpp", "fieldsort64.cpp", "termscount.cpp", "rangecount.cpp", "docset.cpp", "valuemask.cpp", "vectors.cpp", "vectors_bytes.cpp", "vectors_gather.cpp", "dist.cpp"]
-HEADERS = ["plan.h", "topk.hiph", "knn_bytes_body.hiph","bm25_common.hiph", "finalscore.hiph", "termstables.hiph", "host_math.h", "coalescer.h", "runtime_internal.h", os.path.join("..", "..", "include", "nrtgpu.h")]
+SOURCES = ["kernels.hip", "maxscore.hip", "knn.hip", "knn_bytes.hip", "funcscore.hip", "multimatch.hip", "knnclauses.hip", "fieldsort.hip", "fieldsort64.hip", "termscount.hip", "termscount64.hip", "rangecount.hip", "docset.hip", "valuemask.hip", "runtime.cpp", "segment.cpp", "planner.cpp", "search.cpp", "finalscore.cpp", "funcscore.cpp", "multimatch.cpp", "funcscore_multimatch.cpp", "knnclauses.cpp", "fieldsort.cpp", "fieldsort64.cpp", "termscount.cpp", "termscount64.cpp", "rangecount.cpp", "docset.cpp", "valuemask.cpp", "vectors.cpp", "vectors_bytes.cpp", "vectors_gather.cpp", "dist.cpp"]
+HEADERS = ["plan.h", "topk.hiph", "knn_bytes_body.hiph","bm25_common.hiph", "finalscore.hiph", "termstables.hiph", "termstables64.hiph", "host_math.h", "coalescer.h", "runtime_internal.h", os.path.join("..", "..", "include", "nrtgpu.h")]
 # -ffp-contract=off + no fast-math: BM25 arithmetic must round exactly like Java's float ops.
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared", "-ffp-contract=off",
          "-fno-fast-math", "-Wall", "-Wno-unused-function", "-parallel-jobs=8", "-x", "hip"]   # (the translation units compile side by side: 50 s -> 23 s)

@@ -4,7 +4,8 @@
 // query's combined accept set with liveDocs in DPart.live_bits.  Beside it go the sorted / counting route's per-query record
 // (fieldsort.cpp / termscount.cpp build them), one DRangeQuery per query, one DSortPart per part for the sort / count column and
 // kMaxRanges per part for the range clauses' columns (plan.h).  From the plan on the path is finalscore.cpp's; the count route's
-// workspace, collect() and unpacking are termscount.cpp's.
+// workspace, collect() and unpacking are termscount.cpp's (over a 64-bit count column, nrtgpu_count_docset_terms64_batch:
+// termscount64.cpp's).
 #include <cstddef>
 
 #include "runtime_internal.h"
@@ -187,6 +188,33 @@ int check_terms(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docs
   for (int qi = 0; qi < n_queries; ++qi) {
     if ((*kinds)[(size_t)qi] < 0) return no_column(qi, terms[qi].field_id);
     if ((*kinds)[(size_t)qi] >= kDocValuesInt64) return doc_values_wide(qi, terms[qi].field_id, kTermsCountWide);
+    if (int rc = docset_finish(segs, n_segs, docsets[qi], qi, call)) return rc;
+  }
+  work->layout(n_queries, slots, cap);
+  return NRTGPU_OK;
+}
+
+// check_terms for a count over a 64-bit column (termscount64.cpp's records and workspace).
+int check_terms64(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* docsets, const nrtgpu_terms_count* terms,
+                  const nrtgpu_term_counts64* out, int32_t n_queries, DocsetCall* call, std::vector<DTermsQuery>* records, std::vector<int>* kinds,
+                  TermsWork64* work) {
+  std::vector<char> count_multi;
+  uint64_t slots = 0, cap = 0;
+  for (int qi = 0; qi < n_queries; ++qi) {
+    if (int rc = docset_begin(segs, n_segs, docsets[qi], qi, call)) return rc;
+    int kind = -1;
+    bool multi = false;
+    DTermsQuery r{};
+    if (int rc = terms_count64_record(segs, n_segs, terms[qi], out ? &out[qi] : nullptr, qi, &slots, &cap, &r, &kind, &multi)) return rc;
+    r.need = 0u;   // (unread by the doc-set kernel; no multi-valued 64-bit column exists)
+    kinds->push_back(kind);
+    count_multi.push_back(multi ? 1 : 0);
+    records->push_back(r);
+  }
+  for (int qi = 0; qi < n_queries; ++qi) {
+    const int kind = (*kinds)[(size_t)qi];
+    if (kind < 0) return no_column(qi, terms[qi].field_id);
+    if (kind < kDocValuesInt64) return terms_count64_narrow(qi, terms[qi].field_id, count_multi[(size_t)qi] != 0, "nrtgpu_count_docset_terms_batch");
     if (int rc = docset_finish(segs, n_segs, docsets[qi], qi, call)) return rc;
   }
   work->layout(n_queries, slots, cap);
@@ -417,4 +445,68 @@ extern "C" int nrtgpu_count_docset_terms_batch(nrtgpu_ctx* ctx, const nrtgpu_seg
   };
   if (int rc = final_score_run(ctx, hp, call.masks.data(), n_queries, pages.data(), t0, extras, 4, call.any_multi ? multi : single, &own)) return rc;
   return terms_unpack(work, kinds, pages.data(), n_queries, out);
+}
+
+extern "C" int nrtgpu_count_docset_terms64_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* d,
+                                                     const nrtgpu_terms_count* t) {
+  if (int rc = final_score_enter(ctx, segs, n_segs, !d || !t, nullptr)) return rc;
+  SegReadLocks content(segs, n_segs);
+  DocsetCall call;
+  std::vector<DTermsQuery> records;
+  std::vector<int> kinds;
+  TermsWork64 work;
+  if (int rc = check_terms64(segs, n_segs, d, t, nullptr, 1, &call, &records, &kinds, &work)) return rc;
+  HostPlan hp;
+  return docset_plan(ctx, segs, nullptr, n_segs, call.masks.data(), 1, hp);
+}
+
+extern "C" int nrtgpu_count_docset_terms64_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                                 const nrtgpu_docset_query* docsets, const nrtgpu_terms_count* terms, int32_t n_queries,
+                                                 nrtgpu_term_counts64* out) {
+  if (int rc = final_score_enter(ctx, segs, n_segs, !docsets || !terms || !out, &n_queries)) return rc;
+  const double t0 = now_ms();
+  SegReadLocks content(segs, n_segs);   // until this call's kernels have finished
+  DocsetCall call;
+  std::vector<DTermsQuery> records;
+  std::vector<int> kinds;
+  TermsWork64 work;
+  if (int rc = check_terms64(segs, n_segs, docsets, terms, out, n_queries, &call, &records, &kinds, &work)) return rc;
+  HostPlan hp;
+  if (int rc = docset_plan(ctx, segs, doc_bases, n_segs, call.masks.data(), n_queries, hp)) return rc;
+  std::vector<DSortPart> unused, rparts;   // (the range clauses' columns are 32-bit ones: docset_parts' walk; the count's are read below)
+  std::vector<int32_t> no_field((size_t)n_queries, -1);
+  docset_parts(segs, docsets, no_field.data(), hp, &unused, &rparts);
+  std::vector<DSort64Part> sparts(hp.parts.size(), DSort64Part{nullptr, nullptr});
+  for (const DItem& it : hp.items)
+    for (uint32_t pi = 0; pi < it.n_parts; ++pi) {
+      const size_t at = (size_t)it.part_begin + pi;
+      sparts[at] = doc_values_column64(segs[hp.part_leaf[at]], terms[it.query].field_id);
+    }
+  const PlanBytes extras[4] = {{records.data(), records.size() * sizeof(DTermsQuery)},
+                               {call.ranges.data(), call.ranges.size() * sizeof(DRangeQuery)},
+                               {sparts.data(), sparts.size() * sizeof(DSort64Part)},
+                               {rparts.data(), rparts.size() * sizeof(DSortPart)}};
+  std::vector<nrtgpu_topdocs> pages((size_t)n_queries, nrtgpu_topdocs{});   // (no hits come back: the merge's lists are empty; total_hits is read from them)
+  const FinalScoreOwn own{work.bytes, terms64_collect, &work};
+  // the dispatch: a call whose range columns are all single-valued launches the kernel without the walk of their values
+  const FinalScoreLaunch single = [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
+    const TermsWork64* w = (const TermsWork64*)a.own_user;
+    DTermsState64* states;
+    unsigned long long *keys, *out_codes;
+    uint32_t *counts, *out_counts;
+    terms64_regions(*w, (char*)a.own, &states, &keys, &counts, &out_codes, &out_counts);
+    launch_docset_terms_count64(st, false, a, (const DTermsQuery*)d_extra[0], (const DRangeQuery*)d_extra[1], (const DSort64Part*)d_extra[2],
+                                (const DSortPart*)d_extra[3], states, keys, counts, out_codes, out_counts, (uint32_t)w->n_queries, w->out_cap);
+  };
+  const FinalScoreLaunch multi = [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
+    const TermsWork64* w = (const TermsWork64*)a.own_user;
+    DTermsState64* states;
+    unsigned long long *keys, *out_codes;
+    uint32_t *counts, *out_counts;
+    terms64_regions(*w, (char*)a.own, &states, &keys, &counts, &out_codes, &out_counts);
+    launch_docset_terms_count64(st, true, a, (const DTermsQuery*)d_extra[0], (const DRangeQuery*)d_extra[1], (const DSort64Part*)d_extra[2],
+                                (const DSortPart*)d_extra[3], states, keys, counts, out_codes, out_counts, (uint32_t)w->n_queries, w->out_cap);
+  };
+  if (int rc = final_score_run(ctx, hp, call.masks.data(), n_queries, pages.data(), t0, extras, 4, call.any_multi ? multi : single, &own)) return rc;
+  return terms64_unpack(work, kinds, pages.data(), n_queries, out);
 }

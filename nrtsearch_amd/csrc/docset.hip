@@ -9,6 +9,8 @@
 //   docset_sort64_kernel<MULTI> docset_sort_kernel / docset_sort_multi_kernel over a 64-BIT sort column (plan.h: sort_key64; behind them)
 //   docset_range_count_kernel<WIDE, MULTI>   the same hit set; every hit with a value adds 1 to the elementary interval of its
 //                               code among the query's cut points (nrtgpu_count_docset_ranges_batch; behind the 64-bit sort)
+//   docset_terms_count64_kernel<MULTI>   docset_terms_count_kernel over a 64-BIT count column (termstables64.hiph;
+//                               nrtgpu_count_docset_terms64_batch; behind the range facet)
 //
 // The decomposition is the final-score skeleton's (finalscore.hiph): one workgroup of kScanWaves waves per item, a wave takes
 // kTileDocs-doc sub-tiles of the item's parts (final_total_tiles / final_tile), hits per slice through final_count_slice, the
@@ -31,6 +33,7 @@
 
 #include "finalscore.hiph"
 #include "termstables.hiph"
+#include "termstables64.hiph"
 
 namespace nrtgpu {
 
@@ -768,6 +771,101 @@ void docset_range_count_kernel(const DItem* __restrict__ items, const DPart* __r
     }
     item_hits[blockIdx.x] = n;
   }
+}
+
+// ---- a terms count over a 64-BIT column (plan.h: DTermsState64; termstables64.hiph; nrtgpu_count_docset_terms64_batch) ------------
+// docset_terms_count_kernel (MULTI: the doc set's own 32-bit range clauses may name multi-valued columns -- docset_hit_set_multi,
+// as in docset_sort64_kernel<MULTI>) with the count column read as 64-bit codes (docset_column64) and the 64-bit tables.  Only
+// the counted column is wide, and it is single-valued.  Hits are taken by popcount; a word without an accepted doc costs no
+// column load.  Everything else is that kernel's.
+struct DocsetTerms64Smem {
+  Terms64Lds table;                             // the item's count table (plan.h), shared by the waves
+  uint32_t slot_hits[kSliceSlots];              // what final_count_slice and the epilogue read (finalscore.hiph: FinalSmem)
+  uint32_t slot_slice[kSliceSlots];
+};
+
+template <bool MULTI>
+__global__ __launch_bounds__(kScanThreads, kScanWaves / 4)
+void docset_terms_count64_kernel(const DItem* __restrict__ items, const DPart* __restrict__ parts, const DQuery* __restrict__ queries,
+                                 const DTermsQuery* __restrict__ tqueries, const DRangeQuery* __restrict__ rqueries,
+                                 const DSort64Part* __restrict__ sparts, const DSortPart* __restrict__ rparts, DTermsState64* __restrict__ states,
+                                 unsigned long long* __restrict__ table_keys, uint32_t* __restrict__ table_counts, uint32_t* __restrict__ slice_sum,
+                                 uint32_t* __restrict__ item_counts, uint64_t* __restrict__ item_hits) {
+  __shared__ DocsetTerms64Smem s;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)), lane = tid & 63u;
+  const DItem* const item = items + blockIdx.x;
+  const uint32_t query = item->query, part_begin = item->part_begin, n_parts = item->n_parts;
+  const DQuery* const q = queries + query;
+  const DTermsQuery* const tq = tqueries + query;
+  const DRangeQuery* const rq = rqueries + query;
+  const uint32_t max_buckets = tq->max_buckets, shift = tq->table_shift;
+  const uint32_t mask = (1u << (32u - shift)) - 1u;
+  unsigned long long* const keys = table_keys + tq->table_off;
+  uint32_t* const counts = table_counts + tq->table_off;
+  DTermsState64* const st = states + query;
+
+  terms_lds_clear64(s.table, tid, (uint32_t)kScanThreads);
+  if (tid < (uint32_t)kSliceSlots) s.slot_hits[tid] = s.slot_slice[tid] = 0u;
+  __syncthreads();
+
+  const uint32_t total_tiles = final_total_tiles(parts, part_begin, n_parts);
+  uint32_t pi = 0;      // the part of the wave's sub-tile (indices only grow)
+
+  for (uint32_t g = wave; g < total_tiles; g += (uint32_t)kScanWaves) {
+    const FinalTile tl = final_tile(parts, part_begin, n_parts, g, pi);
+    const uint32_t base = tl.base;
+    uint32_t words, hits;
+    const DSortPart* const my_rparts = rparts + (size_t)(part_begin + pi) * (size_t)kMaxRanges;
+    const uint32_t m = MULTI ? docset_hit_set_multi(tl.part, rq, my_rparts, base, tl.tile_len, lane, words, hits)
+                             : docset_hit_set(tl.part, rq, my_rparts, base, tl.tile_len, lane, words, hits);
+    if (words == 0u) continue;   // uniform
+    final_count_slice(s, tl.part, lane, hits);
+    // an overflowed query's buckets are void: its items go on counting hits only (a flag read once, not waited for)
+    if (__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(&st->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0) continue;
+    uint64_t cv[kFinalSlots];
+    uint32_t has_bits;
+    if (!docset_column64(sparts + part_begin + pi, base, base >> 6, lane, words, cv, has_bits)) continue;   // the leaf lacks the column: its hits add to no bucket
+    const uint32_t valued = m & has_bits;
+#pragma unroll
+    for (int j = 0; j < kFinalSlots; ++j)
+      if (((valued >> j) & 1u) != 0u) terms_lds_add64(s.table, keys, counts, shift, mask, max_buckets, st, cv[j], 1u);
+  }
+
+  // ---- the item's table into the query's, once
+  __syncthreads();
+  terms_lds_flush64(s.table, keys, counts, shift, mask, max_buckets, st, tid, (uint32_t)kScanThreads);
+
+  // ---- epilogue: final_epilogue's for an item without candidates
+  if (tid == 0) {
+    item_counts[blockIdx.x] = 0u;
+    uint32_t n = 0;
+    const uint32_t gte_floor = q->gte_floor, slice_base = q->slice_base;
+    for (int i = 0; i < kSliceSlots; ++i) {
+      const uint32_t h = s.slot_hits[i];
+      n += h;
+      if (h != 0u && gte_floor != 0xFFFFFFFFu) atomicAdd(&slice_sum[slice_base + s.slot_slice[i]], h);
+    }
+    item_hits[blockIdx.x] = n;
+  }
+}
+
+// terms_compact64_kernel's launch (termscount64.hip)
+void launch_terms_compact64(hipStream_t stream, const DTermsQuery* tqueries, DTermsState64* states, const unsigned long long* table_keys,
+                            const uint32_t* table_counts, unsigned long long* out_codes, uint32_t* out_counts, uint32_t n_queries, uint32_t out_cap);
+
+void launch_docset_terms_count64(hipStream_t stream, bool multi, const FinalScoreArgs& a, const DTermsQuery* tqueries, const DRangeQuery* rqueries,
+                                 const DSort64Part* sparts, const DSortPart* rparts, DTermsState64* states, unsigned long long* table_keys,
+                                 uint32_t* table_counts, unsigned long long* out_codes, uint32_t* out_counts, uint32_t n_queries, uint32_t out_cap) {
+  if (a.n_items != 0) {
+    if (multi)
+      hipLaunchKernelGGL(docset_terms_count64_kernel<true>, dim3(a.n_items), dim3(kScanThreads), 0, stream, a.items, a.parts, a.queries, tqueries, rqueries,
+                         sparts, rparts, states, table_keys, table_counts, a.slice_sum, a.item_counts, a.item_hits);
+    else
+      hipLaunchKernelGGL(docset_terms_count64_kernel<false>, dim3(a.n_items), dim3(kScanThreads), 0, stream, a.items, a.parts, a.queries, tqueries, rqueries,
+                         sparts, rparts, states, table_keys, table_counts, a.slice_sum, a.item_counts, a.item_hits);
+  }
+  launch_terms_compact64(stream, tqueries, states, table_keys, table_counts, out_codes, out_counts, n_queries, out_cap);
 }
 
 void launch_docset_range_count(hipStream_t stream, bool wide, bool multi, const FinalScoreArgs& a, const DRangeCountQuery* cqueries,

@@ -819,6 +819,41 @@ struct alignas(16) DTermsState {   // per query, zeroed per call; one more behin
 };
 static_assert(sizeof(DTermsState) == 16, "DTermsState layout");
 
+// The terms aggregation over a 64-BIT column (termscount64.hip: bm25_terms_count64_kernel, terms_compact64_kernel; docset.hip:
+// docset_terms_count64_kernel; termscount64.cpp): a bucket is a 64-bit column code (doc_value_code64: longs by value, doubles by
+// doubleToLongBits with every NaN in one bucket).  A code does not fit beside its count in one word, so a slot is TWO words in
+// two arrays: an 8-byte key and a 4-byte count.  Key 0 is "empty"; a key slot is claimed with ONE compare-and-swap (0 -> code)
+// and never changes again, the count beside it grows by atomic adds only and is read behind the kernel (the compaction) or behind
+// the workgroup's barrier (the flush) -- no thread ever waits for a slot to become complete.  EVERY 64-bit code is a value (code 0
+// is Long.MIN_VALUE, code 2^64 - 1 Long.MAX_VALUE), so the one value whose code is the empty marker is counted BESIDE the table:
+// a 4-byte counter of the workgroup in LDS, one of the query in its state record; the add that finds the query's counter at 0 is
+// the value's first arrival and claims a bucket like any other.  Everything else is the 32-bit tables' contract, word for word:
+// linear probing, kTermsLdsProbe steps in LDS (then the value goes straight to the query's table), the table's capacity in global
+// memory (then the overflow flag); every claimed bucket counts in `claimed`; a query overflows iff its hits hold more than
+// max_buckets distinct values, whatever the load (a query's table has the power of two >= 2 x max_buckets slots: it cannot fill
+// before `claimed` passes the bound).  DTermsQuery is reused as it is (table_off: the query's first slot in both arrays).
+// The home slot mixes BOTH halves of the code, each through a multiplier of its own: ids that differ only above bit 32 spread,
+// and so do timestamps that differ only below it.  The ONE statement of it: the kernels and nrtgpu_terms_home_slots64 call
+// terms_home_slot64.
+constexpr int kTerms64LdsSlots = 8192;        // 96 KiB of the workgroup's LDS: 64 KiB of keys, 32 KiB of counts (NRTGPU_TERMS64_LDS_SLOTS)
+constexpr int kTerms64LdsShift = 32 - 13;     // home slot = hash >> shift
+static_assert((1 << (32 - kTerms64LdsShift)) == kTerms64LdsSlots, "the 64-bit LDS table's hash shift");
+constexpr uint32_t kTerms64HashMulHigh = 0xC2B2AE3Du;   // the code's high word (the low word: kTermsHashMul)
+constexpr uint64_t kTerms64SlotBytes = 12;              // a key and a count
+constexpr uint64_t kTerms64MaxCallSlots = (1ull << 28) / kTerms64SlotBytes;   // 22 369 621: the 32-bit entry's 256 MiB of tables per call
+__host__ __device__ inline uint32_t terms_home_slot64(uint64_t code, uint32_t shift) {
+  return ((uint32_t)code * kTermsHashMul + (uint32_t)(code >> 32) * kTerms64HashMulHigh) >> shift;
+}
+struct alignas(16) DTermsState64 {   // DTermsState with the reserved code's counter; one more behind the last query, as there
+  uint32_t claimed;       // buckets claimed (the reserved code's included) == distinct values seen (until the query overflows)
+  uint32_t overflow;
+  uint32_t n_out;
+  uint32_t out_base;
+  uint32_t zero_count;    // hits under code 0, the key that marks an empty slot
+  uint32_t pad[3];
+};
+static_assert(sizeof(DTermsState64) == 32, "DTermsState64 layout");
+
 // Doc-set requests (docset.hip: docset_sort_kernel, docset_terms_count_kernel; docset.cpp): a sorted search or a terms count
 // whose hit set is a doc set -- liveDocs, FILTER / MUST_NOT masks, numeric range clauses -- and no text clause.  The parts of
 // such a plan have no clauses (n_terms == 0) and DPart.live_bits is the query's combined accept set WITH liveDocs (there are no

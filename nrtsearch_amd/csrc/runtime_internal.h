@@ -102,6 +102,16 @@ void launch_bm25_range_count(hipStream_t stream, bool wide, const FinalScoreArgs
                              const void* cuts, uint32_t* counters);
 void launch_docset_range_count(hipStream_t stream, bool wide, bool multi, const FinalScoreArgs& a, const DRangeCountQuery* cqueries,
                                const DRangeQuery* rqueries, const DSortPart* sparts, const DSortPart* rparts, const void* cuts, uint32_t* counters);
+// terms aggregation over a 64-bit column (termscount64.hip, docset.hip): one DTermsQuery per query, one DSort64Part per part, the
+// queries' DTermsState64 records, the tables' key and count arrays; the scorer, then the compaction into out_codes / out_counts
+// (out_cap entries).  The doc-set form with the doc set's DRangeQuery per query and its kMaxRanges 32-bit DSortPart per part
+// (multi: some range clause names a multi-valued column)
+void launch_bm25_terms_count64(hipStream_t stream, const FinalScoreArgs& a, const DTermsQuery* tqueries, const DSort64Part* sparts, DTermsState64* states,
+                               unsigned long long* table_keys, uint32_t* table_counts, unsigned long long* out_codes, uint32_t* out_counts,
+                               uint32_t n_queries, uint32_t out_cap);
+void launch_docset_terms_count64(hipStream_t stream, bool multi, const FinalScoreArgs& a, const DTermsQuery* tqueries, const DRangeQuery* rqueries,
+                                 const DSort64Part* sparts, const DSortPart* rparts, DTermsState64* states, unsigned long long* table_keys,
+                                 uint32_t* table_counts, unsigned long long* out_codes, uint32_t* out_counts, uint32_t n_queries, uint32_t out_cap);
 #ifdef NRTGPU_DEV
 void launch_debug_wave_kth(hipStream_t stream, const uint64_t* keys, uint32_t n, uint32_t r, uint64_t* out);   // (maxscore.hip: topk_kth_wave on its own)
 void launch_debug_walk_value(hipStream_t stream, float weight, const uint32_t* freq, const uint32_t* norm, const float* table, int fx_scale,
@@ -1231,7 +1241,8 @@ int doc_values_masks_resident(const nrtgpu_seg* const* segs, int32_t n_segs, con
 // NRTGPU_ERR_UNSUPPORTED with the reason: a 32-bit entry named a field that holds a 64-bit column (kind >= kDocValuesInt64);
 // instead: what serves such a column, or that nothing does
 int doc_values_wide(int qi, int32_t field_id, const char* instead);
-constexpr const char* kTermsCountWide = "terms counts read 32-bit columns, 64-bit buckets are not built";
+constexpr const char* kTermsCountWide = "terms counts read 32-bit columns, 64-bit buckets are not built by this entry: count it with "
+                                        "nrtgpu_count_terms64_batch / nrtgpu_count_docset_terms64_batch";
 // the leaf (index into segs) of every part of a plan of the flat copies: a part names its (query, leaf) pair by its first DTerm
 int doc_values_part_leaves(const nrtgpu_seg* const* segs, int32_t n_segs, const HostPlan& hp, const char* route, std::vector<int32_t>* out);
 // the column of every part's leaf, for a plan of the flat copies (field_ids: per query)
@@ -1276,11 +1287,33 @@ struct TermsWork {
 // what both refuse of (terms[qi], out[qi]) as an invalid argument (out: nullptr for the predicates), the column's kind over the
 // leaves, the query's record with its table behind the earlier queries' (*slots, *cap: the call's running sums)
 int terms_count_record(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_terms_count& t, const nrtgpu_term_counts* out, int qi, uint64_t* slots,
-                       uint64_t* cap, DTermsQuery* record, int* kind, bool* multi);
+                       uint64_t* cap, DTermsQuery* record, int* kind, bool* multi, uint64_t max_call_slots = kTermsMaxCallSlots);
 // FinalScoreOwn.collect of both (user: the call's TermsWork): the states, then the entries that exist
 int terms_collect(nrtgpu_ctx* ctx, Slot* slot, const char* d_own, void* user);
 // the call's answers from what terms_collect brought back and the merge's (empty) lists
 int terms_unpack(const TermsWork& work, const std::vector<int>& kinds, const nrtgpu_topdocs* pages, int32_t n_queries, nrtgpu_term_counts* out);
+
+// termscount64.cpp: the same of the routes that fill 64-bit count tables (plan.h: DTermsState64; a slot is a key in one array and
+// a count in another, so the compacted entries come back as two lists).
+struct TermsWork64 {
+  int32_t n_queries = 0;
+  size_t o_states = 0, o_keys = 0, o_counts = 0, o_out_codes = 0, o_out_counts = 0, bytes = 0;
+  uint32_t out_cap = 0;    // entries the out lists hold: sum of max_buckets
+  std::vector<DTermsState64> states;   // terms64_collect(): n_queries + 1
+  std::vector<uint64_t> codes;         // terms64_collect(): states[n_queries].claimed entries ...
+  std::vector<uint32_t> counts;        // ... and their counts
+  void layout(int32_t n_queries, uint64_t slots, uint64_t cap);
+};
+// terms_count_record over an output of the 64-bit entries, against the bound of kTerms64MaxCallSlots
+int terms_count64_record(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_terms_count& t, const nrtgpu_term_counts64* out, int qi, uint64_t* slots,
+                         uint64_t* cap, DTermsQuery* record, int* kind, bool* multi);
+// NRTGPU_ERR_UNSUPPORTED with the reason: the count column is a 32-bit one (multi: multi-valued); entry32: the entry that serves it
+int terms_count64_narrow(int qi, int32_t field_id, bool multi, const char* entry32);
+int terms64_collect(nrtgpu_ctx* ctx, Slot* slot, const char* d_own, void* user);
+int terms64_unpack(const TermsWork64& work, const std::vector<int>& kinds, const nrtgpu_topdocs* pages, int32_t n_queries, nrtgpu_term_counts64* out);
+// the regions of the route's workspace (d_own: FinalScoreArgs.own) as the launches take them
+void terms64_regions(const TermsWork64& w, char* d_own, DTermsState64** states, unsigned long long** keys, uint32_t** counts, unsigned long long** out_codes,
+                     uint32_t** out_counts);
 
 // rangecount.cpp: what the routes that count value ranges share (a text query's hits there; a doc set's in docset.cpp).
 // The call's records, cut array and interval counters: what goes into the plan buffer (the DRangeCountQuery records, then the

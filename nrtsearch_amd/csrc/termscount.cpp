@@ -35,7 +35,7 @@ void TermsWork::layout(int32_t n, uint64_t slots, uint64_t cap) {
 // What the routes refuse of (terms[qi], out[qi]) as an invalid argument, the kind of the column over the leaves, and the query's
 // record with its table laid out behind the earlier queries' (*slots, *cap: the call's running sums).
 int terms_count_record(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_terms_count& t, const nrtgpu_term_counts* out, int qi, uint64_t* slots,
-                       uint64_t* cap, DTermsQuery* record, int* kind, bool* multi) {
+                       uint64_t* cap, DTermsQuery* record, int* kind, bool* multi, uint64_t max_call_slots) {
   if (t.max_buckets < 1 || t.max_buckets > NRTGPU_MAX_TERM_BUCKETS)
     return fail(NRTGPU_ERR_INVALID_ARG, "query %d: max_buckets %d outside 1..%d", qi, t.max_buckets, NRTGPU_MAX_TERM_BUCKETS);
   if (out && (out->capacity < t.max_buckets || !out->value_bits || !out->counts))
@@ -48,9 +48,9 @@ int terms_count_record(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtg
   r.table_off = (uint32_t)*slots;
   *slots += 1ull << (32u - r.table_shift);
   *cap += r.max_buckets;
-  if (*slots > kTermsMaxCallSlots)
+  if (*slots > max_call_slots)
     return fail(NRTGPU_ERR_INVALID_ARG, "query %d: the count tables of the call exceed the workspace bound of %llu slots (a query takes the power of two >= 2 x max_buckets)",
-                qi, (unsigned long long)kTermsMaxCallSlots);
+                qi, (unsigned long long)max_call_slots);
   *record = r;
   return NRTGPU_OK;
 }
