@@ -7,6 +7,7 @@
 // workspace, collect() and unpacking are termscount.cpp's (over a 64-bit count column, nrtgpu_count_docset_terms64_batch:
 // termscount64.cpp's).
 #include <cstddef>
+#include <type_traits>
 
 #include "runtime_internal.h"
 
@@ -30,7 +31,7 @@ struct DocsetCall {
   std::vector<nrtgpu_bm25_query> masks;    // per query: k, total_hits_threshold and the mask fields (what docset_plan and final_score_run read)
   std::vector<DRangeQuery> ranges;         // per query (the codes are filled once the columns' kinds are known)
   std::vector<int> range_kinds;            // per (query, clause): kMaxRanges per query
-  bool any_multi = false;                  // some named column of the call (a range clause's, the count's) is multi-valued: the *_multi kernels
+  bool any_multi = false;                  // some named column of the call (a range clause's, the 32-bit count's) is multi-valued: the launches' `multi`
 };
 
 // What the route refuses of docsets[qi] as an invalid argument, the header's table in its order.
@@ -102,206 +103,228 @@ int docset_finish(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_do
 
 int no_column(int qi, int32_t field_id) { return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: no leaf of the call holds doc values of field %d", qi, field_id); }
 
-// The columns of every part's leaf (HostPlan.part_leaf): the collector's (field_ids: per query) and the range clauses'.
-void docset_parts(const nrtgpu_seg* const* segs, const nrtgpu_docset_query* docsets, const int32_t* field_ids, const HostPlan& hp, std::vector<DSortPart>* sparts,
-                  std::vector<DSortPart>* rparts) {
-  sparts->assign(hp.parts.size(), DSortPart{nullptr, nullptr});
-  rparts->assign(hp.parts.size() * (size_t)kMaxRanges, DSortPart{nullptr, nullptr});
+// ---- the driver: one checking half and one running half behind every (predicate, batch entry) pair -------------------------------
+// The checking half, shared by a predicate and its batch entry, in the order the header's tables promise: per query docset_begin,
+// then the collector's invalid-argument step; then, per query, the collector's column refusals (on no leaf, wide / narrow,
+// multi-valued), docset_finish, and the collector's record.  begin / column / record: int(int qi).
+template <class Begin, class Column, class Record>
+int docset_check(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* docsets, int32_t n_queries, DocsetCall* call, Begin begin,
+                 Column column, Record record) {
+  for (int qi = 0; qi < n_queries; ++qi) {
+    if (int rc = docset_begin(segs, n_segs, docsets[qi], qi, call)) return rc;
+    if (int rc = begin(qi)) return rc;
+  }
+  for (int qi = 0; qi < n_queries; ++qi) {
+    if (int rc = column(qi)) return rc;
+    if (int rc = docset_finish(segs, n_segs, docsets[qi], qi, call)) return rc;
+    if (int rc = record(qi)) return rc;
+  }
+  return NRTGPU_OK;
+}
+
+// A predicate: the checking half, then the planner for the leaves (sealed, of this context) and the accept sets, with n = 1.
+// check: int(DocsetCall*).
+template <class Check>
+int docset_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, bool null_argument, Check check) {
+  if (int rc = final_score_enter(ctx, segs, n_segs, null_argument, nullptr)) return rc;
+  SegReadLocks content(segs, n_segs);
+  DocsetCall call;
+  if (int rc = check(&call)) return rc;
+  HostPlan hp;
+  return docset_plan(ctx, segs, nullptr, n_segs, call.masks.data(), 1, hp);
+}
+
+// The running half of a batch entry, from the checked call to the filled pages: the plan, the columns of every part's leaf
+// (HostPlan.part_leaf) -- the collector's (field_of: int32_t(uint32_t query); wide: it holds 64-bit codes) and the range
+// clauses', which are 32-bit ones --, the four extras, the launch for the call's arities, final_score_run.  records: the
+// collector's per-query records (extras[0]); launch[m]: its scorer, m = the call names a multi-valued column.
+template <class FieldOf>
+int docset_run(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, const nrtgpu_docset_query* docsets,
+               int32_t n_queries, const DocsetCall& call, double t0, PlanBytes records, FieldOf field_of, bool wide, const FinalScoreLaunch (&launch)[2],
+               nrtgpu_topdocs* pages, const FinalScoreOwn* own) {
+  HostPlan hp;
+  if (int rc = docset_plan(ctx, segs, doc_bases, n_segs, call.masks.data(), n_queries, hp)) return rc;
+  std::vector<DSortPart> sparts(hp.parts.size(), DSortPart{nullptr, nullptr}), rparts(hp.parts.size() * (size_t)kMaxRanges, DSortPart{nullptr, nullptr});
   for (const DItem& it : hp.items)
     for (uint32_t pi = 0; pi < it.n_parts; ++pi) {
       const size_t at = (size_t)it.part_begin + pi;
       const nrtgpu_seg* seg = segs[hp.part_leaf[at]];
-      (*sparts)[at] = doc_values_column(seg, field_ids[it.query]);
+      sparts[at] = range_count_column_of(seg, field_of(it.query), wide);   // (rangecount.cpp: despite its name the column of ANY collector at either width)
       const nrtgpu_docset_query& d = docsets[it.query];
-      for (int r = 0; r < d.n_ranges; ++r) (*rparts)[at * (size_t)kMaxRanges + (size_t)r] = doc_values_column(seg, d.ranges[r].field_id);
+      for (int r = 0; r < d.n_ranges; ++r) rparts[at * (size_t)kMaxRanges + (size_t)r] = doc_values_column(seg, d.ranges[r].field_id);
     }
+  const PlanBytes extras[4] = {records,
+                               {call.ranges.data(), call.ranges.size() * sizeof(DRangeQuery)},
+                               {sparts.data(), sparts.size() * sizeof(DSortPart)},
+                               {rparts.data(), rparts.size() * sizeof(DSortPart)}};
+  return final_score_run(ctx, hp, call.masks.data(), n_queries, pages, t0, extras, 4, launch[call.any_multi ? 1 : 0], own);
 }
 
-// What the sorted entry refuses of a call before anything is planned (the segments' content is held), and its records.
+// What the counting entries hand final_score_run for pages: no hits come back (the merge's lists are empty; total_hits is read from them).
+std::vector<nrtgpu_topdocs> no_pages(int32_t n_queries) { return std::vector<nrtgpu_topdocs>((size_t)n_queries, nrtgpu_topdocs{}); }
+
+// ---- the collectors: what each checks, and its scorer (d_extra: docset_run's extras) -----------------------------------------------
+// A sort by a 32-bit column (fieldsort.cpp's records).
 int check_sorted(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* docsets, const nrtgpu_field_sort* sorts, int32_t n_queries,
                  DocsetCall* call, std::vector<DSortQuery>* records, std::vector<int>* kinds) {
   std::vector<char> sort_multi;
-  for (int qi = 0; qi < n_queries; ++qi) {
-    if (int rc = docset_begin(segs, n_segs, docsets[qi], qi, call)) return rc;
-    if (int rc = field_sort_check(sorts[qi], qi)) return rc;
-    int kind = -1;
-    bool multi = false;
-    if (int rc = doc_values_kind(segs, n_segs, sorts[qi].field_id, qi, &kind, &multi)) return rc;
-    kinds->push_back(kind);
-    sort_multi.push_back(multi ? 1 : 0);
-  }
-  for (int qi = 0; qi < n_queries; ++qi) {
-    const int kind = (*kinds)[(size_t)qi];
-    if (kind < 0) return no_column(qi, sorts[qi].field_id);
-    if (kind >= kDocValuesInt64) return doc_values_wide(qi, sorts[qi].field_id, "sort by it with nrtgpu_search_docset_sorted64_batch");
-    if (sort_multi[(size_t)qi] != 0) return field_sort_multi(qi, sorts[qi].field_id);
-    if (int rc = docset_finish(segs, n_segs, docsets[qi], qi, call)) return rc;
-    DSortQuery r{};
-    field_sort_record(sorts[qi], kind, &r);
-    records->push_back(r);
-  }
-  return NRTGPU_OK;
+  return docset_check(
+      segs, n_segs, docsets, n_queries, call,
+      [&](int qi) {
+        if (int rc = field_sort_check(sorts[qi], qi)) return rc;
+        int kind = -1;
+        bool multi = false;
+        if (int rc = doc_values_kind(segs, n_segs, sorts[qi].field_id, qi, &kind, &multi)) return rc;
+        kinds->push_back(kind);
+        sort_multi.push_back(multi ? 1 : 0);
+        return (int)NRTGPU_OK;
+      },
+      [&](int qi) {
+        const int kind = (*kinds)[(size_t)qi];
+        if (kind < 0) return no_column(qi, sorts[qi].field_id);
+        if (kind >= kDocValuesInt64) return doc_values_wide(qi, sorts[qi].field_id, "sort by it with nrtgpu_search_docset_sorted64_batch");
+        if (sort_multi[(size_t)qi] != 0) return field_sort_multi(qi, sorts[qi].field_id);
+        return (int)NRTGPU_OK;
+      },
+      [&](int qi) {
+        DSortQuery r{};
+        field_sort_record(sorts[qi], (*kinds)[(size_t)qi], &r);
+        records->push_back(r);
+        return (int)NRTGPU_OK;
+      });
+}
+template <bool MULTI>
+void launch_sorted(hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
+  launch_docset_sort(st, MULTI, a, (const DSortQuery*)d_extra[0], (const DRangeQuery*)d_extra[1], (const DSortPart*)d_extra[2], (const DSortPart*)d_extra[3]);
 }
 
-// check_sorted for a sort by a 64-bit column (fieldsort64.cpp's records; in_order: the predicate's doc bases).
+// A sort by a 64-bit column (fieldsort64.cpp's records; in_order: the predicate's doc bases).
 int check_sorted64(const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs, bool in_order, const nrtgpu_docset_query* docsets,
                    const nrtgpu_field_sort64* sorts, int32_t n_queries, DocsetCall* call, std::vector<DSort64Query>* records, std::vector<int>* kinds) {
   std::vector<char> sort_multi;
-  for (int qi = 0; qi < n_queries; ++qi) {
-    if (int rc = docset_begin(segs, n_segs, docsets[qi], qi, call)) return rc;
-    if (int rc = field_sort64_check(sorts[qi], qi)) return rc;
-    int kind = -1;
-    bool multi = false;
-    if (int rc = doc_values_kind(segs, n_segs, sorts[qi].field_id, qi, &kind, &multi)) return rc;
-    kinds->push_back(kind);
-    sort_multi.push_back(multi ? 1 : 0);
-  }
   uint32_t db = 1;
-  for (int qi = 0; qi < n_queries; ++qi) {
-    const int kind = (*kinds)[(size_t)qi];
-    if (kind < 0) return no_column(qi, sorts[qi].field_id);
-    if (kind < kDocValuesInt64) return field_sort64_narrow(qi, sorts[qi].field_id, sort_multi[(size_t)qi] != 0, "nrtgpu_search_docset_sorted_batch");
-    if (int rc = docset_finish(segs, n_segs, docsets[qi], qi, call)) return rc;
-    if (qi == 0)
-      if (int rc = sort64_doc_bits(segs, doc_bases, n_segs, in_order, &db)) return rc;
-    DSort64Query r{};
-    if (int rc = field_sort64_record(segs, n_segs, sorts[qi], kind, db, qi, &r)) return rc;
-    records->push_back(r);
-  }
-  return NRTGPU_OK;
+  return docset_check(
+      segs, n_segs, docsets, n_queries, call,
+      [&](int qi) {
+        if (int rc = field_sort_check(sorts[qi], qi)) return rc;
+        int kind = -1;
+        bool multi = false;
+        if (int rc = doc_values_kind(segs, n_segs, sorts[qi].field_id, qi, &kind, &multi)) return rc;
+        kinds->push_back(kind);
+        sort_multi.push_back(multi ? 1 : 0);
+        return (int)NRTGPU_OK;
+      },
+      [&](int qi) {
+        const int kind = (*kinds)[(size_t)qi];
+        if (kind < 0) return no_column(qi, sorts[qi].field_id);
+        if (kind < kDocValuesInt64) return field_sort64_narrow(qi, sorts[qi].field_id, sort_multi[(size_t)qi] != 0, "nrtgpu_search_docset_sorted_batch");
+        return (int)NRTGPU_OK;
+      },
+      [&](int qi) {
+        if (qi == 0)
+          if (int rc = sort64_doc_bits(segs, doc_bases, n_segs, in_order, &db)) return rc;
+        DSort64Query r{};
+        if (int rc = field_sort64_record(segs, n_segs, sorts[qi], (*kinds)[(size_t)qi], db, qi, &r)) return rc;
+        records->push_back(r);
+        return (int)NRTGPU_OK;
+      });
+}
+template <bool MULTI>
+void launch_sorted64(hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
+  launch_docset_sort64(st, MULTI, a, (const DSort64Query*)d_extra[0], (const DRangeQuery*)d_extra[1], (const DSort64Part*)d_extra[2],
+                       (const DSortPart*)d_extra[3]);
 }
 
-// The same of the counting entry.  out: the batch entry's outputs (their capacities), nullptr for the predicate.
-int check_terms(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* docsets, const nrtgpu_terms_count* terms,
-                const nrtgpu_term_counts* out, int32_t n_queries, DocsetCall* call, std::vector<DTermsQuery>* records, std::vector<int>* kinds, TermsWork* work) {
-  uint64_t slots = 0, cap = 0;
-  for (int qi = 0; qi < n_queries; ++qi) {
-    if (int rc = docset_begin(segs, n_segs, docsets[qi], qi, call)) return rc;
-    int kind = -1;
-    bool multi = false;
-    DTermsQuery r{};
-    if (int rc = terms_count_record(segs, n_segs, terms[qi], out ? &out[qi] : nullptr, qi, &slots, &cap, &r, &kind, &multi)) return rc;
-    kinds->push_back(kind);
-    records->push_back(r);
-    call->any_multi = call->any_multi || multi;
-  }
-  for (int qi = 0; qi < n_queries; ++qi) {
-    if ((*kinds)[(size_t)qi] < 0) return no_column(qi, terms[qi].field_id);
-    if ((*kinds)[(size_t)qi] >= kDocValuesInt64) return doc_values_wide(qi, terms[qi].field_id, kTermsCountWide);
-    if (int rc = docset_finish(segs, n_segs, docsets[qi], qi, call)) return rc;
-  }
-  work->layout(n_queries, slots, cap);
-  return NRTGPU_OK;
-}
-
-// check_terms for a count over a 64-bit column (termscount64.cpp's records and workspace).
-int check_terms64(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* docsets, const nrtgpu_terms_count* terms,
-                  const nrtgpu_term_counts64* out, int32_t n_queries, DocsetCall* call, std::vector<DTermsQuery>* records, std::vector<int>* kinds,
-                  TermsWork64* work) {
+// A terms count over a 32-bit column (termscount.cpp's records and workspace) or, WORK = TermsWork64, over a 64-bit one
+// (termscount64.cpp's).  out: the batch entry's outputs (their capacities), nullptr for the predicate.
+template <class WORK, class OUT>
+int check_terms(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* docsets, const nrtgpu_terms_count* terms, const OUT* out,
+                int32_t n_queries, DocsetCall* call, std::vector<DTermsQuery>* records, std::vector<int>* kinds, WORK* work) {
+  constexpr bool wide = std::is_same<WORK, TermsWork64>::value;
   std::vector<char> count_multi;
   uint64_t slots = 0, cap = 0;
-  for (int qi = 0; qi < n_queries; ++qi) {
-    if (int rc = docset_begin(segs, n_segs, docsets[qi], qi, call)) return rc;
-    int kind = -1;
-    bool multi = false;
-    DTermsQuery r{};
-    if (int rc = terms_count64_record(segs, n_segs, terms[qi], out ? &out[qi] : nullptr, qi, &slots, &cap, &r, &kind, &multi)) return rc;
-    r.need = 0u;   // (unread by the doc-set kernel; no multi-valued 64-bit column exists)
-    kinds->push_back(kind);
-    count_multi.push_back(multi ? 1 : 0);
-    records->push_back(r);
-  }
-  for (int qi = 0; qi < n_queries; ++qi) {
-    const int kind = (*kinds)[(size_t)qi];
-    if (kind < 0) return no_column(qi, terms[qi].field_id);
-    if (kind < kDocValuesInt64) return terms_count64_narrow(qi, terms[qi].field_id, count_multi[(size_t)qi] != 0, "nrtgpu_count_docset_terms_batch");
-    if (int rc = docset_finish(segs, n_segs, docsets[qi], qi, call)) return rc;
-  }
+  if (int rc = docset_check(
+          segs, n_segs, docsets, n_queries, call,
+          [&](int qi) {
+            int kind = -1;
+            bool multi = false;
+            DTermsQuery r{};
+            if constexpr (wide) {
+              if (int rc = terms_count64_record(segs, n_segs, terms[qi], out ? &out[qi] : nullptr, qi, &slots, &cap, &r, &kind, &multi)) return rc;
+              r.need = 0u;   // (unread by the doc-set kernel; no multi-valued 64-bit column exists)
+            } else {
+              if (int rc = terms_count_record(segs, n_segs, terms[qi], out ? &out[qi] : nullptr, qi, &slots, &cap, &r, &kind, &multi)) return rc;
+              call->any_multi = call->any_multi || multi;
+            }
+            kinds->push_back(kind);
+            count_multi.push_back(multi ? 1 : 0);
+            records->push_back(r);
+            return (int)NRTGPU_OK;
+          },
+          [&](int qi) {
+            const int kind = (*kinds)[(size_t)qi];
+            if (kind < 0) return no_column(qi, terms[qi].field_id);
+            if (wide && kind < kDocValuesInt64)
+              return terms_count64_narrow(qi, terms[qi].field_id, count_multi[(size_t)qi] != 0, "nrtgpu_count_docset_terms_batch");
+            if (!wide && kind >= kDocValuesInt64) return doc_values_wide(qi, terms[qi].field_id, kTermsCountWide);
+            return (int)NRTGPU_OK;
+          },
+          [](int) { return (int)NRTGPU_OK; }))
+    return rc;
   work->layout(n_queries, slots, cap);
   return NRTGPU_OK;
 }
+template <bool MULTI>
+void launch_terms(hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
+  const TermsWork* w = (const TermsWork*)a.own_user;
+  char* d_own = (char*)a.own;
+  launch_docset_terms_count(st, MULTI, a, (const DTermsQuery*)d_extra[0], (const DRangeQuery*)d_extra[1], (const DSortPart*)d_extra[2],
+                            (const DSortPart*)d_extra[3], (DTermsState*)(d_own + w->o_states), (unsigned long long*)(d_own + w->o_tables),
+                            (unsigned long long*)(d_own + w->o_out), (uint32_t)w->n_queries, w->out_cap);
+}
+template <bool MULTI>
+void launch_terms64(hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
+  const TermsWork64* w = (const TermsWork64*)a.own_user;
+  DTermsState64* states;
+  unsigned long long *keys, *out_codes;
+  uint32_t *counts, *out_counts;
+  terms64_regions(*w, (char*)a.own, &states, &keys, &counts, &out_codes, &out_counts);
+  launch_docset_terms_count64(st, MULTI, a, (const DTermsQuery*)d_extra[0], (const DRangeQuery*)d_extra[1], (const DSort64Part*)d_extra[2],
+                              (const DSortPart*)d_extra[3], states, keys, counts, out_codes, out_counts, (uint32_t)w->n_queries, w->out_cap);
+}
 
-// The same of the range-counting entry (rangecount.cpp's records).  out: the batch entry's outputs, nullptr for the predicate.
+// A numeric range facet (rangecount.cpp's records).  out: the batch entry's outputs, nullptr for the predicate.
 int check_ranges(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* docsets, const nrtgpu_range_count* ranges,
                  const nrtgpu_range_counts* out, int32_t n_queries, DocsetCall* call, RangeWork* work) {
-  for (int qi = 0; qi < n_queries; ++qi) {
-    if (int rc = docset_begin(segs, n_segs, docsets[qi], qi, call)) return rc;
-    if (int rc = range_count_begin(segs, n_segs, ranges[qi], out ? &out[qi] : nullptr, qi, work)) return rc;
-  }
-  for (int qi = 0; qi < n_queries; ++qi) {
-    if (work->kinds[(size_t)qi] < 0) return no_column(qi, ranges[qi].field_id);
-    if (int rc = range_count_column(*work, ranges, qi)) return rc;
-    if (int rc = docset_finish(segs, n_segs, docsets[qi], qi, call)) return rc;
-  }
+  if (int rc = docset_check(
+          segs, n_segs, docsets, n_queries, call, [&](int qi) { return range_count_begin(segs, n_segs, ranges[qi], out ? &out[qi] : nullptr, qi, work); },
+          [&](int qi) {
+            if (work->kinds[(size_t)qi] < 0) return no_column(qi, ranges[qi].field_id);
+            return range_count_column(*work, ranges, qi);
+          },
+          [](int) { return (int)NRTGPU_OK; }))
+    return rc;
   work->layout(ranges, n_queries);
   work->seal();
   return NRTGPU_OK;
 }
+template <bool MULTI>
+void launch_ranges(hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
+  const RangeWork* w = (const RangeWork*)a.own_user;
+  const char* d_plan = (const char*)d_extra[0];
+  launch_docset_range_count(st, w->wide, MULTI, a, (const DRangeCountQuery*)d_plan, (const DRangeQuery*)d_extra[1], (const DSortPart*)d_extra[2],
+                            (const DSortPart*)d_extra[3], d_plan + (size_t)w->n_queries * sizeof(DRangeCountQuery), (uint32_t*)a.own);
+}
 
 }  // namespace
 
-extern "C" int nrtgpu_count_docset_ranges_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* d,
-                                                    const nrtgpu_range_count* r) {
-  if (int rc = final_score_enter(ctx, segs, n_segs, !d || !r, nullptr)) return rc;
-  SegReadLocks content(segs, n_segs);
-  DocsetCall call;
-  RangeWork work;
-  if (int rc = check_ranges(segs, n_segs, d, r, nullptr, 1, &call, &work)) return rc;
-  HostPlan hp;
-  return docset_plan(ctx, segs, nullptr, n_segs, call.masks.data(), 1, hp);
-}
-
-extern "C" int nrtgpu_count_docset_ranges_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
-                                                const nrtgpu_docset_query* docsets, const nrtgpu_range_count* ranges, int32_t n_queries,
-                                                nrtgpu_range_counts* out) {
-  if (int rc = final_score_enter(ctx, segs, n_segs, !docsets || !ranges || !out, &n_queries)) return rc;
-  const double t0 = now_ms();
-  SegReadLocks content(segs, n_segs);   // until this call's kernels have finished
-  DocsetCall call;
-  RangeWork work;
-  if (int rc = check_ranges(segs, n_segs, docsets, ranges, out, n_queries, &call, &work)) return rc;
-  HostPlan hp;
-  if (int rc = docset_plan(ctx, segs, doc_bases, n_segs, call.masks.data(), n_queries, hp)) return rc;
-  std::vector<DSortPart> sparts, rparts;   // (the doc set's range clauses' columns are 32-bit ones: docset_parts' walk; the count's are read below)
-  std::vector<int32_t> no_field((size_t)n_queries, -1);
-  docset_parts(segs, docsets, no_field.data(), hp, &sparts, &rparts);
-  for (const DItem& it : hp.items)
-    for (uint32_t pi = 0; pi < it.n_parts; ++pi) {
-      const size_t at = (size_t)it.part_begin + pi;
-      sparts[at] = range_count_column_of(segs[hp.part_leaf[at]], ranges[it.query].field_id, work.wide);
-    }
-  const PlanBytes extras[4] = {{work.plan_bytes.data(), work.plan_bytes.size()},
-                               {call.ranges.data(), call.ranges.size() * sizeof(DRangeQuery)},
-                               {sparts.data(), sparts.size() * sizeof(DSortPart)},
-                               {rparts.data(), rparts.size() * sizeof(DSortPart)}};
-  std::vector<nrtgpu_topdocs> pages((size_t)n_queries, nrtgpu_topdocs{});   // (no hits come back: the merge's lists are empty; total_hits is read from them)
-  const FinalScoreOwn own{work.bytes, range_collect, &work};
-  const FinalScoreLaunch single = [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
-    const RangeWork* w = (const RangeWork*)a.own_user;
-    const char* d_plan = (const char*)d_extra[0];
-    launch_docset_range_count(st, w->wide, false, a, (const DRangeCountQuery*)d_plan, (const DRangeQuery*)d_extra[1], (const DSortPart*)d_extra[2],
-                              (const DSortPart*)d_extra[3], d_plan + (size_t)w->n_queries * sizeof(DRangeCountQuery), (uint32_t*)a.own);
-  };
-  const FinalScoreLaunch multi = [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
-    const RangeWork* w = (const RangeWork*)a.own_user;
-    const char* d_plan = (const char*)d_extra[0];
-    launch_docset_range_count(st, w->wide, true, a, (const DRangeCountQuery*)d_plan, (const DRangeQuery*)d_extra[1], (const DSortPart*)d_extra[2],
-                              (const DSortPart*)d_extra[3], d_plan + (size_t)w->n_queries * sizeof(DRangeCountQuery), (uint32_t*)a.own);
-  };
-  if (int rc = final_score_run(ctx, hp, call.masks.data(), n_queries, pages.data(), t0, extras, 4, call.any_multi ? multi : single, &own)) return rc;
-  return range_unpack(work, ranges, pages.data(), n_queries, out);
-}
-
 extern "C" int nrtgpu_docset_sorted_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* d,
                                               const nrtgpu_field_sort* s) {
-  if (int rc = final_score_enter(ctx, segs, n_segs, !d || !s, nullptr)) return rc;
-  SegReadLocks content(segs, n_segs);
-  DocsetCall call;
-  std::vector<DSortQuery> records;
-  std::vector<int> kinds;
-  if (int rc = check_sorted(segs, n_segs, d, s, 1, &call, &records, &kinds)) return rc;
-  HostPlan hp;   // the planner is the predicate for the leaves (sealed, of this context) and the accept sets
-  return docset_plan(ctx, segs, nullptr, n_segs, call.masks.data(), 1, hp);
+  return docset_supported(ctx, segs, n_segs, !d || !s, [&](DocsetCall* call) {
+    std::vector<DSortQuery> records;
+    std::vector<int> kinds;
+    return check_sorted(segs, n_segs, d, s, 1, call, &records, &kinds);
+  });
 }
 
 extern "C" int nrtgpu_search_docset_sorted_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
@@ -314,43 +337,21 @@ extern "C" int nrtgpu_search_docset_sorted_batch(nrtgpu_ctx* ctx, const nrtgpu_s
   std::vector<DSortQuery> records;
   std::vector<int> kinds;
   if (int rc = check_sorted(segs, n_segs, docsets, sorts, n_queries, &call, &records, &kinds)) return rc;
-  HostPlan hp;
-  if (int rc = docset_plan(ctx, segs, doc_bases, n_segs, call.masks.data(), n_queries, hp)) return rc;
-  std::vector<DSortPart> sparts, rparts;
-  std::vector<int32_t> field_ids((size_t)n_queries);
-  for (int qi = 0; qi < n_queries; ++qi) field_ids[(size_t)qi] = sorts[qi].field_id;
-  docset_parts(segs, docsets, field_ids.data(), hp, &sparts, &rparts);
-  const PlanBytes extras[4] = {{records.data(), records.size() * sizeof(DSortQuery)},
-                               {call.ranges.data(), call.ranges.size() * sizeof(DRangeQuery)},
-                               {sparts.data(), sparts.size() * sizeof(DSortPart)},
-                               {rparts.data(), rparts.size() * sizeof(DSortPart)}};
   nrtgpu_topdocs* pages = reinterpret_cast<nrtgpu_topdocs*>(out);   // (the layout is the same: fieldsort.cpp's static_assert)
-  // the dispatch: a call whose range columns are all single-valued launches what it always launched
-  const FinalScoreLaunch single = [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
-    launch_docset_sort(st, a, (const DSortQuery*)d_extra[0], (const DRangeQuery*)d_extra[1], (const DSortPart*)d_extra[2], (const DSortPart*)d_extra[3]);
-  };
-  const FinalScoreLaunch multi = [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
-    launch_docset_sort_multi(st, a, (const DSortQuery*)d_extra[0], (const DRangeQuery*)d_extra[1], (const DSortPart*)d_extra[2], (const DSortPart*)d_extra[3]);
-  };
-  if (int rc = final_score_run(ctx, hp, call.masks.data(), n_queries, pages, t0, extras, 4, call.any_multi ? multi : single)) return rc;
-  for (int qi = 0; qi < n_queries; ++qi) {   // key high words -> the values the hits sorted as
-    uint32_t* v = out[qi].value_bits;
-    const uint32_t reverse = records[(size_t)qi].reverse;
-    for (int32_t i = 0; v && i < out[qi].n_hits; ++i) v[i] = doc_value_bits(kinds[(size_t)qi], reverse != 0u ? v[i] : ~v[i]);
-  }
+  if (int rc = docset_run(ctx, segs, doc_bases, n_segs, docsets, n_queries, call, t0, {records.data(), records.size() * sizeof(DSortQuery)},
+                          [&](uint32_t q) { return sorts[q].field_id; }, false, {launch_sorted<false>, launch_sorted<true>}, pages, nullptr))
+    return rc;
+  field_sort_values(records, kinds, n_queries, out);
   return NRTGPU_OK;
 }
 
 extern "C" int nrtgpu_docset_sorted64_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* d,
                                                 const nrtgpu_field_sort64* s) {
-  if (int rc = final_score_enter(ctx, segs, n_segs, !d || !s, nullptr)) return rc;
-  SegReadLocks content(segs, n_segs);
-  DocsetCall call;
-  std::vector<DSort64Query> records;
-  std::vector<int> kinds;
-  if (int rc = check_sorted64(segs, nullptr, n_segs, true, d, s, 1, &call, &records, &kinds)) return rc;
-  HostPlan hp;
-  return docset_plan(ctx, segs, nullptr, n_segs, call.masks.data(), 1, hp);
+  return docset_supported(ctx, segs, n_segs, !d || !s, [&](DocsetCall* call) {
+    std::vector<DSort64Query> records;
+    std::vector<int> kinds;
+    return check_sorted64(segs, nullptr, n_segs, true, d, s, 1, call, &records, &kinds);
+  });
 }
 
 extern "C" int nrtgpu_search_docset_sorted64_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
@@ -363,46 +364,24 @@ extern "C" int nrtgpu_search_docset_sorted64_batch(nrtgpu_ctx* ctx, const nrtgpu
   std::vector<DSort64Query> records;
   std::vector<int> kinds;
   if (int rc = check_sorted64(segs, doc_bases, n_segs, false, docsets, sorts, n_queries, &call, &records, &kinds)) return rc;
-  HostPlan hp;
-  if (int rc = docset_plan(ctx, segs, doc_bases, n_segs, call.masks.data(), n_queries, hp)) return rc;
-  std::vector<DSortPart> unused, rparts;   // (the range clauses' columns are 32-bit ones: docset_parts' walk; the sort's are read below)
-  std::vector<int32_t> no_field((size_t)n_queries, -1);
-  docset_parts(segs, docsets, no_field.data(), hp, &unused, &rparts);
-  std::vector<DSort64Part> sparts(hp.parts.size(), DSort64Part{nullptr, nullptr});
-  for (const DItem& it : hp.items)
-    for (uint32_t pi = 0; pi < it.n_parts; ++pi) {
-      const size_t at = (size_t)it.part_begin + pi;
-      sparts[at] = doc_values_column64(segs[hp.part_leaf[at]], sorts[it.query].field_id);
-    }
-  const PlanBytes extras[4] = {{records.data(), records.size() * sizeof(DSort64Query)},
-                               {call.ranges.data(), call.ranges.size() * sizeof(DRangeQuery)},
-                               {sparts.data(), sparts.size() * sizeof(DSort64Part)},
-                               {rparts.data(), rparts.size() * sizeof(DSortPart)}};
-  const FinalScoreLaunch single = [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
-    launch_docset_sort64(st, a, (const DSort64Query*)d_extra[0], (const DRangeQuery*)d_extra[1], (const DSort64Part*)d_extra[2], (const DSortPart*)d_extra[3]);
-  };
-  const FinalScoreLaunch multi = [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
-    launch_docset_sort64_multi(st, a, (const DSort64Query*)d_extra[0], (const DRangeQuery*)d_extra[1], (const DSort64Part*)d_extra[2], (const DSortPart*)d_extra[3]);
-  };
   std::vector<int32_t> ks((size_t)n_queries);
   for (int qi = 0; qi < n_queries; ++qi) ks[(size_t)qi] = docsets[qi].k;
   Sort64Pages pages(ks.data(), out, n_queries);
-  if (int rc = final_score_run(ctx, hp, call.masks.data(), n_queries, pages.pages.data(), t0, extras, 4, call.any_multi ? multi : single)) return rc;
+  if (int rc = docset_run(ctx, segs, doc_bases, n_segs, docsets, n_queries, call, t0, {records.data(), records.size() * sizeof(DSort64Query)},
+                          [&](uint32_t q) { return sorts[q].field_id; }, true, {launch_sorted64<false>, launch_sorted64<true>}, pages.pages.data(), nullptr))
+    return rc;
   pages.decode(records, kinds, out);
   return NRTGPU_OK;
 }
 
 extern "C" int nrtgpu_count_docset_terms_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* d,
                                                    const nrtgpu_terms_count* t) {
-  if (int rc = final_score_enter(ctx, segs, n_segs, !d || !t, nullptr)) return rc;
-  SegReadLocks content(segs, n_segs);
-  DocsetCall call;
-  std::vector<DTermsQuery> records;
-  std::vector<int> kinds;
-  TermsWork work;
-  if (int rc = check_terms(segs, n_segs, d, t, nullptr, 1, &call, &records, &kinds, &work)) return rc;
-  HostPlan hp;
-  return docset_plan(ctx, segs, nullptr, n_segs, call.masks.data(), 1, hp);
+  return docset_supported(ctx, segs, n_segs, !d || !t, [&](DocsetCall* call) {
+    std::vector<DTermsQuery> records;
+    std::vector<int> kinds;
+    TermsWork work;
+    return check_terms(segs, n_segs, d, t, (const nrtgpu_term_counts*)nullptr, 1, call, &records, &kinds, &work);
+  });
 }
 
 extern "C" int nrtgpu_count_docset_terms_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
@@ -415,49 +394,23 @@ extern "C" int nrtgpu_count_docset_terms_batch(nrtgpu_ctx* ctx, const nrtgpu_seg
   std::vector<DTermsQuery> records;
   std::vector<int> kinds;
   TermsWork work;
-  if (int rc = check_terms(segs, n_segs, docsets, terms, out, n_queries, &call, &records, &kinds, &work)) return rc;
-  HostPlan hp;
-  if (int rc = docset_plan(ctx, segs, doc_bases, n_segs, call.masks.data(), n_queries, hp)) return rc;
-  std::vector<DSortPart> sparts, rparts;
-  std::vector<int32_t> field_ids((size_t)n_queries);
-  for (int qi = 0; qi < n_queries; ++qi) field_ids[(size_t)qi] = terms[qi].field_id;
-  docset_parts(segs, docsets, field_ids.data(), hp, &sparts, &rparts);
-  const PlanBytes extras[4] = {{records.data(), records.size() * sizeof(DTermsQuery)},
-                               {call.ranges.data(), call.ranges.size() * sizeof(DRangeQuery)},
-                               {sparts.data(), sparts.size() * sizeof(DSortPart)},
-                               {rparts.data(), rparts.size() * sizeof(DSortPart)}};
-  std::vector<nrtgpu_topdocs> pages((size_t)n_queries, nrtgpu_topdocs{});   // (no hits come back: the merge's lists are empty; total_hits is read from them)
+  if (int rc = check_terms(segs, n_segs, docsets, terms, (const nrtgpu_term_counts*)out, n_queries, &call, &records, &kinds, &work)) return rc;
+  std::vector<nrtgpu_topdocs> pages = no_pages(n_queries);
   const FinalScoreOwn own{work.bytes, terms_collect, &work};
-  // the dispatch: a call whose count and range columns are all single-valued launches what it always launched
-  const FinalScoreLaunch single = [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
-    const TermsWork* w = (const TermsWork*)a.own_user;
-    char* d_own = (char*)a.own;
-    launch_docset_terms_count(st, a, (const DTermsQuery*)d_extra[0], (const DRangeQuery*)d_extra[1], (const DSortPart*)d_extra[2], (const DSortPart*)d_extra[3],
-                              (DTermsState*)(d_own + w->o_states), (unsigned long long*)(d_own + w->o_tables), (unsigned long long*)(d_own + w->o_out),
-                              (uint32_t)w->n_queries, w->out_cap);
-  };
-  const FinalScoreLaunch multi = [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
-    const TermsWork* w = (const TermsWork*)a.own_user;
-    char* d_own = (char*)a.own;
-    launch_docset_terms_count_multi(st, a, (const DTermsQuery*)d_extra[0], (const DRangeQuery*)d_extra[1], (const DSortPart*)d_extra[2],
-                                    (const DSortPart*)d_extra[3], (DTermsState*)(d_own + w->o_states), (unsigned long long*)(d_own + w->o_tables),
-                                    (unsigned long long*)(d_own + w->o_out), (uint32_t)w->n_queries, w->out_cap);
-  };
-  if (int rc = final_score_run(ctx, hp, call.masks.data(), n_queries, pages.data(), t0, extras, 4, call.any_multi ? multi : single, &own)) return rc;
+  if (int rc = docset_run(ctx, segs, doc_bases, n_segs, docsets, n_queries, call, t0, {records.data(), records.size() * sizeof(DTermsQuery)},
+                          [&](uint32_t q) { return terms[q].field_id; }, false, {launch_terms<false>, launch_terms<true>}, pages.data(), &own))
+    return rc;
   return terms_unpack(work, kinds, pages.data(), n_queries, out);
 }
 
 extern "C" int nrtgpu_count_docset_terms64_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* d,
                                                      const nrtgpu_terms_count* t) {
-  if (int rc = final_score_enter(ctx, segs, n_segs, !d || !t, nullptr)) return rc;
-  SegReadLocks content(segs, n_segs);
-  DocsetCall call;
-  std::vector<DTermsQuery> records;
-  std::vector<int> kinds;
-  TermsWork64 work;
-  if (int rc = check_terms64(segs, n_segs, d, t, nullptr, 1, &call, &records, &kinds, &work)) return rc;
-  HostPlan hp;
-  return docset_plan(ctx, segs, nullptr, n_segs, call.masks.data(), 1, hp);
+  return docset_supported(ctx, segs, n_segs, !d || !t, [&](DocsetCall* call) {
+    std::vector<DTermsQuery> records;
+    std::vector<int> kinds;
+    TermsWork64 work;
+    return check_terms(segs, n_segs, d, t, (const nrtgpu_term_counts64*)nullptr, 1, call, &records, &kinds, &work);
+  });
 }
 
 extern "C" int nrtgpu_count_docset_terms64_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
@@ -470,43 +423,36 @@ extern "C" int nrtgpu_count_docset_terms64_batch(nrtgpu_ctx* ctx, const nrtgpu_s
   std::vector<DTermsQuery> records;
   std::vector<int> kinds;
   TermsWork64 work;
-  if (int rc = check_terms64(segs, n_segs, docsets, terms, out, n_queries, &call, &records, &kinds, &work)) return rc;
-  HostPlan hp;
-  if (int rc = docset_plan(ctx, segs, doc_bases, n_segs, call.masks.data(), n_queries, hp)) return rc;
-  std::vector<DSortPart> unused, rparts;   // (the range clauses' columns are 32-bit ones: docset_parts' walk; the count's are read below)
-  std::vector<int32_t> no_field((size_t)n_queries, -1);
-  docset_parts(segs, docsets, no_field.data(), hp, &unused, &rparts);
-  std::vector<DSort64Part> sparts(hp.parts.size(), DSort64Part{nullptr, nullptr});
-  for (const DItem& it : hp.items)
-    for (uint32_t pi = 0; pi < it.n_parts; ++pi) {
-      const size_t at = (size_t)it.part_begin + pi;
-      sparts[at] = doc_values_column64(segs[hp.part_leaf[at]], terms[it.query].field_id);
-    }
-  const PlanBytes extras[4] = {{records.data(), records.size() * sizeof(DTermsQuery)},
-                               {call.ranges.data(), call.ranges.size() * sizeof(DRangeQuery)},
-                               {sparts.data(), sparts.size() * sizeof(DSort64Part)},
-                               {rparts.data(), rparts.size() * sizeof(DSortPart)}};
-  std::vector<nrtgpu_topdocs> pages((size_t)n_queries, nrtgpu_topdocs{});   // (no hits come back: the merge's lists are empty; total_hits is read from them)
+  if (int rc = check_terms(segs, n_segs, docsets, terms, (const nrtgpu_term_counts64*)out, n_queries, &call, &records, &kinds, &work)) return rc;
+  std::vector<nrtgpu_topdocs> pages = no_pages(n_queries);
   const FinalScoreOwn own{work.bytes, terms64_collect, &work};
-  // the dispatch: a call whose range columns are all single-valued launches the kernel without the walk of their values
-  const FinalScoreLaunch single = [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
-    const TermsWork64* w = (const TermsWork64*)a.own_user;
-    DTermsState64* states;
-    unsigned long long *keys, *out_codes;
-    uint32_t *counts, *out_counts;
-    terms64_regions(*w, (char*)a.own, &states, &keys, &counts, &out_codes, &out_counts);
-    launch_docset_terms_count64(st, false, a, (const DTermsQuery*)d_extra[0], (const DRangeQuery*)d_extra[1], (const DSort64Part*)d_extra[2],
-                                (const DSortPart*)d_extra[3], states, keys, counts, out_codes, out_counts, (uint32_t)w->n_queries, w->out_cap);
-  };
-  const FinalScoreLaunch multi = [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
-    const TermsWork64* w = (const TermsWork64*)a.own_user;
-    DTermsState64* states;
-    unsigned long long *keys, *out_codes;
-    uint32_t *counts, *out_counts;
-    terms64_regions(*w, (char*)a.own, &states, &keys, &counts, &out_codes, &out_counts);
-    launch_docset_terms_count64(st, true, a, (const DTermsQuery*)d_extra[0], (const DRangeQuery*)d_extra[1], (const DSort64Part*)d_extra[2],
-                                (const DSortPart*)d_extra[3], states, keys, counts, out_codes, out_counts, (uint32_t)w->n_queries, w->out_cap);
-  };
-  if (int rc = final_score_run(ctx, hp, call.masks.data(), n_queries, pages.data(), t0, extras, 4, call.any_multi ? multi : single, &own)) return rc;
+  if (int rc = docset_run(ctx, segs, doc_bases, n_segs, docsets, n_queries, call, t0, {records.data(), records.size() * sizeof(DTermsQuery)},
+                          [&](uint32_t q) { return terms[q].field_id; }, true, {launch_terms64<false>, launch_terms64<true>}, pages.data(), &own))
+    return rc;
   return terms64_unpack(work, kinds, pages.data(), n_queries, out);
+}
+
+extern "C" int nrtgpu_count_docset_ranges_supported(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_docset_query* d,
+                                                    const nrtgpu_range_count* r) {
+  return docset_supported(ctx, segs, n_segs, !d || !r, [&](DocsetCall* call) {
+    RangeWork work;
+    return check_ranges(segs, n_segs, d, r, nullptr, 1, call, &work);
+  });
+}
+
+extern "C" int nrtgpu_count_docset_ranges_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* doc_bases, int32_t n_segs,
+                                                const nrtgpu_docset_query* docsets, const nrtgpu_range_count* ranges, int32_t n_queries,
+                                                nrtgpu_range_counts* out) {
+  if (int rc = final_score_enter(ctx, segs, n_segs, !docsets || !ranges || !out, &n_queries)) return rc;
+  const double t0 = now_ms();
+  SegReadLocks content(segs, n_segs);   // until this call's kernels have finished
+  DocsetCall call;
+  RangeWork work;
+  if (int rc = check_ranges(segs, n_segs, docsets, ranges, out, n_queries, &call, &work)) return rc;
+  std::vector<nrtgpu_topdocs> pages = no_pages(n_queries);
+  const FinalScoreOwn own{work.bytes, range_collect, &work};
+  if (int rc = docset_run(ctx, segs, doc_bases, n_segs, docsets, n_queries, call, t0, {work.plan_bytes.data(), work.plan_bytes.size()},
+                          [&](uint32_t q) { return ranges[q].field_id; }, work.wide, {launch_ranges<false>, launch_ranges<true>}, pages.data(), &own))
+    return rc;
+  return range_unpack(work, ranges, pages.data(), n_queries, out);
 }

@@ -101,19 +101,20 @@ int doc_values_query(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu
   return NRTGPU_OK;
 }
 
-// What the sorted routes refuse of a nrtgpu_field_sort as an invalid argument, and its side of the query's record (kind: of the
-// column over the leaves; `need` is the caller's).
-int field_sort_check(const nrtgpu_field_sort& s, int qi) {
-  if (s.reverse != 0 && s.reverse != 1) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: reverse %d outside 0..1", qi, s.reverse);
-  if (s.has_after != 0 && s.has_after != 1) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: the sort's has_after %d outside 0..1", qi, s.has_after);
-  if (s.has_after != 0 && s.after_doc < 0) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: after_doc %d", qi, s.after_doc);
-  return NRTGPU_OK;
-}
+// The sort's side of the query's record (kind: of the column over the leaves; `need` is the caller's).
 void field_sort_record(const nrtgpu_field_sort& s, int kind, DSortQuery* r) {
   r->reverse = (uint32_t)s.reverse;
   r->missing_code = doc_value_code(kind, s.missing_bits);
   r->has_after = (uint32_t)s.has_after;
   r->after_key = s.has_after ? sort_key(r->reverse, doc_value_code(kind, s.after_bits), (uint32_t)s.after_doc) : ~0ull;
+}
+
+void field_sort_values(const std::vector<DSortQuery>& records, const std::vector<int>& kinds, int32_t n_queries, nrtgpu_fielddocs* out) {
+  for (int qi = 0; qi < n_queries; ++qi) {
+    uint32_t* v = out[qi].value_bits;
+    const uint32_t reverse = records[(size_t)qi].reverse;
+    for (int32_t i = 0; v && i < out[qi].n_hits; ++i) v[i] = doc_value_bits(kinds[(size_t)qi], reverse != 0u ? v[i] : ~v[i]);
+  }
 }
 
 // The leaf of every part.  A part names its (query, leaf) pair by its first DTerm (HostPlan.qs_begin).
@@ -218,10 +219,6 @@ extern "C" int nrtgpu_search_sorted_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* con
         launch_bm25_field_sort(st, a, (const DSortQuery*)d_extra[0], (const DSortPart*)d_extra[1]);
       }))
     return rc;
-  for (int qi = 0; qi < n_queries; ++qi) {   // key high words -> the values the hits sorted as
-    uint32_t* v = out[qi].value_bits;
-    const uint32_t reverse = records[(size_t)qi].reverse;
-    for (int32_t i = 0; v && i < out[qi].n_hits; ++i) v[i] = doc_value_bits(kinds[(size_t)qi], reverse != 0u ? v[i] : ~v[i]);
-  }
+  field_sort_values(records, kinds, n_queries, out);
   return NRTGPU_OK;
 }

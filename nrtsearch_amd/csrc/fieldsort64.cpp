@@ -38,13 +38,6 @@ extern "C" int nrtgpu_sort_key64(int32_t kind, int32_t reverse, uint64_t lo_bits
 namespace nrtgpu {
 namespace rt {
 
-int field_sort64_check(const nrtgpu_field_sort64& s, int qi) {
-  if (s.reverse != 0 && s.reverse != 1) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: reverse %d outside 0..1", qi, s.reverse);
-  if (s.has_after != 0 && s.has_after != 1) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: the sort's has_after %d outside 0..1", qi, s.has_after);
-  if (s.has_after != 0 && s.after_doc < 0) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: after_doc %d", qi, s.after_doc);
-  return NRTGPU_OK;
-}
-
 int field_sort64_narrow(int qi, int32_t field_id, bool multi, const char* entry32) {
   return fail(NRTGPU_ERR_UNSUPPORTED, "query %d: the doc values of field %d are a %s column: sort by it with %s", qi, field_id,
               multi ? "multi-valued 32-bit" : "32-bit", entry32);
@@ -148,7 +141,7 @@ int check_call64(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32_t* 
   for (int qi = 0; qi < n_queries; ++qi) {
     const nrtgpu_bm25_query& q = queries[qi];
     if (int rc = validate_query(q, qi)) return rc;
-    if (int rc = field_sort64_check(sorts[qi], qi)) return rc;
+    if (int rc = field_sort_check(sorts[qi], qi)) return rc;
     if (q.has_after != 0) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: the query's has_after must be 0 (the cursor of a sorted search lives in the sort)", qi);
     int kind = -1;
     bool m = false;

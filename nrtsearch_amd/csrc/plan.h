@@ -694,14 +694,14 @@ static_assert(sizeof(DSortQuery) == 32, "DSortQuery layout");
 struct alignas(16) DSortPart {
   const uint32_t* code;    // one code per doc, padded to whole sub-tiles; nullptr: the leaf lacks the column
   const uint64_t* has;     // bit d: doc d has a value; nullptr: every doc has
-                           // A MULTI-VALUED column (below: kTermsQueryMulti / DRangeQuery.multi say which are; the *_multi kernels
+                           // A MULTI-VALUED column (below: kTermsQueryMulti / DRangeQuery.multi say which are; the kernels of such calls
                            // alone read one): `code` is codes[], the values' codes in upload order, and `has` is the uint32 start[]
                            // -- one entry per doc, padded to whole sub-tiles, plus one; doc d's values are codes[start[d] ..
                            // start[d + 1]); every padding entry equals the number of values
 };
 static_assert(sizeof(DSortPart) == 16, "DSortPart layout");
 
-// Sort by a 64-BIT column (fieldsort64.hip: bm25_field_sort64_kernel; docset.hip: docset_sort64_kernel; fieldsort64.cpp): LONG /
+// Sort by a 64-BIT column (fieldsort64.hip: bm25_field_sort64_kernel; docset.hip: docset_sort_kernel under DocsetSort64; fieldsort64.cpp): LONG /
 // DATE_TIME (epoch millis) / DOUBLE doc values.  The column is resident as 64-bit order-preserving codes -- unsigned compares of
 // codes order like Long.compare / Double.compare of the values:
 //   kDocValuesInt64   : bits ^ 1 << 63
@@ -777,6 +777,7 @@ struct alignas(16) DSort64Part {
   const uint64_t* has;     // bit d: doc d has a value; nullptr: every doc has
 };
 static_assert(sizeof(DSort64Part) == 16, "DSort64Part layout");
+static_assert(sizeof(DSort64Part) == sizeof(DSortPart), "a per-part column record is read as either (the range facets' count column; docset.cpp's part walk)");
 
 // Terms aggregation (termscount.hip: bm25_terms_count_kernel, terms_compact_kernel; termscount.cpp): a query's hits counted per
 // distinct value of a doc value column.  A bucket is a column CODE (doc_value_code: ints by value, floats by floatToIntBits with
@@ -854,7 +855,7 @@ struct alignas(16) DTermsState64 {   // DTermsState with the reserved code's cou
 };
 static_assert(sizeof(DTermsState64) == 32, "DTermsState64 layout");
 
-// Doc-set requests (docset.hip: docset_sort_kernel, docset_terms_count_kernel; docset.cpp): a sorted search or a terms count
+// Doc-set requests (docset.hip: docset_sort_kernel, docset_count_kernel; docset.cpp): a sorted search or a terms count
 // whose hit set is a doc set -- liveDocs, FILTER / MUST_NOT masks, numeric range clauses -- and no text clause.  The parts of
 // such a plan have no clauses (n_terms == 0) and DPart.live_bits is the query's combined accept set WITH liveDocs (there are no
 // postings to fold them into; nullptr: every doc below max_doc).  Beside the plan go the sorted / counting route's own records
@@ -868,7 +869,7 @@ __host__ __device__ inline bool range_accepts_code(uint32_t lo_code, uint32_t hi
 struct alignas(16) DRangeQuery {
   uint32_t n_ranges;            // 0..kMaxRanges
   uint32_t multi;               // bit r: clause r's column is multi-valued -- the doc passes iff SOME value of it is in the range
-                                // (read by the *_multi kernels only: a call that sets a bit launches them)
+                                // (read under docset.hip's MULTI only: a call that sets a bit launches those kernels)
   uint32_t pad[2];
   uint32_t lo_code[kMaxRanges];
   uint32_t hi_code[kMaxRanges];
@@ -915,7 +916,7 @@ __host__ __device__ inline bool value_set_has(P set, uint32_t len, uint32_t code
   return set[base] == code;
 }
 
-// Numeric range facets (rangecount.hip: bm25_range_count_kernel; docset.hip: docset_range_count_kernel; rangecount.cpp): a
+// Numeric range facets (rangecount.hip: bm25_range_count_kernel; docset.hip: DocsetRanges; rangecount.cpp): a
 // query's hits counted per requested value range [lower, upper], both inclusive, of a single-valued column of any of the four
 // kinds.  Ranges may overlap, nest, repeat or touch, so the device does not count per range: it counts per ELEMENTARY INTERVAL
 // (Lucene's LongRangeCounter construction [Lucene-recall]).  In code space (doc_value_code / doc_value_code64) the cut points of

@@ -67,22 +67,17 @@ void launch_bm25_field_sort(hipStream_t stream, const FinalScoreArgs& a, const D
 void launch_bm25_terms_count(hipStream_t stream, const FinalScoreArgs& a, const DTermsQuery* tqueries, const DSortPart* sparts, DTermsState* states,
                              unsigned long long* tables, unsigned long long* out, uint32_t n_queries, uint32_t out_cap);
 // doc-set requests (docset.hip): the sorted / counting route's per-query record, one DRangeQuery per query, one DSortPart per part
-// for the sort / count column and kMaxRanges per part for the range clauses' columns
-void launch_docset_sort(hipStream_t stream, const FinalScoreArgs& a, const DSortQuery* squeries, const DRangeQuery* rqueries, const DSortPart* sparts,
-                        const DSortPart* rparts);
-void launch_docset_terms_count(hipStream_t stream, const FinalScoreArgs& a, const DTermsQuery* tqueries, const DRangeQuery* rqueries, const DSortPart* sparts,
-                               const DSortPart* rparts, DTermsState* states, unsigned long long* tables, unsigned long long* out, uint32_t n_queries,
-                               uint32_t out_cap);
-// the same three over calls that name a multi-valued column (termscount.hip: bm25_terms_count_multi_kernel; docset.hip:
-// docset_sort_multi_kernel, docset_terms_count_multi_kernel): a column's arity is the query's / the clause's flag (plan.h:
-// kTermsQueryMulti, DRangeQuery.multi), so a batch that mixes arities is one launch
+// for the sort / count column and kMaxRanges per part for the range clauses' columns.  multi: the call names a multi-valued
+// column (a range clause's, the 32-bit count's): a column's arity is the clause's / the query's flag (plan.h: DRangeQuery.multi,
+// kTermsQueryMulti), so a batch that mixes arities is one launch.  Their siblings over 64-bit columns and the range facets: below
+void launch_docset_sort(hipStream_t stream, bool multi, const FinalScoreArgs& a, const DSortQuery* squeries, const DRangeQuery* rqueries,
+                        const DSortPart* sparts, const DSortPart* rparts);
+void launch_docset_terms_count(hipStream_t stream, bool multi, const FinalScoreArgs& a, const DTermsQuery* tqueries, const DRangeQuery* rqueries,
+                               const DSortPart* sparts, const DSortPart* rparts, DTermsState* states, unsigned long long* tables, unsigned long long* out,
+                               uint32_t n_queries, uint32_t out_cap);
+// the text route's terms count over calls that name a multi-valued column (termscount.hip: bm25_terms_count_multi_kernel)
 void launch_bm25_terms_count_multi(hipStream_t stream, const FinalScoreArgs& a, const DTermsQuery* tqueries, const DSortPart* sparts, DTermsState* states,
                                    unsigned long long* tables, unsigned long long* out, uint32_t n_queries, uint32_t out_cap);
-void launch_docset_sort_multi(hipStream_t stream, const FinalScoreArgs& a, const DSortQuery* squeries, const DRangeQuery* rqueries, const DSortPart* sparts,
-                              const DSortPart* rparts);
-void launch_docset_terms_count_multi(hipStream_t stream, const FinalScoreArgs& a, const DTermsQuery* tqueries, const DRangeQuery* rqueries,
-                                     const DSortPart* sparts, const DSortPart* rparts, DTermsState* states, unsigned long long* tables, unsigned long long* out,
-                                     uint32_t n_queries, uint32_t out_cap);
 // a filter mask of one leaf from its doc value columns (valuemask.hip): n_clauses DValueClause, the IN_SET clauses' code sets
 // (n_set_codes codes in all, staged in LDS), n_words words out
 void launch_value_mask(hipStream_t stream, const DValueClause* clauses, uint32_t n_clauses, const uint32_t* sets, uint32_t n_set_codes, uint64_t* out,
@@ -92,10 +87,8 @@ void launch_value_mask64(hipStream_t stream, const DValueClause64* clauses, uint
 // sort by a 64-bit column (fieldsort64.hip, docset.hip): one DSort64Query per query, one DSort64Part per part; the doc-set form
 // with the doc set's DRangeQuery per query and its kMaxRanges 32-bit DSortPart per part
 void launch_bm25_field_sort64(hipStream_t stream, const FinalScoreArgs& a, const DSort64Query* squeries, const DSort64Part* sparts);
-void launch_docset_sort64(hipStream_t stream, const FinalScoreArgs& a, const DSort64Query* squeries, const DRangeQuery* rqueries, const DSort64Part* sparts,
-                          const DSortPart* rparts);
-void launch_docset_sort64_multi(hipStream_t stream, const FinalScoreArgs& a, const DSort64Query* squeries, const DRangeQuery* rqueries,
-                                const DSort64Part* sparts, const DSortPart* rparts);
+void launch_docset_sort64(hipStream_t stream, bool multi, const FinalScoreArgs& a, const DSort64Query* squeries, const DRangeQuery* rqueries,
+                          const DSort64Part* sparts, const DSortPart* rparts);
 // numeric range facets (rangecount.hip, docset.hip): one DRangeCountQuery per query, the call's cut array (uint32 codes, or uint64
 // when `wide`), one DSortPart per part whose `code` is the count column at that width, the call's uint32 interval counters
 void launch_bm25_range_count(hipStream_t stream, bool wide, const FinalScoreArgs& a, const DRangeCountQuery* rqueries, const DSortPart* sparts,
@@ -1230,9 +1223,18 @@ DSortPart doc_values_column(const nrtgpu_seg* seg, int32_t field_id);
 // clauses a hit matches at least; the query's flat copy is pushed
 int doc_values_query(const nrtgpu_seg* const* segs, int32_t n_segs, const nrtgpu_bm25_query& q, int qi, int kind, int32_t field_id, const char* under,
                      uint32_t* need, FlatQueries* flat);
-// what the sorted routes (this one; docset.cpp) refuse of a nrtgpu_field_sort as an invalid argument, and its side of the record
-int field_sort_check(const nrtgpu_field_sort& s, int qi);
+// what the sorted routes (this one, fieldsort64.cpp, docset.cpp) refuse of a nrtgpu_field_sort / nrtgpu_field_sort64 as an invalid argument
+template <class SORT>
+int field_sort_check(const SORT& s, int qi) {
+  if (s.reverse != 0 && s.reverse != 1) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: reverse %d outside 0..1", qi, s.reverse);
+  if (s.has_after != 0 && s.has_after != 1) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: the sort's has_after %d outside 0..1", qi, s.has_after);
+  if (s.has_after != 0 && s.after_doc < 0) return fail(NRTGPU_ERR_INVALID_ARG, "query %d: after_doc %d", qi, s.after_doc);
+  return NRTGPU_OK;
+}
+// a nrtgpu_field_sort's side of the query's record
 void field_sort_record(const nrtgpu_field_sort& s, int kind, DSortQuery* r);
+// the pages' key high words -> the value bits the hits sorted as (both sorted routes over a 32-bit column, behind final_score_run)
+void field_sort_values(const std::vector<DSortQuery>& records, const std::vector<int>& kinds, int32_t n_queries, nrtgpu_fielddocs* out);
 // NRTGPU_ERR_UNSUPPORTED with the reason: the sort's column is multi-valued (both sorted routes, where they refuse "on no leaf")
 int field_sort_multi(int qi, int32_t field_id);
 // the FILTER / MUST_NOT masks of q are resident on every leaf of the call, else NRTGPU_ERR_UNSUPPORTED naming the query (what
@@ -1250,8 +1252,6 @@ int doc_values_parts(const nrtgpu_seg* const* segs, int32_t n_segs, const int32_
                      std::vector<DSortPart>* out);
 
 // fieldsort64.cpp: what the sorted routes over a 64-bit column share (the text route there; the doc-set form in docset.cpp).
-// what they refuse of a nrtgpu_field_sort64 as an invalid argument (field_sort_check's table)
-int field_sort64_check(const nrtgpu_field_sort64& s, int qi);
 // NRTGPU_ERR_UNSUPPORTED with the reason: the sort's column is a 32-bit one (multi: multi-valued); entry32: the entry that serves it
 int field_sort64_narrow(int qi, int32_t field_id, bool multi, const char* entry32);
 // the bits the call's global docids need: max(1, bit_length(D - 1)), D = max over the leaves of base + max_doc; doc_bases NULL:

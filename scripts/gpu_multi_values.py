@@ -8,7 +8,7 @@ disjunctions), two int columns drawn from the same 1000 distinct values: `multi`
 compaction too).
 
   baselines  nrtgpu_count_terms_batch / nrtgpu_count_docset_terms_batch over `single`: bm25_terms_count_kernel and
-             docset_terms_count_kernel, the kernels a call without a multi-valued column launches -- untouched by the feature
+             docset_count_kernel<DocsetTerms32, false>, the kernels a call without a multi-valued column launches -- untouched by the feature
   multi      the same calls over `multi`: bm25_terms_count_multi_kernel / docset_terms_count_multi_kernel
   mixed      every query but ONE counts `single`, that one counts `multi`: ONE launch of the *_multi kernels -- the price of their
              uniform branches for a single-valued column.  mixed_first: the multi-valued query is query 0 (its items start with

@@ -276,7 +276,7 @@ def _range32_columns(rng, n: int) -> dict:
 
 
 def doc_set_shapes() -> List[dict]:
-    """no range clause; a single-valued one; a multi-valued one (int, float); both beside masks: docset_sort64_kernel<false> and <true>
+    """no range clause; a single-valued one; a multi-valued one (int, float); both beside masks: docset_sort_kernel<DocsetSort64, false> and <true>
     and both MULTI forms of the wide range-count kernel run"""
     i32, f32 = (lambda v: fs.bits_of("int", v)), (lambda v: fs.bits_of("float", v))
     return [dict(), dict(filters=(5,)), dict(must_nots=(6,)),
