@@ -42,8 +42,8 @@ int final_score_plan(nrtgpu_ctx* ctx, const nrtgpu_seg* const* segs, const int32
 // Plan upload, expansion, the route's scorer over all items, merge, per-slice relation: enqueued at once on the slot's stream.
 // The scorer wants the whole GPU like the two scorers of search.cpp and takes its turn among them on the device.
 static int enqueue_final_score(nrtgpu_ctx* ctx, Slot* slot, const HostPlan& hp, int32_t n_queries, const PlanBytes* extras, int n_extras,
-                               FinalScoreLaunch launch, const FinalScoreOwn* own, uint64_t** out_keys, uint32_t** out_counts, uint64_t** out_hits,
-                               const char** d_own) {
+                               FinalScoreLaunch launch, const FinalScoreOwn* own, bool counts_past, uint64_t** out_keys, uint32_t** out_counts,
+                               uint64_t** out_hits, const char** d_own) {
   forget_foreign_hip_error();
   const size_t n_items = hp.items.size();
   PlanLayout L(hp, n_items, (size_t)n_queries, hp.k_stride);   // theta: zeros (no min_competitive_score on these routes), then the kernel's
@@ -54,6 +54,7 @@ static int enqueue_final_score(nrtgpu_ctx* ctx, Slot* slot, const HostPlan& hp, 
   if (int rc = slot->h_plan.reserve(plan_bytes)) return rc;
   if (int rc = slot->d_plan.reserve(plan_bytes)) return rc;
   const size_t o_ssum = L.work.take((size_t)n_queries * hp.n_slices * 4);    // hits per (query, searcher slice): zeroed per call
+  const size_t o_past = counts_past ? L.work.take((size_t)n_queries * hp.n_slices * 4) : 0;   // ... those behind the query's cursor: zeroed with them
   const size_t o_own = own ? L.work.take(own->work_bytes) : 0;                // the route's own output: zeroed with the sums
   if (int rc = slot->d_work.reserve(L.work.off)) return rc;
   char* hb = (char*)slot->h_plan.p;
@@ -81,6 +82,7 @@ static int enqueue_final_score(nrtgpu_ctx* ctx, Slot* slot, const HostPlan& hp, 
   a.caches = (const float*)(db + L.caches);
   a.theta_g = (unsigned long long*)(db + L.theta);
   a.slice_sum = (uint32_t*)(wb + o_ssum);
+  a.slice_past = counts_past ? (uint32_t*)(wb + o_past) : nullptr;
   a.item_keys = (uint64_t*)(wb + L.item_keys);
   a.item_counts = (uint32_t*)(wb + L.item_counts);
   a.item_hits = (uint64_t*)(wb + L.item_hits);
@@ -99,7 +101,8 @@ static int enqueue_final_score(nrtgpu_ctx* ctx, Slot* slot, const HostPlan& hp, 
     launch_merge_topk(st, (uint32_t)n_queries, a.item_keys, a.item_counts, a.item_hits, (const uint32_t*)(db + L.list_idx),
                       (const uint32_t*)(db + L.q_base), (const uint32_t*)(db + L.q_nlists), hp.k_stride, (const uint32_t*)(db + L.q_k),
                       (uint64_t*)(wb + L.out_keys), (uint32_t*)(wb + L.out_counts), (uint64_t*)(wb + L.out_hits), hp.k_stride);
-    launch_slice_relation(st, a.slice_sum, a.queries, hp.n_slices, (uint64_t*)(wb + L.out_hits), (uint32_t)n_queries);
+    if (counts_past) launch_slice_relation_past(st, a.slice_sum, a.slice_past, a.queries, hp.n_slices, (uint64_t*)(wb + L.out_hits), (uint32_t)n_queries);
+    else launch_slice_relation(st, a.slice_sum, a.queries, hp.n_slices, (uint64_t*)(wb + L.out_hits), (uint32_t)n_queries);
     if (timing) HIP_TRY(hipEventRecord(slot->ev2, st));
   }
   HIP_TRY(hipGetLastError());
@@ -111,7 +114,7 @@ static int enqueue_final_score(nrtgpu_ctx* ctx, Slot* slot, const HostPlan& hp, 
 }
 
 int final_score_run(nrtgpu_ctx* ctx, const HostPlan& hp, const nrtgpu_bm25_query* queries, int32_t n_queries, nrtgpu_topdocs* out, double t0,
-                    const PlanBytes* extras, int n_extras, FinalScoreLaunch launch, const FinalScoreOwn* own) {
+                    const PlanBytes* extras, int n_extras, FinalScoreLaunch launch, const FinalScoreOwn* own, bool counts_past) {
   const double plan_ms = now_ms() - t0;
 
   Slot* slot = nullptr;
@@ -128,7 +131,7 @@ int final_score_run(nrtgpu_ctx* ctx, const HostPlan& hp, const nrtgpu_bm25_query
   uint32_t* d_counts = nullptr;
   uint64_t* d_hits = nullptr;
   const char* d_own = nullptr;
-  if (int rc = enqueue_final_score(ctx, slot, hp, n_queries, extras, n_extras, launch, own, &d_keys, &d_counts, &d_hits, &d_own)) return rc;
+  if (int rc = enqueue_final_score(ctx, slot, hp, n_queries, extras, n_extras, launch, own, counts_past, &d_keys, &d_counts, &d_hits, &d_own)) return rc;
   HIP_TRY(hipMemcpyAsync(ho + o_k, d_keys, kb, hipMemcpyDeviceToHost, slot->stream));
   HIP_TRY(hipMemcpyAsync(ho + o_c, d_counts, cb, hipMemcpyDeviceToHost, slot->stream));
   HIP_TRY(hipMemcpyAsync(ho + o_h, d_hits, hb, hipMemcpyDeviceToHost, slot->stream));

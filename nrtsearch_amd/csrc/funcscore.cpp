@@ -145,5 +145,5 @@ extern "C" int nrtgpu_search_function_score_batch(nrtgpu_ctx* ctx, const nrtgpu_
   const PlanBytes extras[2] = {{records.data(), records.size() * sizeof(DFuncQuery)}, {fmasks.data(), fmasks.size() * sizeof(DFuncMasks)}};
   return final_score_run(ctx, hp, queries, n_queries, out, t0, extras, 2, [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
     launch_bm25_function_score(st, a, (const DFuncQuery*)d_extra[0], (const DFuncMasks*)d_extra[1]);
-  });
+  }, nullptr, true);   // (counts the hits behind a cursor per slice: slice_relation_past_kernel)
 }

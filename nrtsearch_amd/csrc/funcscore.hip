@@ -38,7 +38,7 @@ __global__ __launch_bounds__(kScanThreads, kScanWaves / 4)
 void bm25_function_score_kernel(const DItem* __restrict__ items, const DPart* __restrict__ parts, const DTerm* __restrict__ terms,
                                 const DQuery* __restrict__ queries, const float* __restrict__ caches,
                                 const DFuncQuery* __restrict__ fqueries, const DFuncMasks* __restrict__ fmasks,
-                                unsigned long long* __restrict__ theta_g, uint32_t* __restrict__ slice_sum,
+                                unsigned long long* __restrict__ theta_g, uint32_t* __restrict__ slice_sum, uint32_t* __restrict__ slice_past,
                                 uint64_t* __restrict__ item_keys, uint32_t* __restrict__ item_counts, uint64_t* __restrict__ item_hits,
                                 uint32_t k_stride) {
   __shared__ FuncSmem s;
@@ -95,7 +95,7 @@ void bm25_function_score_kernel(const DItem* __restrict__ items, const DPart* __
       const NRT_GLOBAL uint64_t* const live_bits = (const NRT_GLOBAL uint64_t*)part->live_bits;
       const DFuncMasks* const fm = fmasks + part_begin + pi;
       const uint32_t word0 = base >> 6;
-      uint32_t wave_hits = 0;
+      uint32_t wave_hits = 0, wave_past = 0;
 #pragma unroll 2
       for (int j = 0; j < kFinalSlots; ++j) {
         const uint32_t i = lane + 64u * (uint32_t)j;
@@ -111,13 +111,13 @@ void bm25_function_score_kernel(const DItem* __restrict__ items, const DPart* __
             const uint64_t mw = m != nullptr ? m[wi] : ~0ull;
             matched |= (uint32_t)((mw >> lane) & 1ull) << fi;
           }
-          key = final_candidate_key(ok, gdoc0 + i, theta, after_key, wave_hits,
+          key = final_candidate_key(ok, gdoc0 + i, theta, after_key, wave_hits, wave_past,
                                     [fq, matched, v, fx_E](bool* hit) { return function_score_value(*fq, matched, acc_score<true>(v, fx_E), hit); });
         }
         acc[i] = key;
         n_cand += (uint32_t)__popcll(__ballot(key != 0ull));
       }
-      final_count_slice(s.t, part, lane, wave_hits);
+      final_count_slice(s.t, part, lane, wave_hits, wave_past);
     }
     if (lane == 0) s.t.wcount[par][wave] = n_cand;
     __syncthreads();
@@ -149,13 +149,40 @@ void bm25_function_score_kernel(const DItem* __restrict__ items, const DPart* __
     }
   }
 
-  final_epilogue(s.t, cnt, k, q, tid, slice_sum, item_keys, item_counts, item_hits, k_stride);
+  final_epilogue(s.t, cnt, k, q, tid, slice_sum, item_keys, item_counts, item_hits, k_stride, slice_past);
+}
+
+// slice_relation_past_kernel: slice_relation_kernel's rule (kernels.hip) for the routes that also count, per (query, slice), the
+// hits BEHIND the query's cursor (finalscore.hiph: slice_past).  A collector with a cursor counts every hit but queues only those behind it, and publishes no
+// min competitive score before its queue is full: the slice must hold more than the floor AND numHits of them behind the cursor.
+// (slice_relation_kernel leaves that to its caller's test that the merged page is full -- which, with a cursor, several slices
+// can fill together when none of them could alone.)
+__global__ __launch_bounds__(256)
+void slice_relation_past_kernel(const uint32_t* __restrict__ slice_sum, const uint32_t* __restrict__ slice_past, const DQuery* __restrict__ queries,
+                                uint32_t n_slices, uint64_t* __restrict__ out_hits, uint32_t n) {
+  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= n) return;
+  if ((out_hits[q] >> 48) != 0ull) return;
+  const uint32_t floor_ = queries[q].gte_floor;
+  if (floor_ == 0xFFFFFFFFu) return;
+  const uint32_t* sums = slice_sum + queries[q].slice_base;
+  const uint32_t* past = slice_past + queries[q].slice_base;
+  const bool cursor = queries[q].has_after != 0u;
+  const uint32_t k = queries[q].k;
+  bool gte = false;
+  for (uint32_t i = 0; i < n_slices; ++i) gte = gte || (sums[i] > floor_ && (!cursor || past[i] >= k));
+  if (gte) out_hits[q] += kHitsPrunedUnit;
+}
+void launch_slice_relation_past(hipStream_t stream, const uint32_t* slice_sum, const uint32_t* slice_past, const DQuery* queries, uint32_t n_slices,
+                                uint64_t* out_hits, uint32_t n) {
+  if (n == 0) return;
+  hipLaunchKernelGGL(slice_relation_past_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, slice_sum, slice_past, queries, n_slices, out_hits, n);
 }
 
 void launch_bm25_function_score(hipStream_t stream, const FinalScoreArgs& a, const DFuncQuery* fqueries, const DFuncMasks* fmasks) {
   if (a.n_items == 0) return;
   hipLaunchKernelGGL(bm25_function_score_kernel, dim3(a.n_items), dim3(kScanThreads), 0, stream, a.items, a.parts, a.terms, a.queries, a.caches,
-                     fqueries, fmasks, a.theta_g, a.slice_sum, a.item_keys, a.item_counts, a.item_hits, a.k_stride);
+                     fqueries, fmasks, a.theta_g, a.slice_sum, a.slice_past, a.item_keys, a.item_counts, a.item_hits, a.k_stride);
 }
 
 }  // namespace nrtgpu

@@ -79,5 +79,5 @@ extern "C" int nrtgpu_search_function_score_multi_match_batch(nrtgpu_ctx* ctx, c
                                {fmasks.data(), fmasks.size() * sizeof(DFuncMasks)}};
   return final_score_run(ctx, hp, queries, n_queries, out, t0, extras, 3, [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
     launch_bm25_multi_match_function_score(st, a, (const DGroupQuery*)d_extra[0], (const DFuncQuery*)d_extra[1], (const DFuncMasks*)d_extra[2]);
-  });
+  }, nullptr, true);   // (counts the hits behind a cursor per slice: slice_relation_past_kernel)
 }

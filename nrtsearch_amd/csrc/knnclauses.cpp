@@ -241,5 +241,5 @@ extern "C" int nrtgpu_search_text_knn_batch(nrtgpu_ctx* ctx, const nrtgpu_seg* c
   const PlanBytes extras[3] = {{kparts.data(), kparts.size() * sizeof(DKnnPart)}, {st.docs.data(), st.docs.size() * 4}, {st.sums.data(), st.sums.size() * 8}};
   return final_score_run(ctx, hp, queries, n_queries, out, t0, extras, 3, [](hipStream_t s, const FinalScoreArgs& a, const void* const* d_extra) {
     launch_bm25_text_knn(s, a, (const DKnnPart*)d_extra[0], (const uint32_t*)d_extra[1], (const double*)d_extra[2]);
-  });
+  }, nullptr, true);   // (counts the hits behind a cursor per slice: slice_relation_past_kernel)
 }

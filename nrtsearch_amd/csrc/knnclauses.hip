@@ -50,7 +50,7 @@ __global__ __launch_bounds__(kScanThreads, kScanWaves / 4)
 void bm25_text_knn_kernel(const DItem* __restrict__ items, const DPart* __restrict__ parts, const DTerm* __restrict__ terms,
                           const DQuery* __restrict__ queries, const float* __restrict__ caches,
                           const DKnnPart* __restrict__ kparts, const uint32_t* __restrict__ kdocs, const double* __restrict__ ksums,
-                          unsigned long long* __restrict__ theta_g, uint32_t* __restrict__ slice_sum,
+                          unsigned long long* __restrict__ theta_g, uint32_t* __restrict__ slice_sum, uint32_t* __restrict__ slice_past,
                           uint64_t* __restrict__ item_keys, uint32_t* __restrict__ item_counts, uint64_t* __restrict__ item_hits,
                           uint32_t k_stride) {
   __shared__ TextKnnSmem s;
@@ -143,7 +143,7 @@ void bm25_text_knn_kernel(const DItem* __restrict__ items, const DPart* __restri
 
       // ---- (2) sweep: slot lane + 64 j is doc base + 64 j + lane, i.e. bit `lane` of word j of the sub-tile's mask words
       const uint32_t word0 = base >> 6;
-      uint32_t wave_hits = 0;
+      uint32_t wave_hits = 0, wave_past = 0;
 #pragma unroll 2
       for (int j = 0; j < kFinalSlots; ++j) {
         const uint32_t i = lane + 64u * (uint32_t)j;
@@ -153,7 +153,7 @@ void bm25_text_knn_kernel(const DItem* __restrict__ items, const DPart* __restri
           const bool tagged = (v & kKnnTag) != 0ull;
           bool ok = v != 0ull;
           if (accept_bits != nullptr) ok = ok && (tagged || ((accept_bits[word0 + (uint32_t)j] >> lane) & 1ull) != 0ull);
-          key = final_candidate_key(ok, gdoc0 + i, theta, after_key, wave_hits, [tagged, v, fx_E](bool* hit) {
+          key = final_candidate_key(ok, gdoc0 + i, theta, after_key, wave_hits, wave_past, [tagged, v, fx_E](bool* hit) {
             *hit = true;
             return tagged ? __uint_as_float((uint32_t)v) : acc_score<true>(v, fx_E);
           });
@@ -161,7 +161,7 @@ void bm25_text_knn_kernel(const DItem* __restrict__ items, const DPart* __restri
         acc[i] = key;
         n_cand += (uint32_t)__popcll(__ballot(key != 0ull));
       }
-      final_count_slice(s.t, part, lane, wave_hits);
+      final_count_slice(s.t, part, lane, wave_hits, wave_past);
     }
     if (lane == 0) s.t.wcount[par][wave] = n_cand;
     __syncthreads();
@@ -193,13 +193,13 @@ void bm25_text_knn_kernel(const DItem* __restrict__ items, const DPart* __restri
     }
   }
 
-  final_epilogue(s.t, cnt, k, q, tid, slice_sum, item_keys, item_counts, item_hits, k_stride);
+  final_epilogue(s.t, cnt, k, q, tid, slice_sum, item_keys, item_counts, item_hits, k_stride, slice_past);
 }
 
 void launch_bm25_text_knn(hipStream_t stream, const FinalScoreArgs& a, const DKnnPart* kparts, const uint32_t* kdocs, const double* ksums) {
   if (a.n_items == 0) return;
   hipLaunchKernelGGL(bm25_text_knn_kernel, dim3(a.n_items), dim3(kScanThreads), 0, stream, a.items, a.parts, a.terms, a.queries, a.caches,
-                     kparts, kdocs, ksums, a.theta_g, a.slice_sum, a.item_keys, a.item_counts, a.item_hits, a.k_stride);
+                     kparts, kdocs, ksums, a.theta_g, a.slice_sum, a.slice_past, a.item_keys, a.item_counts, a.item_hits, a.k_stride);
 }
 
 }  // namespace nrtgpu

@@ -187,5 +187,5 @@ extern "C" int nrtgpu_search_multi_match_batch(nrtgpu_ctx* ctx, const nrtgpu_seg
   const PlanBytes extras[1] = {{records.data(), records.size() * sizeof(DGroupQuery)}};
   return final_score_run(ctx, hp, queries, n_queries, out, t0, extras, 1, [](hipStream_t st, const FinalScoreArgs& a, const void* const* d_extra) {
     launch_bm25_multi_match(st, a, (const DGroupQuery*)d_extra[0]);
-  });
+  }, nullptr, true);   // (counts the hits behind a cursor per slice: slice_relation_past_kernel)
 }

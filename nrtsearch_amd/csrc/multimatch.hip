@@ -47,7 +47,7 @@ __device__ __forceinline__ void multi_match_body(const DItem* __restrict__ items
                                                  const DTerm* __restrict__ terms, const DQuery* __restrict__ queries,
                                                  const float* __restrict__ caches, const DGroupQuery* __restrict__ gqueries,
                                                  const DFuncQuery* __restrict__ fqueries, const DFuncMasks* __restrict__ fmasks,
-                                                 unsigned long long* __restrict__ theta_g, uint32_t* __restrict__ slice_sum,
+                                                 unsigned long long* __restrict__ theta_g, uint32_t* __restrict__ slice_sum, uint32_t* __restrict__ slice_past,
                                                  uint64_t* __restrict__ item_keys, uint32_t* __restrict__ item_counts,
                                                  uint64_t* __restrict__ item_hits, uint32_t k_stride) {
   __shared__ MmSmem s;
@@ -166,7 +166,7 @@ __device__ __forceinline__ void multi_match_body(const DItem* __restrict__ items
       // ---- (3) final sweep: slot lane + 64 j is doc base + 64 j + lane, i.e. bit `lane` of word j of the sub-tile's mask words
       const NRT_GLOBAL uint64_t* const live_bits = (const NRT_GLOBAL uint64_t*)part->live_bits;
       const uint32_t word0 = base >> 6;
-      uint32_t wave_hits = 0;
+      uint32_t wave_hits = 0, wave_past = 0;
 #pragma unroll
       for (int j = 0; j < kFinalSlots; ++j) {
         const uint32_t i = lane + 64u * (uint32_t)j;
@@ -187,18 +187,18 @@ __device__ __forceinline__ void multi_match_body(const DItem* __restrict__ items
               matched |= (uint32_t)((mw >> lane) & 1ull) << fi;
             }
             // a doc the groups reject is no hit whatever the functions say; else the function score's own hit test decides
-            key = final_candidate_key(ok, gdoc0 + i, theta, after_key, wave_hits, [gq, fq, matched, &o](bool* hit) {
+            key = final_candidate_key(ok, gdoc0 + i, theta, after_key, wave_hits, wave_past, [gq, fq, matched, &o](bool* hit) {
               const float inner = multi_match_value(*gq, o, hit);
               return *hit ? function_score_value(*fq, matched, inner, hit) : inner;
             });
           } else {
-            key = final_candidate_key(ok, gdoc0 + i, theta, after_key, wave_hits, [gq, &o](bool* hit) { return multi_match_value(*gq, o, hit); });
+            key = final_candidate_key(ok, gdoc0 + i, theta, after_key, wave_hits, wave_past, [gq, &o](bool* hit) { return multi_match_value(*gq, o, hit); });
           }
         }
         acc[i] = key;
         n_cand += (uint32_t)__popcll(__ballot(key != 0ull));
       }
-      final_count_slice(s.t, part, lane, wave_hits);
+      final_count_slice(s.t, part, lane, wave_hits, wave_past);
     }
     if (lane == 0) s.t.wcount[par][wave] = n_cand;
     __syncthreads();
@@ -230,16 +230,16 @@ __device__ __forceinline__ void multi_match_body(const DItem* __restrict__ items
     }
   }
 
-  final_epilogue(s.t, cnt, k, q, tid, slice_sum, item_keys, item_counts, item_hits, k_stride);
+  final_epilogue(s.t, cnt, k, q, tid, slice_sum, item_keys, item_counts, item_hits, k_stride, slice_past);
 }
 
 __global__ __launch_bounds__(kMmThreads, kMmWaves / 4)
 void bm25_multi_match_kernel(const DItem* __restrict__ items, const DPart* __restrict__ parts, const DTerm* __restrict__ terms,
                              const DQuery* __restrict__ queries, const float* __restrict__ caches,
                              const DGroupQuery* __restrict__ gqueries, unsigned long long* __restrict__ theta_g,
-                             uint32_t* __restrict__ slice_sum, uint64_t* __restrict__ item_keys, uint32_t* __restrict__ item_counts,
+                             uint32_t* __restrict__ slice_sum, uint32_t* __restrict__ slice_past, uint64_t* __restrict__ item_keys, uint32_t* __restrict__ item_counts,
                              uint64_t* __restrict__ item_hits, uint32_t k_stride) {
-  multi_match_body<false>(items, parts, terms, queries, caches, gqueries, nullptr, nullptr, theta_g, slice_sum, item_keys, item_counts,
+  multi_match_body<false>(items, parts, terms, queries, caches, gqueries, nullptr, nullptr, theta_g, slice_sum, slice_past, item_keys, item_counts,
                           item_hits, k_stride);
 }
 
@@ -248,23 +248,23 @@ void bm25_multi_match_function_score_kernel(const DItem* __restrict__ items, con
                                             const DQuery* __restrict__ queries, const float* __restrict__ caches,
                                             const DGroupQuery* __restrict__ gqueries, const DFuncQuery* __restrict__ fqueries,
                                             const DFuncMasks* __restrict__ fmasks, unsigned long long* __restrict__ theta_g,
-                                            uint32_t* __restrict__ slice_sum, uint64_t* __restrict__ item_keys,
+                                            uint32_t* __restrict__ slice_sum, uint32_t* __restrict__ slice_past, uint64_t* __restrict__ item_keys,
                                             uint32_t* __restrict__ item_counts, uint64_t* __restrict__ item_hits, uint32_t k_stride) {
-  multi_match_body<true>(items, parts, terms, queries, caches, gqueries, fqueries, fmasks, theta_g, slice_sum, item_keys, item_counts,
+  multi_match_body<true>(items, parts, terms, queries, caches, gqueries, fqueries, fmasks, theta_g, slice_sum, slice_past, item_keys, item_counts,
                          item_hits, k_stride);
 }
 
 void launch_bm25_multi_match(hipStream_t stream, const FinalScoreArgs& a, const DGroupQuery* gqueries) {
   if (a.n_items == 0) return;
   hipLaunchKernelGGL(bm25_multi_match_kernel, dim3(a.n_items), dim3(kMmThreads), 0, stream, a.items, a.parts, a.terms, a.queries, a.caches,
-                     gqueries, a.theta_g, a.slice_sum, a.item_keys, a.item_counts, a.item_hits, a.k_stride);
+                     gqueries, a.theta_g, a.slice_sum, a.slice_past, a.item_keys, a.item_counts, a.item_hits, a.k_stride);
 }
 
 void launch_bm25_multi_match_function_score(hipStream_t stream, const FinalScoreArgs& a, const DGroupQuery* gqueries, const DFuncQuery* fqueries,
                                             const DFuncMasks* fmasks) {
   if (a.n_items == 0) return;
   hipLaunchKernelGGL(bm25_multi_match_function_score_kernel, dim3(a.n_items), dim3(kMmThreads), 0, stream, a.items, a.parts, a.terms, a.queries,
-                     a.caches, gqueries, fqueries, fmasks, a.theta_g, a.slice_sum, a.item_keys, a.item_counts, a.item_hits, a.k_stride);
+                     a.caches, gqueries, fqueries, fmasks, a.theta_g, a.slice_sum, a.slice_past, a.item_keys, a.item_counts, a.item_hits, a.k_stride);
 }
 
 }  // namespace nrtgpu

@@ -489,6 +489,7 @@ struct FinalScoreArgs {
   const float* caches;           // the queries' normInverse tables
   unsigned long long* theta_g;   // per query: the best FINAL key bound any of its items has published
   uint32_t* slice_sum;           // per (query, searcher slice): hits counted
+  uint32_t* slice_past;          // ... and, for the routes that count them (finalscore.cpp), those behind the query's cursor; else nullptr
   uint64_t* item_keys;           // per item k_stride keys ...
   uint32_t* item_counts;         // ... how many ...
   uint64_t* item_hits;           // ... and the hits counted there

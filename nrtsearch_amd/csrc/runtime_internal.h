@@ -118,6 +118,8 @@ void launch_term_cells(hipStream_t stream, const uint32_t* docids, const uint64_
                        const uint32_t* t_meta, const uint32_t* which, uint32_t n_which, uint32_t max_cells, uint32_t max_doc, void* look_base);
 void launch_expand_terms(hipStream_t stream, const DQExpand* qx, const DQTerm* qterms, const uint32_t* out_begin, uint32_t n_queries,
                          uint32_t n_leaves, DTerm* out);   // (qx: behind the batch's DExpandHead, plan.h)
+void launch_slice_relation_past(hipStream_t stream, const uint32_t* slice_sum, const uint32_t* slice_past, const DQuery* queries, uint32_t n_slices,
+                                uint64_t* out_hits, uint32_t n);
 void launch_slice_relation(hipStream_t stream, const uint32_t* slice_sum, const DQuery* queries, uint32_t n_slices, uint64_t* out_hits,
                            uint32_t n);
 void launch_patch_hits(hipStream_t stream, const uint64_t* lower, uint64_t* hits, uint32_t n);
@@ -1180,13 +1182,15 @@ typedef void (*FinalScoreLaunch)(hipStream_t, const FinalScoreArgs&, const void*
 // memset that zeroes the per-slice sums (their address reaches the scorer as FinalScoreArgs.own), and collect(), called behind the
 // wait and the unpacking, before the call is accounted: it copies what the route wants of them on the slot's stream.  What the
 // routes without one enqueue and copy is what it was.
+// counts_past: the route's kernel hands final_epilogue a slice_past (plan.h: FinalScoreArgs) -- the relation then asks of a query with
+// a cursor that one slice holds numHits hits BEHIND it, as that slice's collector would before it publishes anything.
 struct FinalScoreOwn {
   size_t work_bytes;
   int (*collect)(nrtgpu_ctx* ctx, Slot* slot, const char* d_own, void* user);
   void* user;
 };
 int final_score_run(nrtgpu_ctx* ctx, const HostPlan& hp, const nrtgpu_bm25_query* queries, int32_t n_queries, nrtgpu_topdocs* out, double t0,
-                    const PlanBytes* extras, int n_extras, FinalScoreLaunch launch, const FinalScoreOwn* own = nullptr);
+                    const PlanBytes* extras, int n_extras, FinalScoreLaunch launch, const FinalScoreOwn* own = nullptr, bool counts_past = false);
 
 // ---- what the routes lend each other (multimatch.cpp and funcscore.cpp define them; funcscore_multimatch.cpp uses both halves) ----
 // multimatch.cpp: the record the kernel and nrtgpu_multi_match_value read, from the caller's struct; refusals by the header's

@@ -10,7 +10,9 @@ inside their allocations), memset (offset, extent), event record, stream wait an
 tests/golden/text_host_launch_trace.txt line for line.  The golden file was recorded from the library as it was BEFORE search.cpp
 and finalscore.cpp shared their plan layout, merge staging, two-pass driver and result unpacking, so it pins that the shared code
 kept every blob size, the extent of the zeroing memset, the order of waits, records and copies, the number of copies back, and
-which of two faults of one bad call each entry names.
+which of two faults of one bad call each entry names.  (Since then re-recorded in the function-score and multi-match steps only, twelve
+lines: those kernels take one more pointer, the zeroing memset also covers the per-slice counts of hits behind a cursor, and the
+relation comes from slice_relation_past_kernel.)
 
 The paths of dist.cpp that call merge_lists_on_device and hybrid_tail_on_device need a communicator (nrtgpu_dist_init), which
 cannot be had without the RCCL stand-in and a second process: tests/test_dist_two_ranks_host.py runs them under the same mock."""
